@@ -10,25 +10,31 @@ while the newer ones render - what HipKernel::setFramesInFlight does for the ref
 The primitive ids stay on the device until picking asks (d2h_bitmap).
 
   python bench.py --gpus 1 --steps 200 --warmup 3
+  python bench.py --gpus 1 --steps 200 --warmup 3 --full             (everything below that is not the headline)
+  python bench.py --gpus 1 --steps 200 --warmup 3 --dump-outputs DIR (+ the last step's image as DIR/image.npy)
   python bench.py --gpus N ...                      (bare: starts its own N rank processes)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Timing: W warm-up steps, then the timed region - EXACTLY K steps between barrier + synchronisation on both sides, the
-last image on the host when it ends, no event or other instrument inside it - is run R >= 25 times back to back (as
-many as keep the GPU busy for 0.2 s).  `ms_per_step` and `value` are the MEDIAN region's; `config.step_ms_spread` gives
-the fastest and the slowest region, which bracket it by construction.  At N > 1 a region's time is the MAX over ranks
+Timing: set-up frames, W warm-up steps, then the timed region - EXACTLY K steps between barrier + synchronisation on
+both sides, the last image on the host when it ends, no event or other instrument inside it - run once; `ms_per_step`
+and `value` are its.  That, and --dump-outputs, is all a plain run does.  --full runs the region R >= 25 times back to
+back (as many as keep the GPU busy for 0.2 s): `ms_per_step` and `value` are then the MEDIAN region's and
+`config.step_ms_spread` gives the fastest and the slowest region, which bracket it by construction; every extra named
+below is --full's alone.  At N > 1 a region's time is the MAX over ranks
 of each rank's own time from the start barrier to its last delivered frame (the end barrier itself is the control
 plane's - gloo over TCP - and is reported, not charged).
 
 N > 1 (the launcher, the control plane, the communicator, the delivery routes and the sweep over them live in
 bench_dist.py): row strips re-cut by measured cost (solr_hip_balance_strips), gathered to rank 0 with RCCL called from
 the engine's C ABI on the stream that rendered the frame - `value` is always a combination that makes that RCCL call
-behind every frame, on a communicator of exactly --gpus ranks (exit code 5 otherwise); the reference's equal split is
-timed as a second segment, the assembled frame is compared with the frame rank 0 renders alone, per-rank times and the
-gather alone are reported, and which communicator mode ran (one for everything, or one per frame in flight).
+behind every frame, on a communicator of exactly --gpus ranks (exit code 5 otherwise).  A plain run times the strips
+route on one communicator (--delivery, SOLR_HIP_COMM_PER_FLIGHT choose others); with --full the communicator modes and
+delivery routes are swept first and the headline runs on the fastest, the reference's equal split is timed as a second
+segment, the assembled frame is compared with the frame rank 0 renders alone, and the gather alone is reported.
+Per-rank times and which communicator mode ran (one for everything, or one per frame in flight) are always reported.
 
 Rank 0 prints ONE JSON line.  `value` = (closest-hit walks + shadow walks of the whole
-frame) * steps / the median region's wall time / 1e6, summed over all ranks, max wall time over ranks.
+frame) * steps / the (median) region's wall time / 1e6, summed over all ranks, max wall time over ranks.
 `roofline` prices the renderer kernel against HBM bandwidth with the algorithmic bytes
 of DESIGN.md (51 B per pixel on a first pass + one read of the scene), timed with HIP events on the
 launch stream around launches issued one at a time AFTER the timed regions; `config.rates_mrays_per_s` holds, next to
@@ -58,6 +64,7 @@ SURVEY_FUSED_BYTES_PER_PIXEL = 67  # SURVEY.md 8(d) with k_default fused: + the 
 # MI355X_MICROARCH.md: 4 SIMD-32 per CU, a wave64 vector instruction issues over 2 cycles; one scalar unit per CU
 VALU_PEAK_WAVE_INSTS_PER_S = 256 * 4 * 2.4e9 / 2
 SALU_PEAK_WAVE_INSTS_PER_S = 256 * 2.4e9
+DUMP_BYTES = 48 << 20  # --dump-outputs: an image larger than this as float32 is written as a seeded sample of its pixels
 
 
 def parse():
@@ -108,6 +115,16 @@ def parse():
     ap.add_argument("--no-walk-bound", action="store_true",
                     help="skip the walk's own ceiling (roofline.walk_bound_mrays: a gigabyte of records for one 1080p frame)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the timed region repeated (>= 25 times, median and spread), "
+                         "the kernel's own time and the roofline, the reference's frame protocols, the walk's own ceiling, "
+                         "the delivered frame against the CPU oracle, the CPU baseline; N > 1: the equal strips, the mode "
+                         "sweep, the gather alone, the assembled frame against the one-GPU frame.  Without it a run sets "
+                         "up, warms up, times exactly --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one delivered (the RGB image on the host) as "
+                         "DIR/image.npy, float32 (above %d MiB: a fixed, seeded sample of its pixels, their indices in "
+                         "DIR/image_pixels.npy)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     if args.config == "cfg2":
         args.scene = "height_field"
@@ -260,7 +277,7 @@ def main():
     if args.delivery == "gathered":
         mode["collective"] = True       # (that route delivers what the gather assembled)
     if native:
-        if not cfg4 and not args.no_check:
+        if not cfg4 and not args.no_check and args.full:
             # the frame a rank renders ALONE, whole, before there is a communicator: what every assembled frame of the
             # job is compared with (config.mode_sweep).  Every rank renders it - the ranks run the same program, frame
             # for frame: the engine deals its buffer sets (and, with one communicator per frame in flight, its
@@ -441,17 +458,18 @@ def main():
             issued += t_issued - t0
         k.check(0, "timed frames")
         # the image the LAST timed step delivered, as the host received it (outside the regions; main() compares it
-        # with the oracle's frame: the timed frames are the right frames).  The ring's slot stays untouched until the
-        # next step is issued
-        snapshot = None
-        if rank == 0 and last_image[0] and not cfg4:
+        # with the oracle's frame: the timed frames are the right frames; --dump-outputs writes it).  The ring's slot
+        # stays untouched until the next step is issued
+        snapshot = delivered_image = None
+        if rank == 0 and last_image[0] and (not cfg4 or args.dump_outputs):
             import numpy as np
-            snapshot = np.ctypeslib.as_array((C.c_ubyte * (W * H * 3)).from_address(last_image[0])).reshape(H, W, 3).copy()
+            delivered_image = np.ctypeslib.as_array((C.c_ubyte * (W * H * 3)).from_address(last_image[0])).reshape(H, W, 3).copy()
+            snapshot = None if cfg4 else delivered_image
         # A region's time is the MAX over ranks of `own` (reduce_over_ranks): the moment the slowest rank's last frame
         # was delivered, counted from the start barrier.  The end barrier brackets the region but is not charged to it -
         # a gloo barrier of eight ranks is of the order of a 20-step region of an eight-GPU frame
         return {"regions": own, "with_end_barrier": out, "issued": issued / max(regions, 1), "strip": current_strip(),
-                "last_image": snapshot}
+                "last_image": snapshot, "delivered_image": delivered_image}
 
     def current_strip():
         a, b = C.c_int(), C.c_int()
@@ -460,7 +478,10 @@ def main():
 
     def region_count(steps):
         """at least 25 regions, and enough of them to keep the GPU busy for a fifth of a second: a 20-step region of
-        this workload is 6 ms, and neither a median of three nor a utilisation sampler sees that"""
+        this workload is 6 ms, and neither a median of three nor a utilisation sampler sees that.  Without --full: one
+        region, exactly --steps steps"""
+        if not args.full:
+            return 1
         if os.environ.get("SOLR_BENCH_REGIONS"):
             return max(1, int(os.environ["SOLR_BENCH_REGIONS"]))
         probe = timed(steps, 0, 1)["regions"][0]
@@ -506,7 +527,7 @@ def main():
         # equal strips share out rows, not work (profiles/r2/strip_balance_*.txt): the reference's equal split is
         # timed first, as the second figure; then the strips are re-cut by the cost the frames recorded, the
         # tile-cost feedback settles on the new strips, and the headline segment runs on them
-        if world > 1:
+        if world > 1 and args.full:
             arm("equal strips")
             second = timed(args.steps, args.warmup, max(regions // 3, 5))
         if hip.solr_hip_balance_strips() != 0:
@@ -528,7 +549,7 @@ def main():
     elif not mode["collective"]:
         combos = [(sweep_comms[0], "strips", False)]
     want_sweep = os.environ.get("SOLR_BENCH_SWEEP", "1" if world > 1 else "0") == "1"
-    if native and not cfg4 and len(combos) > 1 and want_sweep:
+    if native and not cfg4 and len(combos) > 1 and want_sweep and args.full:
         from types import SimpleNamespace
         loop = SimpleNamespace(step=step, drain=drain, sync=sync, barrier=barrier, timed=timed, tickets=tickets)
         mode_sweep = bench_dist.mode_sweep(R, loop, combos, steps=args.steps, warmup=args.warmup, regions=regions, alone=alone,
@@ -542,13 +563,21 @@ def main():
         rccl_ranks, comm_count = R.require_communicator()
     arm("the timed regions")
     main_run = timed(args.steps, args.warmup, regions)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        image = main_run["delivered_image"]
+        if pipe is not None and pipe.frame_no > 0:      # --torch-gather: the assembled frame stays on rank 0's device
+            image = pipe.image(pipe.frame_no - 1).cpu().numpy()
+        if image is None:
+            raise SystemExit("bench.py: --dump-outputs: the timed steps delivered no image to the host")
+        dumped = dump_outputs(args.dump_outputs, image)
     if native and mode["collective"] and world > 1 and R.agree(rank == 0 and delivered[0] == 0):
         raise SystemExit("bench.py rank %d: the timed regions delivered no frame to rank 0's host" % rank)
     short_ray_lists = int(hip.solr_hip_short_ray_lists())   # what the engine chose for the delivered frames
     t_issued_ms = main_run["issued"] / args.steps * 1e3
     strips = "balanced by cost" if balanced else "equal rows"
     arm("kernel time")
-    kernel_avg_ms, kernel_spread = kernel_segment()
+    kernel_avg_ms, kernel_spread = kernel_segment() if args.full else (0.0, None)
     main_run["kernel_avg_ms"] = kernel_avg_ms
     if second:
         second["kernel_avg_ms"] = kernel_avg_ms
@@ -560,7 +589,7 @@ def main():
     # `value`): one frame at a time - render, wait - and cudaRender + d2h_bitmap, the wall time SURVEY.md
     # section 8(d) defines the metric over (kernel + read-back of the RGB image and the primitive ids)
     rates = None
-    if not distributed:
+    if not distributed and args.full:
         import numpy as np
         hip.solr_hip_set_frames_in_flight(1)
         n_extra = max(8, min(args.steps, 64))
@@ -659,7 +688,7 @@ def main():
     # ---- the walk's own ceiling (SURVEY.md 8d's second yardstick; N = 1, untimed extra): the walks of one recorded
     # frame replayed with nothing but the node loop (include/solr_hip.h solr_hip_walk_bound)
     walk_bound = None
-    if not distributed and not cfg4 and not args.no_walk_bound:
+    if not distributed and not cfg4 and not args.no_walk_bound and args.full:
         arm("the walk's own ceiling")
         hip.solr_hip_set_frames_in_flight(1)
         for _ in range(24):                  # the launch order the timed frames had settles again on one buffer set
@@ -684,7 +713,7 @@ def main():
     check = None
     headline_collective = mode["collective"]      # (what the timed regions ran with; the extras below gather)
     mode["collective"] = True
-    if native:
+    if native and args.full:
         arm("the gather alone and the one-GPU check")
         import numpy as np
         for _ in range(8):
@@ -780,8 +809,8 @@ def main():
     # early-out test, which a first pass does not make)
     survey_bytes = int(rows_rank0 * W * (SURVEY_FUSED_BYTES_PER_PIXEL if not cfg4 else per_pixel)) + scene_bytes
     achieved_survey = survey_bytes / (kernel_avg_ms * 1e-3) / 1e9 if kernel_avg_ms > 0 else 0.0
-    traffic, traffic_source, traffic_commit = measured_traffic(args, world)
-    valu = measured_counters(args, world)
+    traffic, traffic_source, traffic_commit = measured_traffic(args, world) if args.full else (None, None, None)
+    valu = measured_counters(args, world) if args.full else None
     label = {"cornell": "Cornell", "height_field": "triangle mesh", "molecule": "molecule"}.get(args.scene, args.scene)
     metric = "Mrays/s @%dx%d, %d-bounce %s" % (W, H, si.nbRayIterations, label)
     if cfg4:
@@ -847,20 +876,24 @@ def main():
                               if native else "torch.distributed gather (RCCL)"),
                    "strips": strips,
                    "parallelism": "tile%d" % world},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic, "traffic_source": traffic_source,
-                     "traffic_taken_at_commit": traffic_commit,
-                     "traffic_note": "read from a committed rocprofv3 --pmc profile of this same command (separate FETCH_SIZE / "
-                                     "WRITE_SIZE passes, corrected by the factors measured on known byte counts in the "
-                                     "renderer's own access patterns: profiles/r6/fetch_calibration.txt), not measured by "
-                                     "this run (a process cannot profile itself); null when the workload differs from "
-                                     "the profiled one",
-                     "kernel": "k_standardRenderer", "kernel_ms": round(kernel_avg_ms, 5), "kernel_ms_basis": kernel_basis,
-                     "kernel_ms_spread": kernel_spread,
-                     "algorithmic_bytes": algo_bytes, "algorithmic_bytes_per_pixel": round(per_pixel, 2),
-                     "frac_with_survey_8d_bytes": round(achieved_survey / HBM_PEAK_GBPS, 6),
-                     "survey_8d_bytes_per_pixel": SURVEY_FUSED_BYTES_PER_PIXEL if not cfg4 else round(per_pixel, 2)},
     }
+    if args.full:
+        # the renderer priced against HBM bandwidth: its own time (kernel_segment) and the algorithmic bytes
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                            "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic, "traffic_source": traffic_source,
+                            "traffic_taken_at_commit": traffic_commit,
+                            "traffic_note": "read from a committed rocprofv3 --pmc profile of this same command (separate FETCH_SIZE / "
+                                            "WRITE_SIZE passes, corrected by the factors measured on known byte counts in the "
+                                            "renderer's own access patterns: profiles/r6/fetch_calibration.txt), not measured by "
+                                            "this run (a process cannot profile itself); null when the workload differs from "
+                                            "the profiled one",
+                            "kernel": "k_standardRenderer", "kernel_ms": round(kernel_avg_ms, 5), "kernel_ms_basis": kernel_basis,
+                            "kernel_ms_spread": kernel_spread,
+                            "algorithmic_bytes": algo_bytes, "algorithmic_bytes_per_pixel": round(per_pixel, 2),
+                            "frac_with_survey_8d_bytes": round(achieved_survey / HBM_PEAK_GBPS, 6),
+                            "survey_8d_bytes_per_pixel": SURVEY_FUSED_BYTES_PER_PIXEL if not cfg4 else round(per_pixel, 2)}
+    if dumped:
+        out["config"]["outputs_dumped"] = dumped
     if distributed:
         slowest = max(per_rank, key=lambda r: r["ms_per_step_until_own_frames_delivered"])
         out["config"].update({
@@ -942,7 +975,7 @@ def main():
     # the frame the CPU oracle renders of the same scene, and the engine's ray census against the oracle's own count
     # ("counted by an instrumented build of our CPU restatement")
     rc = 0
-    if not args.no_check and pipe is None:
+    if args.full and not args.no_check and pipe is None:
         image, first_pass_rays = main_run.get("last_image"), rays_total
         if cfg4 and not distributed:
             # a step is a pass and the last delivered image is pass 73's: one pass is checked - pass 0, rendered and
@@ -968,7 +1001,7 @@ def main():
                 print("bench.py: the delivered frame or the ray census is NOT the oracle's: %s" % json.dumps(proof),
                       file=sys.stderr, flush=True)
                 rc = 4
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(flat, si, ppi, eye, direction, angles, args.cpu_seconds)
     if distributed:
         # RCCL writes its version banner to the C library's stdout buffer when the communicator comes up; on a
@@ -979,6 +1012,27 @@ def main():
     print(json.dumps(out), flush=True)
     if rc:
         sys.exit(rc)     # the line is printed (what was measured, and that it was not the right frame); the job failed
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: the RGB8 image the last timed step delivered to the host, as DIR/image.npy (H, W, 3) float32.  An
+    image above DUMP_BYTES as float32 is written as a sample instead: the same pixels every run (seed 0), sorted,
+    image.npy (n, 3) and their row-major indices in image_pixels.npy (n,) float64.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    image = np.asarray(image)
+    h, w, c = image.shape
+    out = {}
+    if h * w * c * 4 <= DUMP_BYTES:
+        out["image"] = image.astype(np.float32)
+    else:
+        n = DUMP_BYTES // (4 * c + 8)
+        pixels = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+        out["image"] = image.reshape(h * w, c)[pixels].astype(np.float32)
+        out["image_pixels"] = pixels.astype(np.float64)
+    for name, array in out.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
+    return {name: list(array.shape) for name, array in out.items()}
 
 
 MAX_MARKED_PIXELS = 8    # tests/test_baseline_sizes.py MAX_EXCEPTIONS: pixels of a frame one RGB8 step off, each behind a mis-rounded powf

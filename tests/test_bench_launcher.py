@@ -76,7 +76,7 @@ def _rehearse(extra, timeout, **more_env):
         env.update(SOLR_BENCH_SHARE_GPU="1", SOLR_HIP_RCCL_LIBRARY=build_loopback(), SOLR_LOOPBACK_DIR=directory,
                    SOLR_LOOPBACK_TIMEOUT="60", SOLR_BENCH_TIMEOUT=str(timeout), SOLR_BENCH_REGIONS="3")
         env.update(more_env)     # (three timed regions: a rehearsal's numbers mean nothing, and its transport is files)
-        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu-baseline"] + extra,
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--no-cpu-baseline"] + extra,
                              env=env, capture_output=True, text=True, timeout=timeout + 60)
         assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
         return json.loads(res.stdout.strip().splitlines()[-1])
@@ -188,7 +188,7 @@ def test_the_whole_job_over_real_rccl_where_the_box_has_the_gpus(solr, world):
                                                             "SOLR_HIP_RCCL_LIBRARY")}
     env.update(SOLR_BENCH_REGIONS="5", MASTER_PORT=str(29650 + world))
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
     line = json.loads(res.stdout.strip().splitlines()[-1])
     cfg = line["config"]
@@ -204,8 +204,9 @@ def test_one_rank_through_the_distributed_path_over_rccl(solr):
     """SOLR_BENCH_FORCE_DIST=1: the N > 1 path with a communicator of one rank of the real RCCL"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(SOLR_BENCH_FORCE_DIST="1", MASTER_PORT="29613")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--no-cpu-baseline",
-                          "--width", "640", "--height", "360"], env=env, capture_output=True, text=True, timeout=600)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--full",
+                          "--no-cpu-baseline", "--width", "640", "--height", "360"], env=env, capture_output=True, text=True,
+                         timeout=600)
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
     line = json.loads(res.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["config"]["rccl_ranks"] == 1 and line["config"]["gathered_equals_single_gpu"] is True
@@ -216,7 +217,7 @@ def test_one_rank_through_the_distributed_path_over_rccl(solr):
 def test_the_drivers_own_command_line_for_two_ranks(solr):
     """`python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port P bench.py
     --gpus 2 --steps K --warmup W` - how the driver starts an N > 1 run - rehearsed on the box's one GPU (every rank on
-    GPU 0, the stand-in transport): one JSON line on stdout, last, from rank 0"""
+    GPU 0, the stand-in transport): one JSON line on stdout, last, from rank 0 (--full: with the one-GPU check)"""
     from test_multi_rank_gpu import build_loopback
     directory = tempfile.mkdtemp(prefix="solr_bench_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     try:
@@ -225,7 +226,7 @@ def test_the_drivers_own_command_line_for_two_ranks(solr):
                    SOLR_LOOPBACK_TIMEOUT="60", SOLR_BENCH_REGIONS="3", HSA_ENABLE_IPC_MODE_LEGACY="0")
         res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                               "--master-addr", "127.0.0.1", "--master-port", "29641", os.path.join(ROOT, "bench.py"),
-                              "--gpus", "2", "--steps", "10", "--warmup", "2", "--width", "640", "--height", "360"],
+                              "--gpus", "2", "--steps", "10", "--warmup", "2", "--width", "640", "--height", "360", "--full"],
                              env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
         lines = [l for l in res.stdout.strip().splitlines() if l.strip()]
@@ -239,11 +240,11 @@ def test_the_drivers_own_command_line_for_two_ranks(solr):
 
 @pytest.mark.gpu
 def test_the_one_gpu_line_keeps_the_contract(solr):
-    """`python bench.py --gpus 1 --steps K --warmup W`: one JSON line, last on stdout, with the keys the driver reads -
-    and the headline inside its own error bar"""
+    """`python bench.py --gpus 1 --steps K --warmup W --full`: one JSON line, last on stdout, with the keys the driver
+    reads and everything --full adds - and the headline inside its own error bar"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--cpu-seconds", "1.5"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--cpu-seconds", "1.5"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
     line = json.loads(res.stdout.strip().splitlines()[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -287,9 +288,91 @@ def test_a_job_that_delivers_a_wrong_frame_fails(solr):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(SOLR_BENCH_TAMPER="1", SOLR_BENCH_REGIONS="3")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-walk-bound", "--width", "640", "--height", "360"], env=env,
+                          "--full", "--no-cpu-baseline", "--no-walk-bound", "--width", "640", "--height", "360"], env=env,
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 4, (res.returncode, res.stderr[-2000:])
     line = json.loads(res.stdout.strip().splitlines()[-1])
     assert line["config"]["delivered_frame_equals_oracle"] is False and line["config"]["rays_equal_oracle_count"] is True
     assert line["config"]["frame_check"]["pixels_differing"] == 16
+
+
+@pytest.mark.gpu
+def test_a_plain_one_gpu_run_times_exactly_its_steps_and_nothing_else(solr):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline keys, ONE region of exactly K steps,
+    and none of --full's extras"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SOLR_BENCH_REGIONS")}
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                         env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
+    line = json.loads(res.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in line, key
+    assert line["metric"].startswith("Mrays/s @1920x1080, 3-bounce Cornell") and line["unit"] == "Mrays/s"
+    assert (line["n_gpus"], line["steps"], line["warmup"]) == (1, 20, 5) and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["protocol"] == "delivered_pipelined"
+    assert line["regions"] == 1 and line["config"]["step_ms_spread"]["regions"] == 1
+    assert line["ms_per_step"] > 0 and line["config"]["step_ms_spread"]["timed_seconds_in_all"] == pytest.approx(
+        line["ms_per_step"] * 20 / 1e3, rel=1e-2)
+    assert line["value"] == pytest.approx(line["config"]["rays_per_frame"] / (line["ms_per_step"] * 1e-3) / 1e6, rel=2e-3)
+    for extra in ("roofline", "cpu_baseline"):
+        assert extra not in line, extra
+    for extra in ("rates_mrays_per_s", "delivered_frame_equals_oracle", "outputs_dumped"):
+        assert extra not in line["config"], extra
+
+
+@pytest.mark.gpu
+def test_the_dumped_outputs_are_the_frame_the_last_step_delivered(solr, oracle):
+    """--dump-outputs DIR: the image the last timed step delivered, as DIR/image.npy float32 - the oracle's frame of the
+    same scene (bench.prove_frames' bar), so the same arguments give the same outputs on any build that is right"""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    directory = tempfile.mkdtemp(prefix="solr_dump_")
+    try:
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2",
+                              "--width", "640", "--height", "360", "--dump-outputs", directory], env=env,
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert line["config"]["outputs_dumped"] == {"image": [360, 640, 3]}
+        assert sorted(os.listdir(directory)) == ["image.npy"]
+        image = np.load(os.path.join(directory, "image.npy"))
+    finally:
+        shutil.rmtree(directory, ignore_errors=True)
+    assert image.dtype == np.float32 and image.shape == (360, 640, 3)
+    assert np.array_equal(image, np.round(image)) and image.min() >= 0 and image.max() <= 255 and image.max() > 0
+    k = solr.Kernel(engine="host-only", deterministic_seed=12345)
+    solr.scenes.cornell(k, width=640, height=360, iterations=3)
+    flat = k.flat_scene()
+    si, ppi, eye, direction, angles = k.frame_parameters()
+    k.finalize()
+    _, _, _, counts, status = oracle.render(flat, si, ppi, eye, direction, angles)
+    assert status == 0
+    proof = bench.prove_frames(flat, si, ppi, eye, direction, angles, image.astype(np.uint8), int(counts[0]) + int(counts[1]))
+    assert proof["delivered_frame_equals_oracle"] is True, proof
+
+
+def test_dumped_outputs_of_a_large_frame_are_a_fixed_sample(tmp_path):
+    """(CPU) bench.dump_outputs: an image above the dump's budget is written as the same seeded sample of its pixels every
+    time, with their indices, all of it float and within 64 MB"""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    image = (np.arange(2160 * 3840 * 3, dtype=np.uint32) % 251).astype(np.uint8).reshape(2160, 3840, 3)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), image)
+    assert bench.dump_outputs(str(tmp_path / "b"), image) == shapes and set(shapes) == {"image", "image_pixels"}
+    total = 0
+    for name in shapes:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b) and list(a.shape) == shapes[name]
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert total <= 64 << 20
+    pixels = np.load(tmp_path / "a" / "image_pixels.npy").astype(np.int64)
+    assert np.all(np.diff(pixels) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), image.reshape(-1, 3)[pixels].astype(np.float32))
+    small = image[:360, :640]
+    assert bench.dump_outputs(str(tmp_path / "c"), small) == {"image": [360, 640, 3]}
+    assert np.array_equal(np.load(tmp_path / "c" / "image.npy"), small.astype(np.float32))

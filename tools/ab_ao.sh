@@ -4,7 +4,7 @@ export TMPDIR=/tmp; R=$PWD; LIB=sol-r_amd/csrc/libsolr_hip.so; cp $LIB /tmp/keep
 for round in 1 2; do
 for l in "$@"; do
   cp $l $LIB
-  SOLR_BENCH_REGIONS=5 python bench.py --config cfg4 --steps 74 --warmup 12 --no-cpu-baseline --no-check 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$(basename $l)', 'ms per delivered pass', d['ms_per_step'], 'renderer', d['roofline']['kernel_ms'])"
+  SOLR_BENCH_REGIONS=5 python bench.py --config cfg4 --steps 74 --warmup 12 --full --no-cpu-baseline --no-check 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$(basename $l)', 'ms per delivered pass', d['ms_per_step'], 'renderer', d['roofline']['kernel_ms'])"
   rm -rf $R/gpurun_out/ao_ab; cd /tmp
   SOLR_BENCH_REGIONS=3 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/ao_ab -o t -- python3 $R/bench.py --config cfg4 --steps 74 --warmup 2 --no-cpu-baseline --no-check > /dev/null 2>&1
   cd $R

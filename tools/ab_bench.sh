@@ -7,7 +7,7 @@ SCENES=$1; shift
 LIB=sol-r_amd/csrc/libsolr_hip.so
 cp $LIB /tmp/libsolr_hip_keep.so
 export SOLR_BENCH_REGIONS=9
-one() { python bench.py --no-cpu-baseline --no-walk-bound --scene $1 --steps 200 --warmup 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-28s %-12s delivered %.4f ms  kernel %.4f ms  one-at-a-time %s' % ('$2', '$1', d['ms_per_step'], d['roofline']['kernel_ms'], d['config']['rates_note']['one_frame_at_a_time'].split(':')[-1].strip()))"; }
+one() { python bench.py --full --no-cpu-baseline --no-walk-bound --scene $1 --steps 200 --warmup 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-28s %-12s delivered %.4f ms  kernel %.4f ms  one-at-a-time %s' % ('$2', '$1', d['ms_per_step'], d['roofline']['kernel_ms'], d['config']['rates_note']['one_frame_at_a_time'].split(':')[-1].strip()))"; }
 for s in $SCENES; do
   for round in 1 2 3; do
     for l in "$@"; do

@@ -30,7 +30,7 @@ for scene in SCENES:
     if out:
         hdr = ("# commit %s\n" % commit +
                "# rocprofv3 --pmc, separate passes (two sets of SQ counters; FETCH_SIZE; WRITE_SIZE) of\n"
-               "#   SOLR_BENCH_REGIONS=3 python3 bench.py %s --warmup 12 --no-cpu-baseline --no-walk-bound --frames-in-flight 1\n"
+               "#   SOLR_BENCH_REGIONS=3 python3 bench.py %s --warmup 12 --full --no-cpu-baseline --no-walk-bound --frames-in-flight 1\n"
                "# per launch of the renderer kernel.  FETCH_SIZE / WRITE_SIZE are in KB (L2 <-> fabric requests x 64 B;\n"
                "# MI355X_MICROARCH.md: FETCH_SIZE under-reports wide streaming reads by 2x on gfx950, WRITE_SIZE is exact).\n"
                % ("--config cfg4 --steps 74" if scene == "cfg4" else "--scene %s --steps 24" % scene))

@@ -8,7 +8,7 @@ ROOT=$PWD; OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 export SOLR_BENCH_REGIONS=1
 cd /tmp
 for SCENE in $SCENES; do
-  CMD="python3 $ROOT/bench.py --scene $SCENE --steps 8 --warmup 4 --no-cpu-baseline --frames-in-flight 1"
+  CMD="python3 $ROOT/bench.py --scene $SCENE --steps 8 --warmup 4 --full --no-cpu-baseline --frames-in-flight 1"
   P=0
   for SET in \
     "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES" \

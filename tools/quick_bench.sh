@@ -3,7 +3,7 @@
 # usage: tools/quick_bench.sh [label] ; extra environment (SOLR_HIP_*) is passed through
 label=${1:-now}
 for scene in cornell height_field molecule; do
-  python bench.py --no-cpu-baseline --scene $scene --steps 200 --warmup 40 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --scene $scene --steps 200 --warmup 40 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['config']['rates_note']

@@ -3,7 +3,7 @@
 # (136 rows) - what a rank of an eight-GPU job does per step - three times: ms per delivered frame of every combination.
 # The send-to-self of the one-rank communicator stands for the gather's cost on the sending side.
 for round in 1 2 3; do
-  SOLR_BENCH_FORCE_DIST=1 SOLR_BENCH_STRIP_SETTINGS=1 SOLR_BENCH_SWEEP=1 SOLR_BENCH_REGIONS=9 python bench.py --height 136 --steps 200 --warmup 40 \
+  SOLR_BENCH_FORCE_DIST=1 SOLR_BENCH_STRIP_SETTINGS=1 SOLR_BENCH_SWEEP=1 SOLR_BENCH_REGIONS=9 python bench.py --height 136 --steps 200 --warmup 40 --full \
       --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); s = d['config']['mode_sweep']
