@@ -118,13 +118,55 @@ struct SharedRing
  * frame's own stream: 2.9 us of every Cornell frame at sixteen, which it was until round 6; 64: delivered frames 0.2442 ->
  * 0.2419 ms, one at a time 0.2734 -> 0.2712.  A decision that changes - cost order on / off, a streamed frame's bands - is
  * still acted on at once.  On a stream of its own the sort cost the delivered frames a third: one stream more, and the
- * runtime's four hardware queues are dealt out differently; on the copy stream it delays the images).
- * SOLR_HIP_SORT_PERIOD (environment): experiments. */
-inline int sortPeriod()
+ * runtime's four hardware queues are dealt out differently; on the copy stream it delays the images). */
+const int SORT_PERIOD = 64;
+
+/* The cost-ordered launch (renderer.h FrameArgs::tileCost / tileOrder; k_orderTiles in solr_post.hip): what the tiles of
+ * the frames cost, the statistics the host decides by, and the launch order made from them.  renderImpl's scheduling
+ * stage (solr_launch.hip) is the only code that advances it. */
+struct TileSchedule
 {
-    static const int period = getenv("SOLR_HIP_SORT_PERIOD") ? std::max(2, atoi(getenv("SOLR_HIP_SORT_PERIOD"))) : 64;
-    return period;
-}
+    int mode = 1;                 /* 0 off, 1 automatic (default), 2 always (solr_hip_set_tile_scheduling) */
+    DeviceBuffer cost, costSnapshot;
+    DeviceBuffer order[2];        /* the launch order; order[orderBuffer] holds the valid one */
+    int orderBuffer = 0;
+    hipEvent_t orderEvent = nullptr;  /* completion of the last tile sort */
+    bool orderWait[MAX_FLIGHTS] = {}; /* that stream has not yet waited for it */
+    unsigned *hostStats = nullptr;    /* mapped host memory, 8 words */
+    unsigned *hostStatsDev = nullptr; /* its device address */
+    long key[6] = {0, 0, 0, 0, 0, 0}; /* the frame geometry the recorded costs belong to */
+    int frames = 0;                   /* frames rendered with that geometry */
+    bool reorder = false;             /* current decision of the automatic mode */
+    bool orderValid = false;          /* the order is one for the current geometry */
+    BandCuts orderCuts = {};          /* ... band after band (ImageStreaming); bands = 0: by cost alone */
+    /* the decision and the order forgotten: the next frames measure again (buffers, and an order a frame in flight reads,
+     * stay as they are) */
+    void reset()
+    {
+        frames = 0;
+        reorder = false;
+        orderValid = false;
+    }
+    void release(); /* everything given back, the mode kept (solr_launch.hip) */
+};
+
+/* solr_hip_set_variant (include/solr_hip.h): the A/B switches, by the numbers the C ABI takes.  Every one renders the same
+ * frame. */
+enum Variant
+{
+    VARIANT_AUTOMATIC = 0,
+    VARIANT_EXACT_LIST = 3,      /* walk the node list exactly as uploaded */
+    VARIANT_ALL_FEATURES = 4,    /* always the all-features kernel */
+    VARIANT_NO_GROUPING = 5,     /* no grouping nodes (at the next h2d_scene) */
+    VARIANT_NO_ORDER_FREE = 6,   /* no order-free lists */
+    VARIANT_STACK_IN_LDS = 7,    /* the whole colour stack in LDS however deep a frame may bounce */
+    VARIANT_REFERENCE_LEAVES = 8, /* no thin copies of the leaves that hold plain axis planes */
+    VARIANT_AO_FIXED_STRIDE = 9, /* k_ambientOcclusion with a fixed stride of tiles per workgroup */
+    VARIANT_NAN_DEEP_STACK = 10, /* NaNs in the colour-stack slots an F_STACK frame keeps in HBM, before every launch */
+    VARIANT_UNSORTED_LISTS = 12, /* no walk takes the copies of the order-free lists with sorted bounds */
+    VARIANT_NO_BAND_WORDS = 13,  /* a streamed frame's waves write no band's word */
+    VARIANT_ZERO_STREAM_COUNTERS = 14, /* the tile counters of streamed frames zeroed every third frame */
+};
 
 struct Engine
 {
@@ -190,7 +232,7 @@ struct Engine
     long nbRandoms = 0;
 
     /* per-pixel buffers of the strip */
-    DeviceBuffer pp, ids, bitmap, counters, tileClock, tileCost, tileCostSnapshot, tileOrder;
+    DeviceBuffer pp, ids, bitmap, counters, tileClock;
     /* ambient occlusion across strips: the depths of the neighbours' rows next to this rank's strip */
     DeviceBuffer haloAbove[MAX_FLIGHTS], haloBelow[MAX_FLIGHTS], haloSendTop[MAX_FLIGHTS], haloSendBottom[MAX_FLIGHTS]; /* per frame in flight */
     DeviceBuffer haloGivenAbove, haloGivenBelow; /* solr_hip_set_depth_halo */
@@ -203,21 +245,10 @@ struct Engine
     int flights = 1;
     hipStream_t extraStream[MAX_FLIGHTS - 1] = {}; /* streams of sets 1 .. MAX_FLIGHTS - 1 */
     bool callerStreams = false; /* the streams belong to the caller (solr_hip_set_flight_streams) */
-    DeviceBuffer ppX[MAX_FLIGHTS - 1], idsX[MAX_FLIGHTS - 1], bitmapX[MAX_FLIGHTS - 1], tileOrder2;
+    DeviceBuffer ppX[MAX_FLIGHTS - 1], idsX[MAX_FLIGHTS - 1], bitmapX[MAX_FLIGHTS - 1];
     int current = 0;           /* set / stream of the last render */
     unsigned frameSerial = 0;
-    hipEvent_t orderEvent = nullptr; /* completion of the last tile sort */
-    bool orderWait[MAX_FLIGHTS] = {}; /* that stream has not yet waited for it */
-    int orderBuffer = 0;       /* which of tileOrder / tileOrder2 holds the valid order */
-    /* cost-ordered launch: 0 off, 1 automatic (default), 2 always */
-    int tileScheduling = 1;
-    unsigned *hostStats = nullptr;    /* mapped host memory, 8 words */
-    unsigned *hostStatsDev = nullptr; /* its device address */
-    long costKey[6] = {0, 0, 0, 0, 0, 0}; /* the frame geometry the recorded costs belong to */
-    int costFrames = 0;               /* frames rendered with that geometry */
-    bool reorder = false;             /* current decision of the automatic mode */
-    bool orderValid = false;          /* tileOrder holds an order for the current geometry */
-    BandCuts orderCuts = {};          /* ... band after band (ImageStreaming); bands = 0: by cost alone */
+    TileSchedule sched;
     unsigned lastSerial = 0;
     bool tileClocks = false; /* diagnostics, solr_hip_enable_tile_clocks */
     int nbTilesTimed = 0;
@@ -308,8 +339,8 @@ struct Engine
     bool deviceAhead = false;           /* the arena has moved on from the host images */
     int nbDeviceRotations = 0;
 
-    int variant = 0;
-    bool grouping = true; /* groupSiblings(); variant 5 turns it off for A/B measurements */
+    int variant = VARIANT_AUTOMATIC; /* enum Variant */
+    bool grouping = true; /* groupSiblings(); VARIANT_NO_GROUPING turns it off for A/B measurements */
 
     /* the walk's own ceiling (solr_hip_walk_bound): the next frame records its walks; how that frame was launched */
     DeviceBuffer walkRecords, walkVisits;
@@ -317,7 +348,7 @@ struct Engine
     bool recorded = false;
     unsigned recordGrid = 0;
     size_t recordLds = 0;
-    int recordVariant = -1; /* row of renderImpl's table */
+    int recordVariant = -1; /* row of solrrows::ROWS (renderer.h) */
     bool recordDeep = false;
     SceneArgs recordScene;
 };
@@ -497,8 +528,8 @@ void refreshExactList();
 void dropFreeStage(bool originToo);
 bool orderFreeListsUsable();
 bool shortRayListsChoice();
-SceneArgs makeScene(bool exactNodes);
-int tightListsFor(const SceneArgs &S, const SceneInfo &sceneInfo, bool exactNodes);
+SceneArgs prepareScene(const SceneInfo &sceneInfo, bool exactNodes);
+bool deepNodeList(const SceneArgs &S);
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */
 void allocateFrame();
 int neededFeatures(const SceneInfo &sceneInfo, bool full);

@@ -1,7 +1,7 @@
 /*
  * renderer.h - what the host side of the engine (solr_launch.hip) and the translation units that hold the renderer's
- * instantiations (the files under csrc/rows) share: the frame's arguments, the kernel's signature, and one look-up per row of
- * renderImpl's table.  The kernel template itself is renderer_kernel.h, included by the row files only - so that an
+ * instantiations (the files under csrc/rows) share: the frame's arguments, the kernel's signature, the renderer's table of
+ * rows and one look-up per row file.  The kernel template itself is renderer_kernel.h, included by the row files only - so that an
  * experiment on one instantiation rebuilds one object (make -j: eight objects side by side instead of one 70-second
  * translation unit).  gfx950 only.
  */
@@ -123,11 +123,44 @@ typedef void (*WalkBoundFn)(const SceneArgs, const char *, unsigned *, unsigned 
 
 namespace solrrows
 {
+/* The renderer's table, smallest row first: the feature masks of the instantiations csrc/rows holds.  A frame takes the
+ * first row that covers what its scene needs (renderImpl).  Rows with bothLoops exist with the two-bank and the three-bank
+ * walk loop (rt_device.h advanceTidy), the others with the three-bank loop only.  The first LEAN_ROWS rows are the lean
+ * ones: they also have the instantiations that record a frame's walks and replay them (solr_hip_walk_bound). */
+struct Row
+{
+    int features;
+    bool bothLoops;
+};
+constexpr Row ROWS[] = {
+    {F_SPHERE | F_PLANE, true},
+    {F_SPHERE | F_TRI, true},
+    {F_SPHERE | F_CYL, true},
+    {F_SPHERE | F_PLANE | F_TRI | F_CYL, false},
+    /* textured scenes of the usual primitives (OBJ meshes with their MTL images; a textured room): the texture tier
+     * without the procedural spheres and the ellipsoids */
+    {F_SPHERE | F_TRI | F_TEX, true},
+    {F_SPHERE | F_PLANE | F_TRI | F_CYL | F_TEX, false},
+    /* the special cameras, global illumination and the box-debug view over the usual untextured primitives (the
+     * texture tier is what costs the registers: profiles/r3/generic_kernels.txt) */
+    {F_SPHERE | F_PLANE | F_TRI | F_CYL | F_FULL, false},
+    {F_ALL & ~F_FULL, false},
+    {F_ALL, false},
+};
+constexpr int NB_ROWS = (int)(sizeof(ROWS) / sizeof(ROWS[0]));
+constexpr int LEAN_ROWS = 4;
+/* the instantiation of row `row` for a scene: F_DEEP (the three-bank node loop) for a deep node list, or where the row has
+ * no other loop */
+constexpr int rowMask(int row, bool deepList)
+{
+    return ROWS[row].features | ((deepList || !ROWS[row].bothLoops) ? F_DEEP : 0);
+}
+
 /* k_standardRenderer<count, features, volume>, or null when no row file instantiates it.  count: 0 a frame, 1 the ray
- * census, 2 a frame that records its walks (the four lean rows only).  features: enum Feature of rt_device.h, with
+ * census, 2 a frame that records its walks (the LEAN_ROWS rows only).  features: enum Feature of rt_device.h, with
  * F_DEEP where the three-bank node loop is wanted. */
 RendererFn renderer(int count, int features, bool volume);
-/* k_walkBound<features> of lean row `row` of renderImpl's table (0 ... 3), or null */
+/* k_walkBound<features> of lean row `row` of ROWS (0 ... LEAN_ROWS - 1), or null */
 WalkBoundFn walkBound(int row, int features);
 /* one look-up per row file (each returns null for what it does not hold) */
 RendererFn spherePlane(int count, int features);

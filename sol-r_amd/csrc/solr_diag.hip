@@ -35,11 +35,10 @@ using namespace solrdev;
 
 using namespace solreng;
 
-/* For csrc/solr_probes.hip (the test-only entry points of include/solr_hip_probes.h): the resident scene exactly as
- * renderImpl hands it to the renderer - pending uploads flushed, the order-free lists built when they are due - the
- * features a frame with this SceneInfo needs, whether the renderer would take the three-bank node loop, and the
- * engine's stream.  exactNodes: the reference's own node list instead of the walk-order list.  Returns 0, or -1 with
- * the engine's error set. */
+/* For csrc/solr_probes.hip (the test-only entry points of include/solr_hip_probes.h): the resident scene as renderImpl
+ * hands it to the renderer (prepareScene), the features a frame with this SceneInfo needs, whether the renderer would take
+ * the three-bank node loop, and the engine's stream.  exactNodes: the reference's own node list instead of the walk-order
+ * list.  Returns 0, or -1 with the engine's error set. */
 namespace solrprobe
 {
 int residentScene(const SceneInfo &sceneInfo, bool exactNodes, SceneArgs *S, int *features, int *deepList, hipStream_t *stream)
@@ -52,16 +51,11 @@ int residentScene(const SceneInfo &sceneInfo, bool exactNodes, SceneArgs *S, int
     if (!ok())
         return -1;
     checkTextureTables();
-    maybeBuildOrderFreeLists();
-    flushGeometry();
-    if (exactNodes)
-        refreshExactList();
+    *S = prepareScene(sceneInfo, exactNodes);
     if (!ok())
         return -1;
-    *S = makeScene(exactNodes);
-    S->tightLists = tightListsFor(*S, sceneInfo, exactNodes);
     *features = neededFeatures(sceneInfo, false);
-    *deepList = S->nbBoxes > 1024;
+    *deepList = deepNodeList(*S);
     *stream = flightStream(0);
     return 0;
 }
@@ -153,13 +147,12 @@ static int recordFrame(const SceneInfo *sceneInfo, const vec4i *objects, const P
 static int replayRecords(unsigned grid, size_t ldsBytes, int repeats, double ms[3], unsigned long long stats[4], bool lists)
 {
     typedef WalkBoundFn BoundFn;
-    static const int leanRows[4] = {F_SPHERE | F_PLANE, F_SPHERE | F_TRI, F_SPHERE | F_CYL, F_SPHERE | F_PLANE | F_TRI | F_CYL};
-    ARGCHECK(g.recordVariant >= 0 && g.recordVariant < 4 && g.walkRecords.ptr && grid > 0 &&
+    ARGCHECK(g.recordVariant >= 0 && g.recordVariant < solrrows::LEAN_ROWS && g.walkRecords.ptr && grid > 0 &&
                  (size_t)grid * SOLR_WALK_SLOT_BYTES <= g.walkRecords.bytes,
              "solr_hip_walk_replay: no recorded frame, or more workgroups than its buffer holds");
     if (!ok())
         return -1;
-    const BoundFn fn = solrrows::walkBound(g.recordVariant, leanRows[g.recordVariant] | (g.recordDeep ? F_DEEP : 0));
+    const BoundFn fn = solrrows::walkBound(g.recordVariant, solrrows::ROWS[g.recordVariant].features | (g.recordDeep ? F_DEEP : 0));
     ARGCHECK(fn != nullptr, "solr_hip_walk_bound: no replay instantiation for this row");
     if (!ok())
         return -1;
@@ -363,7 +356,7 @@ void solr_hip_set_frames_in_flight(int n)
         /* (which tiles are worth four quadrant waves depends on how many frames overlap: the launch order is made anew
          * with the next frame, not at the next regular sort) */
         if (g.flights != before)
-            g.orderValid = false;
+            g.sched.orderValid = false;
         if (g.initialized && g.width > 0)
             allocateFrame();
     });
@@ -387,22 +380,20 @@ int solr_hip_next_flight(void)
 void solr_hip_set_tile_scheduling(int mode)
 {
     onEveryDevice([&](int) {
-        g.tileScheduling = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
-        g.costFrames = 0;
-        g.reorder = false;
-        g.orderValid = false;
+        g.sched.mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
+        g.sched.reset();
     });
 }
 
 /* tiles the current launch order renders as four quadrant waves each (0: none, or no order) */
 int solr_hip_split_tiles(void)
 {
-    return (g.hostStats && g.orderValid) ? (int)g.hostStats[5] : 0;
+    return (g.sched.hostStats && g.sched.orderValid) ? (int)g.sched.hostStats[5] : 0;
 }
 
 int solr_hip_tile_scheduling_active(void)
 {
-    return (g.tileScheduling == 2 || (g.tileScheduling == 1 && g.reorder)) && g.orderValid ? 1 : 0;
+    return (g.sched.mode == 2 || (g.sched.mode == 1 && g.sched.reorder)) && g.sched.orderValid ? 1 : 0;
 }
 
 void solr_hip_enable_tile_clocks(int enable)
@@ -474,7 +465,7 @@ void solr_hip_set_variant(int variant)
 {
     onEveryDevice([&](int) {
         g.variant = variant;
-        g.grouping = (variant != 5); /* takes effect at the next h2d_scene */
+        g.grouping = (variant != VARIANT_NO_GROUPING); /* takes effect at the next h2d_scene */
     });
 }
 

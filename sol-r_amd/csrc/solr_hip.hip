@@ -251,7 +251,7 @@ static void finalizeOne()
     collectEvents();
     DeviceBuffer *all[] = {&g.geometry, &g.materials, &g.textures, &g.randoms, &g.lamps,
                            &g.pp,       &g.ids,       &g.bitmap,   &g.counters, &g.tileClock,
-                           &g.tileCost, &g.tileCostSnapshot, &g.tileOrder, &g.tileOrder2, &g.movable,  &g.refitPlan,
+                           &g.movable,  &g.refitPlan,
                            &g.walkRecords, &g.walkVisits};
     for (DeviceBuffer *b : all)
         release(*b);
@@ -275,20 +275,8 @@ static void finalizeOne()
     dropExtraStreams();
     releaseImageRing();
     releaseImageStreaming();
-    if (g.orderEvent)
-        (void)hipEventDestroy(g.orderEvent);
-    g.orderEvent = nullptr;
+    g.sched.release();
     g.current = 0;
-    g.orderBuffer = 0;
-    for (bool &w : g.orderWait)
-        w = false;
-    if (g.hostStats)
-        (void)hipHostFree(g.hostStats);
-    g.hostStats = g.hostStatsDev = nullptr;
-    g.costFrames = 0;
-    g.reorder = false;
-    g.orderValid = false;
-    memset(g.costKey, 0, sizeof(g.costKey));
     if (g.ownStream && g.stream)
         (void)hipStreamDestroy(g.stream);
     g.stream = nullptr;
@@ -390,7 +378,7 @@ void ensureEngines(int n)
         e.shortRayListsMode = gFirst.shortRayListsMode;
         e.grouping = gFirst.grouping;
         e.flights = gFirst.flights;
-        e.tileScheduling = gFirst.tileScheduling;
+        e.sched.mode = gFirst.sched.mode;
         e.timing = gFirst.timing;
     }
 }

@@ -81,9 +81,6 @@ void releaseImageStreaming()
     g.streamSupport = -1;
 }
 
-/* ImageStreaming, the host's part before a launch (renderImpl): counters, plan and band words for this frame geometry
- * - made, or zeroed, when the geometry changes or the row counts near 2^32 - and the frame's serial.  False: this frame is
- * not streamed (SOLR_HIP_NO_IMAGE_STREAMING=1, too few tile rows, an allocation failed: the read-back then takes the plain route). */
 /* the bands of a frame of that many tile rows; false: such a frame is not streamed (SOLR_HIP_NO_IMAGE_STREAMING=1, a frame
  * of fewer than sixteen tile rows) */
 bool imageStreamingCuts(int tileRows, int firstRow[SOLR_STREAM_BANDS_MAX + 1], int *bands, bool withIds)
@@ -101,47 +98,23 @@ bool imageStreamingCuts(int tileRows, int firstRow[SOLR_STREAM_BANDS_MAX + 1], i
      * to respect the bands (k_orderTiles: the heaviest eighth of the tiles first wherever they lie, the others band after
      * band).  Per frame, Cornell / molecule (profiles/r6/stream_frame.txt): 3 bands 0.313 / 0.398 ms, 4: 0.304 / 0.388,
      * 5: 0.301 / 0.385, 6: 0.387 / 0.432 (the host's calls no longer keep up); read back behind the kernel 0.394 / 0.483.
-     * SOLR_HIP_STREAM_BANDS (experiments): 1 ... SOLR_STREAM_BANDS_MAX; SOLR_HIP_STREAM_EQUAL=0: bands of n : n - 1 : ... : 1,
-     * the last copy the shortest; SOLR_HIP_STREAM_HEAVY=h: the heaviest 1 / h of the tiles first (8; with none first the
-     * molecule's frame is 0.412 ms, with half of them 0.42 and the Cornell box's 0.54) */
-    /* SOLR_HIP_STREAM_CUTS="0.33,0.67,0.89" (experiments): the bands end at these fractions of the frame's tile rows */
-    if (const char *given = getenv("SOLR_HIP_STREAM_CUTS"))
-    {
-        int n = 0;
-        firstRow[0] = 0;
-        for (const char *at = given; *at && n + 1 < SOLR_STREAM_BANDS_MAX;)
-        {
-            char *end = nullptr;
-            const double f = strtod(at, &end);
-            if (end == at)
-                break;
-            const int row = std::max(firstRow[n] + 1, std::min(tileRows - 1, (int)(f * tileRows + 0.5)));
-            if (row > firstRow[n] && row < tileRows)
-                firstRow[++n] = row;
-            at = (*end == ',') ? end + 1 : end;
-        }
-        firstRow[n + 1] = tileRows;
-        *bands = n + 1;
-        return true;
-    }
-    /* (with the primitive ids - 39 MB a frame, PCIe busy from the first band to the last - three: every band is two copies,
+     * (With the primitive ids - 39 MB a frame, PCIe busy from the first band to the last - three: every band is two copies,
      * and five cost 0.943 ms a Cornell frame where three cost 0.873; behind the kernel 1.0) */
-    static const int asked = getenv("SOLR_HIP_STREAM_BANDS") ? std::max(1, std::min(SOLR_STREAM_BANDS_MAX, atoi(getenv("SOLR_HIP_STREAM_BANDS")))) : 0;
-    const int wanted = asked ? asked : (withIds ? 3 : 5);
-    static const bool equal = !(getenv("SOLR_HIP_STREAM_EQUAL") && getenv("SOLR_HIP_STREAM_EQUAL")[0] == '0');
-    const int total = equal ? wanted : wanted * (wanted + 1) / 2;
-    int row = 0, weight = 0;
+    const int wanted = withIds ? 3 : 5;
+    int row = 0;
     for (int b = 0; b < wanted; ++b)
     {
         firstRow[b] = row;
-        weight += equal ? 1 : wanted - b;
-        row = std::max(row + 1, (int)((long)tileRows * weight / total));
+        row = std::max(row + 1, (int)((long)tileRows * (b + 1) / wanted));
     }
     firstRow[wanted] = tileRows;
     *bands = wanted;
     return true;
 }
 
+/* ImageStreaming, the host's part before a launch (renderImpl): counters, plan and band words for this frame geometry
+ * - made, or zeroed, when the geometry changes or the row counts near 2^32 - and the frame's serial.  False: this frame is
+ * not streamed (SOLR_HIP_NO_IMAGE_STREAMING=1, too few tile rows, an allocation failed: the read-back then takes the plain route). */
 bool armImageStreaming(FrameArgs &F, int tileRows, hipStream_t stream, bool withIds)
 {
     int cuts[SOLR_STREAM_BANDS_MAX + 1], bands = 0;
@@ -150,8 +123,9 @@ bool armImageStreaming(FrameArgs &F, int tileRows, hipStream_t stream, bool with
     const long key[3] = {F.tilesX, tileRows + 100000l * bands, g.width};
     const unsigned perRow = (unsigned)(F.tilesX * SPLIT_PARTS);
     const bool fresh = memcmp(key, g.streamKey, sizeof(key)) != 0 || !g.streamCounters.ptr;
-    /* (variant 14, tests: as if the row counts neared 2^32 every third frame) */
-    if (fresh || (unsigned long long)(g.streamSerial + 2u) * perRow >= 0xffffffffull || (g.variant == 14 && g.streamSerial >= 3u))
+    /* (VARIANT_ZERO_STREAM_COUNTERS, tests: as if the row counts neared 2^32 every third frame) */
+    if (fresh || (unsigned long long)(g.streamSerial + 2u) * perRow >= 0xffffffffull ||
+        (g.variant == VARIANT_ZERO_STREAM_COUNTERS && g.streamSerial >= 3u))
     {
         /* nothing of an earlier streamed frame may be under way: its waves count into these words */
         quiesce();

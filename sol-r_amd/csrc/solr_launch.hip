@@ -35,7 +35,7 @@ using namespace solrdev;
 
 using namespace solreng;
 
-/* the renderer's instantiations live in the files under csrc/rows (one object per row of renderImpl's table) */
+/* the renderer's instantiations live in the files under csrc/rows (the rows of solrrows::ROWS, renderer.h) */
 namespace solrrows
 {
 RendererFn renderer(int count, int features, bool volume)
@@ -167,7 +167,7 @@ void launchPostProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppI
         if (ok())
             solrpost::ambientOcclusion(stream, sceneInfo, ppInfo, nbRows, (const PixelRecord *)flightPp(flight).ptr,
                                        (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L, bitmap, halo, firstRow,
-                                       g.randomsReach, g.variant != 9);
+                                       g.randomsReach, g.variant != VARIANT_AO_FIXED_STRIDE);
     }
     else if (ppInfo.type == ppe_depthOfField)
         solrpost::depthOfField(stream, sceneInfo, ppInfo, nbRows, (const PixelRecord *)flightPp(flight).ptr,
@@ -183,93 +183,136 @@ void launchPostProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppI
     HIPCHECK(hipGetLastError());
 }
 
-void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProcessingInfo &ppInfo,
-                const float origin[3], const float direction[3], const float angles[4], bool counting,
-                unsigned long long counts[8])
+/* ---- the stages of a frame, in the order renderImpl runs them ------------------------------------------------------ */
+
+/* the arguments checked, the device selected, the frame's buffers sized.  False: nothing to render (the engine's error is
+ * set, or this process's strip is empty: more processes than rows to share out) */
+static bool frameReady(const SceneInfo &sceneInfo, const vec4i &objects)
 {
-    HostSpan whole("cudaRender (whole)");
-    HaloDebt debt;
-    if (ppInfo.type == ppe_ambientOcclusion && haveCommunicator())
-    {
-        /* (every rank, before anything rank-local can end the call: an all-reduce when the figure is stale) */
-        debt.wanted = agreedHaloRows(ppInfo);
-        debt.width = sceneInfo.size.x;
-        debt.frameRows = sceneInfo.size.y;
-        debt.owed = !(g.haloSuppliedAbove || g.haloSuppliedBelow);
-    }
     if (!ready("cudaRender"))
-        return;
+        return false;
     ARGCHECK(sceneInfo.size.x > 0 && sceneInfo.size.y > 0, "cudaRender: empty image");
     ARGCHECK(objects.x <= g.nbBoxes && objects.y <= g.nbPrimitives, "cudaRender: more objects than were uploaded");
     ARGCHECK(objects.w <= g.nbLights, "cudaRender: more lights than were uploaded");
     ARGCHECK(g.materials.ptr != nullptr, "cudaRender: no materials uploaded");
     ARGCHECK(sceneInfo.skyboxMaterialId <= NB_MAX_MATERIALS, "cudaRender: skybox material beyond the material table");
     if (!ok())
-        return;
+        return false;
     checkTextureTables();
     if (!ok())
-        return;
+        return false;
     HIPCHECK(hipSetDevice(g.device));
-    if (sceneInfo.size.x != g.width || sceneInfo.size.y != g.height)
-    {
-        g.width = sceneInfo.size.x;
-        g.height = sceneInfo.size.y;
-    }
+    g.width = sceneInfo.size.x;
+    g.height = sceneInfo.size.y;
     allocateFrame();
-    if (!ok())
-        return;
-    if (stripRows() == 0)
-        return; /* an empty strip (more processes than rows to share out): nothing to render */
-    /* which stream / buffer set: first-pass frames alternate when two frames may be in flight; a
-     * refinement or accumulation pass reads what the previous pass wrote and stays where that is */
+    return ok() && stripRows() != 0;
+}
+
+/* The buffer set (and stream) of the frame: first-pass frames alternate when two frames may be in flight; a refinement or
+ * accumulation pass reads what the previous pass wrote and stays where that is (so does the 3D-vision camera: it reads a
+ * depth of the frame before).  And the set's RGB image: an asynchronous read-back (solr_hip_d2h_image_async) may still be
+ * reading the image this set rendered last - the frame then goes to the set's other image; only the copy of the frame
+ * before last - long done - is waited for.  -1: an allocation failed. */
+static int takeFlight(const SceneInfo &sceneInfo, bool counting)
+{
     int flight = g.current;
-    /* (the 3D-vision camera reads a depth of the frame before: it stays on one buffer set) */
     if (twoFlights() && !counting && sceneInfo.pathTracingIteration == 0 && sceneInfo.cameraType != ctVR)
         flight = (int)(g.frameSerial++ % (unsigned)activeFlights());
     else if (!twoFlights())
         flight = 0;
-    const hipStream_t stream = flightStream(flight);
     g.current = flight;
     if (!g.boundBitmap && g.flightCopy[flight][g.bitmapSide[flight]] >= 0)
     {
-        /* an asynchronous read-back (solr_hip_d2h_image_async) may still be reading the image this set rendered
-         * last: this frame goes to the set's other image; only the copy of the frame before last - long done - is
-         * waited for */
         const int side = g.bitmapSide[flight] ^ 1;
         reserve(g.bitmapAlt[flight], flightBitmap(flight).bytes);
         if (!ok())
-            return;
+            return -1;
         g.bitmapSide[flight] = side;
         if (g.flightCopy[flight][side] >= 0)
         {
-            HIPCHECK(hipStreamWaitEvent(stream, g.imageDone[g.flightCopy[flight][side]], 0));
+            HIPCHECK(hipStreamWaitEvent(flightStream(flight), g.imageDone[g.flightCopy[flight][side]], 0));
             g.flightCopy[flight][side] = -1;
         }
     }
+    return flight;
+}
 
-    /* the box-debug view and the census count every node of the original tree */
-    const bool full = sceneInfo.renderBoxes != 0 || sceneInfo.advancedIllumination == aiBasic ||
-                      sceneInfo.advancedIllumination == aiFull || sceneInfo.cameraType == ctAntialiazed ||
-                      sceneInfo.cameraType == ctAnaglyph || sceneInfo.cameraType == ctPanoramic ||
-                      sceneInfo.cameraType == ctVR || sceneInfo.cameraType == ctVolumeRendering;
-    /* (the volume camera keeps every hit, nearest first, ties in the order it met them: the reference's list) */
-    const bool exactNodes = counting || sceneInfo.renderBoxes != 0 || objects.x != g.nbBoxes || g.variant == 3 ||
+/* The resident scene as this frame walks it, with the caller's counts of objects.  (The census, the box-debug view, a
+ * frame of fewer nodes than were uploaded and the volume camera walk the reference's own list: the volume camera keeps
+ * every hit, nearest first, ties in the order it met them.)  False: the engine's error is set. */
+static bool frameScene(const SceneInfo &sceneInfo, const vec4i &objects, bool counting, SceneArgs &S)
+{
+    const bool exactNodes = counting || sceneInfo.renderBoxes != 0 || objects.x != g.nbBoxes || g.variant == VARIANT_EXACT_LIST ||
                             sceneInfo.cameraType == ctVolumeRendering;
-    maybeBuildOrderFreeLists();
-    flushGeometry();
-    if (exactNodes)
-        refreshExactList();
+    S = prepareScene(sceneInfo, exactNodes);
     if (!ok())
-        return;
-    SceneArgs S = makeScene(exactNodes);
-    S.tightLists = tightListsFor(S, sceneInfo, exactNodes);
+        return false;
     if (exactNodes)
         S.nbBoxes = objects.x;
     S.nbPrimitives = objects.y;
     S.nbLamps = objects.z;
     S.nbLights = objects.w;
+    return true;
+}
 
-    FrameArgs F;
+/* the box-debug view, the census and the special cameras count every node of the original tree (F_FULL) */
+static bool fullFeatures(const SceneInfo &sceneInfo)
+{
+    return sceneInfo.renderBoxes != 0 || sceneInfo.advancedIllumination == aiBasic || sceneInfo.advancedIllumination == aiFull ||
+           sceneInfo.cameraType == ctAntialiazed || sceneInfo.cameraType == ctAnaglyph || sceneInfo.cameraType == ctPanoramic ||
+           sceneInfo.cameraType == ctVR || sceneInfo.cameraType == ctVolumeRendering;
+}
+
+/* the post-processing reads the pixels around each pixel: a pass of its own behind the renderer (launchPostProcess) */
+static bool neighbourhoodPass(const PostProcessingInfo &ppInfo)
+{
+    return ppInfo.type == ppe_ambientOcclusion || ppInfo.type == ppe_depthOfField || ppInfo.type == ppe_radiosity ||
+           ppInfo.type == ppe_filter || ppInfo.type == ppe_cartoon;
+}
+
+/* colour-stack slots of a lane: one per bounce the frame may take */
+static int bounceSlots(const SceneInfo &sceneInfo)
+{
+    int maxIt = (sceneInfo.graphicsLevel < glReflectionsAndRefractions)
+                    ? 1
+                    : sceneInfo.nbRayIterations + sceneInfo.pathTracingIteration;
+    maxIt = maxIt > NB_MAX_ITERATIONS ? NB_MAX_ITERATIONS : maxIt;
+    return maxIt < 1 ? 1 : maxIt;
+}
+
+static size_t ldsBytesFor(int stackSlots)
+{
+    return ((size_t)stackSlots * 4 + COLD_FIELDS) * WAVE * sizeof(float);
+}
+
+static int tileRows(const FrameArgs &F)
+{
+    return (F.nbRows + TILE_H - 1) / TILE_H;
+}
+
+/* The reciprocal of tilesX for the kernel's tile -> (column, row): tile / tilesX = (tile * magic) >> (32 + shift) for every
+ * tile below `tiles`.  shift = ceil(log2 tilesX) - 1: the multiplier ceil(2^(32 + shift) / tilesX) has 32 bits and is exact
+ * for every index below 2^31; one tile per row (magic 0) needs no division.  False: not exact for every tile. */
+static bool tileReciprocal(int tilesX, int tiles, unsigned *magic, int *shift)
+{
+    int s = 0;
+    while ((2 << s) < tilesX)
+        ++s;
+    const unsigned long long m =
+        tilesX == 1 ? 0ull : ((1ull << (32 + s)) + (unsigned long long)tilesX - 1) / (unsigned long long)tilesX;
+    bool exact = m <= 0xffffffffull;
+    for (int t = 0; t < tiles && exact && m; ++t)
+        exact = (int)(((unsigned long long)(unsigned)t * m) >> (32 + s)) == t / tilesX;
+    *magic = (unsigned)m;
+    *shift = s;
+    return exact;
+}
+
+/* The frame's arguments as the camera, the strip and the bounce limit decide them (the stages that follow add the rest).
+ * The tile reciprocal is verified once per frame geometry and kept in g.  False: there is none (the error is set). */
+static bool frameArgs(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, const float origin[3],
+                      const float direction[3], const float angles[4], FrameArgs &F)
+{
     memset(&F, 0, sizeof(F));
     F.si = sceneInfo;
     F.ppi = ppInfo;
@@ -298,192 +341,198 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     F.firstRow = g.nbRows >= 0 ? g.firstRow : 0;
     F.nbRows = stripRows();
     F.tilesX = (sceneInfo.size.x + TILE_W - 1) / TILE_W;
-    const int tilesY = (F.nbRows + TILE_H - 1) / TILE_H;
+    const int tiles = F.tilesX * tileRows(F);
+    if (g.tileCheckedX != F.tilesX || g.tileCheckedTiles < tiles)
     {
-        /* the reciprocal of tilesX for the kernel's tile -> (column, row): exact for every tile of this frame
-         * (round-up multiplier of ceil(log2) + 16 extra bits; verified below, once per frame geometry) */
-        const int tiles = F.tilesX * tilesY;
-        if (g.tileCheckedX != F.tilesX || g.tileCheckedTiles < tiles)
-        {
-            /* shift = ceil(log2 tilesX) - 1: the multiplier ceil(2^(32 + shift) / tilesX) has 32 bits and is exact for
-             * every index below 2^31; one tile per row (magic 0) needs no division */
-            int shift = 0;
-            while ((2 << shift) < F.tilesX)
-                ++shift;
-            const unsigned long long magic =
-                F.tilesX == 1 ? 0ull : ((1ull << (32 + shift)) + (unsigned long long)F.tilesX - 1) / (unsigned long long)F.tilesX;
-            bool exact = magic <= 0xffffffffull;
-            for (int t = 0; t < tiles && exact && magic; ++t)
-                exact = (int)(((unsigned long long)(unsigned)t * magic) >> (32 + shift)) == t / F.tilesX;
-            ARGCHECK(exact, "cudaRender: no exact reciprocal for this frame width");
-            if (!exact)
-                return; /* (cannot happen below 2^31 tiles; nothing is cached, the next frame checks again) */
-            g.tileCheckedX = F.tilesX;
-            g.tileCheckedTiles = tiles;
-            g.tileCheckedMagic = (unsigned)magic;
-            g.tileCheckedShift = shift;
-        }
-        F.tileMagic = g.tileCheckedMagic;
-        F.tileShift = g.tileCheckedShift;
+        unsigned magic = 0;
+        int shift = 0;
+        const bool exact = tileReciprocal(F.tilesX, tiles, &magic, &shift);
+        ARGCHECK(exact, "cudaRender: no exact reciprocal for this frame width");
+        if (!exact)
+            return false; /* (cannot happen below 2^31 tiles; nothing is cached, the next frame checks again) */
+        g.tileCheckedX = F.tilesX;
+        g.tileCheckedTiles = tiles;
+        g.tileCheckedMagic = magic;
+        g.tileCheckedShift = shift;
     }
-    const bool neighbourhood = (ppInfo.type == ppe_ambientOcclusion || ppInfo.type == ppe_depthOfField ||
-                                ppInfo.type == ppe_radiosity || ppInfo.type == ppe_filter || ppInfo.type == ppe_cartoon);
-    unsigned char *bitmap = (unsigned char *)(g.boundBitmap ? g.boundBitmap : flightBitmap(flight).ptr);
-    F.fuseDefault = neighbourhood ? 0 : 1;
-
-    int maxIt = (sceneInfo.graphicsLevel < glReflectionsAndRefractions)
-                    ? 1
-                    : sceneInfo.nbRayIterations + sceneInfo.pathTracingIteration;
-    maxIt = maxIt > NB_MAX_ITERATIONS ? NB_MAX_ITERATIONS : maxIt;
-    maxIt = maxIt < 1 ? 1 : maxIt;
-    F.stackSlots = maxIt;
+    F.tileMagic = g.tileCheckedMagic;
+    F.tileShift = g.tileCheckedShift;
+    F.fuseDefault = neighbourhoodPass(ppInfo) ? 0 : 1;
+    F.stackSlots = bounceSlots(sceneInfo);
     if (sceneInfo.cameraType == ctVolumeRendering)
         F.stackSlots = 11; /* the ten layers of launchVolumeRendering and the element behind them */
-    if (sceneInfo.cameraType == ctVR)
-    {
-        /* the focus pixel of k_3DVisionRenderer (CRT:973, integer expression as written there) as the frame
-         * before left it; a strip that does not hold it reads 0 */
-        const long focusIndex = (long)(sceneInfo.size.x / 2 * sceneInfo.size.y / 2);
-        const long focusRow = focusIndex / sceneInfo.size.x - F.firstRow;
-        if (focusRow >= 0 && focusRow < F.nbRows && flightPp(flight).ptr)
-        {
-            const PostProcessingBuffer *at = (const PostProcessingBuffer *)flightPp(flight).ptr +
-                                             focusRow * sceneInfo.size.x + focusIndex % sceneInfo.size.x;
-            HIPCHECK(hipMemcpyAsync(&F.focusDepth, &at->colorInfo.w, sizeof(float), hipMemcpyDeviceToHost, stream));
-            HIPCHECK(hipStreamSynchronize(stream));
-        }
-    }
-    /* SOLR_HIP_LDS_PAD (bytes, experiments): more LDS per wave = fewer waves per SIMD; what occupancy is worth */
-    static const size_t ldsPad = getenv("SOLR_HIP_LDS_PAD") ? (size_t)atol(getenv("SOLR_HIP_LDS_PAD")) : 0;
-    size_t ldsBytes = ((size_t)F.stackSlots * 4 + COLD_FIELDS) * WAVE * sizeof(float) + ldsPad;
+    return true;
+}
 
-    const dim3 grid(F.tilesX * tilesY), block(WAVE);
-    if (g.tileClocks)
+/* ctVR: the focus pixel of k_3DVisionRenderer (CRT:973, integer expression as written there) as the frame before left it; a
+ * strip that does not hold it reads 0 */
+static void readFocusDepth(FrameArgs &F, int flight, hipStream_t stream)
+{
+    const long focusIndex = (long)(F.si.size.x / 2 * F.si.size.y / 2);
+    const long focusRow = focusIndex / F.si.size.x - F.firstRow;
+    if (focusRow >= 0 && focusRow < F.nbRows && flightPp(flight).ptr)
     {
-        reserve(g.tileClock, (size_t)grid.x * 2 * sizeof(unsigned long long));
-        if (!ok())
-            return;
-        F.tileClock = (unsigned long long *)g.tileClock.ptr;
-        g.nbTilesTimed = (int)grid.x;
+        const PostProcessingBuffer *at =
+            (const PostProcessingBuffer *)flightPp(flight).ptr + focusRow * F.si.size.x + focusIndex % F.si.size.x;
+        HIPCHECK(hipMemcpyAsync(&F.focusDepth, &at->colorInfo.w, sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
     }
-    /* ImageStreaming (renderer.h): asked for (solr_hip_stream_next_image), and this is a frame whose image the kernel
-     * itself writes, whole, on one device, one frame at a time */
+}
+
+/* diagnostics (solr_hip_enable_tile_clocks): {start, end} of every tile of the frame.  False: the allocation failed */
+static bool armTileClocks(FrameArgs &F, unsigned tiles)
+{
+    reserve(g.tileClock, (size_t)tiles * 2 * sizeof(unsigned long long));
+    if (!ok())
+        return false;
+    F.tileClock = (unsigned long long *)g.tileClock.ptr;
+    g.nbTilesTimed = (int)tiles;
+    return true;
+}
+
+/* ImageStreaming (renderer.h): the bands, in tiles, this frame's image would leave in; bands = 0: it is not streamed.  Asked
+ * for (solr_hip_stream_next_image), and a frame whose image the kernel itself writes, whole, on one device, one frame at a
+ * time.  (Is there an instantiation that counts tiles for the kernel this scene takes?  Asked of the frame before: the
+ * launch order, made further up than the choice of the kernel, has to know.)  The request is used up; *withIds: it was
+ * for the primitive ids too. */
+static BandCuts decideStreamCuts(const FrameArgs &F, bool counting, bool *withIds)
+{
     g.streamedValid = false;
-    BandCuts streamCuts = {};
+    BandCuts cuts = {};
+    int rows[SOLR_STREAM_BANDS_MAX + 1];
+    if (g.streamNext && !counting && !g.recordNext && F.fuseDefault && F.si.frameBufferType != ftBGR && !twoFlights() &&
+        g.nbRows < 0 && gDevices == 1 && !g.boundBitmap && !g.sharedRing && g.lastMask >= 0 &&
+        solrrows::renderer(0, g.lastMask | F_STREAM, false) != nullptr &&
+        imageStreamingCuts(tileRows(F), rows, &cuts.bands, g.streamNext == 2))
     {
-        int rows[SOLR_STREAM_BANDS_MAX + 1];
-        /* (is there an instantiation that counts tiles for the kernel this scene takes?  Asked of the frame before: the
-         * launch order, made further up than the choice of the kernel, has to know) */
-        if (g.streamNext && !counting && !g.recordNext && F.fuseDefault && sceneInfo.frameBufferType != ftBGR && !twoFlights() &&
-            g.nbRows < 0 && gDevices == 1 && !g.boundBitmap && !g.sharedRing && g.lastMask >= 0 &&
-            solrrows::renderer(0, g.lastMask | F_STREAM, false) != nullptr && imageStreamingCuts(tilesY, rows, &streamCuts.bands, g.streamNext == 2))
-        {
-            for (int b = 0; b <= streamCuts.bands; ++b)
-                streamCuts.firstTile[b] = rows[b] * F.tilesX;
-            static const int share = getenv("SOLR_HIP_STREAM_HEAVY") ? std::max(1, atoi(getenv("SOLR_HIP_STREAM_HEAVY"))) : 8;
-            streamCuts.heavyShare = share;
-        }
+        for (int b = 0; b <= cuts.bands; ++b)
+            cuts.firstTile[b] = rows[b] * F.tilesX;
+        /* the heaviest eighth of the tiles first, wherever they lie (k_orderTiles; with none first the molecule's frame is
+         * 0.412 ms against 0.385, with half of them 0.42 and the Cornell box's 0.54: profiles/r6/stream_frame.txt) */
+        cuts.heavyShare = 8;
     }
-    const bool streamIds = g.streamNext == 2;
+    *withIds = g.streamNext == 2;
     g.streamNext = 0;
-    bool streamCandidate = streamCuts.bands > 0;
-    if (g.tileScheduling > 0 && !counting)
+    return cuts;
+}
+
+/* The cost-ordered launch (g.sched, engine.h TileSchedule): the frame records what its tiles cost, and takes the launch
+ * order made from the costs of the frames before it.  Statistics (and, in cost order, a fresh order) every
+ * SORT_PERIOD-th frame, and at once when the decision has just changed; in between the last order is reused.
+ * *streamCandidate: a frame whose longest tile would be rendered by four quadrant waves is not streamed.  False: an
+ * allocation failed. */
+static bool scheduleTiles(FrameArgs &F, unsigned tiles, int flight, hipStream_t stream, const BandCuts &streamCuts,
+                          bool *streamCandidate)
+{
+    TileSchedule &s = g.sched;
+    const long key[6] = {(long)tiles, F.tilesX, F.firstRow, F.nbRows, F.si.size.x, F.si.size.y};
+    if (!s.hostStats)
     {
-        const long key[6] = {(long)grid.x, F.tilesX, F.firstRow, F.nbRows, sceneInfo.size.x, sceneInfo.size.y};
-        if (!g.hostStats)
+        HIPCHECK(hipHostMalloc((void **)&s.hostStats, 8 * sizeof(unsigned), hipHostMallocMapped));
+        if (ok())
         {
-            HIPCHECK(hipHostMalloc((void **)&g.hostStats, 8 * sizeof(unsigned), hipHostMallocMapped));
-            if (ok())
-            {
-                memset(g.hostStats, 0, 8 * sizeof(unsigned));
-                HIPCHECK(hipHostGetDevicePointer((void **)&g.hostStatsDev, g.hostStats, 0));
-            }
+            memset(s.hostStats, 0, 8 * sizeof(unsigned));
+            HIPCHECK(hipHostGetDevicePointer((void **)&s.hostStatsDev, s.hostStats, 0));
         }
-        if (memcmp(key, g.costKey, sizeof(key)) != 0 || !g.tileCost.ptr)
-        {
-            memcpy(g.costKey, key, sizeof(key));
-            g.costFrames = 0;
-            g.reorder = false;
-            g.orderValid = false;
-            /* none of them is read before a sort has written it; a fresh allocation still gets a defined
-             * content (a buffer that is kept may be in use by a frame in flight and is left alone) */
-            for (DeviceBuffer *b : {&g.tileCost, &g.tileCostSnapshot, &g.tileOrder, &g.tileOrder2})
-            {
-                const void *before = b->ptr;
-                reserve(*b, ((size_t)grid.x + (SPLIT_PARTS - 1) * SPLIT_TILES_MAX) * sizeof(unsigned));
-                if (ok() && b->ptr != before)
-                    HIPCHECK(hipMemset(b->ptr, 0, b->bytes));
-            }
-            g.orderBuffer = 0;
-            for (bool &w : g.orderWait)
-                w = false;
-        }
-        if (!ok())
-            return;
-        /* decision of the automatic mode from the newest frame the host can see (no synchronisation:
-         * the figures are one or two frames old, which is as good for a scheduling hint) */
-        if (g.costFrames > 0 && g.hostStats[4] != 0 && g.hostStats[3] == grid.x)
-        {
-            const unsigned long long sum = (unsigned long long)g.hostStats[1] | ((unsigned long long)g.hostStats[2] << 32);
-            const unsigned long long mx = g.hostStats[0];
-            if (mx * grid.x > 2ull * sum)
-                g.reorder = true;
-            else if (2ull * mx * grid.x < 3ull * sum)
-                g.reorder = false;
-            /* a frame whose longest tile would be rendered by four quadrant waves (k_orderTiles' criterion, for one frame
-             * in flight) keeps the order that puts those first: it is not streamed */
-            const float mean = (float)sum / (float)grid.x;
-            const float critical = fmaxf(2.f * mean, (float)sum / 5120.f);
-            if (g.reorder && (unsigned)(critical * (64.f / ((float)mx + 1.f))) < 63u)
-                streamCandidate = false;
-        }
-        F.tileCost = (unsigned *)g.tileCost.ptr;
-        /* statistics (and, in cost order, a fresh order) every sortPeriod()-th frame, and at once when the
-         * decision has just changed; in between the last order is reused */
-        const bool ordered = g.costFrames > 0 && (g.tileScheduling == 2 || g.reorder);
-        /* a streamed frame takes its tiles band after band (k_orderTiles), any other by cost alone: the order is re-made
-         * at once when the frame at hand is of the other kind */
-        const BandCuts cuts = streamCandidate ? streamCuts : BandCuts();
-        if (ordered && g.orderValid && memcmp(&g.orderCuts, &cuts, sizeof(cuts)) != 0)
-            g.orderValid = false;
-        const bool refresh = g.costFrames > 0 && (g.costFrames % sortPeriod() == 1 || (ordered && !g.orderValid));
-        const bool sort = ordered && refresh;
-        if (!ordered)
-            g.orderValid = false;
-        if (refresh)
-        {
-            /* a new order goes to the buffer no frame in flight is reading; the other stream waits for
-             * the sort before its next frame picks that buffer up */
-            const int target = sort ? (g.orderBuffer ^ 1) : g.orderBuffer;
-            DeviceBuffer &orderOut = target ? g.tileOrder2 : g.tileOrder;
-            solrpost::orderTiles(stream, (const unsigned *)g.tileCost.ptr, (unsigned *)g.tileCostSnapshot.ptr,
-                                 (unsigned *)orderOut.ptr, (int)grid.x, (volatile unsigned *)g.hostStatsDev, sort ? activeFlights() : 0, cuts);
-            HIPCHECK(hipGetLastError());
-            if (sort)
-            {
-                g.orderValid = true;
-                g.orderCuts = cuts;
-                g.orderBuffer = target;
-                if (twoFlights())
-                {
-                    if (!g.orderEvent)
-                        HIPCHECK(hipEventCreateWithFlags(&g.orderEvent, hipEventDisableTiming));
-                    if (ok())
-                        HIPCHECK(hipEventRecord(g.orderEvent, stream));
-                    for (int f = 0; f < MAX_FLIGHTS; ++f)
-                        g.orderWait[f] = (f != flight);
-                }
-            }
-        }
-        if (g.orderWait[flight] && g.orderEvent)
-        {
-            HIPCHECK(hipStreamWaitEvent(stream, g.orderEvent, 0));
-            g.orderWait[flight] = false;
-        }
-        if (ordered && g.orderValid)
-            F.tileOrder = (const unsigned *)(g.orderBuffer ? g.tileOrder2.ptr : g.tileOrder.ptr);
-        g.costFrames++;
     }
+    if (memcmp(key, s.key, sizeof(key)) != 0 || !s.cost.ptr)
+    {
+        memcpy(s.key, key, sizeof(key));
+        s.reset();
+        /* none of them is read before a sort has written it; a fresh allocation still gets a defined
+         * content (a buffer that is kept may be in use by a frame in flight and is left alone) */
+        for (DeviceBuffer *b : {&s.cost, &s.costSnapshot, &s.order[0], &s.order[1]})
+        {
+            const void *before = b->ptr;
+            reserve(*b, ((size_t)tiles + (SPLIT_PARTS - 1) * SPLIT_TILES_MAX) * sizeof(unsigned));
+            if (ok() && b->ptr != before)
+                HIPCHECK(hipMemset(b->ptr, 0, b->bytes));
+        }
+        s.orderBuffer = 0;
+        for (bool &w : s.orderWait)
+            w = false;
+    }
+    if (!ok())
+        return false;
+    /* decision of the automatic mode from the newest frame the host can see (no synchronisation:
+     * the figures are one or two frames old, which is as good for a scheduling hint) */
+    if (s.frames > 0 && s.hostStats[4] != 0 && s.hostStats[3] == tiles)
+    {
+        const unsigned long long sum = (unsigned long long)s.hostStats[1] | ((unsigned long long)s.hostStats[2] << 32);
+        const unsigned long long mx = s.hostStats[0];
+        if (mx * tiles > 2ull * sum)
+            s.reorder = true;
+        else if (2ull * mx * tiles < 3ull * sum)
+            s.reorder = false;
+        /* a frame whose longest tile would be rendered by four quadrant waves (k_orderTiles' criterion, for one frame
+         * in flight) keeps the order that puts those first: it is not streamed */
+        const float mean = (float)sum / (float)tiles;
+        const float critical = fmaxf(2.f * mean, (float)sum / 5120.f);
+        if (s.reorder && (unsigned)(critical * (64.f / ((float)mx + 1.f))) < 63u)
+            *streamCandidate = false;
+    }
+    F.tileCost = (unsigned *)s.cost.ptr;
+    const bool ordered = s.frames > 0 && (s.mode == 2 || s.reorder);
+    /* a streamed frame takes its tiles band after band (k_orderTiles), any other by cost alone: the order is re-made
+     * at once when the frame at hand is of the other kind */
+    const BandCuts cuts = *streamCandidate ? streamCuts : BandCuts();
+    if (ordered && s.orderValid && memcmp(&s.orderCuts, &cuts, sizeof(cuts)) != 0)
+        s.orderValid = false;
+    const bool refresh = s.frames > 0 && (s.frames % SORT_PERIOD == 1 || (ordered && !s.orderValid));
+    const bool sort = ordered && refresh;
+    if (!ordered)
+        s.orderValid = false;
+    if (refresh)
+    {
+        /* a new order goes to the buffer no frame in flight is reading; the other stream waits for
+         * the sort before its next frame picks that buffer up */
+        const int target = sort ? (s.orderBuffer ^ 1) : s.orderBuffer;
+        solrpost::orderTiles(stream, (const unsigned *)s.cost.ptr, (unsigned *)s.costSnapshot.ptr, (unsigned *)s.order[target].ptr,
+                             (int)tiles, (volatile unsigned *)s.hostStatsDev, sort ? activeFlights() : 0, cuts);
+        HIPCHECK(hipGetLastError());
+        if (sort)
+        {
+            s.orderValid = true;
+            s.orderCuts = cuts;
+            s.orderBuffer = target;
+            if (twoFlights())
+            {
+                if (!s.orderEvent)
+                    HIPCHECK(hipEventCreateWithFlags(&s.orderEvent, hipEventDisableTiming));
+                if (ok())
+                    HIPCHECK(hipEventRecord(s.orderEvent, stream));
+                for (int f = 0; f < MAX_FLIGHTS; ++f)
+                    s.orderWait[f] = (f != flight);
+            }
+        }
+    }
+    if (s.orderWait[flight] && s.orderEvent)
+    {
+        HIPCHECK(hipStreamWaitEvent(stream, s.orderEvent, 0));
+        s.orderWait[flight] = false;
+    }
+    if (ordered && s.orderValid)
+        F.tileOrder = (const unsigned *)s.order[s.orderBuffer].ptr;
+    s.frames++;
+    return true;
+}
+
+void TileSchedule::release()
+{
+    for (DeviceBuffer *b : {&cost, &costSnapshot, &order[0], &order[1]})
+        solreng::release(*b);
+    if (orderEvent)
+        (void)hipEventDestroy(orderEvent);
+    if (hostStats)
+        (void)hipHostFree(hostStats);
+    const int keep = mode;
+    *this = TileSchedule();
+    mode = keep;
+}
+
+/* every g.timing-th frame's kernel between two events (solr_hip_enable_timing, collectEvents); {null, null}: not this one */
+static std::pair<hipEvent_t, hipEvent_t> startKernelTimer(bool counting, hipStream_t stream)
+{
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (g.timing > 0 && !counting && (g.timingTick++ % (unsigned)g.timing) == 0)
     {
@@ -491,68 +540,153 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
         HIPCHECK(hipEventCreate(&e1));
         HIPCHECK(hipEventRecord(e0, stream));
     }
-    PixelRecord *ppPtr = (PixelRecord *)flightPp(flight).ptr;
-    int4 *idPtr = (int4 *)flightIds(flight).ptr;
-    unsigned long long *cntPtr = (unsigned long long *)g.counters.ptr;
+    return std::make_pair(e0, e1);
+}
+
+/* the kernel a frame takes: the function; the row of solrrows::ROWS and the features of its instantiation (-1: the census
+ * or the all-features kernel); the colour-stack slots of the frame kept in HBM (F_STACK) */
+struct KernelChoice
+{
+    RendererFn fn;
+    int row, mask, deepSlots;
+};
+static KernelChoice chooseKernel(const SceneInfo &sceneInfo, bool full, bool deepList, bool counting)
+{
+    const bool volumeCamera = sceneInfo.cameraType == ctVolumeRendering;
+    if (counting)
+        return {solrrows::renderer(1, F_ALL, volumeCamera), -1, -1, 0};
+    KernelChoice k = {solrrows::renderer(0, F_ALL | F_DEEP, volumeCamera), -1, -1, 0};
+    if (volumeCamera || g.variant == VARIANT_ALL_FEATURES)
+        return k;
     /* smallest instantiation that covers the scene (rt_device.h, enum Feature) */
     const int need = neededFeatures(sceneInfo, full);
-    typedef RendererFn KernelFn;
-    /* the rows of the table, smallest first: feature masks of the instantiations csrc/rows/ holds (renderer.h); the
-     * lean ones exist with the two-bank and the three-bank walk loop (rt_device.h advanceTidy), the others with the
-     * three-bank loop only */
-    static const struct
-    {
-        int features;
-        bool bothLoops;
-    } variants[] = {
-        {F_SPHERE | F_PLANE, true},
-        {F_SPHERE | F_TRI, true},
-        {F_SPHERE | F_CYL, true},
-        {F_SPHERE | F_PLANE | F_TRI | F_CYL, false},
-        /* textured scenes of the usual primitives (OBJ meshes with their MTL images; a textured room): the texture tier
-         * without the procedural spheres and the ellipsoids */
-        {F_SPHERE | F_TRI | F_TEX, true},
-        {F_SPHERE | F_PLANE | F_TRI | F_CYL | F_TEX, false},
-        /* the special cameras, global illumination and the box-debug view over the usual untextured primitives (the
-         * texture tier is what costs the registers: profiles/r3/generic_kernels.txt) */
-        {F_SPHERE | F_PLANE | F_TRI | F_CYL | F_FULL, false},
-        {F_ALL & ~F_FULL, false},
-        {F_ALL, false},
-    };
-    /* a list of more than a thousand nodes does not live in the scalar cache: skips land on cold records */
-    const bool deepList = S.nbBoxes > 1024;
-    const bool volumeCamera = sceneInfo.cameraType == ctVolumeRendering;
-    KernelFn fn = solrrows::renderer(1, F_ALL, volumeCamera);
-    int deepSlots = 0; /* colour-stack slots of this frame kept in HBM (F_STACK) */
-    int chosenMask = -1; /* features of the row chosen: what an instantiation with another epilogue (F_STREAM) is asked for with */
-    if (!counting)
-    {
-        fn = solrrows::renderer(0, F_ALL | F_DEEP, volumeCamera);
-        int row = 0, chosen = -1;
-        chosenMask = -1;
-        for (const auto &v : variants)
+    for (int row = 0; row < solrrows::NB_ROWS; ++row)
+        if ((need & ~solrrows::ROWS[row].features) == 0)
         {
-            if ((need & ~v.features) == 0 && g.variant != 4 && !volumeCamera)
-            {
-                const int mask = v.features | ((deepList || !v.bothLoops) ? F_DEEP : 0);
-                fn = solrrows::renderer(0, mask, false);
-                /* more bounces than colour-stack slots fit the LDS of 16 waves per CU: the lean rows have an
-                 * instantiation that keeps the deeper slots in HBM (rt_device.h ColorStack, F_STACK) */
-                if (maxIt > SOLR_LDS_STACK_SLOTS && !g.recordNext && g.variant != 7)
-                    if (KernelFn spilling = solrrows::renderer(0, mask | F_STACK, false))
-                    {
-                        fn = spilling;
-                        deepSlots = maxIt - SOLR_LDS_STACK_SLOTS;
-                    }
-                chosen = row;
-                chosenMask = mask;
-                break;
-            }
-            ++row;
+            k.row = row;
+            k.mask = solrrows::rowMask(row, deepList);
+            k.fn = solrrows::renderer(0, k.mask, false);
+            /* more bounces than colour-stack slots fit the LDS of 16 waves per CU: the lean rows have an
+             * instantiation that keeps the deeper slots in HBM (rt_device.h ColorStack, F_STACK) */
+            const int slots = bounceSlots(sceneInfo);
+            if (slots > SOLR_LDS_STACK_SLOTS && !g.recordNext && g.variant != VARIANT_STACK_IN_LDS)
+                if (RendererFn spilling = solrrows::renderer(0, k.mask | F_STACK, false))
+                {
+                    k.fn = spilling;
+                    k.deepSlots = slots - SOLR_LDS_STACK_SLOTS;
+                }
+            break;
         }
-        g.recordVariant = chosen;
+    return k;
+}
+
+/* This frame leaves a record of its walks (rt_device.h recordWalk; solr_hip_walk_bound): the same kernel with COUNT == 2,
+ * launched exactly as it would have been - grid, order, LDS - with the record buffer in place of the counters.  Only the
+ * lean rows of the table have such an instantiation.  Null: none, or an allocation failed (the error is set). */
+static RendererFn recordingKernel(const KernelChoice &k, const SceneArgs &S, unsigned grid, size_t ldsBytes, hipStream_t stream)
+{
+    g.recordNext = false;
+    ARGCHECK(k.row >= 0 && k.row < solrrows::LEAN_ROWS,
+             "solr_hip_walk_bound: the kernel this scene needs has no recording instantiation (untextured spheres, "
+             "planes, triangles, cylinders only)");
+    if (!ok())
+        return nullptr;
+    reserve(g.walkRecords, (size_t)grid * SOLR_WALK_SLOT_BYTES);
+    reserve(g.walkVisits, (size_t)grid * WAVE * sizeof(unsigned) + 64);
+    if (!ok())
+        return nullptr;
+    HIPCHECK(hipMemsetAsync(g.walkRecords.ptr, 0, (size_t)grid * SOLR_WALK_SLOT_BYTES, stream));
+    const RendererFn fn = solrrows::renderer(2, k.mask, false);
+    ARGCHECK(fn != nullptr, "solr_hip_walk_bound: no recording instantiation");
+    if (!ok())
+        return nullptr;
+    g.recordGrid = grid;
+    g.recordLds = ldsBytes;
+    g.recordDeep = (k.mask & F_DEEP) != 0;
+    g.recordScene = S;
+    g.recorded = true;
+    return fn;
+}
+
+/* An F_STACK instantiation: SOLR_LDS_STACK_SLOTS slots in LDS - 16 waves per CU whatever the bounce limit - and the rest of
+ * this buffer set's frame in HBM, a plane of the strip per slot (3840 x 2160 x 7 slots: 0.9 GB of the 288; touched only by
+ * the rays that go that deep).  False: the allocation failed. */
+static bool armDeepStack(FrameArgs &F, int deepSlots, int flight, hipStream_t stream)
+{
+    F.stackSlots = SOLR_LDS_STACK_SLOTS;
+    F.deepStride = (long)F.si.size.x * F.nbRows;
+    reserve(g.deepStack[flight], (size_t)deepSlots * (size_t)F.deepStride * sizeof(float4));
+    if (!ok())
+        return false;
+    F.deepStack = (float4 *)g.deepStack[flight].ptr;
+    /* the deep slots are never zeroed: every slot a lane reads was written by the trip that made it (rt_device.h
+     * launchRayTracing).  VARIANT_NAN_DEEP_STACK proves it: NaNs in every slot before the launch, the same frame after */
+    if (g.variant == VARIANT_NAN_DEEP_STACK)
+        HIPCHECK(hipMemsetAsync(F.deepStack, 0xff, (size_t)deepSlots * (size_t)F.deepStride * sizeof(float4), stream));
+    return true;
+}
+
+/* ImageStreaming: the instantiation of the frame's row that counts its tiles, when there is one and the counters are armed
+ * (tiles in launch order, or band after band: an order by cost alone completes every band at the end; the epilogue that
+ * counts tiles is in instantiations of its own - the lean rows have them, rt_device.h F_STREAM).  False: the frame is not
+ * streamed. */
+static bool armStreamedFrame(FrameArgs &F, const KernelChoice &k, const BandCuts &cuts, hipStream_t stream, bool withIds,
+                             RendererFn *fn)
+{
+    if (k.mask < 0 || (F.tileOrder && memcmp(&g.sched.orderCuts, &cuts, sizeof(cuts)) != 0))
+        return false;
+    const RendererFn streaming = solrrows::renderer(0, k.mask | (k.deepSlots > 0 ? F_STACK : 0) | F_STREAM, false);
+    if (!streaming || !armImageStreaming(F, tileRows(F), stream, withIds))
+        return false;
+    *fn = streaming;
+    F.fuseDefault |= withIds ? 6 : 2;
+    if (g.variant == VARIANT_NO_BAND_WORDS) /* (tests: the waves write no band's word - the host goes by the end of the kernel) */
+        F.streamSerial = 0x7fffff00u;
+    return true;
+}
+
+void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProcessingInfo &ppInfo,
+                const float origin[3], const float direction[3], const float angles[4], bool counting,
+                unsigned long long counts[8])
+{
+    HostSpan whole("cudaRender (whole)");
+    HaloDebt debt;
+    if (ppInfo.type == ppe_ambientOcclusion && haveCommunicator())
+    {
+        /* (every rank, before anything rank-local can end the call: an all-reduce when the figure is stale) */
+        debt.wanted = agreedHaloRows(ppInfo);
+        debt.width = sceneInfo.size.x;
+        debt.frameRows = sceneInfo.size.y;
+        debt.owed = !(g.haloSuppliedAbove || g.haloSuppliedBelow);
     }
-    ARGCHECK(fn != nullptr, "cudaRender: no instantiation of the renderer for this scene (csrc/rows)");
+    if (!frameReady(sceneInfo, objects))
+        return;
+    const int flight = takeFlight(sceneInfo, counting);
+    if (flight < 0)
+        return;
+    const hipStream_t stream = flightStream(flight);
+    SceneArgs S;
+    if (!frameScene(sceneInfo, objects, counting, S))
+        return;
+    FrameArgs F;
+    if (!frameArgs(sceneInfo, ppInfo, origin, direction, angles, F))
+        return;
+    const unsigned tiles = (unsigned)(F.tilesX * tileRows(F));
+    if (sceneInfo.cameraType == ctVR)
+        readFocusDepth(F, flight, stream);
+    if (g.tileClocks && !armTileClocks(F, tiles))
+        return;
+    bool streamIds = false;
+    const BandCuts streamCuts = decideStreamCuts(F, counting, &streamIds);
+    bool streamCandidate = streamCuts.bands > 0;
+    if (g.sched.mode > 0 && !counting && !scheduleTiles(F, tiles, flight, stream, streamCuts, &streamCandidate))
+        return;
+    const std::pair<hipEvent_t, hipEvent_t> timer = startKernelTimer(counting, stream);
+
+    const KernelChoice k = chooseKernel(sceneInfo, fullFeatures(sceneInfo), deepNodeList(S), counting);
+    if (!counting)
+        g.recordVariant = k.row;
+    ARGCHECK(k.fn != nullptr, "cudaRender: no instantiation of the renderer for this scene (csrc/rows)");
     if (!ok())
         return;
     /* (the census kernel adds into them; a frame's own kernel does not touch them: zeroing them on the stream of EVERY frame
@@ -561,79 +695,29 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
         HIPCHECK(hipMemsetAsync(g.counters.ptr, 0, 8 * sizeof(unsigned long long), stream));
     /* the ordered launch has a fixed number of extra workgroups for the quadrant waves of split tiles
      * (k_orderTiles); the ones the order does not use return at once */
-    F.nbTiles = (int)grid.x;
-    const dim3 launchGrid(F.tileOrder ? grid.x + (unsigned)(SPLIT_PARTS - 1) * SPLIT_TILES_MAX : grid.x);
-    if (g.recordNext && !counting)
-    {
-        /* this frame leaves a record of its walks (rt_device.h recordWalk; solr_hip_walk_bound): the same kernel with
-         * COUNT == 2, launched exactly as it would have been - grid, order, LDS - with the record buffer in place of the
-         * counters.  Only the lean rows of the table have such an instantiation. */
-        g.recordNext = false;
-        ARGCHECK(g.recordVariant >= 0 && g.recordVariant < 4,
-                 "solr_hip_walk_bound: the kernel this scene needs has no recording instantiation (untextured spheres, "
-                 "planes, triangles, cylinders only)");
-        if (!ok())
-            return;
-        reserve(g.walkRecords, (size_t)launchGrid.x * SOLR_WALK_SLOT_BYTES);
-        reserve(g.walkVisits, (size_t)launchGrid.x * WAVE * sizeof(unsigned) + 64);
-        if (!ok())
-            return;
-        HIPCHECK(hipMemsetAsync(g.walkRecords.ptr, 0, (size_t)launchGrid.x * SOLR_WALK_SLOT_BYTES, stream));
-        fn = solrrows::renderer(2, variants[g.recordVariant].features | ((deepList || g.recordVariant == 3) ? F_DEEP : 0), false);
-        ARGCHECK(fn != nullptr, "solr_hip_walk_bound: no recording instantiation");
-        if (!ok())
-            return;
-        cntPtr = (unsigned long long *)g.walkRecords.ptr;
-        g.recordGrid = launchGrid.x;
-        g.recordLds = ldsBytes;
-        g.recordDeep = deepList || g.recordVariant == 3;
-        g.recordScene = S;
-        g.recorded = true;
-    }
-    if (deepSlots > 0)
-    {
-        /* an F_STACK instantiation: SOLR_LDS_STACK_SLOTS slots in LDS - 16 waves per CU whatever the bounce limit - and
-         * the rest of this buffer set's frame in HBM, a plane of the strip per slot (3840 x 2160 x 7 slots: 0.9 GB of
-         * the 288; touched only by the rays that go that deep) */
-        F.stackSlots = SOLR_LDS_STACK_SLOTS;
-        ldsBytes = ((size_t)F.stackSlots * 4 + COLD_FIELDS) * WAVE * sizeof(float) + ldsPad;
-        F.deepStride = (long)sceneInfo.size.x * F.nbRows;
-        reserve(g.deepStack[flight], (size_t)deepSlots * (size_t)F.deepStride * sizeof(float4));
-        if (!ok())
-            return;
-        F.deepStack = (float4 *)g.deepStack[flight].ptr;
-        /* the deep slots are never zeroed: every slot a lane reads was written by the trip that made it (rt_device.h
-         * launchRayTracing).  Variant 10 proves it: NaNs in every slot before the launch, the same frame after */
-        if (g.variant == 10)
-            HIPCHECK(hipMemsetAsync(F.deepStack, 0xff, (size_t)deepSlots * (size_t)F.deepStride * sizeof(float4), stream));
-    }
-    /* (tiles in launch order, or band after band: an order by cost alone completes every band at the end; the epilogue that
-     * counts tiles is in instantiations of its own - the lean rows have them, rt_device.h F_STREAM) */
-    bool streamed = false;
-    const int streamMask = chosenMask | (deepSlots > 0 ? F_STACK : 0) | F_STREAM;
-    if (streamCandidate && cntPtr == (unsigned long long *)g.counters.ptr && chosenMask >= 0 &&
-        (!F.tileOrder || memcmp(&g.orderCuts, &streamCuts, sizeof(streamCuts)) == 0))
-        if (KernelFn streaming = solrrows::renderer(0, streamMask, false))
-            if (armImageStreaming(F, tilesY, stream, streamIds))
-            {
-                fn = streaming;
-                streamed = true;
-            }
-    g.lastMask = chosenMask;
-    if (streamed)
-        F.fuseDefault |= streamIds ? 6 : 2;
+    F.nbTiles = (int)tiles;
+    const dim3 grid(F.tileOrder ? tiles + (unsigned)(SPLIT_PARTS - 1) * SPLIT_TILES_MAX : tiles);
+    RendererFn fn = k.fn;
+    const bool recording = g.recordNext && !counting;
+    if (recording && !(fn = recordingKernel(k, S, grid.x, ldsBytesFor(F.stackSlots), stream)))
+        return;
+    unsigned long long *cntPtr = (unsigned long long *)(recording ? g.walkRecords.ptr : g.counters.ptr);
+    if (k.deepSlots > 0 && !armDeepStack(F, k.deepSlots, flight, stream))
+        return;
+    unsigned char *bitmap = (unsigned char *)(g.boundBitmap ? g.boundBitmap : flightBitmap(flight).ptr);
+    const bool streamed = streamCandidate && !recording && armStreamedFrame(F, k, streamCuts, stream, streamIds, &fn);
+    g.lastMask = k.mask;
     g.streamedIds = streamed && streamIds;
-    if (streamed && g.variant == 13) /* (tests: the waves write no band's word - the host goes by the end of the kernel) */
-        F.streamSerial = 0x7fffff00u;
     {
         HostSpan launch("  of which the kernel launch");
-        hipLaunchKernelGGL(fn, launchGrid, block, ldsBytes, stream, S, F, ppPtr, idPtr, bitmap, cntPtr);
+        hipLaunchKernelGGL(fn, grid, dim3(WAVE), ldsBytesFor(F.stackSlots), stream, S, F, (PixelRecord *)flightPp(flight).ptr,
+                           (int4 *)flightIds(flight).ptr, bitmap, cntPtr);
     }
     HIPCHECK(hipGetLastError());
-    if (e0)
+    if (timer.first)
     {
-        HIPCHECK(hipEventRecord(e1, stream));
-        g.events.push_back(std::make_pair(e0, e1));
+        HIPCHECK(hipEventRecord(timer.second, stream));
+        g.events.push_back(timer);
     }
     if (streamed)
     {
@@ -643,9 +727,8 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     }
 
     g.haloWanted = 0;
-    if (neighbourhood)
+    if (neighbourhoodPass(ppInfo))
         launchPostProcess(sceneInfo, ppInfo, flight, stream, F.firstRow, F.nbRows, bitmap, debt);
-
     if (counting && counts)
     {
         HIPCHECK(hipMemcpyAsync(counts, g.counters.ptr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost,

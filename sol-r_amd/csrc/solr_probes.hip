@@ -357,8 +357,8 @@ __global__ __launch_bounds__(64) void k_probeIntersectionShader(const SceneArgs 
 }
 
 /* ---- which instantiation ----------------------------------------------------------------------------------------
- * The lean instantiations the renderer launches for untextured scenes of the usual primitives (solr_launch.hip,
- * renderImpl's table, first four rows, each with the two-bank and the three-bank node loop) and the all-features one
+ * The lean instantiations the renderer launches for untextured scenes of the usual primitives (the LEAN_ROWS first rows of
+ * solrrows::ROWS, renderer.h, each with the two-bank and the three-bank node loop but the fourth) and the all-features one
  * that covers everything else here (the renderer has three more textured / special-camera rows between them). */
 constexpr int LEAN[4] = {F_SPHERE | F_PLANE, F_SPHERE | F_TRI, F_SPHERE | F_CYL, F_SPHERE | F_PLANE | F_TRI | F_CYL};
 constexpr int EVERYTHING = (F_ALL & ~F_FULL) | F_DEEP;

@@ -565,14 +565,14 @@ int solr_hip_strip_row_costs(float *rowCost, int height)
     if (!ready("solr_hip_strip_row_costs"))
         return -1;
     ARGCHECK(rowCost != nullptr && height == g.height, "solr_hip_strip_row_costs: rowCost[height of the frame]");
-    ARGCHECK(g.tileCost.ptr != nullptr && g.costFrames > 0 && g.costKey[0] > 0 && g.costKey[1] > 0,
+    ARGCHECK(g.sched.cost.ptr != nullptr && g.sched.frames > 0 && g.sched.key[0] > 0 && g.sched.key[1] > 0,
              "solr_hip_strip_row_costs: no frame has recorded tile costs (tile scheduling off?)");
     if (!ok())
         return -1;
     quiesce();
-    const int nbTiles = (int)g.costKey[0], tilesX = (int)g.costKey[1], firstRow = (int)g.costKey[2], nbRows = (int)g.costKey[3];
+    const int nbTiles = (int)g.sched.key[0], tilesX = (int)g.sched.key[1], firstRow = (int)g.sched.key[2], nbRows = (int)g.sched.key[3];
     std::vector<unsigned> cost((size_t)nbTiles);
-    HIPCHECK(hipMemcpy(cost.data(), g.tileCost.ptr, cost.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(cost.data(), g.sched.cost.ptr, cost.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
     if (!ok())
         return -1;
     for (int y = 0; y < height; ++y)
@@ -612,7 +612,7 @@ int solr_hip_balance_strips(void)
     const int height = g.height;
     std::vector<float> cost((size_t)std::max(height, 1), 0.f);
     /* a rank that has nothing to report (an empty strip, tile scheduling off, no frame yet) contributes zeros */
-    const bool recorded = mine && height > 0 && stripRows() > 0 && g.tileCost.ptr != nullptr && g.costFrames > 0 && g.costKey[0] > 0;
+    const bool recorded = mine && height > 0 && stripRows() > 0 && g.sched.cost.ptr != nullptr && g.sched.frames > 0 && g.sched.key[0] > 0;
     if (recorded && solr_hip_strip_row_costs(cost.data(), height) != 0)
     {
         mine = false;

@@ -6,7 +6,7 @@
  *   - the host side of the uploads: row conversion (scene_layout.h), material tags, texture tables, the walk-order list
  *     (chains collapsed, siblings grouped, inner nodes that hardly cull pruned) and the order-free lists, built on the
  *     device (solr_lists.hip) when they are due;
- *   - makeScene(): the SceneArgs a launch is handed.
+ *   - prepareScene(): the SceneArgs a frame's launch is handed.
  * Part of the engine's host side (engine.h); the boundary that calls into it is solr_hip.hip.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
@@ -438,7 +438,7 @@ int materialTag(const Material &m)
 
 /* What solr_hip_rotate_primitives refits and in which order: the nodes of a list by height, children
  * before parents.  A frame walks the walk-order list, so that is the one refitted with every rotation; the
- * reference's own list (box-debug view, census, variant 3, read-back) follows when somebody needs it
+ * reference's own list (box-debug view, census, VARIANT_EXACT_LIST, read-back) follows when somebody needs it
  * (refreshExactList) - node bounds are a function of the primitives alone, so late is as good as at once.
  * Both give a node of the reference's tree the same bounds: min / max over the level-0 boxes below it,
  * clamped once or several times by the same +-viewDistance seed, first occurrence winning a tie in either
@@ -925,7 +925,7 @@ void flushGeometry()
 bool orderFreeListsUsable()
 {
     return g.nbBoxesFree > 0 && g.freeRows == 16 * (size_t)g.nbBoxesFree && g.primsContained && !g.freeStale &&
-           g.nested && g.orderedCompact && g.variant != 6;
+           g.nested && g.orderedCompact && g.variant != VARIANT_NO_ORDER_FREE;
 }
 
 /* bounce rays on the order-free lists: the API's word, else SOLR_HIP_SHORT_RAY_LISTS=0|1 (experiments), else the engine's
@@ -941,7 +941,7 @@ bool shortRayListsChoice()
     return mode < 0 ? activeFlights() >= 2 : mode != 0;
 }
 
-SceneArgs makeScene(bool exactNodes)
+static SceneArgs makeScene(bool exactNodes)
 {
     SceneArgs S;
     memset(&S, 0, sizeof(S));
@@ -972,19 +972,42 @@ SceneArgs makeScene(bool exactNodes)
     }
     /* the thin copies behind the lists this frame walks (set by tightListsFor: they also depend on the frame) */
     S.tightLists = 0;
-    /* ... and the copies with sorted bounds behind those (variant 12: the walks take the lists as they are) */
-    S.sortedLists = (S.nbBoxesFree > 0 && g.sortedFree && g.variant != 12) ? 1 : 0;
+    /* ... and the copies with sorted bounds behind those (VARIANT_UNSORTED_LISTS: the walks take the lists as they are) */
+    S.sortedLists = (S.nbBoxesFree > 0 && g.sortedFree && g.variant != VARIANT_UNSORTED_LISTS) ? 1 : 0;
     return S;
 }
 
 /* may the walks of a frame with this SceneInfo take the thin copies of the lists S names (rt_device.h tightRay)? */
-int tightListsFor(const SceneArgs &S, const SceneInfo &sceneInfo, bool exactNodes)
+static int tightListsFor(const SceneArgs &S, const SceneInfo &sceneInfo, bool exactNodes)
 {
-    if (exactNodes || g.variant == 8 || !g.tightCompact || !sceneInfo.extendedGeometry)
+    if (exactNodes || g.variant == VARIANT_REFERENCE_LEAVES || !g.tightCompact || !sceneInfo.extendedGeometry)
         return 0;
     if (S.nbBoxesFree > 0 && !g.tightFree)
         return 0;
     return (sceneInfo.viewDistance > 0.f && sceneInfo.viewDistance <= 64.f * g.sceneExtent) ? 1 : 0;
+}
+
+/* The resident scene as a frame with this SceneInfo walks it (renderImpl; the probes, solrprobe::residentScene): pending
+ * uploads flushed, the order-free lists built when they are due, the reference's own node list refitted when it is the
+ * one wanted (exactNodes).  A failure is the engine's error (ok()). */
+SceneArgs prepareScene(const SceneInfo &sceneInfo, bool exactNodes)
+{
+    maybeBuildOrderFreeLists();
+    flushGeometry();
+    if (exactNodes)
+        refreshExactList();
+    if (!ok())
+        return SceneArgs();
+    SceneArgs S = makeScene(exactNodes);
+    S.tightLists = tightListsFor(S, sceneInfo, exactNodes);
+    return S;
+}
+
+/* a list of more than a thousand nodes does not live in the scalar cache: skips land on cold records, and the walks take
+ * the three-bank node loop (F_DEEP) */
+bool deepNodeList(const SceneArgs &S)
+{
+    return S.nbBoxes > 1024;
 }
 
 /* The texel fetch (rt_device.h fetchTexel, skyboxMapping) indexes the atlas with textureOffset + index % texels
