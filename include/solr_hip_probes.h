@@ -80,6 +80,18 @@ int solr_hip_probe_postprocess(const SceneInfo *sceneInfo, const PostProcessingI
 int solr_hip_probe_ticket(long long serial, int *slot, long long *period);
 long long solr_hip_probe_image_serial(long long setTo);
 
+/* k_orderTiles (sol-r_amd/csrc/solr_post.hip), the tile sort of the cost-ordered launch, over n tile costs of the caller's:
+ * `flights` as renderImpl passes it (0: the statistics only), and the bands of a streamed frame (bands = 0: by cost alone;
+ * otherwise firstTile[0 ... bands] in tiles, and the heaviest n / heavyShare tiles first).  order (n + 3 x 256 words),
+ * snapshot (n) and hostStats (8) are in/out: whatever the caller put there is what the kernel did not overwrite. */
+int solr_hip_probe_order_tiles(int n, const unsigned *cost, int flights, int bands, int heavyShare, const int *firstTile,
+                               unsigned *order, unsigned *snapshot, unsigned *hostStats);
+
+/* what the frame rendered last launched: {row of the renderer's table or -1, features of the instantiation (enum Feature
+ * of rt_device.h with F_DEEP, F_STACK, F_STREAM) or -1, streamed (1 / 0), its bands, cost-ordered launch (1 / 0), the
+ * bands of that order} */
+void solr_hip_probe_last_frame(int out[6]);
+
 /* vectorRefraction (VU:73-87) and vectorReflection (VU:61-64) */
 int solr_hip_probe_vectors(int n, const float *incident, const float *normals, const float *n1, const float *n2,
                            float *refracted, float *reflected);

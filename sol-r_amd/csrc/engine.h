@@ -323,6 +323,10 @@ struct Engine
     hipEvent_t streamRendered = nullptr; /* behind the kernel of the streamed frame rendered last */
     long streamedDelivered = 0;          /* images that left in bands */
     int lastMask = -1;                   /* features of the lean row the frame before took (-1: another kernel, or none yet) */
+    /* what the frame rendered last launched (solr_hip_probe_last_frame): its row of solrrows::ROWS (-1: none), the features of
+     * its instantiation with F_DEEP / F_STACK / F_STREAM, streamed (1 / 0) and in how many bands, cost-ordered (1 / 0) and
+     * the bands of that order */
+    int lastFrame[6] = {-1, -1, 0, 0, 0, 0};
     int streamSupport = -1;              /* 1 / 0; -1: not asked yet (SOLR_HIP_NO_IMAGE_STREAMING) */
 
     /* device-side rotation (solr_hip_rotate_primitives): what to refit, in which order */

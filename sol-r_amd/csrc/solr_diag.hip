@@ -103,6 +103,12 @@ int postProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, co
     HIPCHECK(hipStreamSynchronize(stream));
     return ok() ? 0 : -1;
 }
+
+/* what the frame rendered last launched (Engine::lastFrame, written by renderImpl) */
+void lastFrame(int out[6])
+{
+    memcpy(out, g.lastFrame, sizeof(g.lastFrame));
+}
 } // namespace solrprobe
 
 extern "C" {

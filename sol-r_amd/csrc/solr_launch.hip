@@ -708,6 +708,13 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     const bool streamed = streamCandidate && !recording && armStreamedFrame(F, k, streamCuts, stream, streamIds, &fn);
     g.lastMask = k.mask;
     g.streamedIds = streamed && streamIds;
+    if (!counting)
+    {
+        const int features = k.mask < 0 ? -1 : k.mask | (k.deepSlots > 0 ? F_STACK : 0) | (streamed ? F_STREAM : 0);
+        const int last[6] = {k.row, features, streamed ? 1 : 0, streamed ? streamCuts.bands : 0, F.tileOrder ? 1 : 0,
+                             F.tileOrder ? g.sched.orderCuts.bands : 0};
+        memcpy(g.lastFrame, last, sizeof(last));
+    }
     {
         HostSpan launch("  of which the kernel launch");
         hipLaunchKernelGGL(fn, grid, dim3(WAVE), ldsBytesFor(F.stackSlots), stream, S, F, (PixelRecord *)flightPp(flight).ptr,

@@ -15,6 +15,7 @@
 #include "../../include/solr_hip.h"
 #include "../../include/solr_hip_probes.h"
 #include "rt_device.h"
+#include "renderer.h"
 
 using namespace solrdev;
 
@@ -27,7 +28,15 @@ int ticketOfSerial(long long serial, int *slot, long long *period);
 long long imageSerial(long long setTo);
 int postProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, const PostProcessingBuffer *frame,
                 unsigned char *bitmapOut);
+void lastFrame(int out[6]);
 } // namespace solrprobe
+
+/* solr_post.hip: k_orderTiles behind its launcher, as renderImpl's scheduling stage calls it */
+namespace solrpost
+{
+void orderTiles(hipStream_t stream, const unsigned *cost, unsigned *snapshot, unsigned *order, int nbTiles,
+                volatile unsigned *hostStats, int flights, const BandCuts &cuts);
+} // namespace solrpost
 
 namespace
 {
@@ -538,6 +547,32 @@ int solr_hip_probe_ticket(long long serial, int *slot, long long *period)
 }
 
 long long solr_hip_probe_image_serial(long long setTo) { return solrprobe::imageSerial(setTo); }
+
+int solr_hip_probe_order_tiles(int n, const unsigned *cost, int flights, int bands, int heavyShare, const int *firstTile,
+                               unsigned *order, unsigned *snapshot, unsigned *hostStats)
+{
+    if (n <= 0 || flights < 0 || bands < 0 || bands > SOLR_STREAM_BANDS_MAX || (bands > 0 && !firstTile))
+    {
+        solrprobe::fail(-1, "solr_hip_probe_order_tiles: n > 0, flights >= 0, 0 <= bands <= 8 with bands + 1 first tiles");
+        return -1;
+    }
+    BandCuts cuts = {};
+    cuts.bands = bands;
+    cuts.heavyShare = heavyShare;
+    for (int b = 0; bands > 0 && b <= bands; ++b)
+        cuts.firstTile[b] = firstTile[b];
+    Arrays a;
+    const unsigned *dC = a.in(cost, (size_t)n);
+    unsigned *dO = a.out(order, (size_t)n + (SPLIT_PARTS - 1) * SPLIT_TILES_MAX);
+    unsigned *dS = a.out(snapshot, (size_t)n);
+    unsigned *dH = a.out(hostStats, 8);
+    if (a.failed)
+        return -1;
+    solrpost::orderTiles(0, dC, dS, dO, n, dH, flights, cuts);
+    return a.finish(0) ? 1 : -1;
+}
+
+void solr_hip_probe_last_frame(int out[6]) { solrprobe::lastFrame(out); }
 
 int solr_hip_probe_vectors(int n, const float *incident, const float *normals, const float *n1, const float *n2,
                            float *refracted, float *reflected)

@@ -50,8 +50,11 @@ def declare(hip):
     hip.solr_hip_probe_skybox.argtypes = [v, i, v, v, v]
     hip.solr_hip_probe_intersection_shader.argtypes = [v, i, v, v, v, v, v, v, v]
     hip.h2d_textures.argtypes = [C.c_uint64, i, v]
+    hip.solr_hip_probe_order_tiles.argtypes = [i, v, i, i, i, v, v, v, v]
+    hip.solr_hip_probe_last_frame.argtypes = [v]
+    hip.solr_hip_probe_last_frame.restype = None
     for name in ("box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "vectors",
-                 "make_color", "skybox", "intersection_shader"):
+                 "make_color", "skybox", "intersection_shader", "order_tiles"):
         getattr(hip, "solr_hip_probe_" + name).restype = i
     del P
 

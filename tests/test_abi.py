@@ -27,6 +27,15 @@ def test_every_declared_symbol_is_exported(solr):
     assert not missing, missing
 
 
+def test_every_declared_probe_is_exported(solr):
+    """the test-only entry points of include/solr_hip_probes.h, the tile sort and the last frame's launch among them"""
+    names = declared_functions("solr_hip_probes.h")
+    assert {"solr_hip_probe_order_tiles", "solr_hip_probe_last_frame", "solr_hip_probe_make_color"} <= set(names), names
+    lib = solr.hip_lib()
+    missing = [n for n in names if not hasattr(lib, n)]
+    assert not missing, missing
+
+
 def test_host_library_exports_the_flat_api(solr):
     lib = solr.host_lib()
     for n in ("SolR_SetSceneInfo", "SolR_SetPostProcessingInfo", "SolR_SetDraftMode", "SolR_InitializeKernel",

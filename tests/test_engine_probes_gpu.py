@@ -295,12 +295,16 @@ def test_the_probes_run_the_instantiations_the_renderer_launches(solr, probes, f
         assert E.engine_outputs(solr, case)["features"] == features, name
 
 
-def test_the_probe_entry_points_are_exported(solr):
-    """(CPU) include/solr_hip_probes.h is test-only, but what it declares must be in the library"""
+def test_all_fifteen_probe_entry_points_are_exported(solr):
+    """(CPU) include/solr_hip_probes.h is test-only, but what it declares must be in the library: the thirteen probes of
+    the device functions and the read-back tickets, and the two of the frame's launch (the tile sort, the last frame)"""
     import re
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "solr_hip_probes.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     names = sorted(set(re.findall(r"\b(solr_hip_probe_\w+)\s*\(", text)))
-    assert len(names) == 13
+    assert len(names) == 15
+    assert names == sorted("solr_hip_probe_" + n for n in (
+        "box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "image_serial", "vectors",
+        "make_color", "skybox", "intersection_shader", "order_tiles", "last_frame")), names
     hip = solr.hip_lib()
     assert all(hasattr(hip, n) for n in names), [n for n in names if not hasattr(hip, n)]
