@@ -405,7 +405,8 @@ void solr_hip_render_counting(const SceneInfo *sceneInfo, const vec4i *objects,
  * the copies of the order-free lists with sorted bounds (the node loop without its min / max, rt_device.h
  * SOLR_ORDER_SORTED); 13 = a streamed frame (solr_hip_stream_next_image) whose waves do not write the bands' words: the
  * host goes by the end of the kernel (solr_hip_d2h_streamed_image); 14 = the tile counters of streamed frames are zeroed
- * every third frame, as they are when a count nears 2^32.  Every setting renders the same frame. */
+ * every third frame, as they are when a count nears 2^32; 15 = the shadow walks in the reference's order keep the
+ * reference's cut-off alone (no lamp cut-off, rt_device.h shadowWalk).  Every setting renders the same frame. */
 void solr_hip_set_variant(int variant);
 /* Bounce rays (|direction| = 1 - rayEpsilon) of the long-list triangle kernels on the order-free lists, checked: lanes
  * whose hit has a rival the reference's cut-off could have preferred are walked again in the reference's order
@@ -418,6 +419,10 @@ int solr_hip_short_ray_lists(void);
 int solr_hip_order_free_nodes(void);
 /* 1 if the shadow walks take them as well (nothing in the scene is transparent or a textured plane), else 0 */
 int solr_hip_order_free_shadows(void);
+/* 1 if the shadow walks that keep the reference's order leave out the boxes that begin beyond the lamp (the walk-order
+ * list was found to hold what it names - every inner node its children, every leaf its primitives - at its upload and
+ * after every rotation on the device since; variant not 15), else 0 */
+int solr_hip_shadow_lamp_cutoff(void);
 int solr_hip_get_variant(void);
 
 /* Animated scenes.  The reference re-runs GPUKernel::rotatePrimitives (GPUKernel.cpp:1378-1460: rotate

@@ -166,6 +166,7 @@ enum Variant
     VARIANT_UNSORTED_LISTS = 12, /* no walk takes the copies of the order-free lists with sorted bounds */
     VARIANT_NO_BAND_WORDS = 13,  /* a streamed frame's waves write no band's word */
     VARIANT_ZERO_STREAM_COUNTERS = 14, /* the tile counters of streamed frames zeroed every third frame */
+    VARIANT_NO_LAMP_CUTOFF = 15  /* shadow walks in the reference's order keep the reference's cut-off alone */
 };
 
 struct Engine
@@ -199,6 +200,9 @@ struct Engine
     bool freeStale = false;     /* rotated on the device since it was built: not refitted, not walked */
     bool primsContained = false; /* every primitive lies inside its leaf's box (retagPrimitives) */
     bool opaqueShadows = false;  /* no transparent primitive, no textured plane (retagPrimitives) */
+    /* the walk-order list as the arena holds it: every inner node contains its children, every leaf its primitives
+     * (checked at h2d_scene and again after every rotation on the device; lampCutoffUsable) */
+    bool compactEncloses = false;
     /* the thin copies of the walk-order list and of the order-free lists (tightenList; rt_device.h tightRay) */
     bool plainPlanes = false;    /* the scene holds a plain axis plane: thin copies are worth making (retagPrimitives) */
     float sceneExtent = 1.f;     /* max |coordinate| + |size| over the primitives, at least 1 */
@@ -331,6 +335,7 @@ struct Engine
 
     /* device-side rotation (solr_hip_rotate_primitives): what to refit, in which order */
     DeviceBuffer movable, refitPlan;
+    DeviceBuffer enclosesFlag; /* k_listEncloses' answer */
     int nbMovable = -1;                 /* flags uploaded for that many primitives, -1: none */
     std::vector<int> refitLevels;       /* exact list: [offset, count] per height, offsets into refitPlan (ints) */
     std::vector<int> refitWalkLevels;   /* walk-order list, same form */
@@ -531,6 +536,7 @@ void flushGeometry();
 void refreshExactList();
 void dropFreeStage(bool originToo);
 bool orderFreeListsUsable();
+bool lampCutoffUsable();
 bool shortRayListsChoice();
 SceneArgs prepareScene(const SceneInfo &sceneInfo, bool exactNodes);
 bool deepNodeList(const SceneArgs &S);

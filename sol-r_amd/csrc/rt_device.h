@@ -2073,8 +2073,30 @@ SOLR_DEV float shadowWalk(const Scene &S, const SceneInfo &si, bool active, v3 l
      * against the view distance, hence the condition on it - never uses.  The list of the OPPOSITE octant, the
      * lamp's side first: for an any-hit query that measured best (mesh -5 %, molecule -2 %; the near side first
      * +10 % on the molecule: the point's own neighbourhood is where the boxes are entered and the tests miss). */
-    const bool freeOrder = tidy && S.nbBoxesFree > 0 && S.opaqueShadows &&
+    const bool freeOrder = tidy && S.nbBoxesFree > 0 && (S.opaqueShadows & SHADOWS_OPAQUE) &&
                            ballot(active && !(longRay(r.d) && minDistance >= 2.f)) == 0ull;
+    /* The lamp's cut-off in the reference's order.  A scene with glass keeps the reference's order and its accumulation
+     * (result += ratio, the early-out result < shadowIntensity): nothing of that is touched here.  But the walk need not
+     * enter the boxes that BEGIN BEYOND THE LAMP either, in any scene:
+     *   1. a hit counts only if l < lengthOL below, i.e. its parameter along the un-normalised direction is below 1;
+     *   2. it lies inside its leaf's box (the host's certificate, SHADOWS_LAMP_CUTOFF: every primitive of the list inside
+     *      its leaf's box) - in the thin copy inside the rectangle's box up to the margin, tightRay's argument, and the
+     *      thin copy is only walked by rays that argument holds for;
+     *   3. so that leaf's entry parameter is below farFree = 1.0002 + 1e-4 sum|o| / lengthOL, the margins of the
+     *      order-free cut-off above (2e-4 of the distance, 1e-4 of the origin's coordinates for the cancellation in
+     *      bound - origin; a zero direction component has the reciprocal 1 and, the origin inside that slab, an entry
+     *      parameter <= 0 on its axis);
+     *   4. every inner node contains its children (the certificate's other half; the thin copy's inner nodes are the
+     *      unions of their leaves), and the slab values are monotonic in the bounds: an inner node that is culled culls
+     *      only leaves that would have been culled themselves;
+     *   5. a leaf that is left out would have produced only hits that l < lengthOL rejects, and a rejected hit leaves no
+     *      trace: the same result, the same color, the lane done after the same leaf.
+     * The reference's own cut-off - the parameter against the view distance, thousands against 1 - stays where it is
+     * the tighter one (fminf), and lanes whose ray the order-free path would not take (shorter than 2, a view distance
+     * under 2) keep it alone: per lane, `far` is a vector operand of the node loop anyway.  In the Cornell room the lamp
+     * hangs in mid-air, and every shadow ray prolonged beyond it entered a wall's leaf and made its plane test for a
+     * hit that was thrown away (solr_hip_set_variant(15) walks without). */
+    const bool lampCut = tidy && !freeOrder && (S.opaqueShadows & SHADOWS_LAMP_CUTOFF);
     Scene W = S;
     float farFree = 0.f;
     int octant = 0;
@@ -2090,8 +2112,12 @@ SOLR_DEV float shadowWalk(const Scene &S, const SceneInfo &si, bool active, v3 l
         W.offBoxes = S.offBoxesFree + 2u * (unsigned)(octant * S.nbBoxesFree);
         W.offLeaf = S.offLeafFree + 4u * (unsigned)(octant * S.nbBoxesFree);
         W.nbBoxes = S.nbBoxesFree;
-        farFree = 1.0002f + 1.0e-4f * (fabsf(r.o.x) + fabsf(r.o.y) + fabsf(r.o.z)) / lengthOL;
     }
+    if (freeOrder || lampCut)
+        farFree = 1.0002f + 1.0e-4f * (fabsf(r.o.x) + fabsf(r.o.y) + fabsf(r.o.z)) / lengthOL;
+    /* the cut-off of the walks in the reference's order (the order-free ones take farFree as it is) */
+    const float farOrdered =
+        (lampCut && longRay(r.d) && minDistance >= 2.f) ? fminf(minDistance, farFree) : minDistance;
     /* the thin copy of that list (tightRay: a shadow ray reaches from the point to the lamp, thousands of units) */
     const bool tight = (FEAT & F_PLANE) && tidy && S.tightLists && ballot(active && !tightRay(r, si)) == 0ull;
     if (tight)
@@ -2127,7 +2153,7 @@ SOLR_DEV float shadowWalk(const Scene &S, const SceneInfo &si, bool active, v3 l
                 leaf = leaf < 0 ? leaf : leaf >> 5;
             }
             else
-                leaf = advanceTidy<FEAT>(W, pr, freeOrder ? farFree : minDistance, cursor, cur, nbPrimitives, entered);
+                leaf = advanceTidy<FEAT>(W, pr, freeOrder ? farFree : farOrdered, cursor, cur, nbPrimitives, entered);
             SOLR_T(const unsigned long long tb = SOLR_NOW(); cnt.tNode += tb - ta; ++cnt.nAdvance; ta = tb;)
             if (leaf < 0)
                 break;
@@ -2271,7 +2297,7 @@ SOLR_DEV float shadowWalk(const Scene &S, const SceneInfo &si, bool active, v3 l
         SOLR_T(cnt.tLeaf += SOLR_NOW() - ta; ++cnt.nLeaf;)
     }
     if (COUNT == 2)
-        recordWalk(cnt, tidy ? WALK_SHADOW : WALK_GENERAL, freeOrder, octant, walked, r, freeOrder ? farFree : minDistance,
+        recordWalk(cnt, tidy ? WALK_SHADOW : WALK_GENERAL, freeOrder, octant, walked, r, freeOrder ? farFree : farOrdered,
                    doneAfter, tight, reversed ? 2 : 0);
     result = fmaxf(0.f, fminf(result, si.shadowIntensity));
     SOLR_T(cnt.tShadow += SOLR_NOW() - tw0;)

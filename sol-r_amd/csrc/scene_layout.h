@@ -134,6 +134,17 @@ enum PrimRow
     PRIM_ROWS = 8
 };
 
+/* SceneArgs::opaqueShadows, bit by bit (one word: the shadow walk reads it once, and the renderer kernels have no
+ * scalar register to spare for a second one) */
+enum ShadowFacts
+{
+    SHADOWS_OPAQUE = 1,     /* no primitive is transparent or a textured plane: any occluder saturates a shadow, and
+                             * the order-free lists exist (rt_device.h shadowWalk, freeOrder) */
+    SHADOWS_LAMP_CUTOFF = 2 /* the walk-order list holds what it names: every inner node contains its children, every
+                             * leaf its primitives - a shadow walk in the reference's order may leave out the boxes that
+                             * begin beyond the lamp (rt_device.h shadowWalk, lampCut; solr_scene.hip lampCutoffUsable) */
+};
+
 /* What the host passes to the kernel. Offsets are in rows of 16 bytes from the
  * arena base (offBoxStart: in ints). */
 struct SceneArgs
@@ -154,7 +165,7 @@ struct SceneArgs
     /* the order-free list (closest-hit walks of rays longer than 2, rt_device.h): 0 nodes when there is none */
     unsigned offBoxesFree, offLeafFree;
     int nbBoxesFree;
-    int opaqueShadows; /* no primitive is transparent or a textured plane: any occluder saturates a shadow */
+    int opaqueShadows; /* enum ShadowFacts: what the host has established for the shadow walks of the lists it names */
     int shortRayLists; /* bounce rays (shorter than 1) take the order-free lists, checked (rt_device.h closestHitWalk) */
     /* behind the walk-order list and behind the eight order-free lists lies a copy of their node rows in which every
      * leaf that holds nothing but plain axis planes is as thin as its planes (solr_scene.hip tightenList): long rays with
@@ -200,7 +211,7 @@ struct Scene
     unsigned offLeaf;
     unsigned offBoxesFree, offLeafFree;
     int nbBoxesFree;
-    int opaqueShadows;
+    int opaqueShadows; /* enum ShadowFacts */
     int shortRayLists;
     int tightLists;
     int sortedLists;

@@ -512,6 +512,13 @@ extern "C" int solr_hip_order_free_shadows(void)
     return (g.initialized && orderFreeListsUsable() && g.opaqueShadows) ? 1 : 0;
 }
 
+/* Extension: 1 if shadow walks in the reference's order leave out the boxes that begin beyond the lamp (rt_device.h
+ * shadowWalk, lampCut), else 0. */
+extern "C" int solr_hip_shadow_lamp_cutoff(void)
+{
+    return (g.initialized && lampCutoffUsable()) ? 1 : 0;
+}
+
 #ifdef SOLR_TIMING
 /* development build only (tools/wave_time_split.py): shader-clock cycles summed over the waves of every frame
  * since the last reset - [0] whole kernel, [1] closest-hit walks, [2] shadow walks, [3] node loop, [4] leaves,

@@ -251,7 +251,7 @@ static void finalizeOne()
     collectEvents();
     DeviceBuffer *all[] = {&g.geometry, &g.materials, &g.textures, &g.randoms, &g.lamps,
                            &g.pp,       &g.ids,       &g.bitmap,   &g.counters, &g.tileClock,
-                           &g.movable,  &g.refitPlan,
+                           &g.movable,  &g.refitPlan, &g.enclosesFlag,
                            &g.walkRecords, &g.walkVisits};
     for (DeviceBuffer *b : all)
         release(*b);
@@ -287,6 +287,7 @@ static void finalizeOne()
     g.hostOriginFree.clear();
     g.exactStale = false;
     g.deviceAhead = false;
+    g.compactEncloses = false;
     g.nbMovable = -1;
     g.nbDeviceRotations = 0;
     g.nbBoxes = g.nbPrimitives = g.nbLights = g.nbLamps = g.nbMaterials = 0;

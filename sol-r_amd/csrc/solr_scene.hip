@@ -928,6 +928,15 @@ bool orderFreeListsUsable()
            g.nested && g.orderedCompact && g.variant != VARIANT_NO_ORDER_FREE;
 }
 
+/* shadow walks in the reference's order may leave out the boxes that begin beyond the lamp (rt_device.h shadowWalk,
+ * lampCut): the walk-order list is nested and ordered, it holds what it names (checked where it was built or last
+ * refitted; its thin copy is made from it, leaves cut out of its leaves, inner nodes their unions), and no primitive
+ * reaches beyond what the check takes for its extent (retagPrimitives) */
+bool lampCutoffUsable()
+{
+    return g.compactEncloses && g.primsContained && g.nested && g.orderedCompact && g.variant != VARIANT_NO_LAMP_CUTOFF;
+}
+
 /* bounce rays on the order-free lists: the API's word, else SOLR_HIP_SHORT_RAY_LISTS=0|1 (experiments), else the engine's
  * own choice for this frame */
 bool shortRayListsChoice()
@@ -967,9 +976,11 @@ static SceneArgs makeScene(bool exactNodes)
         S.offBoxesFree = g.offBoxesFree;
         S.offLeafFree = g.offLeafFree;
         S.nbBoxesFree = g.nbBoxesFree; /* per list; the eight lists and their leaf records lie one behind the other */
-        S.opaqueShadows = g.opaqueShadows ? 1 : 0;
+        S.opaqueShadows = g.opaqueShadows ? SHADOWS_OPAQUE : 0;
         S.shortRayLists = shortRayListsChoice() ? 1 : 0;
     }
+    if (!exactNodes && lampCutoffUsable())
+        S.opaqueShadows |= SHADOWS_LAMP_CUTOFF;
     /* the thin copies behind the lists this frame walks (set by tightListsFor: they also depend on the frame) */
     S.tightLists = 0;
     /* ... and the copies with sorted bounds behind those (VARIANT_UNSORTED_LISTS: the walks take the lists as they are) */
@@ -1487,59 +1498,17 @@ static int buildFreeOrderLists(const std::vector<float4> &rows, const std::vecto
     return count;
 }
 
-/* The scene has been rendered `freeCountdown` times since its upload: build the order-free lists now, from the
- * host images of the reference's list and the primitives as they are (brought up to date first if rotations ran
- * on the device), after checking what their use rests on - every inner node encloses its children, every leaf
- * holds its primitives (the reference's builder makes it so, GPUKernel.cpp:741-830; another host's boxes are
- * taken at their word only after this check; the types whose extent is not what the builder adds around p0 -
- * cones, ellipsoids ... - are sorted out by retagPrimitives). */
-void maybeBuildOrderFreeLists()
+/* Does a nested node list hold what it names: every inner node its direct children (hence everything below it), every
+ * leaf its primitives, as the reference's builder makes it so (GPUKernel.cpp:741-830)?  The host's form of
+ * k_listEncloses, the same float arithmetic; `prims`: PRIM_ROWS rows per primitive, tagged or not. */
+static bool listEnclosesOnHost(const std::vector<float4> &rows, const std::vector<int> &start, const std::vector<float4> &prims)
 {
-    if (g.freeCountdown <= 0 || --g.freeCountdown > 0)
-        return;
-    if (!g.primsContained)
-    {
-        g.freeCountdown = 1; /* no walk would take them (orderFreeListsUsable): asked again with the next frame */
-        return;
-    }
-    PhaseTimer phase;
-    quiesce();
-    pullGeometry();
-    if (!ok())
-        return;
-    phase.mark("order-free: host images");
-    const std::vector<float4> &rows = g.hostBoxes;
-    const std::vector<int> &start = g.hostBoxStart;
     const int n = (int)start.size();
-    if (n < 2 || rows.size() != 2 * (size_t)n || n > 16000000) /* (beyond that the eight lists pass a dozen GB) */
-        return;
+    if (rows.size() < 2 * (size_t)n)
+        return false;
     auto skipOf = [&](int i) { return std::max(bitsi(rows[2 * i + 1].w), 1); };
     bool encloses = true;
-    /* with the arena laid out as the host images are (the usual case: the scene has been rendered once), the checks
-     * and the builder read the exact list and the primitive records there */
-    const bool fromArena = !g.geometryDirty && g.geometry.ptr != nullptr && !g.exactStale && !g.deviceAhead &&
-                           !getenv("SOLR_HIP_LISTS_ON_HOST") && !getenv("SOLR_HIP_LISTS_VIA_HOST") && !getenv("SOLR_HIP_FREE_WIDE");
-    const float4 *arena = (const float4 *)g.geometry.ptr;
-    if (fromArena)
-    {
-        HIPCHECK(hipSetDevice(g.device));
-        int *bad = nullptr, found = 1;
-        HIPCHECK(hipMalloc((void **)&bad, sizeof(int)));
-        if (ok())
-        {
-            HIPCHECK(hipMemsetAsync(bad, 0, sizeof(int), g.stream));
-            hipLaunchKernelGGL(k_listEncloses, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, arena, g.offBoxes, g.offBoxStart,
-                               g.offPrims, n, (int)(g.hostPrims.size() / PRIM_ROWS), bad);
-            HIPCHECK(hipGetLastError());
-            HIPCHECK(hipMemcpyAsync(&found, bad, sizeof(int), hipMemcpyDeviceToHost, g.stream));
-            HIPCHECK(hipStreamSynchronize(g.stream));
-            (void)hipFree(bad);
-        }
-        if (!ok())
-            return;
-        encloses = found == 0;
-    }
-    for (int i = 0; i < n && encloses && !fromArena; ++i)
+    for (int i = 0; i < n && encloses; ++i)
     {
         const int end = std::min(i + skipOf(i), n);
         if (bitsi(rows[2 * i + 1].z) > 0 || end <= i + 1)
@@ -1549,8 +1518,8 @@ void maybeBuildOrderFreeLists()
                        rows[2 * j + 1].x <= rows[2 * i + 1].x && rows[2 * j + 1].y <= rows[2 * i + 1].y &&
                        rows[2 * j].w <= rows[2 * i].w;
     }
-    const size_t nbPrims = g.hostPrims.size() / PRIM_ROWS;
-    for (int i = 0; i < n && encloses && !fromArena; ++i)
+    const size_t nbPrims = prims.size() / PRIM_ROWS;
+    for (int i = 0; i < n && encloses; ++i)
     {
         const int count = bitsi(rows[2 * i + 1].z);
         for (int k = 0; k < count && encloses; ++k)
@@ -1561,7 +1530,7 @@ void maybeBuildOrderFreeLists()
                 encloses = false;
                 break;
             }
-            const float4 *r = &g.hostPrims[PRIM_ROWS * pi];
+            const float4 *r = &prims[PRIM_ROWS * pi];
             const int type = bitsi(r[ROW_P0_TYPE].w) & PRIM_TYPE_MASK;
             float lo[3] = {r[ROW_P0_TYPE].x, r[ROW_P0_TYPE].y, r[ROW_P0_TYPE].z};
             float hi[3] = {lo[0], lo[1], lo[2]};
@@ -1593,6 +1562,60 @@ void maybeBuildOrderFreeLists()
                        rows[2 * i + 1].y >= hi[1] + fabsf(grow[1]) - ey && rows[2 * i].w >= hi[2] + fabsf(grow[2]) - ez;
         }
     }
+    return encloses;
+}
+
+/* ... and the same question for a list of the arena as it is now (k_listEncloses); waits for the stream */
+static bool listEnclosesInArena(unsigned offNodes, unsigned offStart, int n)
+{
+    HIPCHECK(hipSetDevice(g.device));
+    reserve(g.enclosesFlag, sizeof(int));
+    if (!ok())
+        return false;
+    int found = 1;
+    HIPCHECK(hipMemsetAsync(g.enclosesFlag.ptr, 0, sizeof(int), g.stream));
+    hipLaunchKernelGGL(k_listEncloses, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, (const float4 *)g.geometry.ptr, offNodes,
+                       offStart, g.offPrims, n, (int)(g.hostPrims.size() / PRIM_ROWS), (int *)g.enclosesFlag.ptr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(&found, g.enclosesFlag.ptr, sizeof(int), hipMemcpyDeviceToHost, g.stream));
+    HIPCHECK(hipStreamSynchronize(g.stream));
+    return ok() && found == 0;
+}
+
+/* The scene has been rendered `freeCountdown` times since its upload: build the order-free lists now, from the
+ * host images of the reference's list and the primitives as they are (brought up to date first if rotations ran
+ * on the device), after checking what their use rests on - every inner node encloses its children, every leaf
+ * holds its primitives (the reference's builder makes it so, GPUKernel.cpp:741-830; another host's boxes are
+ * taken at their word only after this check; the types whose extent is not what the builder adds around p0 -
+ * cones, ellipsoids ... - are sorted out by retagPrimitives). */
+void maybeBuildOrderFreeLists()
+{
+    if (g.freeCountdown <= 0 || --g.freeCountdown > 0)
+        return;
+    if (!g.primsContained)
+    {
+        g.freeCountdown = 1; /* no walk would take them (orderFreeListsUsable): asked again with the next frame */
+        return;
+    }
+    PhaseTimer phase;
+    quiesce();
+    pullGeometry();
+    if (!ok())
+        return;
+    phase.mark("order-free: host images");
+    const std::vector<float4> &rows = g.hostBoxes;
+    const std::vector<int> &start = g.hostBoxStart;
+    const int n = (int)start.size();
+    if (n < 2 || rows.size() != 2 * (size_t)n || n > 16000000) /* (beyond that the eight lists pass a dozen GB) */
+        return;
+    /* with the arena laid out as the host images are (the usual case: the scene has been rendered once), the checks
+     * and the builder read the exact list and the primitive records there */
+    const bool fromArena = !g.geometryDirty && g.geometry.ptr != nullptr && !g.exactStale && !g.deviceAhead &&
+                           !getenv("SOLR_HIP_LISTS_ON_HOST") && !getenv("SOLR_HIP_LISTS_VIA_HOST") && !getenv("SOLR_HIP_FREE_WIDE");
+    const float4 *arena = (const float4 *)g.geometry.ptr;
+    const bool encloses = fromArena ? listEnclosesInArena(g.offBoxes, g.offBoxStart, n) : listEnclosesOnHost(rows, start, g.hostPrims);
+    if (!ok())
+        return;
     if (!encloses)
     {
         if (getenv("SOLR_HIP_DEBUG_TREE"))
@@ -2030,6 +2053,11 @@ void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primi
     g.nbBoxesFree = nbFreeNodes;
     g.freeStale = false;
     g.hostPrims.swap(prims);
+    /* the lamp's cut-off of the shadow walks rests on this (lampCutoffUsable): another host's boxes are taken at their
+     * word only after the check */
+    g.compactEncloses = g.nested && g.orderedCompact && nbWalkNodes > 0 &&
+                        listEnclosesOnHost(g.hostBoxesCompact, g.hostBoxStartCompact, g.hostPrims);
+    phase.mark("h2d_scene: enclosure check");
     retagPrimitives();
     phase.mark("h2d_scene: tags");
     HIPCHECK(hipSetDevice(g.device));
@@ -2116,6 +2144,10 @@ int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const f
     else
         g.freeStale = g.nbBoxesFree > 0; /* no plan: rotated scenes walk the reference's order until the next upload */
     buildLeafRecords(); /* the leaves' copies of their first primitive follow the primitives */
+    /* the refitted list encloses by construction (k_refitNodes); asked all the same, like any list the walks cut off at
+     * the lamp (a scene that failed the check at its upload is not asked again) */
+    if (g.compactEncloses)
+        g.compactEncloses = listEnclosesInArena(g.offBoxesCompact, g.offBoxStartCompact, g.nbBoxesCompact);
     g.exactStale = true;
     g.exactStaleViewDistance = viewDistance;
     HIPCHECK(hipGetLastError());
