@@ -261,6 +261,31 @@ int solr_hip_build_tree(const Primitive *primitives, const unsigned char *emissi
                         int boxCapacity, int *order, int *nbBoxes, int *nbLamps);
 const char *solr_hip_build_tree_message(void);
 
+/* The pixel stage of the JPEG texture loader on the device (sol-r_amd/csrc/solr_textures.hip; the arithmetic is
+ * sol-r_amd/csrc/jpeg_pixels.h, the reference decoder's, solr/images/jpgd.cpp, bit for bit).  The host has parsed the
+ * file and decoded its Huffman stream (sol-r_amd/host/ImageLoader.cpp); the device dequantises, runs the inverse DCTs,
+ * upsamples the chroma and converts to RGB.
+ *   frame          size, luma sampling factors (1x1, 2x1 or 2x2; chroma is 1x1), the MCU grid, and the quantisation
+ *                  tables of Y, Cb, Cr in natural (row-major) order
+ *   coefficients   nbBlocks blocks of 64 coefficients in MCU order - inside an MCU the luma blocks row by row, then
+ *                  Cb, then Cr - in natural order inside a block, not yet dequantised
+ *   nbBlocks       must be mcusPerRow * mcuRows * (lumaH * lumaV + 2)
+ *   rgb            the caller's host buffer of width * height * 3 bytes; receives the texture as the reference stores
+ *                  it: turned by 180 degrees (pixel order reversed, R, G, B kept), MCUs clipped to width x height
+ * Synchronous; runs on the device of solr_hip_get_device() on a stream of its own, with or without an initialised
+ * scene, and gives its device buffers back before it returns.  0, or -1 with the error set (bad arguments are refused
+ * before anything is launched). */
+typedef struct
+{
+    int width, height, lumaH, lumaV, mcusPerRow, mcuRows;
+    unsigned short quant[3][64];
+} SolrJpegFrame;
+#define SOLR_JPEG_MAX_SIDE 16384
+#define SOLR_JPEG_MAX_PIXELS (1L << 26)
+int solr_hip_jpeg_to_rgb(const SolrJpegFrame *frame, const short *coefficients, long nbBlocks, unsigned char *rgb);
+/* 8x8 output blocks (after chroma upsampling: 3, 4 or 12 per MCU) the device has produced since the library was loaded */
+unsigned long long solr_hip_jpeg_blocks(void);
+
 /* Device pointers of the current per-pixel buffers (strip-sized), for
  * collectives issued by the launcher (RCCL gather of the RGB strip). */
 void *solr_hip_device_bitmap(void);

@@ -78,6 +78,12 @@ class Vec4i(C.Structure):
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("z", C.c_int), ("w", C.c_int)]
 
 
+class JpegFrame(C.Structure):
+    """SolrJpegFrame of include/solr_hip.h: what solr_hip_jpeg_to_rgb is told about the coefficient blocks"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("lumaH", C.c_int), ("lumaV", C.c_int),
+                ("mcusPerRow", C.c_int), ("mcuRows", C.c_int), ("quant", (C.c_ushort * 64) * 3)]
+
+
 assert C.sizeof(SceneInfo) == 112 and C.sizeof(PostProcessingInfo) == 16
 
 # ---- numpy views of the flattened arrays --------------------------------------
@@ -229,6 +235,9 @@ def _declare_hip(L):
     L.solr_hip_read_nodes.restype = C.c_int
     L.solr_hip_read_primitives.argtypes = [C.c_void_p, C.c_int]
     L.solr_hip_read_primitives.restype = C.c_int
+    L.solr_hip_jpeg_to_rgb.argtypes = [P(JpegFrame), C.c_void_p, C.c_long, C.c_void_p]
+    L.solr_hip_jpeg_to_rgb.restype = C.c_int
+    L.solr_hip_jpeg_blocks.restype = C.c_ulonglong
     # the by-value reference entry points are exercised from C++ (host/HipKernel.cpp);
     # ctypes cannot 16-byte align a by-value struct, so they get no argtypes here
     L.h2d_scene.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -266,6 +275,8 @@ def _declare_host(L):
     L.SolR_SetTexture.argtypes = [i, C.c_void_p, i, i, i, i]
     L.SolR_GetTextureSize.argtypes = [i, P(i), P(i), P(i)]
     L.SolR_GetNbTextures.argtypes = [P(i)]
+    L.SolR_LoadTextureFromFile.argtypes = [i, C.c_char_p]
+    L.SolRx_GetTextureType.argtypes = [i]
     L.SolRx_SelectEngine.argtypes = [C.c_char_p]
     L.SolRx_SetDeterministic.argtypes = [C.c_long]
     L.SolRx_LastError.argtypes = [C.c_char_p, i]
@@ -425,6 +436,12 @@ class Kernel:
         h, w, d = a.shape
         if self.L.SolR_SetTexture(index, a.ctypes.data, w, h, d, texture_type) != 0:
             raise SolrError("SolR_SetTexture failed")
+
+    def load_texture(self, index, path):
+        """A .bmp, .tga or .jpg file into texture slot `index` (reference: GPUKernel::loadTextureFromFile via
+        SolR_LoadTextureFromFile); the texture's type follows the file's name.  With the HIP engine a JPEG file's
+        pixels are decoded on the device.  True when the file loaded; the slot is left alone otherwise."""
+        return self.L.SolR_LoadTextureFromFile(index, os.fsencode(path)) == 1
 
     def compact_boxes(self, reconstruct=True):
         return self.L.SolR_CompactBoxes(reconstruct)

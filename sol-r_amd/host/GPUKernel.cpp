@@ -8,6 +8,7 @@
  * project's own.
  */
 #include "GPUKernel.h"
+#include "ImageLoader.h"
 
 #include <chrono>
 #include <cstdio>
@@ -152,6 +153,7 @@ void GPUKernel::cleanup()
     m_lightInformation.clear();
     m_nbActiveMaterials = -1;
     m_nbActiveTextures = 0;
+    m_textureFilenames.clear();
     m_materialsTransfered = false;
     m_primitivesTransfered = false;
     m_texturesTransfered = false;
@@ -1004,6 +1006,7 @@ void GPUKernel::resetAll()
         delete[] m_hTextures[i].buffer;
     memset(m_hTextures, 0, sizeof(m_hTextures));
     m_nbActiveTextures = 0;
+    m_textureFilenames.clear();
     m_texturesTransfered = false;
 }
 
@@ -1324,6 +1327,87 @@ void GPUKernel::getTexture(const int index, TextureInfo &textureInfo)
 }
 
 TextureInfo &GPUKernel::getTextureInformation(const int index) { return m_hTextures[index]; }
+
+/* reference: GPUKernel.cpp:2110-2161 */
+bool GPUKernel::loadTextureFromFile(const int index, const std::string &filename)
+{
+    std::string why;
+    Image image;
+    bool result = false;
+    if (filename.empty())
+        why = "empty file name";
+    else if (index < 0 || index >= NB_MAX_TEXTURES)
+        why = "texture slot out of range";
+    else if (filename.find(".bmp") != std::string::npos)
+        result = ImageLoader::loadBMP24(filename, image, why);
+    else if (filename.find(".jpg") != std::string::npos)
+    {
+        SolrJpegFrame frame;
+        std::vector<short> coefficients;
+        if (ImageLoader::parseJPEG(filename, frame, coefficients, why))
+        {
+            image.width = frame.width;
+            image.height = frame.height;
+            image.depth = 3;
+            image.pixels.resize((size_t)frame.width * frame.height * 3);
+            result = jpegPixels(frame, coefficients, image.pixels.data());
+            if (!result)
+                why = "the engine's pixel stage failed";
+        }
+    }
+    else if (filename.find(".tga") != std::string::npos)
+        result = ImageLoader::loadTGA(filename, image, why);
+    else
+        why = "neither .bmp, .jpg nor .tga";
+    if (!result)
+    {
+        std::cerr << "GPUKernel::loadTextureFromFile: failed to load " << filename << ": " << why << std::endl;
+        return false;
+    }
+
+    TextureInfo &texture = m_hTextures[index];
+    delete[] texture.buffer;
+    texture.buffer = new BitmapBuffer[image.pixels.size()];
+    memcpy(texture.buffer, image.pixels.data(), image.pixels.size());
+    texture.offset = 0;
+    texture.size.x = image.width;
+    texture.size.y = image.height;
+    texture.size.z = image.depth;
+    m_textureFilenames[index] = filename;
+    texture.type = tex_diffuse;
+    if (filename.find("b.") != std::string::npos)
+        texture.type = tex_bump;
+    if (filename.find("n.") != std::string::npos)
+        texture.type = tex_normal;
+    if (filename.find("a.") != std::string::npos)
+        texture.type = tex_ambient_occlusion;
+    if (filename.find("r.") != std::string::npos)
+        texture.type = tex_reflective;
+    if (filename.find("s.") != std::string::npos)
+        texture.type = tex_specular;
+    if (filename.find("t.") != std::string::npos)
+        texture.type = tex_transparent;
+    ++m_nbActiveTextures;
+    m_texturesTransfered = false;
+    /* Not in the reference, which leaves the new slot's offset at 0 until some material change makes the engine realign
+     * (CudaKernel.cpp:214-230): a texture loaded between two frames would then be packed over the first one in the
+     * atlas.  As setTexture does: every slot gets its place now, and the materials follow with the next frame */
+    realignTexturesAndMaterials();
+    m_materialsTransfered = false;
+    return true;
+}
+
+std::string GPUKernel::getTextureFilename(const int index)
+{
+    const std::map<int, std::string>::const_iterator it = m_textureFilenames.find(index);
+    return it == m_textureFilenames.end() ? std::string() : it->second;
+}
+
+bool GPUKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb)
+{
+    ImageLoader::jpegPixelsOnHost(frame, coefficients.data(), rgb);
+    return true;
+}
 
 /* reference: GPUKernel.cpp:2691-2705 */
 void GPUKernel::processTextureOffsets()

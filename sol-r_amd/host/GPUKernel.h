@@ -9,8 +9,8 @@
  * render_begin / render_end / getBitmap frame protocol.  Method names,
  * argument order and the dirty-flag protocol (GPUKernel.h:371-374,387) are the
  * reference's, so code written against the reference class reads the same
- * here.  Out of scope (and absent): file loaders, fake-GL vertex assembly,
- * Kinect/Oculus hooks, JPEG screenshots.
+ * here.  Out of scope (and absent): fake-GL vertex assembly, Kinect/Oculus
+ * hooks, JPEG screenshots.
  *
  * The flattened arrays this class produces (BoundingBox[], Primitive[],
  * Lamp[], LightInformation[], Material[]) are bit-for-bit what the reference
@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/solr_hip.h"
 #include "../../include/solr_types.h"
 
 namespace solr
@@ -380,6 +381,12 @@ public:
     void realignTexturesAndMaterials();
     void processTextureOffsets();
     TextureInfo &getTextureInformation(const int index);
+    /* reference: GPUKernel.h:204, GPUKernel.cpp:2110-2161.  A .bmp, .jpg or .tga file (chosen by that substring of the
+     * name) into slot `index`; the texture's type from the b. / n. / a. / r. / s. / t. substrings of the name, the
+     * last match winning.  An empty name or a file that does not load gives false, one line on stderr, and leaves
+     * the slot and the counters as they were (host/ImageLoader.h has the readers) */
+    bool loadTextureFromFile(const int index, const std::string &filename);
+    std::string getTextureFilename(const int index);
 
     /* ---------- Scene (GPUKernel.h:208-221) ---------- */
     void setSceneInfo(int width, int height, float transparentColor, int graphicsLevel, float viewDistance,
@@ -521,6 +528,10 @@ protected:
     void buildLevelsOnHost();
     /* engine hook: apply the rotation to the resident scene; false = not done, nothing changed */
     virtual bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) { return false; }
+    /* engine hook: the pixel stage of a JPEG texture (csrc/jpeg_pixels.h) - coefficient blocks as
+     * ImageLoader::parseJPEG leaves them to frame.width * frame.height * 3 bytes in `rgb`.  Here: a loop on the CPU;
+     * false = the engine failed (its error is pending) */
+    virtual bool jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb);
     void rotatePrimitivesOnly(Frame &f, const vec3f &rotationCenter, const vec3f &cosA, const vec3f &sinA);
     void refitBoxes(Frame &f);
 
@@ -547,6 +558,7 @@ protected:
     std::vector<unsigned char> m_hMovable;
     std::vector<Material> m_hMaterials;
     TextureInfo m_hTextures[NB_MAX_TEXTURES];
+    std::map<int, std::string> m_textureFilenames;
     std::vector<BitmapBuffer> m_textureAtlas;
     std::vector<RandomBuffer> m_hRandoms;
     bool m_randomsFilled = false;

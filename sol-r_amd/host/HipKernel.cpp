@@ -214,6 +214,13 @@ bool HipKernel::deviceRotatePrimitives(const vec3f &center, const vec3f &cosA, c
     return solr_hip_rotate_primitives(c, co, si, m_sceneInfo.viewDistance) == 1;
 }
 
+bool HipKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb)
+{
+    if (solr_hip_device_count() < 1)
+        return GPUKernel::jpegPixels(frame, coefficients, rgb);
+    return solr_hip_jpeg_to_rgb(&frame, coefficients.data(), (long)(coefficients.size() / 64), rgb) == 0;
+}
+
 int HipKernel::deviceBuildTree(const std::vector<Primitive> &primitives, const std::vector<unsigned char> &emissive,
                                const vec3f &minPos, const vec3f &maxPos, float viewDistance,
                                std::vector<BoundingBox> &boxes, std::vector<int> &order, int &nbLamps)

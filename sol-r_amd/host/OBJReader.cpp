@@ -125,10 +125,35 @@ unsigned int OBJReader::loadMaterialsFromFile(const std::string &filename, std::
         }
         if (line.find("Ks") == 0 && line.length() > 3)
             materials[id].Ks = triple(line.substr(3));
-        if (line.find("map_Kd") == 0 || line.find("map_bump") == 0 || line.find("map_norm") == 0 ||
-            line.find("map_spec") == 0)
-            std::cerr << "OBJReader: " << filename << ": texture map not loaded (no image codecs in this engine): "
-                      << line << std::endl;
+        /* OBJReader.cpp:243-299: the image sits next to the .mtl file and goes into the next free texture slot */
+        const bool diffuseMap = line.find("map_Kd") == 0, bumpMap = line.find("map_bump") == 0;
+        const bool normalMap = line.find("map_norm") == 0, specularMap = line.find("map_spec") == 0;
+        if (diffuseMap || bumpMap || normalMap || specularMap)
+        {
+            const size_t skip = diffuseMap ? 7 : 9;
+            std::string folder(filename);
+            size_t slash = filename.rfind('/');
+            if (slash == std::string::npos)
+                slash = filename.rfind('\\');
+            if (slash != std::string::npos)
+                folder = filename.substr(0, slash);
+            const std::string image = folder + '/' + (line.length() > skip ? line.substr(skip) : std::string());
+            const int slot = (int)kernel.getNbActiveTextures();
+            if (kernel.loadTextureFromFile(slot, image))
+            {
+                MaterialMTL &m = materials[id];
+                if (diffuseMap)
+                    m.diffuseTextureId = slot;
+                if (bumpMap)
+                    m.bumpTextureId = slot;
+                if (normalMap)
+                    m.normalTextureId = slot;
+                if (specularMap)
+                    m.specularTextureId = slot;
+            }
+            else
+                std::cerr << "OBJReader: " << filename << ": failed to load texture " << image << std::endl;
+        }
         if (line.find("Tr") == 0)
         {
             const float d = static_cast<float>(atof(line.substr(2).c_str()));

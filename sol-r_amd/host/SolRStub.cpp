@@ -408,6 +408,18 @@ int SolR_GetTextureSize(int index, int *width, int *height, int *depth)
     return 0;
 }
 
+int SolR_LoadTextureFromFile(int index, char *filename)
+{
+    return SingletonKernel::kernel()->loadTextureFromFile(index, filename ? filename : "") ? 1 : 0;
+}
+
+int SolRx_GetTextureType(int index)
+{
+    if (index < 0 || index >= NB_MAX_TEXTURES)
+        return -1;
+    return SingletonKernel::kernel()->getTextureInformation(index).type;
+}
+
 int SolR_GetNbTextures(int *nbTextures)
 {
     *nbTextures = SingletonKernel::kernel()->getNbActiveTextures();

@@ -5,9 +5,10 @@
  * solr/SolRStub.h:36-135 (0 / -1 ints, doubles converted to floats, no C++
  * exceptions across the boundary) for every call that feeds or runs the
  * rendering path, including the scene-file loaders (SolR_LoadMolecule,
- * SolR_LoadOBJModel, SolR_SaveToFile, SolR_LoadFromFile).  Not provided (out
- * of scope): the OpenCL queries, SolR_LoadTextureFromFile
- * and SolR_GenerateScreenshot (image codecs) and the Kinect call.
+ * SolR_LoadOBJModel, SolR_SaveToFile, SolR_LoadFromFile) and the texture-file
+ * loader (SolR_LoadTextureFromFile).  Not provided (out of scope, SURVEY.md
+ * section 2): the OpenCL queries, SolR_GenerateScreenshot (a JPEG encoder) and
+ * the Kinect call.
  *
  * SolRx_* are extensions used by the test-suite and bench.py: engine
  * selection, deterministic timestamps/randoms, access to the flattened arrays
@@ -117,6 +118,11 @@ int SolR_GetLight(int index);
 int SolR_SetTexture(int index, const unsigned char *pixels, int width, int height, int depth, int textureType);
 int SolR_GetTextureSize(int index, int *width, int *height, int *depth);
 int SolR_GetNbTextures(int *nbTextures);
+/* SolRStub.h:130.  A .bmp, .tga or .jpg file into slot `index` (GPUKernel::loadTextureFromFile).  Returns the
+ * reference's bool (SolRStub.cpp:313-317): 1 = loaded, 0 = not - NOT the 0 / -1 of its neighbours */
+int SolR_LoadTextureFromFile(int index, char *filename);
+/* extension: the TextureType the loader derived from the file's name, -1 for a slot out of range */
+int SolRx_GetTextureType(int index);
 
 /* ---------- Extensions ---------- */
 /* "hip" (default) or "host-only"; destroys the current singleton */
