@@ -117,6 +117,33 @@ struct DepthHalo
     int nbAbove, nbBelow;
 };
 
+/* k_standardRenderer's kernel-argument segment as the kernel reads it: its parameters, in the order of its signature, each
+ * at its natural alignment - the layout the code-object ABI gives explicit arguments.  The kernel reads them through this
+ * view and not through the parameters (rt_device.h again()): nothing of the 480 bytes has to stay in a register from the
+ * entry to the epilogue.  Scene is SceneArgs field for field (scene_layout.h) with the four base pointers typed for
+ * constant memory, so the view hands the segment's own SceneArgs out as one.  At most 512 bytes: beyond, the runtime
+ * passes arguments another way. */
+struct RendererArgs
+{
+    SceneArgs SA;
+    FrameArgs F;
+    PixelRecord *pp;
+    int4 *ids;
+    unsigned char *bitmap;
+    unsigned long long *counters;
+    __device__ __forceinline__ const Scene &scene() const { return *(const Scene *)&SA; }
+};
+static_assert(sizeof(Scene) == sizeof(SceneArgs) && alignof(Scene) == alignof(SceneArgs), "Scene is SceneArgs, retyped");
+static_assert(offsetof(Scene, offBoxes) == offsetof(SceneArgs, offBoxes) && offsetof(Scene, nbRandoms) == offsetof(SceneArgs, nbRandoms) &&
+                  offsetof(Scene, offLeaf) == offsetof(SceneArgs, offLeaf) && offsetof(Scene, sortedLists) == offsetof(SceneArgs, sortedLists),
+              "Scene is SceneArgs, retyped");
+static_assert(offsetof(RendererArgs, SA) == 0 && sizeof(RendererArgs) <= 512, "the kernel-argument segment of k_standardRenderer");
+/* the segment of the running kernel (k_standardRenderer only) */
+__device__ __forceinline__ const RendererArgs &rendererArgs()
+{
+    return *(const RendererArgs *)(const SOLR_CONST_AS char *)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
 /* the renderer kernel and the replay of its walks (renderer_kernel.h), as the host launches them */
 typedef void (*RendererFn)(const SceneArgs, const FrameArgs, PixelRecord *, int4 *, unsigned char *, unsigned long long *);
 typedef void (*WalkBoundFn)(const SceneArgs, const char *, unsigned *, unsigned *);

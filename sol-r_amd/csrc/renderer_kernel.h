@@ -24,14 +24,27 @@ template <int COUNT, int FEAT, bool VOLUME = false>
 #ifndef SOLR_WAVES_PER_EU
 #define SOLR_WAVES_PER_EU 4
 #endif
-__global__ __launch_bounds__(WAVE, (SOLR_GENERIC_WAVES && (FEAT & F_TEX)) ? SOLR_GENERIC_WAVES : SOLR_WAVES_PER_EU) void k_standardRenderer(const SceneArgs SA, const FrameArgs F,
-                                                           PixelRecord *__restrict__ pp,
-                                                           int4 *__restrict__ ids, unsigned char *__restrict__ bitmap,
-                                                           unsigned long long *__restrict__ counters)
+__global__ __launch_bounds__(WAVE, (SOLR_GENERIC_WAVES && (FEAT & F_TEX)) ? SOLR_GENERIC_WAVES : SOLR_WAVES_PER_EU) void k_standardRenderer(const SceneArgs, const FrameArgs,
+                                                           PixelRecord *__restrict__,
+                                                           int4 *__restrict__, unsigned char *__restrict__,
+                                                           unsigned long long *__restrict__)
 {
     extern __shared__ float ldsStack[];
-    const Scene S = makeScene(SA);
+    /* The arguments are read where they lie (renderer.h RendererArgs; rt_device.h again()): here, for the primary ray, as
+     * the compiler would read the parameters themselves; by every phase of the trace for itself (F_ARGS); and by the
+     * epilogue once more.  Nothing of them has to outlive a walk. */
+    constexpr int ARGS = FEAT | F_ARGS;
+    /* (the trace of the instantiations with triangles or the texture tier reads them as it always did: measured, the mesh
+     * frame was 1.7 % and a textured one 20 % slower with the phases' own reads - those kernels keep vector registers in
+     * scratch, and where the allocator puts them moves with every change; profiles/r8/kernel_argument_reloads.txt) */
+    constexpr int TRACE = (FEAT & (F_TRI | F_TEX)) ? FEAT : ARGS;
+    const RendererArgs &A = rendererArgs();
+    const FrameArgs &F = A.F;
+    const Scene &S = A.scene();
     const SceneInfo &si = F.si;
+    PixelRecord *__restrict__ const pp = A.pp;
+    int4 *__restrict__ const ids = A.ids;
+    unsigned long long *__restrict__ const counters = A.counters;
     const int lane = threadIdx.x;
     /* the order is a permutation by construction (k_orderTiles); the clamp keeps a damaged one inside the frame */
     const unsigned entry = F.tileOrder ? F.tileOrder[blockIdx.x] : blockIdx.x;
@@ -159,12 +172,14 @@ __global__ __launch_bounds__(WAVE, (SOLR_GENERIC_WAVES && (FEAT & F_TEX)) ? SOLR
      * eyes, their distance scaled by look-at depth / depth of the focus pixel (F.focusDepth: the value
      * before this frame, see the oracle's visionRendererPixel for the race it stands for) */
     const bool vision = (FEAT & F_FULL) && (si.cameraType == ctVR);
-    const bool plainStore = anaglyph || fishEye || vision;
     v3 leftEye = V(0.f, 0.f, 0.f);
     const int nbRays = antialiasingActivated ? 5 : (anaglyph ? 2 : 1);
 #pragma unroll 1
     for (int I = 0; I < nbRays; ++I)
     {
+        /* (the cameras with more than one trace per pixel read the frame after a trace: again) */
+        const FrameArgs &F = again<(FEAT & F_FULL) ? ARGS : 0>(A.F);
+        const SceneInfo &si = F.si;
         v3 rO = rayO;
         v3 rD = rayD;
         if (anaglyph)
@@ -246,11 +261,11 @@ __global__ __launch_bounds__(WAVE, (SOLR_GENERIC_WAVES && (FEAT & F_TEX)) ? SOLR
         v3 c;
         if constexpr (volume)
         {
-            c = launchVolumeRendering<COUNT, FEAT>(S, active, gindex, rO, rD, si, F.ppi, id, cs, cnt);
+            c = launchVolumeRendering<COUNT, TRACE>(S, active, gindex, rO, rD, si, F.ppi, id, cs, cnt);
             c = V(0.f + c.x, 0.f + c.y, 0.f + c.z);
         }
         else
-            c = launchRayTracing<COUNT, FEAT>(S, active, gindex, rO, rD, si, dof, id, cs, cnt);
+            c = launchRayTracing<COUNT, TRACE>(S, active, gindex, rO, rD, si, dof, id, cs, cnt);
         if (anaglyph)
         {
             if (I == 0)
@@ -262,182 +277,197 @@ __global__ __launch_bounds__(WAVE, (SOLR_GENERIC_WAVES && (FEAT & F_TEX)) ? SOLR
             color = color + c;
     }
 
-    SOLR_T(const unsigned long long tEpilogue0 = SOLR_NOW();)
-    /* The pixel's coordinates once more, from the wave's tile number and the lane's position in the wave,
-     * through values the compiler cannot identify with the ones above: what the prologue computed would
-     * otherwise stay alive - in vector registers, in practice in scratch - through the whole path trace
-     * just to address the stores below. */
-    int tileAgain = tile, partAgain = part, laneAgain = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    asm volatile("" : "+s"(tileAgain), "+s"(partAgain), "+v"(laneAgain));
-    const int tyAgain = F.tileMagic ? (int)(__umulhi((unsigned)tileAgain, F.tileMagic) >> F.tileShift) : tileAgain;
-    const int xAgain = (tileAgain - tyAgain * F.tilesX) * TILE_W + (laneAgain & (TILE_W - 1));
-    const int yAgain = tyAgain * TILE_H + (laneAgain >> SOLR_TILE_W_LOG2);
-    const int index = ((xAgain < si.size.x) && (yAgain < F.nbRows)) ? yAgain * si.size.x + xAgain : 0;
-    const int gindexAgain = (F.firstRow + yAgain) * si.size.x + xAgain;
+    { /* the epilogue: a scope of its own, whose F, S, si, pp ... are the arguments as read again below */
+        SOLR_T(const unsigned long long tEpilogue0 = SOLR_NOW();)
+        /* The pixel's coordinates once more, from the wave's tile number and the lane's position in the wave,
+         * through values the compiler cannot identify with the ones above: what the prologue computed would
+         * otherwise stay alive - in vector registers, in practice in scratch - through the whole path trace
+         * just to address the stores below. */
+        int tileAgain = tile, partAgain = part, laneAgain = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+s"(tileAgain), "+s"(partAgain), "+v"(laneAgain));
+        /* ... and the arguments once more, for the same reason (the fields the stores need are read here, under the
+         * address arithmetic, not carried from the entry in lanes of a spill register) */
+        const RendererArgs &E = again<ARGS>(A);
+        const FrameArgs &F = E.F;
+        const Scene &S = E.scene();
+        const SceneInfo &si = F.si;
+        PixelRecord *__restrict__ const pp = E.pp;
+        int4 *__restrict__ const ids = E.ids;
+        unsigned char *__restrict__ const bitmap = E.bitmap;
+        unsigned long long *__restrict__ const counters = E.counters;
+        const bool antialiasingActivated = (FEAT & F_FULL) && (si.cameraType == ctAntialiazed);
+        const bool vision = (FEAT & F_FULL) && (si.cameraType == ctVR);
+        const bool plainStore = vision || ((FEAT & F_FULL) && (si.cameraType == ctAnaglyph || si.cameraType == ctPanoramic));
+        const int tyAgain = F.tileMagic ? (int)(__umulhi((unsigned)tileAgain, F.tileMagic) >> F.tileShift) : tileAgain;
+        const int xAgain = (tileAgain - tyAgain * F.tilesX) * TILE_W + (laneAgain & (TILE_W - 1));
+        const int yAgain = tyAgain * TILE_H + (laneAgain >> SOLR_TILE_W_LOG2);
+        const int index = ((xAgain < si.size.x) && (yAgain < F.nbRows)) ? yAgain * si.size.x + xAgain : 0;
+        const int gindexAgain = (F.firstRow + yAgain) * si.size.x + xAgain;
 
-    if ((!plainStore || vision) && si.advancedIllumination == aiRandomIllumination)
-    {
-        int rindex = (gindexAgain + si.timestamp) % MAX_BITMAP_SIZE;
-        float rv = rnd(S, rindex);
-        color.x += si.backgroundColor.x * rv * 5.f;
-        color.y += si.backgroundColor.y * rv * 5.f;
-        color.z += si.backgroundColor.z * rv * 5.f;
-    }
-    if (antialiasingActivated)
-    {
-        color.x /= 5.f;
-        color.y /= 5.f;
-        color.z /= 5.f;
-    }
-
-    if (active)
-    {
-        float4 ppColor = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 ppScene = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (si.pathTracingIteration > 0)
+        if ((!plainStore || vision) && si.advancedIllumination == aiRandomIllumination)
         {
-            ppColor = pp[index].colorInfo;
-            ppScene = pp[index].sceneInfo;
+            int rindex = (gindexAgain + si.timestamp) % MAX_BITMAP_SIZE;
+            float rv = rnd(S, rindex);
+            color.x += si.backgroundColor.x * rv * 5.f;
+            color.y += si.backgroundColor.y * rv * 5.f;
+            color.z += si.backgroundColor.z * rv * 5.f;
         }
-        if (si.pathTracingIteration == 0)
-            ppColor.w = dof;
-        if (plainStore) /* plain store / accumulate, the last-sample record is not touched (CRT:801-812, 936-947) */
+        if (antialiasingActivated)
         {
-            if (si.pathTracingIteration <= NB_MAX_ITERATIONS)
+            color.x /= 5.f;
+            color.y /= 5.f;
+            color.z /= 5.f;
+        }
+
+        if (active)
+        {
+            float4 ppColor = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 ppScene = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (si.pathTracingIteration > 0)
+            {
+                ppColor = pp[index].colorInfo;
+                ppScene = pp[index].sceneInfo;
+            }
+            if (si.pathTracingIteration == 0)
+                ppColor.w = dof;
+            if (plainStore) /* plain store / accumulate, the last-sample record is not touched (CRT:801-812, 936-947) */
+            {
+                if (si.pathTracingIteration <= NB_MAX_ITERATIONS)
+                {
+                    ppColor.x = color.x;
+                    ppColor.y = color.y;
+                    ppColor.z = color.z;
+                }
+                else
+                {
+                    ppColor.x += color.x;
+                    ppColor.y += color.y;
+                    ppColor.z += color.z;
+                }
+            }
+            else if (si.pathTracingIteration <= NB_MAX_ITERATIONS)
             {
                 ppColor.x = color.x;
                 ppColor.y = color.y;
                 ppColor.z = color.z;
+                ppScene.x = color.x;
+                ppScene.y = color.y;
+                ppScene.z = color.z;
             }
             else
             {
-                ppColor.x += color.x;
-                ppColor.y += color.y;
-                ppColor.z += color.z;
+                ppScene.x = (id.z > 0) ? fmaxf(ppScene.x, color.x) : color.x;
+                ppScene.y = (id.z > 0) ? fmaxf(ppScene.y, color.y) : color.y;
+                ppScene.z = (id.z > 0) ? fmaxf(ppScene.z, color.z) : color.z;
+                ppColor.x += ppScene.x;
+                ppColor.y += ppScene.y;
+                ppColor.z += ppScene.z;
             }
-        }
-        else if (si.pathTracingIteration <= NB_MAX_ITERATIONS)
-        {
-            ppColor.x = color.x;
-            ppColor.y = color.y;
-            ppColor.z = color.z;
-            ppScene.x = color.x;
-            ppScene.y = color.y;
-            ppScene.z = color.z;
-        }
-        else
-        {
-            ppScene.x = (id.z > 0) ? fmaxf(ppScene.x, color.x) : color.x;
-            ppScene.y = (id.z > 0) ? fmaxf(ppScene.y, color.y) : color.y;
-            ppScene.z = (id.z > 0) ? fmaxf(ppScene.z, color.z) : color.z;
-            ppColor.x += ppScene.x;
-            ppColor.y += ppScene.y;
-            ppColor.z += ppScene.z;
-        }
-        pp[index].colorInfo = ppColor;
-        pp[index].sceneInfo = ppScene;
-        if ((FEAT & F_STREAM) && (F.fuseDefault & 4)) /* (ImageStreaming with the ids: written through to memory, where the copy engine reads the band) */
-        {
-            typedef int FourInts __attribute__((ext_vector_type(4)));
-            const FourInts four = {id.x, id.y, id.z, id.w};
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(ids + index), "v"(four) : "memory");
-        }
-        else
-            ids[index] = id;
-
-        if (F.fuseDefault)
-        {
-            v3 c = V(ppColor.x, ppColor.y, ppColor.z);
-            if (si.pathTracingIteration > NB_MAX_ITERATIONS)
+            pp[index].colorInfo = ppColor;
+            pp[index].sceneInfo = ppScene;
+            if ((FEAT & F_STREAM) && (F.fuseDefault & 4)) /* (ImageStreaming with the ids: written through to memory, where the copy engine reads the band) */
             {
-                float d = (float)(si.pathTracingIteration - NB_MAX_ITERATIONS + 1);
-                c.x /= d;
-                c.y /= d;
-                c.z /= d;
+                typedef int FourInts __attribute__((ext_vector_type(4)));
+                const FourInts four = {id.x, id.y, id.z, id.w};
+                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(ids + index), "v"(four) : "memory");
             }
-            if ((FEAT & F_STREAM) && (F.fuseDefault & 2))
-                makeColor<true>(si, c, bitmap, index);
             else
-                makeColor(si, c, bitmap, index);
-        }
-    }
-    if ((FEAT & F_STREAM) && (F.fuseDefault & 2)) /* ImageStreaming (renderer.h): this tile's bytes are out; is its row, is its band? */
-    {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned units = partAgain ? 1u : (unsigned)SPLIT_PARTS;
-        unsigned before = 0u;
-        if (laneAgain == 0)
-            before = __hip_atomic_fetch_add(F.rowDone + 64 * tyAgain, units, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        before = (unsigned)__builtin_amdgcn_readfirstlane((int)before);
-        if (before + units == F.streamSerial * (unsigned)(F.tilesX * SPLIT_PARTS) && laneAgain == 0)
-        {
-            const StreamPlan *plan = F.streamPlan;
-            int band = 0;
-            while (band + 1 < plan->bands && tyAgain >= plan->firstRow[band + 1])
-                ++band;
-            const int rows = plan->firstRow[band + 1] - plan->firstRow[band];
-            const unsigned rowsBefore = __hip_atomic_fetch_add(plan->bandDone + 64 * band, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (rowsBefore + 1u == F.streamSerial * (unsigned)rows)
-                __hip_atomic_store(plan->hostWord + band, F.streamSerial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+                ids[index] = id;
 
-    if (F.tileClock && laneAgain == 0)
-    {
-        F.tileClock[2 * tileAgain] = clock0;
-        F.tileClock[2 * tileAgain + 1] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (F.tileCost && laneAgain == 0) /* what this tile cost, for the launch order of the next frames */
-    {
-        /* a quadrant takes about 0.8 of what its whole tile takes (profiles/r1: DESIGN.md section 5): reported
-         * as twice its own time, a split tile stays among the expensive ones and stays split (four waves write
-         * the same word; any of them will do) */
-        const unsigned cost = (unsigned)(__builtin_amdgcn_s_memrealtime() - clock0);
-        F.tileCost[tileAgain] = partAgain ? (unsigned)(SOLR_SPLIT_LOG2 + 1) * cost : cost;
-    }
+            if (F.fuseDefault)
+            {
+                v3 c = V(ppColor.x, ppColor.y, ppColor.z);
+                if (si.pathTracingIteration > NB_MAX_ITERATIONS)
+                {
+                    float d = (float)(si.pathTracingIteration - NB_MAX_ITERATIONS + 1);
+                    c.x /= d;
+                    c.y /= d;
+                    c.z /= d;
+                }
+                if ((FEAT & F_STREAM) && (F.fuseDefault & 2))
+                    makeColor<true>(si, c, bitmap, index);
+                else
+                    makeColor(si, c, bitmap, index);
+            }
+        }
+        if ((FEAT & F_STREAM) && (F.fuseDefault & 2)) /* ImageStreaming (renderer.h): this tile's bytes are out; is its row, is its band? */
+        {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const unsigned units = partAgain ? 1u : (unsigned)SPLIT_PARTS;
+            unsigned before = 0u;
+            if (laneAgain == 0)
+                before = __hip_atomic_fetch_add(F.rowDone + 64 * tyAgain, units, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            before = (unsigned)__builtin_amdgcn_readfirstlane((int)before);
+            if (before + units == F.streamSerial * (unsigned)(F.tilesX * SPLIT_PARTS) && laneAgain == 0)
+            {
+                const StreamPlan *plan = F.streamPlan;
+                int band = 0;
+                while (band + 1 < plan->bands && tyAgain >= plan->firstRow[band + 1])
+                    ++band;
+                const int rows = plan->firstRow[band + 1] - plan->firstRow[band];
+                const unsigned rowsBefore = __hip_atomic_fetch_add(plan->bandDone + 64 * band, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (rowsBefore + 1u == F.streamSerial * (unsigned)rows)
+                    __hip_atomic_store(plan->hostWord + band, F.streamSerial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+
+        if (F.tileClock && laneAgain == 0)
+        {
+            F.tileClock[2 * tileAgain] = clock0;
+            F.tileClock[2 * tileAgain + 1] = __builtin_amdgcn_s_memrealtime();
+        }
+        if (F.tileCost && laneAgain == 0) /* what this tile cost, for the launch order of the next frames */
+        {
+            /* a quadrant takes about 0.8 of what its whole tile takes (profiles/r1: DESIGN.md section 5): reported
+             * as twice its own time, a split tile stays among the expensive ones and stays split (four waves write
+             * the same word; any of them will do) */
+            const unsigned cost = (unsigned)(__builtin_amdgcn_s_memrealtime() - clock0);
+            F.tileCost[tileAgain] = partAgain ? (unsigned)(SOLR_SPLIT_LOG2 + 1) * cost : cost;
+        }
 #ifdef SOLR_TIMING
-    if (COUNT == 0 && laneAgain == 0 && counters)
-    {
-        /* one record per workgroup, summed by the host (atomics on one address would serialise the frame) */
-        unsigned long long *slot = counters + 16 + 16ull * blockIdx.x;
-        slot[0] += SOLR_NOW() - tKernel0;
-        slot[8] += cnt.tShade;
-        slot[9] += cnt.tTrace;
-        slot[10] += SOLR_NOW() - tEpilogue0;
-        slot[1] += cnt.tClosest;
-        slot[2] += cnt.tShadow;
-        slot[3] += cnt.tNode;
-        slot[4] += cnt.tLeaf;
-        slot[5] += (unsigned long long)cnt.nAdvance;
-        slot[6] += (unsigned long long)cnt.nLeaf;
-        slot[7] += 1ull;
-        slot[11] += cnt.tClosestPrimary;
-        slot[12] += cnt.tAgain;
-        slot[13] += ((unsigned long long)cnt.nAgain << 32) | cnt.nAgainLanes;
-        slot[14] += ((unsigned long long)cnt.nAdvanceFirst << 32) | cnt.nAdvanceAgain;
-        slot[15] += (unsigned long long)cnt.nChecked;
-    }
-#endif
-    if (COUNT == 2 && lane == 0)
-        ((int4 *)cnt.record)[0] = make_int4((int)cnt.ordinal, 0, 0, 0);
-    if (COUNT == 1)
-    {
-        unsigned int vals[4] = {cnt.closest, cnt.shadow, cnt.boxes, cnt.prims};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
+        if (COUNT == 0 && laneAgain == 0 && counters)
         {
-            unsigned int v = vals[k];
-            for (int off = 32; off > 0; off >>= 1)
-                v += __shfl_xor(v, off, 64);
-            if (lane == 0)
-                atomicAdd(&counters[k], (unsigned long long)v);
+            /* one record per workgroup, summed by the host (atomics on one address would serialise the frame) */
+            unsigned long long *slot = counters + 16 + 16ull * blockIdx.x;
+            slot[0] += SOLR_NOW() - tKernel0;
+            slot[8] += cnt.tShade;
+            slot[9] += cnt.tTrace;
+            slot[10] += SOLR_NOW() - tEpilogue0;
+            slot[1] += cnt.tClosest;
+            slot[2] += cnt.tShadow;
+            slot[3] += cnt.tNode;
+            slot[4] += cnt.tLeaf;
+            slot[5] += (unsigned long long)cnt.nAdvance;
+            slot[6] += (unsigned long long)cnt.nLeaf;
+            slot[7] += 1ull;
+            slot[11] += cnt.tClosestPrimary;
+            slot[12] += cnt.tAgain;
+            slot[13] += ((unsigned long long)cnt.nAgain << 32) | cnt.nAgainLanes;
+            slot[14] += ((unsigned long long)cnt.nAdvanceFirst << 32) | cnt.nAdvanceAgain;
+            slot[15] += (unsigned long long)cnt.nChecked;
         }
-        if (lane == 0)
+#endif
+        if (COUNT == 2 && lane == 0)
+            ((int4 *)cnt.record)[0] = make_int4((int)cnt.ordinal, 0, 0, 0);
+        if (COUNT == 1)
         {
-            atomicAdd(&counters[4], (unsigned long long)cnt.wNodes);
-            atomicAdd(&counters[5], (unsigned long long)cnt.wPrims);
-            atomicAdd(&counters[6], (unsigned long long)cnt.wClosest);
-            atomicAdd(&counters[7], (unsigned long long)cnt.wShadow);
+            unsigned int vals[4] = {cnt.closest, cnt.shadow, cnt.boxes, cnt.prims};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                unsigned int v = vals[k];
+                for (int off = 32; off > 0; off >>= 1)
+                    v += __shfl_xor(v, off, 64);
+                if (lane == 0)
+                    atomicAdd(&counters[k], (unsigned long long)v);
+            }
+            if (lane == 0)
+            {
+                atomicAdd(&counters[4], (unsigned long long)cnt.wNodes);
+                atomicAdd(&counters[5], (unsigned long long)cnt.wPrims);
+                atomicAdd(&counters[6], (unsigned long long)cnt.wClosest);
+                atomicAdd(&counters[7], (unsigned long long)cnt.wShadow);
+            }
         }
     }
 }

@@ -579,11 +579,40 @@ enum Feature
     F_DEEP = 256,   /* not a feature of the scene but of its node list: walk it with the three-bank loop (advanceTidy) */
     F_STACK = 512,  /* nor of the scene but of the frame: more bounces than colour-stack slots are kept in LDS
                      * (SOLR_LDS_STACK_SLOTS) - the deeper slots live in a per-pixel buffer in HBM (ColorStack) */
-    F_STREAM = 1024 /* of the frame: its image leaves in bands while it renders (renderer.h ImageStreaming) - the epilogue
-                     * that counts tiles lives in instantiations of its own, so that every other frame runs the code it
+    F_STREAM = 1024, /* of the frame: its image leaves in bands while it renders (renderer.h ImageStreaming) - the epilogue
+                      * that counts tiles lives in instantiations of its own, so that every other frame runs the code it
                      * always ran (an epilogue with the branches in it cost the Cornell kernel 0.5 %: the compiler's
                      * allocation of the WHOLE kernel changed with it) */
+    F_ARGS = 2048   /* nor of the scene nor of the frame but of the caller: `S` and `si` are references INTO THE KERNEL-ARGUMENT
+                     * SEGMENT (k_standardRenderer sets the bit itself; the host never sees it) and every phase re-reads the
+                     * fields it uses - see again() below */
 };
+
+/* Where the kernel's arguments live.  k_standardRenderer receives 480 bytes of them (the scene's offsets and counts, the
+ * whole SceneInfo, the frame); loaded at entry, as the compiler does by itself, they are scalars that must outlive both
+ * walks of every bounce - whose hand-scheduled node loops own s[64:94] - and all but a few wait in lanes of spill
+ * registers, one v_writelane / v_readlane and its hazard nops per word and use (9 % of the lean Cornell kernel's vector
+ * instructions, tools/lane_spills.py).  The kernel-argument segment is constant memory that the scalar cache holds for
+ * every wave, so a phase that needs a field reads it again, at its head, with scalar loads its own arithmetic covers.
+ * again(v): the same object through an address the compiler cannot identify with the one it has seen - the kernel's own
+ * idiom for the tile number of its epilogue - so that what a phase read is not kept for the next one.  An INTEGER is
+ * laundered, not the pointer (that fails in divergent control flow: "illegal VGPR to SGPR copy"), and the address is
+ * still inferred to be constant memory: the loads are s_load, none is a vector load.  Callers copy what again() returns
+ * BY VALUE at the head of a phase - `const Scene S = again<FEAT>(S_)` - which places the loads there; through the
+ * reference itself they would be made wherever a field is used, inside the leaf loops too.  Without F_ARGS (the probes'
+ * kernels, whose scene and frame are values of their own) it is the object itself. */
+template <int FEAT, class T>
+SOLR_DEV const T &again(const T &v)
+{
+    if constexpr ((FEAT & F_ARGS) != 0)
+    {
+        int zero = 0;
+        asm volatile("" : "+s"(zero));
+        return *(const T *)((const char *)&v + zero);
+    }
+    else
+        return v;
+}
 /* Colour-stack slots (4 dwords each) a lane keeps in LDS.  With the 27-dword cold record that is 39 dwords per lane: what
  * 16 waves per CU - 4 per SIMD, the kernel's register budget - leave each lane of the 160 KB.  A frame that may bounce
  * deeper (the accumulation passes: up to NB_MAX_ITERATIONS = 10) used to size the LDS stack for it - 67 dwords, 9 waves
@@ -1597,13 +1626,16 @@ SOLR_DEV bool tightRay(const WalkRay &r, const SceneInfo &si)
 }
 
 template <int COUNT, int FEAT>
-SOLR_DEV bool closestHitWalk(const Scene &S, const SceneInfo &si, bool active, v3 origin, v3 target, int iteration,
+SOLR_DEV bool closestHitWalk(const Scene &S_, const SceneInfo &si_, bool active, v3 origin, v3 target, int iteration,
                              int currentMaterialId, int &closestPrimitive, v3 &closestIntersection,
                              v3 &closestNormal, v3 &closestAreas, v3 &colorBox, Counters &cnt)
 {
     bool intersections = false;
     if (ballot(active) == 0ull)
         return false;
+    /* the walk's own reading of the arguments (again() above): the loads are issued here, under makeWalkRay */
+    const Scene S = again<FEAT>(S_);
+    const SceneInfo si = again<FEAT>(si_);
     SOLR_T(const unsigned long long tw0 = SOLR_NOW();)
     float minDistance = (iteration < 2) ? si.viewDistance : si.viewDistance / (iteration + 1);
     const WalkRay r = makeWalkRay(origin, target - origin);
@@ -2046,13 +2078,16 @@ SOLR_DEV bool closestHitWalk(const Scene &S, const SceneInfo &si, bool active, v
 /* GI:798-908, wave-synchronous.  objectId is the flattened index of the
  * shaded primitive, compared with Primitive.index like the reference does. */
 template <int COUNT, int FEAT>
-SOLR_DEV float shadowWalk(const Scene &S, const SceneInfo &si, bool active, v3 lampCenter, v3 origin, int lightId,
+SOLR_DEV float shadowWalk(const Scene &S_, const SceneInfo &si_, bool active, v3 lampCenter, v3 origin, int lightId,
                           int iteration, v3 &color, int objectId, Counters &cnt)
 {
     float result = 0.f;
     color = V(0.f, 0.f, 0.f);
     if (ballot(active) == 0ull)
         return 0.f;
+    /* the walk's own reading of the arguments (again() above) */
+    const Scene S = again<FEAT>(S_);
+    const SceneInfo si = again<FEAT>(si_);
     SOLR_T(const unsigned long long tw0 = SOLR_NOW();)
     WalkRay r = makeWalkRay(origin, lampCenter - origin);
     r.o = origin + r.dn * si.rayEpsilon; /* GI:810-811 */
@@ -2412,11 +2447,15 @@ SOLR_DEV float4 intersectionShader(const Scene &S, const SceneInfo &si, int pi, 
  * the lanes that actually shade.  The light loop is wave-uniform, the shadow
  * walk inside it is wave-synchronous. */
 template <int COUNT, int FEAT>
-SOLR_DEV v3 primitiveShader(const Scene &S, bool active, int index, const SceneInfo &si, v3 origin, v3 &normal,
+SOLR_DEV v3 primitiveShader(const Scene &S_, bool active, int index, const SceneInfo &si_, v3 origin, v3 &normal,
                             int objectId, v3 intersection, v3 areas, v3 &closestColor, int iteration,
                             float &shadowIntensity, v3 &totalBlinn, float4 &attributes, Counters &cnt)
 {
     SOLR_T(const unsigned long long tShade0 = SOLR_NOW();)
+    /* the arguments as the head of the shader reads them (again() above); every lamp reads them again, before its shadow
+     * walk and after it */
+    const Scene S = again<FEAT>(S_);
+    const SceneInfo si = again<FEAT>(si_);
     const int pi = active ? objectId : 0;
     const int type = asint(primRow(S, pi, ROW_P0_TYPE).w) & PRIM_TYPE_MASK; /* row 0 carries type + material facts */
     const int materialId = asint(primRow(S, pi, ROW_SIZE_MAT).w);
@@ -2450,8 +2489,10 @@ SOLR_DEV v3 primitiveShader(const Scene &S, bool active, int index, const SceneI
             closestColor.y *= mh.innerIllumination.x;
             closestColor.z *= mh.innerIllumination.x;
         }
-        for (int cpt = 0; cpt < S.nbLights; ++cpt)
+        for (int cpt = 0; cpt < again<FEAT>(S_).nbLights; ++cpt)
         {
+            const Scene S = again<FEAT>(S_);
+            const SceneInfo si = again<FEAT>(si_);
             const int cptLamp =
                 (si.pathTracingIteration >= NB_MAX_ITERATIONS) ? (si.pathTracingIteration % S.nbLights) : 0;
             const LightPlane li = loadLight(S, cptLamp);
@@ -2484,7 +2525,7 @@ SOLR_DEV v3 primitiveShader(const Scene &S, bool active, int index, const SceneI
                                     mh.innerIllumination.x == 0.f;
             {
                 v3 sc;
-                float s = shadowWalk<COUNT, FEAT>(S, si, wantShadow, center, intersection, lightPrimitiveId, iteration, sc,
+                float s = shadowWalk<COUNT, FEAT>(S_, si_, wantShadow, center, intersection, lightPrimitiveId, iteration, sc,
                                             objectId, cnt);
                 if (wantShadow)
                 {
@@ -2494,6 +2535,8 @@ SOLR_DEV v3 primitiveShader(const Scene &S, bool active, int index, const SceneI
             }
             if (inRange) /* graphicsLevel > glNoShading holds here, GI:1000 */
             {
+                const Scene S = again<FEAT>(S_); /* (behind the shadow walk) */
+                const SceneInfo si = again<FEAT>(si_);
                 float photonEnergy = sqrt_ieee(lightRayLength / m.innerIllumination.z);
                 photonEnergy = (photonEnergy > 1.f) ? 1.f : photonEnergy;
                 photonEnergy = (photonEnergy < 0.f) ? 0.f : photonEnergy;
@@ -2717,10 +2760,14 @@ struct V3Ref
  * shader call site, which keeps the instruction footprint and the live
  * register set of the kernel small. */
 template <int COUNT, int FEAT>
-SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3 rayD, const SceneInfo &si,
+SOLR_DEV v3 launchRayTracing(const Scene &S_, bool active, int index, v3 rayO, v3 rayD, const SceneInfo &si_,
                              float &depthOfField, int4 &primitiveXYId, const ColorStack &cs, Counters &cnt)
 {
     SOLR_T(const unsigned long long tTrace0 = SOLR_NOW();)
+    /* The arguments, phase by phase (again() above): what is read here serves the set-up; every trip reads them for its
+     * head, each walk and the shader for themselves, the bookkeeping behind the shader and the blend behind the loop
+     * once more.  What the trips share of them is derived here: the bounce limit and two facts of the frame. */
+    const SceneInfo si = again<FEAT>(si_);
     v3 intersectionColor = V(0.f, 0.f, 0.f);
     v3 closestIntersection = V(0.f, 0.f, 0.f);
     v3 normal = V(0.f, 0.f, 0.f);
@@ -2800,6 +2847,7 @@ SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3
         bool want;
         v3 tO, tD;
         int tIter, tMat;
+        const SceneInfo si = again<FEAT>(si_); /* the head of the trip */
         if (phase == 0)
         {
             running = running && (iteration < currentMaxIteration) && (rayLength < si.viewDistance) && carryon;
@@ -2832,9 +2880,10 @@ SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3
         }
 
         v3 areas = V(0.f, 0.f, 0.f);
-        const bool hit = closestHitWalk<COUNT, FEAT>(S, si, want, tO, tD, tIter, tMat, closestPrimitive,
+        const bool hit = closestHitWalk<COUNT, FEAT>(S_, si_, want, tO, tD, tIter, tMat, closestPrimitive,
                                                closestIntersection, normal, areas, colorBox, cnt);
         const bool hitLane = want && hit;
+        const Scene S = again<FEAT>(S_); /* behind the walk: the gather of the hit's material, the first hit's records */
 
         /* material of the hit (per-lane gather) */
         const int cp = hitLane ? closestPrimitive : 0;
@@ -2846,6 +2895,7 @@ SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3
 
         if (phase == 0)
         {
+            const SceneInfo si = again<FEAT>(si_);
             if (running)
                 carryon = hit;
             attributes = make_float4(cm.reflection, cm.transparency, cm.refraction, cm.opacity);
@@ -2906,6 +2956,7 @@ SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3
                     pathTracingRatio *= STANDARD_LUNINANCE_STRENGTH;
                     if (cm.innerIllumination.x == 0.f)
                     {
+                        const SceneInfo &si = again<FEAT>(si_);
                         cs.at(0, 0) -= si.shadowIntensity;
                         cs.at(0, 1) -= si.shadowIntensity;
                         cs.at(0, 2) -= si.shadowIntensity;
@@ -2917,12 +2968,14 @@ SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3
             shadeIteration = lastIteration;
         }
 
-        const v3 shaded = primitiveShader<COUNT, FEAT>(S, shadeLane, index, si, tO, normal, closestPrimitive,
+        const v3 shaded = primitiveShader<COUNT, FEAT>(S_, shadeLane, index, si_, tO, normal, closestPrimitive,
                                                  closestIntersection, areas, closestColor, shadeIteration,
                                                  shadowIntensity, rBlinn, attributes, cnt);
 
         if (phase == 0)
         {
+            const Scene S = again<FEAT>(S_); /* the bookkeeping of the bounce, behind the shader */
+            const SceneInfo si = again<FEAT>(si_);
             if (hitLane)
             {
                 v3 colorIt = shaded;
@@ -3039,6 +3092,8 @@ SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3
         {
             if (shadeLane)
                 pathTracingColor = shaded;
+            const Scene &S = again<FEAT>(S_);
+            const SceneInfo &si = again<FEAT>(si_);
             if (active && !hitLane && si.skyboxMaterialId != MATERIAL_NONE)
             {
                 pathTracingColor = skyboxMapping<FEAT>(S, si, ptO, ptD);
@@ -3085,6 +3140,7 @@ SOLR_DEV v3 launchRayTracing(const Scene &S, bool active, int index, v3 rayO, v3
         else
             intersectionColor = cs.get(0);
 
+        const SceneInfo si = again<FEAT>(si_); /* behind the loop */
         float D1 = si.viewDistance * 0.95f;
         const float dofNow = dofCold;
         if (si.atmosphericEffect == aeFog && dofNow > D1)
