@@ -15,11 +15,17 @@
  *                                                                             jpgd.cpp:786-985 (P_Q, R_S), 1670-1788
  *   colour          fixed-point YCbCr -> RGB with 16 fractional bits          jpgd.cpp:1614-1629, 2233-2265
  * jpgd's sparse variants (Row<N>, Col<N>, the DC-only shortcut, P_Q<rows, cols>) only leave out terms that are zero:
- * the general forms below give the same integers on zero-filled blocks (tests/golden/texture_files.npz holds jpgd's own
- * output for every path).
+ * the general forms below give the same integers on zero-filled blocks WHILE EVERY SUM FITS IN 32 BITS AND EVERY 16-BIT
+ * STORE KEEPS ITS VALUE - which holds for every coefficient a baseline file can carry (+-1023) with quantisers up to 2,
+ * dense blocks included, and far beyond for what encoders write.  tests/golden/jpeg_synthetic.npz holds jpgd's output
+ * for every last zigzag position in every component (each Row / Col pair, each of the fifteen P_Q / R_S instantiations)
+ * and for dense blocks at that limit, tests/golden/texture_files.npz for files an encoder wrote.
  *
  * No floating point anywhere.  Sums that only a corrupt file can push past 32 bits wrap (unsigned arithmetic) instead of
- * being undefined; every 16-bit truncation is an explicit cast.
+ * being undefined; every 16-bit truncation is an explicit cast.  Out there the general forms and jpgd part: a shortcut
+ * never forms the sum that wraps here (Col<1> only descales row 0 of the first pass, the general column pass shifts it
+ * left by 13 first), and jpgd's own general forms are undefined.  The same npz pins the engine's bytes for such files
+ * (its wrap tier); they are not jpgd's.
  */
 #pragma once
 
