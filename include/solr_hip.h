@@ -286,6 +286,30 @@ int solr_hip_jpeg_to_rgb(const SolrJpegFrame *frame, const short *coefficients, 
 /* 8x8 output blocks (after chroma upsampling: 3, 4 or 12 per MCU) the device has produced since the library was loaded */
 unsigned long long solr_hip_jpeg_blocks(void);
 
+/* The pixel stage of the JPEG screenshot writer on the device (sol-r_amd/csrc/solr_jpeg_encode.hip; the arithmetic is
+ * sol-r_amd/csrc/jpeg_encode.h, the reference encoder's, solr/images/jpge.cpp, bit for bit): colour conversion, chroma
+ * averaging, the forward DCTs and quantisation.  The host then codes the blocks (sol-r_amd/host/JpegWriter.cpp).
+ *   source         size, luma sampling factors (1x1, 2x1 or 2x2; chroma is 1x1), the JPEG quality 1..100 the two
+ *                  quantisation tables are made from, and how the picture is read: turned != 0 - pixel p of the
+ *                  encoded picture is pixel width * height - p of `rgb` (that index clamped to the last pixel for
+ *                  p = 0), as GPUKernel::generateScreenshot reads a frame; swapRedBlue != 0 - a pixel's bytes are B, G, R
+ *   rgb            the caller's host buffer of width * height * 3 bytes
+ *   coefficients   the caller's host buffer of nbBlocks * 64 shorts; receives the blocks in MCU order - inside an MCU
+ *                  the luma blocks row by row, then Cb, then Cr - each in zigzag order, quantised
+ *   nbBlocks       must be mcusPerRow * mcuRows * (lumaH * lumaV + 2)
+ * Synchronous; runs on the device of solr_hip_get_device() on a stream of its own, with or without an initialised
+ * scene, and gives its device buffers back before it returns.  0, or -1 with the error set (bad arguments - a size
+ * beyond SOLR_JPEG_MAX_SIDE / SOLR_JPEG_MAX_PIXELS, a quality outside 1..100, another sampling - are refused before
+ * anything is launched). */
+typedef struct
+{
+    int width, height, lumaH, lumaV, quality, turned, swapRedBlue;
+} SolrJpegSource;
+int solr_hip_rgb_to_jpeg_blocks(const SolrJpegSource *source, const unsigned char *rgb, short *coefficients,
+                                long nbBlocks);
+/* coefficient blocks the device has produced since the library was loaded */
+unsigned long long solr_hip_jpeg_encoded_blocks(void);
+
 /* Device pointers of the current per-pixel buffers (strip-sized), for
  * collectives issued by the launcher (RCCL gather of the RGB strip). */
 void *solr_hip_device_bitmap(void);

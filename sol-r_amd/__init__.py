@@ -84,6 +84,12 @@ class JpegFrame(C.Structure):
                 ("mcusPerRow", C.c_int), ("mcuRows", C.c_int), ("quant", (C.c_ushort * 64) * 3)]
 
 
+class JpegSource(C.Structure):
+    """SolrJpegSource of include/solr_hip.h: what solr_hip_rgb_to_jpeg_blocks is told about the picture"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("lumaH", C.c_int), ("lumaV", C.c_int),
+                ("quality", C.c_int), ("turned", C.c_int), ("swapRedBlue", C.c_int)]
+
+
 assert C.sizeof(SceneInfo) == 112 and C.sizeof(PostProcessingInfo) == 16
 
 # ---- numpy views of the flattened arrays --------------------------------------
@@ -238,6 +244,9 @@ def _declare_hip(L):
     L.solr_hip_jpeg_to_rgb.argtypes = [P(JpegFrame), C.c_void_p, C.c_long, C.c_void_p]
     L.solr_hip_jpeg_to_rgb.restype = C.c_int
     L.solr_hip_jpeg_blocks.restype = C.c_ulonglong
+    L.solr_hip_rgb_to_jpeg_blocks.argtypes = [P(JpegSource), C.c_void_p, C.c_void_p, C.c_long]
+    L.solr_hip_rgb_to_jpeg_blocks.restype = C.c_int
+    L.solr_hip_jpeg_encoded_blocks.restype = C.c_ulonglong
     # the by-value reference entry points are exercised from C++ (host/HipKernel.cpp);
     # ctypes cannot 16-byte align a by-value struct, so they get no argtypes here
     L.h2d_scene.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -277,6 +286,11 @@ def _declare_host(L):
     L.SolR_GetNbTextures.argtypes = [P(i)]
     L.SolR_LoadTextureFromFile.argtypes = [i, C.c_char_p]
     L.SolRx_GetTextureType.argtypes = [i]
+    L.SolR_GenerateScreenshot.argtypes = [C.c_char_p, i, i, i]
+    L.SolRx_EncodeJpeg.argtypes = [C.c_char_p, C.c_void_p, i, i, i, i, i, i, i]
+    L.SolRx_JpegCoefficients.argtypes = [C.c_void_p, i, i, i, i, i, i, i, C.c_void_p, C.c_long]
+    L.SolRx_JpegFromCoefficients.argtypes = [C.c_char_p, C.c_void_p, C.c_long, i, i, i, i, i]
+    L.SolRx_JpegQuantise.argtypes = [i, i, i, i, C.c_void_p]
     L.SolRx_SelectEngine.argtypes = [C.c_char_p]
     L.SolRx_SetDeterministic.argtypes = [C.c_long]
     L.SolRx_LastError.argtypes = [C.c_char_p, i]
@@ -520,6 +534,29 @@ class Kernel:
         status = self.L.SolR_RunKernel(0.0, image.ctypes.data)
         self.check(status, "SolR_RunKernel")
         return image
+
+    def screenshot(self, path, width, height, quality):
+        """SolR_GenerateScreenshot (reference: GPUKernel::generateScreenshot): `quality` passes of path tracing
+        (pathTracingIteration 0 ... quality - 1 of maxPathTracingIterations = quality) at width x height, at most
+        1920 x 1080, and the last image as a JPEG file of JPEG quality 85 with 2x2 chroma - `quality` is the number of
+        passes, not the JPEG quality.  With the HIP engine the encoder's pixel stage runs on the device.  The scene
+        settings and the frame size are as before afterwards."""
+        self.set_scene_info()
+        status = self.L.SolR_GenerateScreenshot(os.fsencode(path), width, height, quality)
+        self.check(status, "SolR_GenerateScreenshot")
+
+    def encode_jpeg(self, path, pixels, quality=85, sampling=(2, 2), turned=False, swap_red_blue=False):
+        """The screenshot's encoder alone (SolRx_EncodeJpeg): `pixels` (H, W, 3) uint8 to a baseline JPEG file, byte for
+        byte the reference encoder's.  quality: JPEG quality 1 ... 100; sampling: luma (H, V), one of (1, 1), (2, 1),
+        (2, 2); turned / swap_red_blue read the pixels as a screenshot reads a frame: pixel p from pixel N - p (N = W * H;
+        N itself is read as N - 1), first and third channel swapped."""
+        a = np.ascontiguousarray(pixels, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("pixels must be (height, width, 3)")
+        status = self.L.SolRx_EncodeJpeg(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0], quality,
+                                         sampling[0], sampling[1], int(bool(turned)), int(bool(swap_red_blue)))
+        if status != 0:
+            raise SolrError("SolRx_EncodeJpeg refused its arguments or could not write %s" % path)
 
     def postprocessing_buffer(self):
         """Float framebuffer of the last frame: (H, W, 8) = colorInfo.xyzw, sceneInfo.xyzw."""

@@ -9,6 +9,8 @@
  */
 #include "GPUKernel.h"
 #include "ImageLoader.h"
+#include "JpegWriter.h"
+#include "../csrc/jpeg_encode.h"
 
 #include <chrono>
 #include <cstdio>
@@ -1407,6 +1409,97 @@ bool GPUKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> 
 {
     ImageLoader::jpegPixelsOnHost(frame, coefficients.data(), rgb);
     return true;
+}
+
+/* the arguments solr_hip_rgb_to_jpeg_blocks refuses (include/solr_hip.h), refused alike by the loop */
+static bool jpegSourceInRange(const SolrJpegSource &s)
+{
+    return s.width >= 1 && s.height >= 1 && s.width <= SOLR_JPEG_MAX_SIDE && s.height <= SOLR_JPEG_MAX_SIDE &&
+           (long)s.width * s.height <= SOLR_JPEG_MAX_PIXELS && s.quality >= 1 && s.quality <= 100 &&
+           jpe::samplingSupported(s.lumaH, s.lumaV);
+}
+
+bool GPUKernel::jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb, std::vector<short> &coefficients)
+{
+    if (!rgb || !jpegSourceInRange(source))
+        return false;
+    unsigned short quant[2][64];
+    jpe::u32 recip[2][64];
+    for (int t = 0; t < 2; ++t)
+    {
+        jpe::quantTable(source.quality, t, quant[t]);
+        for (int k = 0; k < 64; ++k)
+            recip[t][k] = jpe::reciprocal(quant[t][k]);
+    }
+    const int mcusPerRow = (source.width + 8 * source.lumaH - 1) / (8 * source.lumaH);
+    const int mcuRows = (source.height + 8 * source.lumaV - 1) / (8 * source.lumaV);
+    const int perMcu = jpe::blocksPerMcu(source.lumaH, source.lumaV);
+    coefficients.resize((size_t)mcusPerRow * mcuRows * perMcu * 64);
+    for (int y = 0; y < mcuRows; ++y)
+        for (int x = 0; x < mcusPerRow; ++x)
+            jpe::encodeMcu(rgb, source.width, source.height, source.lumaH, source.lumaV, source.turned,
+                           source.swapRedBlue, x, y, quant, recip,
+                           &coefficients[((size_t)y * mcusPerRow + x) * perMcu * 64]);
+    return true;
+}
+
+bool GPUKernel::encodeJpeg(const std::string &filename, const unsigned char *pixels, int width, int height,
+                           int jpegQuality, int lumaH, int lumaV, bool turned, bool swapRedBlue)
+{
+    const SolrJpegSource source = {width, height, lumaH, lumaV, jpegQuality, turned ? 1 : 0, swapRedBlue ? 1 : 0};
+    if (filename.empty() || !pixels || !jpegSourceInRange(source))
+        return false;
+    std::vector<short> coefficients;
+    if (!jpegCoefficients(source, pixels, coefficients))
+        return false;
+    unsigned short quant[2][64];
+    jpe::quantTable(jpegQuality, 0, quant[0]);
+    jpe::quantTable(jpegQuality, 1, quant[1]);
+    return JpegWriter::writeFile(filename, JpegWriter::encode(width, height, lumaH, lumaV, quant, coefficients.data(),
+                                                              (long)(coefficients.size() / 64)));
+}
+
+/* reference: GPUKernel.cpp:2792-2852; what differs is said in GPUKernel.h */
+void GPUKernel::generateScreenshot(const std::string &filename, const unsigned int width, const unsigned int height,
+                                   const unsigned int quality)
+{
+    flushFrames();
+    const SceneInfo bakSceneInfo = m_sceneInfo;
+    SceneInfo sceneInfo = m_sceneInfo;
+    sceneInfo.size.x = (int)std::min<unsigned int>(std::max(width, 1u), MAX_BITMAP_WIDTH);
+    sceneInfo.size.y = (int)std::min<unsigned int>(std::max(height, 1u), MAX_BITMAP_HEIGHT);
+    sceneInfo.maxPathTracingIterations = (int)quality;
+    const bool resized = sceneInfo.size.x != bakSceneInfo.size.x || sceneInfo.size.y != bakSceneInfo.size.y;
+    m_sceneInfo = sceneInfo;
+    if (resized)
+        reshape();
+    m_refresh = true;
+    bool rendered = quality > 0;
+    for (unsigned int i = 0; i < quality && rendered; ++i)
+    {
+        sceneInfo.pathTracingIteration = (int)i;
+        m_sceneInfo = sceneInfo;
+        render_begin(0);
+        render_end();
+        rendered = lastError() == 0;
+    }
+    if (rendered)
+    {
+        flushFrames(); /* with frames in flight the image on show lags behind: wait for the last pass's */
+        const BitmapBuffer *bitmap = getBitmap();
+        /* jpge's default parameters (jpge.h:31-34): quality 85, H2V2 */
+        if (!bitmap || !encodeJpeg(filename, bitmap, sceneInfo.size.x, sceneInfo.size.y, 85, 2, 2, true,
+                                   sceneInfo.frameBufferType != ftRGB))
+            std::cerr << "GPUKernel::generateScreenshot: " << filename << " was not written" << std::endl;
+        /* the frame that was encoded stays what getBitmap() shows until the next frame is rendered, as in the reference,
+         * whose m_bitmap it is; with frames in flight it sits in the engine's image, which goes with the re-shape */
+        const size_t frameBytes = (size_t)sceneInfo.size.x * (size_t)sceneInfo.size.y * (size_t)SOLR_COLOR_DEPTH;
+        if (bitmap && bitmap != m_bitmap.data() && m_bitmap.size() >= frameBytes)
+            memcpy(m_bitmap.data(), bitmap, frameBytes);
+    }
+    m_sceneInfo = bakSceneInfo;
+    if (resized)
+        reshape();
 }
 
 /* reference: GPUKernel.cpp:2691-2705 */

@@ -10,7 +10,7 @@
  * argument order and the dirty-flag protocol (GPUKernel.h:371-374,387) are the
  * reference's, so code written against the reference class reads the same
  * here.  Out of scope (and absent): fake-GL vertex assembly, Kinect/Oculus
- * hooks, JPEG screenshots.
+ * hooks.
  *
  * The flattened arrays this class produces (BoundingBox[], Primitive[],
  * Lamp[], LightInformation[], Material[]) are bit-for-bit what the reference
@@ -388,6 +388,27 @@ public:
     bool loadTextureFromFile(const int index, const std::string &filename);
     std::string getTextureFilename(const int index);
 
+    /* ---------- Screenshots (GPUKernel.h:262 of the reference, GPUKernel.cpp:2792-2852) ---------- */
+    /* `quality` passes of path tracing (pathTracingIteration 0 ... quality - 1 of maxPathTracingIterations = quality)
+     * at width x height, clamped to MAX_BITMAP_WIDTH x MAX_BITMAP_HEIGHT, then the last image as a JPEG file with the
+     * reference encoder's default parameters (quality 85, 2x2 chroma).  The reference writes the file after every pass;
+     * here it is written once, after the last.  The picture is read as the reference reads it: pixel p from pixel
+     * N - p of the frame (N = width * height; for p = 0 the reference reads one pixel past the frame, here that index is
+     * N - 1), red and blue swapped unless the frame buffer is ftRGB.  Frames in flight are flushed first, the buffers
+     * re-shaped for the screenshot and back, the scene info restored.  Nothing is written when a pass fails.  Until the
+     * next frame is rendered getBitmap() is the frame that was encoded (width * height * 3 bytes of the screenshot's size). */
+    void generateScreenshot(const std::string &filename, const unsigned int width, const unsigned int height,
+                            const unsigned int quality);
+    /* extension: the encoder alone, on the caller's width * height * 3 bytes; false when an argument is out of range
+     * (nothing is written), the engine failed or the file could not be written */
+    /* the engine's pixel stage alone (the jpegCoefficients hook), for the tests */
+    bool jpegCoefficientsOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<short> &coefficients)
+    {
+        return jpegCoefficients(source, rgb, coefficients);
+    }
+    bool encodeJpeg(const std::string &filename, const unsigned char *pixels, int width, int height, int jpegQuality,
+                    int lumaH, int lumaV, bool turned, bool swapRedBlue);
+
     /* ---------- Scene (GPUKernel.h:208-221) ---------- */
     void setSceneInfo(int width, int height, float transparentColor, int graphicsLevel, float viewDistance,
                       float shadowIntensity, int nbRayIterations, vec4f backgroundColor, int cameraType,
@@ -532,6 +553,11 @@ protected:
      * ImageLoader::parseJPEG leaves them to frame.width * frame.height * 3 bytes in `rgb`.  Here: a loop on the CPU;
      * false = the engine failed (its error is pending) */
     virtual bool jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb);
+    /* engine hook: the pixel stage of a JPEG screenshot (csrc/jpeg_encode.h) - width * height * 3 bytes in `rgb`, read
+     * as `source` says, to quantised coefficient blocks in MCU and zigzag order (`coefficients` is resized).  Here: a
+     * loop on the CPU; false = the arguments are out of range or the engine failed (its error is pending) */
+    virtual bool jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb,
+                                  std::vector<short> &coefficients);
     void rotatePrimitivesOnly(Frame &f, const vec3f &rotationCenter, const vec3f &cosA, const vec3f &sinA);
     void refitBoxes(Frame &f);
 

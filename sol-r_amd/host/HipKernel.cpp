@@ -221,6 +221,21 @@ bool HipKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> 
     return solr_hip_jpeg_to_rgb(&frame, coefficients.data(), (long)(coefficients.size() / 64), rgb) == 0;
 }
 
+bool HipKernel::jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb, std::vector<short> &coefficients)
+{
+    if (solr_hip_device_count() < 1)
+        return GPUKernel::jpegCoefficients(source, rgb, coefficients);
+    /* (the sizes below are only meaningful for arguments the engine accepts; it refuses the others itself) */
+    long nbBlocks = 0;
+    if (source.width >= 1 && source.height >= 1 && source.width <= SOLR_JPEG_MAX_SIDE &&
+        source.height <= SOLR_JPEG_MAX_SIDE && source.lumaH >= 1 && source.lumaH <= 2 && source.lumaV >= 1 &&
+        source.lumaV <= 2)
+        nbBlocks = (long)((source.width + 8 * source.lumaH - 1) / (8 * source.lumaH)) *
+                   ((source.height + 8 * source.lumaV - 1) / (8 * source.lumaV)) * (source.lumaH * source.lumaV + 2);
+    coefficients.resize((size_t)nbBlocks * 64);
+    return solr_hip_rgb_to_jpeg_blocks(&source, rgb, coefficients.data(), nbBlocks) == 0;
+}
+
 int HipKernel::deviceBuildTree(const std::vector<Primitive> &primitives, const std::vector<unsigned char> &emissive,
                                const vec3f &minPos, const vec3f &maxPos, float viewDistance,
                                std::vector<BoundingBox> &boxes, std::vector<int> &order, int &nbLamps)

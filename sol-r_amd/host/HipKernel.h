@@ -66,6 +66,9 @@ protected:
                         std::vector<int> &order, int &nbLamps) override;
     /* solr_hip_jpeg_to_rgb (include/solr_hip.h) where there is a device, the base class's loop where there is none */
     bool jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb) override;
+    /* solr_hip_rgb_to_jpeg_blocks (include/solr_hip.h) where there is a device, the base class's loop where there is none */
+    bool jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb,
+                          std::vector<short> &coefficients) override;
 
 private:
     vec4i m_blockSize;

@@ -1,0 +1,27 @@
+/*
+ * JpegWriter.h - the entropy half of the JPEG screenshot writer: quantised coefficient blocks, as the pixel stage
+ * (csrc/jpeg_encode.h) leaves them, to the bytes of a baseline JPEG file.
+ *
+ * The file is the one the reference's encoder writes in its one-pass mode (solr/images/jpge.cpp): the markers in the
+ * order of emit_markers (:517-525) - SOI, JFIF APP0, one DQT per table, SOF0, four DHT segments with the standard tables
+ * of ITU T.81 annex K.3, SOS - then one interleaved scan coded as code_coefficients_pass_two does (:883-952), closed by
+ * terminate_pass_two (:1032-1039).  Serial work: it stays on the host with either engine.
+ */
+#pragma once
+
+#include <string>
+#include <vector>
+
+namespace solr
+{
+class JpegWriter
+{
+public:
+    /* quant: the luma and the chroma table in zigzag order (jpe::quantTable); blocks: nbBlocks x 64 coefficients in
+     * MCU order - the luma blocks row by row, then Cb, then Cr - each in zigzag order.  lumaH x lumaV is 1x1, 2x1 or
+     * 2x2.  Returns the file's bytes. */
+    static std::vector<unsigned char> encode(int width, int height, int lumaH, int lumaV,
+                                             const unsigned short quant[2][64], const short *blocks, long nbBlocks);
+    static bool writeFile(const std::string &filename, const std::vector<unsigned char> &bytes);
+};
+}

@@ -8,10 +8,13 @@
 
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/solr_hip.h"
 #include "FileMarshaller.h"
 #include "GPUKernel.h"
+#include "JpegWriter.h"
+#include "../csrc/jpeg_encode.h"
 #include "OBJReader.h"
 #include "PDBReader.h"
 #include "SWCReader.h"
@@ -177,6 +180,75 @@ int SolR_RunKernel(double timer, BitmapBuffer *image)
     kernel->render_begin(static_cast<float>(timer));
     kernel->render_end(image);
     return engineStatus();
+}
+
+/* reference: SolRStub.cpp:546-550 - always 0.  `quality` is the number of path-tracing passes, not the JPEG quality
+ * (GPUKernel::generateScreenshot).  The scene and post-processing settings are the ones SolR_RunKernel would render with. */
+int SolR_GenerateScreenshot(char *filename, int width, int height, int quality)
+{
+    solr::GPUKernel *kernel = SingletonKernel::kernel();
+    kernel->setSceneInfo(gSceneInfoStub);
+    kernel->setPostProcessingInfo(gPostProcessingInfoStub);
+    kernel->generateScreenshot(filename ? filename : "", width < 0 ? 0 : width, height < 0 ? 0 : height,
+                               quality < 0 ? 0 : quality);
+    return 0;
+}
+
+/* Extension: the screenshot's encoder alone on the caller's pixels (GPUKernel::encodeJpeg): 0, or -1 when an argument is
+ * out of range - nothing is written then - or the file could not be written */
+int SolRx_EncodeJpeg(const char *filename, const unsigned char *pixels, int width, int height, int jpegQuality,
+                     int lumaH, int lumaV, int turned, int swapRedBlue)
+{
+    if (!filename || !pixels)
+        return -1;
+    return SingletonKernel::kernel()->encodeJpeg(filename, pixels, width, height, jpegQuality, lumaH, lumaV,
+                                                 turned != 0, swapRedBlue != 0)
+               ? 0
+               : -1;
+}
+
+/* Extensions for the tests of the encoder's two halves.  SolRx_JpegCoefficients: the engine's pixel stage alone
+ * (GPUKernel::jpegCoefficients) - `coefficients` has room for nbBlocks blocks of 64, which must be the number the
+ * picture has.  SolRx_JpegFromCoefficients: the writer alone (host/JpegWriter.h).  SolRx_JpegQuantise: count values
+ * first, first + 1, ... (negated if negative != 0) through jpe::quantise with quantiser q. */
+int SolRx_JpegCoefficients(const unsigned char *pixels, int width, int height, int jpegQuality, int lumaH, int lumaV,
+                           int turned, int swapRedBlue, short *coefficients, long nbBlocks)
+{
+    if (!pixels || !coefficients)
+        return -1;
+    const SolrJpegSource source = {width, height, lumaH, lumaV, jpegQuality, turned, swapRedBlue};
+    std::vector<short> blocks;
+    if (!SingletonKernel::kernel()->jpegCoefficientsOf(source, pixels, blocks) || (long)(blocks.size() / 64) != nbBlocks)
+        return -1;
+    memcpy(coefficients, blocks.data(), blocks.size() * sizeof(short));
+    return 0;
+}
+
+int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, long nbBlocks, int width, int height,
+                               int jpegQuality, int lumaH, int lumaV)
+{
+    if (!filename || !coefficients || width < 1 || height < 1 || jpegQuality < 1 || jpegQuality > 100 ||
+        !jpe::samplingSupported(lumaH, lumaV) ||
+        nbBlocks != (long)((width + 8 * lumaH - 1) / (8 * lumaH)) * ((height + 8 * lumaV - 1) / (8 * lumaV)) *
+                        jpe::blocksPerMcu(lumaH, lumaV))
+        return -1;
+    unsigned short quant[2][64];
+    jpe::quantTable(jpegQuality, 0, quant[0]);
+    jpe::quantTable(jpegQuality, 1, quant[1]);
+    return solr::JpegWriter::writeFile(filename, solr::JpegWriter::encode(width, height, lumaH, lumaV, quant,
+                                                                          coefficients, nbBlocks))
+               ? 0
+               : -1;
+}
+
+int SolRx_JpegQuantise(int q, int first, int count, int negative, short *out)
+{
+    if (q < 1 || q > 255 || first < 0 || count < 0 || (long)first + count - 1 + (q >> 1) > jpe::MAX_MAGNITUDE || !out)
+        return -1;
+    const jpe::u32 m = jpe::reciprocal(q);
+    for (int i = 0; i < count; ++i)
+        out[i] = jpe::quantise(negative ? -(first + i) : first + i, q, m);
+    return 0;
 }
 
 int SolR_AddPrimitive(int type, int movable)

@@ -6,9 +6,10 @@
  * exceptions across the boundary) for every call that feeds or runs the
  * rendering path, including the scene-file loaders (SolR_LoadMolecule,
  * SolR_LoadOBJModel, SolR_SaveToFile, SolR_LoadFromFile) and the texture-file
- * loader (SolR_LoadTextureFromFile).  Not provided (out of scope, SURVEY.md
- * section 2): the OpenCL queries, SolR_GenerateScreenshot (a JPEG encoder) and
- * the Kinect call.
+ * loader (SolR_LoadTextureFromFile) and the screenshot (SolR_GenerateScreenshot:
+ * a JPEG file, byte for byte the one the reference's encoder writes for the
+ * same frame).  Not provided (out of scope): the three
+ * OpenCL-device queries and the Kinect call.
  *
  * SolRx_* are extensions used by the test-suite and bench.py: engine
  * selection, deterministic timestamps/randoms, access to the flattened arrays
@@ -123,6 +124,21 @@ int SolR_GetNbTextures(int *nbTextures);
 int SolR_LoadTextureFromFile(int index, char *filename);
 /* extension: the TextureType the loader derived from the file's name, -1 for a slot out of range */
 int SolRx_GetTextureType(int index);
+
+/* ---------- Screenshots (SolRStub.h:62) ---------- */
+/* `quality` passes of path tracing at width x height (at most 1920 x 1080), the last image as a JPEG file of JPEG
+ * quality 85 with 2x2 chroma (the reference encoder's defaults); always 0, as in the reference */
+int SolR_GenerateScreenshot(char *filename, int width, int height, int quality);
+/* the screenshot's encoder on the caller's width * height * 3 bytes: JPEG quality 1..100, luma sampling 1x1, 2x1 or
+ * 2x2; turned / swapRedBlue read the pixels as a screenshot reads a frame (include/solr_hip.h, SolrJpegSource) */
+int SolRx_EncodeJpeg(const char *filename, const unsigned char *pixels, int width, int height, int jpegQuality,
+                     int lumaH, int lumaV, int turned, int swapRedBlue);
+/* the two halves of the encoder and its division, for the tests (SolRStub.cpp) */
+int SolRx_JpegCoefficients(const unsigned char *pixels, int width, int height, int jpegQuality, int lumaH, int lumaV,
+                           int turned, int swapRedBlue, short *coefficients, long nbBlocks);
+int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, long nbBlocks, int width, int height,
+                               int jpegQuality, int lumaH, int lumaV);
+int SolRx_JpegQuantise(int q, int first, int count, int negative, short *out);
 
 /* ---------- Extensions ---------- */
 /* "hip" (default) or "host-only"; destroys the current singleton */
