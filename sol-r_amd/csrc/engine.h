@@ -1,6 +1,6 @@
 /*
  * engine.h - the state of the MI355X rendering engine and the helpers every part of its host side uses: what
- * solr_hip.hip (the boundary), solr_scene.hip (scene upload, list builders), solr_launch.hip (the renderer's launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined
+ * solr_hip.hip (the boundary), solr_scene.hip (scene upload, the node lists; their host builders: list_builders.h), solr_launch.hip (the renderer's launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined
  * read-back), solr_rccl.hip (strips, communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  gfx950 only.
  */
@@ -20,6 +20,7 @@
 #include "../../include/solr_hip.h"
 #include "renderer.h"
 #include "lists_device.h"
+#include "list_builders.h"
 
 namespace solreng
 {
@@ -169,6 +170,48 @@ enum Variant
     VARIANT_NO_LAMP_CUTOFF = 15  /* shadow walks in the reference's order keep the reference's cut-off alone */
 };
 
+/* A node list of the resident scene: its host image, the count a frame is told, where the arena holds it (the layout
+ * itself is scene_layout.h's), and what is known about it.  Behind its rows the arena holds one pad record - the walk
+ * requests the record after the node it tests (rt_device.h advanceTidy), after the last node too - then, for a list
+ * kept in more than one copy, the thin copy (tightenList; rt_device.h tightRay) and the copy with sorted bounds
+ * (k_sortNodeBounds), each padded alike: the functions below are the only place that knows where. */
+struct NodeList
+{
+    int copies, lists; /* how often the arena holds the rows (1 ... 3); lists one behind the other (eight order-free ones) */
+    explicit NodeList(int copies_ = 1, int lists_ = 1) : copies(copies_), lists(lists_) {}
+    std::vector<float4> rows;       /* host image: two rows a node (list_builders.h) */
+    std::vector<int> start, origin; /* ... its first primitive, the node of the reference's list it is (-1: ours) */
+    int nb = 0;                     /* nodes per list, as a frame is told */
+    unsigned offRows = 0, offLeaf = 0; /* float4 rows of the arena: node rows, leaf records (64 bytes a node) */
+    unsigned offStart = 0;             /* ints of the arena: start indices */
+    int ordered = 0;                /* sign-free slab test allowed on it */
+    bool tight = false;             /* the thin copy behind it is up to date */
+    std::vector<int> refitLevels;   /* [offset, count] per height, offsets into Engine::refitPlan (ints) */
+
+    void reset() { *this = NodeList(copies, lists); }
+    unsigned nodes() const { return (unsigned)lists * (unsigned)nb; }
+    unsigned rowsOf(int list) const { return offRows + 2u * (unsigned)list * (unsigned)nb; }
+    unsigned offThin() const { return offRows + 2u * nodes() + 2u; }
+    unsigned offSorted() const { return offRows + 2u * (2u * nodes() + 2u); }
+    /* the three parts of the layout: each takes the first free row and returns the next */
+    unsigned layRows(unsigned row)
+    {
+        offRows = row;
+        return row + (unsigned)copies * (2u * nodes() + 2u);
+    }
+    unsigned layStart(unsigned row)
+    {
+        offStart = row * 4;
+        return row + (nodes() + 3u) / 4u;
+    }
+    unsigned layLeaf(unsigned row)
+    {
+        row = (row + 3u) & ~3u; /* one 64-byte line per node */
+        offLeaf = row;
+        return row + 4u * nodes() + 4u;
+    }
+};
+
 struct Engine
 {
     bool initialized = false;
@@ -181,32 +224,28 @@ struct Engine
     /* scene planes */
     /* two arenas (scene_layout.h) and their host images */
     DeviceBuffer geometry, materials, textures, randoms, lamps;
-    std::vector<float4> hostBoxes, hostBoxesCompact, hostPrims, hostLights;
-    std::vector<int> hostBoxStart, hostBoxStartCompact, hostOriginCompact;
+    std::vector<float4> hostPrims, hostLights;
+    /* the node lists: the reference's as uploaded; the walk-order list (chains collapsed, siblings grouped, inner nodes
+     * that hardly cull pruned) with its thin copy; the eight order-free lists, one per direction octant - the leaves of
+     * the scene under a surface-area hierarchy of our own (buildFreeOrderLists) - with thin and sorted copies */
+    NodeList exact = NodeList(1, 1), walk = NodeList(2, 1), orderFree = NodeList(3, 8);
     int freeCountdown = 0; /* renders until the order-free lists are built (0: not scheduled) */
-    /* the order-free list: the leaves of the scene under a surface-area hierarchy of our own (buildFreeOrderList) */
-    std::vector<float4> hostBoxesFree;
-    std::vector<int> hostBoxStartFree;
-    /* lists built on the device stay there: `freeRows` float4 rows (16 per node of a list) that go into the arena with
-     * a device-to-device copy (freeStage, until the next flushGeometry); the host images above are filled from the
-     * arena when somebody needs them (ensureHostFreeLists: the refit plan of a rotated scene, a second layout) */
-    size_t freeRows = 0;
+    /* lists built on the device stay there and go into the arena with a device-to-device copy (freeStage, until the
+     * next flushGeometry); orderFree's host image is filled from the arena when somebody needs it (ensureHostFreeLists:
+     * the refit plan of a rotated scene, a second layout) */
     bool freeHostValid = true;
     bool freeDirty = false;  /* the staged lists are to be added to an arena that is otherwise up to date */
     unsigned rowsFixed = 0;  /* rows of the arena in front of the order-free lists */
     SolrDeviceLists freeStage;
-    unsigned offBoxesFree = 0, offBoxStartFree = 0, offLeafFree = 0;
-    int nbBoxesFree = 0;        /* nodes per list; there are eight, one per direction octant */
     bool freeStale = false;     /* rotated on the device since it was built: not refitted, not walked */
     bool primsContained = false; /* every primitive lies inside its leaf's box (retagPrimitives) */
     bool opaqueShadows = false;  /* no transparent primitive, no textured plane (retagPrimitives) */
     /* the walk-order list as the arena holds it: every inner node contains its children, every leaf its primitives
      * (checked at h2d_scene and again after every rotation on the device; lampCutoffUsable) */
-    bool compactEncloses = false;
+    bool walkEncloses = false;
     /* the thin copies of the walk-order list and of the order-free lists (tightenList; rt_device.h tightRay) */
     bool plainPlanes = false;    /* the scene holds a plain axis plane: thin copies are worth making (retagPrimitives) */
     float sceneExtent = 1.f;     /* max |coordinate| + |size| over the primitives, at least 1 */
-    bool tightCompact = false, tightFree = false; /* the copy behind that list is up to date */
     bool sortedFree = false;                      /* the copy of the order-free lists with sorted bounds is up to date */
     /* bounce rays on the order-free lists, checked (rt_device.h closestHitWalk): -1 the engine decides per frame
      * (shortRayListsChoice: with frames in flight), 0 / 1 forced */
@@ -225,13 +264,10 @@ struct Engine
     bool textureTablesChecked = false;
     std::vector<float> materialAverage; /* (r + g + b) / 3.f per material id (plane colour key, GI:561) */
     int sceneFeatures = F_ALL & ~F_FULL; /* rt_device.h enum Feature, recomputed with the tags */
-    unsigned offBoxes = 0, offBoxesCompact = 0, offBoxStart = 0, offBoxStartCompact = 0, offPrims = 0, offLights = 0;
-    unsigned offLeaf = 0, offLeafCompact = 0; /* leaf records of the two node lists (scene_layout.h) */
+    unsigned offPrims = 0, offLights = 0;
     unsigned offMatCold = 0;
     bool geometryDirty = true;
-    int nbBoxesCompact = 0;
-    int orderedExact = 0, orderedCompact = 0; /* sign-free slab test allowed on that node list */
-    int nbBoxes = 0, nbPrimitives = 0, nbLights = 0, nbLamps = 0, nbMaterials = 0;
+    int nbPrimitives = 0, nbLights = 0, nbLamps = 0, nbMaterials = 0;
     int nested = 1;
     long nbRandoms = 0;
 
@@ -337,12 +373,8 @@ struct Engine
     DeviceBuffer movable, refitPlan;
     DeviceBuffer enclosesFlag; /* k_listEncloses' answer */
     int nbMovable = -1;                 /* flags uploaded for that many primitives, -1: none */
-    std::vector<int> refitLevels;       /* exact list: [offset, count] per height, offsets into refitPlan (ints) */
-    std::vector<int> refitWalkLevels;   /* walk-order list, same form */
-    std::vector<int> refitFreeLevels;   /* the eight order-free lists as one forest, same form */
     bool refitReady = false;
     bool refitPlanPending = false;      /* the lists changed: the plan is made when the first rotation asks (ensureRefitPlan) */
-    std::vector<int> hostOriginFree;    /* per node of the order-free lists: the node of the reference's list it is, -1: ours */
     bool exactStale = false;            /* the exact list has not been refitted since the last rotation */
     float exactStaleViewDistance = 0.f;
     bool deviceAhead = false;           /* the arena has moved on from the host images */
@@ -498,19 +530,6 @@ void upload(DeviceBuffer &b, const std::vector<T> &host)
         HIPCHECK(hipMemcpyAsync(b.ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, g.stream));
         HIPCHECK(hipStreamSynchronize(g.stream));
     }
-}
-
-inline int bitsi(float v)
-{
-    int i;
-    memcpy(&i, &v, sizeof(i));
-    return i;
-}
-inline float bitsf(int v)
-{
-    float f;
-    memcpy(&f, &v, 4);
-    return f;
 }
 
 inline int stripRows()

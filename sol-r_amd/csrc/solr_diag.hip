@@ -502,7 +502,7 @@ void solr_hip_memory_usage(unsigned long long bytes[4])
  * not 6), else 0. */
 extern "C" int solr_hip_order_free_nodes(void)
 {
-    return (g.initialized && orderFreeListsUsable()) ? g.nbBoxesFree : 0;
+    return (g.initialized && orderFreeListsUsable()) ? g.orderFree.nb : 0;
 }
 
 /* Extension: 1 if the shadow walks of the resident scene take the order-free lists as well (they are in use and

@@ -284,24 +284,19 @@ static void finalizeOne()
     g.initialized = false;
     g.refitReady = false;
     g.refitPlanPending = false;
-    g.hostOriginFree.clear();
     g.exactStale = false;
     g.deviceAhead = false;
-    g.compactEncloses = false;
+    g.walkEncloses = false;
     g.nbMovable = -1;
     g.nbDeviceRotations = 0;
-    g.nbBoxes = g.nbPrimitives = g.nbLights = g.nbLamps = g.nbMaterials = 0;
+    g.nbPrimitives = g.nbLights = g.nbLamps = g.nbMaterials = 0;
     g.allocW = g.allocRows = 0;
     g.boundBitmap = nullptr;
-    g.hostBoxes.clear();
-    g.hostBoxesCompact.clear();
+    g.exact.reset();
+    g.walk.reset();
+    g.orderFree.reset();
     g.hostPrims.clear();
     g.hostLights.clear();
-    g.hostBoxStart.clear();
-    g.hostBoxStartCompact.clear();
-    g.hostBoxesFree.clear();
-    g.hostBoxStartFree.clear();
-    g.freeRows = 0;
     g.freeHostValid = true;
     g.freeDirty = false;
     dropFreeStage(true);
@@ -310,8 +305,6 @@ static void finalizeOne()
         std::lock_guard<std::mutex> nobodyBuilding(pool.busy);
         pool.release();
     }
-    g.hostOriginCompact.clear();
-    g.nbBoxesFree = 0;
     g.freeCountdown = 0;
     g.freeStale = false;
     g.materialTags.clear();

@@ -192,7 +192,7 @@ static bool frameReady(const SceneInfo &sceneInfo, const vec4i &objects)
     if (!ready("cudaRender"))
         return false;
     ARGCHECK(sceneInfo.size.x > 0 && sceneInfo.size.y > 0, "cudaRender: empty image");
-    ARGCHECK(objects.x <= g.nbBoxes && objects.y <= g.nbPrimitives, "cudaRender: more objects than were uploaded");
+    ARGCHECK(objects.x <= g.exact.nb && objects.y <= g.nbPrimitives, "cudaRender: more objects than were uploaded");
     ARGCHECK(objects.w <= g.nbLights, "cudaRender: more lights than were uploaded");
     ARGCHECK(g.materials.ptr != nullptr, "cudaRender: no materials uploaded");
     ARGCHECK(sceneInfo.skyboxMaterialId <= NB_MAX_MATERIALS, "cudaRender: skybox material beyond the material table");
@@ -242,7 +242,7 @@ static int takeFlight(const SceneInfo &sceneInfo, bool counting)
  * every hit, nearest first, ties in the order it met them.)  False: the engine's error is set. */
 static bool frameScene(const SceneInfo &sceneInfo, const vec4i &objects, bool counting, SceneArgs &S)
 {
-    const bool exactNodes = counting || sceneInfo.renderBoxes != 0 || objects.x != g.nbBoxes || g.variant == VARIANT_EXACT_LIST ||
+    const bool exactNodes = counting || sceneInfo.renderBoxes != 0 || objects.x != g.exact.nb || g.variant == VARIANT_EXACT_LIST ||
                             sceneInfo.cameraType == ctVolumeRendering;
     S = prepareScene(sceneInfo, exactNodes);
     if (!ok())

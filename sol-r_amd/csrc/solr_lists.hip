@@ -1,5 +1,5 @@
 /*
- * solr_lists.hip - the order-free node lists (solr_scene.hip, buildFreeOrderLists) built on the device.
+ * solr_lists.hip - the order-free node lists (list_builders.cpp, buildFreeOrderLists) built on the device.
  *
  * What is built is the engine's own hierarchy over the reference's leaves, not anything of the reference's: a
  * binary surface-area tree (binned SAH, sixteen bins, over the leaf boxes' centres), the inner nodes that hardly
@@ -349,7 +349,7 @@ __device__ inline double areaOf(const float *lo, const float *hi)
     return x * y + y * z + z * x;
 }
 
-/* the host's cost loop (solr_scene.hip buildFreeOrderLists), one thread per open node */
+/* the host's cost loop (list_builders.cpp buildFreeOrderLists), one thread per open node */
 __global__ void k_split(Node *nodes, const BinSet *bins, int levelFirst, int count, int nextFree, int *splitting)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -476,7 +476,7 @@ __global__ void k_scatter(const Node *nodes, const int *nodeOf, const int *order
     orderOut[to] = order[i];
 }
 
-/* Which inner nodes stay (solr_scene.hip pruneInnerNodes on the octant-0 flattening): one workgroup per node of the
+/* Which inner nodes stay (list_builders.cpp pruneInnerNodes on the octant-0 flattening): one workgroup per node of the
  * level, top-down, so that the nearest kept ancestor is known.  The leaves of a node in octant-0 order are the
  * positions [from, to) of the final leaf order. */
 __global__ __launch_bounds__(256) void k_prune(Node *nodes, const int *order, const float *llo, const float *lhi, int levelFirst,
@@ -619,7 +619,6 @@ inline dim3 blocksFor(size_t n, int block = 256)
 } // namespace
 
 int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const int *origin, int n, double threshold,
-                                    std::vector<float4> &outRows, std::vector<int> &outStart, std::vector<int> &outOrigin,
                                     int *nbPruned, hipStream_t stream, SolrDeviceLists *stay)
 {
     *nbPruned = 0;
@@ -774,35 +773,22 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
     phase.mark("pruning, sizes, places", listLength);
     if (listLength < 2)
         return -1;
-    if (stay ? !dOutRows.allocOwn(16 * (size_t)listLength) || !dOutStart.allocOwn(8 * (size_t)listLength) ||
-                   !dOutOrigin.allocOwn(8 * (size_t)listLength)
-             : !dOutRows.alloc(16 * (size_t)listLength) || !dOutStart.alloc(8 * (size_t)listLength) || !dOutOrigin.alloc(8 * (size_t)listLength))
+    if (!dOutRows.allocOwn(16 * (size_t)listLength) || !dOutStart.allocOwn(8 * (size_t)listLength) ||
+        !dOutOrigin.allocOwn(8 * (size_t)listLength))
         return -1;
     hipLaunchKernelGGL(k_emit, blocksFor((size_t)nbNodes * 8), dim3(256), 0, stream, dNodes.p, dPlace.p, dLeafRows.p, dLeafStart.p, dLeafOrigin.p,
                        dOutRows.p, dOutStart.p, dOutOrigin.p, nbNodes, listLength);
     LISTS_CHECK(hipGetLastError());
-    if (stay)
-    {
-        LISTS_CHECK(hipStreamSynchronize(stream));
-        stay->rows = dOutRows.p, stay->start = dOutStart.p, stay->origin = dOutOrigin.p;
-        dOutRows.p = nullptr, dOutStart.p = nullptr, dOutOrigin.p = nullptr;
-        phase.mark("lists written");
-        return listLength;
-    }
-    outRows.resize(16 * (size_t)listLength);
-    outStart.resize(8 * (size_t)listLength);
-    outOrigin.resize(8 * (size_t)listLength);
-    LISTS_CHECK(hipMemcpyAsync(outRows.data(), dOutRows.p, outRows.size() * 16, hipMemcpyDeviceToHost, stream));
-    LISTS_CHECK(hipMemcpyAsync(outStart.data(), dOutStart.p, outStart.size() * 4, hipMemcpyDeviceToHost, stream));
-    LISTS_CHECK(hipMemcpyAsync(outOrigin.data(), dOutOrigin.p, outOrigin.size() * 4, hipMemcpyDeviceToHost, stream));
     LISTS_CHECK(hipStreamSynchronize(stream));
 #undef LISTS_CHECK
-    phase.mark("lists written and copied back");
+    stay->rows = dOutRows.p, stay->start = dOutStart.p, stay->origin = dOutOrigin.p;
+    dOutRows.p = nullptr, dOutStart.p = nullptr, dOutOrigin.p = nullptr;
+    phase.mark("lists written");
     return listLength;
 }
 
 
-/* ---- pruneInnerNodes' decisions for a node list with skip pointers (solr_scene.hip), on the device ------------------------
+/* ---- pruneInnerNodes' decisions for a node list with skip pointers (list_builders.cpp), on the device ------------------------
  * The host walks the list once and, for every inner node, samples up to 8 000 leaf centres of its nearest kept
  * ancestor: 13 + 8 ms of h2d_scene for the 100k-primitive scenes.  The decisions of one depth of the list are
  * independent of each other once the depths above are decided, so: parents and depths on the host (one pass with a

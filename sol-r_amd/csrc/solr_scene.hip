@@ -3,29 +3,20 @@
  * h2d_randoms / h2d_lightInformation (CudaRayTracer.cu:1536-1625) leave on the device, and the lists the walks take.
  *   - the arena's device kernels: leaf records, thin copies of plain-plane leaves, the enclosure check, rotation and refit
  *     of animated scenes;
- *   - the host side of the uploads: row conversion (scene_layout.h), material tags, texture tables, the walk-order list
- *     (chains collapsed, siblings grouped, inner nodes that hardly cull pruned) and the order-free lists, built on the
- *     device (solr_lists.hip) when they are due;
+ *   - the host side of the uploads: row conversion (scene_layout.h), material tags, texture tables, the three node
+ *     lists (engine.h NodeList) and their place in the arena.  The walk-order list comes from the host builders
+ *     (list_builders.cpp); the order-free lists are built on the device (solr_lists.hip) when they are due, by the host
+ *     builders where that is switched off or declines;
  *   - prepareScene(): the SceneArgs a frame's launch is handed.
  * Part of the engine's host side (engine.h); the boundary that calls into it is solr_hip.hip.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <fcntl.h>
-#include <sched.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <atomic>
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <functional>
-#include <chrono>
 #include <vector>
 
 #include "../../include/solr_hip.h"
@@ -42,6 +33,12 @@ using namespace solreng;
 
 namespace solreng
 {
+/* list_builders.h names the rows of a primitive record on its own (it is compiled without the device headers) */
+static_assert((int)LB_ROW_P0_TYPE == (int)ROW_P0_TYPE && (int)LB_ROW_SIZE_MAT == (int)ROW_SIZE_MAT &&
+                  (int)LB_ROW_P1_INDEX == (int)ROW_P1_INDEX && (int)LB_ROW_P2 == (int)ROW_P2 && (int)LB_PRIM_ROWS == (int)PRIM_ROWS &&
+                  (int)LB_PRIM_TYPE_MASK == (int)PRIM_TYPE_MASK,
+              "list_builders.h and scene_layout.h disagree about the primitive record");
+
 /* ---- animated scenes: rotate + refit on the device ---------------------------------------------------
  * The reference animates a scene by GPUKernel::rotatePrimitives + compactBoxes(false) on the host and a
  * full upload, every frame (MoleculeScene.cpp:75-81; GPUKernel.cpp:1378-1460 rotates the primitives of
@@ -391,25 +388,6 @@ __global__ __launch_bounds__(256) void k_refitNodes(float4 *__restrict__ arena, 
     rows[2 * node + 1] = make_float4(hx, hy, row1.z, row1.w);
 }
 
-/* skip pointers must describe nested intervals for the ballot-only walk */
-int validateNesting(const BoundingBox *boxes, int n)
-{
-    std::vector<int> ends;
-    for (int i = 0; i < n; ++i)
-    {
-        const int skip = boxes[i].indexForNextBox.x;
-        if (skip < 1 || (long)i + skip > n)
-            return 0;
-        while (!ends.empty() && ends.back() <= i)
-            ends.pop_back();
-        const int end = i + skip;
-        if (!ends.empty() && end > ends.back())
-            return 0;
-        ends.push_back(end);
-    }
-    return 1;
-}
-
 /* join the material facts the walks need into every primitive's tag (scene_layout.h) */
 int materialTag(const Material &m)
 {
@@ -443,88 +421,29 @@ int materialTag(const Material &m)
  * Both give a node of the reference's tree the same bounds: min / max over the level-0 boxes below it,
  * clamped once or several times by the same +-viewDistance seed, first occurrence winning a tie in either
  * nesting.  Node 0, the light cell, keeps its +-viewDistance (GPUKernel.cpp:1189). */
-static void buildRefitPlan(const std::vector<float4> &exact, const std::vector<float4> &walk, const std::vector<int> &origin,
-                           const std::vector<float4> &free, const std::vector<int> &freeOrigin)
+static void buildRefitPlan()
 {
     g.refitReady = false;
     g.exactStale = false;
-    g.refitLevels.clear();
-    g.refitWalkLevels.clear();
-    g.refitFreeLevels.clear();
+    for (NodeList *list : {&g.exact, &g.walk, &g.orderFree})
+        list->refitLevels.clear();
     if (!g.nested)
         return;
-    auto heights = [](const std::vector<float4> &rows, std::vector<int> &height) {
-        const int n = (int)(rows.size() / 2);
-        height.assign(n, 0);
-        /* nested skip pointers: a node's subtree is the nodes after it up to its skip; going backwards
-         * every child is finished before its parent reads it */
-        std::vector<int> parent(n, -1), stack;
-        for (int i = 0; i < n; ++i)
-        {
-            while (!stack.empty() && i >= stack.back() + std::max(bitsi(rows[2 * stack.back() + 1].w), 1))
-                stack.pop_back();
-            parent[i] = stack.empty() ? -1 : stack.back();
-            stack.push_back(i);
-        }
-        int top = 0;
-        for (int i = n - 1; i >= 0; --i)
-        {
-            if (parent[i] >= 0)
-                height[parent[i]] = std::max(height[parent[i]], height[i] + 1);
-            top = std::max(top, height[i]);
-        }
-        return n ? top + 1 : 0;
-    };
     std::vector<int> plan;
-    auto byHeight = [&](const std::vector<int> &height, int nbHeights, std::vector<int> &levels, auto entry) {
-        std::vector<std::vector<int>> bucket((size_t)nbHeights);
-        for (int i = 0; i < (int)height.size(); ++i)
-        {
-            const long e = entry(i);
-            if (e != -1)
-                bucket[(size_t)height[i]].push_back((int)e);
-        }
-        for (const std::vector<int> &b : bucket)
-            if (!b.empty())
-            {
-                levels.push_back((int)plan.size());
-                levels.push_back((int)b.size());
-                plan.insert(plan.end(), b.begin(), b.end());
-            }
-    };
-    std::vector<int> height;
-    int nbHeights = heights(exact, height);
-    byHeight(height, nbHeights, g.refitLevels, [](int i) { return i != 0 ? (long)i : -1L; });
-    nbHeights = heights(walk, height);
-    byHeight(height, nbHeights, g.refitWalkLevels, [&](int j) {
-        if (origin[j] == 0)
-            return -1L;                                   /* the light cell */
-        return origin[j] < 0 ? (long)(j | (int)0x80000000) : (long)j; /* sign bit: a grouping node */
-    });
-    /* the eight order-free lists, one behind the other: a forest with the same kinds of node (leaves of the
-     * reference's tree, unions above them) */
-    if (!free.empty())
-    {
-        nbHeights = heights(free, height);
-        byHeight(height, nbHeights, g.refitFreeLevels, [&](int j) {
-            if (freeOrigin[j] == 0)
-                return -1L;
-            return freeOrigin[j] < 0 ? (long)(j | (int)0x80000000) : (long)j;
-        });
-    }
-    if (plan.empty())
-        plan.push_back(0);
+    planRefit(g.exact.rows, g.walk.rows, g.walk.origin, g.orderFree.rows, g.orderFree.origin, plan, g.exact.refitLevels,
+              g.walk.refitLevels, g.orderFree.refitLevels);
     upload(g.refitPlan, plan);
     g.refitReady = ok();
 }
 
-static void refitList(const std::vector<int> &levels, unsigned offNodes, unsigned offStart, float viewDistance)
+static void refitList(const NodeList &list, float viewDistance)
 {
     float4 *arena = (float4 *)g.geometry.ptr;
     const int *plan = (const int *)g.refitPlan.ptr;
+    const std::vector<int> &levels = list.refitLevels;
     for (size_t l = 0; l + 1 < levels.size(); l += 2)
         hipLaunchKernelGGL(k_refitNodes, dim3((unsigned)((levels[l + 1] + 255) / 256)), dim3(256), 0, g.stream, arena,
-                           offNodes, offStart, g.offPrims, plan + levels[l], levels[l + 1], viewDistance);
+                           list.offRows, list.offStart, g.offPrims, plan + levels[l], levels[l + 1], viewDistance);
 }
 
 /* the reference's node list is wanted: refit it from the primitives as they are now */
@@ -533,7 +452,7 @@ void refreshExactList()
     if (!g.exactStale || !g.geometry.ptr)
         return;
     quiesce();
-    refitList(g.refitLevels, g.offBoxes, g.offBoxStart, g.exactStaleViewDistance);
+    refitList(g.exact, g.exactStaleViewDistance);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(g.stream));
     g.exactStale = false;
@@ -562,9 +481,11 @@ static void ensureHostFreeLists()
     if (g.freeHostValid || !ok())
         return;
     quiesce();
-    g.hostBoxesFree.resize(g.freeRows);
-    g.hostBoxStartFree.resize(g.freeRows / 2);
-    g.hostOriginFree.resize(g.freeRows / 2);
+    NodeList &list = g.orderFree;
+    const size_t n = list.nodes();
+    list.rows.resize(2 * n);
+    list.start.resize(n);
+    list.origin.resize(n);
     const bool staged = g.freeStage.rows != nullptr;
     const char *arena = (const char *)g.geometry.ptr;
     if (!staged && !arena)
@@ -572,12 +493,12 @@ static void ensureHostFreeLists()
         setError(-1, "order-free lists neither staged nor in the arena", __FILE__, __LINE__);
         return;
     }
-    HIPCHECK(hipMemcpy(g.hostBoxesFree.data(), staged ? (const void *)g.freeStage.rows : arena + (size_t)g.offBoxesFree * 16, g.freeRows * 16,
+    HIPCHECK(hipMemcpy(list.rows.data(), staged ? (const void *)g.freeStage.rows : arena + (size_t)list.offRows * 16, 2 * n * 16,
                        hipMemcpyDeviceToHost));
-    HIPCHECK(hipMemcpy(g.hostBoxStartFree.data(), staged ? (const void *)g.freeStage.start : arena + (size_t)g.offBoxStartFree * 4,
-                       g.freeRows / 2 * 4, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(list.start.data(), staged ? (const void *)g.freeStage.start : arena + (size_t)list.offStart * 4, n * 4,
+                       hipMemcpyDeviceToHost));
     if (g.freeStage.origin)
-        HIPCHECK(hipMemcpy(g.hostOriginFree.data(), g.freeStage.origin, g.freeRows / 2 * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(list.origin.data(), g.freeStage.origin, n * 4, hipMemcpyDeviceToHost));
     if (ok())
     {
         g.freeHostValid = true;
@@ -596,10 +517,9 @@ static void pullGeometry()
         if (bytes)
             HIPCHECK(hipMemcpy(dst, (const char *)g.geometry.ptr + (size_t)at * 16, bytes, hipMemcpyDeviceToHost));
     };
-    get(g.offBoxes, g.hostBoxes.data(), g.hostBoxes.size() * 16);
-    get(g.offBoxesCompact, g.hostBoxesCompact.data(), g.hostBoxesCompact.size() * 16);
-    if (g.freeHostValid)
-        get(g.offBoxesFree, g.hostBoxesFree.data(), g.hostBoxesFree.size() * 16);
+    for (NodeList *list : {&g.exact, &g.walk, &g.orderFree})
+        if (list != &g.orderFree || g.freeHostValid)
+            get(list->offRows, list->rows.data(), list->rows.size() * 16);
     get(g.offPrims, g.hostPrims.data(), g.hostPrims.size() * 16);
     g.deviceAhead = false;
 }
@@ -690,20 +610,21 @@ void retagPrimitives()
     g.geometryDirty = true;
 }
 
-/* The thin copy of a node list behind it (rows offNodes + 2 n + 2 ...; rt_device.h tightRay): made where the scene has
+/* The thin copy of a node list behind it (NodeList::offThin; rt_device.h tightRay): made where the scene has
  * plain axis planes at all and the list is short enough for an inner node's thread to read its whole subtree (the
  * room of a 100 k-triangle model keeps the reference's boxes).  false: there is no copy to walk. */
-bool tightenList(unsigned offNodes, unsigned offStart, int nbNodes, int listLength)
+static bool tightenList(const NodeList &list)
 {
     static const bool off = getenv("SOLR_HIP_NO_TIGHT_LEAVES") != nullptr;
+    const int nbNodes = (int)list.nodes(), listLength = list.nb;
     if (off || !g.plainPlanes || nbNodes <= 0 || listLength <= 0 || listLength > 65536 || !ok())
         return false;
     float4 *arena = (float4 *)g.geometry.ptr;
-    const unsigned offTight = offNodes + 2u * (unsigned)nbNodes + 2u;
     const float margin = g.sceneExtent * (1.f / 1024.f);
     const dim3 grid((unsigned)((nbNodes + 255) / 256));
-    hipLaunchKernelGGL(k_tightenLeaves, grid, dim3(256), 0, g.stream, arena, offNodes, offTight, offStart, g.offPrims, nbNodes, margin);
-    hipLaunchKernelGGL(k_tightenInner, grid, dim3(256), 0, g.stream, arena, offTight, nbNodes, listLength);
+    hipLaunchKernelGGL(k_tightenLeaves, grid, dim3(256), 0, g.stream, arena, list.offRows, list.offThin(), list.offStart, g.offPrims,
+                       nbNodes, margin);
+    hipLaunchKernelGGL(k_tightenInner, grid, dim3(256), 0, g.stream, arena, list.offThin(), nbNodes, listLength);
     HIPCHECK(hipGetLastError());
     return ok();
 }
@@ -712,10 +633,9 @@ bool tightenList(unsigned offNodes, unsigned offStart, int nbNodes, int listLeng
  * axis for the octant the list was flattened for (bit 0: x, 1: y, 2: z negative) - {n.x, n.y, n.z, f.z} {f.x, f.y, count,
  * 32 x skip} (scene_layout.h sortedLists; rt_device.h SOLR_ORDER_SORTED, SOLR_NEXT_BY_BYTES).  Made wherever the lists'
  * bounds change. */
-__global__ __launch_bounds__(256) void k_sortNodeBounds(float4 *__restrict__ arena, unsigned offBoxesFree, int nb)
+__global__ __launch_bounds__(256) void k_sortNodeBounds(float4 *__restrict__ arena, unsigned offBoxesFree, unsigned offSorted, int nb)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned offSorted = offBoxesFree + 32u * (unsigned)nb + 4u;
     if (i > 8 * nb)
         return;
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a; /* (i == 8 nb: the pad record behind the last list) */
@@ -749,62 +669,59 @@ __global__ __launch_bounds__(256) void k_sortNodeBounds(float4 *__restrict__ are
     arena[offSorted + 2u * (unsigned)i + 1u] = b;
 }
 
-static bool sortFreeLists(int nbRows)
+static bool sortFreeLists()
 {
     static const bool off = getenv("SOLR_HIP_NO_SORTED_LISTS") != nullptr;
-    const int nb = nbRows / 16; /* nodes per list: eight lists of two rows a node */
-    if (off || nb <= 0 || !ok())
+    const NodeList &list = g.orderFree;
+    if (off || list.nb <= 0 || !ok())
         return false;
-    hipLaunchKernelGGL(k_sortNodeBounds, dim3((unsigned)((8 * nb + 1 + 255) / 256)), dim3(256), 0, g.stream,
-                       (float4 *)g.geometry.ptr, g.offBoxesFree, nb);
+    hipLaunchKernelGGL(k_sortNodeBounds, dim3((unsigned)((8 * list.nb + 1 + 255) / 256)), dim3(256), 0, g.stream,
+                       (float4 *)g.geometry.ptr, list.offRows, list.offSorted(), list.nb);
     HIPCHECK(hipGetLastError());
     return ok();
 }
 
-/* the leaf records of both node lists from the primitive records as the arena holds them now */
+/* what the arena holds of a list beyond its rows, from those and the primitive records as they are now: the leaf
+ * records, and the copies behind the rows - they follow the bounds and the primitives they were made from (an upload, a
+ * rotation on the device).  Order-free lists that a rotation left behind (freeStale) get none. */
+static void deriveList(NodeList &list)
+{
+    const bool orderFree = &list == &g.orderFree;
+    const int n = (orderFree && g.freeStale) ? 0 : (int)list.nodes();
+    if (n > 0)
+        hipLaunchKernelGGL(k_buildLeafRecords, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, (float4 *)g.geometry.ptr,
+                           list.offRows, list.offStart, g.offPrims, list.offLeaf, n);
+    HIPCHECK(hipGetLastError());
+    list.tight = list.copies > 1 && n > 0 && tightenList(list);
+    if (orderFree)
+        g.sortedFree = n > 0 && sortFreeLists();
+}
+
+/* the leaf records of every node list from the primitive records as the arena holds them now */
 void buildLeafRecords()
 {
     if (!ok() || !g.geometry.ptr)
         return;
-    float4 *arena = (float4 *)g.geometry.ptr;
-    const int n = (int)(g.hostBoxes.size() / 2), nc = (int)(g.hostBoxesCompact.size() / 2);
-    if (n > 0)
-        hipLaunchKernelGGL(k_buildLeafRecords, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, arena, g.offBoxes,
-                           g.offBoxStart, g.offPrims, g.offLeaf, n);
-    if (nc > 0)
-        hipLaunchKernelGGL(k_buildLeafRecords, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, g.stream, arena,
-                           g.offBoxesCompact, g.offBoxStartCompact, g.offPrims, g.offLeafCompact, nc);
-    const int nf = (int)(g.freeRows / 2);
-    if (nf > 0 && !g.freeStale)
-        hipLaunchKernelGGL(k_buildLeafRecords, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, g.stream, arena,
-                           g.offBoxesFree, g.offBoxStartFree, g.offPrims, g.offLeafFree, nf);
-    HIPCHECK(hipGetLastError());
-    /* the thin copies follow the bounds and the primitives they were made from (an upload, a rotation on the device) */
-    g.tightCompact = tightenList(g.offBoxesCompact, g.offBoxStartCompact, nc, nc);
-    g.tightFree = nf > 0 && !g.freeStale && tightenList(g.offBoxesFree, g.offBoxStartFree, nf, nf / 8);
-    g.sortedFree = nf > 0 && !g.freeStale && sortFreeLists((int)g.freeRows);
+    for (NodeList *list : {&g.exact, &g.walk, &g.orderFree})
+        deriveList(*list);
     HIPCHECK(hipStreamSynchronize(g.stream));
 }
 
-/* where the order-free lists go: behind everything else, so that they can be added to an arena that is laid out */
-static unsigned layoutFreeLists(unsigned row)
+/* the lists the device builder left (g.freeStage) to their place in the arena */
+static void copyStagedLists()
 {
-    g.offBoxesFree = row;
-    /* (one pad record, as behind every node list; then the thin copy and the copy with sorted bounds, padded alike) */
-    row += 3u * ((unsigned)g.freeRows + 2u);
-    g.offBoxStartFree = row * 4;
-    row += (unsigned)((g.freeRows / 2 + 3) / 4);
-    row = (row + 3u) & ~3u; /* leaf records: one 64-byte line per node */
-    g.offLeafFree = row;
-    row += 2u * (unsigned)g.freeRows + 4u;
-    return row;
+    const NodeList &list = g.orderFree;
+    char *arena = (char *)g.geometry.ptr;
+    HIPCHECK(hipMemcpyAsync(arena + (size_t)list.offRows * 16, g.freeStage.rows, (size_t)list.nodes() * 32, hipMemcpyDeviceToDevice, g.stream));
+    HIPCHECK(hipMemcpyAsync(arena + (size_t)list.offStart * 4, g.freeStage.start, (size_t)list.nodes() * 4, hipMemcpyDeviceToDevice, g.stream));
 }
 
 /* the lists the device builder has just left (g.freeStage) into an arena that holds everything else already: what
  * is there stays where it is (moved to a larger allocation when this one is too small), nothing is uploaded again */
 static void appendFreeLists()
 {
-    const unsigned end = layoutFreeLists(g.rowsFixed);
+    /* (the order-free lists lie behind everything else, so that they can be added to an arena that is laid out) */
+    const unsigned end = g.orderFree.layLeaf(g.orderFree.layStart(g.orderFree.layRows(g.rowsFixed)));
     const size_t bytes = (size_t)end * 16, fixedBytes = (size_t)g.rowsFixed * 16;
     PhaseTimer phase;
     if (g.geometry.bytes < bytes)
@@ -818,17 +735,10 @@ static void appendFreeLists()
         release(g.geometry);
         g.geometry = larger;
     }
-    char *arena = (char *)g.geometry.ptr;
-    HIPCHECK(hipMemsetAsync(arena + fixedBytes, 0, bytes - fixedBytes, g.stream));
-    HIPCHECK(hipMemcpyAsync(arena + (size_t)g.offBoxesFree * 16, g.freeStage.rows, g.freeRows * 16, hipMemcpyDeviceToDevice, g.stream));
-    HIPCHECK(hipMemcpyAsync(arena + (size_t)g.offBoxStartFree * 4, g.freeStage.start, g.freeRows / 2 * 4, hipMemcpyDeviceToDevice, g.stream));
-    const int nf = (int)(g.freeRows / 2);
-    if (ok() && nf > 0)
-        hipLaunchKernelGGL(k_buildLeafRecords, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, g.stream, (float4 *)g.geometry.ptr,
-                           g.offBoxesFree, g.offBoxStartFree, g.offPrims, g.offLeafFree, nf);
-    HIPCHECK(hipGetLastError());
-    g.tightFree = nf > 0 && tightenList(g.offBoxesFree, g.offBoxStartFree, nf, nf / 8);
-    g.sortedFree = nf > 0 && sortFreeLists((int)g.freeRows);
+    HIPCHECK(hipMemsetAsync((char *)g.geometry.ptr + fixedBytes, 0, bytes - fixedBytes, g.stream));
+    copyStagedLists();
+    if (ok())
+        deriveList(g.orderFree);
     HIPCHECK(hipStreamSynchronize(g.stream));
     phase.mark("geometry: lists appended");
     if (ok())
@@ -853,32 +763,18 @@ void flushGeometry()
     pullGeometry();
     if (!g.freeStage.rows)
         ensureHostFreeLists(); /* laid out again from the host images: the lists too, then */
-    auto rowsOfInts = [](size_t n) { return (unsigned)((n + 3) / 4); };
-    unsigned row = 0;
-    /* each node list is followed by one pad record: the walk requests the record after the node it tests
-     * (rt_device.h advanceTidy), after the last node too */
-    g.offBoxes = row;
-    row += (unsigned)g.hostBoxes.size() + 2u;
-    g.offBoxesCompact = row;
-    row += 2u * ((unsigned)g.hostBoxesCompact.size() + 2u); /* ... and its thin copy (tightenList), padded alike */
+    /* node rows (NodeList: pad records and copies behind them), primitive and light records, start indices, leaf records;
+     * then the order-free lists, whole */
+    unsigned row = g.walk.layRows(g.exact.layRows(0));
     row = (row + 3u) & ~3u; /* primitive records start on a 64-byte line */
     g.offPrims = row;
     row += (unsigned)g.hostPrims.size();
     g.offLights = row;
     row += (unsigned)g.hostLights.size();
-    const unsigned startRow = row;
-    row += rowsOfInts(g.hostBoxStart.size());
-    const unsigned startRowCompact = row;
-    row += rowsOfInts(g.hostBoxStartCompact.size());
-    g.offBoxStart = startRow * 4;
-    g.offBoxStartCompact = startRowCompact * 4;
-    row = (row + 3u) & ~3u; /* leaf records: one 64-byte line per node */
-    g.offLeaf = row;
-    row += 2u * (unsigned)g.hostBoxes.size() + 4u;
-    g.offLeafCompact = row;
-    row += 2u * (unsigned)g.hostBoxesCompact.size() + 4u;
+    row = g.walk.layStart(g.exact.layStart(row));
+    row = g.walk.layLeaf(g.exact.layLeaf(row));
     g.rowsFixed = row;
-    row = layoutFreeLists(row);
+    row = g.orderFree.layLeaf(g.orderFree.layStart(g.orderFree.layRows(row)));
     PhaseTimer phase;
     /* the pieces go straight to their rows of the arena (a staged host copy of the whole arena, zero-filled first,
      * took 10-14 ms for 100 k primitives); pad records and the leaf-record area start as zeros */
@@ -890,24 +786,19 @@ void flushGeometry()
         if (bytes && ok())
             HIPCHECK(hipMemcpyAsync((char *)g.geometry.ptr + (size_t)at * 16, src, bytes, hipMemcpyHostToDevice, g.stream));
     };
-    put(g.offBoxes, g.hostBoxes.data(), g.hostBoxes.size() * 16);
-    put(g.offBoxesCompact, g.hostBoxesCompact.data(), g.hostBoxesCompact.size() * 16);
+    for (const NodeList *list : {&g.exact, &g.walk, &g.orderFree})
+        if (list == &g.orderFree && g.freeStage.rows)
+        {
+            if (ok())
+                copyStagedLists();
+        }
+        else
+        {
+            put(list->offRows, list->rows.data(), list->rows.size() * 16);
+            put(list->offStart / 4, list->start.data(), list->start.size() * 4);
+        }
     put(g.offPrims, g.hostPrims.data(), g.hostPrims.size() * 16);
     put(g.offLights, g.hostLights.data(), g.hostLights.size() * 16);
-    put(startRow, g.hostBoxStart.data(), g.hostBoxStart.size() * 4);
-    put(startRowCompact, g.hostBoxStartCompact.data(), g.hostBoxStartCompact.size() * 4);
-    if (g.freeStage.rows && ok())
-    {
-        HIPCHECK(hipMemcpyAsync((char *)g.geometry.ptr + (size_t)g.offBoxesFree * 16, g.freeStage.rows, g.freeRows * 16,
-                                hipMemcpyDeviceToDevice, g.stream));
-        HIPCHECK(hipMemcpyAsync((char *)g.geometry.ptr + (size_t)g.offBoxStartFree * 4, g.freeStage.start, g.freeRows / 2 * 4,
-                                hipMemcpyDeviceToDevice, g.stream));
-    }
-    else
-    {
-        put(g.offBoxesFree, g.hostBoxesFree.data(), g.hostBoxesFree.size() * 16);
-        put(g.offBoxStartFree / 4, g.hostBoxStartFree.data(), g.hostBoxStartFree.size() * 4);
-    }
     HIPCHECK(hipStreamSynchronize(g.stream)); /* pageable sources: complete for the caller when this returns */
     if (ok())
         dropFreeStage(false);
@@ -924,8 +815,7 @@ void flushGeometry()
 /* the order-free lists exist for the resident scene and every condition of their use holds (rt_device.h closestHitWalk) */
 bool orderFreeListsUsable()
 {
-    return g.nbBoxesFree > 0 && g.freeRows == 16 * (size_t)g.nbBoxesFree && g.primsContained && !g.freeStale &&
-           g.nested && g.orderedCompact && g.variant != VARIANT_NO_ORDER_FREE;
+    return g.orderFree.nb > 0 && g.primsContained && !g.freeStale && g.nested && g.walk.ordered && g.variant != VARIANT_NO_ORDER_FREE;
 }
 
 /* shadow walks in the reference's order may leave out the boxes that begin beyond the lamp (rt_device.h shadowWalk,
@@ -934,7 +824,7 @@ bool orderFreeListsUsable()
  * reaches beyond what the check takes for its extent (retagPrimitives) */
 bool lampCutoffUsable()
 {
-    return g.compactEncloses && g.primsContained && g.nested && g.orderedCompact && g.variant != VARIANT_NO_LAMP_CUTOFF;
+    return g.walkEncloses && g.primsContained && g.nested && g.walk.ordered && g.variant != VARIANT_NO_LAMP_CUTOFF;
 }
 
 /* bounce rays on the order-free lists: the API's word, else SOLR_HIP_SHORT_RAY_LISTS=0|1 (experiments), else the engine's
@@ -952,30 +842,31 @@ bool shortRayListsChoice()
 
 static SceneArgs makeScene(bool exactNodes)
 {
+    const NodeList &list = exactNodes ? g.exact : g.walk;
     SceneArgs S;
     memset(&S, 0, sizeof(S));
     S.geometry = g.geometry.ptr;
     S.materials = g.materials.ptr;
     S.textures = g.textures.ptr;
     S.randoms = g.randoms.ptr;
-    S.offBoxes = exactNodes ? g.offBoxes : g.offBoxesCompact;
-    S.offBoxStart = exactNodes ? g.offBoxStart : g.offBoxStartCompact;
-    S.offLeaf = exactNodes ? g.offLeaf : g.offLeafCompact;
+    S.offBoxes = list.offRows;
+    S.offBoxStart = list.offStart;
+    S.offLeaf = list.offLeaf;
     S.offPrims = g.offPrims;
     S.offLights = g.offLights;
     S.offMatCold = g.offMatCold;
-    S.nbBoxes = exactNodes ? g.nbBoxes : g.nbBoxesCompact;
+    S.nbBoxes = list.nb;
     S.nbPrimitives = g.nbPrimitives;
     S.nbLights = g.nbLights;
     S.nbLamps = g.nbLamps;
     S.nested = g.nested;
-    S.orderedBoxes = exactNodes ? g.orderedExact : g.orderedCompact;
+    S.orderedBoxes = list.ordered;
     S.nbRandoms = g.randoms.ptr ? g.nbRandoms : 0;
     if (!exactNodes && orderFreeListsUsable())
     {
-        S.offBoxesFree = g.offBoxesFree;
-        S.offLeafFree = g.offLeafFree;
-        S.nbBoxesFree = g.nbBoxesFree; /* per list; the eight lists and their leaf records lie one behind the other */
+        S.offBoxesFree = g.orderFree.offRows;
+        S.offLeafFree = g.orderFree.offLeaf;
+        S.nbBoxesFree = g.orderFree.nb; /* per list; the eight lists and their leaf records lie one behind the other */
         S.opaqueShadows = g.opaqueShadows ? SHADOWS_OPAQUE : 0;
         S.shortRayLists = shortRayListsChoice() ? 1 : 0;
     }
@@ -991,9 +882,9 @@ static SceneArgs makeScene(bool exactNodes)
 /* may the walks of a frame with this SceneInfo take the thin copies of the lists S names (rt_device.h tightRay)? */
 static int tightListsFor(const SceneArgs &S, const SceneInfo &sceneInfo, bool exactNodes)
 {
-    if (exactNodes || g.variant == VARIANT_REFERENCE_LEAVES || !g.tightCompact || !sceneInfo.extendedGeometry)
+    if (exactNodes || g.variant == VARIANT_REFERENCE_LEAVES || !g.walk.tight || !sceneInfo.extendedGeometry)
         return 0;
-    if (S.nbBoxesFree > 0 && !g.tightFree)
+    if (S.nbBoxesFree > 0 && !g.orderFree.tight)
         return 0;
     return (sceneInfo.viewDistance > 0.f && sceneInfo.viewDistance <= 64.f * g.sceneExtent) ? 1 : 0;
 }
@@ -1048,538 +939,50 @@ void checkTextureTables()
     }
 }
 
-/* (defined with the list builders further down) */
-void maybeBuildOrderFreeLists();
 
 /* exchangeDepthHalo, agreedHaloRows, haveCommunicator: solr_rccl.hip (engine.h) */
 
-/* Inner nodes that hardly ever cull are left out of the walk list.  An inner node - one of the reference's tree
- * whose children all lie inside it, or a grouping node, which is the union of its members - passes whenever one
- * of its children would (the argument of groupSiblings below, read the other way: slab values are monotonic in
- * the bounds, the cut-off only shrinks along a walk), so testing the children without it reaches the same
- * leaves in the same order.  What the node buys is the tests of its subtree for the rays that miss it; what it
- * costs is one test for those that do not.  A ray that is in the parent enters the node
- *   - because it starts there: the rays of a frame start on the geometry (and at the camera, which is in the
- *     room it looks at), so about the share of the parent's leaves whose centre lies in the node;
- *   - otherwise with the surface-area probability area(node) / area(parent).
- * The node stays if (1 - the larger of the two) x (nodes below it) is at least `threshold` tests.  Cornell's
- * upper cells and the groups around its walls hold every leaf centre of the room: they go, the groups of small
- * spheres on the floor stay.  Works on the walk-order rows in place; returns the new node count. */
-static int pruneInnerNodes(std::vector<float4> &rows, std::vector<int> &start, std::vector<int> &origin, int *nbPruned,
-                           bool everyInnerNode = false)
+/* does a list of the arena as it is now hold what it names (k_listEncloses; the host's form of the question is
+ * listEnclosesOnHost, list_builders.cpp)?  Waits for the stream */
+static bool listEnclosesInArena(const NodeList &list)
 {
-    const int n = (int)start.size();
-    const double threshold = everyInnerNode ? 1e300 : (getenv("SOLR_HIP_PRUNE") ? atof(getenv("SOLR_HIP_PRUNE")) : 1.0);
-    *nbPruned = 0;
-    if (n < 2 || !(threshold > 0.0))
-        return n;
-    auto skipOf = [&](int i) { return std::max(bitsi(rows[2 * i + 1].w), 1); };
-    auto countOf = [&](int i) { return bitsi(rows[2 * i + 1].z); };
-    auto lo = [&](int i, int k) { return k == 0 ? rows[2 * i].x : (k == 1 ? rows[2 * i].y : rows[2 * i].z); };
-    auto hi = [&](int i, int k) { return k == 0 ? rows[2 * i + 1].x : (k == 1 ? rows[2 * i + 1].y : rows[2 * i].w); };
-    auto areaOf = [&](int i) {
-        const double x = (double)hi(i, 0) - lo(i, 0), y = (double)hi(i, 1) - lo(i, 1), z = (double)hi(i, 2) - lo(i, 2);
-        return x * y + y * z + z * x;
-    };
-    std::vector<char> keep(n, 1);
-    /* the decisions: on the device (solr_lists.hip, one launch per depth of the list; the same arithmetic, the same
-     * decisions) unless told otherwise or declined */
-    int decided = -1;
-    if (!everyInnerNode && g.initialized && !getenv("SOLR_HIP_LISTS_ON_HOST"))
-        decided = solrPruneDecisionsOnDevice(rows.data(), n, threshold, keep, g.stream);
-    if (decided >= 0)
-        *nbPruned = decided;
-    else
-    {
-        keep.assign(n, 1);
-        std::vector<int> leaves; /* node indices of the leaves, in walk order */
-        std::vector<int> leavesBefore(n + 1, 0);
-        for (int i = 0; i < n; ++i)
-        {
-            leavesBefore[i + 1] = leavesBefore[i] + (countOf(i) > 0 ? 1 : 0);
-            if (countOf(i) > 0)
-                leaves.push_back(i);
-        }
-        struct Open
-        {
-            int node, end;
-        };
-        std::vector<Open> open; /* kept ancestors of node i */
-        double sceneLo[3] = {1e300, 1e300, 1e300}, sceneHi[3] = {-1e300, -1e300, -1e300};
-        for (int j = 0; j < n; j += skipOf(j))
-            for (int k = 0; k < 3; ++k)
-            {
-                sceneLo[k] = std::min(sceneLo[k], (double)lo(j, k));
-                sceneHi[k] = std::max(sceneHi[k], (double)hi(j, k));
-            }
-        const double sceneArea = (sceneHi[0] - sceneLo[0]) * (sceneHi[1] - sceneLo[1]) + (sceneHi[1] - sceneLo[1]) * (sceneHi[2] - sceneLo[2]) +
-                                 (sceneHi[2] - sceneLo[2]) * (sceneHi[0] - sceneLo[0]);
-        for (int i = 0; i < n; ++i)
-        {
-            while (!open.empty() && open.back().end <= i)
-                open.pop_back();
-            const int end = std::min(i + skipOf(i), n);
-            if (countOf(i) == 0 && end > i + 1)
-            {
-                const int parentFrom = open.empty() ? 0 : open.back().node, parentTo = open.empty() ? n : open.back().end;
-                const double parentArea = open.empty() ? sceneArea : areaOf(open.back().node);
-                const double bySurface = parentArea > 0.0 ? std::min(1.0, areaOf(i) / parentArea) : 1.0;
-                /* share of the parent's leaves whose centre lies in the node (sampled beyond 4096 leaves) */
-                const int firstLeaf = leavesBefore[parentFrom], lastLeaf = leavesBefore[parentTo];
-                const int stride = std::max(1, (lastLeaf - firstLeaf) / 4096);
-                int sampled = 0, inside = 0;
-                for (int q = firstLeaf; q < lastLeaf; q += stride)
-                {
-                    const int leaf = leaves[q];
-                    bool in = true;
-                    for (int k = 0; k < 3 && in; ++k)
-                    {
-                        const double c = 0.5 * ((double)lo(leaf, k) + hi(leaf, k));
-                        in = c >= lo(i, k) && c <= hi(i, k);
-                    }
-                    ++sampled;
-                    inside += in ? 1 : 0;
-                }
-                const double byOrigin = sampled ? (double)inside / sampled : 1.0;
-                bool encloses = true; /* every child within the node: what the argument above rests on */
-                for (int j = i + 1; j < end && encloses; j += skipOf(j))
-                    for (int k = 0; k < 3; ++k)
-                        encloses = encloses && lo(j, k) >= lo(i, k) && hi(j, k) <= hi(i, k);
-                if (encloses && (1.0 - std::max(bySurface, byOrigin)) * (end - i - 1) < threshold)
-                {
-                    keep[i] = 0;
-                    ++*nbPruned;
-                    continue;
-                }
-            }
-            open.push_back({i, end});
-        }
-    }
-    if (*nbPruned == 0)
-        return n;
-    std::vector<int> newIndex(n + 1, 0);
-    for (int i = 0; i < n; ++i)
-        newIndex[i + 1] = newIndex[i] + (keep[i] ? 1 : 0);
-    const int m = newIndex[n];
-    std::vector<float4> outRows(2 * (size_t)m);
-    std::vector<int> outStart(m), outOrigin(m);
-    for (int i = 0; i < n; ++i)
-        if (keep[i])
-        {
-            const int j = newIndex[i];
-            const int end = std::min(i + skipOf(i), n);
-            outRows[2 * j] = rows[2 * i];
-            outRows[2 * j + 1] = rows[2 * i + 1];
-            outRows[2 * j + 1].w = bitsf(newIndex[end] - j);
-            outStart[j] = start[i];
-            outOrigin[j] = origin[i];
-        }
-    rows.swap(outRows);
-    start.swap(outStart);
-    origin.swap(outOrigin);
-    return m;
-}
-
-/* The order-free lists: the leaves of the scene - every node with primitives, whatever the reference put above
- * it - under a binary surface-area hierarchy of our own (binned SAH over the leaf boxes' centres, sixteen bins),
- * flattened depth-first with skip pointers like the other lists, EIGHT TIMES: once per sign octant of a ray's
- * direction, the child on the near side of each split first.  Closest-hit walks whose result does not depend on
- * the order of the leaves (rt_device.h closestHitWalk: rays longer than 2, ties to the smaller flattened index)
- * walk the list of their octant instead of the reference's order - near boxes first, so that the first hits
- * shrink the cut-off and the far side of the scene is culled, which no fixed order can do for every direction.
- * Any of the eight is correct for any ray; the choice is only speed.  Inner nodes that hardly cull are left
- * out as in the other lists (decided once, on the first flattening).  Valid only when every primitive lies
- * inside its leaf's box and every inner node of the reference's list encloses its children (the caller checks
- * both).  `rows` / `start`: a nested list.  Output: 8 x count nodes, list after list. */
-static int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> &start, const std::vector<int> &origin,
-                               std::vector<float4> &outRows, std::vector<int> &outStart, std::vector<int> &outOrigin,
-                               int *nbPruned)
-{
-    struct Leaf
-    {
-        float lo[3], hi[3];
-        int node;
-    };
-    struct TreeNode
-    {
-        float lo[3], hi[3];
-        int left, right, axis, leaf; /* leaf: node of the input list, -1 for an inner node */
-        int depth;
-        bool keep;
-    };
-    const int n = (int)start.size();
-    std::vector<Leaf> leaves;
-    for (int i = 0; i < n; ++i)
-        if (bitsi(rows[2 * i + 1].z) > 0)
-        {
-            Leaf l;
-            l.lo[0] = rows[2 * i].x, l.lo[1] = rows[2 * i].y, l.lo[2] = rows[2 * i].z;
-            l.hi[0] = rows[2 * i + 1].x, l.hi[1] = rows[2 * i + 1].y, l.hi[2] = rows[2 * i].w;
-            l.node = i;
-            leaves.push_back(l);
-        }
-    outRows.clear();
-    outStart.clear();
-    outOrigin.clear();
-    *nbPruned = 0;
-    if (leaves.size() < 2)
-        return 0;
-    auto area = [](const float *lo, const float *hi) {
-        const double x = (double)hi[0] - lo[0], y = (double)hi[1] - lo[1], z = (double)hi[2] - lo[2];
-        return x * y + y * z + z * x;
-    };
-    std::vector<TreeNode> tree;
-    tree.reserve(2 * leaves.size());
-    struct Range
-    {
-        int from, to, node;
-    };
-    std::vector<Range> todo;
-    tree.push_back(TreeNode());
-    tree[0].depth = 0;
-    todo.push_back({0, (int)leaves.size(), 0});
-    while (!todo.empty())
-    {
-        const Range r = todo.back();
-        todo.pop_back();
-        const int count = r.to - r.from;
-        TreeNode t;
-        t.left = t.right = -1;
-        t.axis = 0;
-        t.leaf = -1;
-        t.depth = tree[r.node].depth;
-        t.keep = true;
-        if (count == 1)
-        {
-            for (int k = 0; k < 3; ++k)
-                t.lo[k] = leaves[r.from].lo[k], t.hi[k] = leaves[r.from].hi[k];
-            t.leaf = leaves[r.from].node;
-            tree[r.node] = t;
-            continue;
-        }
-        float clo[3] = {1e30f, 1e30f, 1e30f}, chi[3] = {-1e30f, -1e30f, -1e30f};
-        for (int k = 0; k < 3; ++k)
-            t.lo[k] = 1e30f, t.hi[k] = -1e30f;
-        for (int q = r.from; q < r.to; ++q)
-            for (int k = 0; k < 3; ++k)
-            {
-                t.lo[k] = std::min(t.lo[k], leaves[q].lo[k]);
-                t.hi[k] = std::max(t.hi[k], leaves[q].hi[k]);
-                const float c = 0.5f * (leaves[q].lo[k] + leaves[q].hi[k]);
-                clo[k] = std::min(clo[k], c);
-                chi[k] = std::max(chi[k], c);
-            }
-        /* zeros are +0 (std::min keeps whichever zero it met first; the device builder of solr_lists.hip, whose
-         * minima are atomics, could not tell which that was) */
-        for (int k = 0; k < 3; ++k)
-            t.lo[k] += 0.f, t.hi[k] += 0.f;
-        /* binned surface-area split: one pass over the leaves fills the bins of all three axes */
-        const int BINS = 16;
-        int bestAxis = -1, bestBin = 0;
-        double bestCost = 1e300;
-        {
-            int counts[3][BINS];
-            float blo[3][BINS][3], bhi[3][BINS][3];
-            float scale[3];
-            for (int axis = 0; axis < 3; ++axis)
-            {
-                const float extent = chi[axis] - clo[axis];
-                scale[axis] = extent > 0.f ? BINS / extent : 0.f;
-                for (int b = 0; b < BINS; ++b)
-                {
-                    counts[axis][b] = 0;
-                    for (int k = 0; k < 3; ++k)
-                        blo[axis][b][k] = 1e30f, bhi[axis][b][k] = -1e30f;
-                }
-            }
-            for (int q = r.from; q < r.to; ++q)
-            {
-                const Leaf &l = leaves[q];
-                for (int axis = 0; axis < 3; ++axis)
-                {
-                    if (!(scale[axis] > 0.f))
-                        continue;
-                    const float c = 0.5f * (l.lo[axis] + l.hi[axis]);
-                    const int b = std::min(BINS - 1, std::max(0, (int)((c - clo[axis]) * scale[axis])));
-                    ++counts[axis][b];
-                    float *lo3 = blo[axis][b], *hi3 = bhi[axis][b];
-                    lo3[0] = std::min(lo3[0], l.lo[0]), lo3[1] = std::min(lo3[1], l.lo[1]), lo3[2] = std::min(lo3[2], l.lo[2]);
-                    hi3[0] = std::max(hi3[0], l.hi[0]), hi3[1] = std::max(hi3[1], l.hi[1]), hi3[2] = std::max(hi3[2], l.hi[2]);
-                }
-            }
-            for (int axis = 0; axis < 3; ++axis)
-            {
-                if (!(scale[axis] > 0.f))
-                    continue;
-                double rightArea[BINS];
-                int rightCount[BINS];
-                float rlo[3] = {1e30f, 1e30f, 1e30f}, rhi[3] = {-1e30f, -1e30f, -1e30f};
-                int rc = 0;
-                for (int b = BINS - 1; b > 0; --b)
-                {
-                    rc += counts[axis][b];
-                    for (int k = 0; k < 3; ++k)
-                    {
-                        rlo[k] = std::min(rlo[k], blo[axis][b][k]);
-                        rhi[k] = std::max(rhi[k], bhi[axis][b][k]);
-                    }
-                    rightCount[b] = rc;
-                    rightArea[b] = rc ? area(rlo, rhi) : 0.0;
-                }
-                float llo[3] = {1e30f, 1e30f, 1e30f}, lhi[3] = {-1e30f, -1e30f, -1e30f};
-                int lc = 0;
-                for (int b = 0; b + 1 < BINS; ++b)
-                {
-                    lc += counts[axis][b];
-                    for (int k = 0; k < 3; ++k)
-                    {
-                        llo[k] = std::min(llo[k], blo[axis][b][k]);
-                        lhi[k] = std::max(lhi[k], bhi[axis][b][k]);
-                    }
-                    if (lc == 0 || rightCount[b + 1] == 0)
-                        continue;
-                    const double cost = area(llo, lhi) * lc + rightArea[b + 1] * rightCount[b + 1];
-                    if (cost < bestCost)
-                    {
-                        bestCost = cost;
-                        bestAxis = axis;
-                        bestBin = b;
-                    }
-                }
-            }
-        }
-        int mid;
-        if (bestAxis < 0)
-            mid = r.from + count / 2; /* all centres coincide */
-        else
-        {
-            const float scale = BINS / (chi[bestAxis] - clo[bestAxis]);
-            const float origin = clo[bestAxis];
-            const int axis = bestAxis, bin = bestBin;
-            /* stable: the order inside a node stays the order of the leaf list (it decides the halving by position
-             * below, and the device builder partitions the same way) */
-            mid = (int)(std::stable_partition(leaves.begin() + r.from, leaves.begin() + r.to,
-                                       [&](const Leaf &l) {
-                                           const float c = 0.5f * (l.lo[axis] + l.hi[axis]);
-                                           return std::min(BINS - 1, std::max(0, (int)((c - origin) * scale))) <= bin;
-                                       }) -
-                        leaves.begin());
-            if (mid == r.from || mid == r.to)
-                mid = r.from + count / 2;
-            t.axis = bestAxis;
-        }
-        t.left = (int)tree.size(); /* the low side of the split */
-        t.right = t.left + 1;
-        tree.push_back(TreeNode());
-        tree.push_back(TreeNode());
-        tree[t.left].depth = tree[t.right].depth = t.depth + 1;
-        tree[r.node] = t;
-        todo.push_back({r.from, mid, t.left});
-        todo.push_back({mid, r.to, t.right});
-    }
-
-    /* one flattening: depth-first, the child on the near side of a ray of this octant first */
-    auto flatten = [&](int octant, std::vector<float4> &fr, std::vector<int> &fs, std::vector<int> *which,
-                       std::vector<int> *from) {
-        struct Visit
-        {
-            int node, slot; /* slot >= 0: close the inner node written at `slot` */
-        };
-        std::vector<Visit> stack;
-        stack.push_back({0, -1});
-        while (!stack.empty())
-        {
-            const Visit v = stack.back();
-            stack.pop_back();
-            if (v.slot >= 0)
-            {
-                fr[2 * v.slot + 1].w = bitsf((int)fs.size() - v.slot);
-                continue;
-            }
-            const TreeNode &t = tree[v.node];
-            if (t.leaf >= 0)
-            {
-                fr.push_back(rows[2 * t.leaf]);
-                float4 second = rows[2 * t.leaf + 1];
-                second.w = bitsf(1);
-                fr.push_back(second);
-                fs.push_back(start[t.leaf]);
-                if (which)
-                    which->push_back(v.node);
-                if (from)
-                    from->push_back(origin[t.leaf]); /* the node of the reference's list this leaf is */
-                continue;
-            }
-            if (t.keep)
-            {
-                const int slot = (int)fs.size();
-                fr.push_back(make_float4(t.lo[0], t.lo[1], t.lo[2], t.hi[2]));
-                fr.push_back(make_float4(t.hi[0], t.hi[1], bitsf(0), bitsf(1)));
-                fs.push_back(0);
-                if (which)
-                    which->push_back(v.node);
-                if (from)
-                    from->push_back(-1);
-                stack.push_back({0, slot});
-            }
-            const bool highFirst = (octant >> t.axis) & 1; /* direction negative along the split axis */
-            stack.push_back({highFirst ? t.left : t.right, -1});
-            stack.push_back({highFirst ? t.right : t.left, -1}); /* popped first */
-        }
-    };
-    /* which inner nodes stay: decided on the first flattening */
-    {
-        std::vector<float4> fr;
-        std::vector<int> fs, which;
-        flatten(0, fr, fs, &which, nullptr);
-        std::vector<int> survivors(which);
-        pruneInnerNodes(fr, fs, survivors, nbPruned);
-        std::vector<char> kept(tree.size(), 0);
-        for (int t : survivors)
-            kept[t] = 1;
-        const int wide = getenv("SOLR_HIP_FREE_WIDE") ? atoi(getenv("SOLR_HIP_FREE_WIDE")) : 0;
-        for (size_t t = 0; t < tree.size(); ++t)
-            if (tree[t].leaf < 0)
-            {
-                tree[t].keep = kept[t] != 0;
-                if (wide > 1 && tree[t].depth % wide != 0) /* experiment: only every wide-th level keeps its nodes */
-                    tree[t].keep = false;
-            }
-    }
-    /* the eight lists: every node's place follows from the sizes of the subtrees before it (children are stored
-     * behind their parent in `tree`, so one backward pass gives the sizes); skip pointers are relative, each list
-     * is self-contained */
-    std::vector<int> size(tree.size(), 0);
-    for (int t = (int)tree.size() - 1; t >= 0; --t)
-        size[t] = tree[t].leaf >= 0 ? 1 : (tree[t].keep ? 1 : 0) + size[tree[t].left] + size[tree[t].right];
-    const int count = size[0];
-    outRows.assign(16 * (size_t)count, make_float4(0.f, 0.f, 0.f, 0.f));
-    outStart.assign(8 * (size_t)count, 0);
-    outOrigin.assign(8 * (size_t)count, -1);
-    struct Place
-    {
-        int node, at;
-    };
-    std::vector<Place> stack;
-    for (int octant = 0; octant < 8; ++octant)
-    {
-        float4 *fr = outRows.data() + 2 * (size_t)octant * count;
-        int *fs = outStart.data() + (size_t)octant * count, *fo = outOrigin.data() + (size_t)octant * count;
-        stack.clear();
-        stack.push_back({0, 0});
-        while (!stack.empty())
-        {
-            const Place v = stack.back();
-            stack.pop_back();
-            const TreeNode &t = tree[v.node];
-            if (t.leaf >= 0)
-            {
-                fr[2 * v.at] = rows[2 * t.leaf];
-                float4 second = rows[2 * t.leaf + 1];
-                second.w = bitsf(1);
-                fr[2 * v.at + 1] = second;
-                fs[v.at] = start[t.leaf];
-                fo[v.at] = origin[t.leaf]; /* the node of the reference's list this leaf is */
-                continue;
-            }
-            int at = v.at;
-            if (t.keep)
-            {
-                fr[2 * at] = make_float4(t.lo[0], t.lo[1], t.lo[2], t.hi[2]);
-                fr[2 * at + 1] = make_float4(t.hi[0], t.hi[1], bitsf(0), bitsf(size[v.node]));
-                ++at;
-            }
-            const bool highFirst = (octant >> t.axis) & 1; /* direction negative along the split axis */
-            const int first = highFirst ? t.right : t.left, second = highFirst ? t.left : t.right;
-            stack.push_back({second, at + size[first]});
-            stack.push_back({first, at});
-        }
-    }
-    return count;
-}
-
-/* Does a nested node list hold what it names: every inner node its direct children (hence everything below it), every
- * leaf its primitives, as the reference's builder makes it so (GPUKernel.cpp:741-830)?  The host's form of
- * k_listEncloses, the same float arithmetic; `prims`: PRIM_ROWS rows per primitive, tagged or not. */
-static bool listEnclosesOnHost(const std::vector<float4> &rows, const std::vector<int> &start, const std::vector<float4> &prims)
-{
-    const int n = (int)start.size();
-    if (rows.size() < 2 * (size_t)n)
-        return false;
-    auto skipOf = [&](int i) { return std::max(bitsi(rows[2 * i + 1].w), 1); };
-    bool encloses = true;
-    for (int i = 0; i < n && encloses; ++i)
-    {
-        const int end = std::min(i + skipOf(i), n);
-        if (bitsi(rows[2 * i + 1].z) > 0 || end <= i + 1)
-            continue;
-        for (int j = i + 1; j < end && encloses; j += skipOf(j))
-            encloses = rows[2 * j].x >= rows[2 * i].x && rows[2 * j].y >= rows[2 * i].y && rows[2 * j].z >= rows[2 * i].z &&
-                       rows[2 * j + 1].x <= rows[2 * i + 1].x && rows[2 * j + 1].y <= rows[2 * i + 1].y &&
-                       rows[2 * j].w <= rows[2 * i].w;
-    }
-    const size_t nbPrims = prims.size() / PRIM_ROWS;
-    for (int i = 0; i < n && encloses; ++i)
-    {
-        const int count = bitsi(rows[2 * i + 1].z);
-        for (int k = 0; k < count && encloses; ++k)
-        {
-            const size_t pi = (size_t)start[i] + k;
-            if (start[i] < 0 || pi >= nbPrims)
-            {
-                encloses = false;
-                break;
-            }
-            const float4 *r = &prims[PRIM_ROWS * pi];
-            const int type = bitsi(r[ROW_P0_TYPE].w) & PRIM_TYPE_MASK;
-            float lo[3] = {r[ROW_P0_TYPE].x, r[ROW_P0_TYPE].y, r[ROW_P0_TYPE].z};
-            float hi[3] = {lo[0], lo[1], lo[2]};
-            auto add = [&](const float4 &v) {
-                lo[0] = std::min(lo[0], v.x), lo[1] = std::min(lo[1], v.y), lo[2] = std::min(lo[2], v.z);
-                hi[0] = std::max(hi[0], v.x), hi[1] = std::max(hi[1], v.y), hi[2] = std::max(hi[2], v.z);
-            };
-            float grow[3] = {r[ROW_SIZE_MAT].x, r[ROW_SIZE_MAT].y, r[ROW_SIZE_MAT].z};
-            if (type == ptTriangle)
-            {
-                add(r[ROW_P1_INDEX]);
-                add(r[ROW_P2]);
-                grow[0] = grow[1] = grow[2] = 0.f;
-            }
-            else if (type == ptCylinder)
-            {
-                add(r[ROW_P1_INDEX]);
-                grow[1] = grow[2] = grow[0];
-            }
-            else if (type == ptSphere)
-                grow[1] = grow[2] = grow[0];
-            /* the builder subtracts and adds in another order: four ulps of the coordinates' magnitude of slack, per
-             * axis - relative, so that it stays far below the order-free walks' cut-off margin (2e-4 of the distance
-             * + 1e-4 of the origin's coordinates, rt_device.h) whatever the scale of the scene */
-            auto slack = [&](int k) { return 4.f * 1.1920929e-7f * std::max(std::max(fabsf(lo[k]), fabsf(hi[k])), fabsf(grow[k])); };
-            const float ex = slack(0), ey = slack(1), ez = slack(2);
-            encloses = rows[2 * i].x <= lo[0] - fabsf(grow[0]) + ex && rows[2 * i].y <= lo[1] - fabsf(grow[1]) + ey &&
-                       rows[2 * i].z <= lo[2] - fabsf(grow[2]) + ez && rows[2 * i + 1].x >= hi[0] + fabsf(grow[0]) - ex &&
-                       rows[2 * i + 1].y >= hi[1] + fabsf(grow[1]) - ey && rows[2 * i].w >= hi[2] + fabsf(grow[2]) - ez;
-        }
-    }
-    return encloses;
-}
-
-/* ... and the same question for a list of the arena as it is now (k_listEncloses); waits for the stream */
-static bool listEnclosesInArena(unsigned offNodes, unsigned offStart, int n)
-{
+    const int n = (int)list.nodes();
     HIPCHECK(hipSetDevice(g.device));
     reserve(g.enclosesFlag, sizeof(int));
     if (!ok())
         return false;
     int found = 1;
     HIPCHECK(hipMemsetAsync(g.enclosesFlag.ptr, 0, sizeof(int), g.stream));
-    hipLaunchKernelGGL(k_listEncloses, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, (const float4 *)g.geometry.ptr, offNodes,
-                       offStart, g.offPrims, n, (int)(g.hostPrims.size() / PRIM_ROWS), (int *)g.enclosesFlag.ptr);
+    hipLaunchKernelGGL(k_listEncloses, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, (const float4 *)g.geometry.ptr, list.offRows,
+                       list.offStart, g.offPrims, n, (int)(g.hostPrims.size() / PRIM_ROWS), (int *)g.enclosesFlag.ptr);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(&found, g.enclosesFlag.ptr, sizeof(int), hipMemcpyDeviceToHost, g.stream));
     HIPCHECK(hipStreamSynchronize(g.stream));
     return ok() && found == 0;
+}
+
+/* the host builders' parameters (list_builders.h), read once per build */
+static ListKnobs listKnobs()
+{
+    ListKnobs knobs;
+    if (const char *v = getenv("SOLR_HIP_PRUNE"))
+        knobs.pruneThreshold = atof(v);
+    if (const char *v = getenv("SOLR_HIP_GROUP_FLAT"))
+        knobs.groupFlat = atoi(v);
+    if (const char *v = getenv("SOLR_HIP_GROUP_LEVELS"))
+        knobs.groupLevels = std::max(atoi(v), 0);
+    return knobs;
+}
+
+/* pruneInnerNodes' decisions on the device (solr_lists.hip) unless SOLR_HIP_LISTS_ON_HOST says otherwise */
+static PruneDecider pruneDecider()
+{
+    if (getenv("SOLR_HIP_LISTS_ON_HOST"))
+        return nullptr;
+    const hipStream_t stream = g.stream;
+    return [stream](const float4 *rows, int n, double threshold, std::vector<char> &keep) {
+        return solrPruneDecisionsOnDevice(rows, n, threshold, keep, stream);
+    };
 }
 
 /* The scene has been rendered `freeCountdown` times since its upload: build the order-free lists now, from the
@@ -1603,17 +1006,18 @@ void maybeBuildOrderFreeLists()
     if (!ok())
         return;
     phase.mark("order-free: host images");
-    const std::vector<float4> &rows = g.hostBoxes;
-    const std::vector<int> &start = g.hostBoxStart;
+    const std::vector<float4> &rows = g.exact.rows;
+    const std::vector<int> &start = g.exact.start;
     const int n = (int)start.size();
     if (n < 2 || rows.size() != 2 * (size_t)n || n > 16000000) /* (beyond that the eight lists pass a dozen GB) */
         return;
+    const ListKnobs knobs = listKnobs();
+    const bool onHost = getenv("SOLR_HIP_LISTS_ON_HOST") != nullptr;
     /* with the arena laid out as the host images are (the usual case: the scene has been rendered once), the checks
      * and the builder read the exact list and the primitive records there */
-    const bool fromArena = !g.geometryDirty && g.geometry.ptr != nullptr && !g.exactStale && !g.deviceAhead &&
-                           !getenv("SOLR_HIP_LISTS_ON_HOST") && !getenv("SOLR_HIP_LISTS_VIA_HOST") && !getenv("SOLR_HIP_FREE_WIDE");
+    const bool fromArena = !g.geometryDirty && g.geometry.ptr != nullptr && !g.exactStale && !g.deviceAhead && !onHost;
     const float4 *arena = (const float4 *)g.geometry.ptr;
-    const bool encloses = fromArena ? listEnclosesInArena(g.offBoxes, g.offBoxStart, n) : listEnclosesOnHost(rows, start, g.hostPrims);
+    const bool encloses = fromArena ? listEnclosesInArena(g.exact) : listEnclosesOnHost(rows, start, g.hostPrims);
     if (!ok())
         return;
     if (!encloses)
@@ -1623,58 +1027,51 @@ void maybeBuildOrderFreeLists()
         return;
     }
     phase.mark("order-free: checks");
-    std::vector<int> origin;
-    if (!fromArena)
-    {
+    std::vector<int> origin; /* (every node of the exact list is its own origin) */
+    auto ownOrigins = [&]() {
         origin.resize(n);
         for (int i = 0; i < n; ++i)
             origin[i] = i;
-    }
-    std::vector<float4> boxesF;
-    std::vector<int> startF, originF;
+    };
     int prunedFree = 0;
     /* on the device (solr_lists.hip: the same tree level by level, the same lists bit for bit) unless told otherwise
      * or declined */
     int count = -1;
-    const bool onHost = getenv("SOLR_HIP_LISTS_ON_HOST") != nullptr || getenv("SOLR_HIP_FREE_WIDE") != nullptr;
     if (!onHost)
     {
         HIPCHECK(hipSetDevice(g.device));
-        const double threshold = getenv("SOLR_HIP_PRUNE") ? atof(getenv("SOLR_HIP_PRUNE")) : 1.0;
-        if (ok() && threshold > 0.0)
+        if (ok() && knobs.pruneThreshold > 0.0)
         {
             dropFreeStage(true);
             if (fromArena)
-                count = solrBuildOrderFreeListsOnDevice(arena + g.offBoxes, (const int *)arena + g.offBoxStart, nullptr, n, threshold, boxesF,
-                                                        startF, originF, &prunedFree, g.stream, &g.freeStage);
+                count = solrBuildOrderFreeListsOnDevice(arena + g.exact.offRows, (const int *)arena + g.exact.offStart, nullptr, n,
+                                                        knobs.pruneThreshold, &prunedFree, g.stream, &g.freeStage);
             else
-                count = solrBuildOrderFreeListsOnDevice(rows.data(), start.data(), origin.data(), n, threshold, boxesF, startF, originF,
-                                                        &prunedFree, g.stream, getenv("SOLR_HIP_LISTS_VIA_HOST") ? nullptr : &g.freeStage);
+            {
+                ownOrigins();
+                count = solrBuildOrderFreeListsOnDevice(rows.data(), start.data(), origin.data(), n, knobs.pruneThreshold, &prunedFree,
+                                                        g.stream, &g.freeStage);
+            }
         }
     }
     const bool stayed = count > 0 && g.freeStage.rows != nullptr;
+    NodeList built(g.orderFree.copies, g.orderFree.lists);
     if (count < 0)
     {
         if (origin.empty())
-        {
-            origin.resize(n);
-            for (int i = 0; i < n; ++i)
-                origin[i] = i;
-        }
-        count = buildFreeOrderLists(rows, start, origin, boxesF, startF, originF, &prunedFree);
+            ownOrigins();
+        count = buildFreeOrderLists(rows, start, origin, built.rows, built.start, built.origin, &prunedFree, knobs.pruneThreshold,
+                                    pruneDecider());
     }
     if (getenv("SOLR_HIP_DEBUG_TREE"))
         fprintf(stderr, "solr_hip: order-free lists: 8 x %d nodes (%d inner nodes that hardly cull left out)\n", count, prunedFree);
     if (count <= 0)
         return;
     phase.mark("order-free: tree, pruning, eight flattenings");
-    g.hostBoxesFree.swap(boxesF);
-    g.hostBoxStartFree.swap(startF);
-    g.nbBoxesFree = count;
-    g.freeRows = 16 * (size_t)count;
+    built.nb = count;
+    g.orderFree = built; /* (in the arena with the next flushGeometry) */
     g.freeHostValid = !stayed;
     g.freeStale = false;
-    g.hostOriginFree.swap(originF);
     g.refitReady = false;
     g.refitPlanPending = true; /* 8-12 ms for 100 k primitives: only scenes that are rotated on the device pay them */
     /* the lists join the arena: added behind what it holds when they are on the device and it is up to date, else
@@ -1683,208 +1080,6 @@ void maybeBuildOrderFreeLists()
         g.freeDirty = true;
     else
         g.geometryDirty = true;
-}
-
-/* Grouping nodes.  The reference's grid builder produces wide levels - 31 sibling leaves under the root of
- * the Cornell scene, 134 top-level cells for the 100k-primitive molecule - and a walk tests every sibling
- * of every node it enters.  Here runs of CONSECUTIVE siblings are wrapped in nodes of our own whose bounds
- * are the union of the siblings' bounds (up to four parts per level, split points by the surface-area
- * heuristic, recursively while a part has more than four members; members about as large as their whole
- * run are left out).  No result can change:
- *   - the depth-first order of the original nodes, hence of every primitive test, is untouched (only
- *     consecutive runs are wrapped), so ties and the shadow accumulation resolve as before;
- *   - a walk reaches an original node only through nodes whose tests it passed, and a group passes
- *     whenever one of its members does: the slab values (b - o) * inv are monotonic in b under IEEE
- *     rounding, so the union's near values are <= and its far values >= the member's on every axis, and
- *     the member's three conditions tnear <= tfar, tnear < far, tfar > 0 carry over (for the sign-selected
- *     form with an infinite reciprocal as well: a member can only pass an axis whose slab contains the
- *     origin coordinate, and then so does the union); the closest-distance cut-off a group is tested
- *     with is never smaller than the one its members will see;
- *   - groups hold no primitives and have no side effects.
- * Requires nested skip pointers and ordered finite bounds (checked by the caller).  Rewrites the node
- * rows and the first-primitive plane in place; returns the new node count. */
-static int groupSiblings(std::vector<float4> &rows, std::vector<int> &start, std::vector<int> &origin)
-{
-    const int n = (int)start.size();
-    auto skipOf = [&](int i) { return bitsi(rows[2 * i + 1].w); };
-    struct Bounds
-    {
-        float lo[3], hi[3];
-    };
-    auto boundsOf = [&](int i) {
-        Bounds b;
-        b.lo[0] = rows[2 * i].x, b.lo[1] = rows[2 * i].y, b.lo[2] = rows[2 * i].z;
-        b.hi[0] = rows[2 * i + 1].x, b.hi[1] = rows[2 * i + 1].y, b.hi[2] = rows[2 * i].w;
-        return b;
-    };
-    auto merge = [](Bounds a, const Bounds &b) {
-        for (int k = 0; k < 3; ++k)
-        {
-            a.lo[k] = std::min(a.lo[k], b.lo[k]);
-            a.hi[k] = std::max(a.hi[k], b.hi[k]);
-        }
-        return a;
-    };
-    auto area = [](const Bounds &b) {
-        const double x = (double)b.hi[0] - b.lo[0], y = (double)b.hi[1] - b.lo[1], z = (double)b.hi[2] - b.lo[2];
-        return x * y + y * z + z * x;
-    };
-    std::vector<float4> outRows;
-    std::vector<int> outStart, outOrigin; /* origin: the caller's tag of each node, -1 for the nodes made here */
-    outRows.reserve(rows.size() + rows.size() / 2);
-    outStart.reserve(start.size() + start.size() / 2);
-    outOrigin.reserve(start.size() + start.size() / 2);
-
-    /* best split of sib[from, to) into two consecutive parts */
-    std::vector<Bounds> suffix;
-    auto splitPoint = [&](const std::vector<int> &sib, int from, int to) {
-        const int count = to - from;
-        suffix.resize((size_t)count);
-        Bounds acc = boundsOf(sib[to - 1]);
-        suffix[count - 1] = acc;
-        for (int k = count - 2; k >= 0; --k)
-        {
-            acc = merge(acc, boundsOf(sib[from + k]));
-            suffix[k] = acc;
-        }
-        Bounds left = boundsOf(sib[from]);
-        double best = 1e300;
-        int bestAt = from + count / 2;
-        for (int k = 1; k < count; ++k)
-        {
-            const double cost = area(left) * k + area(suffix[k]) * (count - k);
-            if (cost < best)
-            {
-                best = cost;
-                bestAt = from + k;
-            }
-            left = merge(left, boundsOf(sib[from + k]));
-        }
-        return bestAt;
-    };
-
-    /* tuning knobs (tools/group_sweep.sh); parts[] / next[] below hold at most 2^4 parts */
-    const int flatMax = std::max(1, getenv("SOLR_HIP_GROUP_FLAT") ? atoi(getenv("SOLR_HIP_GROUP_FLAT")) : 4);
-    struct Emit
-    {
-        std::function<void(const std::vector<int> &, int, int)> siblings;
-        std::function<void(int)> node;
-    } emit;
-    emit.node = [&](int i) {
-        const size_t at = outStart.size();
-        outRows.push_back(rows[2 * i]);
-        outRows.push_back(rows[2 * i + 1]);
-        outStart.push_back(start[i]);
-        outOrigin.push_back(origin[i]);
-        /* (most inner nodes have a handful of children, which siblings() would emit as they are: no list is made for
-         * them - a vector per inner node was two thirds of this function's time for a 100k-primitive scene) */
-        const int end = std::min(i + skipOf(i), n);
-        int few = 0;
-        for (int j = i + 1; j < end && few <= flatMax; j += std::max(skipOf(j), 1))
-            ++few;
-        if (few > flatMax)
-        {
-            std::vector<int> children;
-            for (int j = i + 1; j < end; j += std::max(skipOf(j), 1))
-                children.push_back(j);
-            emit.siblings(children, 0, (int)children.size());
-        }
-        else
-            for (int j = i + 1; j < end;)
-            {
-                const int next = j + std::max(skipOf(j), 1); /* (read before the node is emitted: rows are not touched, but so it stays) */
-                emit.node(j);
-                j = next;
-            }
-        outRows[2 * at + 1].w = bitsf((int)(outStart.size() - at));
-    };
-    /* (a list of a few dozen nodes - the Cornell room - gains 2 % from a third round of splits, lists of
-     * thousands lose 7 %: profiles/r2/group_sweep.txt) */
-    /* (at least one round: with none a run longer than flatMax would be wrapped in a node around itself, for ever - no
-     * grouping at all is solr_hip_set_variant(5)) */
-    const int levels = std::min(
-        4, std::max(1, getenv("SOLR_HIP_GROUP_LEVELS") ? atoi(getenv("SOLR_HIP_GROUP_LEVELS")) : (n <= 64 ? 3 : 2)));
-    emit.siblings = [&](const std::vector<int> &sib, int from, int to) {
-        if (to - from <= flatMax)
-        {
-            for (int k = from; k < to; ++k)
-                emit.node(sib[k]);
-            return;
-        }
-        /* a member about as large as the whole run (a wall of the room, the light cell that spans the
-         * view distance) would make every group around it as large as itself and never culled: such
-         * members stay where they are, ungrouped, and the runs between them are grouped on their own */
-        {
-            Bounds u = boundsOf(sib[from]);
-            for (int k = from + 1; k < to; ++k)
-                u = merge(u, boundsOf(sib[k]));
-            const double limit = 0.5 * area(u);
-            bool dominant = false;
-            for (int k = from; k < to && !dominant; ++k)
-                dominant = area(boundsOf(sib[k])) > limit;
-            if (dominant)
-            {
-                int runStart = from;
-                for (int k = from; k <= to; ++k)
-                    if (k == to || area(boundsOf(sib[k])) > limit)
-                    {
-                        if (k > runStart)
-                            emit.siblings(sib, runStart, k);
-                        if (k < to)
-                            emit.node(sib[k]);
-                        runStart = k + 1;
-                    }
-                return;
-            }
-        }
-        /* `levels` rounds of binary splits without intermediate nodes: up to 2^levels parts */
-        int parts[17];
-        int np = 1;
-        parts[0] = from;
-        parts[1] = to;
-        for (int level = 0; level < levels; ++level)
-        {
-            int next[17];
-            int nn = 0;
-            for (int q = 0; q < np; ++q)
-            {
-                next[nn++] = parts[q];
-                if (parts[q + 1] - parts[q] > 2)
-                    next[nn++] = splitPoint(sib, parts[q], parts[q + 1]);
-            }
-            next[nn] = to;
-            np = nn;
-            for (int q = 0; q <= np; ++q)
-                parts[q] = next[q];
-        }
-        for (int q = 0; q < np; ++q)
-        {
-            const int a = parts[q], b = parts[q + 1];
-            if (b - a == 1)
-            {
-                emit.node(sib[a]);
-                continue;
-            }
-            Bounds u = boundsOf(sib[a]);
-            for (int k = a + 1; k < b; ++k)
-                u = merge(u, boundsOf(sib[k]));
-            const size_t at = outStart.size();
-            outRows.push_back(make_float4(u.lo[0], u.lo[1], u.lo[2], u.hi[2]));
-            outRows.push_back(make_float4(u.hi[0], u.hi[1], bitsf(0), bitsf(1)));
-            outStart.push_back(0);
-            outOrigin.push_back(-1);
-            emit.siblings(sib, a, b);
-            outRows[2 * at + 1].w = bitsf((int)(outStart.size() - at));
-        }
-    };
-    std::vector<int> top;
-    for (int j = 0; j < n; j += std::max(skipOf(j), 1))
-        top.push_back(j);
-    emit.siblings(top, 0, (int)top.size());
-    rows.swap(outRows);
-    start.swap(outStart);
-    origin.swap(outOrigin);
-    return (int)start.size();
 }
 
 void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primitives, int nbPrimitives, Lamp *lamps,
@@ -1927,83 +1122,24 @@ void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primi
             return;
     }
 
-    /* Collapsed walk order.  The reference's grid builder wraps most leaves in
-     * a chain of inner nodes with bit-identical bounds (one per tree level,
-     * GPUKernel.cpp:1008-1035).  A ray that enters the first node of such a
-     * chain enters all of them - same slabs, same ray, same minDistance since
-     * no primitive is tested in between - and a ray that misses it skips all
-     * of them, so dropping every inner node whose only child has the same
-     * bounds changes no result.  Skip pointers are recomputed in the compacted
-     * numbering and stay nested. */
-    /* (one pass: which nodes stay, whether every bound is ordered and finite, the compacted numbering) */
-    std::vector<char> keep(nbActiveBoxes, 1);
-    std::vector<int> newIndex((size_t)nbActiveBoxes + 1);
-    newIndex[0] = 0;
-    g.orderedExact = 1;
-    g.orderedCompact = 1;
-    for (int i = 0; i < nbActiveBoxes; ++i)
-    {
-        const BoundingBox &a = boundingBoxes[i];
-        if (g.nested && a.nbPrimitives == 0)
-        {
-            if (i + 1 < nbActiveBoxes)
-            {
-                const BoundingBox &b = boundingBoxes[i + 1];
-                if (a.indexForNextBox.x >= 2 && b.indexForNextBox.x == a.indexForNextBox.x - 1 &&
-                    memcmp(a.parameters, b.parameters, sizeof(a.parameters)) == 0)
-                    keep[i] = 0;
-            }
-            /* an inner node without emitted children (its cell held only lights or nothing,
-             * GPUKernel.cpp:1096) leads nowhere: entering or missing it changes nothing */
-            if (a.indexForNextBox.x == 1)
-                keep[i] = 0;
-        }
-        const float *lo = &a.parameters[0].x, *hi = &a.parameters[1].x;
-        bool ordered = true;
-        for (int k = 0; k < 3; ++k)
-            ordered = ordered && (lo[k] <= hi[k]) && (fabsf(lo[k]) < 1.0e30f) && (fabsf(hi[k]) < 1.0e30f);
-        if (!ordered)
-        {
-            g.orderedExact = 0;
-            if (keep[i])
-                g.orderedCompact = 0;
-        }
-        newIndex[(size_t)i + 1] = newIndex[i] + (keep[i] ? 1 : 0);
-    }
-    const int nc = newIndex[nbActiveBoxes];
-    std::vector<float4> boxesC(2 * (size_t)nc);
-    std::vector<int> startC(nc), originC(nc);
-    for (int i = 0; i < nbActiveBoxes; ++i)
-        if (keep[i])
-        {
-            const int j = newIndex[i];
-            originC[j] = i;
-            const int end = std::min(i + boundingBoxes[i].indexForNextBox.x, nbActiveBoxes);
-            boxesC[2 * j] = boxes[2 * i];
-            boxesC[2 * j + 1] = boxes[2 * i + 1];
-            boxesC[2 * j + 1].w = bitsf(newIndex[end] - j);
-            startC[j] = start[i];
-        }
+    /* the walk-order list (list_builders.cpp): chains of nodes with the same bounds collapsed ... */
+    std::vector<float4> boxesC;
+    std::vector<int> startC, originC;
+    const int nc = collapseChains(boxes, start, g.nested != 0, boxesC, startC, originC, &g.exact.ordered, &g.walk.ordered);
 
     /* the order-free lists are built when the scene has stayed for a frame (maybeBuildOrderFreeLists): a host that
      * uploads the scene again for every frame - the reference's own way of animating - never pays for them */
-    std::vector<float4> boxesF;
-    std::vector<int> startF, originF;
-    const int nbFreeNodes = 0;
     g.freeCountdown = 0;
-    if (g.nested && g.orderedCompact && nc > 1 && g.grouping && !getenv("SOLR_HIP_NO_FREE_ORDER"))
+    if (g.nested && g.walk.ordered && nc > 1 && g.grouping && !getenv("SOLR_HIP_NO_FREE_ORDER"))
         g.freeCountdown = std::max(1, getenv("SOLR_HIP_FREE_AFTER") ? atoi(getenv("SOLR_HIP_FREE_AFTER")) : 2);
 
+    /* ... cells that do not cull pruned, siblings grouped, groups that do not cull either pruned */
     int nbWalkNodes = nc, prunedBefore = 0, prunedAfter = 0;
-    if (g.nested && g.orderedCompact && nc > 0 && g.grouping)
+    if (g.nested && g.walk.ordered && nc > 0 && g.grouping)
     {
         phase.mark("h2d_scene: chain collapse");
-        pruneInnerNodes(boxesC, startC, originC, &prunedBefore, getenv("SOLR_HIP_REBUILD") != nullptr); /* cells that do not cull: their children join the run above */
-        phase.mark("h2d_scene: prune");
-        groupSiblings(boxesC, startC, originC);
-        phase.mark("h2d_scene: grouping");
-        nbWalkNodes = pruneInnerNodes(boxesC, startC, originC, &prunedAfter); /* groups that do not cull either */
-        phase.mark("h2d_scene: prune groups");
+        nbWalkNodes = buildWalkOrderList(boxesC, startC, originC, listKnobs(), pruneDecider(), &prunedBefore, &prunedAfter,
+                                         [&](const char *what) { phase.mark((std::string("h2d_scene: ") + what).c_str()); });
     }
     if (getenv("SOLR_HIP_DEBUG_TREE"))
     {
@@ -2036,27 +1172,24 @@ void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primi
     g.refitReady = false;
     g.exactStale = false;
     g.refitPlanPending = true;
-    g.hostOriginFree.swap(originF);
     g.deviceAhead = false;
     g.nbMovable = -1;
-    g.hostBoxes.swap(boxes);
-    g.hostBoxesCompact.swap(boxesC);
-    g.hostBoxStart.swap(start);
-    g.hostBoxStartCompact.swap(startC);
-    g.hostOriginCompact = originC;
-    g.hostBoxesFree.swap(boxesF);
-    g.hostBoxStartFree.swap(startF);
-    g.freeRows = 0;
+    g.exact.rows.swap(boxes);
+    g.exact.start.swap(start);
+    g.exact.nb = nbActiveBoxes;
+    g.walk.rows.swap(boxesC);
+    g.walk.start.swap(startC);
+    g.walk.origin.swap(originC);
+    g.walk.nb = nbWalkNodes;
+    g.orderFree.reset();
     g.freeHostValid = true;
     g.freeDirty = false;
     dropFreeStage(true);
-    g.nbBoxesFree = nbFreeNodes;
     g.freeStale = false;
     g.hostPrims.swap(prims);
     /* the lamp's cut-off of the shadow walks rests on this (lampCutoffUsable): another host's boxes are taken at their
      * word only after the check */
-    g.compactEncloses = g.nested && g.orderedCompact && nbWalkNodes > 0 &&
-                        listEnclosesOnHost(g.hostBoxesCompact, g.hostBoxStartCompact, g.hostPrims);
+    g.walkEncloses = g.nested && g.walk.ordered && nbWalkNodes > 0 && listEnclosesOnHost(g.walk.rows, g.walk.start, g.hostPrims);
     phase.mark("h2d_scene: enclosure check");
     retagPrimitives();
     phase.mark("h2d_scene: tags");
@@ -2065,8 +1198,6 @@ void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primi
     upload(g.lamps, l);
     if (ok())
     {
-        g.nbBoxes = nbActiveBoxes;
-        g.nbBoxesCompact = nbWalkNodes;
         g.nbPrimitives = nbPrimitives;
         g.nbLamps = nbLamps;
     }
@@ -2108,16 +1239,16 @@ bool canRotateOne(const float center[3], const float cosAngles[3], const float s
         /* which nodes to refit, in which order: made for the first rotation after the lists changed */
         g.refitPlanPending = false;
         ensureHostFreeLists();
-        buildRefitPlan(g.hostBoxes, g.hostBoxesCompact, g.hostOriginCompact, g.hostBoxesFree, g.hostOriginFree);
+        buildRefitPlan();
     }
     /* the seeds of the two box updates only commute with the unions while viewDistance <= 1e6, and a
      * tree cut off at NB_MAX_BOXES has host-side children the flattened list does not show */
     if (!g.refitReady || g.nbMovable != g.nbPrimitives || g.nbPrimitives <= 0 || !(viewDistance <= 1000000.f) ||
-        !(viewDistance > 0.f) || g.nbBoxes >= NB_MAX_BOXES || !center || !cosAngles || !sinAngles)
+        !(viewDistance > 0.f) || g.exact.nb >= NB_MAX_BOXES || !center || !cosAngles || !sinAngles)
     {
         if (getenv("SOLR_HIP_DEBUG_TREE"))
             fprintf(stderr, "solr_hip_rotate_primitives refused: plan %d, flags for %d of %d primitives, viewDistance %g, %d nodes\n",
-                    (int)g.refitReady, g.nbMovable, g.nbPrimitives, viewDistance, g.nbBoxes);
+                    (int)g.refitReady, g.nbMovable, g.nbPrimitives, viewDistance, g.exact.nb);
         return false;
     }
     return true;
@@ -2138,16 +1269,16 @@ int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const f
     R.sinx = sinAngles[0], R.siny = sinAngles[1], R.sinz = sinAngles[2];
     hipLaunchKernelGGL(k_rotatePrimitives, dim3((unsigned)((g.nbPrimitives + 255) / 256)), dim3(256), 0, g.stream,
                        (float4 *)g.geometry.ptr, g.offPrims, g.nbPrimitives, (const unsigned char *)g.movable.ptr, R);
-    refitList(g.refitWalkLevels, g.offBoxesCompact, g.offBoxStartCompact, viewDistance);
-    if (g.nbBoxesFree > 0 && !g.refitFreeLevels.empty())
-        refitList(g.refitFreeLevels, g.offBoxesFree, g.offBoxStartFree, viewDistance);
+    refitList(g.walk, viewDistance);
+    if (g.orderFree.nb > 0 && !g.orderFree.refitLevels.empty())
+        refitList(g.orderFree, viewDistance);
     else
-        g.freeStale = g.nbBoxesFree > 0; /* no plan: rotated scenes walk the reference's order until the next upload */
+        g.freeStale = g.orderFree.nb > 0; /* no plan: rotated scenes walk the reference's order until the next upload */
     buildLeafRecords(); /* the leaves' copies of their first primitive follow the primitives */
     /* the refitted list encloses by construction (k_refitNodes); asked all the same, like any list the walks cut off at
      * the lamp (a scene that failed the check at its upload is not asked again) */
-    if (g.compactEncloses)
-        g.compactEncloses = listEnclosesInArena(g.offBoxesCompact, g.offBoxStartCompact, g.nbBoxesCompact);
+    if (g.walkEncloses)
+        g.walkEncloses = listEnclosesInArena(g.walk);
     g.exactStale = true;
     g.exactStaleViewDistance = viewDistance;
     HIPCHECK(hipGetLastError());
@@ -2394,13 +1525,14 @@ int solr_hip_read_nodes(int exact, float *rows, int capacityRows)
     if (exact)
         refreshExactList();
     quiesce();
-    int n = 2 * (exact ? g.nbBoxes : g.nbBoxesCompact);
-    unsigned at = exact ? g.offBoxes : g.offBoxesCompact;
+    const NodeList &list = exact ? g.exact : g.walk;
+    int n = 2 * list.nb;
+    unsigned at = list.offRows;
     if (exact >= 2) /* 2 ... 9: the order-free list of octant exact - 2 (0 rows when there are none) */
     {
-        const bool have = exact <= 9 && g.nbBoxesFree > 0 && !g.freeStale && g.freeRows == 16 * (size_t)g.nbBoxesFree;
-        n = have ? 2 * g.nbBoxesFree : 0;
-        at = g.offBoxesFree + 2u * (unsigned)((exact - 2) * g.nbBoxesFree);
+        const bool have = exact <= 9 && g.orderFree.nb > 0 && !g.freeStale;
+        n = have ? 2 * g.orderFree.nb : 0;
+        at = g.orderFree.rowsOf(exact - 2);
     }
     if (!rows)
         return n; /* size query */

@@ -1,5 +1,5 @@
 """The order-free node lists built on the device (sol-r_amd/csrc/solr_lists.hip) against the host builder
-(solr_scene.hip buildFreeOrderLists): the eight lists - bounds, primitive counts, skip pointers, the inner nodes that
+(list_builders.cpp buildFreeOrderLists): the eight lists - bounds, primitive counts, skip pointers, the inner nodes that
 were left out - must be the host's bit for bit, on BASELINE's scenes at their full size, on scenes whose leaves
 coincide (twins: the split that halves by position, which only a stable partition on both sides makes the same),
 and after the frames rendered from them equal the ones of the reference-order walks (variant 6)."""
@@ -26,14 +26,14 @@ def _lists(solr, build, **kw):
     return n, lists, image
 
 
-def _twins(k, width=96, height=64, **info):
+def _twins(k, width=96, height=64, triples=300, **info):
     """spheres in identical pairs, each pair in two different grid cells' worth of distance apart so that they are
     leaves of their own - but some exactly on top of each other in separate leaves is what the reference's grid does
     not produce; coinciding CENTRES of different leaves come from equal boxes: cylinders and their end spheres"""
     k.initialize(width=width, height=height, nbRayIterations=2, **info)
     m = k.add_material(0.6, 0.5, 0.4, specValue=0.3, specPower=20.0)
     rng = solr_rng(3)
-    for i in range(300):
+    for i in range(triples):
         c = (rng.uniform(-6000, 6000), rng.uniform(-4000, 4000), rng.uniform(-3000, 6000))
         k.add_primitive(k_solr.ptSphere, c, size=(120.0, 0, 0), material=m)
         k.add_primitive(k_solr.ptSphere, c, size=(120.0, 0, 0), material=m)          # the same box again
@@ -118,8 +118,7 @@ def test_lists_that_stay_on_the_device(solr, scene, kw, after):
     global k_solr
     k_solr = solr
     build = getattr(solr.scenes, scene)
-    for name in ("SOLR_HIP_LISTS_ON_HOST", "SOLR_HIP_LISTS_VIA_HOST"):
-        os.environ.pop(name, None)
+    os.environ.pop("SOLR_HIP_LISTS_ON_HOST", None)
     n_dev, first, second, third, image = _sequence(solr, build, kw, after)
     os.environ["SOLR_HIP_LISTS_ON_HOST"] = "1"
     try:
