@@ -310,6 +310,43 @@ int solr_hip_rgb_to_jpeg_blocks(const SolrJpegSource *source, const unsigned cha
 /* coefficient blocks the device has produced since the library was loaded */
 unsigned long long solr_hip_jpeg_encoded_blocks(void);
 
+/* The iso-surface of a field of metaballs as triangles, on the device (sol-r_amd/csrc/solr_iso.hip; the arithmetic is
+ * sol-r_amd/csrc/iso_surface.h, that of the reference's apps/scenes/animation/MetaballsScene.cpp, in IEEE binary32 in
+ * source order; the host-only engine runs the same header in loops and gives the same bits).
+ *   grid           gridSize = N cubes a side, (N+1)^3 vertices, vertex (i, j, k) at index (i * (N+1) + j) * (N+1) + k and
+ *                  at position (i * size.x / N - size.x / 2, ...); the surface is where the field equals `threshold`;
+ *                  an output vertex is center + scale * p, its texture coordinates (p.x, p.z) / textureGrid + 1.5
+ *   balls          nbBalls records of x, y, z, squared radius; summed in this order
+ *   field          (N+1)^3 records of {normal x, y, z, value}
+ *   triangles      cubes in index order ((i * N + j) * N + k), a cube's triangles in the order of the engine's case
+ *                  table: the order does not vary from run to run.  `cube` is the cube's index, edge[v] the grid edge
+ *                  vertex v lies on: axis * (N+1)^3 + index of the edge's lower grid vertex, axis 0 / 1 / 2 for i / j / k
+ * solr_hip_iso_field: balls to field.  solr_hip_iso_surface: field to triangles.  solr_hip_metaballs: both, the field
+ * never leaving the device.  The two surface calls return the number of triangles the surface HAS and write the first
+ * min(count, capacity) of them: a caller sizes its buffer with capacity = 0 (triangles may then be null).  All pointers are
+ * host pointers.  Synchronous; on the device of solr_hip_get_device() on a stream of their own, with or without an
+ * initialised scene; the device buffers are given back before the call returns (the 4 KiB case table stays).
+ * -1 with the error set, and nothing launched, for a null pointer, gridSize outside 1 ... SOLR_ISO_MAX_GRID, nbBalls
+ * outside 0 ... SOLR_ISO_MAX_BALLS, a threshold or size that is not finite, a negative capacity.  No balls: no triangles. */
+typedef struct
+{
+    int gridSize;
+    float size[3], threshold, center[3], scale[3], textureGrid;
+} SolrIsoGrid;
+typedef struct
+{
+    float p[3][3], n[3][3], vt[3][2];
+    int cube, edge[3];
+} SolrIsoTriangle; /* 112 bytes */
+#define SOLR_ISO_MAX_GRID 128
+#define SOLR_ISO_MAX_BALLS 1024
+int solr_hip_iso_field(const SolrIsoGrid *grid, const float *balls, int nbBalls, float *field);
+int solr_hip_iso_surface(const SolrIsoGrid *grid, const float *field, SolrIsoTriangle *triangles, int capacity);
+int solr_hip_metaballs(const SolrIsoGrid *grid, const float *balls, int nbBalls, SolrIsoTriangle *triangles,
+                       int capacity);
+/* cubes classified on the device since the library was loaded */
+unsigned long long solr_hip_iso_cubes(void);
+
 /* Device pointers of the current per-pixel buffers (strip-sized), for
  * collectives issued by the launcher (RCCL gather of the RGB strip). */
 void *solr_hip_device_bitmap(void);

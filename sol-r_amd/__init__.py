@@ -90,7 +90,20 @@ class JpegSource(C.Structure):
                 ("quality", C.c_int), ("turned", C.c_int), ("swapRedBlue", C.c_int)]
 
 
+class IsoGrid(C.Structure):
+    """SolrIsoGrid of include/solr_hip.h: the grid the field of metaballs is sampled on and how its surface is placed"""
+    _fields_ = [("gridSize", C.c_int), ("size", C.c_float * 3), ("threshold", C.c_float), ("center", C.c_float * 3),
+                ("scale", C.c_float * 3), ("textureGrid", C.c_float)]
+
+
+class IsoTriangle(C.Structure):
+    """SolrIsoTriangle of include/solr_hip.h: one triangle of an iso-surface"""
+    _fields_ = [("p", (C.c_float * 3) * 3), ("n", (C.c_float * 3) * 3), ("vt", (C.c_float * 2) * 3),
+                ("cube", C.c_int), ("edge", C.c_int * 3)]
+
+
 assert C.sizeof(SceneInfo) == 112 and C.sizeof(PostProcessingInfo) == 16
+assert C.sizeof(IsoGrid) == 48 and C.sizeof(IsoTriangle) == 112
 
 # ---- numpy views of the flattened arrays --------------------------------------
 f4, i4 = np.float32, np.int32
@@ -106,6 +119,9 @@ MATERIAL_DTYPE = np.dtype({"names": ["innerIllumination", "color", "specular", "
                                      "textureIds", "advancedTextureOffset", "advancedTextureIds", "mappingOffset"],
                            "formats": [(f4, 4)] * 3 + [f4] * 4 + [(i4, 4)] * 6 + [(f4, 2)],
                            "offsets": [0, 16, 32, 48, 52, 56, 60, 64, 80, 96, 112, 128, 144, 160], "itemsize": 176})
+ISO_TRIANGLE_DTYPE = np.dtype({"names": ["p", "n", "vt", "cube", "edge"],
+                               "formats": [(f4, (3, 3)), (f4, (3, 3)), (f4, (3, 2)), i4, (i4, 3)],
+                               "offsets": [0, 36, 72, 96, 100], "itemsize": 112})
 LIGHT_DTYPE = np.dtype({"names": ["primitiveId", "materialId", "location", "color"],
                         "formats": [i4, i4, (f4, 3), (f4, 4)], "offsets": [0, 4, 8, 32], "itemsize": 48})
 PP_DTYPE = np.dtype({"names": ["colorInfo", "sceneInfo"], "formats": [(f4, 4), (f4, 4)], "offsets": [0, 16],
@@ -247,6 +263,13 @@ def _declare_hip(L):
     L.solr_hip_rgb_to_jpeg_blocks.argtypes = [P(JpegSource), C.c_void_p, C.c_void_p, C.c_long]
     L.solr_hip_rgb_to_jpeg_blocks.restype = C.c_int
     L.solr_hip_jpeg_encoded_blocks.restype = C.c_ulonglong
+    L.solr_hip_iso_field.argtypes = [P(IsoGrid), C.c_void_p, C.c_int, C.c_void_p]
+    L.solr_hip_iso_field.restype = C.c_int
+    L.solr_hip_iso_surface.argtypes = [P(IsoGrid), C.c_void_p, C.c_void_p, C.c_int]
+    L.solr_hip_iso_surface.restype = C.c_int
+    L.solr_hip_metaballs.argtypes = [P(IsoGrid), C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.solr_hip_metaballs.restype = C.c_int
+    L.solr_hip_iso_cubes.restype = C.c_ulonglong
     # the by-value reference entry points are exercised from C++ (host/HipKernel.cpp);
     # ctypes cannot 16-byte align a by-value struct, so they get no argtypes here
     L.h2d_scene.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -291,6 +314,10 @@ def _declare_host(L):
     L.SolRx_JpegCoefficients.argtypes = [C.c_void_p, i, i, i, i, i, i, i, C.c_void_p, C.c_long]
     L.SolRx_JpegFromCoefficients.argtypes = [C.c_char_p, C.c_void_p, C.c_long, i, i, i, i, i]
     L.SolRx_JpegQuantise.argtypes = [i, i, i, i, C.c_void_p]
+    L.SolRx_AddMetaballs.argtypes = [P(IsoGrid), C.c_void_p, i, i]
+    L.SolRx_IsoField.argtypes = [P(IsoGrid), C.c_void_p, i, C.c_void_p]
+    L.SolRx_IsoSurface.argtypes = [P(IsoGrid), C.c_void_p, C.c_void_p, i]
+    L.SolRx_IsoCaseTable.argtypes = [C.c_void_p, C.c_void_p]
     L.SolRx_SelectEngine.argtypes = [C.c_char_p]
     L.SolRx_SetDeterministic.argtypes = [C.c_long]
     L.SolRx_LastError.argtypes = [C.c_char_p, i]
@@ -345,6 +372,13 @@ SCENE_DEFAULTS = dict(
 """Defaults of the reference's Scene::initialize (apps/scenes/Scene.cpp:199-228) except that the skybox is off
 and transparentColor lets axis planes be hit (the viewer's 0 makes every plane fully transparent,
 GeometryIntersections.cuh:561)."""
+
+
+def iso_grid(grid_size=50, size=(150.0, 150.0, 150.0), threshold=1.0, center=(0.0, 0.0, -2500.0),
+             scale=(40.0, 40.0, 40.0), texture_grid=40.0):
+    """An IsoGrid; the defaults are the reference's MetaballsScene (apps/scenes/animation/MetaballsScene.cpp:34-50, :357)"""
+    return IsoGrid(grid_size, (C.c_float * 3)(*size), threshold, (C.c_float * 3)(*center), (C.c_float * 3)(*scale),
+                   texture_grid)
 
 
 class Kernel:
@@ -438,6 +472,23 @@ class Kernel:
         self.L.SolR_SetPrimitive(idx, p0[0], p0[1], p0[2], p1[0], p1[1], p1[2], p2[0], p2[1], p2[2], size[0],
                                  size[1], size[2], material)
         return idx
+
+    def reset_frame(self):
+        """GPUKernel::resetFrame: drop the frame's primitives, boxes and lamps; materials and textures stay"""
+        self.L.SolRx_ResetFrame()
+
+    def add_metaballs(self, balls, grid_size=50, size=(150.0, 150.0, 150.0), threshold=1.0, center=(0.0, 0.0, -2500.0),
+                      scale=(40.0, 40.0, 40.0), texture_grid=40.0, material=0):
+        """The iso-surface of a field of metaballs appended as triangles (SolRx_AddMetaballs): what the reference's
+        MetaballsScene makes per frame (apps/scenes/animation/MetaballsScene.cpp:247-400).  balls: (n, 4) float32 of
+        x, y, z, squared radius; the defaults are that scene's.  With the HIP engine the field and the cubes run on the
+        device.  Returns the number of triangles added."""
+        b = np.ascontiguousarray(balls, dtype=np.float32).reshape(-1, 4)
+        n = self.L.SolRx_AddMetaballs(C.byref(iso_grid(grid_size, size, threshold, center, scale, texture_grid)),
+                                      b.ctypes.data, len(b), material)
+        if n < 0:
+            raise SolrError("SolRx_AddMetaballs refused its arguments or the engine failed")
+        return n
 
     def set_normals(self, idx, n0, n1, n2):
         self.L.SolR_SetPrimitiveNormals(idx, *n0, *n1, *n2)

@@ -11,6 +11,7 @@
 #include "ImageLoader.h"
 #include "JpegWriter.h"
 #include "../csrc/jpeg_encode.h"
+#include "../csrc/iso_surface.h"
 
 #include <chrono>
 #include <cstdio>
@@ -1441,6 +1442,55 @@ bool GPUKernel::jpegCoefficients(const SolrJpegSource &source, const unsigned ch
                            source.swapRedBlue, x, y, quant, recip,
                            &coefficients[((size_t)y * mcusPerRow + x) * perMcu * 64]);
     return true;
+}
+
+bool GPUKernel::isoField(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field)
+{
+    if (!balls || !field || iso::refusal(&grid, nbBalls, 0))
+        return false;
+    iso::fieldLoop(grid, balls, nbBalls, field);
+    return true;
+}
+
+int GPUKernel::isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity)
+{
+    const iso::CaseTable *table = iso::caseTable();
+    if (!table || !field || (!triangles && capacity != 0) || iso::refusal(&grid, 0, capacity))
+        return -1;
+    return iso::surfaceLoop(grid, *table, field, triangles, capacity);
+}
+
+bool GPUKernel::isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,
+                           std::vector<SolrIsoTriangle> &triangles)
+{
+    const iso::CaseTable *table = iso::caseTable();
+    if (!table || !balls || iso::refusal(&grid, nbBalls, 0))
+        return false;
+    const size_t side = (size_t)grid.gridSize + 1;
+    std::vector<float> field(side * side * side * 4);
+    iso::fieldLoop(grid, balls, nbBalls, field.data());
+    triangles.resize((size_t)iso::surfaceLoop(grid, *table, field.data(), nullptr, 0));
+    iso::surfaceLoop(grid, *table, field.data(), triangles.data(), (int)triangles.size());
+    return true;
+}
+
+int GPUKernel::addMetaballs(const SolrIsoGrid &grid, const float *balls, int nbBalls, int materialId)
+{
+    std::vector<SolrIsoTriangle> triangles;
+    if (!isoSurface(grid, balls, nbBalls, triangles))
+        return -1;
+    /* the reference's GL_TRIANGLES branch (GPUKernel.cpp:2538-2563) */
+    for (const SolrIsoTriangle &t : triangles)
+    {
+        const int p = addPrimitive(ptTriangle);
+        setPrimitive(p, t.p[0][0], t.p[0][1], t.p[0][2], t.p[1][0], t.p[1][1], t.p[1][2], t.p[2][0], t.p[2][1],
+                     t.p[2][2], 0.f, 0.f, 0.f, materialId);
+        setPrimitiveTextureCoordinates(p, make_vec2f(t.vt[0][0], t.vt[0][1]), make_vec2f(t.vt[1][0], t.vt[1][1]),
+                                       make_vec2f(t.vt[2][0], t.vt[2][1]));
+        setPrimitiveNormals(p, make_vec3f(t.n[0][0], t.n[0][1], t.n[0][2]), make_vec3f(t.n[1][0], t.n[1][1], t.n[1][2]),
+                            make_vec3f(t.n[2][0], t.n[2][1], t.n[2][2]));
+    }
+    return (int)triangles.size();
 }
 
 bool GPUKernel::encodeJpeg(const std::string &filename, const unsigned char *pixels, int width, int height,

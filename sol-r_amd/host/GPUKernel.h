@@ -348,6 +348,22 @@ public:
                                         const vec2f &vt2);
     void setPrimitiveNormals(unsigned int index, vec3f n0, vec3f n1, vec3f n2);
     CPUPrimitive *getPrimitive(const unsigned int index);
+    /* extension: the iso-surface of a field of metaballs appended as triangles - what the reference's MetaballsScene makes
+     * per frame with two host loops and the fake-GL entry points (apps/scenes/animation/MetaballsScene.cpp:247-400).
+     * balls: nbBalls records of x, y, z, squared radius.  The triangles come from the engine (the isoSurface hook) and are
+     * appended as the reference's GL_TRIANGLES branch appends them (GPUKernel.cpp:2538-2563): addPrimitive(ptTriangle),
+     * setPrimitive, setPrimitiveTextureCoordinates, setPrimitiveNormals.  The number of triangles added; -1 when an
+     * argument is out of range (include/solr_hip.h) or the engine failed - nothing is added then */
+    int addMetaballs(const SolrIsoGrid &grid, const float *balls, int nbBalls, int materialId);
+    /* the engine's two halves alone (the isoField / isoTriangles hooks), for the tests */
+    bool isoFieldOf(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field)
+    {
+        return isoField(grid, balls, nbBalls, field);
+    }
+    int isoTrianglesOf(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity)
+    {
+        return isoTriangles(grid, field, triangles, capacity);
+    }
     int getLight(int index);
 
     /* rotation of the whole scene about a centre (GPUKernel.h:122-125) */
@@ -558,6 +574,14 @@ protected:
      * loop on the CPU; false = the arguments are out of range or the engine failed (its error is pending) */
     virtual bool jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb,
                                   std::vector<short> &coefficients);
+    /* engine hooks: the iso-surface of a field of metaballs (csrc/iso_surface.h).  isoSurface: balls to triangles, cubes in
+     * index order (`triangles` is resized); isoField: balls to (N+1)^3 records of {nx, ny, nz, value}; isoTriangles: such
+     * a field to triangles - the number the surface has, the first min(count, capacity) written, -1 on failure.  Here:
+     * loops on the CPU; false / -1 = the arguments are out of range or the engine failed (its error is pending) */
+    virtual bool isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,
+                            std::vector<SolrIsoTriangle> &triangles);
+    virtual bool isoField(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field);
+    virtual int isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity);
     void rotatePrimitivesOnly(Frame &f, const vec3f &rotationCenter, const vec3f &cosA, const vec3f &sinA);
     void refitBoxes(Frame &f);
 

@@ -236,6 +236,44 @@ bool HipKernel::jpegCoefficients(const SolrJpegSource &source, const unsigned ch
     return solr_hip_rgb_to_jpeg_blocks(&source, rgb, coefficients.data(), nbBlocks) == 0;
 }
 
+bool HipKernel::isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,
+                           std::vector<SolrIsoTriangle> &triangles)
+{
+    if (solr_hip_device_count() < 1)
+        return GPUKernel::isoSurface(grid, balls, nbBalls, triangles);
+    /* the field is worked out once for a surface of any size: a buffer the last frame's surface fits in is tried first,
+     * and the call repeated only when the surface has outgrown it */
+    triangles.resize(m_isoCapacity);
+    int count = solr_hip_metaballs(&grid, balls, nbBalls, triangles.data(), (int)triangles.size());
+    if (count > (int)triangles.size())
+    {
+        triangles.resize((size_t)count);
+        count = solr_hip_metaballs(&grid, balls, nbBalls, triangles.data(), count);
+    }
+    if (count < 0)
+    {
+        triangles.clear();
+        return false;
+    }
+    triangles.resize((size_t)count);
+    m_isoCapacity = (size_t)count + (size_t)count / 8 + 64;
+    return true;
+}
+
+bool HipKernel::isoField(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field)
+{
+    if (solr_hip_device_count() < 1)
+        return GPUKernel::isoField(grid, balls, nbBalls, field);
+    return solr_hip_iso_field(&grid, balls, nbBalls, field) == 0;
+}
+
+int HipKernel::isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity)
+{
+    if (solr_hip_device_count() < 1)
+        return GPUKernel::isoTriangles(grid, field, triangles, capacity);
+    return solr_hip_iso_surface(&grid, field, triangles, capacity);
+}
+
 int HipKernel::deviceBuildTree(const std::vector<Primitive> &primitives, const std::vector<unsigned char> &emissive,
                                const vec3f &minPos, const vec3f &maxPos, float viewDistance,
                                std::vector<BoundingBox> &boxes, std::vector<int> &order, int &nbLamps)

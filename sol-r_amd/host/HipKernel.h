@@ -69,12 +69,19 @@ protected:
     /* solr_hip_rgb_to_jpeg_blocks (include/solr_hip.h) where there is a device, the base class's loop where there is none */
     bool jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb,
                           std::vector<short> &coefficients) override;
+    /* solr_hip_metaballs, solr_hip_iso_field, solr_hip_iso_surface (include/solr_hip.h) where there is a device, the base
+     * class's loops where there is none */
+    bool isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,
+                    std::vector<SolrIsoTriangle> &triangles) override;
+    bool isoField(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field) override;
+    int isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity) override;
 
 private:
     vec4i m_blockSize;
     int m_sharedMemSize;
     bool m_deviceInitialized;
     bool m_idsOnDevice = false;
+    size_t m_isoCapacity = 4096; /* triangles the buffer of the next isoSurface call starts with */
     bool m_streamed = false;       /* the frame render_begin launched counts its tiles: render_end takes its image band by band */
     bool m_bitmapOnDevice = false; /* render_end(image) delivered to the caller's array: m_bitmap follows when asked */
     unsigned m_sharedSeed = 0, m_sharedState = 0; /* solr_hip_comm_shared_seed and the generator it seeds (render_begin) */

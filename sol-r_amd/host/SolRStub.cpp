@@ -15,6 +15,7 @@
 #include "GPUKernel.h"
 #include "JpegWriter.h"
 #include "../csrc/jpeg_encode.h"
+#include "../csrc/iso_surface.h"
 #include "OBJReader.h"
 #include "PDBReader.h"
 #include "SWCReader.h"
@@ -248,6 +249,47 @@ int SolRx_JpegQuantise(int q, int first, int count, int negative, short *out)
     const jpe::u32 m = jpe::reciprocal(q);
     for (int i = 0; i < count; ++i)
         out[i] = jpe::quantise(negative ? -(first + i) : first + i, q, m);
+    return 0;
+}
+
+/* Extension: GPUKernel::resetFrame */
+int SolRx_ResetFrame()
+{
+    SingletonKernel::kernel()->resetFrame();
+    return 0;
+}
+
+/* Extension: GPUKernel::addMetaballs */
+int SolRx_AddMetaballs(const SolrIsoGrid *grid, const float *balls, int nbBalls, int materialId)
+{
+    if (!grid || !balls)
+        return -1;
+    return SingletonKernel::kernel()->addMetaballs(*grid, balls, nbBalls, materialId);
+}
+
+/* Extensions for the tests: the engine's field and surface stages alone (GPUKernel::isoField / isoTriangles), and the
+ * table of cases the header's generator makes */
+int SolRx_IsoField(const SolrIsoGrid *grid, const float *balls, int nbBalls, float *field)
+{
+    if (!grid || !balls || !field)
+        return -1;
+    return SingletonKernel::kernel()->isoFieldOf(*grid, balls, nbBalls, field) ? 0 : -1;
+}
+
+int SolRx_IsoSurface(const SolrIsoGrid *grid, const float *field, SolrIsoTriangle *triangles, int capacity)
+{
+    if (!grid || !field)
+        return -1;
+    return SingletonKernel::kernel()->isoTrianglesOf(*grid, field, triangles, capacity);
+}
+
+int SolRx_IsoCaseTable(unsigned char *count, unsigned char *edges)
+{
+    iso::CaseTable table;
+    if (!count || !edges || !iso::buildCaseTable(table))
+        return -1;
+    memcpy(count, table.count, sizeof(table.count));
+    memcpy(edges, table.edges, sizeof(table.edges));
     return 0;
 }
 

@@ -17,6 +17,7 @@
  */
 #pragma once
 
+#include "../../include/solr_hip.h"
 #include "../../include/solr_types.h"
 
 #ifdef __cplusplus
@@ -139,6 +140,19 @@ int SolRx_JpegCoefficients(const unsigned char *pixels, int width, int height, i
 int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, long nbBlocks, int width, int height,
                                int jpegQuality, int lumaH, int lumaV);
 int SolRx_JpegQuantise(int q, int first, int count, int negative, short *out);
+/* GPUKernel::resetFrame: the current frame's primitives, boxes and lamps dropped, materials and textures kept - what a
+ * scene that makes its geometry anew every frame begins a frame with */
+int SolRx_ResetFrame();
+/* the iso-surface of a field of metaballs appended to the scene as triangles of material materialId
+ * (GPUKernel::addMetaballs; grid, balls and the order of the triangles: include/solr_hip.h).  With the HIP engine the field
+ * and the cubes run on the device.  The number of triangles added, -1 on error (nothing is added then) */
+int SolRx_AddMetaballs(const SolrIsoGrid *grid, const float *balls, int nbBalls, int materialId);
+/* for the tests: the two halves through the current engine (solr_hip_iso_field / solr_hip_iso_surface or the loops over
+ * csrc/iso_surface.h; same arguments and results), and the engine's table of cases: count[256] triangles per case,
+ * edges[256][15] their cube edges */
+int SolRx_IsoField(const SolrIsoGrid *grid, const float *balls, int nbBalls, float *field);
+int SolRx_IsoSurface(const SolrIsoGrid *grid, const float *field, SolrIsoTriangle *triangles, int capacity);
+int SolRx_IsoCaseTable(unsigned char *count, unsigned char *edges);
 
 /* ---------- Extensions ---------- */
 /* "hip" (default) or "host-only"; destroys the current singleton */

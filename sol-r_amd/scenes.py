@@ -222,3 +222,79 @@ def pdb_molecule(k, path, width=1920, height=1080, iterations=3, geometry_type=3
     k.compact_boxes(True)
     k.set_camera((0.0, 0.0, -15000.0), look_at=(0.0, 0.0, 0.0))
     return k
+
+
+def metaball_positions(timer, count=50, amplitude=(50.0, 50.0, 50.0), ratio=0.1):
+    """(count, 4) float32 of x, y, z, squared radius: squared radius 5 + i (MetaballsScene.cpp:147) and the trajectories
+    of apps/scenes/animation/MetaballsScene.cpp:214-241 about the origin - the branch that moves the balls with its
+    skeleton centre at 0, its ratio 0.1 and the plain build's amplitude size / 3 (:49)."""
+    import numpy as np
+    out = np.zeros((count, 4), np.float32)
+    ax, ay, az = amplitude
+    for i in range(count):
+        t = i * 3 + timer * 40.0
+        c = 2.0 * math.cos(t / 600)
+        z = abs(ratio * az * math.sin(math.cos(t / ((500, 400, 450, 450)[i % 4] + i))) - c)
+        if i % 4 == 0:
+            x = -ratio * ax * math.cos(t / (740 + i * count)) - c
+            y = ratio * ay * math.sin(t / (620 + i * count)) - c
+        elif i % 4 == 1:
+            x = ratio * ax * math.sin(t / (420 + i * count)) + c
+            y = -ratio * ay * math.cos(t / (340 + i * count)) - c
+        elif i % 4 == 2:
+            x = ratio * ax * math.cos(t / (820 + count)) - 0.2 * math.sin(t / 600)
+            y = ratio * ay * math.sin(t / (512 + count)) - 0.2 * math.sin(t / 400)
+        else:
+            x = ratio * ax * math.cos(t / (1200 + count)) - 0.4 * math.sin(t / 1250)
+            y = ratio * ay * math.sin(t / (2120 + count)) - 0.4 * math.sin(t / 640)
+        out[i] = (x, y, z, 5.0 + i)
+    return out
+
+
+def metaballs(k, timer=0.0, width=512, height=512, iterations=3, balls=None, grid_size=50, count=50, size=150.0,
+              scale=40.0, center=(0.0, 0.0, -2500.0), threshold=1.0, seed=2017, **scene_info):
+    """One frame of the reference's MetaballsScene (apps/scenes/animation/MetaballsScene.cpp:150-419), geometry made anew
+    every frame: resetFrame, the iso-surface of the balls as triangles (Kernel.add_metaballs: grid 50, 50 balls of squared
+    radius 5 + i, size 150, scale 40, centre (0, 0, -2500)), the Cornell box, the lamp at (-10000, 10000, -10000) of radius
+    500, compactBoxes(true).  Call it again with the next timer value (the reference steps it by 1.5) for the next
+    frame; the first call initialises the kernel and makes the materials.
+
+    In the reference's plain build the balls never leave the origin: only its Kinect and Leap branches move them.  This
+    scene moves them on the trajectories of :214-241 about the origin (metaball_positions); `balls` overrides them.
+    Returns the number of triangles of the surface."""
+    metaballs_begin(k, width=width, height=height, iterations=iterations, seed=seed, **scene_info)
+    m = k.metaballs_materials
+    if balls is None:
+        balls = metaball_positions(timer, count=count, amplitude=(size / 3.0,) * 3)
+    k.reset_frame()
+    n = k.add_metaballs(balls, grid_size=grid_size, size=(size,) * 3, threshold=threshold, center=center,
+                        scale=(scale,) * 3, material=m["surface"])
+    metaballs_surroundings(k)
+    k.compact_boxes(True)
+    return n
+
+
+def metaballs_begin(k, width=512, height=512, iterations=3, seed=2017, **scene_info):
+    """what comes before the first frame: the kernel initialised, the materials, the camera (nothing on later calls)"""
+    if k.initialized and getattr(k, "metaballs_materials", None):
+        return
+    rng = LCG(seed)
+    scene_info.setdefault("graphicsLevel", glFull)
+    k.initialize(width=width, height=height, nbRayIterations=iterations, **scene_info)
+    c = _wall_color(rng)
+    k.metaballs_materials = dict(
+        surface=k.add_material(c[0], c[1], c[2], reflection=0.3, specValue=1.0, specPower=100.0),
+        walls=[k.add_material(*_wall_color(rng), specValue=0.1, specPower=200.0) for _ in range(6)],
+        lamp=k.add_material(1.0, 1.0, 1.0, innerIllumination=2.0))
+    k.set_camera((0.0, 0.0, -15000.0))
+
+
+def metaballs_surroundings(k):
+    """what MetaballsScene.cpp:403-413 adds after the surface: the Cornell box (six rectangles) and the lamp"""
+    m = k.metaballs_materials
+    x, y, z, w, h, d = 0.0, 15000.0, 0.0, 20000.0, 20000.0, 20000.0
+    walls = ((ptXYPlane, (x, y, z + d)), (ptXYPlane, (x, y, z - d)), (ptYZPlane, (x - w, y, z)),
+             (ptYZPlane, (x + w, y, z)), (ptXZPlane, (x, y + h, z)), (ptXZPlane, (x, y - h, z)))
+    for (ptype, p0), material in zip(walls, m["walls"]):
+        k.add_primitive(ptype, p0, size=(w, h, d), material=material)
+    k.add_primitive(ptSphere, (-10000.0, 10000.0, -10000.0), size=(500.0, 0, 0), material=m["lamp"], movable=0)
