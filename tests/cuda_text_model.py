@@ -140,7 +140,16 @@ def _rotate(p, center, cx, cy, cz, sx, sy, sz):
 
 
 def to_int(x):
-    """C's (int) of a float: truncation towards zero (the scenes of the tests stay far inside int's range)"""
+    """(int) of a float as the CUDA engine's device code converts (cvt.rzi.s32.f32, PTX ISA "cvt"): truncation towards
+    zero, a NaN is 0, what is beyond int's range saturates.  (The scenes stay far inside the range; the synthetic random
+    buffers of tests/post_processing_cases.py do not.)"""
+    x = float(x)
+    if x != x:
+        return 0
+    if x >= 2147483648.0:
+        return 2147483647
+    if x <= -2147483648.0:
+        return -2147483648
     return int(x)
 
 
