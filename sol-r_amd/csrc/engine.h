@@ -190,14 +190,14 @@ struct NodeList
 
     void reset() { *this = NodeList(copies, lists); }
     unsigned nodes() const { return (unsigned)lists * (unsigned)nb; }
-    unsigned rowsOf(int list) const { return offRows + 2u * (unsigned)list * (unsigned)nb; }
-    unsigned offThin() const { return offRows + 2u * nodes() + 2u; }
-    unsigned offSorted() const { return offRows + 2u * (2u * nodes() + 2u); }
+    unsigned rowsOf(int list) const { return solrdev::listRows(offRows, (unsigned)nb, (unsigned)list); }
+    unsigned offThin() const { return solrdev::listThin(offRows, nodes()); }
+    unsigned offSorted() const { return solrdev::listSorted(offRows, nodes()); }
     /* the three parts of the layout: each takes the first free row and returns the next */
     unsigned layRows(unsigned row)
     {
         offRows = row;
-        return row + (unsigned)copies * (2u * nodes() + 2u);
+        return row + (unsigned)copies * solrdev::listCopyRows(nodes());
     }
     unsigned layStart(unsigned row)
     {
@@ -228,7 +228,7 @@ struct Engine
     /* the node lists: the reference's as uploaded; the walk-order list (chains collapsed, siblings grouped, inner nodes
      * that hardly cull pruned) with its thin copy; the eight order-free lists, one per direction octant - the leaves of
      * the scene under a surface-area hierarchy of our own (buildFreeOrderLists) - with thin and sorted copies */
-    NodeList exact = NodeList(1, 1), walk = NodeList(2, 1), orderFree = NodeList(3, 8);
+    NodeList exact = NodeList(1, 1), walk = NodeList(2, 1), orderFree = NodeList(3, solrdev::ORDER_FREE_LISTS);
     int freeCountdown = 0; /* renders until the order-free lists are built (0: not scheduled) */
     /* lists built on the device stay there and go into the arena with a device-to-device copy (freeStage, until the
      * next flushGeometry); orderFree's host image is filled from the arena when somebody needs it (ensureHostFreeLists:

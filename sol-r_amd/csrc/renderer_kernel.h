@@ -504,23 +504,11 @@ __global__ __launch_bounds__(WAVE, SOLR_WAVES_PER_EU) void k_walkBound(const Sce
         const bool took_part = doneAfter >= 0;
         /* (a lane that took no part gets a harmless ray: its cursor is done from the start) */
         const WalkRay r = makeWalkRay(V(a.x, a.y, a.z), took_part ? V(b.x, b.y, b.z) : V(1.f, 1.f, 1.f));
-        Scene W = S;
-        if (__builtin_amdgcn_readfirstlane(h.y))
-        {
-            const int octant = __builtin_amdgcn_readfirstlane(h.z);
-            W.offBoxes = S.offBoxesFree + 2u * (unsigned)(octant * S.nbBoxesFree);
-            W.offLeaf = S.offLeafFree + 4u * (unsigned)(octant * S.nbBoxesFree);
-            W.nbBoxes = S.nbBoxesFree;
-        }
-        if (__builtin_amdgcn_readfirstlane(h.w) & 1) /* the walk took the thin copy of its list (rt_device.h tightRay) */
-            W.offBoxes += __builtin_amdgcn_readfirstlane(h.y) ? 16u * (unsigned)S.nbBoxesFree + 2u : 2u * (unsigned)S.nbBoxes + 2u;
         /* the form of the node loop the recorded walk took (rt_device.h walkOrder: bits 1-2 of the record's fourth word) */
         const int order = (FEAT & F_DEEP) ? (__builtin_amdgcn_readfirstlane(h.w) >> 1) & 3 : 0;
-        if (order)
-        {
-            W.offBoxes += 32u * (unsigned)S.nbBoxesFree + 4u;
-            W.nbBoxes = S.nbBoxesFree << 5; /* (such a walk's cursors count bytes: rt_device.h SOLR_NEXT_BY_BYTES) */
-        }
+        /* the list it took: order-free or not, its octant, the thin copy (bit 0; rt_device.h tightRay), the sorted one */
+        const Scene W = walkList(S, __builtin_amdgcn_readfirstlane(h.y) != 0, __builtin_amdgcn_readfirstlane(h.z),
+                                 (__builtin_amdgcn_readfirstlane(h.w) & 1) != 0, order != 0);
         const PackedRay pr = packRay(r);
         const float cutOff = a.w;
         int cursor = took_part ? 0 : SOLR_CURSOR_DONE;

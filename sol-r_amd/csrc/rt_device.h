@@ -1718,7 +1718,6 @@ SOLR_DEV bool closestHitWalk(const Scene &S_, const SceneInfo &si_, bool active,
         const bool checked = unitRays && attempt == 0;
         const bool freeList = freeOrder || checked;
         SOLR_T(const unsigned long long tAttempt = SOLR_NOW();)
-        Scene W = S;
         int octant = 0;
         int order = 0; /* the form of the node loop: 0 any record and ray, 1 sorted bounds (SOLR_ORDER_SORTED) */
         if (freeList)
@@ -1728,23 +1727,15 @@ SOLR_DEV bool closestHitWalk(const Scene &S_, const SceneInfo &si_, bool active,
             const int signs = (r.d.x < 0.f ? 1 : 0) | (r.d.y < 0.f ? 2 : 0) | (r.d.z < 0.f ? 4 : 0);
             const int lane = (int)__builtin_ctzll(ballot(lanesNow));
             octant = __builtin_amdgcn_readlane(signs, lane);
-            W.offBoxes = S.offBoxesFree + 2u * (unsigned)(octant * S.nbBoxesFree);
-            W.offLeaf = S.offLeafFree + 4u * (unsigned)(octant * S.nbBoxesFree);
-            W.nbBoxes = S.nbBoxesFree;
             /* every ray of the wave points into the list's octant (a tile of primary rays, but for the tiles the
              * camera's axes run through): the copy with sorted bounds, the node loop without its six min / max */
             if ((FEAT & F_DEEP) && S.sortedLists && !tight && ballot(lanesNow && signs != octant) == 0ull)
-            {
                 order = 1;
-                W.offBoxes += 32u * (unsigned)S.nbBoxesFree + 4u;
-                W.nbBoxes = S.nbBoxesFree << 5; /* (this walk's cursors count bytes: SOLR_NEXT_BY_BYTES) */
-            }
         }
-        if (tight) /* the same nodes, leaf records and start indices: only the bounds differ */
-            W.offBoxes += freeList ? 16u * (unsigned)S.nbBoxesFree + 2u : 2u * (unsigned)S.nbBoxes + 2u;
+        /* (fatCheck: the thin copy of the walk-order list while `tight` is false - see tightShort) */
         const bool fatCheck = tightShort && !freeList;
-        if (fatCheck)
-            W.offBoxes += 2u * (unsigned)S.nbBoxes + 2u;
+        /* the thin copy has the same nodes, leaf records and start indices: only the bounds differ */
+        const Scene W = walkList(S, freeList, octant, tight || fatCheck, order == 1);
         /* The reference's cut-off never culls for such rays (a slab parameter of order 1 against a distance of
          * thousands).  The order-free walk may cull by the TRUE distance: a box whose entry point lies farther than the
          * closest hit so far holds nothing that could replace it, not even on a tie.  The margins cover the rounding
@@ -2132,7 +2123,6 @@ SOLR_DEV float shadowWalk(const Scene &S_, const SceneInfo &si_, bool active, v3
      * hangs in mid-air, and every shadow ray prolonged beyond it entered a wall's leaf and made its plane test for a
      * hit that was thrown away (solr_hip_set_variant(15) walks without). */
     const bool lampCut = tidy && !freeOrder && (S.opaqueShadows & SHADOWS_LAMP_CUTOFF);
-    Scene W = S;
     float farFree = 0.f;
     int octant = 0;
     bool reversed = false;
@@ -2144,9 +2134,6 @@ SOLR_DEV float shadowWalk(const Scene &S_, const SceneInfo &si_, bool active, v3
         /* every ray of the wave points into the octant OPPOSITE the list's (the points of a tile towards one lamp): the
          * copy with sorted bounds read the other way round (SOLR_ORDER_REVERSED) */
         reversed = (FEAT & F_DEEP) && S.sortedLists && ballot(active && signs != octant) == 0ull;
-        W.offBoxes = S.offBoxesFree + 2u * (unsigned)(octant * S.nbBoxesFree);
-        W.offLeaf = S.offLeafFree + 4u * (unsigned)(octant * S.nbBoxesFree);
-        W.nbBoxes = S.nbBoxesFree;
     }
     if (freeOrder || lampCut)
         farFree = 1.0002f + 1.0e-4f * (fabsf(r.o.x) + fabsf(r.o.y) + fabsf(r.o.z)) / lengthOL;
@@ -2155,14 +2142,8 @@ SOLR_DEV float shadowWalk(const Scene &S_, const SceneInfo &si_, bool active, v3
         (lampCut && longRay(r.d) && minDistance >= 2.f) ? fminf(minDistance, farFree) : minDistance;
     /* the thin copy of that list (tightRay: a shadow ray reaches from the point to the lamp, thousands of units) */
     const bool tight = (FEAT & F_PLANE) && tidy && S.tightLists && ballot(active && !tightRay(r, si)) == 0ull;
-    if (tight)
-        W.offBoxes += freeOrder ? 16u * (unsigned)S.nbBoxesFree + 2u : 2u * (unsigned)S.nbBoxes + 2u;
     reversed = reversed && !tight;
-    if (reversed)
-    {
-        W.offBoxes += 32u * (unsigned)S.nbBoxesFree + 4u;
-        W.nbBoxes = S.nbBoxesFree << 5; /* (this walk's cursors count bytes: SOLR_NEXT_BY_BYTES) */
-    }
+    const Scene W = walkList(S, freeOrder, octant, tight, reversed);
     const int nbBoxes = W.nbBoxes;
     const PackedRay pr = packRay(r);
     int cursor = (active && result < si.shadowIntensity) ? 0 : SOLR_CURSOR_DONE;

@@ -175,9 +175,21 @@ struct SceneArgs
      * are sorted for the octant its list was flattened for - per axis (the bound a ray of that octant reaches first, the
      * other one): {n.x, n.y, n.z, f.z} {f.x, f.y, count, 32 x skip: bytes} (solr_scene.hip sortFreeLists).  A walk whose rays all
      * have that octant's signs - or all the opposite ones - takes it with a node loop that has no min / max per axis
-     * (rt_device.h SOLR_ORDER_SORTED / _REVERSED).  Row offset: offBoxesFree + 2 (16 nbBoxesFree + 2) */
+     * (rt_device.h SOLR_ORDER_SORTED / _REVERSED).  Where it lies: listSorted below */
     int sortedLists;
 };
+
+/* Where the arena holds the copies of a node list (engine.h NodeList lays them out, the walks of rt_device.h and the
+ * replay of renderer_kernel.h find them: through these functions, both).  `lists` lists of `nb` nodes each lie one behind
+ * the other, two rows a node, and one pad record behind the last (the walk requests the record after the node it tests);
+ * behind that the thin copy, padded alike, and behind that the copy with sorted bounds.  offRows: the first row of the
+ * first list; nodes = lists x nb.  Leaf records: four rows a node, list behind list. */
+const int ORDER_FREE_LISTS = 8; /* one per direction octant */
+__host__ __device__ constexpr unsigned listCopyRows(unsigned nodes) { return 2u * nodes + 2u; }
+__host__ __device__ constexpr unsigned listRows(unsigned offRows, unsigned nb, unsigned list) { return offRows + 2u * (list * nb); }
+__host__ __device__ constexpr unsigned listThin(unsigned offRows, unsigned nodes) { return offRows + listCopyRows(nodes); }
+__host__ __device__ constexpr unsigned listSorted(unsigned offRows, unsigned nodes) { return offRows + 2u * listCopyRows(nodes); }
+__host__ __device__ constexpr unsigned listLeaf(unsigned offLeaf, unsigned nb, unsigned list) { return offLeaf + 4u * (list * nb); }
 
 /* Device view: everything is read through the CONSTANT address space.  The
  * scene is immutable for the lifetime of a launch, and for loads from this
@@ -245,6 +257,33 @@ __device__ __forceinline__ Scene makeScene(const SceneArgs &a)
     s.tightLists = a.tightLists;
     s.sortedLists = a.sortedLists;
     return s;
+}
+
+/* The view of the scene a walk takes: the walk-order list, or (freeList) the order-free list of `octant`; of that list
+ * the rows as they are, their thin copy (thin), or - of an order-free list only - the copy with sorted bounds (sorted).
+ * The walks never ask for both, there is no thin sorted copy; if both are set, sorted wins, and sorted without freeList
+ * is ignored (only a malformed walk record can say either: k_walkBound then replays over rows that exist).  Leaf
+ * records and start indices are the same for every copy.  A walk over the sorted copy has cursors that count bytes
+ * (rt_device.h SOLR_NEXT_BY_BYTES: the copy's skip fields are 32 x skip), so its nbBoxes is the list's length in bytes. */
+__device__ __forceinline__ Scene walkList(const Scene &S, bool freeList, int octant, bool thin, bool sorted)
+{
+    Scene W = S;
+    unsigned nodes = (unsigned)S.nbBoxes;
+    if (freeList)
+    {
+        nodes = (unsigned)ORDER_FREE_LISTS * (unsigned)S.nbBoxesFree;
+        W.offBoxes = listRows(S.offBoxesFree, (unsigned)S.nbBoxesFree, (unsigned)octant);
+        W.offLeaf = listLeaf(S.offLeafFree, (unsigned)S.nbBoxesFree, (unsigned)octant);
+        W.nbBoxes = S.nbBoxesFree;
+    }
+    if (freeList && sorted)
+    {
+        W.offBoxes = listSorted(W.offBoxes, nodes);
+        W.nbBoxes = S.nbBoxesFree << 5; /* (32 bytes a node) */
+    }
+    else if (thin)
+        W.offBoxes = listThin(W.offBoxes, nodes);
+    return W;
 }
 
 typedef float f8v __attribute__((ext_vector_type(8)));
