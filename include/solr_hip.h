@@ -492,7 +492,9 @@ void solr_hip_render_counting(const SceneInfo *sceneInfo, const vec4i *objects,
  * SOLR_ORDER_SORTED); 13 = a streamed frame (solr_hip_stream_next_image) whose waves do not write the bands' words: the
  * host goes by the end of the kernel (solr_hip_d2h_streamed_image); 14 = the tile counters of streamed frames are zeroed
  * every third frame, as they are when a count nears 2^32; 15 = the shadow walks in the reference's order keep the
- * reference's cut-off alone (no lamp cut-off, rt_device.h shadowWalk).  Every setting renders the same frame. */
+ * reference's cut-off alone (no lamp cut-off, rt_device.h shadowWalk); 16 = the trace makes the trips that no lane takes
+ * (the deferred-reflection trip of a wave without one, the material gather and the shader call of a trip in which every
+ * lane missed; rt_device.h launchRayTracing).  Every setting renders the same frame. */
 void solr_hip_set_variant(int variant);
 /* Bounce rays (|direction| = 1 - rayEpsilon) of the long-list triangle kernels on the order-free lists, checked: lanes
  * whose hit has a rival the reference's cut-off could have preferred are walked again in the reference's order

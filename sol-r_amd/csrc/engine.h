@@ -167,7 +167,9 @@ enum Variant
     VARIANT_UNSORTED_LISTS = 12, /* no walk takes the copies of the order-free lists with sorted bounds */
     VARIANT_NO_BAND_WORDS = 13,  /* a streamed frame's waves write no band's word */
     VARIANT_ZERO_STREAM_COUNTERS = 14, /* the tile counters of streamed frames zeroed every third frame */
-    VARIANT_NO_LAMP_CUTOFF = 15  /* shadow walks in the reference's order keep the reference's cut-off alone */
+    VARIANT_NO_LAMP_CUTOFF = 15, /* shadow walks in the reference's order keep the reference's cut-off alone */
+    VARIANT_ALL_TRIPS = 16       /* the trace makes the trips no lane takes: the deferred-reflection trip of a wave without
+                                  * one, the gather and the shader call of a trip in which every lane missed */
 };
 
 /* A node list of the resident scene: its host image, the count a frame is told, where the arena holds it (the layout

@@ -2424,13 +2424,33 @@ SOLR_DEV float4 intersectionShader(const Scene &S, const SceneInfo &si, int pi, 
     return c;
 }
 
+/* The records of a hit that launchRayTracing has gathered for its own bookkeeping and hands to the shader: the material
+ * id of the primitive (row ROW_SIZE_MAT, .w), its index word (row ROW_P1_INDEX, .w) and the material's hot half.  The
+ * shader used to gather all three again - again() hides from the compiler that it is the same scene - behind two more
+ * dependent round trips.  `given` is wave-uniform.  Handed over only where handsOverHit() says so: the instantiations
+ * whose trace reads its arguments phase by phase (F_ARGS: neither triangles nor the texture tier) and does not count.
+ * In the others the longer lives of these registers end in scratch (profiles/r12/trace_dead_trips.txt), and they
+ * compile to the code they always had. */
+struct HitRecords
+{
+    bool given;
+    int materialId, primIndex;
+    MaterialHot mh;
+};
+template <int COUNT, int FEAT>
+constexpr bool handsOverHit()
+{
+    return COUNT == 0 && (FEAT & F_ARGS) != 0 && (FEAT & (F_TRI | F_TEX)) == 0;
+}
+
 /* GI:916-1080.  Every lane of the wave calls this together; `active` marks
  * the lanes that actually shade.  The light loop is wave-uniform, the shadow
  * walk inside it is wave-synchronous. */
 template <int COUNT, int FEAT>
 SOLR_DEV v3 primitiveShader(const Scene &S_, bool active, int index, const SceneInfo &si_, v3 origin, v3 &normal,
                             int objectId, v3 intersection, v3 areas, v3 &closestColor, int iteration,
-                            float &shadowIntensity, v3 &totalBlinn, float4 &attributes, Counters &cnt)
+                            float &shadowIntensity, v3 &totalBlinn, float4 &attributes, Counters &cnt,
+                            const HitRecords *hit = nullptr)
 {
     SOLR_T(const unsigned long long tShade0 = SOLR_NOW();)
     /* the arguments as the head of the shader reads them (again() above); every lamp reads them again, before its shadow
@@ -2439,9 +2459,20 @@ SOLR_DEV v3 primitiveShader(const Scene &S_, bool active, int index, const Scene
     const SceneInfo si = again<FEAT>(si_);
     const int pi = active ? objectId : 0;
     const int type = asint(primRow(S, pi, ROW_P0_TYPE).w) & PRIM_TYPE_MASK; /* row 0 carries type + material facts */
-    const int materialId = asint(primRow(S, pi, ROW_SIZE_MAT).w);
-    const int primIndex = asint(primRow(S, pi, ROW_P1_INDEX).w);
-    const MaterialHot mh = loadMaterialHot(S, materialId);
+    int materialId, primIndex;
+    MaterialHot mh;
+    if (handsOverHit<COUNT, FEAT>() && hit && hit->given)
+    {
+        materialId = hit->materialId;
+        primIndex = hit->primIndex;
+        mh = hit->mh;
+    }
+    else
+    {
+        materialId = asint(primRow(S, pi, ROW_SIZE_MAT).w);
+        primIndex = asint(primRow(S, pi, ROW_P1_INDEX).w);
+        mh = loadMaterialHot(S, materialId);
+    }
     v3 lampsColor = V(0.f, 0.f, 0.f);
     v3 intersectionColor = V(0.f, 0.f, 0.f);
     float4 specular = make_float4(mh.specular.x, mh.specular.y, mh.specular.z, 0.f);
@@ -2732,6 +2763,27 @@ struct V3Ref
     }
 };
 
+/* The phase machine of launchRayTracing leaves out the trips no lane takes unless the host asks
+ * for all of them (solr_hip_set_variant(16): SHADOWS_ALL_TRIPS, a bit of the word the shadow walks read anyway).
+ * Compiled per instantiation: not into the triangle kernels that hold no scratch and would get 16 to 32 bytes a lane from
+ * the new edges (the short-list sphere + triangle kernels, the F_STACK forms, the untextured mix) - those stay the code
+ * they were; into the long-list sphere + triangle pair, which takes it without scratch (the mesh's background tiles:
+ * - 4 %), and into the texture / GI tier, which lives with scratch either way (profiles/r12/trace_dead_trips.txt). */
+template <int FEAT>
+constexpr bool skipsDeadTrips()
+{
+    return (FEAT & F_TRI) == 0 || (FEAT & (F_TEX | F_FULL)) != 0 ||
+           ((FEAT & F_ALL) == (F_SPHERE | F_TRI) && (FEAT & F_DEEP) != 0 && (FEAT & F_STACK) == 0);
+}
+template <int FEAT>
+SOLR_DEV bool skipDeadTrips(const Scene &S_)
+{
+    if constexpr (skipsDeadTrips<FEAT>())
+        return !(again<FEAT>(S_).opaqueShadows & SHADOWS_ALL_TRIPS);
+    else
+        return false;
+}
+
 /* CRT:69-408.  Called by the whole wave; `active` lanes own a pixel.
  *
  * The reference traces up to three kinds of rays per pixel: the bounce loop
@@ -2846,6 +2898,15 @@ SOLR_DEV v3 launchRayTracing(const Scene &S_, bool active, int index, v3 rayO, v
         else if (phase == 1)
         {
             want = active && si.graphicsLevel >= glReflectionsAndRefractions && reflectedRays != -1;
+            /* a deferred reflection exists only behind a hit that is transparent AND reflective: in most waves no lane
+             * has one, and the trip would gather, shade and walk for nobody */
+            if (skipDeadTrips<FEAT>(S_) && ballot(want) == 0ull)
+            {
+                if (!giPass)
+                    break;
+                phase = 2; /* whose tail shades the sky for the lanes that did not hit */
+                continue;
+            }
             tO = rrO;
             tD = rrD;
             tIter = reflectedRays;
@@ -2866,10 +2927,22 @@ SOLR_DEV v3 launchRayTracing(const Scene &S_, bool active, int index, v3 rayO, v
         const bool hitLane = want && hit;
         const Scene S = again<FEAT>(S_); /* behind the walk: the gather of the hit's material, the first hit's records */
 
-        /* material of the hit (per-lane gather) */
+        /* material of the hit (per-lane gather), and its index word next to the id: once per trip, for the first hit's
+         * record below and for the shader (HitRecords).  In a trip in which no lane hit - a tile of background - nobody
+         * reads them, and the shader would change nothing: everything it writes it writes for a shading lane. */
+        constexpr bool HAND = handsOverHit<COUNT, FEAT>();
+        const bool anyHit = !skipsDeadTrips<FEAT>() || (S.opaqueShadows & SHADOWS_ALL_TRIPS) != 0 || ballot(hitLane) != 0ull;
         const int cp = hitLane ? closestPrimitive : 0;
-        const int cpMaterial = asint(primRow(S, cp, ROW_SIZE_MAT).w);
-        const MaterialHot cm = loadMaterialHot(S, cpMaterial < 0 ? 0 : cpMaterial);
+        int cpMaterial = 0;
+        HitRecords records = {};
+        if (anyHit)
+        {
+            cpMaterial = asint(primRow(S, cp, ROW_SIZE_MAT).w);
+            if (HAND)
+                records.primIndex = asint(primRow(S, cp, ROW_P1_INDEX).w);
+            records.mh = loadMaterialHot(S, cpMaterial < 0 ? 0 : cpMaterial);
+        }
+        const MaterialHot &cm = records.mh;
         float4 attributes = make_float4(0.f, 0.f, 0.f, 0.f);
         bool shadeLane = hitLane;
         int shadeIteration = tIter;
@@ -2903,7 +2976,7 @@ SOLR_DEV v3 launchRayTracing(const Scene &S_, bool active, int index, v3 rayO, v
                         pathTracingRatio = (1.f - attributes.y) * fabsf(cos_theta);
                         useGlobalIllumination = true;
                     }
-                    idX = asint(primRow(S, cp, ROW_P1_INDEX).w);
+                    idX = HAND ? records.primIndex : asint(primRow(S, cp, ROW_P1_INDEX).w);
                 }
             }
         }
@@ -2949,9 +3022,15 @@ SOLR_DEV v3 launchRayTracing(const Scene &S_, bool active, int index, v3 rayO, v
             shadeIteration = lastIteration;
         }
 
-        const v3 shaded = primitiveShader<COUNT, FEAT>(S_, shadeLane, index, si_, tO, normal, closestPrimitive,
-                                                 closestIntersection, areas, closestColor, shadeIteration,
-                                                 shadowIntensity, rBlinn, attributes, cnt);
+        /* (the trace clamps a negative material id for its own load and the shader does not, as the reference reads out of
+         * bounds: a wave in which a shading lane has one keeps the shader's own gather) */
+        records.materialId = cpMaterial;
+        records.given = HAND && ballot(shadeLane && cpMaterial < 0) == 0ull;
+        v3 shaded = V(0.f, 0.f, 0.f);
+        if (anyHit)
+            shaded = primitiveShader<COUNT, FEAT>(S_, shadeLane, index, si_, tO, normal, closestPrimitive,
+                                                  closestIntersection, areas, closestColor, shadeIteration,
+                                                  shadowIntensity, rBlinn, attributes, cnt, &records);
 
         if (phase == 0)
         {

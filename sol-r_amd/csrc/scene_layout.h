@@ -140,9 +140,12 @@ enum ShadowFacts
 {
     SHADOWS_OPAQUE = 1,     /* no primitive is transparent or a textured plane: any occluder saturates a shadow, and
                              * the order-free lists exist (rt_device.h shadowWalk, freeOrder) */
-    SHADOWS_LAMP_CUTOFF = 2 /* the walk-order list holds what it names: every inner node contains its children, every
+    SHADOWS_LAMP_CUTOFF = 2, /* the walk-order list holds what it names: every inner node contains its children, every
                              * leaf its primitives - a shadow walk in the reference's order may leave out the boxes that
                              * begin beyond the lamp (rt_device.h shadowWalk, lampCut; solr_scene.hip lampCutoffUsable) */
+    SHADOWS_ALL_TRIPS = 4   /* no fact about shadows, but the A/B switch of the trace in the word it has at hand: every trip
+                             * of the phase machine is made, those that no lane takes too (rt_device.h launchRayTracing;
+                             * VARIANT_ALL_TRIPS) */
 };
 
 /* What the host passes to the kernel. Offsets are in rows of 16 bytes from the

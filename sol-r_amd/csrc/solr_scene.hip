@@ -872,6 +872,8 @@ static SceneArgs makeScene(bool exactNodes)
     }
     if (!exactNodes && lampCutoffUsable())
         S.opaqueShadows |= SHADOWS_LAMP_CUTOFF;
+    if (g.variant == VARIANT_ALL_TRIPS)
+        S.opaqueShadows |= SHADOWS_ALL_TRIPS;
     /* the thin copies behind the lists this frame walks (set by tightListsFor: they also depend on the frame) */
     S.tightLists = 0;
     /* ... and the copies with sorted bounds behind those (VARIANT_UNSORTED_LISTS: the walks take the lists as they are) */

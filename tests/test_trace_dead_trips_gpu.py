@@ -1,0 +1,248 @@
+"""The trips of the trace that no lane takes (sol-r_amd/csrc/rt_device.h launchRayTracing): a wave
+in which no lane has a deferred reflection leaves phase 1 at its head, a trip in which every lane missed makes neither
+the material gather nor the shader call, and where the trace hands its hit's records to the shader (HitRecords: the
+kernels of spheres, cylinders and planes) the shader gathers none of its own.  Nothing of that may show: these are the
+smallest frames in which each of the skipped or shortened trips occurs next to the trips that are made, every one held
+bit for bit to the oracle as pinned (helpers.assert_frame_pinned / assert_pass_parity: ids and depth exact, RGB8 exact,
+float colour <= 1 ULP but for the counted pixels behind a mis-rounded libm result - at most two, as everywhere else), and
+the same frames with solr_hip_set_variant(16), which makes every trip."""
+import numpy as np
+import pytest
+
+from helpers import assert_frame_pinned, assert_pass_parity, gpu_frame, oracle_frame
+
+pytestmark = pytest.mark.gpu
+
+W, H = 76, 44            # 10 x 6 tiles of 8 x 8, the last column 4 pixels wide, the last row 4 pixels high
+TILE = 8
+NB_MAX_ITERATIONS = 10   # include/solr_types.h
+ALL_TRIPS = 16           # include/solr_hip.h solr_hip_set_variant
+
+
+def _copy(frame):
+    return tuple(np.array(a, copy=True) for a in frame)
+
+
+def _same_frames(a, b):
+    return (np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1], b[1]) and
+            np.array_equal(a[2], b[2]))
+
+
+def _tiles(mask):
+    """per 8 x 8 tile of a (H, W) boolean mask: (pixels of the tile, pixels of it that are set)"""
+    out = []
+    for y in range(0, mask.shape[0], TILE):
+        for x in range(0, mask.shape[1], TILE):
+            t = mask[y:y + TILE, x:x + TILE]
+            out.append((t.size, int(t.sum())))
+    return out
+
+
+def _kinds(k, ids):
+    """(glass, plain) masks of a frame from its first hits: glass = a material that is transparent AND reflective, the
+    only kind of hit that leaves a deferred reflection; plain = neither, the ray ends there"""
+    flat = k.flat_scene()
+    material_of = {int(p["index"]): int(p["materialId"]) for p in flat.primitives}
+    mats = flat.materials
+    glass_ids = [i for i, m in material_of.items() if m >= 0 and mats["transparency"][m] != 0 and mats["reflection"][m] != 0]
+    plain_ids = [i for i, m in material_of.items() if m >= 0 and mats["transparency"][m] == 0 and mats["reflection"][m] == 0]
+    return np.isin(ids[..., 0], glass_ids), np.isin(ids[..., 0], plain_ids)
+
+
+def _glass_close_up(solr, k, **info):
+    """the Cornell box from in front of its left glass sphere: the sphere covers whole tiles, its rim cuts others, and
+    most of the frame is wall"""
+    solr.scenes.cornell(k, width=W, height=H, iterations=3, glass=2, **info)
+    k.set_camera((-5000.0, 3500.0, -11500.0), look_at=(-5000.0, 3500.0, -6000.0), w=3200.0)
+
+
+def _open_room(solr, k, **info):
+    solr.scenes.cornell(k, width=W, height=H, iterations=3, room=False, **info)
+
+
+def test_no_glass_every_deferred_trip_is_the_skipped_one(solr, oracle):
+    k = solr.Kernel(engine="hip")
+    solr.scenes.cornell(k, width=W, height=H, iterations=3, glass=0)
+    try:
+        frame = gpu_frame(k)
+        print(assert_frame_pinned(k, oracle, frame, 2, "Cornell without glass"))
+        glass, _ = _kinds(k, frame[1])
+        assert not glass.any()
+    finally:
+        k.finalize()
+
+
+def test_glass_tiles_without_with_and_of_nothing_but_deferred_reflections(solr, oracle):
+    k = solr.Kernel(engine="hip")
+    _glass_close_up(solr, k)
+    try:
+        frame = gpu_frame(k)
+        print(assert_frame_pinned(k, oracle, frame, 2, "Cornell, the glass sphere close up"))
+        oids = oracle_frame(k, oracle)[1]
+        glass, plain = _kinds(k, oids)
+        of_glass = sum(1 for n, g in _tiles(glass) if g == n)
+        mixed = sum(1 for n, g in _tiles(glass) if 0 < g < n)
+        without = sum(1 for n, p in _tiles(plain) if p == n)
+        print("tiles of glass lanes only %d, with some %d, of lanes whose ray ends at its first hit %d" % (of_glass, mixed, without))
+        assert of_glass > 0 and mixed > 0 and without > 0, "the frame does not hold all three kinds of tile"
+    finally:
+        k.finalize()
+
+
+def test_glass_from_the_default_camera(solr, oracle):
+    k = solr.Kernel(engine="hip")
+    solr.scenes.cornell(k, width=W, height=H, iterations=3, glass=2)
+    try:
+        print(assert_frame_pinned(k, oracle, gpu_frame(k), 2, "Cornell with glass"))
+    finally:
+        k.finalize()
+
+
+@pytest.mark.parametrize("info", [dict(bgColor=(0.3, 0.1, 0.5, 0.2)), dict(gradientBackground=1, bgColor=(0.3, 0.5, 0.7, 0.2))],
+                         ids=["plain-background", "gradient-background"])
+def test_open_room_tiles_in_which_every_lane_misses_and_tiles_in_which_some_do(solr, oracle, info):
+    k = solr.Kernel(engine="hip")
+    _open_room(solr, k, **info)
+    try:
+        frame = gpu_frame(k)
+        print(assert_frame_pinned(k, oracle, frame, 2, "Cornell without its room, %s" % sorted(info)))
+        oids = oracle_frame(k, oracle)[1]
+        missed = _tiles(oids[..., 0] < 0)
+        all_miss = sum(1 for n, m in missed if m == n)
+        some_miss = sum(1 for n, m in missed if 0 < m < n)
+        print("tiles in which every primary ray misses %d, in which some do %d" % (all_miss, some_miss))
+        assert all_miss > 0 and some_miss > 0, "the frame does not hold both kinds of tile"
+    finally:
+        k.finalize()
+
+
+def test_the_textured_kernel_under_its_skybox(solr, oracle):
+    """the arm whose tail calls skyboxMapping: the lanes that miss take their colour from the skybox's texture"""
+    import scenes_extra as X
+    k = solr.Kernel(engine="hip")
+    X.textured(k, width=W, height=H, skybox=True)
+    k.set_camera((0.0, 500.0, -13000.0), look_at=(0.0, 6000.0, 0.0))          # over the top of the back wall
+    try:
+        frame = gpu_frame(k)
+        print(assert_frame_pinned(k, oracle, frame, 2, "textured scene under a skybox"))
+        assert (frame[1][..., 0] < 0).any() and (frame[1][..., 0] >= 0).any()
+    finally:
+        k.finalize()
+
+
+@pytest.mark.parametrize("level", ["glNoShading", "glPhong", "glPhongAndBlinn", "glReflectionsAndRefractions"])
+def test_graphics_levels(solr, oracle, level):
+    """below glReflectionsAndRefractions no lane wants phase 1 and a ray makes one trip; glNoShading returns the texel"""
+    k = solr.Kernel(engine="hip")
+    _glass_close_up(solr, k, graphicsLevel=getattr(solr, level))
+    try:
+        print(assert_frame_pinned(k, oracle, gpu_frame(k), 2, level))
+    finally:
+        k.finalize()
+
+
+def _passes(solr, oracle, k, passes):
+    """the passes one after the other, each held to the oracle over the engine's buffers of the pass before"""
+    previous = None
+    frames = []
+    for it in passes:
+        k.set_scene_info(pathTracingIteration=it)
+        frame = _copy(gpu_frame(k))
+        assert_pass_parity(k, oracle, frame, previous, what="pass %d" % it)
+        previous = (frame[0], frame[1])
+        frames.append(frame)
+    return frames
+
+
+GI_PASSES = (0, 1, 2, 3, NB_MAX_ITERATIONS, NB_MAX_ITERATIONS + 1)
+
+
+@pytest.mark.parametrize("illumination", ["aiBasic", "aiFull"])
+@pytest.mark.parametrize("glass", [0, 2], ids=["no-glass", "glass"])
+def test_gi_pass_a_dead_phase_1_still_reaches_phase_2(solr, oracle, illumination, glass):
+    """F_FULL kernel; from NB_MAX_ITERATIONS on the GI ray of phase 2 is traced (aiFull) or its sky is shaded (aiBasic)"""
+    k = solr.Kernel(engine="hip")
+    solr.scenes.cornell(k, width=W, height=H, iterations=1, glass=glass, maxPathTracingIterations=40,
+                        advancedIllumination=getattr(solr, illumination))
+    try:
+        frames = _passes(solr, oracle, k, GI_PASSES)
+        assert not np.array_equal(frames[-2][2], frames[0][2])
+    finally:
+        k.finalize()
+
+
+def test_refinement_passes_take_the_first_hit_s_index_from_the_handed_over_word(solr, oracle):
+    k = solr.Kernel(engine="hip")
+    solr.scenes.cornell(k, width=W, height=H, iterations=1)
+    try:
+        frames = _passes(solr, oracle, k, (0, 1, 2, 3))
+        assert not np.array_equal(frames[0][2], frames[3][2])
+        assert (frames[0][1][..., 0] >= 0).all()          # the closed room: every pixel has a first hit, and its index
+    finally:
+        k.finalize()
+
+
+@pytest.mark.parametrize("scene", ["molecule", "mesh"])
+def test_long_lists(solr, oracle, scene):
+    """the smallest molecule and mesh with long node lists: background tiles, kernels that get no records handed over
+    (the mesh) or get them in the three-bank instantiation (the molecule)"""
+    k = solr.Kernel(engine="hip")
+    if scene == "molecule":
+        solr.scenes.molecule(k, atoms=2500, width=W, height=H, iterations=2)
+    else:
+        solr.scenes.height_field(k, n=40, width=W, height=H)
+    try:
+        for n in range(2):
+            frame = gpu_frame(k)
+            print(assert_frame_pinned(k, oracle, frame, 2, "%s, frame %d" % (scene, n)))
+        assert len(k.flat_scene().boxes) > 1024
+        missed = _tiles(frame[1][..., 0] < 0)
+        assert any(m == n for n, m in missed) and any(0 < m < n for n, m in missed), "no background tile in the frame"
+    finally:
+        k.finalize()
+
+
+def _gi_frames(solr, k):
+    solr.scenes.cornell(k, width=W, height=H, iterations=1, maxPathTracingIterations=40, advancedIllumination=solr.aiFull)
+    out = []
+    for it in GI_PASSES:
+        k.set_scene_info(pathTracingIteration=it)
+        out.append(_copy(gpu_frame(k)))
+    return out
+
+
+@pytest.mark.parametrize("case", ["glass", "open-room", "open-room-gradient", "gi", "molecule"])
+def test_the_same_frames_with_every_trip_made(solr, case):
+    """solr_hip_set_variant(16): the same build, the trips that nobody takes made as they were"""
+    hip = solr.hip_lib()
+    got = {}
+    try:
+        for variant in (0, ALL_TRIPS):
+            hip.solr_hip_set_variant(variant)
+            k = solr.Kernel(engine="hip")
+            try:
+                if case == "glass":
+                    _glass_close_up(solr, k)
+                    frames = [_copy(gpu_frame(k)) for _ in range(2)]
+                elif case == "open-room":
+                    _open_room(solr, k)
+                    frames = [_copy(gpu_frame(k)) for _ in range(2)]
+                elif case == "open-room-gradient":
+                    _open_room(solr, k, gradientBackground=1)
+                    frames = [_copy(gpu_frame(k)) for _ in range(2)]
+                elif case == "gi":
+                    frames = _gi_frames(solr, k)
+                else:
+                    solr.scenes.molecule(k, atoms=2500, width=W, height=H, iterations=2)
+                    frames = [_copy(gpu_frame(k)) for _ in range(2)]
+                k.check(0, "render")
+                assert hip.solr_hip_get_variant() == variant
+            finally:
+                k.finalize()
+            got[variant] = frames
+    finally:
+        hip.solr_hip_set_variant(0)
+    assert len(got[0]) == len(got[ALL_TRIPS]) > 0
+    for n, (a, b) in enumerate(zip(got[0], got[ALL_TRIPS])):
+        assert _same_frames(a, b), "frame %d differs with and without the skipped trips" % n
+    assert got[0][-1][2].any()
