@@ -92,6 +92,19 @@ int solr_hip_probe_order_tiles(int n, const unsigned *cost, int flights, int ban
  * bands of that order} */
 void solr_hip_probe_last_frame(int out[6]);
 
+/* What the arena holds of a node list, read back as it is now (pending uploads flushed, the stream idle).  list: 0 the
+ * walk-order list, 1 the reference's list, 2 the eight order-free lists one behind the other.  what: 0 the node rows, 1 the
+ * thin copy (solr_scene.hip k_tightenLeaves / k_tightenInner), 2 the copy with sorted bounds and the pad record behind it
+ * (k_sortNodeBounds), 3 the leaf records (k_buildLeafRecords), 4 the start indices.  Returns the number of 16-byte rows
+ * (of ints for what = 4) written to out, 0 where the engine holds no such copy up to date, -1 with the error set on
+ * failure; out == NULL: the size alone. */
+int solr_hip_probe_list_copy(int list, int what, void *out, int capacity);
+
+/* what a walk of the resident scene would be handed for this SceneInfo (order-free lists built when they are due):
+ * out = {tightLists, sortedLists, nbBoxesFree, opaqueShadows, shortRayLists, nbBoxes (SceneArgs, scene_layout.h), the thin
+ * copies' margin, the scene's extent - both as float bits}.  Returns 0, or -1 with the error set. */
+int solr_hip_probe_walk_offer(const SceneInfo *sceneInfo, int exactNodes, int out[8]);
+
 /* vectorRefraction (VU:73-87) and vectorReflection (VU:61-64) */
 int solr_hip_probe_vectors(int n, const float *incident, const float *normals, const float *n1, const float *n2,
                            float *refracted, float *reflected);

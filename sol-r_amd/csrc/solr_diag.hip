@@ -109,6 +109,74 @@ void lastFrame(int out[6])
 {
     memcpy(out, g.lastFrame, sizeof(g.lastFrame));
 }
+
+/* solr_hip_probe_list_copy (include/solr_hip_probes.h says what `list` and `what` select): from the arena as
+ * solr_scene.hip deriveList left it */
+int listCopy(int list, int what, void *out, int capacity)
+{
+    if (!ready("solr_hip_probe_list_copy"))
+        return -1;
+    ARGCHECK(list >= 0 && list <= 2 && what >= 0 && what <= 4, "solr_hip_probe_list_copy: no such list or copy");
+    ARGCHECK(g.geometry.ptr != nullptr || g.geometryDirty, "solr_hip_probe_list_copy: no scene uploaded");
+    if (!ok())
+        return -1;
+    HIPCHECK(hipSetDevice(g.device));
+    flushGeometry();
+    if (list == 1)
+        refreshExactList();
+    quiesce();
+    if (!ok() || !g.geometry.ptr)
+        return -1;
+    const NodeList &L = list == 0 ? g.walk : (list == 1 ? g.exact : g.orderFree);
+    const unsigned nodes = (list == 2 && g.freeStale) ? 0u : L.nodes();
+    size_t at = 0, count = 0, unit = 16; /* where (bytes of the arena), how many, of which size */
+    switch (what)
+    {
+    case 0:
+        at = (size_t)L.offRows * 16, count = 2 * (size_t)nodes;
+        break;
+    case 1:
+        at = (size_t)L.offThin() * 16, count = (L.copies > 1 && L.tight) ? 2 * (size_t)nodes : 0;
+        break;
+    case 2:
+        at = (size_t)L.offSorted() * 16, count = (list == 2 && L.copies > 2 && g.sortedFree) ? 2 * (size_t)nodes + 2 : 0;
+        break;
+    case 3:
+        at = (size_t)L.offLeaf * 16, count = 4 * (size_t)nodes;
+        break;
+    default:
+        at = (size_t)L.offStart * 4, count = nodes, unit = 4;
+        break;
+    }
+    if (nodes == 0)
+        count = 0;
+    if (!out)
+        return (int)count;
+    ARGCHECK(count <= (size_t)(capacity < 0 ? 0 : capacity), "solr_hip_probe_list_copy: capacity too small");
+    ARGCHECK(at + count * unit <= g.geometry.bytes, "solr_hip_probe_list_copy: the copy lies outside the arena");
+    if (!ok())
+        return -1;
+    if (count)
+        HIPCHECK(hipMemcpy(out, (const char *)g.geometry.ptr + at, count * unit, hipMemcpyDeviceToHost));
+    return ok() ? (int)count : -1;
+}
+
+/* what residentScene hands a walk for this SceneInfo: {tightLists, sortedLists, nbBoxesFree, opaqueShadows, shortRayLists,
+ * nbBoxes, the thin copies' margin, the scene's extent (both as float bits)} */
+int walkOffer(const SceneInfo &sceneInfo, bool exactNodes, int out[8])
+{
+    SceneArgs S;
+    int features, deep;
+    hipStream_t stream;
+    if (residentScene(sceneInfo, exactNodes, &S, &features, &deep, &stream) != 0)
+        return -1;
+    const float margin = g.sceneExtent * (1.f / 1024.f), extent = g.sceneExtent;
+    out[0] = S.tightLists, out[1] = S.sortedLists, out[2] = S.nbBoxesFree, out[3] = S.opaqueShadows, out[4] = S.shortRayLists;
+    out[5] = S.nbBoxes;
+    memcpy(&out[6], &margin, 4);
+    memcpy(&out[7], &extent, 4);
+    return 0;
+}
 } // namespace solrprobe
 
 extern "C" {

@@ -29,6 +29,8 @@ long long imageSerial(long long setTo);
 int postProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, const PostProcessingBuffer *frame,
                 unsigned char *bitmapOut);
 void lastFrame(int out[6]);
+int listCopy(int list, int what, void *out, int capacity);
+int walkOffer(const SceneInfo &sceneInfo, bool exactNodes, int out[8]);
 } // namespace solrprobe
 
 /* solr_post.hip: k_orderTiles behind its launcher, as renderImpl's scheduling stage calls it */
@@ -547,6 +549,13 @@ int solr_hip_probe_ticket(long long serial, int *slot, long long *period)
 }
 
 long long solr_hip_probe_image_serial(long long setTo) { return solrprobe::imageSerial(setTo); }
+
+int solr_hip_probe_list_copy(int list, int what, void *out, int capacity) { return solrprobe::listCopy(list, what, out, capacity); }
+
+int solr_hip_probe_walk_offer(const SceneInfo *sceneInfo, int exactNodes, int out[8])
+{
+    return solrprobe::walkOffer(*sceneInfo, exactNodes != 0, out);
+}
 
 int solr_hip_probe_order_tiles(int n, const unsigned *cost, int flights, int bands, int heavyShare, const int *firstTile,
                                unsigned *order, unsigned *snapshot, unsigned *hostStats)

@@ -881,10 +881,15 @@ static SceneArgs makeScene(bool exactNodes)
     return S;
 }
 
-/* may the walks of a frame with this SceneInfo take the thin copies of the lists S names (rt_device.h tightRay)? */
+/* may the walks of a frame with this SceneInfo take the thin copies of the lists S names (rt_device.h tightRay)?  A thin
+ * leaf is its planes' rectangle CUT WITH THE BOX AS UPLOADED, and the reference never asks a hit to lie inside its leaf's
+ * box, only the ray to enter it: through a box smaller than its plane's rectangle a ray can hit the plane beside the box -
+ * the reference finds that hit, the copy does not.  So only for a list that holds what it names (walkEncloses: checked at
+ * h2d_scene and after every rotation on the device; the order-free lists exist only behind the same check of the
+ * reference's list) - the reference's builder makes no other, another host's boxes are taken at their word only after it. */
 static int tightListsFor(const SceneArgs &S, const SceneInfo &sceneInfo, bool exactNodes)
 {
-    if (exactNodes || g.variant == VARIANT_REFERENCE_LEAVES || !g.walk.tight || !sceneInfo.extendedGeometry)
+    if (exactNodes || g.variant == VARIANT_REFERENCE_LEAVES || !g.walk.tight || !g.walkEncloses || !sceneInfo.extendedGeometry)
         return 0;
     if (S.nbBoxesFree > 0 && !g.orderFree.tight)
         return 0;

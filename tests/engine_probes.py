@@ -53,8 +53,10 @@ def declare(hip):
     hip.solr_hip_probe_order_tiles.argtypes = [i, v, i, i, i, v, v, v, v]
     hip.solr_hip_probe_last_frame.argtypes = [v]
     hip.solr_hip_probe_last_frame.restype = None
+    hip.solr_hip_probe_list_copy.argtypes = [i, i, v, i]
+    hip.solr_hip_probe_walk_offer.argtypes = [v, i, v]
     for name in ("box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "vectors",
-                 "make_color", "skybox", "intersection_shader", "order_tiles"):
+                 "make_color", "skybox", "intersection_shader", "order_tiles", "list_copy", "walk_offer"):
         getattr(hip, "solr_hip_probe_" + name).restype = i
     del P
 
@@ -109,6 +111,44 @@ class Resident:
         return False
 
 
+WALK_LIST, EXACT_LIST, FREE_LISTS = 0, 1, 2                              # solr_hip_probe_list_copy: list
+NODE_ROWS, THIN_COPY, SORTED_COPY, LEAF_RECORDS, START_INDICES = 0, 1, 2, 3, 4   # ... and what
+
+
+def list_copy(hip, which, what):
+    """what the arena holds of a node list now (solr_hip_probe_list_copy): (n, 2, 4) float32 node rows, (n, 4, 4) leaf
+    records, n int32 start indices; None where the engine holds no such copy up to date"""
+    declare(hip)
+    n = _check(hip, hip.solr_hip_probe_list_copy(which, what, None, 0), "probe_list_copy (size)")
+    if n == 0:
+        return None
+    out = np.full(n if what == START_INDICES else (n, 4), -1, i32 if what == START_INDICES else f32)
+    got = _check(hip, hip.solr_hip_probe_list_copy(which, what, _p(out), n), "probe_list_copy")
+    assert got == n, (got, n)
+    return out if what == START_INDICES else out.reshape(-1, 4 if what == LEAF_RECORDS else 2, 4)
+
+
+def walk_offer(hip, si, exact=0):
+    """what a walk of the resident scene is handed for this SceneInfo (solr_hip_probe_walk_offer; the order-free lists are
+    built when they are due)"""
+    declare(hip)
+    out = np.zeros(8, i32)
+    _check(hip, hip.solr_hip_probe_walk_offer(C.byref(si), exact, _p(out)), "probe_walk_offer")
+    keys = ("tightLists", "sortedLists", "nbBoxesFree", "opaqueShadows", "shortRayLists", "nbBoxes")
+    offer = {k: int(x) for k, x in zip(keys, out[:6])}
+    offer["margin"], offer["extent"] = out[6:].view(f32)
+    return offer
+
+
+def primitive_records(hip):
+    """the resident primitive records, (n, 8, 4) float32 (solr_hip_read_primitives)"""
+    declare(hip)
+    n = _check(hip, hip.solr_hip_read_primitives(None, 0), "read_primitives (size)")
+    out = np.zeros((n, 4), f32)
+    _check(hip, hip.solr_hip_read_primitives(_p(out), n), "read_primitives")
+    return out.reshape(-1, 8, 4)
+
+
 def one_leaf(solr, prims):
     """a node list of one leaf that holds every primitive (the per-primitive probes never walk it)"""
     boxes = np.zeros(1, solr.BOX_DTYPE)
@@ -116,6 +156,28 @@ def one_leaf(solr, prims):
     boxes["nbPrimitives"], boxes["startIndex"] = len(prims), 0
     boxes["indexForNextBox"][:, 0] = 1
     return boxes
+
+
+def walk_outputs(hip, case, features=0, exact=0):
+    """a closest-hit or shadow case over the scene that is resident now (several calls may share one Resident, with
+    solr_hip_set_variant in between)"""
+    si, n = case["si"], len(case["origins"])
+    if case["name"] == "closest":
+        hit, prim = np.zeros(n, i32), np.zeros(n, i32)
+        inter, normal, areas = np.zeros((n, 3), f32), np.zeros((n, 3), f32), np.zeros((n, 3), f32)
+        used = _check(hip, hip.solr_hip_probe_closest(C.byref(si), n, _p(case["origins"]), _p(case["targets"]),
+                                                      _p(case["iteration"]), _p(case["current"]), features, exact,
+                                                      _p(hit), _p(prim), _p(inter), _p(normal), _p(areas)),
+                      "probe_closest")
+        return dict(hit=hit, primitive=prim, intersection=inter, normal=normal, areas=areas, features=used)
+    result, color = np.zeros(n, f32), np.zeros((n, 3), f32)
+    # the reference's probe (the OpenCL engine) leaves out the lamp only; the renderer's call also the primitive
+    # the point lies on (GI:829) - the cases that name it (`shaded`) are probed the renderer's way
+    nobody = case["shaded"] if "shaded" in case else np.full(n, NOBODY, i32)
+    used = _check(hip, hip.solr_hip_probe_shadow(C.byref(si), n, _p(case["lamps"]), _p(case["origins"]),
+                                                 _p(case["object_id"]), _p(nobody), _p(case["iteration"]), features,
+                                                 exact, _p(result), _p(color)), "probe_shadow")
+    return dict(result=result, color=color, features=used)
 
 
 def engine_outputs(solr, case, features=0, exact=0):
@@ -163,22 +225,7 @@ def engine_outputs(solr, case, features=0, exact=0):
         s = case["scene"]
         n = len(case["origins"])
         with Resident(solr, si, s.boxes, s.prims, s.materials, s.textures, s.lights, s.nb_lamps):
-            if name == "closest":
-                hit, prim = np.zeros(n, i32), np.zeros(n, i32)
-                inter, normal, areas = np.zeros((n, 3), f32), np.zeros((n, 3), f32), np.zeros((n, 3), f32)
-                used = _check(hip, hip.solr_hip_probe_closest(C.byref(si), n, _p(case["origins"]), _p(case["targets"]),
-                                                              _p(case["iteration"]), _p(case["current"]), features, exact,
-                                                              _p(hit), _p(prim), _p(inter), _p(normal), _p(areas)),
-                              "probe_closest")
-                return dict(hit=hit, primitive=prim, intersection=inter, normal=normal, areas=areas, features=used)
-            result, color = np.zeros(n, f32), np.zeros((n, 3), f32)
-            # the reference's probe (the OpenCL engine) leaves out the lamp only; the renderer's call also the primitive
-            # the point lies on (GI:829) - the cases that name it (`shaded`) are probed the renderer's way
-            nobody = case["shaded"] if "shaded" in case else np.full(n, NOBODY, i32)
-            used = _check(hip, hip.solr_hip_probe_shadow(C.byref(si), n, _p(case["lamps"]), _p(case["origins"]),
-                                                         _p(case["object_id"]), _p(nobody), _p(case["iteration"]), features,
-                                                         exact, _p(result), _p(color)), "probe_shadow")
-            return dict(result=result, color=color, features=used)
+            return walk_outputs(hip, case, features, exact)
     if name == "shader":
         s = case["scene"]
         n = len(case["origins"])

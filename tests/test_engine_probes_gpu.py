@@ -296,15 +296,17 @@ def test_the_probes_run_the_instantiations_the_renderer_launches(solr, probes, f
 
 
 def test_all_fifteen_probe_entry_points_are_exported(solr):
-    """(CPU) include/solr_hip_probes.h is test-only, but what it declares must be in the library: the thirteen probes of
-    the device functions and the read-back tickets, and the two of the frame's launch (the tile sort, the last frame)"""
+    """(CPU) include/solr_hip_probes.h is test-only, but what it declares must be in the library: the fifteen probes of the
+    device functions and of a frame - thirteen of the device functions and the read-back tickets, two of the frame's launch
+    (the tile sort, the last frame) - and, since, the two of the resident lists (their copies read back, what a walk is
+    offered): seventeen"""
     import re
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "solr_hip_probes.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     names = sorted(set(re.findall(r"\b(solr_hip_probe_\w+)\s*\(", text)))
-    assert len(names) == 15
+    assert len(names) == 17
     assert names == sorted("solr_hip_probe_" + n for n in (
         "box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "image_serial", "vectors",
-        "make_color", "skybox", "intersection_shader", "order_tiles", "last_frame")), names
+        "make_color", "skybox", "intersection_shader", "order_tiles", "last_frame", "list_copy", "walk_offer")), names
     hip = solr.hip_lib()
     assert all(hasattr(hip, n) for n in names), [n for n in names if not hasattr(hip, n)]
