@@ -2,7 +2,12 @@
  * engine.h - the state of the MI355X rendering engine and the helpers every part of its host side uses: what
  * solr_hip.hip (the boundary), solr_scene.hip (scene upload, the node lists; their host builders: list_builders.h), solr_launch.hip (the renderer's launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined
  * read-back), solr_rccl.hip (strips, communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
- * One Engine per device this process renders on; `g` is the engine a function works on.  gfx950 only.
+ * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
+ * NodeList (a node list of the resident scene), TileSchedule (the cost-ordered launch), Flight (a frame in flight: its
+ * stream and per-pixel buffers; Engine::flight[0] is the one of a process that renders one frame at a time), CopyLane (the
+ * device's part of the pipelined read-back) and ImageStreaming (a frame read back in bands); ImageRing - the page-locked
+ * host images of the pipelined read-back and their tickets - exists once per process (gImageRing), whatever the number of
+ * engines.  gfx950 only.
  */
 #ifndef SOLR_ENGINE_H
 #define SOLR_ENGINE_H
@@ -102,11 +107,50 @@ struct DeviceBuffer
     void *ptr = nullptr;
     size_t bytes = 0;
 };
+inline void release(DeviceBuffer &b)
+{
+    if (b.ptr)
+        (void)hipFree(b.ptr);
+    b.ptr = nullptr;
+    b.bytes = 0;
+}
 
 /* frames in flight at most (per-pixel buffer sets and streams).  Whole 1080p frames gain nothing beyond three, a
  * 1/8 strip - one round of waves, as slow as its longest - up to four; six and eight were tried (the mesh's
  * slowest strip: 0.114 ms with three, 0.089 with four, 0.12 and 0.11 with six and eight). */
 const int MAX_FLIGHTS = 4;
+/* A frame in flight (solr_hip_set_frames_in_flight): with n > 1, consecutive first-pass frames rotate over n streams and
+ * n sets of per-pixel buffers, so that the tail of one frame - a few long waves on an otherwise idle chip - overlaps the
+ * start of the next.  Engine::flight[0] is the set of a process that renders one frame at a time. */
+struct Flight
+{
+    hipStream_t stream = nullptr; /* the engine's own or the caller's (Engine::ownStream, callerStreams) */
+    DeviceBuffer pp, ids;         /* per-pixel buffers of the strip */
+    /* two RGB images, the second ("side" 1) for the time a copy still reads the first: a refinement or accumulation pass
+     * stays on the set of the pass before it, and would otherwise wait for that pass's copy (made when first needed) */
+    DeviceBuffer image[2];
+    int side = 0;           /* the image the set's frames go to */
+    int copy[2] = {-1, -1}; /* slot of the image ring whose copy reads that image, or -1 */
+    DeviceBuffer deepStack; /* F_STACK frames: the colour-stack slots beyond the LDS ones */
+    /* ambient occlusion across strips: the depths of the neighbours' rows next to this rank's strip */
+    DeviceBuffer haloAbove, haloBelow, haloSendTop, haloSendBottom;
+
+    DeviceBuffer &shown() { return image[side]; }
+    /* no copy reads an image any more (the image ring is gone): back to the first image, the second given back */
+    void forgetCopies()
+    {
+        copy[0] = copy[1] = -1;
+        side = 0;
+        solreng::release(image[1]);
+    }
+    /* every buffer given back; the stream stays */
+    void release()
+    {
+        for (DeviceBuffer *b : {&pp, &ids, &image[0], &deepStack, &haloAbove, &haloBelow, &haloSendTop, &haloSendBottom})
+            solreng::release(*b);
+        forgetCopies();
+    }
+};
 /* head of the shared segment of solr_hip_image_share; the images follow, page-aligned.  done[r][slot]: the serial of
  * the last copy of rank r into that slot that has landed; consumed: the last serial the root has handed to its host. */
 struct SharedRing
@@ -114,6 +158,73 @@ struct SharedRing
     std::atomic<long> done[64][MAX_FLIGHTS + 2];
     std::atomic<long> consumed;
     long frameBytes, imageStride;
+};
+/* The pipelined read-back (solr_hip_d2h_image_async), the process's part: a ring of page-locked host images - every
+ * in-process device copies its strip into the same image - and the tickets handed out for them.  One per process
+ * (gImageRing); what an engine adds is its CopyLane. */
+struct ImageRing
+{
+    static const int IMAGE_RING = MAX_FLIGHTS + 2; /* MAX_FLIGHTS tickets outstanding, the image on show, one spare */
+    BitmapBuffer *pinnedImage[IMAGE_RING] = {};
+    size_t pinnedBytes = 0;
+    /* a ticket is (serial mod TICKET_PERIOD) * IMAGE_RING + slot - a positive int whatever the age of the process (the
+     * serial itself is 64 bits, counts every ticket this process ever handed out and is never reset or reduced: 0.04 ms
+     * per frame of an eight-rank job is 2^31 / 6 tickets in four hours) - and the serial tells a ticket whose slot has
+     * been handed out again (or whose ring was re-allocated for a larger frame, or shared / unshared since) from a live
+     * one: two tickets of one process are alike only 357 million tickets apart */
+    static const long TICKET_PERIOD = ((long)0x7fffffff / IMAGE_RING / IMAGE_RING - 1) * IMAGE_RING;
+    static int ticketOf(long serial, int slot) { return (int)((serial % TICKET_PERIOD) * IMAGE_RING + slot); }
+    long imageSerial = 0;
+    long slotSerial[IMAGE_RING] = {};
+    /* A ring the ranks of a job share (solr_hip_image_share) is addressed by a sequence number of its own, counted
+     * from the share on every rank alike (the ranks run the same program): it picks the slot and is what `done` /
+     * `consumed` of the segment's head hold; the ticket's generation stays this process's own serial */
+    long shareSeq = 0;
+    long slotShareSeq[IMAGE_RING] = {};
+    long lastWaitedSeq = 0;               /* sequence number of the newest ticket solr_hip_image_wait was asked for */
+    long sharePublished[IMAGE_RING] = {}; /* the sequence number this rank has reported as landed, per slot */
+    /* the ring in memory that several processes share (solr_hip_image_share): every rank's strip lands, over that
+     * rank's own PCIe link, at its rows of ONE host image */
+    struct SharedRing *sharedRing = nullptr;
+    size_t sharedBytes = 0;
+    std::string sharedName;
+    int shareRank = 0, shareWorld = 0;
+    bool slotOfStrips[IMAGE_RING] = {}; /* that slot's ticket was for every rank's strip (not the root's gathered frame) */
+    long lastHandedOut = 0;             /* root: the serial of the image its last solr_hip_image_wait returned */
+    bool copyOnRenderStream = false;    /* solr_hip_set_copy_route */
+    /* the images given back, the shared segment left: outstanding tickets are void (their serial no longer matches).
+     * Nothing to do, and harmless, when there is no ring (solr_image_ring.hip) */
+    void release();
+};
+extern ImageRing gImageRing; /* (solr_image_ring.hip) */
+/* ... and an engine's part: a copy stream, and per slot of the ring the event that says this device's copy has landed */
+struct CopyLane
+{
+    hipStream_t stream = nullptr;
+    hipEvent_t frameRendered = nullptr;
+    hipEvent_t imageDone[ImageRing::IMAGE_RING] = {};
+    void release(); /* waits for the stream first (solr_image_ring.hip) */
+};
+/* ImageStreaming (renderer.h): the next frame counts its tiles if it can (solr_hip_stream_next_image), and
+ * solr_hip_d2h_streamed_image then sends its image off band by band as the bands' words come */
+struct ImageStreaming
+{
+    int next = 0;                  /* 0 no, 1 the image, 2 the image and the primitive ids */
+    bool ids = false;              /* the frame rendered last stored its ids for the bands too */
+    bool valid = false;            /* the frame rendered last counted its tiles: serial, image and bands below */
+    const void *bitmap = nullptr;
+    unsigned serial = 0;           /* streamed frames since the counters were zeroed */
+    long key[3] = {0, 0, 0};       /* tilesX, tile rows (+ 100000 x the number of bands), image width the counters belong to */
+    DeviceBuffer counters;         /* rowDone | bandDone | the StreamPlan */
+    StreamPlan plan = {};          /* host image of the plan */
+    int bands = 0;
+    unsigned *hostWords = nullptr; /* StreamPlan::hostWord, the host's address */
+    hipEvent_t rendered = nullptr; /* behind the kernel of the streamed frame rendered last */
+    long delivered = 0;            /* images that left in bands */
+    int support = -1;              /* 1 / 0; -1: not asked yet (SOLR_HIP_NO_IMAGE_STREAMING) */
+    /* at finalize only: a ring that is re-made for a larger frame must leave the counters alone - the frame that is being
+     * read back may still be counting into them (solr_image_ring.hip) */
+    void release();
 };
 /* Frames between two sorts of the tiles by cost (k_orderTiles: one workgroup, 46 us for the 32 400 tiles of a 1080p frame, on the
  * frame's own stream: 2.9 us of every Cornell frame at sixteen, which it was until round 6; 64: delivered frames 0.2442 ->
@@ -218,8 +329,6 @@ struct Engine
 {
     bool initialized = false;
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
     int errorCode = 0;
     std::string errorText;
 
@@ -273,22 +382,20 @@ struct Engine
     int nested = 1;
     long nbRandoms = 0;
 
-    /* per-pixel buffers of the strip */
-    DeviceBuffer pp, ids, bitmap, counters, tileClock;
-    /* ambient occlusion across strips: the depths of the neighbours' rows next to this rank's strip */
-    DeviceBuffer haloAbove[MAX_FLIGHTS], haloBelow[MAX_FLIGHTS], haloSendTop[MAX_FLIGHTS], haloSendBottom[MAX_FLIGHTS]; /* per frame in flight */
+    DeviceBuffer counters, tileClock;
+    /* ambient occlusion across strips: the depths of the neighbours' rows a host hands over itself (the ones traded over
+     * RCCL: Flight) */
     DeviceBuffer haloGivenAbove, haloGivenBelow; /* solr_hip_set_depth_halo */
     int haloSuppliedAbove = 0, haloSuppliedBelow = 0; /* rows handed over by solr_hip_set_depth_halo (0: none) */
     float randomsReach = 0.f;                          /* max |randoms[i]|, i < 356: what the 256 taps can read */
     int haloWanted = -1; /* rows beyond a strip the last frame's post-processing reached (0: none; -1: no frame here) */
-    /* Frames in flight (solr_hip_set_frames_in_flight): with n > 1, consecutive first-pass frames rotate
-     * over n streams and n sets of per-pixel buffers, so that the tail of one frame - a few long waves
-     * on an otherwise idle chip - overlaps the start of the next.  Set 0 is the members above. */
-    int flights = 1;
-    hipStream_t extraStream[MAX_FLIGHTS - 1] = {}; /* streams of sets 1 .. MAX_FLIGHTS - 1 */
-    bool callerStreams = false; /* the streams belong to the caller (solr_hip_set_flight_streams) */
-    DeviceBuffer ppX[MAX_FLIGHTS - 1], idsX[MAX_FLIGHTS - 1], bitmapX[MAX_FLIGHTS - 1];
-    int current = 0;           /* set / stream of the last render */
+    /* the frames in flight: their streams and per-pixel buffers.  flight[0]'s stream is also the one uploads and list
+     * kernels run on (sceneStream) */
+    Flight flight[MAX_FLIGHTS];
+    int flights = 1;            /* how many were asked for (solr_hip_set_frames_in_flight; in use: activeFlights) */
+    bool ownStream = false;     /* flight[0]'s stream is the engine's own (else the caller's: solr_hip_set_stream) */
+    bool callerStreams = false; /* the streams of the other flights belong to the caller (solr_hip_set_flight_streams) */
+    int current = 0;            /* flight of the last render */
     unsigned frameSerial = 0;
     TileSchedule sched;
     unsigned lastSerial = 0;
@@ -307,69 +414,16 @@ struct Engine
     int timedLaunches = 0;
     std::vector<float> kernelSamples, intervalSamples; /* per timed launch: its duration; end-to-end gap to the one before */
 
-    /* pipelined read-back (solr_hip_d2h_image_async): a ring of page-locked host images, a copy stream, and per
-     * slot the event that says its copy has landed */
-    static const int IMAGE_RING = MAX_FLIGHTS + 2; /* MAX_FLIGHTS tickets outstanding, the image on show, one spare */
-    hipStream_t copyStream = nullptr;
-    BitmapBuffer *pinnedImage[IMAGE_RING] = {};
-    size_t pinnedBytes = 0;
-    hipEvent_t imageDone[IMAGE_RING] = {};
-    hipEvent_t frameRendered = nullptr;
-    /* a ticket is (serial mod TICKET_PERIOD) * IMAGE_RING + slot - a positive int whatever the age of the process (the
-     * serial itself is 64 bits, counts every ticket this process ever handed out and is never reset or reduced: 0.04 ms
-     * per frame of an eight-rank job is 2^31 / 6 tickets in four hours) - and the serial tells a ticket whose slot has
-     * been handed out again (or whose ring was re-allocated for a larger frame, or shared / unshared since) from a live
-     * one: two tickets of one process are alike only 357 million tickets apart */
-    static const long TICKET_PERIOD = ((long)0x7fffffff / IMAGE_RING / IMAGE_RING - 1) * IMAGE_RING;
-    static int ticketOf(long serial, int slot) { return (int)((serial % TICKET_PERIOD) * IMAGE_RING + slot); }
-    long imageSerial = 0;
-    long slotSerial[IMAGE_RING] = {};
-    /* A ring the ranks of a job share (solr_hip_image_share) is addressed by a sequence number of its own, counted
-     * from the share on every rank alike (the ranks run the same program): it picks the slot and is what `done` /
-     * `consumed` of the segment's head hold; the ticket's generation stays this process's own serial */
-    long shareSeq = 0;
-    long slotShareSeq[IMAGE_RING] = {};
-    long lastWaitedSeq = 0;               /* sequence number of the newest ticket solr_hip_image_wait was asked for */
-    long sharePublished[IMAGE_RING] = {}; /* the sequence number this rank has reported as landed, per slot */
-    /* the ring in memory that several processes share (solr_hip_image_share): every rank's strip lands, over that
-     * rank's own PCIe link, at its rows of ONE host image */
-    struct SharedRing *sharedRing = nullptr;
-    size_t sharedBytes = 0;
-    std::string sharedName;
-    int shareRank = 0, shareWorld = 0;
-    bool slotOfStrips[IMAGE_RING] = {}; /* that slot's ticket was for every rank's strip (not the root's gathered frame) */
-    long lastHandedOut = 0;             /* root: the serial of the image its last solr_hip_image_wait returned */
-    bool copyOnRenderStream = false;    /* solr_hip_set_copy_route */
+    CopyLane copyLane;        /* this device's part of the pipelined read-back (the ring of host images: gImageRing) */
+    ImageStreaming streaming; /* the read-back of a frame taken one at a time, in bands */
     /* the reciprocal of tilesX that was verified for a frame geometry (renderImpl) */
     int tileCheckedX = 0, tileCheckedTiles = 0, tileCheckedShift = 0;
     unsigned tileCheckedMagic = 0;
-    /* every buffer set has a second RGB image ("side") for the time a copy still reads the first: a refinement or
-     * accumulation pass stays on the set of the pass before it, and would otherwise wait for that pass's copy */
-    DeviceBuffer bitmapAlt[MAX_FLIGHTS];
-    DeviceBuffer deepStack[MAX_FLIGHTS]; /* F_STACK frames: the colour-stack slots beyond the LDS ones, per buffer set */
-    int bitmapSide[MAX_FLIGHTS] = {0, 0, 0, 0};
-    int flightCopy[MAX_FLIGHTS][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}}; /* slot whose copy reads that image, or -1 */
-
-    /* ImageStreaming (renderer.h): the next frame counts its tiles if it can (solr_hip_stream_next_image), and
-     * solr_hip_d2h_streamed_image then sends its image off band by band as the bands' words come */
-    int streamNext = 0;                  /* 0 no, 1 the image, 2 the image and the primitive ids */
-    bool streamedIds = false;            /* the frame rendered last stored its ids for the bands too */
-    bool streamedValid = false;          /* the frame rendered last counted its tiles: serial, image and bands below */
-    const void *streamedBitmap = nullptr;
-    unsigned streamSerial = 0;           /* streamed frames since the counters were zeroed */
-    long streamKey[3] = {0, 0, 0};       /* tilesX, tile rows (+ 100000 x the number of bands), image width the counters belong to */
-    DeviceBuffer streamCounters;         /* rowDone | bandDone | the StreamPlan */
-    StreamPlan streamPlan = {};          /* host image of the plan */
-    int streamBands = 0;
-    unsigned *streamHostWords = nullptr; /* StreamPlan::hostWord, the host's address */
-    hipEvent_t streamRendered = nullptr; /* behind the kernel of the streamed frame rendered last */
-    long streamedDelivered = 0;          /* images that left in bands */
-    int lastMask = -1;                   /* features of the lean row the frame before took (-1: another kernel, or none yet) */
+    int lastMask = -1;                  /* features of the lean row the frame before took (-1: another kernel, or none yet) */
     /* what the frame rendered last launched (solr_hip_probe_last_frame): its row of solrrows::ROWS (-1: none), the features of
      * its instantiation with F_DEEP / F_STACK / F_STREAM, streamed (1 / 0) and in how many bands, cost-ordered (1 / 0) and
      * the bands of that order */
     int lastFrame[6] = {-1, -1, 0, 0, 0, 0};
-    int streamSupport = -1;              /* 1 / 0; -1: not asked yet (SOLR_HIP_NO_IMAGE_STREAMING) */
 
     /* device-side rotation (solr_hip_rotate_primitives): what to refit, in which order */
     DeviceBuffer movable, refitPlan;
@@ -431,25 +485,23 @@ inline int activeFlights()
     if (g.flights < 2 || !(g.ownStream || g.callerStreams))
         return 1;
     int n = 1;
-    while (n < g.flights && n < MAX_FLIGHTS && g.extraStream[n - 1])
+    while (n < g.flights && n < MAX_FLIGHTS && g.flight[n].stream)
         ++n;
     return n;
 }
 inline bool twoFlights() { return activeFlights() > 1; }
-inline hipStream_t flightStream(int f) { return f ? g.extraStream[f - 1] : g.stream; }
-inline DeviceBuffer &flightPp(int f) { return f ? g.ppX[f - 1] : g.pp; }
-inline DeviceBuffer &flightIds(int f) { return f ? g.idsX[f - 1] : g.ids; }
-inline DeviceBuffer &flightBitmap(int f) { return g.bitmapSide[f] ? g.bitmapAlt[f] : (f ? g.bitmapX[f - 1] : g.bitmap); }
+/* the stream uploads, list kernels and everything else that is not a frame run on */
+inline hipStream_t sceneStream() { return g.flight[0].stream; }
 /* nothing may touch scene or frame buffers while a frame is still in flight on the other stream */
 inline void quiesce()
 {
-    for (hipStream_t extra : g.extraStream)
-        if (extra)
-            (void)hipStreamSynchronize(extra);
-    if (g.stream)
-        (void)hipStreamSynchronize(g.stream);
-    if (g.copyStream)
-        (void)hipStreamSynchronize(g.copyStream);
+    for (int f = 1; f < MAX_FLIGHTS; ++f)
+        if (g.flight[f].stream)
+            (void)hipStreamSynchronize(g.flight[f].stream);
+    if (g.flight[0].stream)
+        (void)hipStreamSynchronize(g.flight[0].stream);
+    if (g.copyLane.stream)
+        (void)hipStreamSynchronize(g.copyLane.stream);
 }
 
 inline void setError(int code, const char *what, const char *file, int line)
@@ -501,14 +553,6 @@ inline bool ready(const char *who)
     return true;
 }
 
-inline void release(DeviceBuffer &b)
-{
-    if (b.ptr)
-        (void)hipFree(b.ptr);
-    b.ptr = nullptr;
-    b.bytes = 0;
-}
-
 /* grow-only device allocation */
 inline void reserve(DeviceBuffer &b, size_t bytes)
 {
@@ -529,8 +573,8 @@ void upload(DeviceBuffer &b, const std::vector<T> &host)
     if (ok() && !host.empty())
     {
         /* pageable source: the copy is complete for the caller when this returns */
-        HIPCHECK(hipMemcpyAsync(b.ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, g.stream));
-        HIPCHECK(hipStreamSynchronize(g.stream));
+        HIPCHECK(hipMemcpyAsync(b.ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, sceneStream()));
+        HIPCHECK(hipStreamSynchronize(sceneStream()));
     }
 }
 
@@ -570,8 +614,7 @@ void collectEvents();
 void d2hBitmapOne(const SceneInfo &sceneInfo, BitmapBuffer *bitmap, PrimitiveXYIdBuffer *primitivesXYIds, bool wait);
 void d2hBitmapWait();
 /* solr_image_ring.hip: the ring of page-locked host images behind solr_hip_d2h_image_async */
-void releaseImageRing();
-void releaseImageStreaming();
+void releaseCopies(); /* the current engine's copy lane, and what its flights know of copies (engine 0: before gImageRing.release()) */
 bool imageStreamingCuts(int tileRows, int firstRow[SOLR_STREAM_BANDS_MAX + 1], int *bands, bool withIds);
 bool armImageStreaming(FrameArgs &F, int tileRows, hipStream_t stream, bool withIds);
 void markStreamedFrame(hipStream_t stream);
@@ -596,7 +639,7 @@ struct HaloDebt
     ~HaloDebt()
     {
         if (owed)
-            exchangeDepthHalo(g.current, flightStream(g.current), nullptr, width, 0, 0, frameRows, wanted, nullptr);
+            exchangeDepthHalo(g.current, g.flight[g.current].stream, nullptr, width, 0, 0, frameRows, wanted, nullptr);
     }
 };
 /* solr_launch.hip: the neighbourhood post-processing of a frame (also what the test-only solr_hip_probe_postprocess runs) */

@@ -56,7 +56,7 @@ int residentScene(const SceneInfo &sceneInfo, bool exactNodes, SceneArgs *S, int
         return -1;
     *features = neededFeatures(sceneInfo, false);
     *deepList = deepNodeList(*S);
-    *stream = flightStream(0);
+    *stream = g.flight[0].stream;
     return 0;
 }
 void fail(int code, const char *what) { setError(code, what, __FILE__, __LINE__); }
@@ -83,10 +83,10 @@ int postProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, co
     if (!ok())
         return -1;
     const int flight = g.current;
-    const hipStream_t stream = flightStream(flight);
+    const hipStream_t stream = g.flight[flight].stream;
     const size_t pixels = (size_t)g.width * g.height;
-    HIPCHECK(hipMemcpyAsync(flightPp(flight).ptr, frame, pixels * sizeof(PostProcessingBuffer), hipMemcpyHostToDevice, stream));
-    unsigned char *bitmap = (unsigned char *)flightBitmap(flight).ptr;
+    HIPCHECK(hipMemcpyAsync(g.flight[flight].pp.ptr, frame, pixels * sizeof(PostProcessingBuffer), hipMemcpyHostToDevice, stream));
+    unsigned char *bitmap = (unsigned char *)g.flight[flight].shown().ptr;
     const bool neighbourhood = (ppInfo.type == ppe_ambientOcclusion || ppInfo.type == ppe_depthOfField ||
                                 ppInfo.type == ppe_radiosity || ppInfo.type == ppe_filter || ppInfo.type == ppe_cartoon);
     if (neighbourhood)
@@ -96,7 +96,7 @@ int postProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, co
     }
     else
     {
-        solrpost::defaultConversion(stream, sceneInfo, (int)pixels, (const PixelRecord *)flightPp(flight).ptr, bitmap);
+        solrpost::defaultConversion(stream, sceneInfo, (int)pixels, (const PixelRecord *)g.flight[flight].pp.ptr, bitmap);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipMemcpyAsync(bitmapOut, bitmap, pixels * SOLR_COLOR_DEPTH, hipMemcpyDeviceToHost, stream));
@@ -206,7 +206,7 @@ static int recordFrame(const SceneInfo *sceneInfo, const vec4i *objects, const P
         return -1;
     renderImpl(*sceneInfo, *objects, *postProcessingInfo, origin, direction, angles, false, nullptr);
     g.recordNext = false;
-    HIPCHECK(hipStreamSynchronize(flightStream(g.current)));
+    HIPCHECK(hipStreamSynchronize(g.flight[g.current].stream));
     if (!ok() || !g.recorded)
     {
         if (ok())
@@ -236,7 +236,7 @@ static int replayRecords(unsigned grid, size_t ldsBytes, int repeats, double ms[
     HIPCHECK(hipEventCreate(&e1));
     if (!ok())
         return -1;
-    const hipStream_t stream = flightStream(g.current);
+    const hipStream_t stream = g.flight[g.current].stream;
     unsigned *visits = (unsigned *)g.walkVisits.ptr;
     unsigned *skipped = visits + (size_t)grid * WAVE;
     double sum = 0.0, best = 1.0e30;
@@ -443,7 +443,7 @@ int solr_hip_get_frames_in_flight(void)
 
 void *solr_hip_flight_stream(int flight)
 {
-    return (flight >= 0 && flight < MAX_FLIGHTS) ? (void *)flightStream(flight) : nullptr;
+    return (flight >= 0 && flight < MAX_FLIGHTS) ? (void *)g.flight[flight].stream : nullptr;
 }
 
 int solr_hip_next_flight(void)
@@ -489,8 +489,8 @@ int solr_hip_tile_clocks(unsigned long long *clocks, int capacityTiles)
 
 double solr_hip_kernel_time(int *nbLaunches, int reset)
 {
-    if (g.initialized && g.stream)
-        (void)hipStreamSynchronize(g.stream);
+    if (g.initialized && g.flight[0].stream)
+        (void)hipStreamSynchronize(g.flight[0].stream);
     collectEvents();
     double ms = g.timedMs;
     if (nbLaunches)
@@ -511,8 +511,8 @@ double solr_hip_kernel_time(int *nbLaunches, int reset)
  * error bar of a short timed region.  Returns the number of samples written (at most `capacity`). */
 int solr_hip_timing_samples(float *kernelMs, float *intervalMs, int capacity)
 {
-    if (g.initialized && g.stream)
-        (void)hipStreamSynchronize(g.stream);
+    if (g.initialized && g.flight[0].stream)
+        (void)hipStreamSynchronize(g.flight[0].stream);
     collectEvents();
     const int n = std::min((int)g.kernelSamples.size(), std::max(capacity, 0));
     for (int i = 0; i < n; ++i)
@@ -553,11 +553,9 @@ void solr_hip_memory_usage(unsigned long long bytes[4])
     bytes[0] = g.geometry.bytes + g.lamps.bytes + g.movable.bytes + g.refitPlan.bytes;
     bytes[1] = g.materials.bytes;
     bytes[2] = g.textures.bytes;
-    bytes[3] = g.pp.bytes + g.ids.bytes + g.bitmap.bytes + g.randoms.bytes;
-    for (int f = 0; f < MAX_FLIGHTS - 1; ++f)
-        bytes[3] += g.ppX[f].bytes + g.idsX[f].bytes + g.bitmapX[f].bytes;
-    for (int f = 0; f < MAX_FLIGHTS; ++f)
-        bytes[3] += g.deepStack[f].bytes;
+    bytes[3] = g.randoms.bytes;
+    for (const Flight &set : g.flight) /* (a set's second image and its halo rows are not counted) */
+        bytes[3] += set.pp.bytes + set.ids.bytes + set.image[0].bytes + set.deepStack.bytes;
 }
 
 

@@ -102,11 +102,11 @@ void solr_hip_set_device(int device)
 
 void dropExtraStreams()
 {
-    for (hipStream_t &extra : g.extraStream)
+    for (int f = 1; f < MAX_FLIGHTS; ++f)
     {
-        if (extra && !g.callerStreams)
-            (void)hipStreamDestroy(extra);
-        extra = nullptr;
+        if (g.flight[f].stream && !g.callerStreams)
+            (void)hipStreamDestroy(g.flight[f].stream);
+        g.flight[f].stream = nullptr;
     }
     g.callerStreams = false;
 }
@@ -117,13 +117,12 @@ void solr_hip_set_flight_streams(void *const *streams, int n)
     g.current = 0;
     if (!streams || n < 1 || !streams[0])
         return;
-    if (g.ownStream && g.stream)
-        (void)hipStreamDestroy(g.stream);
+    if (g.ownStream && g.flight[0].stream)
+        (void)hipStreamDestroy(g.flight[0].stream);
     dropExtraStreams();
     g.ownStream = false;
-    g.stream = (hipStream_t)streams[0];
-    for (int f = 1; f < n && f < MAX_FLIGHTS; ++f)
-        g.extraStream[f - 1] = (hipStream_t)streams[f];
+    for (int f = 0; f < n && f < MAX_FLIGHTS; ++f)
+        g.flight[f].stream = (hipStream_t)streams[f];
     g.callerStreams = n > 1;
     if (g.initialized && g.width > 0)
         allocateFrame();
@@ -135,16 +134,17 @@ void solr_hip_set_stream(void *stream)
     g.current = 0; /* a caller's stream is the only stream: one frame in flight */
     if (g.callerStreams)
         dropExtraStreams();
-    if (g.ownStream && g.stream)
+    hipStream_t &mine = g.flight[0].stream;
+    if (g.ownStream && mine)
     {
-        (void)hipStreamSynchronize(g.stream);
-        (void)hipStreamDestroy(g.stream);
+        (void)hipStreamSynchronize(mine);
+        (void)hipStreamDestroy(mine);
         g.ownStream = false;
     }
-    g.stream = (hipStream_t)stream;
-    if (!g.stream && g.initialized)
+    mine = (hipStream_t)stream;
+    if (!mine && g.initialized)
     {
-        HIPCHECK(hipStreamCreate(&g.stream));
+        HIPCHECK(hipStreamCreate(&mine));
         g.ownStream = ok();
     }
 }
@@ -153,10 +153,10 @@ static void synchronizeOne()
 {
     if (!ready("solr_hip_synchronize"))
         return;
-    HIPCHECK(hipStreamSynchronize(g.stream));
-    for (hipStream_t extra : g.extraStream)
-        if (extra)
-            HIPCHECK(hipStreamSynchronize(extra));
+    HIPCHECK(hipStreamSynchronize(g.flight[0].stream));
+    for (int f = 1; f < MAX_FLIGHTS; ++f)
+        if (g.flight[f].stream)
+            HIPCHECK(hipStreamSynchronize(g.flight[f].stream));
 }
 
 void solr_hip_set_strip(int firstRow, int nbRows)
@@ -178,15 +178,15 @@ void solr_hip_set_strip(int firstRow, int nbRows)
 
 void *solr_hip_device_bitmap(void)
 {
-    return g.boundBitmap ? g.boundBitmap : flightBitmap(g.current).ptr;
+    return g.boundBitmap ? g.boundBitmap : g.flight[g.current].shown().ptr;
 }
 void *solr_hip_device_primitive_ids(void)
 {
-    return flightIds(g.current).ptr;
+    return g.flight[g.current].ids.ptr;
 }
 void *solr_hip_device_postprocessing(void)
 {
-    return flightPp(g.current).ptr;
+    return g.flight[g.current].pp.ptr;
 }
 /* the strip this process renders now (solr_hip_set_strip, solr_hip_balance_strips): rows [*firstRow, *firstRow +
  * *nbRows) of the frame; the full frame reads as (0, height of the last frame or 0 before one) */
@@ -220,16 +220,16 @@ static void initializeOne(const SceneInfo &sceneInfo)
     if (!ok())
         return;
     HIPCHECK(hipSetDevice(g.device));
-    if (!g.stream)
+    if (!g.flight[0].stream)
     {
-        HIPCHECK(hipStreamCreate(&g.stream));
+        HIPCHECK(hipStreamCreate(&g.flight[0].stream));
         g.ownStream = ok();
         /* the other streams right away: streams are dealt to the hardware queues in creation order, and
          * streams that share a hardware queue do not overlap (measured: created after a framework had
          * made its pool of 32, both engine streams sat on one queue and frames in flight gained nothing) */
         for (int f = 1; f < MAX_FLIGHTS && ok(); ++f)
-            if (!g.extraStream[f - 1])
-                HIPCHECK(hipStreamCreate(&g.extraStream[f - 1]));
+            if (!g.flight[f].stream)
+                HIPCHECK(hipStreamCreate(&g.flight[f].stream));
     }
     g.initialized = ok();
     g.width = sceneInfo.size.x;
@@ -243,43 +243,30 @@ static void finalizeOne()
     if (!g.initialized)
         return;
     (void)hipSetDevice(g.device);
-    if (g.stream)
-        (void)hipStreamSynchronize(g.stream);
-    for (hipStream_t extra : g.extraStream)
-        if (extra)
-            (void)hipStreamSynchronize(extra);
+    for (const Flight &flight : g.flight)
+        if (flight.stream)
+            (void)hipStreamSynchronize(flight.stream);
     collectEvents();
-    DeviceBuffer *all[] = {&g.geometry, &g.materials, &g.textures, &g.randoms, &g.lamps,
-                           &g.pp,       &g.ids,       &g.bitmap,   &g.counters, &g.tileClock,
-                           &g.movable,  &g.refitPlan, &g.enclosesFlag,
-                           &g.walkRecords, &g.walkVisits};
-    for (DeviceBuffer *b : all)
-        release(*b);
-    for (int f = 0; f < MAX_FLIGHTS; ++f)
-    {
-        release(g.deepStack[f]);
-        release(g.haloAbove[f]);
-        release(g.haloBelow[f]);
-        release(g.haloSendTop[f]);
-        release(g.haloSendBottom[f]);
-    }
-    release(g.haloGivenAbove);
-    release(g.haloGivenBelow);
-    g.haloSuppliedAbove = g.haloSuppliedBelow = 0;
-    for (int f = 0; f < MAX_FLIGHTS - 1; ++f)
-    {
-        release(g.ppX[f]);
-        release(g.idsX[f]);
-        release(g.bitmapX[f]);
-    }
+    /* the read-back first - the copy stream is waited for before an image goes (the ring of host images is the process's:
+     * it goes with engine 0, and stays when a later engine goes alone) - then the frames' buffers, the streams but
+     * flight 0's, streamed frames, the launch order */
+    releaseCopies();
+    if (&g == &gFirst)
+        gImageRing.release();
+    for (Flight &flight : g.flight)
+        flight.release();
     dropExtraStreams();
-    releaseImageRing();
-    releaseImageStreaming();
+    g.streaming.release();
     g.sched.release();
     g.current = 0;
-    if (g.ownStream && g.stream)
-        (void)hipStreamDestroy(g.stream);
-    g.stream = nullptr;
+    /* the scene */
+    for (DeviceBuffer *b : {&g.geometry, &g.materials, &g.textures, &g.randoms, &g.lamps, &g.counters, &g.tileClock, &g.movable,
+                            &g.refitPlan, &g.enclosesFlag, &g.walkRecords, &g.walkVisits, &g.haloGivenAbove, &g.haloGivenBelow})
+        release(*b);
+    g.haloSuppliedAbove = g.haloSuppliedBelow = 0;
+    if (g.ownStream && g.flight[0].stream)
+        (void)hipStreamDestroy(g.flight[0].stream);
+    g.flight[0].stream = nullptr;
     g.ownStream = false;
     g.initialized = false;
     g.refitReady = false;

@@ -22,75 +22,83 @@ using namespace solreng;
 
 namespace solreng
 {
-void releaseImageRing()
+ImageRing gImageRing;
+
+void ImageRing::release()
 {
-    if (g.copyStream)
-        (void)hipStreamSynchronize(g.copyStream);
-    for (int i = 0; i < Engine::IMAGE_RING; ++i)
+    for (int i = 0; i < IMAGE_RING; ++i)
     {
-        if (g.pinnedImage[i] && !g.sharedRing)
-            (void)hipHostFree(g.pinnedImage[i]);
-        g.pinnedImage[i] = nullptr;
-        if (g.imageDone[i])
-            (void)hipEventDestroy(g.imageDone[i]);
-        g.imageDone[i] = nullptr;
+        if (pinnedImage[i] && !sharedRing)
+            (void)hipHostFree(pinnedImage[i]);
+        pinnedImage[i] = nullptr;
     }
-    if (g.frameRendered)
-        (void)hipEventDestroy(g.frameRendered);
-    g.frameRendered = nullptr;
-    if (g.copyStream)
-        (void)hipStreamDestroy(g.copyStream);
-    g.copyStream = nullptr;
-    g.pinnedBytes = 0;
-    for (long &serial : g.slotSerial)
+    pinnedBytes = 0;
+    for (long &serial : slotSerial)
         serial = -1;
-    if (g.sharedRing)
+    if (sharedRing)
     {
-        (void)hipHostUnregister(g.sharedRing);
-        (void)munmap(g.sharedRing, g.sharedBytes);
-        if (g.shareRank == 0 && !g.sharedName.empty())
-            (void)shm_unlink(g.sharedName.c_str());
-        g.sharedName.clear();
-        g.sharedRing = nullptr;
-        g.sharedBytes = 0;
-    }
-    for (int f = 0; f < MAX_FLIGHTS; ++f)
-    {
-        g.flightCopy[f][0] = g.flightCopy[f][1] = -1;
-        g.bitmapSide[f] = 0;
-        release(g.bitmapAlt[f]);
+        (void)hipHostUnregister(sharedRing);
+        (void)munmap(sharedRing, sharedBytes);
+        if (shareRank == 0 && !sharedName.empty())
+            (void)shm_unlink(sharedName.c_str());
+        sharedName.clear();
+        sharedRing = nullptr;
+        sharedBytes = 0;
     }
 }
 
-/* (at finalize only: a ring that is re-made for a larger frame must leave the counters alone - the frame that is being
- * read back may still be counting into them) */
-void releaseImageStreaming()
+void CopyLane::release()
 {
-    if (g.streamRendered)
-        (void)hipEventDestroy(g.streamRendered);
-    g.streamRendered = nullptr;
-    if (g.streamHostWords)
-        (void)hipHostFree(g.streamHostWords);
-    g.streamHostWords = nullptr;
-    release(g.streamCounters);
-    g.streamPlan = StreamPlan();
-    g.streamBands = 0;
-    g.streamSerial = 0;
-    g.streamKey[0] = g.streamKey[1] = g.streamKey[2] = 0;
-    g.streamedValid = false;
-    g.streamSupport = -1;
+    if (stream)
+        (void)hipStreamSynchronize(stream);
+    for (hipEvent_t &done : imageDone)
+    {
+        if (done)
+            (void)hipEventDestroy(done);
+        done = nullptr;
+    }
+    if (frameRendered)
+        (void)hipEventDestroy(frameRendered);
+    frameRendered = nullptr;
+    if (stream)
+        (void)hipStreamDestroy(stream);
+    stream = nullptr;
+}
+
+void releaseCopies()
+{
+    g.copyLane.release();
+    for (Flight &flight : g.flight)
+        flight.forgetCopies();
+}
+
+void ImageStreaming::release()
+{
+    if (rendered)
+        (void)hipEventDestroy(rendered);
+    rendered = nullptr;
+    if (hostWords)
+        (void)hipHostFree(hostWords);
+    hostWords = nullptr;
+    solreng::release(counters);
+    plan = StreamPlan();
+    bands = 0;
+    serial = 0;
+    key[0] = key[1] = key[2] = 0;
+    valid = false;
+    support = -1;
 }
 
 /* the bands of a frame of that many tile rows; false: such a frame is not streamed (SOLR_HIP_NO_IMAGE_STREAMING=1, a frame
  * of fewer than sixteen tile rows) */
 bool imageStreamingCuts(int tileRows, int firstRow[SOLR_STREAM_BANDS_MAX + 1], int *bands, bool withIds)
 {
-    if (g.streamSupport < 0)
+    if (g.streaming.support < 0)
     {
         static const char *off = getenv("SOLR_HIP_NO_IMAGE_STREAMING");
-        g.streamSupport = (off && off[0] == '1') ? 0 : 1;
+        g.streaming.support = (off && off[0] == '1') ? 0 : 1;
     }
-    if (!g.streamSupport || tileRows < 2 * SOLR_STREAM_BANDS_MAX)
+    if (!g.streaming.support || tileRows < 2 * SOLR_STREAM_BANDS_MAX)
         return false;
     /* Five bands of equal height.  The copy engine moves rows twice as fast as the Cornell kernel renders them: every
      * band but the last has landed before the next is complete, and the last is what the frame waits for behind its
@@ -122,58 +130,58 @@ bool armImageStreaming(FrameArgs &F, int tileRows, hipStream_t stream, bool with
         return false;
     const long key[3] = {F.tilesX, tileRows + 100000l * bands, g.width};
     const unsigned perRow = (unsigned)(F.tilesX * SPLIT_PARTS);
-    const bool fresh = memcmp(key, g.streamKey, sizeof(key)) != 0 || !g.streamCounters.ptr;
+    const bool fresh = memcmp(key, g.streaming.key, sizeof(key)) != 0 || !g.streaming.counters.ptr;
     /* (VARIANT_ZERO_STREAM_COUNTERS, tests: as if the row counts neared 2^32 every third frame) */
-    if (fresh || (unsigned long long)(g.streamSerial + 2u) * perRow >= 0xffffffffull ||
-        (g.variant == VARIANT_ZERO_STREAM_COUNTERS && g.streamSerial >= 3u))
+    if (fresh || (unsigned long long)(g.streaming.serial + 2u) * perRow >= 0xffffffffull ||
+        (g.variant == VARIANT_ZERO_STREAM_COUNTERS && g.streaming.serial >= 3u))
     {
         /* nothing of an earlier streamed frame may be under way: its waves count into these words */
         quiesce();
         const size_t words = (size_t)64 * tileRows + (size_t)64 * SOLR_STREAM_BANDS_MAX;
-        reserve(g.streamCounters, words * sizeof(unsigned) + sizeof(StreamPlan));
+        reserve(g.streaming.counters, words * sizeof(unsigned) + sizeof(StreamPlan));
         if (!ok())
             return false;
-        HIPCHECK(hipMemset(g.streamCounters.ptr, 0, words * sizeof(unsigned)));
-        if (!g.streamHostWords)
+        HIPCHECK(hipMemset(g.streaming.counters.ptr, 0, words * sizeof(unsigned)));
+        if (!g.streaming.hostWords)
         {
-            HIPCHECK(hipHostMalloc((void **)&g.streamHostWords, SOLR_STREAM_BANDS_MAX * sizeof(unsigned), hipHostMallocMapped));
+            HIPCHECK(hipHostMalloc((void **)&g.streaming.hostWords, SOLR_STREAM_BANDS_MAX * sizeof(unsigned), hipHostMallocMapped));
             if (ok())
-                HIPCHECK(hipHostGetDevicePointer((void **)&g.streamPlan.hostWord, g.streamHostWords, 0));
+                HIPCHECK(hipHostGetDevicePointer((void **)&g.streaming.plan.hostWord, g.streaming.hostWords, 0));
         }
         if (!ok())
         {
             /* no page-locked words: the frames are rendered and read back as they always were */
             (void)solr_hip_clear_error();
-            g.streamSupport = 0;
+            g.streaming.support = 0;
             return false;
         }
         for (int b = 0; b < SOLR_STREAM_BANDS_MAX; ++b)
-            g.streamHostWords[b] = 0u;
-        g.streamPlan.bandDone = (unsigned *)g.streamCounters.ptr + (size_t)64 * tileRows;
-        g.streamPlan.bands = bands;
+            g.streaming.hostWords[b] = 0u;
+        g.streaming.plan.bandDone = (unsigned *)g.streaming.counters.ptr + (size_t)64 * tileRows;
+        g.streaming.plan.bands = bands;
         for (int b = 0; b <= bands; ++b)
-            g.streamPlan.firstRow[b] = cuts[b];
-        HIPCHECK(hipMemcpy((char *)g.streamCounters.ptr + words * sizeof(unsigned), &g.streamPlan, sizeof(StreamPlan), hipMemcpyHostToDevice));
+            g.streaming.plan.firstRow[b] = cuts[b];
+        HIPCHECK(hipMemcpy((char *)g.streaming.counters.ptr + words * sizeof(unsigned), &g.streaming.plan, sizeof(StreamPlan), hipMemcpyHostToDevice));
         HIPCHECK(hipStreamSynchronize(stream));
         if (!ok())
             return false;
-        memcpy(g.streamKey, key, sizeof(key));
-        g.streamBands = bands;
-        g.streamSerial = 0;
+        memcpy(g.streaming.key, key, sizeof(key));
+        g.streaming.bands = bands;
+        g.streaming.serial = 0;
     }
-    F.rowDone = (unsigned *)g.streamCounters.ptr;
-    F.streamPlan = (const StreamPlan *)((const char *)g.streamCounters.ptr + ((size_t)64 * tileRows + (size_t)64 * SOLR_STREAM_BANDS_MAX) * sizeof(unsigned));
-    F.streamSerial = ++g.streamSerial;
+    F.rowDone = (unsigned *)g.streaming.counters.ptr;
+    F.streamPlan = (const StreamPlan *)((const char *)g.streaming.counters.ptr + ((size_t)64 * tileRows + (size_t)64 * SOLR_STREAM_BANDS_MAX) * sizeof(unsigned));
+    F.streamSerial = ++g.streaming.serial;
     return true;
 }
 
 /* ... and behind the launch, on the frame's own stream: the event that says the kernel has ended */
 void markStreamedFrame(hipStream_t stream)
 {
-    if (!g.streamRendered)
-        HIPCHECK(hipEventCreateWithFlags(&g.streamRendered, hipEventDisableTiming));
+    if (!g.streaming.rendered)
+        HIPCHECK(hipEventCreateWithFlags(&g.streaming.rendered, hipEventDisableTiming));
     if (ok())
-        HIPCHECK(hipEventRecord(g.streamRendered, stream));
+        HIPCHECK(hipEventRecord(g.streaming.rendered, stream));
 }
 } // namespace solreng
 
@@ -190,7 +198,7 @@ namespace solreng
 /* the copy stream of the current engine and its events (one per slot of the ring) */
 void ensureCopyStream()
 {
-    if (g.copyStream)
+    if (g.copyLane.stream)
         return;
     /* (at the render streams' priority.  Measured, profiles/r3/readback_probe.txt: with one or two render streams
      * the copies cost nothing - 0.286 ms per Cornell frame with the image against 0.285 without; with three the
@@ -198,38 +206,35 @@ void ensureCopyStream()
      * render stream ends up sharing one with this stream; a stream of the highest priority, which gets queues of
      * its own, was slower in every combination (0.33 at best).  HipKernel::setFramesInFlight therefore keeps
      * the engine at two buffer sets and puts the rest of the depth into the host's lag.) */
-    HIPCHECK(hipStreamCreateWithFlags(&g.copyStream, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&g.frameRendered, hipEventDisableTiming));
-    for (int i = 0; i < Engine::IMAGE_RING && ok(); ++i)
-        HIPCHECK(hipEventCreateWithFlags(&g.imageDone[i], hipEventDisableTiming));
+    HIPCHECK(hipStreamCreateWithFlags(&g.copyLane.stream, hipStreamNonBlocking));
+    HIPCHECK(hipEventCreateWithFlags(&g.copyLane.frameRendered, hipEventDisableTiming));
+    for (int i = 0; i < ImageRing::IMAGE_RING && ok(); ++i)
+        HIPCHECK(hipEventCreateWithFlags(&g.copyLane.imageDone[i], hipEventDisableTiming));
 }
 
-/* the ring of page-locked images lives in engine 0 (every in-process device copies its strip into the same image) */
+/* the ring of page-locked images, of engine 0's frame size (every in-process device copies its strip into the same image) */
 bool ensureImageRing()
 {
-    Engine &e = gFirst;
-    const size_t frameBytes = (size_t)e.width * e.height * SOLR_COLOR_DEPTH;
-    if (e.pinnedBytes >= frameBytes)
+    ImageRing &ring = gImageRing;
+    const size_t frameBytes = (size_t)gFirst.width * gFirst.height * SOLR_COLOR_DEPTH;
+    if (ring.pinnedBytes >= frameBytes)
         return true;
-    if (e.sharedRing)
+    if (ring.sharedRing)
     {
         setError(-1, "the frame has grown beyond the host image the ranks share (solr_hip_image_share): share again", __FILE__, __LINE__);
         return false;
     }
-    Engine *const was = gCurrent;
-    gCurrent = &gFirst;
-    releaseImageRing(); /* (outstanding tickets are void from here on: their serial no longer matches) */
-    for (int i = 0; i < Engine::IMAGE_RING && ok(); ++i)
+    releaseCopies(); /* (the caller's engine is engine 0: it loses its copy lane with the ring) */
+    ring.release(); /* (outstanding tickets are void from here on: their serial no longer matches) */
+    for (int i = 0; i < ImageRing::IMAGE_RING && ok(); ++i)
     {
-        HIPCHECK(hipHostMalloc((void **)&g.pinnedImage[i], frameBytes, hipHostMallocPortable));
+        HIPCHECK(hipHostMalloc((void **)&ring.pinnedImage[i], frameBytes, hipHostMallocPortable));
         if (ok())
-            memset(g.pinnedImage[i], 0, frameBytes);
+            memset(ring.pinnedImage[i], 0, frameBytes);
     }
     if (ok())
-        g.pinnedBytes = frameBytes;
-    const bool fine = ok();
-    gCurrent = was;
-    return fine;
+        ring.pinnedBytes = frameBytes;
+    return ok();
 }
 
 /* the current engine's strip of the frame it rendered last -> its rows of `image`, on the engine's copy stream behind
@@ -245,44 +250,46 @@ void copyStripBehindFrame(BitmapBuffer *image, int slot)
     const int flight = g.current;
     const int rows = stripRows();
     const int first = g.nbRows >= 0 ? g.firstRow : 0;
-    const void *src = g.boundBitmap ? g.boundBitmap : flightBitmap(flight).ptr;
+    Flight &set = g.flight[flight];
+    CopyLane &lane = g.copyLane;
+    const void *src = g.boundBitmap ? g.boundBitmap : set.shown().ptr;
     /* The copy on the frame's own stream instead of the copy stream (solr_hip_set_copy_route; SOLR_HIP_COPY_INLINE=0/1
      * overrides): it then delays that stream's next frame, not the other streams'.  Measured, profiles/r4/readback_routes.txt:
      * a whole 1080p frame is best served by two buffer sets and the copy stream (0.272 ms; three sets and their own
      * streams 0.280), a 1/8 strip - one round of waves, as slow as its slowest - by three sets and their own streams
      * (0.038 ms against 0.045). */
     static const char *forced = getenv("SOLR_HIP_COPY_INLINE");
-    const bool inlineCopy = forced && forced[0] ? forced[0] == '1' : gFirst.copyOnRenderStream;
-    const hipStream_t copyOn = inlineCopy ? flightStream(flight) : g.copyStream;
+    const bool inlineCopy = forced && forced[0] ? forced[0] == '1' : gImageRing.copyOnRenderStream;
+    const hipStream_t copyOn = inlineCopy ? set.stream : lane.stream;
     if (!inlineCopy)
     {
-        HIPCHECK(hipEventRecord(g.frameRendered, flightStream(flight)));
-        HIPCHECK(hipStreamWaitEvent(g.copyStream, g.frameRendered, 0));
+        HIPCHECK(hipEventRecord(lane.frameRendered, set.stream));
+        HIPCHECK(hipStreamWaitEvent(lane.stream, lane.frameRendered, 0));
     }
     if (rows > 0 && src)
         HIPCHECK(hipMemcpyAsync(image + (size_t)g.width * first * SOLR_COLOR_DEPTH, src,
                                 (size_t)g.width * rows * SOLR_COLOR_DEPTH, hipMemcpyDeviceToHost, copyOn));
-    HIPCHECK(hipEventRecord(g.imageDone[slot], copyOn));
+    HIPCHECK(hipEventRecord(lane.imageDone[slot], copyOn));
     if (!g.boundBitmap)
-        g.flightCopy[flight][g.bitmapSide[flight]] = slot;
+        set.copy[set.side] = slot;
 }
 
 /* hands out the next slot of the ring; the ticket is (serial mod TICKET_PERIOD) * IMAGE_RING + slot: positive for ever
  * (`(int)(serial * IMAGE_RING + slot)` went negative after 2^31 / 6 tickets and read as an error code) */
 int nextTicket(int *slot)
 {
-    Engine &e = gFirst;
-    const long serial = ++e.imageSerial;
-    if (e.sharedRing)
+    ImageRing &ring = gImageRing;
+    const long serial = ++ring.imageSerial;
+    if (ring.sharedRing)
     {
-        const long seq = ++e.shareSeq;
-        *slot = (int)(seq % Engine::IMAGE_RING);
-        e.slotShareSeq[*slot] = seq;
+        const long seq = ++ring.shareSeq;
+        *slot = (int)(seq % ImageRing::IMAGE_RING);
+        ring.slotShareSeq[*slot] = seq;
     }
     else
-        *slot = (int)(serial % Engine::IMAGE_RING);
-    e.slotSerial[*slot] = serial;
-    return Engine::ticketOf(serial, *slot);
+        *slot = (int)(serial % ImageRing::IMAGE_RING);
+    ring.slotSerial[*slot] = serial;
+    return ImageRing::ticketOf(serial, *slot);
 }
 
 /* the slot of a ticket whose image is still the one it was handed out for (the slot's full serial says so; generations
@@ -291,9 +298,10 @@ bool liveTicket(int ticket, int *slot)
 {
     if (ticket < 0)
         return false;
-    *slot = ticket % Engine::IMAGE_RING;
-    const long held = gFirst.slotSerial[*slot];
-    return gFirst.pinnedImage[*slot] != nullptr && held >= 0 && held % Engine::TICKET_PERIOD == (long)(ticket / Engine::IMAGE_RING);
+    *slot = ticket % ImageRing::IMAGE_RING;
+    const long held = gImageRing.slotSerial[*slot];
+    return gImageRing.pinnedImage[*slot] != nullptr && held >= 0 &&
+           held % ImageRing::TICKET_PERIOD == (long)(ticket / ImageRing::IMAGE_RING);
 }
 
 /* shared ring: report, for every slot, the newest copy of this rank that has LANDED (its event has fired) - at every
@@ -301,18 +309,19 @@ bool liveTicket(int ticket, int *slot)
  * solr_hip_image_wait must not keep the root waiting */
 void publishLanded()
 {
-    Engine &e = gFirst;
-    if (!e.sharedRing)
+    ImageRing &ring = gImageRing;
+    if (!ring.sharedRing)
         return;
-    for (int slot = 0; slot < Engine::IMAGE_RING; ++slot)
+    const CopyLane &lane = gFirst.copyLane; /* (a shared ring: one device per process) */
+    for (int slot = 0; slot < ImageRing::IMAGE_RING; ++slot)
     {
-        const long seq = e.slotShareSeq[slot];
-        if (seq <= e.sharePublished[slot] || !e.imageDone[slot] || !e.slotOfStrips[slot])
+        const long seq = ring.slotShareSeq[slot];
+        if (seq <= ring.sharePublished[slot] || !lane.imageDone[slot] || !ring.slotOfStrips[slot])
             continue;
-        if (hipEventQuery(e.imageDone[slot]) != hipSuccess)
+        if (hipEventQuery(lane.imageDone[slot]) != hipSuccess)
             continue;
-        e.sharedRing->done[e.shareRank][slot].store(seq, std::memory_order_release);
-        e.sharePublished[slot] = seq;
+        ring.sharedRing->done[ring.shareRank][slot].store(seq, std::memory_order_release);
+        ring.sharePublished[slot] = seq;
     }
 }
 } // namespace solreng
@@ -323,7 +332,7 @@ extern "C" {
  * stream (what to choose: see copyStripBehindFrame) */
 void solr_hip_set_copy_route(int onTheFramesOwnStream)
 {
-    gFirst.copyOnRenderStream = onTheFramesOwnStream != 0;
+    gImageRing.copyOnRenderStream = onTheFramesOwnStream != 0;
 }
 
 /* ImageStreaming: the frame the next cudaRender launches counts its tiles, if it is a whole frame of one device with
@@ -336,11 +345,11 @@ int solr_hip_stream_next_image(int on)
     if (!ready("solr_hip_stream_next_image"))
         return 0;
     if (on == -2) /* (tests, tools: images that have left in bands since initialize_scene) */
-        return (int)(g.streamedDelivered & 0x7fffffff);
+        return (int)(g.streaming.delivered & 0x7fffffff);
     if (on < 0) /* (asked behind a cudaRender: did that frame count its tiles?) */
-        return g.streamedValid ? 1 : 0;
-    g.streamNext = on >= 2 ? 2 : (on != 0 ? 1 : 0);
-    return g.streamSupport != 0 ? 1 : 0;
+        return g.streaming.valid ? 1 : 0;
+    g.streaming.next = on >= 2 ? 2 : (on != 0 ? 1 : 0);
+    return g.streaming.support != 0 ? 1 : 0;
 }
 
 /* Behind a cudaRender that counted its tiles: every band of the image is copied to its rows of `image` - host memory of
@@ -355,8 +364,8 @@ static int streamedReadBack(BitmapBuffer *image, PrimitiveXYIdBuffer *primitiveI
     if (!ok())
         return -1;
     const int flight = g.current;
-    const void *src = flightBitmap(flight).ptr;
-    if (!g.streamedValid || src != g.streamedBitmap || g.nbRows >= 0 || g.streamBands <= 0 || (primitiveIds && !g.streamedIds))
+    const void *src = g.flight[flight].shown().ptr;
+    if (!g.streaming.valid || src != g.streaming.bitmap || g.nbRows >= 0 || g.streaming.bands <= 0 || (primitiveIds && !g.streaming.ids))
         return 0;
     HIPCHECK(hipSetDevice(g.device));
     ensureCopyStream();
@@ -364,25 +373,25 @@ static int streamedReadBack(BitmapBuffer *image, PrimitiveXYIdBuffer *primitiveI
      * when the kernel has ended - everything it wrote is in memory then, whatever became of the word.  (`image` is
      * pageable as a rule, and a copy into pageable memory returns when it is done: the loop is the pipeline.) */
     const size_t rowBytes = (size_t)g.width * SOLR_COLOR_DEPTH, rowIds = (size_t)g.width;
-    const PrimitiveXYIdBuffer *srcIds = (const PrimitiveXYIdBuffer *)flightIds(flight).ptr;
+    const PrimitiveXYIdBuffer *srcIds = (const PrimitiveXYIdBuffer *)g.flight[flight].ids.ptr;
     bool ended = false;
-    for (int b = 0; b < g.streamBands && ok(); ++b)
+    for (int b = 0; b < g.streaming.bands && ok(); ++b)
     {
-        const int y0 = g.streamPlan.firstRow[b] * TILE_H, y1 = std::min(g.height, g.streamPlan.firstRow[b + 1] * TILE_H);
-        volatile unsigned *word = g.streamHostWords + b;
-        while (!ended && (int)(*word - g.streamSerial) < 0)
-            ended = !g.streamRendered || hipEventQuery(g.streamRendered) != hipErrorNotReady;
+        const int y0 = g.streaming.plan.firstRow[b] * TILE_H, y1 = std::min(g.height, g.streaming.plan.firstRow[b + 1] * TILE_H);
+        volatile unsigned *word = g.streaming.hostWords + b;
+        while (!ended && (int)(*word - g.streaming.serial) < 0)
+            ended = !g.streaming.rendered || hipEventQuery(g.streaming.rendered) != hipErrorNotReady;
         std::atomic_thread_fence(std::memory_order_acquire);
         if (y1 > y0)
             HIPCHECK(hipMemcpyAsync(image + rowBytes * y0, (const char *)src + rowBytes * y0, rowBytes * (y1 - y0), hipMemcpyDeviceToHost,
-                                    g.copyStream));
+                                    g.copyLane.stream));
         if (y1 > y0 && primitiveIds && ok())
             HIPCHECK(hipMemcpyAsync(primitiveIds + rowIds * y0, srcIds + rowIds * y0, rowIds * (y1 - y0) * sizeof(PrimitiveXYIdBuffer),
-                                    hipMemcpyDeviceToHost, g.copyStream));
+                                    hipMemcpyDeviceToHost, g.copyLane.stream));
     }
-    HIPCHECK(hipStreamSynchronize(g.copyStream));
-    g.streamedValid = false;
-    ++g.streamedDelivered;
+    HIPCHECK(hipStreamSynchronize(g.copyLane.stream));
+    g.streaming.valid = false;
+    ++g.streaming.delivered;
     return ok() ? 1 : -1;
 }
 
@@ -413,21 +422,21 @@ int solr_hip_d2h_image_async(void)
     HIPCHECK(hipSetDevice(g.device));
     if (!ensureImageRing())
         return -1;
-    if (g.sharedRing)
+    if (gImageRing.sharedRing)
     {
         publishLanded();
         /* the slot's last frame must have been handed to the root's host before this rank overwrites its rows (ranks
          * are a few frames apart at most: normally no wait at all).  The root gives an image back when it asks for the
          * NEXT one, so a host that lets IMAGE_RING - 1 tickets pile up without asking for any would wait for itself:
          * refused up front, with the limit, before a ticket is taken (the ranks' ticket sequences stay alike) */
-        const long serial = g.shareSeq + 1; /* (the ring's sequence number of the ticket about to be taken) */
-        ARGCHECK(serial - 1 - g.lastWaitedSeq < Engine::IMAGE_RING - 1,
+        const long serial = gImageRing.shareSeq + 1; /* (the ring's sequence number of the ticket about to be taken) */
+        ARGCHECK(serial - 1 - gImageRing.lastWaitedSeq < ImageRing::IMAGE_RING - 1,
                  "solr_hip_d2h_image_async: 5 tickets of the shared image ring are outstanding (IMAGE_RING - 1): ask for "
                  "the oldest one (solr_hip_image_wait) before the next frame is read back");
         if (!ok())
             return -1;
         const auto t0 = std::chrono::steady_clock::now();
-        while (g.sharedRing->consumed.load(std::memory_order_acquire) < serial - Engine::IMAGE_RING)
+        while (gImageRing.sharedRing->consumed.load(std::memory_order_acquire) < serial - ImageRing::IMAGE_RING)
         {
             if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0)
             {
@@ -440,8 +449,8 @@ int solr_hip_d2h_image_async(void)
     }
     int slot = 0;
     const int ticket = nextTicket(&slot);
-    g.slotOfStrips[slot] = g.sharedRing != nullptr;
-    BitmapBuffer *const image = gFirst.pinnedImage[slot];
+    gImageRing.slotOfStrips[slot] = gImageRing.sharedRing != nullptr;
+    BitmapBuffer *const image = gImageRing.pinnedImage[slot];
     onEveryDevice([&](int) { copyStripBehindFrame(image, slot); });
     return solr_hip_last_error(nullptr, 0) == 0 ? ticket : -1;
 }
@@ -449,11 +458,12 @@ int solr_hip_d2h_image_async(void)
 /* back to a ring of this process's own (after solr_hip_image_share; outstanding tickets are void) */
 void solr_hip_image_unshare(void)
 {
-    if (!g.initialized || !g.sharedRing)
+    if (!g.initialized || !gImageRing.sharedRing)
         return;
     quiesce();
     (void)hipSetDevice(g.device);
-    releaseImageRing();
+    releaseCopies();
+    gImageRing.release();
 }
 
 /* One host image for all ranks of a multi-process job.  The reference copies every device's strip to its place in
@@ -476,11 +486,12 @@ int solr_hip_image_share(const char *name, int rank, int world)
         return -1;
     quiesce();
     HIPCHECK(hipSetDevice(g.device));
-    releaseImageRing();
+    releaseCopies();
+    gImageRing.release();
     const size_t frameBytes = (size_t)g.width * g.height * SOLR_COLOR_DEPTH;
     const size_t stride = (frameBytes + 4095) & ~(size_t)4095;
     const size_t head = (sizeof(SharedRing) + 4095) & ~(size_t)4095;
-    const size_t bytes = head + stride * Engine::IMAGE_RING;
+    const size_t bytes = head + stride * ImageRing::IMAGE_RING;
     int fd = -1;
     if (rank == 0)
     {
@@ -532,23 +543,23 @@ int solr_hip_image_share(const char *name, int rank, int world)
             (void)shm_unlink(name);
         return -1;
     }
-    g.sharedRing = ring;
-    g.sharedBytes = bytes;
-    g.sharedName = name;
-    g.shareRank = rank;
-    g.shareWorld = world;
-    for (int i = 0; i < Engine::IMAGE_RING; ++i)
+    gImageRing.sharedRing = ring;
+    gImageRing.sharedBytes = bytes;
+    gImageRing.sharedName = name;
+    gImageRing.shareRank = rank;
+    gImageRing.shareWorld = world;
+    for (int i = 0; i < ImageRing::IMAGE_RING; ++i)
     {
-        g.pinnedImage[i] = (BitmapBuffer *)base + head + stride * i;
-        g.sharePublished[i] = g.slotShareSeq[i] = 0;
+        gImageRing.pinnedImage[i] = (BitmapBuffer *)base + head + stride * i;
+        gImageRing.sharePublished[i] = gImageRing.slotShareSeq[i] = 0;
     }
-    g.pinnedBytes = frameBytes;
+    gImageRing.pinnedBytes = frameBytes;
     /* the ranks count the ring's slots alike from here (shareSeq); the tickets' generation - this process's own serial -
      * goes on counting: a ticket from before the share never names a slot of the shared ring (the serial
      * used to be reset to 0 here, and an old ticket with the same serial then returned a new frame's image) */
-    g.shareSeq = 0;
-    g.lastHandedOut = 0;
-    g.lastWaitedSeq = 0;
+    gImageRing.shareSeq = 0;
+    gImageRing.lastHandedOut = 0;
+    gImageRing.lastWaitedSeq = 0;
     return ok() ? 0 : -1;
 }
 
@@ -557,10 +568,10 @@ int solr_hip_image_share(const char *name, int rank, int world)
  * Harmless on the other ranks and without a shared ring. */
 void solr_hip_image_share_sealed(void)
 {
-    if (g.initialized && g.sharedRing && g.shareRank == 0 && !g.sharedName.empty())
+    if (g.initialized && gImageRing.sharedRing && gImageRing.shareRank == 0 && !gImageRing.sharedName.empty())
     {
-        (void)shm_unlink(g.sharedName.c_str());
-        g.sharedName.clear();
+        (void)shm_unlink(gImageRing.sharedName.c_str());
+        gImageRing.sharedName.clear();
     }
 }
 
@@ -578,31 +589,31 @@ const BitmapBuffer *solr_hip_image_wait(int ticket)
     if (!ok())
         return nullptr;
     onEveryDevice([&](int) {
-        if (g.imageDone[slot])
-            HIPCHECK(hipEventSynchronize(g.imageDone[slot]));
+        if (g.copyLane.imageDone[slot])
+            HIPCHECK(hipEventSynchronize(g.copyLane.imageDone[slot]));
     });
-    if (g.sharedRing && ok())
+    if (gImageRing.sharedRing && ok())
     {
         /* this rank's strip of that frame has landed; the root returns when everybody's has */
-        const long serial = g.slotShareSeq[slot]; /* (the shared ring's sequence number of that frame) */
-        if (serial > g.lastWaitedSeq)
-            g.lastWaitedSeq = serial;
-        SharedRing &ring = *g.sharedRing;
-        if (g.slotOfStrips[slot] && serial > g.sharePublished[slot])
+        const long serial = gImageRing.slotShareSeq[slot]; /* (the shared ring's sequence number of that frame) */
+        if (serial > gImageRing.lastWaitedSeq)
+            gImageRing.lastWaitedSeq = serial;
+        SharedRing &ring = *gImageRing.sharedRing;
+        if (gImageRing.slotOfStrips[slot] && serial > gImageRing.sharePublished[slot])
         {
-            ring.done[g.shareRank][slot].store(serial, std::memory_order_release);
-            g.sharePublished[slot] = serial;
+            ring.done[gImageRing.shareRank][slot].store(serial, std::memory_order_release);
+            gImageRing.sharePublished[slot] = serial;
         }
         publishLanded();
-        if (g.shareRank == 0)
+        if (gImageRing.shareRank == 0)
         {
             /* asking for the next image gives the last one back: only now may the other ranks overwrite its rows (a
              * rank can be frames ahead of the root's host - a transport that buffers its sends lets it) */
-            if (ring.consumed.load(std::memory_order_relaxed) < g.lastHandedOut)
-                ring.consumed.store(g.lastHandedOut, std::memory_order_release);
+            if (ring.consumed.load(std::memory_order_relaxed) < gImageRing.lastHandedOut)
+                ring.consumed.store(gImageRing.lastHandedOut, std::memory_order_release);
             const auto t0 = std::chrono::steady_clock::now();
             /* (a ticket of solr_hip_d2h_gathered_async is the root's own copy of the assembled frame: nobody to wait for) */
-            for (int r = 1; r < g.shareWorld && g.slotOfStrips[slot]; ++r)
+            for (int r = 1; r < gImageRing.shareWorld && gImageRing.slotOfStrips[slot]; ++r)
                 while (ring.done[r][slot].load(std::memory_order_acquire) < serial)
                 {
                     if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0)
@@ -613,10 +624,10 @@ const BitmapBuffer *solr_hip_image_wait(int ticket)
                     }
                     sched_yield();
                 }
-            g.lastHandedOut = serial;
+            gImageRing.lastHandedOut = serial;
         }
     }
-    return solr_hip_last_error(nullptr, 0) == 0 ? gFirst.pinnedImage[slot] : nullptr;
+    return solr_hip_last_error(nullptr, 0) == 0 ? gImageRing.pinnedImage[slot] : nullptr;
 }
 
 } // extern "C"
@@ -628,18 +639,18 @@ namespace solrprobe
  * that a test can put a running engine a few frames before 2^31 / IMAGE_RING tickets and go across */
 int ticketOfSerial(long long serial, int *slot, long long *period)
 {
-    const int s = (int)(serial % Engine::IMAGE_RING); /* (a ring of this process's own; a shared ring counts its slots itself) */
+    const int s = (int)(serial % ImageRing::IMAGE_RING); /* (a ring of this process's own; a shared ring counts its slots itself) */
     if (slot)
         *slot = s;
     if (period)
-        *period = Engine::TICKET_PERIOD;
-    return Engine::ticketOf((long)serial, s);
+        *period = ImageRing::TICKET_PERIOD;
+    return ImageRing::ticketOf((long)serial, s);
 }
 long long imageSerial(long long setTo)
 {
     if (setTo >= 0)
-        gFirst.imageSerial = (long)setTo;
-    return gFirst.imageSerial;
+        gImageRing.imageSerial = (long)setTo;
+    return gImageRing.imageSerial;
 }
 
 } // namespace solrprobe

@@ -67,52 +67,48 @@ void allocateFrame()
 {
     const int rows = stripRows();
     const size_t pixels = (size_t)std::max(g.width, 1) * (size_t)std::max(rows, 1);
-    const bool grow = pixels * sizeof(PostProcessingBuffer) > g.pp.bytes;
-    reserve(g.pp, pixels * sizeof(PostProcessingBuffer));
-    reserve(g.ids, pixels * sizeof(PrimitiveXYIdBuffer));
-    reserve(g.bitmap, pixels * SOLR_COLOR_DEPTH);
-    /* (a buffer set's second RGB image - renderImpl makes it when a read-back still holds the first - grows with the
-     * frame too: the set may be on that side when the frame is re-shaped) */
-    for (int f = 0; f < MAX_FLIGHTS; ++f)
-        if (g.bitmapAlt[f].ptr)
-            reserve(g.bitmapAlt[f], pixels * SOLR_COLOR_DEPTH);
-#ifdef SOLR_TIMING
-    if (!g.counters.ptr)
+    /* the sets in use: flight 0's whatever happens, the others' as far as frames may be in flight */
+    const int sets = g.flights >= 2 && (g.ownStream || g.callerStreams) ? std::min(g.flights, MAX_FLIGHTS) : 1;
+    bool fresh = g.allocW != g.width || g.allocRows != rows;
+    for (int f = 0; f < sets && (f == 0 || ok()); ++f)
     {
-        reserve(g.counters, (16 + 16 * SOLR_TIMING_SLOTS) * sizeof(unsigned long long));
-        if (ok())
-            HIPCHECK(hipMemset(g.counters.ptr, 0, g.counters.bytes));
-    }
-#else
-    reserve(g.counters, 16 * sizeof(unsigned long long));
-#endif
-    const bool fresh = grow || g.allocW != g.width || g.allocRows != rows;
-    if (ok() && fresh)
-    {
-        HIPCHECK(hipMemsetAsync(g.pp.ptr, 0, g.pp.bytes, g.stream));
-        HIPCHECK(hipMemsetAsync(g.ids.ptr, 0, g.ids.bytes, g.stream));
-        HIPCHECK(hipMemsetAsync(g.bitmap.ptr, 0, g.bitmap.bytes, g.stream));
-    }
-    if (ok() && g.flights >= 2 && (g.ownStream || g.callerStreams))
-        for (int f = 1; f < g.flights && f < MAX_FLIGHTS; ++f)
+        Flight &set = g.flight[f];
+        if (f && !set.stream)
         {
-            if (!g.extraStream[f - 1])
-            {
-                if (g.callerStreams)
-                    break; /* the caller gave fewer streams */
-                HIPCHECK(hipStreamCreate(&g.extraStream[f - 1]));
-            }
-            const bool growX = pixels * sizeof(PostProcessingBuffer) > g.ppX[f - 1].bytes;
-            reserve(g.ppX[f - 1], pixels * sizeof(PostProcessingBuffer));
-            reserve(g.idsX[f - 1], pixels * sizeof(PrimitiveXYIdBuffer));
-            reserve(g.bitmapX[f - 1], pixels * SOLR_COLOR_DEPTH);
-            if (ok() && (fresh || growX))
-            {
-                HIPCHECK(hipMemsetAsync(g.ppX[f - 1].ptr, 0, g.ppX[f - 1].bytes, g.extraStream[f - 1]));
-                HIPCHECK(hipMemsetAsync(g.idsX[f - 1].ptr, 0, g.idsX[f - 1].bytes, g.extraStream[f - 1]));
-                HIPCHECK(hipMemsetAsync(g.bitmapX[f - 1].ptr, 0, g.bitmapX[f - 1].bytes, g.extraStream[f - 1]));
-            }
+            if (g.callerStreams)
+                break; /* the caller gave fewer streams */
+            HIPCHECK(hipStreamCreate(&set.stream));
         }
+        const bool grow = pixels * sizeof(PostProcessingBuffer) > set.pp.bytes;
+        reserve(set.pp, pixels * sizeof(PostProcessingBuffer));
+        reserve(set.ids, pixels * sizeof(PrimitiveXYIdBuffer));
+        reserve(set.image[0], pixels * SOLR_COLOR_DEPTH);
+        if (f == 0) /* (here, not in front of the loop: the order of the device calls is the one it always was) */
+        {
+            fresh = fresh || grow;
+            /* (a buffer set's second RGB image - renderImpl makes it when a read-back still holds the first - grows with
+             * the frame too, in use or not: the set may be on that side when the frame is re-shaped) */
+            for (Flight &any : g.flight)
+                if (any.image[1].ptr)
+                    reserve(any.image[1], pixels * SOLR_COLOR_DEPTH);
+#ifdef SOLR_TIMING
+            if (!g.counters.ptr)
+            {
+                reserve(g.counters, (16 + 16 * SOLR_TIMING_SLOTS) * sizeof(unsigned long long));
+                if (ok())
+                    HIPCHECK(hipMemset(g.counters.ptr, 0, g.counters.bytes));
+            }
+#else
+            reserve(g.counters, 16 * sizeof(unsigned long long));
+#endif
+        }
+        if (ok() && (fresh || grow))
+        {
+            HIPCHECK(hipMemsetAsync(set.pp.ptr, 0, set.pp.bytes, set.stream));
+            HIPCHECK(hipMemsetAsync(set.ids.ptr, 0, set.ids.bytes, set.stream));
+            HIPCHECK(hipMemsetAsync(set.image[0].ptr, 0, set.image[0].bytes, set.stream));
+        }
+    }
     g.allocW = g.width;
     g.allocRows = rows;
 }
@@ -140,6 +136,7 @@ int neededFeatures(const SceneInfo &sceneInfo, bool full)
 void launchPostProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, int flight, hipStream_t stream, int firstRow,
                        int nbRows, unsigned char *bitmap, HaloDebt &debt)
 {
+    const PixelRecord *const pp = (const PixelRecord *)g.flight[flight].pp.ptr;
     if (ppInfo.type == ppe_ambientOcclusion)
     {
         /* a strip's taps reach into the rows of the ranks above and below: their depths come from the host
@@ -160,26 +157,26 @@ void launchPostProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppI
             else if (debt.owed)
             {
                 debt.owed = false;
-                exchangeDepthHalo(flight, stream, (const PixelRecord *)flightPp(flight).ptr, sceneInfo.size.x, firstRow,
+                exchangeDepthHalo(flight, stream, pp, sceneInfo.size.x, firstRow,
                                   nbRows, sceneInfo.size.y, wanted, &halo);
             }
         }
         if (ok())
-            solrpost::ambientOcclusion(stream, sceneInfo, ppInfo, nbRows, (const PixelRecord *)flightPp(flight).ptr,
+            solrpost::ambientOcclusion(stream, sceneInfo, ppInfo, nbRows, pp,
                                        (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L, bitmap, halo, firstRow,
                                        g.randomsReach, g.variant != VARIANT_AO_FIXED_STRIDE);
     }
     else if (ppInfo.type == ppe_depthOfField)
-        solrpost::depthOfField(stream, sceneInfo, ppInfo, nbRows, (const PixelRecord *)flightPp(flight).ptr,
+        solrpost::depthOfField(stream, sceneInfo, ppInfo, nbRows, pp,
                                (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L, bitmap);
     else if (ppInfo.type == ppe_radiosity)
-        solrpost::radiosity(stream, sceneInfo, ppInfo, nbRows, (const PixelRecord *)flightPp(flight).ptr,
-                            (const int4 *)flightIds(flight).ptr, (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L,
+        solrpost::radiosity(stream, sceneInfo, ppInfo, nbRows, pp,
+                            (const int4 *)g.flight[flight].ids.ptr, (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L,
                             bitmap);
     else if (ppInfo.type == ppe_filter)
-        solrpost::filter(stream, sceneInfo, ppInfo, nbRows, (const PixelRecord *)flightPp(flight).ptr, bitmap);
+        solrpost::filter(stream, sceneInfo, ppInfo, nbRows, pp, bitmap);
     else
-        solrpost::cartoon(stream, sceneInfo, ppInfo, nbRows, (const PixelRecord *)flightPp(flight).ptr, bitmap);
+        solrpost::cartoon(stream, sceneInfo, ppInfo, nbRows, pp, bitmap);
     HIPCHECK(hipGetLastError());
 }
 
@@ -221,17 +218,18 @@ static int takeFlight(const SceneInfo &sceneInfo, bool counting)
     else if (!twoFlights())
         flight = 0;
     g.current = flight;
-    if (!g.boundBitmap && g.flightCopy[flight][g.bitmapSide[flight]] >= 0)
+    Flight &set = g.flight[flight];
+    if (!g.boundBitmap && set.copy[set.side] >= 0)
     {
-        const int side = g.bitmapSide[flight] ^ 1;
-        reserve(g.bitmapAlt[flight], flightBitmap(flight).bytes);
+        const int side = set.side ^ 1;
+        reserve(set.image[1], set.shown().bytes);
         if (!ok())
             return -1;
-        g.bitmapSide[flight] = side;
-        if (g.flightCopy[flight][side] >= 0)
+        set.side = side;
+        if (set.copy[side] >= 0)
         {
-            HIPCHECK(hipStreamWaitEvent(flightStream(flight), g.imageDone[g.flightCopy[flight][side]], 0));
-            g.flightCopy[flight][side] = -1;
+            HIPCHECK(hipStreamWaitEvent(set.stream, g.copyLane.imageDone[set.copy[side]], 0));
+            set.copy[side] = -1;
         }
     }
     return flight;
@@ -370,10 +368,10 @@ static void readFocusDepth(FrameArgs &F, int flight, hipStream_t stream)
 {
     const long focusIndex = (long)(F.si.size.x / 2 * F.si.size.y / 2);
     const long focusRow = focusIndex / F.si.size.x - F.firstRow;
-    if (focusRow >= 0 && focusRow < F.nbRows && flightPp(flight).ptr)
+    if (focusRow >= 0 && focusRow < F.nbRows && g.flight[flight].pp.ptr)
     {
         const PostProcessingBuffer *at =
-            (const PostProcessingBuffer *)flightPp(flight).ptr + focusRow * F.si.size.x + focusIndex % F.si.size.x;
+            (const PostProcessingBuffer *)g.flight[flight].pp.ptr + focusRow * F.si.size.x + focusIndex % F.si.size.x;
         HIPCHECK(hipMemcpyAsync(&F.focusDepth, &at->colorInfo.w, sizeof(float), hipMemcpyDeviceToHost, stream));
         HIPCHECK(hipStreamSynchronize(stream));
     }
@@ -397,13 +395,13 @@ static bool armTileClocks(FrameArgs &F, unsigned tiles)
  * for the primitive ids too. */
 static BandCuts decideStreamCuts(const FrameArgs &F, bool counting, bool *withIds)
 {
-    g.streamedValid = false;
+    g.streaming.valid = false;
     BandCuts cuts = {};
     int rows[SOLR_STREAM_BANDS_MAX + 1];
-    if (g.streamNext && !counting && !g.recordNext && F.fuseDefault && F.si.frameBufferType != ftBGR && !twoFlights() &&
-        g.nbRows < 0 && gDevices == 1 && !g.boundBitmap && !g.sharedRing && g.lastMask >= 0 &&
+    if (g.streaming.next && !counting && !g.recordNext && F.fuseDefault && F.si.frameBufferType != ftBGR && !twoFlights() &&
+        g.nbRows < 0 && gDevices == 1 && !g.boundBitmap && !gImageRing.sharedRing && g.lastMask >= 0 &&
         solrrows::renderer(0, g.lastMask | F_STREAM, false) != nullptr &&
-        imageStreamingCuts(tileRows(F), rows, &cuts.bands, g.streamNext == 2))
+        imageStreamingCuts(tileRows(F), rows, &cuts.bands, g.streaming.next == 2))
     {
         for (int b = 0; b <= cuts.bands; ++b)
             cuts.firstTile[b] = rows[b] * F.tilesX;
@@ -411,8 +409,8 @@ static BandCuts decideStreamCuts(const FrameArgs &F, bool counting, bool *withId
          * 0.412 ms against 0.385, with half of them 0.42 and the Cornell box's 0.54: profiles/r6/stream_frame.txt) */
         cuts.heavyShare = 8;
     }
-    *withIds = g.streamNext == 2;
-    g.streamNext = 0;
+    *withIds = g.streaming.next == 2;
+    g.streaming.next = 0;
     return cuts;
 }
 
@@ -615,10 +613,10 @@ static bool armDeepStack(FrameArgs &F, int deepSlots, int flight, hipStream_t st
 {
     F.stackSlots = SOLR_LDS_STACK_SLOTS;
     F.deepStride = (long)F.si.size.x * F.nbRows;
-    reserve(g.deepStack[flight], (size_t)deepSlots * (size_t)F.deepStride * sizeof(float4));
+    reserve(g.flight[flight].deepStack, (size_t)deepSlots * (size_t)F.deepStride * sizeof(float4));
     if (!ok())
         return false;
-    F.deepStack = (float4 *)g.deepStack[flight].ptr;
+    F.deepStack = (float4 *)g.flight[flight].deepStack.ptr;
     /* the deep slots are never zeroed: every slot a lane reads was written by the trip that made it (rt_device.h
      * launchRayTracing).  VARIANT_NAN_DEEP_STACK proves it: NaNs in every slot before the launch, the same frame after */
     if (g.variant == VARIANT_NAN_DEEP_STACK)
@@ -664,7 +662,7 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     const int flight = takeFlight(sceneInfo, counting);
     if (flight < 0)
         return;
-    const hipStream_t stream = flightStream(flight);
+    const hipStream_t stream = g.flight[flight].stream;
     SceneArgs S;
     if (!frameScene(sceneInfo, objects, counting, S))
         return;
@@ -704,10 +702,10 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     unsigned long long *cntPtr = (unsigned long long *)(recording ? g.walkRecords.ptr : g.counters.ptr);
     if (k.deepSlots > 0 && !armDeepStack(F, k.deepSlots, flight, stream))
         return;
-    unsigned char *bitmap = (unsigned char *)(g.boundBitmap ? g.boundBitmap : flightBitmap(flight).ptr);
+    unsigned char *bitmap = (unsigned char *)(g.boundBitmap ? g.boundBitmap : g.flight[flight].shown().ptr);
     const bool streamed = streamCandidate && !recording && armStreamedFrame(F, k, streamCuts, stream, streamIds, &fn);
     g.lastMask = k.mask;
-    g.streamedIds = streamed && streamIds;
+    g.streaming.ids = streamed && streamIds;
     if (!counting)
     {
         const int features = k.mask < 0 ? -1 : k.mask | (k.deepSlots > 0 ? F_STACK : 0) | (streamed ? F_STREAM : 0);
@@ -717,8 +715,8 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     }
     {
         HostSpan launch("  of which the kernel launch");
-        hipLaunchKernelGGL(fn, grid, dim3(WAVE), ldsBytesFor(F.stackSlots), stream, S, F, (PixelRecord *)flightPp(flight).ptr,
-                           (int4 *)flightIds(flight).ptr, bitmap, cntPtr);
+        hipLaunchKernelGGL(fn, grid, dim3(WAVE), ldsBytesFor(F.stackSlots), stream, S, F, (PixelRecord *)g.flight[flight].pp.ptr,
+                           (int4 *)g.flight[flight].ids.ptr, bitmap, cntPtr);
     }
     HIPCHECK(hipGetLastError());
     if (timer.first)
@@ -729,8 +727,8 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     if (streamed)
     {
         markStreamedFrame(stream);
-        g.streamedValid = ok();
-        g.streamedBitmap = bitmap;
+        g.streaming.valid = ok();
+        g.streaming.bitmap = bitmap;
     }
 
     g.haloWanted = 0;
@@ -781,13 +779,13 @@ void d2hBitmapOne(const SceneInfo &sceneInfo, BitmapBuffer *bitmap, PrimitiveXYI
     const size_t pixels = (size_t)sceneInfo.size.x * rows;
     const size_t offset = (size_t)sceneInfo.size.x * first;
     /* the frame rendered last: its buffer set, on its stream */
-    const hipStream_t stream = flightStream(g.current);
-    const void *src = g.boundBitmap ? g.boundBitmap : flightBitmap(g.current).ptr;
+    const hipStream_t stream = g.flight[g.current].stream;
+    const void *src = g.boundBitmap ? g.boundBitmap : g.flight[g.current].shown().ptr;
     if (bitmap && src)
         HIPCHECK(hipMemcpyAsync(bitmap + offset * SOLR_COLOR_DEPTH, src, pixels * SOLR_COLOR_DEPTH,
                                 hipMemcpyDeviceToHost, stream));
-    if (primitivesXYIds && flightIds(g.current).ptr)
-        HIPCHECK(hipMemcpyAsync(primitivesXYIds + offset, flightIds(g.current).ptr,
+    if (primitivesXYIds && g.flight[g.current].ids.ptr)
+        HIPCHECK(hipMemcpyAsync(primitivesXYIds + offset, g.flight[g.current].ids.ptr,
                                 pixels * sizeof(PrimitiveXYIdBuffer), hipMemcpyDeviceToHost, stream));
     if (wait)
         HIPCHECK(hipStreamSynchronize(stream));
@@ -795,7 +793,7 @@ void d2hBitmapOne(const SceneInfo &sceneInfo, BitmapBuffer *bitmap, PrimitiveXYI
 void d2hBitmapWait()
 {
     if (g.initialized && ok())
-        HIPCHECK(hipStreamSynchronize(flightStream(g.current)));
+        HIPCHECK(hipStreamSynchronize(g.flight[g.current].stream));
 }
 
 } // namespace solreng
@@ -808,14 +806,14 @@ void solr_hip_d2h_postprocessing(PostProcessingBuffer *hostBuffer)
     onEveryDevice([&](int) {
         if (!ready("solr_hip_d2h_postprocessing"))
             return;
-        ARGCHECK(hostBuffer != nullptr && flightPp(g.current).ptr != nullptr, "solr_hip_d2h_postprocessing: no buffer");
+        ARGCHECK(hostBuffer != nullptr && g.flight[g.current].pp.ptr != nullptr, "solr_hip_d2h_postprocessing: no buffer");
         if (!ok())
             return;
         const size_t pixels = (size_t)g.width * stripRows();
         const size_t offset = gDevices > 1 ? (size_t)g.width * (g.nbRows >= 0 ? g.firstRow : 0) : 0;
-        HIPCHECK(hipMemcpyAsync(hostBuffer + offset, flightPp(g.current).ptr, pixels * sizeof(PostProcessingBuffer),
-                                hipMemcpyDeviceToHost, flightStream(g.current)));
-        HIPCHECK(hipStreamSynchronize(flightStream(g.current)));
+        HIPCHECK(hipMemcpyAsync(hostBuffer + offset, g.flight[g.current].pp.ptr, pixels * sizeof(PostProcessingBuffer),
+                                hipMemcpyDeviceToHost, g.flight[g.current].stream));
+        HIPCHECK(hipStreamSynchronize(g.flight[g.current].stream));
     });
 }
 
@@ -829,12 +827,12 @@ void solr_hip_h2d_postprocessing(const PostProcessingBuffer *hostBuffer, const P
         return;
     /* into the set the next refinement / accumulation pass will read: the current one */
     const size_t pixels = (size_t)g.width * stripRows();
-    const hipStream_t stream = flightStream(g.current);
+    const hipStream_t stream = g.flight[g.current].stream;
     if (hostBuffer)
-        HIPCHECK(hipMemcpyAsync(flightPp(g.current).ptr, hostBuffer, pixels * sizeof(PostProcessingBuffer),
+        HIPCHECK(hipMemcpyAsync(g.flight[g.current].pp.ptr, hostBuffer, pixels * sizeof(PostProcessingBuffer),
                                 hipMemcpyHostToDevice, stream));
     if (ids)
-        HIPCHECK(hipMemcpyAsync(flightIds(g.current).ptr, ids, pixels * sizeof(PrimitiveXYIdBuffer),
+        HIPCHECK(hipMemcpyAsync(g.flight[g.current].ids.ptr, ids, pixels * sizeof(PrimitiveXYIdBuffer),
                                 hipMemcpyHostToDevice, stream));
     HIPCHECK(hipStreamSynchronize(stream));
 }

@@ -185,7 +185,7 @@ bool allReduceFloats(float *values, size_t n, int op, const char *what)
     if (!rccl.comm)
         return false;
     (void)hipSetDevice(g.device);
-    const hipStream_t stream = flightStream(0);
+    const hipStream_t stream = g.flight[0].stream;
     bool fine = reserveQuietly(rccl.scratch, n * sizeof(float), false);
     /* (a rank that cannot even allocate the few floats still has to show up: it reduces in the zero buffer) */
     void *buffer = fine ? rccl.scratch.ptr : (void *)zeroPayload(n * sizeof(float));
@@ -288,7 +288,7 @@ bool shareRandoms()
     if (n == 0)
         return true;
     (void)hipSetDevice(g.device);
-    const hipStream_t stream = flightStream(0);
+    const hipStream_t stream = g.flight[0].stream;
     bool fine = rcclOk(rccl.GroupStart(), "ncclGroupStart");
     if (fine && rccl.rank == 0)
         for (int r = 1; r < rccl.world && fine; ++r)
@@ -361,12 +361,13 @@ void exchangeDepthHalo(int flight, hipStream_t stream, const PixelRecord *pp, in
         setError(-1, "cudaRender: this process's strip is not the one solr_hip_strip_rows (or the table of "
                      "solr_hip_set_strip_table) gives its rank; its neighbours received zeros for its boundary rows",
                  __FILE__, __LINE__);
-    const bool room = reserveQuietly(g.haloAbove[flight], (size_t)std::max(recvAbove, 1) * W * sizeof(float), false) &&
-                      reserveQuietly(g.haloBelow[flight], (size_t)std::max(recvBelow, 1) * W * sizeof(float), false);
-    if (own && !(reserveQuietly(g.haloSendTop[flight], mineBytes, false) && reserveQuietly(g.haloSendBottom[flight], mineBytes, false)))
+    Flight &set = g.flight[flight];
+    const bool room = reserveQuietly(set.haloAbove, (size_t)std::max(recvAbove, 1) * W * sizeof(float), false) &&
+                      reserveQuietly(set.haloBelow, (size_t)std::max(recvBelow, 1) * W * sizeof(float), false);
+    if (own && !(reserveQuietly(set.haloSendTop, mineBytes, false) && reserveQuietly(set.haloSendBottom, mineBytes, false)))
         own = false;
-    const void *top = own ? g.haloSendTop[flight].ptr : zeroPayload(mineBytes);
-    const void *bottom = own ? g.haloSendBottom[flight].ptr : top;
+    const void *top = own ? set.haloSendTop.ptr : zeroPayload(mineBytes);
+    const void *bottom = own ? set.haloSendBottom.ptr : top;
     if (!room || !top)
     {
         setError(-1, "cudaRender: no device memory for the depth-halo exchange; the neighbouring ranks are left waiting",
@@ -376,9 +377,9 @@ void exchangeDepthHalo(int flight, hipStream_t stream, const PixelRecord *pp, in
     if (own)
     {
         if (sendUp)
-            solrpost::packDepthRows(stream, pp, W, 0, mine, (float *)g.haloSendTop[flight].ptr);
+            solrpost::packDepthRows(stream, pp, W, 0, mine, (float *)set.haloSendTop.ptr);
         if (sendDown)
-            solrpost::packDepthRows(stream, pp, W, nbRows - mine, mine, (float *)g.haloSendBottom[flight].ptr);
+            solrpost::packDepthRows(stream, pp, W, nbRows - mine, mine, (float *)set.haloSendBottom.ptr);
         HIPCHECK(hipGetLastError());
     }
     bool fine = rcclOk(rccl.GroupStart(), "ncclGroupStart");
@@ -388,15 +389,15 @@ void exchangeDepthHalo(int flight, hipStream_t stream, const PixelRecord *pp, in
         fine = rcclOk(rccl.Send(bottom, (size_t)mine * W, RCCL_FLOAT32, rccl.rank + 1, commOf(flight), stream),
                       "ncclSend (depth rows, down)");
     if (fine && recvAbove)
-        fine = rcclOk(rccl.Recv(g.haloAbove[flight].ptr, (size_t)recvAbove * W, RCCL_FLOAT32, rccl.rank - 1, commOf(flight), stream),
+        fine = rcclOk(rccl.Recv(set.haloAbove.ptr, (size_t)recvAbove * W, RCCL_FLOAT32, rccl.rank - 1, commOf(flight), stream),
                       "ncclRecv (depth rows, above)");
     if (fine && recvBelow)
-        fine = rcclOk(rccl.Recv(g.haloBelow[flight].ptr, (size_t)recvBelow * W, RCCL_FLOAT32, rccl.rank + 1, commOf(flight), stream),
+        fine = rcclOk(rccl.Recv(set.haloBelow.ptr, (size_t)recvBelow * W, RCCL_FLOAT32, rccl.rank + 1, commOf(flight), stream),
                       "ncclRecv (depth rows, below)");
     if (!rcclOk(rccl.GroupEnd(), "ncclGroupEnd") || !fine || !own || !halo)
         return;
-    halo->above = (const float *)g.haloAbove[flight].ptr;
-    halo->below = (const float *)g.haloBelow[flight].ptr;
+    halo->above = (const float *)set.haloAbove.ptr;
+    halo->below = (const float *)set.haloBelow.ptr;
     halo->nbAbove = recvAbove;
     halo->nbBelow = recvBelow;
 }
@@ -819,7 +820,7 @@ int gatherImpl(int root, bool ids, const char *who)
     }
     (void)hipSetDevice(g.device);
     const int flight = g.current;
-    const hipStream_t stream = flightStream(flight);
+    const hipStream_t stream = g.flight[flight].stream;
     const size_t rowBytes = (size_t)g.width * (ids ? sizeof(PrimitiveXYIdBuffer) : (size_t)SOLR_COLOR_DEPTH);
     /* rank-local trouble decides what is sent, not whether (see the note on collectives above) */
     bool mine = ok();
@@ -830,7 +831,7 @@ int gatherImpl(int root, bool ids, const char *who)
                  __FILE__, __LINE__);
         mine = false;
     }
-    const void *src = ids ? flightIds(flight).ptr : (g.boundBitmap ? g.boundBitmap : flightBitmap(flight).ptr);
+    const void *src = ids ? g.flight[flight].ids.ptr : (g.boundBitmap ? g.boundBitmap : g.flight[flight].shown().ptr);
     if (!src)
         mine = false;
     DeviceBuffer &assembled = ids ? rccl.idsFrame : rccl.frame[flight];
@@ -844,8 +845,8 @@ int gatherImpl(int root, bool ids, const char *who)
     {
         /* a pipelined read-back (solr_hip_d2h_gathered_async) may still be copying the frame this flight assembled
          * last: the gather that overwrites it goes behind that copy */
-        if (gFirst.imageDone[rccl.frameCopy[flight]])
-            (void)hipStreamWaitEvent(stream, gFirst.imageDone[rccl.frameCopy[flight]], 0);
+        if (gFirst.copyLane.imageDone[rccl.frameCopy[flight]])
+            (void)hipStreamWaitEvent(stream, gFirst.copyLane.imageDone[rccl.frameCopy[flight]], 0);
         rccl.frameCopy[flight] = -1;
     }
     const bool fine = gatherRows(root, mine ? src : nullptr, rccl.rank == root ? assembled.ptr : nullptr, rowBytes,
@@ -890,7 +891,7 @@ int solr_hip_d2h_gathered(BitmapBuffer *hostBitmap)
              "solr_hip_d2h_gathered: nothing was gathered on this rank");
     if (!ok())
         return -1;
-    const hipStream_t stream = flightStream(rccl.lastFlight);
+    const hipStream_t stream = g.flight[rccl.lastFlight].stream;
     HIPCHECK(hipMemcpyAsync(hostBitmap, rccl.frame[rccl.lastFlight].ptr, (size_t)g.height * g.width * SOLR_COLOR_DEPTH,
                             hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
@@ -908,13 +909,13 @@ int solr_hip_d2h_gathered_async(void)
         return -1;
     if (!rccl.comm || !rccl.frame[rccl.lastFlight].ptr)
     {
-        if (!g.sharedRing)
+        if (!gImageRing.sharedRing)
             return -2;
         /* with a ring the ranks share (solr_hip_image_share) every rank takes the ticket, so that the ranks keep
          * counting alike; only the root has something to copy */
         int slot = 0;
         const int ticket = nextTicket(&slot);
-        g.slotOfStrips[slot] = false;
+        gImageRing.slotOfStrips[slot] = false;
         return ticket;
     }
     HIPCHECK(hipSetDevice(g.device));
@@ -926,12 +927,12 @@ int solr_hip_d2h_gathered_async(void)
     const int flight = rccl.lastFlight;
     int slot = 0;
     const int ticket = nextTicket(&slot);
-    HIPCHECK(hipEventRecord(g.frameRendered, flightStream(flight)));
-    HIPCHECK(hipStreamWaitEvent(g.copyStream, g.frameRendered, 0));
-    HIPCHECK(hipMemcpyAsync(g.pinnedImage[slot], rccl.frame[flight].ptr, (size_t)g.height * g.width * SOLR_COLOR_DEPTH,
-                            hipMemcpyDeviceToHost, g.copyStream));
-    HIPCHECK(hipEventRecord(g.imageDone[slot], g.copyStream));
-    g.slotOfStrips[slot] = false;
+    HIPCHECK(hipEventRecord(g.copyLane.frameRendered, g.flight[flight].stream));
+    HIPCHECK(hipStreamWaitEvent(g.copyLane.stream, g.copyLane.frameRendered, 0));
+    HIPCHECK(hipMemcpyAsync(gImageRing.pinnedImage[slot], rccl.frame[flight].ptr, (size_t)g.height * g.width * SOLR_COLOR_DEPTH,
+                            hipMemcpyDeviceToHost, g.copyLane.stream));
+    HIPCHECK(hipEventRecord(g.copyLane.imageDone[slot], g.copyLane.stream));
+    gImageRing.slotOfStrips[slot] = false;
     rccl.frameCopy[flight] = slot;
     return ok() ? ticket : -1;
 }
@@ -943,7 +944,7 @@ int solr_hip_d2h_gathered_ids(PrimitiveXYIdBuffer *hostIds)
     ARGCHECK(hostIds != nullptr && rccl.idsFrame.ptr != nullptr, "solr_hip_d2h_gathered_ids: nothing was gathered on this rank");
     if (!ok())
         return -1;
-    const hipStream_t stream = flightStream(rccl.idsFlight);
+    const hipStream_t stream = g.flight[rccl.idsFlight].stream;
     HIPCHECK(hipMemcpyAsync(hostIds, rccl.idsFrame.ptr, (size_t)g.height * g.width * sizeof(PrimitiveXYIdBuffer),
                             hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));

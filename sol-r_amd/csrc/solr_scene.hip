@@ -442,7 +442,7 @@ static void refitList(const NodeList &list, float viewDistance)
     const int *plan = (const int *)g.refitPlan.ptr;
     const std::vector<int> &levels = list.refitLevels;
     for (size_t l = 0; l + 1 < levels.size(); l += 2)
-        hipLaunchKernelGGL(k_refitNodes, dim3((unsigned)((levels[l + 1] + 255) / 256)), dim3(256), 0, g.stream, arena,
+        hipLaunchKernelGGL(k_refitNodes, dim3((unsigned)((levels[l + 1] + 255) / 256)), dim3(256), 0, sceneStream(), arena,
                            list.offRows, list.offStart, g.offPrims, plan + levels[l], levels[l + 1], viewDistance);
 }
 
@@ -454,7 +454,7 @@ void refreshExactList()
     quiesce();
     refitList(g.exact, g.exactStaleViewDistance);
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(g.stream));
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
     g.exactStale = false;
 }
 
@@ -622,9 +622,9 @@ static bool tightenList(const NodeList &list)
     float4 *arena = (float4 *)g.geometry.ptr;
     const float margin = g.sceneExtent * (1.f / 1024.f);
     const dim3 grid((unsigned)((nbNodes + 255) / 256));
-    hipLaunchKernelGGL(k_tightenLeaves, grid, dim3(256), 0, g.stream, arena, list.offRows, list.offThin(), list.offStart, g.offPrims,
+    hipLaunchKernelGGL(k_tightenLeaves, grid, dim3(256), 0, sceneStream(), arena, list.offRows, list.offThin(), list.offStart, g.offPrims,
                        nbNodes, margin);
-    hipLaunchKernelGGL(k_tightenInner, grid, dim3(256), 0, g.stream, arena, list.offThin(), nbNodes, listLength);
+    hipLaunchKernelGGL(k_tightenInner, grid, dim3(256), 0, sceneStream(), arena, list.offThin(), nbNodes, listLength);
     HIPCHECK(hipGetLastError());
     return ok();
 }
@@ -675,7 +675,7 @@ static bool sortFreeLists()
     const NodeList &list = g.orderFree;
     if (off || list.nb <= 0 || !ok())
         return false;
-    hipLaunchKernelGGL(k_sortNodeBounds, dim3((unsigned)((8 * list.nb + 1 + 255) / 256)), dim3(256), 0, g.stream,
+    hipLaunchKernelGGL(k_sortNodeBounds, dim3((unsigned)((8 * list.nb + 1 + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.geometry.ptr, list.offRows, list.offSorted(), list.nb);
     HIPCHECK(hipGetLastError());
     return ok();
@@ -689,7 +689,7 @@ static void deriveList(NodeList &list)
     const bool orderFree = &list == &g.orderFree;
     const int n = (orderFree && g.freeStale) ? 0 : (int)list.nodes();
     if (n > 0)
-        hipLaunchKernelGGL(k_buildLeafRecords, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, (float4 *)g.geometry.ptr,
+        hipLaunchKernelGGL(k_buildLeafRecords, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sceneStream(), (float4 *)g.geometry.ptr,
                            list.offRows, list.offStart, g.offPrims, list.offLeaf, n);
     HIPCHECK(hipGetLastError());
     list.tight = list.copies > 1 && n > 0 && tightenList(list);
@@ -704,7 +704,7 @@ void buildLeafRecords()
         return;
     for (NodeList *list : {&g.exact, &g.walk, &g.orderFree})
         deriveList(*list);
-    HIPCHECK(hipStreamSynchronize(g.stream));
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
 }
 
 /* the lists the device builder left (g.freeStage) to their place in the arena */
@@ -712,8 +712,8 @@ static void copyStagedLists()
 {
     const NodeList &list = g.orderFree;
     char *arena = (char *)g.geometry.ptr;
-    HIPCHECK(hipMemcpyAsync(arena + (size_t)list.offRows * 16, g.freeStage.rows, (size_t)list.nodes() * 32, hipMemcpyDeviceToDevice, g.stream));
-    HIPCHECK(hipMemcpyAsync(arena + (size_t)list.offStart * 4, g.freeStage.start, (size_t)list.nodes() * 4, hipMemcpyDeviceToDevice, g.stream));
+    HIPCHECK(hipMemcpyAsync(arena + (size_t)list.offRows * 16, g.freeStage.rows, (size_t)list.nodes() * 32, hipMemcpyDeviceToDevice, sceneStream()));
+    HIPCHECK(hipMemcpyAsync(arena + (size_t)list.offStart * 4, g.freeStage.start, (size_t)list.nodes() * 4, hipMemcpyDeviceToDevice, sceneStream()));
 }
 
 /* the lists the device builder has just left (g.freeStage) into an arena that holds everything else already: what
@@ -730,16 +730,16 @@ static void appendFreeLists()
         reserve(larger, bytes);
         if (!ok())
             return;
-        HIPCHECK(hipMemcpyAsync(larger.ptr, g.geometry.ptr, fixedBytes, hipMemcpyDeviceToDevice, g.stream));
-        HIPCHECK(hipStreamSynchronize(g.stream));
+        HIPCHECK(hipMemcpyAsync(larger.ptr, g.geometry.ptr, fixedBytes, hipMemcpyDeviceToDevice, sceneStream()));
+        HIPCHECK(hipStreamSynchronize(sceneStream()));
         release(g.geometry);
         g.geometry = larger;
     }
-    HIPCHECK(hipMemsetAsync((char *)g.geometry.ptr + fixedBytes, 0, bytes - fixedBytes, g.stream));
+    HIPCHECK(hipMemsetAsync((char *)g.geometry.ptr + fixedBytes, 0, bytes - fixedBytes, sceneStream()));
     copyStagedLists();
     if (ok())
         deriveList(g.orderFree);
-    HIPCHECK(hipStreamSynchronize(g.stream));
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
     phase.mark("geometry: lists appended");
     if (ok())
     {
@@ -781,10 +781,10 @@ void flushGeometry()
     reserve(g.geometry, (size_t)std::max(row, 1u) * 16);
     if (!ok())
         return;
-    HIPCHECK(hipMemsetAsync(g.geometry.ptr, 0, (size_t)std::max(row, 1u) * 16, g.stream));
+    HIPCHECK(hipMemsetAsync(g.geometry.ptr, 0, (size_t)std::max(row, 1u) * 16, sceneStream()));
     auto put = [&](unsigned at, const void *src, size_t bytes) {
         if (bytes && ok())
-            HIPCHECK(hipMemcpyAsync((char *)g.geometry.ptr + (size_t)at * 16, src, bytes, hipMemcpyHostToDevice, g.stream));
+            HIPCHECK(hipMemcpyAsync((char *)g.geometry.ptr + (size_t)at * 16, src, bytes, hipMemcpyHostToDevice, sceneStream()));
     };
     for (const NodeList *list : {&g.exact, &g.walk, &g.orderFree})
         if (list == &g.orderFree && g.freeStage.rows)
@@ -799,7 +799,7 @@ void flushGeometry()
         }
     put(g.offPrims, g.hostPrims.data(), g.hostPrims.size() * 16);
     put(g.offLights, g.hostLights.data(), g.hostLights.size() * 16);
-    HIPCHECK(hipStreamSynchronize(g.stream)); /* pageable sources: complete for the caller when this returns */
+    HIPCHECK(hipStreamSynchronize(sceneStream())); /* pageable sources: complete for the caller when this returns */
     if (ok())
         dropFreeStage(false);
     phase.mark("geometry: upload");
@@ -959,12 +959,12 @@ static bool listEnclosesInArena(const NodeList &list)
     if (!ok())
         return false;
     int found = 1;
-    HIPCHECK(hipMemsetAsync(g.enclosesFlag.ptr, 0, sizeof(int), g.stream));
-    hipLaunchKernelGGL(k_listEncloses, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, (const float4 *)g.geometry.ptr, list.offRows,
+    HIPCHECK(hipMemsetAsync(g.enclosesFlag.ptr, 0, sizeof(int), sceneStream()));
+    hipLaunchKernelGGL(k_listEncloses, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sceneStream(), (const float4 *)g.geometry.ptr, list.offRows,
                        list.offStart, g.offPrims, n, (int)(g.hostPrims.size() / PRIM_ROWS), (int *)g.enclosesFlag.ptr);
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(&found, g.enclosesFlag.ptr, sizeof(int), hipMemcpyDeviceToHost, g.stream));
-    HIPCHECK(hipStreamSynchronize(g.stream));
+    HIPCHECK(hipMemcpyAsync(&found, g.enclosesFlag.ptr, sizeof(int), hipMemcpyDeviceToHost, sceneStream()));
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
     return ok() && found == 0;
 }
 
@@ -986,7 +986,7 @@ static PruneDecider pruneDecider()
 {
     if (getenv("SOLR_HIP_LISTS_ON_HOST"))
         return nullptr;
-    const hipStream_t stream = g.stream;
+    const hipStream_t stream = sceneStream();
     return [stream](const float4 *rows, int n, double threshold, std::vector<char> &keep) {
         return solrPruneDecisionsOnDevice(rows, n, threshold, keep, stream);
     };
@@ -1052,12 +1052,12 @@ void maybeBuildOrderFreeLists()
             dropFreeStage(true);
             if (fromArena)
                 count = solrBuildOrderFreeListsOnDevice(arena + g.exact.offRows, (const int *)arena + g.exact.offStart, nullptr, n,
-                                                        knobs.pruneThreshold, &prunedFree, g.stream, &g.freeStage);
+                                                        knobs.pruneThreshold, &prunedFree, sceneStream(), &g.freeStage);
             else
             {
                 ownOrigins();
                 count = solrBuildOrderFreeListsOnDevice(rows.data(), start.data(), origin.data(), n, knobs.pruneThreshold, &prunedFree,
-                                                        g.stream, &g.freeStage);
+                                                        sceneStream(), &g.freeStage);
             }
         }
     }
@@ -1274,7 +1274,7 @@ int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const f
     R.cx = center[0], R.cy = center[1], R.cz = center[2];
     R.cosx = cosAngles[0], R.cosy = cosAngles[1], R.cosz = cosAngles[2];
     R.sinx = sinAngles[0], R.siny = sinAngles[1], R.sinz = sinAngles[2];
-    hipLaunchKernelGGL(k_rotatePrimitives, dim3((unsigned)((g.nbPrimitives + 255) / 256)), dim3(256), 0, g.stream,
+    hipLaunchKernelGGL(k_rotatePrimitives, dim3((unsigned)((g.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.geometry.ptr, g.offPrims, g.nbPrimitives, (const unsigned char *)g.movable.ptr, R);
     refitList(g.walk, viewDistance);
     if (g.orderFree.nb > 0 && !g.orderFree.refitLevels.empty())
@@ -1290,7 +1290,7 @@ int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const f
     g.exactStaleViewDistance = viewDistance;
     HIPCHECK(hipGetLastError());
     /* the other flights' streams start their next frame only after this */
-    HIPCHECK(hipStreamSynchronize(g.stream));
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
     if (!ok())
         return 0;
     g.deviceAhead = true;
@@ -1382,21 +1382,21 @@ void h2dMaterialsOne(Material *materials, int nbActiveMaterials)
     /* zeros beyond the active records: the whole table when it is new, else what the last call left behind */
     const int stale = fresh ? capacity : std::min(std::max(g.nbMaterials, 0), capacity);
     if (fresh)
-        HIPCHECK(hipMemsetAsync(table, 0, tableBytes, g.stream));
+        HIPCHECK(hipMemsetAsync(table, 0, tableBytes, sceneStream()));
     else if (stale > active)
     {
         HIPCHECK(hipMemsetAsync(table + (size_t)active * sizeof(MaterialHot), 0, (size_t)(stale - active) * sizeof(MaterialHot),
-                                g.stream));
+                                sceneStream()));
         HIPCHECK(hipMemsetAsync(table + coldAt + (size_t)active * sizeof(MaterialCold), 0,
-                                (size_t)(stale - active) * sizeof(MaterialCold), g.stream));
+                                (size_t)(stale - active) * sizeof(MaterialCold), sceneStream()));
     }
     if (active > 0)
     {
-        HIPCHECK(hipMemcpyAsync(table, hot.data(), (size_t)active * sizeof(MaterialHot), hipMemcpyHostToDevice, g.stream));
+        HIPCHECK(hipMemcpyAsync(table, hot.data(), (size_t)active * sizeof(MaterialHot), hipMemcpyHostToDevice, sceneStream()));
         HIPCHECK(hipMemcpyAsync(table + coldAt, cold.data(), (size_t)active * sizeof(MaterialCold), hipMemcpyHostToDevice,
-                                g.stream));
+                                sceneStream()));
     }
-    HIPCHECK(hipStreamSynchronize(g.stream)); /* pageable sources: complete for the caller when this returns */
+    HIPCHECK(hipStreamSynchronize(sceneStream())); /* pageable sources: complete for the caller when this returns */
     if (ok())
     {
         g.offMatCold = 6u * (unsigned)capacity;
