@@ -94,7 +94,7 @@ void solr_hip_probe_last_frame(int out[6]);
 
 /* What the arena holds of a node list, read back as it is now (pending uploads flushed, the stream idle).  list: 0 the
  * walk-order list, 1 the reference's list, 2 the eight order-free lists one behind the other.  what: 0 the node rows, 1 the
- * thin copy (solr_scene.hip k_tightenLeaves / k_tightenInner), 2 the copy with sorted bounds and the pad record behind it
+ * thin copy (solr_arena.hip k_tightenLeaves / k_tightenInner), 2 the copy with sorted bounds and the pad record behind it
  * (k_sortNodeBounds), 3 the leaf records (k_buildLeafRecords), 4 the start indices.  Returns the number of 16-byte rows
  * (of ints for what = 4) written to out, 0 where the engine holds no such copy up to date, -1 with the error set on
  * failure; out == NULL: the size alone. */

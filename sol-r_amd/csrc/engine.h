@@ -1,12 +1,16 @@
 /*
  * engine.h - the state of the MI355X rendering engine and the helpers every part of its host side uses: what
- * solr_hip.hip (the boundary), solr_scene.hip (scene upload, the node lists; their host builders: list_builders.h), solr_launch.hip (the renderer's launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined
- * read-back), solr_rccl.hip (strips, communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
+ * solr_hip.hip (the boundary), solr_uploads.hip (the h2d_* uploads), solr_arena.hip (the arena and the node lists; their
+ * host builders: list_builders.h), solr_rotation.hip (rotation and refit on the device), solr_launch.hip (the renderer's
+ * launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined read-back), solr_rccl.hip (strips,
+ * communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
- * NodeList (a node list of the resident scene), TileSchedule (the cost-ordered launch), Flight (a frame in flight: its
- * stream and per-pixel buffers; Engine::flight[0] is the one of a process that renders one frame at a time), CopyLane (the
- * device's part of the pipelined read-back) and ImageStreaming (a frame read back in bands); ImageRing - the page-locked
- * host images of the pipelined read-back and their tickets - exists once per process (gImageRing), whatever the number of
+ * NodeList (a node list of the resident scene), Scene with Arena, OrderFreeState and Rotation, Lights, Materials, Textures,
+ * Randoms and SceneFacts (the resident scene, cut by who writes them), KernelTimer, WalkRecording, TileSchedule (the
+ * cost-ordered launch), Flight (a frame in flight: its stream and per-pixel buffers; Engine::flight[0] is the one of a
+ * process that renders one frame at a time), CopyLane (the device's part of the pipelined read-back) and ImageStreaming (a
+ * frame read back in bands); ImageRing - the page-locked host images of the pipelined read-back and their tickets - exists
+ * once per process (gImageRing), whatever the number of
  * engines.  gfx950 only.
  */
 #ifndef SOLR_ENGINE_H
@@ -299,7 +303,7 @@ struct NodeList
     unsigned offStart = 0;             /* ints of the arena: start indices */
     int ordered = 0;                /* sign-free slab test allowed on it */
     bool tight = false;             /* the thin copy behind it is up to date */
-    std::vector<int> refitLevels;   /* [offset, count] per height, offsets into Engine::refitPlan (ints) */
+    std::vector<int> refitLevels;   /* [offset, count] per height, offsets into Rotation::refitPlan (ints) */
 
     void reset() { *this = NodeList(copies, lists); }
     unsigned nodes() const { return (unsigned)lists * (unsigned)nb; }
@@ -325,6 +329,262 @@ struct NodeList
     }
 };
 
+/* ---- the resident scene: what the device holds of it and what may be done with it ------------------------------------
+ * Records cut by who writes them.  Every validity flag is assigned in the record's named transitions below and in the
+ * three functions that derive state from the scene (retagPrimitives, deriveList, buildRefitPlan), nowhere else; a
+ * default-constructed record is the state after initialize_scene, and release() gives the buffers back and returns to it. */
+
+/* The arena of the geometry (scene_layout.h) against its host images.  Written by flushGeometry / appendFreeLists; told
+ * that it is out of date by whoever changes a host image (retagPrimitives, h2d_lightInformation).  Part of Scene: no
+ * transition moves its flags without moving the lists' or the rotation's. */
+struct Arena
+{
+    DeviceBuffer geometry;
+    unsigned offPrims = 0, offLights = 0; /* float4 rows of the arena */
+    unsigned rowsFixed = 0;               /* rows of the arena in front of the order-free lists */
+    bool geometryDirty = true;            /* a host image changed: laid out and uploaded again by the next flushGeometry */
+    bool deviceAhead = false;             /* the arena has moved on from the host images (rotations on the device) */
+    void layOutAgain() { geometryDirty = true; }
+};
+/* The state of the order-free lists (Scene::orderFree).  Lists built on the device stay there and go into the arena with
+ * a device-to-device copy (freeStage, until the next flushGeometry); orderFree's host image is filled from the arena
+ * when somebody needs it (ensureHostFreeLists: the refit plan of a rotated scene, a second layout). */
+struct OrderFreeState
+{
+    int freeCountdown = 0;     /* renders until the order-free lists are built (0: not scheduled) */
+    bool freeHostValid = true; /* orderFree's host image is the lists (false: they are staged or in the arena alone) */
+    bool freeDirty = false;    /* the staged lists are to be added to an arena that is otherwise up to date */
+    SolrDeviceLists freeStage;
+    bool freeStale = false;    /* rotated on the device since it was built: not refitted, not walked */
+    bool sortedFree = false;   /* the copy of the order-free lists with sorted bounds is up to date (deriveList) */
+    /* the buffers the device builder left its lists in: rows and start indices until they are in the arena, the origins
+     * (only the refit plan reads them) until the host has them or the lists go */
+    void dropStage(bool originToo)
+    {
+        if (freeStage.rows)
+            (void)hipFree(freeStage.rows);
+        if (freeStage.start)
+            (void)hipFree(freeStage.start);
+        freeStage.rows = nullptr;
+        freeStage.start = nullptr;
+        if (originToo && freeStage.origin)
+        {
+            (void)hipFree(freeStage.origin);
+            freeStage.origin = nullptr;
+        }
+    }
+};
+/* Rotation on the device (solr_hip_rotate_primitives): what to refit, in which order.  Written by solr_hip_set_movable,
+ * buildRefitPlan and the transitions of Scene. */
+struct Rotation
+{
+    DeviceBuffer movable, refitPlan;
+    DeviceBuffer enclosesFlag;     /* k_listEncloses' answer */
+    int nbMovable = -1;            /* flags uploaded for that many primitives, -1: none */
+    bool refitReady = false;       /* refitPlan is the plan of the lists as they are (buildRefitPlan) */
+    bool refitPlanPending = false; /* the lists changed: the plan is made when the first rotation asks (canRotateOne) */
+    bool exactStale = false;       /* the exact list has not been refitted since the last rotation */
+    float exactStaleViewDistance = 0.f;
+    int nbDeviceRotations = 0;
+};
+/* The scene proper: what h2d_scene replaces and finalize_scene drops, with the arena it is resident in. */
+struct Scene
+{
+    /* the node lists: the reference's as uploaded; the walk-order list (chains collapsed, siblings grouped, inner nodes
+     * that hardly cull pruned) with its thin copy; the eight order-free lists, one per direction octant - the leaves of
+     * the scene under a surface-area hierarchy of our own (buildFreeOrderLists) - with thin and sorted copies */
+    NodeList exact = NodeList(1, 1), walk = NodeList(2, 1), orderFree = NodeList(3, solrdev::ORDER_FREE_LISTS);
+    std::vector<float4> hostPrims; /* host image of the primitive records */
+    int nbPrimitives = 0;
+    DeviceBuffer lamps;
+    int nbLamps = 0;
+    int nested = 1;
+    /* the walk-order list as the arena holds it: every inner node contains its children, every leaf its primitives
+     * (checked at h2d_scene and again after every rotation on the device; lampCutoffUsable, tightListsFor) */
+    bool walkEncloses = false;
+    OrderFreeState lists;
+    Rotation rotation;
+    Arena arena;
+
+    /* h2d_scene has new host images of the lists and the primitives (swapped in by the caller): nothing that was made
+     * from the old ones holds.  The movable flags go, the count of rotations stays; the arena follows with
+     * retagPrimitives (layOutAgain) */
+    void newGeometry(int nested_, bool walkEncloses_, int freeCountdown_)
+    {
+        nested = nested_;
+        walkEncloses = walkEncloses_;
+        rotation.refitReady = false;
+        rotation.exactStale = false;
+        rotation.refitPlanPending = true;
+        rotation.nbMovable = -1;
+        arena.deviceAhead = false;
+        orderFree.reset();
+        lists.freeCountdown = freeCountdown_;
+        lists.freeHostValid = true;
+        lists.freeDirty = false;
+        lists.dropStage(true);
+        lists.freeStale = false;
+    }
+    /* a frame has been rendered: true when the order-free lists are due now (maybeBuildOrderFreeLists) */
+    bool orderFreeDue() { return lists.freeCountdown > 0 && --lists.freeCountdown == 0; }
+    /* ... and no walk would take them yet (orderFreeListsUsable): asked again with the next frame */
+    void orderFreeAskAgain() { lists.freeCountdown = 1; }
+    /* maybeBuildOrderFreeLists has built them; stayed: on the device (lists.freeStage), fromArena: made from an arena
+     * that is up to date.  They join the arena with the next flushGeometry: added behind what it holds when both, else
+     * laid out and uploaded again */
+    void orderFreeBuilt(const NodeList &built, bool stayed, bool fromArena)
+    {
+        orderFree = built;
+        lists.freeHostValid = !stayed;
+        lists.freeStale = false;
+        rotation.refitReady = false;
+        rotation.refitPlanPending = true; /* 8-12 ms for 100 k primitives: only scenes that are rotated on the device pay them */
+        if (stayed && fromArena)
+            lists.freeDirty = true;
+        else
+            arena.layOutAgain();
+    }
+    /* appendFreeLists / flushGeometry: the arena holds the staged lists / everything the host images hold */
+    void listsAppended()
+    {
+        lists.dropStage(false);
+        lists.freeDirty = false;
+    }
+    void arenaFlushed()
+    {
+        arena.geometryDirty = false;
+        lists.freeDirty = false;
+    }
+    /* ensureHostFreeLists / pullGeometry: the host images are what the device holds again (the next layout takes the
+     * lists from their host image) */
+    void hostListsPulled()
+    {
+        lists.freeHostValid = true;
+        lists.dropStage(true);
+    }
+    void hostImagesPulled() { arena.deviceAhead = false; }
+    /* rotatePrimitivesOne has queued a rotation and the refit of the walk-order list (listsFollow: of the order-free
+     * lists too; without a plan for them, rotated scenes walk the reference's order until the next upload); the
+     * reference's own list follows when somebody needs it (refreshExactList) */
+    void rotationQueued(bool listsFollow, float viewDistance)
+    {
+        if (!listsFollow)
+            lists.freeStale = orderFree.nb > 0;
+        rotation.exactStale = true;
+        rotation.exactStaleViewDistance = viewDistance;
+    }
+    void exactRefitted() { rotation.exactStale = false; }
+    /* ... and has served it; walkHolds: the refitted walk-order list passed the check again, landed: without an error */
+    void rotationServed(bool walkHolds, bool landed)
+    {
+        walkEncloses = walkHolds;
+        if (landed)
+        {
+            arena.deviceAhead = true;
+            ++rotation.nbDeviceRotations;
+        }
+    }
+    /* finalize_scene */
+    void release()
+    {
+        lists.dropStage(true);
+        for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag})
+            solreng::release(*b);
+        *this = Scene();
+    }
+};
+/* Lights (h2d_lightInformation): their records lie in the arena behind the primitives'.  h2d_scene keeps them,
+ * finalize_scene drops them. */
+struct Lights
+{
+    std::vector<float4> hostLights;
+    int nbLights = 0;
+};
+/* texture tables of a textured material: checked against the atlas (checkTextureTables) */
+struct TextureUse
+{
+    int material;
+    long texels;     /* bytes of the diffuse map: x * y * depth */
+    long offsets[7]; /* diffuse, normal, bump, specular, reflection, transparency, ambient occlusion; -1 unused */
+};
+/* Materials (h2d_materials) */
+struct Materials
+{
+    DeviceBuffer table; /* NB_MAX_MATERIALS + 1 hot records, then as many cold ones (offMatCold, float4 rows) */
+    unsigned offMatCold = 0;
+    int nbMaterials = 0;
+    std::vector<int> materialTags;      /* PRIM_* bits per material id */
+    std::vector<float> materialAverage; /* (r + g + b) / 3.f per material id (plane colour key, GI:561) */
+    std::vector<TextureUse> textureUses;
+    void release()
+    {
+        solreng::release(table);
+        *this = Materials();
+    }
+};
+/* Textures (h2d_textures): the atlas, and whether the materials' texture tables have been checked against it - before the
+ * first frame that follows either upload (checkTextureTables; kept here: the atlas is what the check protects) */
+struct Textures
+{
+    DeviceBuffer atlas;
+    size_t atlasBytes = 0;
+    bool textureTablesChecked = false;
+    void release()
+    {
+        solreng::release(atlas);
+        *this = Textures();
+    }
+};
+/* Randoms (h2d_randoms, solr_hip_h2d_randoms_sized; with a communicator rank 0's: shareRandoms) */
+struct Randoms
+{
+    DeviceBuffer values;
+    long nbRandoms = 0;
+    float randomsReach = 0.f; /* max |randoms[i]|, i < 356: what the 256 taps can read */
+    void release()
+    {
+        solreng::release(values);
+        *this = Randoms();
+    }
+};
+/* What retagPrimitives derives from the primitives and the materials, after every upload of either */
+struct SceneFacts
+{
+    bool primsContained = false; /* every primitive lies inside its leaf's box */
+    bool opaqueShadows = false;  /* no transparent primitive, no textured plane */
+    bool plainPlanes = false;    /* the scene holds a plain axis plane: thin copies are worth making (tightenList) */
+    float sceneExtent = 1.f;     /* max |coordinate| + |size| over the primitives, at least 1 */
+    int sceneFeatures = F_ALL & ~F_FULL; /* rt_device.h enum Feature */
+};
+/* The kernel timer (solr_hip_enable_timing: Engine::timing; solr_launch.hip, solr_diag.hip) */
+struct KernelTimer
+{
+    unsigned timingTick = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    double timedMs = 0.0;
+    int timedLaunches = 0;
+    std::vector<float> kernelSamples, intervalSamples; /* per timed launch: its duration; end-to-end gap to the one before */
+};
+/* The walk's own ceiling (solr_hip_walk_bound): the next frame records its walks; how that frame was launched
+ * (solr_launch.hip, solr_diag.hip) */
+struct WalkRecording
+{
+    DeviceBuffer walkRecords, walkVisits;
+    bool recordNext = false;
+    bool recorded = false;
+    unsigned recordGrid = 0;
+    size_t recordLds = 0;
+    int recordVariant = -1; /* row of solrrows::ROWS (renderer.h) */
+    bool recordDeep = false;
+    SceneArgs recordScene = {};
+    void release()
+    {
+        solreng::release(walkRecords);
+        solreng::release(walkVisits);
+        *this = WalkRecording();
+    }
+};
+
 struct Engine
 {
     bool initialized = false;
@@ -332,87 +592,49 @@ struct Engine
     int errorCode = 0;
     std::string errorText;
 
-    /* scene planes */
-    /* two arenas (scene_layout.h) and their host images */
-    DeviceBuffer geometry, materials, textures, randoms, lamps;
-    std::vector<float4> hostPrims, hostLights;
-    /* the node lists: the reference's as uploaded; the walk-order list (chains collapsed, siblings grouped, inner nodes
-     * that hardly cull pruned) with its thin copy; the eight order-free lists, one per direction octant - the leaves of
-     * the scene under a surface-area hierarchy of our own (buildFreeOrderLists) - with thin and sorted copies */
-    NodeList exact = NodeList(1, 1), walk = NodeList(2, 1), orderFree = NodeList(3, solrdev::ORDER_FREE_LISTS);
-    int freeCountdown = 0; /* renders until the order-free lists are built (0: not scheduled) */
-    /* lists built on the device stay there and go into the arena with a device-to-device copy (freeStage, until the
-     * next flushGeometry); orderFree's host image is filled from the arena when somebody needs it (ensureHostFreeLists:
-     * the refit plan of a rotated scene, a second layout) */
-    bool freeHostValid = true;
-    bool freeDirty = false;  /* the staged lists are to be added to an arena that is otherwise up to date */
-    unsigned rowsFixed = 0;  /* rows of the arena in front of the order-free lists */
-    SolrDeviceLists freeStage;
-    bool freeStale = false;     /* rotated on the device since it was built: not refitted, not walked */
-    bool primsContained = false; /* every primitive lies inside its leaf's box (retagPrimitives) */
-    bool opaqueShadows = false;  /* no transparent primitive, no textured plane (retagPrimitives) */
-    /* the walk-order list as the arena holds it: every inner node contains its children, every leaf its primitives
-     * (checked at h2d_scene and again after every rotation on the device; lampCutoffUsable) */
-    bool walkEncloses = false;
-    /* the thin copies of the walk-order list and of the order-free lists (tightenList; rt_device.h tightRay) */
-    bool plainPlanes = false;    /* the scene holds a plain axis plane: thin copies are worth making (retagPrimitives) */
-    float sceneExtent = 1.f;     /* max |coordinate| + |size| over the primitives, at least 1 */
-    bool sortedFree = false;                      /* the copy of the order-free lists with sorted bounds is up to date */
+    /* the knobs: set by the host, they outlive finalize_scene (no release() resets them; initialize_scene hands engine
+     * 0's to the engines of further devices) */
+    int variant = VARIANT_AUTOMATIC; /* enum Variant */
+    bool grouping = true; /* groupSiblings(); VARIANT_NO_GROUPING turns it off for A/B measurements */
     /* bounce rays on the order-free lists, checked (rt_device.h closestHitWalk): -1 the engine decides per frame
      * (shortRayListsChoice: with frames in flight), 0 / 1 forced */
     int shortRayListsMode = -1;
-    std::vector<int> materialTags; /* PRIM_* bits per material id */
-    /* texture tables of the textured materials and the size of the uploaded atlas: checked against each other
-     * before the first frame that follows either upload (checkTextureTables) */
-    struct TextureUse
-    {
-        int material;
-        long texels;      /* bytes of the diffuse map: x * y * depth */
-        long offsets[7];  /* diffuse, normal, bump, specular, reflection, transparency, ambient occlusion; -1 unused */
-    };
-    std::vector<TextureUse> textureUses;
-    size_t atlasBytes = 0;
-    bool textureTablesChecked = false;
-    std::vector<float> materialAverage; /* (r + g + b) / 3.f per material id (plane colour key, GI:561) */
-    int sceneFeatures = F_ALL & ~F_FULL; /* rt_device.h enum Feature, recomputed with the tags */
-    unsigned offPrims = 0, offLights = 0;
-    unsigned offMatCold = 0;
-    bool geometryDirty = true;
-    int nbPrimitives = 0, nbLights = 0, nbLamps = 0, nbMaterials = 0;
-    int nested = 1;
-    long nbRandoms = 0;
+    int flights = 1;         /* how many frames in flight were asked for (solr_hip_set_frames_in_flight; in use: activeFlights) */
+    bool tileClocks = false; /* diagnostics, solr_hip_enable_tile_clocks */
+    int timing = 0;          /* 0 off, n: every n-th launch is bracketed with events (KernelTimer) */
+    /* (and sched.mode, TileSchedule) */
+
+    /* the resident scene */
+    Scene scene;
+    Lights lights;
+    Materials materials;
+    Textures textures;
+    Randoms randoms;
+    SceneFacts facts;
 
     DeviceBuffer counters, tileClock;
     /* ambient occlusion across strips: the depths of the neighbours' rows a host hands over itself (the ones traded over
      * RCCL: Flight) */
     DeviceBuffer haloGivenAbove, haloGivenBelow; /* solr_hip_set_depth_halo */
     int haloSuppliedAbove = 0, haloSuppliedBelow = 0; /* rows handed over by solr_hip_set_depth_halo (0: none) */
-    float randomsReach = 0.f;                          /* max |randoms[i]|, i < 356: what the 256 taps can read */
     int haloWanted = -1; /* rows beyond a strip the last frame's post-processing reached (0: none; -1: no frame here) */
     /* the frames in flight: their streams and per-pixel buffers.  flight[0]'s stream is also the one uploads and list
      * kernels run on (sceneStream) */
     Flight flight[MAX_FLIGHTS];
-    int flights = 1;            /* how many were asked for (solr_hip_set_frames_in_flight; in use: activeFlights) */
     bool ownStream = false;     /* flight[0]'s stream is the engine's own (else the caller's: solr_hip_set_stream) */
     bool callerStreams = false; /* the streams of the other flights belong to the caller (solr_hip_set_flight_streams) */
     int current = 0;            /* flight of the last render */
     unsigned frameSerial = 0;
     TileSchedule sched;
     unsigned lastSerial = 0;
-    bool tileClocks = false; /* diagnostics, solr_hip_enable_tile_clocks */
     int nbTilesTimed = 0;
     void *boundBitmap = nullptr;
     int width = 0, height = 0;       /* full image */
     int firstRow = 0, nbRows = -1;   /* strip; nbRows < 0 -> full frame, 0 -> this process renders no row */
     int allocW = 0, allocRows = 0;
 
-    /* timing */
-    int timing = 0; /* 0 off, n: every n-th launch is bracketed with events */
-    unsigned timingTick = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    double timedMs = 0.0;
-    int timedLaunches = 0;
-    std::vector<float> kernelSamples, intervalSamples; /* per timed launch: its duration; end-to-end gap to the one before */
+    KernelTimer timer;
+    WalkRecording recording;
 
     CopyLane copyLane;        /* this device's part of the pipelined read-back (the ring of host images: gImageRing) */
     ImageStreaming streaming; /* the read-back of a frame taken one at a time, in bands */
@@ -424,30 +646,6 @@ struct Engine
      * its instantiation with F_DEEP / F_STACK / F_STREAM, streamed (1 / 0) and in how many bands, cost-ordered (1 / 0) and
      * the bands of that order */
     int lastFrame[6] = {-1, -1, 0, 0, 0, 0};
-
-    /* device-side rotation (solr_hip_rotate_primitives): what to refit, in which order */
-    DeviceBuffer movable, refitPlan;
-    DeviceBuffer enclosesFlag; /* k_listEncloses' answer */
-    int nbMovable = -1;                 /* flags uploaded for that many primitives, -1: none */
-    bool refitReady = false;
-    bool refitPlanPending = false;      /* the lists changed: the plan is made when the first rotation asks (ensureRefitPlan) */
-    bool exactStale = false;            /* the exact list has not been refitted since the last rotation */
-    float exactStaleViewDistance = 0.f;
-    bool deviceAhead = false;           /* the arena has moved on from the host images */
-    int nbDeviceRotations = 0;
-
-    int variant = VARIANT_AUTOMATIC; /* enum Variant */
-    bool grouping = true; /* groupSiblings(); VARIANT_NO_GROUPING turns it off for A/B measurements */
-
-    /* the walk's own ceiling (solr_hip_walk_bound): the next frame records its walks; how that frame was launched */
-    DeviceBuffer walkRecords, walkVisits;
-    bool recordNext = false;
-    bool recorded = false;
-    unsigned recordGrid = 0;
-    size_t recordLds = 0;
-    int recordVariant = -1; /* row of solrrows::ROWS (renderer.h) */
-    bool recordDeep = false;
-    SceneArgs recordScene;
 };
 
 /* One Engine per device this process renders on.  The reference drives occupancyParameters.x devices from ONE host
@@ -585,7 +783,7 @@ inline int stripRows()
 
 
 /* ---- what the parts ask of each other (defined in the file named) ---------------------------------------------------- */
-/* solr_scene.hip: the resident scene - uploads (one engine's share of the boundary's h2d_* calls), its lists, rotation */
+/* solr_uploads.hip: one engine's share of the boundary's h2d_* calls */
 void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primitives, int nbPrimitives, Lamp *lamps, int nbLamps);
 void h2dMaterialsOne(Material *materials, int nbActiveMaterials);
 void h2dRandomsOne(float *randoms);
@@ -593,18 +791,25 @@ void h2dRandomsSizedOne(const float *randoms, long count);
 void h2dTexturesOne(int activeTextures, TextureInfo *textureInfos);
 void h2dLightInformationOne(LightInformation *lightInformation, int lightInformationSize);
 void setMovableOne(const unsigned char *flags, int nbPrimitives);
-bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
-int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
 void checkTextureTables();
+/* solr_arena.hip: the arena the scene is resident in, its lists, what a frame is told of them */
 void maybeBuildOrderFreeLists();
 void flushGeometry();
-void refreshExactList();
-void dropFreeStage(bool originToo);
+void pullGeometry();
+void ensureHostFreeLists();
+void buildLeafRecords();
+bool listEnclosesInArena(const NodeList &list);
+ListKnobs listKnobs();
+PruneDecider pruneDecider();
 bool orderFreeListsUsable();
 bool lampCutoffUsable();
 bool shortRayListsChoice();
 SceneArgs prepareScene(const SceneInfo &sceneInfo, bool exactNodes);
 bool deepNodeList(const SceneArgs &S);
+/* solr_rotation.hip: rotation and refit on the device */
+bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
+int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
+void refreshExactList();
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */
 void allocateFrame();
 int neededFeatures(const SceneInfo &sceneInfo, bool full);

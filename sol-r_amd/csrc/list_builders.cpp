@@ -817,7 +817,7 @@ bool listEnclosesOnHost(const std::vector<float4> &rows, const std::vector<int> 
     return encloses;
 }
 
-/* What a rotation on the device refits and in which order (solr_scene.hip buildRefitPlan): the nodes of each list by
+/* What a rotation on the device refits and in which order (solr_rotation.hip buildRefitPlan): the nodes of each list by
  * height, children before parents.  `plan`: the entries of all three lists (sign bit: a grouping node, seeded with
  * infinities); per list [offset into plan, count] for every height.  `origin` / `freeOrigin`: per node of the walk-order
  * list and of the eight order-free lists (one behind the other: a forest) the node of the reference's list it is;

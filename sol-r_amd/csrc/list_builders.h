@@ -1,7 +1,8 @@
 /*
  * list_builders.h - the host builders of the engine's node lists (list_builders.cpp): plain C++17 over std::vector, no
- * engine state, no environment, no HIP call.  solr_scene.hip calls them for the walk-order list of every upload, for the
- * order-free lists where the device builders (solr_lists.hip) are switched off or decline, and for the refit plan; they
+ * engine state, no environment, no HIP call.  The engine's scene units (solr_uploads.hip,
+ * solr_arena.hip, solr_rotation.hip) call them for the walk-order list of every upload, for the order-free lists where the
+ * device builders (solr_lists.hip) are switched off or decline, and for the refit plan; they
  * are the reference the device builders are held to (tests/test_lists_gpu.py), and tests/list_builders_check.cpp runs
  * them on their own.
  * A node list: two float4 rows per node, { min.xyz, max.z } { max.xy, nbPrimitives, skip } (scene_layout.h); `start`: the
@@ -33,7 +34,7 @@ inline float bitsf(int v)
     return f;
 }
 
-/* the facts of a primitive record (scene_layout.h, device code) that listEnclosesOnHost reads; solr_scene.hip holds them
+/* the facts of a primitive record (scene_layout.h, device code) that listEnclosesOnHost reads; solr_uploads.hip holds them
  * to that header */
 enum ListBuilderPrimRow
 {

@@ -47,7 +47,7 @@ int residentScene(const SceneInfo &sceneInfo, bool exactNodes, SceneArgs *S, int
         return -1;
     quiesce();
     HIPCHECK(hipSetDevice(g.device));
-    ARGCHECK(g.materials.ptr != nullptr, "solr_hip_probe: no materials uploaded");
+    ARGCHECK(g.materials.table.ptr != nullptr, "solr_hip_probe: no materials uploaded");
     if (!ok())
         return -1;
     checkTextureTables();
@@ -111,13 +111,13 @@ void lastFrame(int out[6])
 }
 
 /* solr_hip_probe_list_copy (include/solr_hip_probes.h says what `list` and `what` select): from the arena as
- * solr_scene.hip deriveList left it */
+ * solr_arena.hip deriveList left it */
 int listCopy(int list, int what, void *out, int capacity)
 {
     if (!ready("solr_hip_probe_list_copy"))
         return -1;
     ARGCHECK(list >= 0 && list <= 2 && what >= 0 && what <= 4, "solr_hip_probe_list_copy: no such list or copy");
-    ARGCHECK(g.geometry.ptr != nullptr || g.geometryDirty, "solr_hip_probe_list_copy: no scene uploaded");
+    ARGCHECK(g.scene.arena.geometry.ptr != nullptr || g.scene.arena.geometryDirty, "solr_hip_probe_list_copy: no scene uploaded");
     if (!ok())
         return -1;
     HIPCHECK(hipSetDevice(g.device));
@@ -125,10 +125,10 @@ int listCopy(int list, int what, void *out, int capacity)
     if (list == 1)
         refreshExactList();
     quiesce();
-    if (!ok() || !g.geometry.ptr)
+    if (!ok() || !g.scene.arena.geometry.ptr)
         return -1;
-    const NodeList &L = list == 0 ? g.walk : (list == 1 ? g.exact : g.orderFree);
-    const unsigned nodes = (list == 2 && g.freeStale) ? 0u : L.nodes();
+    const NodeList &L = list == 0 ? g.scene.walk : (list == 1 ? g.scene.exact : g.scene.orderFree);
+    const unsigned nodes = (list == 2 && g.scene.lists.freeStale) ? 0u : L.nodes();
     size_t at = 0, count = 0, unit = 16; /* where (bytes of the arena), how many, of which size */
     switch (what)
     {
@@ -139,7 +139,7 @@ int listCopy(int list, int what, void *out, int capacity)
         at = (size_t)L.offThin() * 16, count = (L.copies > 1 && L.tight) ? 2 * (size_t)nodes : 0;
         break;
     case 2:
-        at = (size_t)L.offSorted() * 16, count = (list == 2 && L.copies > 2 && g.sortedFree) ? 2 * (size_t)nodes + 2 : 0;
+        at = (size_t)L.offSorted() * 16, count = (list == 2 && L.copies > 2 && g.scene.lists.sortedFree) ? 2 * (size_t)nodes + 2 : 0;
         break;
     case 3:
         at = (size_t)L.offLeaf * 16, count = 4 * (size_t)nodes;
@@ -153,11 +153,11 @@ int listCopy(int list, int what, void *out, int capacity)
     if (!out)
         return (int)count;
     ARGCHECK(count <= (size_t)(capacity < 0 ? 0 : capacity), "solr_hip_probe_list_copy: capacity too small");
-    ARGCHECK(at + count * unit <= g.geometry.bytes, "solr_hip_probe_list_copy: the copy lies outside the arena");
+    ARGCHECK(at + count * unit <= g.scene.arena.geometry.bytes, "solr_hip_probe_list_copy: the copy lies outside the arena");
     if (!ok())
         return -1;
     if (count)
-        HIPCHECK(hipMemcpy(out, (const char *)g.geometry.ptr + at, count * unit, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(out, (const char *)g.scene.arena.geometry.ptr + at, count * unit, hipMemcpyDeviceToHost));
     return ok() ? (int)count : -1;
 }
 
@@ -170,7 +170,7 @@ int walkOffer(const SceneInfo &sceneInfo, bool exactNodes, int out[8])
     hipStream_t stream;
     if (residentScene(sceneInfo, exactNodes, &S, &features, &deep, &stream) != 0)
         return -1;
-    const float margin = g.sceneExtent * (1.f / 1024.f), extent = g.sceneExtent;
+    const float margin = g.facts.sceneExtent * (1.f / 1024.f), extent = g.facts.sceneExtent;
     out[0] = S.tightLists, out[1] = S.sortedLists, out[2] = S.nbBoxesFree, out[3] = S.opaqueShadows, out[4] = S.shortRayLists;
     out[5] = S.nbBoxes;
     memcpy(&out[6], &margin, 4);
@@ -194,20 +194,20 @@ void solr_hip_walk_bound_lists(unsigned long long out[6])
         memcpy(out, walkLists, sizeof(walkLists));
 }
 
-/* a frame whose walks are recorded: the records stay in g.walkRecords (a gigabyte for a 1080p frame) */
+/* a frame whose walks are recorded: the records stay in g.recording.walkRecords (a gigabyte for a 1080p frame) */
 static int recordFrame(const SceneInfo *sceneInfo, const vec4i *objects, const PostProcessingInfo *postProcessingInfo,
                        const float origin[3], const float direction[3], const float angles[4], const char *who)
 {
     quiesce();
     HIPCHECK(hipSetDevice(g.device));
-    g.recorded = false;
-    g.recordNext = true;
+    g.recording.recorded = false;
+    g.recording.recordNext = true;
     if (!ok())
         return -1;
     renderImpl(*sceneInfo, *objects, *postProcessingInfo, origin, direction, angles, false, nullptr);
-    g.recordNext = false;
+    g.recording.recordNext = false;
     HIPCHECK(hipStreamSynchronize(g.flight[g.current].stream));
-    if (!ok() || !g.recorded)
+    if (!ok() || !g.recording.recorded)
     {
         if (ok())
             setError(-1, "solr_hip_walk_bound: the frame was not recorded", __FILE__, __LINE__);
@@ -217,27 +217,28 @@ static int recordFrame(const SceneInfo *sceneInfo, const vec4i *objects, const P
     return 0;
 }
 
-/* the first `grid` workgroup slots of g.walkRecords replayed `repeats` times with `ldsBytes` of dynamic LDS a wave */
+/* the first `grid` workgroup slots of g.recording.walkRecords replayed `repeats` times with `ldsBytes` of dynamic LDS a wave */
 static int replayRecords(unsigned grid, size_t ldsBytes, int repeats, double ms[3], unsigned long long stats[4], bool lists)
 {
     typedef WalkBoundFn BoundFn;
-    ARGCHECK(g.recordVariant >= 0 && g.recordVariant < solrrows::LEAN_ROWS && g.walkRecords.ptr && grid > 0 &&
-                 (size_t)grid * SOLR_WALK_SLOT_BYTES <= g.walkRecords.bytes,
+    ARGCHECK(g.recording.recordVariant >= 0 && g.recording.recordVariant < solrrows::LEAN_ROWS && g.recording.walkRecords.ptr && grid > 0 &&
+                 (size_t)grid * SOLR_WALK_SLOT_BYTES <= g.recording.walkRecords.bytes,
              "solr_hip_walk_replay: no recorded frame, or more workgroups than its buffer holds");
     if (!ok())
         return -1;
-    const BoundFn fn = solrrows::walkBound(g.recordVariant, solrrows::ROWS[g.recordVariant].features | (g.recordDeep ? F_DEEP : 0));
+    const int row = g.recording.recordVariant;
+    const BoundFn fn = solrrows::walkBound(row, solrrows::ROWS[row].features | (g.recording.recordDeep ? F_DEEP : 0));
     ARGCHECK(fn != nullptr, "solr_hip_walk_bound: no replay instantiation for this row");
     if (!ok())
         return -1;
-    reserve(g.walkVisits, (size_t)grid * WAVE * sizeof(unsigned) + 64);
+    reserve(g.recording.walkVisits, (size_t)grid * WAVE * sizeof(unsigned) + 64);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHECK(hipEventCreate(&e0));
     HIPCHECK(hipEventCreate(&e1));
     if (!ok())
         return -1;
     const hipStream_t stream = g.flight[g.current].stream;
-    unsigned *visits = (unsigned *)g.walkVisits.ptr;
+    unsigned *visits = (unsigned *)g.recording.walkVisits.ptr;
     unsigned *skipped = visits + (size_t)grid * WAVE;
     double sum = 0.0, best = 1.0e30;
     repeats = repeats < 1 ? 1 : repeats;
@@ -245,7 +246,7 @@ static int replayRecords(unsigned grid, size_t ldsBytes, int repeats, double ms[
     {
         HIPCHECK(hipMemsetAsync(skipped, 0, sizeof(unsigned), stream));
         HIPCHECK(hipEventRecord(e0, stream));
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(WAVE), ldsBytes, stream, g.recordScene, (const char *)g.walkRecords.ptr,
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(WAVE), ldsBytes, stream, g.recording.recordScene, (const char *)g.recording.walkRecords.ptr,
                            visits, skipped);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipEventRecord(e1, stream));
@@ -263,7 +264,7 @@ static int replayRecords(unsigned grid, size_t ldsBytes, int repeats, double ms[
         std::vector<unsigned> v((size_t)grid * WAVE + 1);
         HIPCHECK(hipMemcpy(v.data(), visits, v.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
         std::vector<int> heads((size_t)grid * 4);
-        HIPCHECK(hipMemcpy2D(heads.data(), 16, g.walkRecords.ptr, SOLR_WALK_SLOT_BYTES, 16, grid, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy2D(heads.data(), 16, g.recording.walkRecords.ptr, SOLR_WALK_SLOT_BYTES, 16, grid, hipMemcpyDeviceToHost));
         if (const char *dump = getenv("SOLR_HIP_WALK_BOUND_DUMP"))
         {
             /* diagnostics (tools/longest_wave.py): leaf entries per lane and walks per workgroup of the replay */
@@ -283,7 +284,7 @@ static int replayRecords(unsigned grid, size_t ldsBytes, int repeats, double ms[
         {
             /* which list each recorded walk took (solr_hip_walk_bound_lists) */
             std::vector<int> kinds((size_t)grid * 4 * (SOLR_WALK_SLOTS + 1));
-            HIPCHECK(hipMemcpy2D(kinds.data(), 16 * (SOLR_WALK_SLOTS + 1), g.walkRecords.ptr, SOLR_WALK_SLOT_BYTES,
+            HIPCHECK(hipMemcpy2D(kinds.data(), 16 * (SOLR_WALK_SLOTS + 1), g.recording.walkRecords.ptr, SOLR_WALK_SLOT_BYTES,
                                  16 * (SOLR_WALK_SLOTS + 1), grid, hipMemcpyDeviceToHost));
             for (int i = 0; i < 6; ++i)
                 walkLists[i] = 0;
@@ -333,13 +334,13 @@ int solr_hip_walk_bound(const SceneInfo *sceneInfo, const vec4i *objects, const 
         return -1;
     if (recordFrame(sceneInfo, objects, postProcessingInfo, origin, direction, angles, "solr_hip_walk_bound") != 0)
         return -1;
-    const int rc = replayRecords(g.recordGrid, g.recordLds, repeats, ms, stats, true);
+    const int rc = replayRecords(g.recording.recordGrid, g.recording.recordLds, repeats, ms, stats, true);
     if (!keepWalkRecords)
     {
         /* the buffers are a gigabyte for a 1080p frame: given back at once */
-        release(g.walkRecords);
-        release(g.walkVisits);
-        g.recorded = false;
+        release(g.recording.walkRecords);
+        release(g.recording.walkVisits);
+        g.recording.recorded = false;
     }
     return rc;
 }
@@ -359,9 +360,9 @@ int solr_hip_walk_records_info(unsigned long long info[4])
 {
     if (!ready("solr_hip_walk_records_info") || !info)
         return -1;
-    info[0] = g.recorded ? g.recordGrid : 0;
+    info[0] = g.recording.recorded ? g.recording.recordGrid : 0;
     info[1] = SOLR_WALK_SLOT_BYTES;
-    info[2] = g.recordLds;
+    info[2] = g.recording.recordLds;
     info[3] = SOLR_WALK_SLOTS;
     return 0;
 }
@@ -370,24 +371,24 @@ int solr_hip_walk_records_copy(void *host, unsigned grid, int toDevice)
 {
     if (!ready("solr_hip_walk_records_copy"))
         return -1;
-    ARGCHECK(host && grid > 0 && g.recorded, "solr_hip_walk_records_copy: no recorded frame");
+    ARGCHECK(host && grid > 0 && g.recording.recorded, "solr_hip_walk_records_copy: no recorded frame");
     if (!ok())
         return -1;
     const size_t bytes = (size_t)grid * SOLR_WALK_SLOT_BYTES;
     HIPCHECK(hipSetDevice(g.device));
     if (toDevice)
     {
-        reserve(g.walkRecords, bytes);
+        reserve(g.recording.walkRecords, bytes);
         if (!ok())
             return -1;
-        HIPCHECK(hipMemcpy(g.walkRecords.ptr, host, bytes, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(g.recording.walkRecords.ptr, host, bytes, hipMemcpyHostToDevice));
     }
     else
     {
-        ARGCHECK(bytes <= g.walkRecords.bytes, "solr_hip_walk_records_copy: more workgroups than were recorded");
+        ARGCHECK(bytes <= g.recording.walkRecords.bytes, "solr_hip_walk_records_copy: more workgroups than were recorded");
         if (!ok())
             return -1;
-        HIPCHECK(hipMemcpy(host, g.walkRecords.ptr, bytes, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(host, g.recording.walkRecords.ptr, bytes, hipMemcpyDeviceToHost));
     }
     return ok() ? 0 : -1;
 }
@@ -396,25 +397,25 @@ int solr_hip_walk_replay(unsigned grid, long ldsBytes, int repeats, double ms[3]
 {
     if (!ready("solr_hip_walk_replay"))
         return -1;
-    ARGCHECK(g.recorded, "solr_hip_walk_replay: no recorded frame (solr_hip_walk_records_keep(1), then solr_hip_walk_bound)");
+    ARGCHECK(g.recording.recorded, "solr_hip_walk_replay: no recorded frame (solr_hip_walk_records_keep(1), then solr_hip_walk_bound)");
     if (!ok())
         return -1;
     HIPCHECK(hipSetDevice(g.device));
-    return replayRecords(grid, ldsBytes < 0 ? g.recordLds : (size_t)ldsBytes, repeats, ms, stats, false);
+    return replayRecords(grid, ldsBytes < 0 ? g.recording.recordLds : (size_t)ldsBytes, repeats, ms, stats, false);
 }
 
 void solr_hip_walk_records_release(void)
 {
-    release(g.walkRecords);
-    release(g.walkVisits);
-    g.recorded = false;
+    release(g.recording.walkRecords);
+    release(g.recording.walkVisits);
+    g.recording.recorded = false;
 }
 
 void solr_hip_enable_timing(int enable)
 {
     onEveryDevice([&](int) {
         g.timing = enable > 0 ? enable : 0;
-        g.timingTick = 0;
+        g.timer.timingTick = 0;
     });
 }
 
@@ -492,15 +493,15 @@ double solr_hip_kernel_time(int *nbLaunches, int reset)
     if (g.initialized && g.flight[0].stream)
         (void)hipStreamSynchronize(g.flight[0].stream);
     collectEvents();
-    double ms = g.timedMs;
+    double ms = g.timer.timedMs;
     if (nbLaunches)
-        *nbLaunches = g.timedLaunches;
+        *nbLaunches = g.timer.timedLaunches;
     if (reset)
     {
-        g.timedMs = 0.0;
-        g.timedLaunches = 0;
-        g.kernelSamples.clear();
-        g.intervalSamples.clear();
+        g.timer.timedMs = 0.0;
+        g.timer.timedLaunches = 0;
+        g.timer.kernelSamples.clear();
+        g.timer.intervalSamples.clear();
     }
     return ms;
 }
@@ -514,13 +515,13 @@ int solr_hip_timing_samples(float *kernelMs, float *intervalMs, int capacity)
     if (g.initialized && g.flight[0].stream)
         (void)hipStreamSynchronize(g.flight[0].stream);
     collectEvents();
-    const int n = std::min((int)g.kernelSamples.size(), std::max(capacity, 0));
+    const int n = std::min((int)g.timer.kernelSamples.size(), std::max(capacity, 0));
     for (int i = 0; i < n; ++i)
     {
         if (kernelMs)
-            kernelMs[i] = g.kernelSamples[i];
+            kernelMs[i] = g.timer.kernelSamples[i];
         if (intervalMs)
-            intervalMs[i] = g.intervalSamples[i];
+            intervalMs[i] = g.timer.intervalSamples[i];
     }
     return n;
 }
@@ -550,10 +551,10 @@ int solr_hip_get_variant(void)
 
 void solr_hip_memory_usage(unsigned long long bytes[4])
 {
-    bytes[0] = g.geometry.bytes + g.lamps.bytes + g.movable.bytes + g.refitPlan.bytes;
-    bytes[1] = g.materials.bytes;
-    bytes[2] = g.textures.bytes;
-    bytes[3] = g.randoms.bytes;
+    bytes[0] = g.scene.arena.geometry.bytes + g.scene.lamps.bytes + g.scene.rotation.movable.bytes + g.scene.rotation.refitPlan.bytes;
+    bytes[1] = g.materials.table.bytes;
+    bytes[2] = g.textures.atlas.bytes;
+    bytes[3] = g.randoms.values.bytes;
     for (const Flight &set : g.flight) /* (a set's second image and its halo rows are not counted) */
         bytes[3] += set.pp.bytes + set.ids.bytes + set.image[0].bytes + set.deepStack.bytes;
 }
@@ -568,14 +569,14 @@ void solr_hip_memory_usage(unsigned long long bytes[4])
  * not 6), else 0. */
 extern "C" int solr_hip_order_free_nodes(void)
 {
-    return (g.initialized && orderFreeListsUsable()) ? g.orderFree.nb : 0;
+    return (g.initialized && orderFreeListsUsable()) ? g.scene.orderFree.nb : 0;
 }
 
 /* Extension: 1 if the shadow walks of the resident scene take the order-free lists as well (they are in use and
  * nothing in the scene is transparent or a textured plane), else 0. */
 extern "C" int solr_hip_order_free_shadows(void)
 {
-    return (g.initialized && orderFreeListsUsable() && g.opaqueShadows) ? 1 : 0;
+    return (g.initialized && orderFreeListsUsable() && g.facts.opaqueShadows) ? 1 : 0;
 }
 
 /* Extension: 1 if shadow walks in the reference's order leave out the boxes that begin beyond the lamp (rt_device.h

@@ -1,9 +1,10 @@
 /*
  * solr_hip.hip - the C ABI of the MI355X rendering engine (include/solr_hip.h): the reference's ten entry points
  * (CudaRayTracer.h:25-67) once per in-process device, device / stream / strip selection, the life of an engine
- * (initialize_scene ... finalize_scene).  The rest of the engine's host side: engine.h (state), solr_scene.hip (the
- * resident scene and its lists), solr_launch.hip (a frame), solr_post.hip, solr_image_ring.hip, solr_rccl.hip,
- * solr_diag.hip; the kernels: rt_device.h, renderer_kernel.h, rows/.  gfx950 only.
+ * (initialize_scene ... finalize_scene).  The rest of the engine's host side: engine.h (state), solr_uploads.hip,
+ * solr_arena.hip and solr_rotation.hip (the resident scene: its uploads, its arena and lists, rotation on the device),
+ * solr_launch.hip (a frame), solr_post.hip, solr_image_ring.hip, solr_rccl.hip, solr_diag.hip; the kernels: rt_device.h,
+ * renderer_kernel.h, rows/.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -259,44 +260,31 @@ static void finalizeOne()
     g.streaming.release();
     g.sched.release();
     g.current = 0;
-    /* the scene */
-    for (DeviceBuffer *b : {&g.geometry, &g.materials, &g.textures, &g.randoms, &g.lamps, &g.counters, &g.tileClock, &g.movable,
-                            &g.refitPlan, &g.enclosesFlag, &g.walkRecords, &g.walkVisits, &g.haloGivenAbove, &g.haloGivenBelow})
+    for (DeviceBuffer *b : {&g.counters, &g.tileClock, &g.haloGivenAbove, &g.haloGivenBelow})
         release(*b);
+    g.recording.release();
     g.haloSuppliedAbove = g.haloSuppliedBelow = 0;
     if (g.ownStream && g.flight[0].stream)
         (void)hipStreamDestroy(g.flight[0].stream);
     g.flight[0].stream = nullptr;
     g.ownStream = false;
     g.initialized = false;
-    g.refitReady = false;
-    g.refitPlanPending = false;
-    g.exactStale = false;
-    g.deviceAhead = false;
-    g.walkEncloses = false;
-    g.nbMovable = -1;
-    g.nbDeviceRotations = 0;
-    g.nbPrimitives = g.nbLights = g.nbLamps = g.nbMaterials = 0;
     g.allocW = g.allocRows = 0;
     g.boundBitmap = nullptr;
-    g.exact.reset();
-    g.walk.reset();
-    g.orderFree.reset();
-    g.hostPrims.clear();
-    g.hostLights.clear();
-    g.freeHostValid = true;
-    g.freeDirty = false;
-    dropFreeStage(true);
+    /* the scene: every record back to what initialize_scene finds (the knobs stay).  The staged lists go before the
+     * builders' scratch */
+    g.scene.lists.dropStage(true);
     {
         SolrScratchPool &pool = solrScratchPool(); /* the builders' scratch goes with the scene */
         std::lock_guard<std::mutex> nobodyBuilding(pool.busy);
         pool.release();
     }
-    g.freeCountdown = 0;
-    g.freeStale = false;
-    g.materialTags.clear();
-    g.materialAverage.clear();
-    g.geometryDirty = true;
+    g.scene.release();
+    g.materials.release();
+    g.textures.release();
+    g.randoms.release();
+    g.lights = Lights();
+    g.facts = SceneFacts();
     /* no hipDeviceReset: the process may share the device with torch/RCCL */
 }
 

@@ -116,17 +116,17 @@ void allocateFrame()
 /* the features a frame of the resident scene needs (rt_device.h, enum Feature): decides the kernel instantiation */
 int neededFeatures(const SceneInfo &sceneInfo, bool full)
 {
-    int need = g.sceneFeatures;
+    int need = g.facts.sceneFeatures;
     if (!sceneInfo.extendedGeometry)
         /* every primitive is tested as a triangle, GI:743-747 - and textured as one (GI:916-931) */
-        need = F_TRI | (g.sceneFeatures & F_TEX);
+        need = F_TRI | (g.facts.sceneFeatures & F_TEX);
     if (full)
         need |= F_FULL;
     /* SOLR_HIP_FORCE_FEATURES=mask (experiments, rt_device.h enum Feature): as if the scene had these features too */
     static const int forced = getenv("SOLR_HIP_FORCE_FEATURES") ? atoi(getenv("SOLR_HIP_FORCE_FEATURES")) & F_ALL : 0;
     need |= forced;
-    if (sceneInfo.skyboxMaterialId >= 0 && sceneInfo.skyboxMaterialId < (int)g.materialTags.size() &&
-        (g.materialTags[sceneInfo.skyboxMaterialId] & PRIM_TEXTURED))
+    if (sceneInfo.skyboxMaterialId >= 0 && sceneInfo.skyboxMaterialId < (int)g.materials.materialTags.size() &&
+        (g.materials.materialTags[sceneInfo.skyboxMaterialId] & PRIM_TEXTURED))
         need |= F_TEX;
     return need;
 }
@@ -144,7 +144,7 @@ void launchPostProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppI
         DepthHalo halo = {nullptr, nullptr, 0, 0};
         if (g.nbRows >= 0 && nbRows > 0)
         {
-            const float reach = 16.f * fabsf(ppInfo.param2) * g.randomsReach / 10.f;
+            const float reach = 16.f * fabsf(ppInfo.param2) * g.randoms.randomsReach / 10.f;
             const int wanted = debt.owed ? debt.wanted : (reach < 4096.f ? (int)reach + 2 : 4096);
             g.haloWanted = wanted;
             if (g.haloSuppliedAbove || g.haloSuppliedBelow)
@@ -163,15 +163,15 @@ void launchPostProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppI
         }
         if (ok())
             solrpost::ambientOcclusion(stream, sceneInfo, ppInfo, nbRows, pp,
-                                       (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L, bitmap, halo, firstRow,
-                                       g.randomsReach, g.variant != VARIANT_AO_FIXED_STRIDE);
+                                       (const float *)g.randoms.values.ptr, g.randoms.values.ptr ? g.randoms.nbRandoms : 0L, bitmap, halo, firstRow,
+                                       g.randoms.randomsReach, g.variant != VARIANT_AO_FIXED_STRIDE);
     }
     else if (ppInfo.type == ppe_depthOfField)
         solrpost::depthOfField(stream, sceneInfo, ppInfo, nbRows, pp,
-                               (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L, bitmap);
+                               (const float *)g.randoms.values.ptr, g.randoms.values.ptr ? g.randoms.nbRandoms : 0L, bitmap);
     else if (ppInfo.type == ppe_radiosity)
         solrpost::radiosity(stream, sceneInfo, ppInfo, nbRows, pp,
-                            (const int4 *)g.flight[flight].ids.ptr, (const float *)g.randoms.ptr, g.randoms.ptr ? g.nbRandoms : 0L,
+                            (const int4 *)g.flight[flight].ids.ptr, (const float *)g.randoms.values.ptr, g.randoms.values.ptr ? g.randoms.nbRandoms : 0L,
                             bitmap);
     else if (ppInfo.type == ppe_filter)
         solrpost::filter(stream, sceneInfo, ppInfo, nbRows, pp, bitmap);
@@ -189,9 +189,9 @@ static bool frameReady(const SceneInfo &sceneInfo, const vec4i &objects)
     if (!ready("cudaRender"))
         return false;
     ARGCHECK(sceneInfo.size.x > 0 && sceneInfo.size.y > 0, "cudaRender: empty image");
-    ARGCHECK(objects.x <= g.exact.nb && objects.y <= g.nbPrimitives, "cudaRender: more objects than were uploaded");
-    ARGCHECK(objects.w <= g.nbLights, "cudaRender: more lights than were uploaded");
-    ARGCHECK(g.materials.ptr != nullptr, "cudaRender: no materials uploaded");
+    ARGCHECK(objects.x <= g.scene.exact.nb && objects.y <= g.scene.nbPrimitives, "cudaRender: more objects than were uploaded");
+    ARGCHECK(objects.w <= g.lights.nbLights, "cudaRender: more lights than were uploaded");
+    ARGCHECK(g.materials.table.ptr != nullptr, "cudaRender: no materials uploaded");
     ARGCHECK(sceneInfo.skyboxMaterialId <= NB_MAX_MATERIALS, "cudaRender: skybox material beyond the material table");
     if (!ok())
         return false;
@@ -240,7 +240,7 @@ static int takeFlight(const SceneInfo &sceneInfo, bool counting)
  * every hit, nearest first, ties in the order it met them.)  False: the engine's error is set. */
 static bool frameScene(const SceneInfo &sceneInfo, const vec4i &objects, bool counting, SceneArgs &S)
 {
-    const bool exactNodes = counting || sceneInfo.renderBoxes != 0 || objects.x != g.exact.nb || g.variant == VARIANT_EXACT_LIST ||
+    const bool exactNodes = counting || sceneInfo.renderBoxes != 0 || objects.x != g.scene.exact.nb || g.variant == VARIANT_EXACT_LIST ||
                             sceneInfo.cameraType == ctVolumeRendering;
     S = prepareScene(sceneInfo, exactNodes);
     if (!ok())
@@ -398,7 +398,7 @@ static BandCuts decideStreamCuts(const FrameArgs &F, bool counting, bool *withId
     g.streaming.valid = false;
     BandCuts cuts = {};
     int rows[SOLR_STREAM_BANDS_MAX + 1];
-    if (g.streaming.next && !counting && !g.recordNext && F.fuseDefault && F.si.frameBufferType != ftBGR && !twoFlights() &&
+    if (g.streaming.next && !counting && !g.recording.recordNext && F.fuseDefault && F.si.frameBufferType != ftBGR && !twoFlights() &&
         g.nbRows < 0 && gDevices == 1 && !g.boundBitmap && !gImageRing.sharedRing && g.lastMask >= 0 &&
         solrrows::renderer(0, g.lastMask | F_STREAM, false) != nullptr &&
         imageStreamingCuts(tileRows(F), rows, &cuts.bands, g.streaming.next == 2))
@@ -532,7 +532,7 @@ void TileSchedule::release()
 static std::pair<hipEvent_t, hipEvent_t> startKernelTimer(bool counting, hipStream_t stream)
 {
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g.timing > 0 && !counting && (g.timingTick++ % (unsigned)g.timing) == 0)
+    if (g.timing > 0 && !counting && (g.timer.timingTick++ % (unsigned)g.timing) == 0)
     {
         HIPCHECK(hipEventCreate(&e0));
         HIPCHECK(hipEventCreate(&e1));
@@ -567,7 +567,7 @@ static KernelChoice chooseKernel(const SceneInfo &sceneInfo, bool full, bool dee
             /* more bounces than colour-stack slots fit the LDS of 16 waves per CU: the lean rows have an
              * instantiation that keeps the deeper slots in HBM (rt_device.h ColorStack, F_STACK) */
             const int slots = bounceSlots(sceneInfo);
-            if (slots > SOLR_LDS_STACK_SLOTS && !g.recordNext && g.variant != VARIANT_STACK_IN_LDS)
+            if (slots > SOLR_LDS_STACK_SLOTS && !g.recording.recordNext && g.variant != VARIANT_STACK_IN_LDS)
                 if (RendererFn spilling = solrrows::renderer(0, k.mask | F_STACK, false))
                 {
                     k.fn = spilling;
@@ -583,26 +583,26 @@ static KernelChoice chooseKernel(const SceneInfo &sceneInfo, bool full, bool dee
  * lean rows of the table have such an instantiation.  Null: none, or an allocation failed (the error is set). */
 static RendererFn recordingKernel(const KernelChoice &k, const SceneArgs &S, unsigned grid, size_t ldsBytes, hipStream_t stream)
 {
-    g.recordNext = false;
+    g.recording.recordNext = false;
     ARGCHECK(k.row >= 0 && k.row < solrrows::LEAN_ROWS,
              "solr_hip_walk_bound: the kernel this scene needs has no recording instantiation (untextured spheres, "
              "planes, triangles, cylinders only)");
     if (!ok())
         return nullptr;
-    reserve(g.walkRecords, (size_t)grid * SOLR_WALK_SLOT_BYTES);
-    reserve(g.walkVisits, (size_t)grid * WAVE * sizeof(unsigned) + 64);
+    reserve(g.recording.walkRecords, (size_t)grid * SOLR_WALK_SLOT_BYTES);
+    reserve(g.recording.walkVisits, (size_t)grid * WAVE * sizeof(unsigned) + 64);
     if (!ok())
         return nullptr;
-    HIPCHECK(hipMemsetAsync(g.walkRecords.ptr, 0, (size_t)grid * SOLR_WALK_SLOT_BYTES, stream));
+    HIPCHECK(hipMemsetAsync(g.recording.walkRecords.ptr, 0, (size_t)grid * SOLR_WALK_SLOT_BYTES, stream));
     const RendererFn fn = solrrows::renderer(2, k.mask, false);
     ARGCHECK(fn != nullptr, "solr_hip_walk_bound: no recording instantiation");
     if (!ok())
         return nullptr;
-    g.recordGrid = grid;
-    g.recordLds = ldsBytes;
-    g.recordDeep = (k.mask & F_DEEP) != 0;
-    g.recordScene = S;
-    g.recorded = true;
+    g.recording.recordGrid = grid;
+    g.recording.recordLds = ldsBytes;
+    g.recording.recordDeep = (k.mask & F_DEEP) != 0;
+    g.recording.recordScene = S;
+    g.recording.recorded = true;
     return fn;
 }
 
@@ -683,7 +683,7 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
 
     const KernelChoice k = chooseKernel(sceneInfo, fullFeatures(sceneInfo), deepNodeList(S), counting);
     if (!counting)
-        g.recordVariant = k.row;
+        g.recording.recordVariant = k.row;
     ARGCHECK(k.fn != nullptr, "cudaRender: no instantiation of the renderer for this scene (csrc/rows)");
     if (!ok())
         return;
@@ -696,10 +696,10 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     F.nbTiles = (int)tiles;
     const dim3 grid(F.tileOrder ? tiles + (unsigned)(SPLIT_PARTS - 1) * SPLIT_TILES_MAX : tiles);
     RendererFn fn = k.fn;
-    const bool recording = g.recordNext && !counting;
+    const bool recording = g.recording.recordNext && !counting;
     if (recording && !(fn = recordingKernel(k, S, grid.x, ldsBytesFor(F.stackSlots), stream)))
         return;
-    unsigned long long *cntPtr = (unsigned long long *)(recording ? g.walkRecords.ptr : g.counters.ptr);
+    unsigned long long *cntPtr = (unsigned long long *)(recording ? g.recording.walkRecords.ptr : g.counters.ptr);
     if (k.deepSlots > 0 && !armDeepStack(F, k.deepSlots, flight, stream))
         return;
     unsigned char *bitmap = (unsigned char *)(g.boundBitmap ? g.boundBitmap : g.flight[flight].shown().ptr);
@@ -722,7 +722,7 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
     if (timer.first)
     {
         HIPCHECK(hipEventRecord(timer.second, stream));
-        g.events.push_back(timer);
+        g.timer.events.push_back(timer);
     }
     if (streamed)
     {
@@ -745,18 +745,18 @@ void renderImpl(const SceneInfo &sceneInfo, const vec4i &objects, const PostProc
 void collectEvents()
 {
     hipEvent_t before = nullptr;
-    for (auto &ev : g.events)
+    for (auto &ev : g.timer.events)
     {
         float ms = 0.f, gap = 0.f;
         if (hipEventSynchronize(ev.second) == hipSuccess && hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess)
         {
-            g.timedMs += ms;
-            g.timedLaunches++;
-            if (g.kernelSamples.size() < 65536)
+            g.timer.timedMs += ms;
+            g.timer.timedLaunches++;
+            if (g.timer.kernelSamples.size() < 65536)
             {
-                g.kernelSamples.push_back(ms);
+                g.timer.kernelSamples.push_back(ms);
                 /* end of the launch before to the end of this one: what a step of a pipelined loop takes */
-                g.intervalSamples.push_back((before && hipEventElapsedTime(&gap, before, ev.second) == hipSuccess) ? gap : -1.f);
+                g.timer.intervalSamples.push_back((before && hipEventElapsedTime(&gap, before, ev.second) == hipSuccess) ? gap : -1.f);
             }
         }
         if (before)
@@ -766,7 +766,7 @@ void collectEvents()
     }
     if (before)
         (void)hipEventDestroy(before);
-    g.events.clear();
+    g.timer.events.clear();
 }
 /* wait == false: the copies are enqueued and d2hBitmapWait() is owed (several devices copy side by side) */
 void d2hBitmapOne(const SceneInfo &sceneInfo, BitmapBuffer *bitmap, PrimitiveXYIdBuffer *primitivesXYIds, bool wait)

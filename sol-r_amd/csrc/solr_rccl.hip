@@ -224,7 +224,7 @@ namespace solreng /* (engine.h) */
 {
 int agreedHaloRows(const PostProcessingInfo &ppInfo)
 {
-    const float reach = 16.f * fabsf(ppInfo.param2) * g.randomsReach / 10.f;
+    const float reach = 16.f * fabsf(ppInfo.param2) * g.randoms.randomsReach / 10.f;
     const int wanted = reach < 4096.f ? (int)reach + 2 : 4096;
     if (!rccl.comm || rccl.world < 2)
         return wanted;
@@ -257,7 +257,7 @@ bool shareRandoms()
     if (!rccl.comm || rccl.world < 2)
         return true;
     rccl.haloStale = true;
-    const long n = g.randoms.ptr ? g.nbRandoms : 0;
+    const long n = g.randoms.values.ptr ? g.randoms.nbRandoms : 0;
     /* the same count everywhere?  (two 16-bit halves: a float holds them exactly) */
     /* (two more slots: a seed of rank 0's, in 16-bit halves, for what the hosts draw per frame - see
      * solr_hip_comm_shared_seed) */
@@ -268,7 +268,7 @@ bool shareRandoms()
         draw = (draw ^ (draw >> 15)) | 1u;
     }
     float v[8] = {(float)(n >> 16), -(float)(n >> 16), (float)(n & 0xffff), -(float)(n & 0xffff), ok() ? 0.f : 1.f,
-                  rccl.rank == 0 ? g.randomsReach : 0.f, (float)(draw >> 16), (float)(draw & 0xffffu)};
+                  rccl.rank == 0 ? g.randoms.randomsReach : 0.f, (float)(draw >> 16), (float)(draw & 0xffffu)};
     if (!allReduceFloats(v, 8, RCCL_MAX, "ncclAllReduce (size of the random buffer)"))
         return false;
     if (rccl.sharedSeed == 0)
@@ -292,15 +292,15 @@ bool shareRandoms()
     bool fine = rcclOk(rccl.GroupStart(), "ncclGroupStart");
     if (fine && rccl.rank == 0)
         for (int r = 1; r < rccl.world && fine; ++r)
-            fine = rcclOk(rccl.Send(g.randoms.ptr, (size_t)n, RCCL_FLOAT32, r, rccl.comm, stream), "ncclSend (random buffer)");
+            fine = rcclOk(rccl.Send(g.randoms.values.ptr, (size_t)n, RCCL_FLOAT32, r, rccl.comm, stream), "ncclSend (random buffer)");
     else if (fine)
-        fine = rcclOk(rccl.Recv(g.randoms.ptr, (size_t)n, RCCL_FLOAT32, 0, rccl.comm, stream), "ncclRecv (random buffer)");
+        fine = rcclOk(rccl.Recv(g.randoms.values.ptr, (size_t)n, RCCL_FLOAT32, 0, rccl.comm, stream), "ncclRecv (random buffer)");
     if (!rcclOk(rccl.GroupEnd(), "ncclGroupEnd"))
         fine = false;
     if (hipStreamSynchronize(stream) != hipSuccess)
         fine = false;
     if (fine)
-        g.randomsReach = v[5];
+        g.randoms.randomsReach = v[5];
     return fine;
 }
 } // namespace solreng

@@ -1,5 +1,5 @@
 """A numpy binary32 model of what the arena holds of a node list beyond its rows (test infrastructure, no test functions):
-the thin copy, the copy with sorted bounds, the leaf records - sol-r_amd/csrc/solr_scene.hip k_tightenLeaves,
+the thin copy, the copy with sorted bounds, the leaf records - sol-r_amd/csrc/solr_arena.hip k_tightenLeaves,
 k_tightenInner, k_sortNodeBounds, k_buildLeafRecords - written from the comments above those kernels and from
 scene_layout.h, one function per kernel; and the hand-made node lists the copies are read back for
 (tests/test_list_copies_model.py holds the model to its own properties, tests/test_list_copies_gpu.py the engine to the

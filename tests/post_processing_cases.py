@@ -120,7 +120,7 @@ def halo_rows_wanted(randoms_, param2):
 
 
 def _randoms_reach(randoms_):
-    """noteRandomsReach (solr_scene.hip): max |randoms[i]|, i < 356, by std::max - which never takes a NaN"""
+    """noteRandomsReach (solr_uploads.hip): max |randoms[i]|, i < 356, by std::max - which never takes a NaN"""
     a = np.abs(np.asarray(randoms_[:356], np.float32))
     a = a[~np.isnan(a)]
     return F(a.max()) if len(a) else F(0)

@@ -13,7 +13,7 @@ business).
 
 `foreign` - leaf boxes of another host's that are smaller than their planes - is the case the thin copy could not be
 walked on: a ray through such a box hits the plane beside it, the reference finds that hit, the copy cut with the box does
-not.  The engine offers the thin copy only for lists that hold what they name (solr_scene.hip tightListsFor).
+not.  The engine offers the thin copy only for lists that hold what they name (solr_arena.hip tightListsFor).
 """
 import os
 import sys
