@@ -494,7 +494,9 @@ void solr_hip_render_counting(const SceneInfo *sceneInfo, const vec4i *objects,
  * every third frame, as they are when a count nears 2^32; 15 = the shadow walks in the reference's order keep the
  * reference's cut-off alone (no lamp cut-off, rt_device.h shadowWalk); 16 = the trace makes the trips that no lane takes
  * (the deferred-reflection trip of a wave without one, the material gather and the shader call of a trip in which every
- * lane missed; rt_device.h launchRayTracing).  Every setting renders the same frame. */
+ * lane missed; rt_device.h launchRayTracing); 17 = the hierarchy of the order-free lists is built on the leaves' boxes
+ * as uploaded, no leaf set apart (csrc/build_bounds.h; lists that exist are built again with the next frame).  Every
+ * setting renders the same frame. */
 void solr_hip_set_variant(int variant);
 /* Bounce rays (|direction| = 1 - rayEpsilon) of the long-list triangle kernels on the order-free lists, checked: lanes
  * whose hit has a rival the reference's cut-off could have preferred are walked again in the reference's order

@@ -1,0 +1,100 @@
+/*
+ * build_bounds.h - the box of a leaf that the order-free hierarchy is BUILT on (list_builders.cpp buildFreeOrderLists,
+ * solr_lists.hip): the box a long ray will test, which for a leaf of axis-plane rectangles is not the box as uploaded
+ * (the reference boxes a wall as p0 +- size on all three axes) but the rectangles' own, one margin thick - the
+ * arithmetic of the thin copy (solr_arena.hip k_tightenLeaves calls the same function), decided by primitive type alone: materials may arrive
+ * after the lists, and any hierarchy over the leaves is correct.  What the lists hold is never this box: leaves are
+ * emitted as uploaded, inner nodes as the unions of those.
+ * One function for the host and the device builder, which have to make the same lists bit for bit; plain float
+ * arithmetic, no contraction possible (no product feeds a sum).
+ */
+#ifndef SOLR_BUILD_BOUNDS_H
+#define SOLR_BUILD_BOUNDS_H
+
+#include <hip/hip_vector_types.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "../../include/solr_types.h"
+
+#if defined(__HIPCC__)
+#define SOLR_BUILD_BOUNDS_FN __host__ __device__ inline
+#else
+#define SOLR_BUILD_BOUNDS_FN inline
+#endif
+
+namespace solreng
+{
+/* Which share of its range's surface measure (xy + yz + zx of the union of the build boxes) makes a leaf dominant:
+ * it is taken out of the range before the binned split and emitted as a sibling of the subtree over the rest
+ * (profiles/r15/free_list_topology.txt has the counts behind the number).  A wall of a cubic room is 1/3 of the room. */
+#define SOLR_DOMINANT_SHARE 0.25
+
+/* How the order-free hierarchy is built.  prims == nullptr: on the boxes as uploaded, nothing set apart - the lists of
+ * every build before this one.  Otherwise `prims` are the primitive records (8 rows each: p0 | type word, size | ...),
+ * tagged or not, on the side of the caller (host memory for the host builder, device memory for the device's). */
+struct BuildBounds
+{
+    const float4 *prims = nullptr;
+    float margin = 0.f;                 /* scene extent / 1024, as the thin copies take it */
+    double dominantShare = SOLR_DOMINANT_SHARE; /* <= 0: no leaf is set apart */
+};
+
+/* the kinds a primitive record's tag holds for a PLAIN axis plane (scene_layout.h PrimKind, bits 24 ... 27 of the type
+ * word; solr_arena.hip holds these to that header) */
+enum BuildBoundsPlainKind
+{
+    BB_KIND_SHIFT = 24,
+    BB_KIND_PLANE_XY = 2,
+    BB_KIND_PLANE_YZ = 3,
+    BB_KIND_PLANE_XZ = 4
+};
+
+/* The build box of the leaf { row0, row1 } whose `count` primitives begin at prims[8 * start].  true: the leaf holds
+ * nothing but axis-plane rectangles and lo / hi are their thin box cut with the leaf's own; false: lo / hi are the
+ * leaf's box as uploaded.  byKind: a rectangle is what the record's tag calls a plain plane, not what its type says -
+ * the thin copy's rule (solr_arena.hip k_tightenLeaves, which is this function: one arithmetic for the box a ray
+ * tests and the box the hierarchy is built on). */
+SOLR_BUILD_BOUNDS_FN bool leafBuildBounds(const float4 &row0, const float4 &row1, const float4 *prims, int start, int count, float margin,
+                                          float lo[3], float hi[3], bool byKind = false)
+{
+    lo[0] = row0.x, lo[1] = row0.y, lo[2] = row0.z;
+    hi[0] = row1.x, hi[1] = row1.y, hi[2] = row0.w;
+    if (prims == nullptr || count <= 0 || start < 0)
+        return false;
+    float lx = INFINITY, ly = INFINITY, lz = INFINITY, hx = -INFINITY, hy = -INFINITY, hz = -INFINITY;
+    for (int k = 0; k < count; ++k)
+    {
+        const float4 p = prims[8 * (size_t)(start + k)], s = prims[8 * (size_t)(start + k) + 1];
+        int word;
+        memcpy(&word, &p.w, 4);
+        const int type = word & 0xff, kind = (word >> BB_KIND_SHIFT) & 15;
+        /* the axis the rectangle lies across */
+        const int across = byKind ? (kind == BB_KIND_PLANE_YZ ? 0 : kind == BB_KIND_PLANE_XZ ? 1 : kind == BB_KIND_PLANE_XY ? 2 : -1)
+                                  : (type == ptYZPlane ? 0 : type == ptXZPlane ? 1 : type == ptXYPlane ? 2 : -1);
+        if (across < 0)
+            return false;
+        /* (a size is compared with a distance: its sign cannot make the rectangle larger than |size|) */
+        const float ex = across == 0 ? margin : fabsf(s.x) + margin;
+        const float ey = across == 1 ? margin : fabsf(s.y) + margin;
+        const float ez = across == 2 ? margin : fabsf(s.z) + margin;
+        lx = fminf(lx, p.x - ex), hx = fmaxf(hx, p.x + ex);
+        ly = fminf(ly, p.y - ey), hy = fmaxf(hy, p.y + ey);
+        lz = fminf(lz, p.z - ez), hz = fmaxf(hz, p.z + ez);
+    }
+    /* (finite, ordered bounds only: anything else keeps the box as uploaded) */
+    if (!(lx <= hx && ly <= hy && lz <= hz && fabsf(lx) < 3.0e38f && fabsf(hx) < 3.0e38f && fabsf(ly) < 3.0e38f && fabsf(hy) < 3.0e38f &&
+          fabsf(lz) < 3.0e38f && fabsf(hz) < 3.0e38f))
+        return false;
+    const float nlx = fmaxf(lo[0], lx), nly = fmaxf(lo[1], ly), nlz = fmaxf(lo[2], lz);
+    const float nhx = fminf(hi[0], hx), nhy = fminf(hi[1], hy), nhz = fminf(hi[2], hz);
+    if (!(nlx <= nhx && nly <= nhy && nlz <= nhz))
+        return false;
+    lo[0] = nlx, lo[1] = nly, lo[2] = nlz;
+    hi[0] = nhx, hi[1] = nhy, hi[2] = nhz;
+    return true;
+}
+} // namespace solreng
+
+#endif

@@ -283,8 +283,10 @@ enum Variant
     VARIANT_NO_BAND_WORDS = 13,  /* a streamed frame's waves write no band's word */
     VARIANT_ZERO_STREAM_COUNTERS = 14, /* the tile counters of streamed frames zeroed every third frame */
     VARIANT_NO_LAMP_CUTOFF = 15, /* shadow walks in the reference's order keep the reference's cut-off alone */
-    VARIANT_ALL_TRIPS = 16       /* the trace makes the trips no lane takes: the deferred-reflection trip of a wave without
+    VARIANT_ALL_TRIPS = 16,      /* the trace makes the trips no lane takes: the deferred-reflection trip of a wave without
                                   * one, the gather and the shader call of a trip in which every lane missed */
+    VARIANT_UPLOADED_BUILD_BOXES = 17 /* the order-free hierarchy is built on the leaves' boxes as uploaded, no leaf set
+                                       * apart (build_bounds.h); the lists are built again with the next frame */
 };
 
 /* A node list of the resident scene: its host image, the count a frame is told, where the arena holds it (the layout
@@ -429,6 +431,13 @@ struct Scene
     bool orderFreeDue() { return lists.freeCountdown > 0 && --lists.freeCountdown == 0; }
     /* ... and no walk would take them yet (orderFreeListsUsable): asked again with the next frame */
     void orderFreeAskAgain() { lists.freeCountdown = 1; }
+    /* what the lists are built on has changed (VARIANT_UPLOADED_BUILD_BOXES set or taken back): lists that exist are built
+     * again with the next frame; a scene that is still waiting for its own goes on waiting */
+    void orderFreeBuildAgain()
+    {
+        if (orderFree.nb > 0 && lists.freeCountdown == 0)
+            lists.freeCountdown = 1;
+    }
     /* maybeBuildOrderFreeLists has built them; stayed: on the device (lists.freeStage), fromArena: made from an arena
      * that is up to date.  They join the arena with the next flushGeometry: added behind what it holds when both, else
      * laid out and uploaded again */

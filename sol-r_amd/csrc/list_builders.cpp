@@ -451,30 +451,39 @@ int buildWalkOrderList(std::vector<float4> &rows, std::vector<int> &start, std::
  * Any of the eight is correct for any ray; the choice is only speed.  Inner nodes that hardly cull are left
  * out as in the other lists (decided once, on the first flattening).  Valid only when every primitive lies
  * inside its leaf's box and every inner node of the reference's list encloses its children (the caller checks
- * both).  `rows` / `start`: a nested list.  Output: 8 x count nodes, list after list. */
+ * both).  `rows` / `start`: a nested list.  Output: 8 x count nodes, list after list.
+ * `build` (build_bounds.h): with primitive records, the hierarchy is built on the box a long ray tests - a leaf of
+ * nothing but axis-plane rectangles by its thin box - and a leaf that dominates its range is set apart before the
+ * binned split: centres, bins, SAH areas and the prune decisions see those boxes.  What is emitted stays what it was:
+ * the leaves' rows as uploaded, every inner node's row the union of its leaves' uploaded boxes.  A scene without such a
+ * leaf, and a call without `build`, get the lists of the builder before build bounds, byte for byte. */
 int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> &start, const std::vector<int> &origin,
                         std::vector<float4> &outRows, std::vector<int> &outStart, std::vector<int> &outOrigin, int *nbPruned,
-                        double threshold, const PruneDecider &decider)
+                        double threshold, const PruneDecider &decider, const BuildBounds &build)
 {
     struct Leaf
     {
-        float lo[3], hi[3];
+        float lo[3], hi[3]; /* the build box (build_bounds.h) */
         int node;
+        bool thin;          /* ... which is not the box as uploaded */
     };
     struct TreeNode
     {
-        float lo[3], hi[3];
+        float lo[3], hi[3];   /* of the build boxes: what the splits and the prune decisions see */
+        float ulo[3], uhi[3]; /* of the boxes as uploaded: what is emitted */
         int left, right, axis, leaf; /* leaf: node of the input list, -1 for an inner node */
-        bool keep;
+        bool keep, apart;            /* apart: one child is a dominant leaf set apart; such a node is never emitted */
     };
+    bool onBuildBounds = false; /* a leaf is built on another box than its own: only then is anything built differently */
     const int n = (int)start.size();
     std::vector<Leaf> leaves;
     for (int i = 0; i < n; ++i)
         if (bitsi(rows[2 * i + 1].z) > 0)
         {
             Leaf l;
-            l.lo[0] = rows[2 * i].x, l.lo[1] = rows[2 * i].y, l.lo[2] = rows[2 * i].z;
-            l.hi[0] = rows[2 * i + 1].x, l.hi[1] = rows[2 * i + 1].y, l.hi[2] = rows[2 * i].w;
+            l.thin = leafBuildBounds(rows[2 * i], rows[2 * i + 1], build.prims, start[i], bitsi(rows[2 * i + 1].z), build.margin, l.lo, l.hi);
+            if (l.thin)
+                onBuildBounds = true;
             l.node = i;
             leaves.push_back(l);
         }
@@ -507,6 +516,7 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
         t.axis = 0;
         t.leaf = -1;
         t.keep = true;
+        t.apart = false;
         if (count == 1)
         {
             for (int k = 0; k < 3; ++k)
@@ -531,6 +541,51 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
          * minima are atomics, could not tell which that was) */
         for (int k = 0; k < 3; ++k)
             t.lo[k] += 0.f, t.hi[k] += 0.f;
+        /* A dominant leaf set apart.  Top-down SAH does not see what peeling a wall off a room buys until all of them
+         * are out, so: the leaf with the largest build box (the first of them in the range), if that is more than
+         * `dominantShare` of the range's union, becomes one child of this node and the rest of the range the other -
+         * on the axis along which its centre lies farthest from the union's, the near side first like every split -
+         * and the node itself is never emitted: the leaf is a sibling of the subtree over the rest (groupSiblings
+         * above does the same for the walk-order list). */
+        if (onBuildBounds && build.dominantShare > 0.0 && count >= 3)
+        {
+            int largest = -1;
+            double largestArea = 0.0;
+            for (int q = r.from; q < r.to; ++q)
+            {
+                const double a = area(leaves[q].lo, leaves[q].hi);
+                if (a > largestArea)
+                    largestArea = a, largest = q;
+            }
+            if (largest >= 0 && largestArea > build.dominantShare * area(t.lo, t.hi))
+            {
+                const Leaf l = leaves[largest];
+                float farthest = -1.f;
+                bool lowSide = true;
+                for (int k = 0; k < 3; ++k)
+                {
+                    const float cl = 0.5f * (l.lo[k] + l.hi[k]), cu = 0.5f * (t.lo[k] + t.hi[k]);
+                    if (fabsf(cl - cu) > farthest)
+                        farthest = fabsf(cl - cu), t.axis = k, lowSide = cl <= cu;
+                }
+                /* (stable: the rest keeps the order of the leaf list) */
+                if (lowSide)
+                    std::rotate(leaves.begin() + r.from, leaves.begin() + largest, leaves.begin() + largest + 1);
+                else
+                    std::rotate(leaves.begin() + largest, leaves.begin() + largest + 1, leaves.begin() + r.to);
+                const int mid = lowSide ? r.from + 1 : r.to - 1;
+                t.apart = true;
+                t.keep = false;
+                t.left = (int)tree.size();
+                t.right = t.left + 1;
+                tree.push_back(TreeNode());
+                tree.push_back(TreeNode());
+                tree[r.node] = t;
+                todo.push_back({r.from, mid, t.left});
+                todo.push_back({mid, r.to, t.right});
+                continue;
+            }
+        }
         /* binned surface-area split: one pass over the leaves fills the bins of all three axes */
         const int BINS = 16;
         int bestAxis = -1, bestBin = 0;
@@ -635,7 +690,32 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
         todo.push_back({mid, r.to, t.right});
     }
 
-    /* one flattening: depth-first, the child on the near side of a ray of this octant first */
+    /* what is emitted for an inner node: the union of its leaves' boxes as uploaded (children are stored behind their
+     * parent in `tree`: one backward pass).  Without build bounds that is the box the node was split on. */
+    for (int t = (int)tree.size() - 1; t >= 0; --t)
+    {
+        TreeNode &node = tree[t];
+        if (!onBuildBounds)
+        {
+            for (int k = 0; k < 3; ++k)
+                node.ulo[k] = node.lo[k], node.uhi[k] = node.hi[k];
+            continue;
+        }
+        if (node.leaf >= 0)
+        {
+            node.ulo[0] = rows[2 * node.leaf].x, node.ulo[1] = rows[2 * node.leaf].y, node.ulo[2] = rows[2 * node.leaf].z;
+            node.uhi[0] = rows[2 * node.leaf + 1].x, node.uhi[1] = rows[2 * node.leaf + 1].y, node.uhi[2] = rows[2 * node.leaf].w;
+            continue;
+        }
+        for (int k = 0; k < 3; ++k)
+        {
+            node.ulo[k] = std::min(tree[node.left].ulo[k], tree[node.right].ulo[k]) + 0.f; /* (zeros are +0, as above) */
+            node.uhi[k] = std::max(tree[node.left].uhi[k], tree[node.right].uhi[k]) + 0.f;
+        }
+    }
+
+    /* one flattening: depth-first, the child on the near side of a ray of this octant first (only the prune decisions
+     * read it: the nodes with their build boxes) */
     auto flatten = [&](int octant, std::vector<float4> &fr, std::vector<int> &fs, std::vector<int> *which,
                        std::vector<int> *from) {
         struct Visit
@@ -656,9 +736,14 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
             const TreeNode &t = tree[v.node];
             if (t.leaf >= 0)
             {
-                fr.push_back(rows[2 * t.leaf]);
-                float4 second = rows[2 * t.leaf + 1];
+                float4 first = rows[2 * t.leaf], second = rows[2 * t.leaf + 1];
+                if (onBuildBounds)
+                {
+                    first = make_float4(t.lo[0], t.lo[1], t.lo[2], t.hi[2]);
+                    second.x = t.hi[0], second.y = t.hi[1];
+                }
                 second.w = bitsf(1);
+                fr.push_back(first);
                 fr.push_back(second);
                 fs.push_back(start[t.leaf]);
                 if (which)
@@ -696,7 +781,7 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
             kept[t] = 1;
         for (size_t t = 0; t < tree.size(); ++t)
             if (tree[t].leaf < 0)
-                tree[t].keep = kept[t] != 0;
+                tree[t].keep = kept[t] != 0 && !tree[t].apart;
     }
     /* the eight lists: every node's place follows from the sizes of the subtrees before it (children are stored
      * behind their parent in `tree`, so one backward pass gives the sizes); skip pointers are relative, each list
@@ -737,8 +822,8 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
             int at = v.at;
             if (t.keep)
             {
-                fr[2 * at] = make_float4(t.lo[0], t.lo[1], t.lo[2], t.hi[2]);
-                fr[2 * at + 1] = make_float4(t.hi[0], t.hi[1], bitsf(0), bitsf(size[v.node]));
+                fr[2 * at] = make_float4(t.ulo[0], t.ulo[1], t.ulo[2], t.uhi[2]);
+                fr[2 * at + 1] = make_float4(t.uhi[0], t.uhi[1], bitsf(0), bitsf(size[v.node]));
                 ++at;
             }
             const bool highFirst = (octant >> t.axis) & 1; /* direction negative along the split axis */

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/solr_types.h"
+#include "build_bounds.h"
 
 namespace solreng
 {
@@ -69,7 +70,7 @@ int buildWalkOrderList(std::vector<float4> &rows, std::vector<int> &start, std::
                        const std::function<void(const char *)> &mark = nullptr);
 int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> &start, const std::vector<int> &origin,
                         std::vector<float4> &outRows, std::vector<int> &outStart, std::vector<int> &outOrigin, int *nbPruned,
-                        double threshold, const PruneDecider &decider = nullptr);
+                        double threshold, const PruneDecider &decider = nullptr, const BuildBounds &build = BuildBounds());
 bool listEnclosesOnHost(const std::vector<float4> &rows, const std::vector<int> &start, const std::vector<float4> &prims);
 void planRefit(const std::vector<float4> &exact, const std::vector<float4> &walk, const std::vector<int> &origin,
                const std::vector<float4> &free, const std::vector<int> &freeOrigin, std::vector<int> &plan,

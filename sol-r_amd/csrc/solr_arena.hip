@@ -75,35 +75,17 @@ __global__ __launch_bounds__(256) void k_tightenLeaves(float4 *__restrict__ aren
     const int nb = __float_as_int(row1.z);
     if (nb > 0)
     {
+        /* (build_bounds.h: the rectangles' union cut with the box, finite and ordered, or the reference's box stays; by the
+         * records' kinds - a plane that is textured, transparent or emissive keeps its box) */
+        static_assert(BB_KIND_SHIFT == PRIM_KIND_SHIFT && BB_KIND_PLANE_XY == KIND_PLANE_XY && BB_KIND_PLANE_YZ == KIND_PLANE_YZ &&
+                          BB_KIND_PLANE_XZ == KIND_PLANE_XZ && ROW_P0_TYPE == 0 && ROW_SIZE_MAT == 1,
+                      "build_bounds.h reads the primitive records as scene_layout.h lays them out");
         const int start = ((const int *)arena)[offStart + (unsigned)i];
-        float lx = INFINITY, ly = INFINITY, lz = INFINITY, hx = -INFINITY, hy = -INFINITY, hz = -INFINITY;
-        bool plain = true;
-        for (int k = 0; k < nb && plain; ++k)
+        float lo[3], hi[3];
+        if (leafBuildBounds(row0, row1, arena + offPrims, start, nb, margin, lo, hi, true))
         {
-            const float4 *prim = arena + offPrims + 8u * (unsigned)(start + k);
-            const float4 p = prim[ROW_P0_TYPE], s = prim[ROW_SIZE_MAT];
-            const int kind = (__float_as_int(p.w) >> PRIM_KIND_SHIFT) & 15;
-            plain = kind == KIND_PLANE_XY || kind == KIND_PLANE_YZ || kind == KIND_PLANE_XZ;
-            /* (a size is compared with a distance: its sign cannot make the rectangle larger than |size|) */
-            const float ex = kind == KIND_PLANE_YZ ? margin : fabsf(s.x) + margin;
-            const float ey = kind == KIND_PLANE_XZ ? margin : fabsf(s.y) + margin;
-            const float ez = kind == KIND_PLANE_XY ? margin : fabsf(s.z) + margin;
-            lx = fminf(lx, p.x - ex), hx = fmaxf(hx, p.x + ex);
-            ly = fminf(ly, p.y - ey), hy = fmaxf(hy, p.y + ey);
-            lz = fminf(lz, p.z - ez), hz = fmaxf(hz, p.z + ez);
-        }
-        /* (finite, ordered bounds only: anything else keeps the reference's box) */
-        plain = plain && lx <= hx && ly <= hy && lz <= hz && fabsf(lx) < 3.0e38f && fabsf(hx) < 3.0e38f && fabsf(ly) < 3.0e38f &&
-                fabsf(hy) < 3.0e38f && fabsf(lz) < 3.0e38f && fabsf(hz) < 3.0e38f;
-        if (plain)
-        {
-            const float nlx = fmaxf(row0.x, lx), nly = fmaxf(row0.y, ly), nlz = fmaxf(row0.z, lz);
-            const float nhx = fminf(row1.x, hx), nhy = fminf(row1.y, hy), nhz = fminf(row0.w, hz);
-            if (nlx <= nhx && nly <= nhy && nlz <= nhz)
-            {
-                row0 = make_float4(nlx, nly, nlz, nhz);
-                row1 = make_float4(nhx, nhy, row1.z, row1.w);
-            }
+            row0 = make_float4(lo[0], lo[1], lo[2], hi[2]);
+            row1 = make_float4(hi[0], hi[1], row1.z, row1.w);
         }
     }
     arena[offTight + 2u * (unsigned)i] = row0;
@@ -546,6 +528,14 @@ void maybeBuildOrderFreeLists()
             origin[i] = i;
     };
     int prunedFree = 0;
+    /* what the hierarchy is built on (build_bounds.h): the box a long ray tests - a leaf of axis-plane rectangles by its
+     * thin box, such leaves set apart where they dominate - unless the variant asks for the boxes as uploaded */
+    BuildBounds build;
+    if (g.variant != VARIANT_UPLOADED_BUILD_BOXES)
+    {
+        build.prims = g.scene.hostPrims.data();
+        build.margin = g.facts.sceneExtent * (1.f / 1024.f);
+    }
     /* on the device (solr_lists.hip: the same tree level by level, the same lists bit for bit) unless told otherwise
      * or declined */
     int count = -1;
@@ -556,13 +546,18 @@ void maybeBuildOrderFreeLists()
         {
             g.scene.lists.dropStage(true);
             if (fromArena)
+            {
+                BuildBounds inArena = build; /* (the primitive records where the rows are) */
+                if (build.prims)
+                    inArena.prims = arena + g.scene.arena.offPrims;
                 count = solrBuildOrderFreeListsOnDevice(arena + g.scene.exact.offRows, (const int *)arena + g.scene.exact.offStart, nullptr, n,
-                                                        knobs.pruneThreshold, &prunedFree, sceneStream(), &g.scene.lists.freeStage);
+                                                        knobs.pruneThreshold, &prunedFree, sceneStream(), &g.scene.lists.freeStage, inArena);
+            }
             else
             {
                 ownOrigins();
                 count = solrBuildOrderFreeListsOnDevice(rows.data(), start.data(), origin.data(), n, knobs.pruneThreshold, &prunedFree,
-                                                        sceneStream(), &g.scene.lists.freeStage);
+                                                        sceneStream(), &g.scene.lists.freeStage, build);
             }
         }
     }
@@ -573,7 +568,7 @@ void maybeBuildOrderFreeLists()
         if (origin.empty())
             ownOrigins();
         count = buildFreeOrderLists(rows, start, origin, built.rows, built.start, built.origin, &prunedFree, knobs.pruneThreshold,
-                                    pruneDecider());
+                                    pruneDecider(), build);
     }
     if (getenv("SOLR_HIP_DEBUG_TREE"))
         fprintf(stderr, "solr_hip: order-free lists: 8 x %d nodes (%d inner nodes that hardly cull left out)\n", count, prunedFree);

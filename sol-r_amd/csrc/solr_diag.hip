@@ -539,6 +539,8 @@ int solr_hip_short_ray_lists(void)
 void solr_hip_set_variant(int variant)
 {
     onEveryDevice([&](int) {
+        if ((g.variant == VARIANT_UPLOADED_BUILD_BOXES) != (variant == VARIANT_UPLOADED_BUILD_BOXES))
+            g.scene.orderFreeBuildAgain();
         g.variant = variant;
         g.grouping = (variant != VARIANT_NO_GROUPING); /* takes effect at the next h2d_scene */
     });

@@ -21,6 +21,10 @@
  *                             leaves the leaves in), the surface ratio, the decision - all in double
  *               k_sizes       bottom-up per level; k_places top-down per level, eight octants at once
  *               k_emit        rows, start indices and origins of the eight lists
+ * On build bounds (build_bounds.h: the leaves' boxes are the ones a long ray tests, where the scene has a leaf of
+ * axis-plane rectangles) k_largest finds every open node's largest leaf, k_split sets it apart when it dominates (the
+ * host's test, word for word; k_flags sends it to one side), the decisions of k_prune see the build boxes, and k_unions
+ * gives k_emit the unions of the uploaded boxes for the inner nodes.
  * Every quantity is a min, a max, a count or a double-precision expression of those: none depends on the order in
  * which the atomics land, so the lists are the host's BIT FOR BIT (tests/test_lists_gpu.py holds them to the host
  * builder on the BASELINE scenes; SOLR_HIP_LISTS_ON_HOST=1 keeps the host path).  Zeros are canonical (+0) in both
@@ -77,6 +81,12 @@ struct Node
     int size;             /* nodes of its subtree in a list */
     int mid;              /* first position of the right child */
     int split;            /* 1: splits this level */
+    /* on build bounds (build_bounds.h; lo / hi above are then of the build boxes): */
+    float ulo[3], uhi[3];           /* bounds of the leaves' boxes as uploaded: what is emitted */
+    unsigned long long largestArea; /* the largest build-box area among its leaves: the bits of a double >= 0 */
+    int largestAt;                  /* the first position of a leaf that has it */
+    int apart;                      /* 1: one child is that leaf, set apart; such a node is never emitted */
+    int apartLeaf, lowSide;         /* the leaf, and whether it is the left child */
 };
 
 struct BinSet
@@ -160,6 +170,11 @@ __global__ void k_open(Node *nodes, BinSet *bins, int first, int count)
     t.keep = 1;
     t.split = 0;
     t.mid = t.from;
+    t.largestArea = 0ull;
+    t.largestAt = 0x7fffffff;
+    t.apart = 0;
+    t.apartLeaf = -1;
+    t.lowSide = 0;
 }
 
 __device__ inline float waveMin(float v)
@@ -349,8 +364,30 @@ __device__ inline double areaOf(const float *lo, const float *hi)
     return x * y + y * z + z * x;
 }
 
-/* the host's cost loop (list_builders.cpp buildFreeOrderLists), one thread per open node */
-__global__ void k_split(Node *nodes, const BinSet *bins, int levelFirst, int count, int nextFree, int *splitting)
+/* the leaf with the largest build box of every open node of three leaves or more, the first of them in the node's order
+ * (the host: a > largest so far, in range order).  pass 0: the area (the bits of a non-negative double order like an
+ * integer), pass 1: the lowest position that has it */
+__global__ __launch_bounds__(256) void k_largest(Node *nodes, const int *nodeOf, const int *order, const float *llo, const float *lhi,
+                                                  int nbLeaves, int levelFirst, int pass)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbLeaves)
+        return;
+    const int t = nodeOf[i];
+    if (t < levelFirst || nodes[t].to - nodes[t].from < 3)
+        return;
+    const int leaf = order[i];
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(areaOf(llo + 3 * leaf, lhi + 3 * leaf));
+    if (pass == 0)
+        atomicMax(&nodes[t].largestArea, bits);
+    else if (bits == nodes[t].largestArea)
+        atomicMin(&nodes[t].largestAt, i);
+}
+
+/* the host's cost loop (list_builders.cpp buildFreeOrderLists), one thread per open node; before it, with share > 0 (on
+ * build bounds), the host's test for a dominant leaf that is set apart */
+__global__ void k_split(Node *nodes, const BinSet *bins, int levelFirst, int count, int nextFree, int *splitting, const int *order,
+                        const float *llo, const float *lhi, double share)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count)
@@ -359,6 +396,35 @@ __global__ void k_split(Node *nodes, const BinSet *bins, int levelFirst, int cou
     const int n = t.to - t.from;
     if (n < 2)
         return;
+    if (share > 0.0 && n >= 3 && t.largestArea != 0ull && t.largestAt < t.to &&
+        __longlong_as_double((long long)t.largestArea) > share * areaOf(t.lo, t.hi))
+    {
+        const int leaf = order[t.largestAt];
+        float farthest = -1.f;
+        int axis = 0, lowSide = 1;
+        for (int k = 0; k < 3; ++k)
+        {
+            const float cl = 0.5f * (llo[3 * leaf + k] + lhi[3 * leaf + k]), cu = 0.5f * (t.lo[k] + t.hi[k]);
+            if (fabsf(cl - cu) > farthest)
+                farthest = fabsf(cl - cu), axis = k, lowSide = cl <= cu ? 1 : 0;
+        }
+        t.split = 1;
+        t.apart = 1;
+        t.keep = 0;
+        t.axis = axis;
+        t.bin = -2; /* k_flags: the leaf to one side, the rest to the other */
+        t.apartLeaf = leaf;
+        t.lowSide = lowSide;
+        t.mid = lowSide ? t.from + 1 : t.to - 1;
+        const int left = nextFree + 2 * atomicAdd(splitting, 1);
+        t.left = left;
+        t.right = left + 1;
+        nodes[left].from = t.from;
+        nodes[left].to = t.mid;
+        nodes[left + 1].from = t.mid;
+        nodes[left + 1].to = t.to;
+        return;
+    }
     const BinSet &b = bins[i];
     int bestAxis = -1, bestBin = 0;
     double bestCost = 1e300;
@@ -442,7 +508,9 @@ __global__ void k_flags(const Node *nodes, const int *nodeOf, const int *order, 
     if (t >= levelFirst && nodes[t].split)
     {
         const Node &node = nodes[t];
-        if (node.bin < 0)
+        if (node.bin == -2)
+            f = (order[i] == node.apartLeaf) == (node.lowSide != 0);
+        else if (node.bin < 0)
             f = i < node.mid;
         else
         {
@@ -490,6 +558,17 @@ __global__ __launch_bounds__(256) void k_prune(Node *nodes, const int *order, co
     if (node.leaf >= 0)
         return;
     const int ancestor = node.keptAncestor;
+    if (node.apart)
+    {
+        /* never emitted, so never in the list the host decides on: its children look past it */
+        if (threadIdx.x == 0)
+        {
+            node.keep = 0;
+            nodes[node.left].keptAncestor = ancestor;
+            nodes[node.right].keptAncestor = ancestor;
+        }
+        return;
+    }
     const int parentFrom = ancestor < 0 ? 0 : nodes[ancestor].from, parentTo = ancestor < 0 ? nbLeaves : nodes[ancestor].to;
     if (threadIdx.x == 0)
         inside = sampled = 0;
@@ -517,7 +596,7 @@ __global__ __launch_bounds__(256) void k_prune(Node *nodes, const int *order, co
     const double parentArea = ancestor < 0 ? areaOf(nodes[0].lo, nodes[0].hi) : areaOf(nodes[ancestor].lo, nodes[ancestor].hi);
     const double bySurface = parentArea > 0.0 ? fmin(1.0, areaOf(node.lo, node.hi) / parentArea) : 1.0;
     const double byOrigin = sampled ? (double)inside / sampled : 1.0;
-    const int below = 2 * (node.to - node.from) - 2; /* nodes under it in the unpruned list */
+    const int below = node.size - 1; /* nodes under it in the unpruned list (k_sizes before any decision) */
     const bool prune = (1.0 - fmax(bySurface, byOrigin)) * below < threshold;
     node.keep = prune ? 0 : 1;
     if (prune)
@@ -534,6 +613,29 @@ __global__ void k_sizes(Node *nodes, int levelFirst, int count)
         return;
     Node &t = nodes[levelFirst + i];
     t.size = t.leaf >= 0 ? 1 : (t.keep ? 1 : 0) + nodes[t.left].size + nodes[t.right].size;
+}
+
+/* what an inner node is emitted with on build bounds: the union of its leaves' boxes as uploaded, zeros +0 like the
+ * host's; bottom-up per level */
+__global__ void k_unions(Node *nodes, const float4 *leafRows, int levelFirst, int count)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count)
+        return;
+    Node &t = nodes[levelFirst + i];
+    if (t.leaf >= 0)
+    {
+        const float4 a = leafRows[2 * t.leaf], b = leafRows[2 * t.leaf + 1];
+        t.ulo[0] = a.x, t.ulo[1] = a.y, t.ulo[2] = a.z;
+        t.uhi[0] = b.x, t.uhi[1] = b.y, t.uhi[2] = a.w;
+        return;
+    }
+    const Node &l = nodes[t.left], &r = nodes[t.right];
+    for (int k = 0; k < 3; ++k)
+    {
+        t.ulo[k] = fminf(l.ulo[k], r.ulo[k]) + 0.f;
+        t.uhi[k] = fmaxf(l.uhi[k], r.uhi[k]) + 0.f;
+    }
 }
 
 __global__ void k_places(const Node *nodes, int *place, int levelFirst, int count)
@@ -553,7 +655,7 @@ __global__ void k_places(const Node *nodes, int *place, int levelFirst, int coun
 }
 
 __global__ void k_emit(const Node *nodes, const int *place, const float4 *leafRows, const int *leafStart, const int *leafOrigin,
-                       float4 *outRows, int *outStart, int *outOrigin, int nbNodes, int listLength)
+                       float4 *outRows, int *outStart, int *outOrigin, int nbNodes, int listLength, int uploaded)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nbNodes * 8)
@@ -574,8 +676,9 @@ __global__ void k_emit(const Node *nodes, const int *place, const float4 *leafRo
     }
     if (!node.keep)
         return;
-    rows[2 * at] = make_float4(node.lo[0], node.lo[1], node.lo[2], node.hi[2]);
-    rows[2 * at + 1] = make_float4(node.hi[0], node.hi[1], __int_as_float(0), __int_as_float(node.size));
+    const float *lo = uploaded ? node.ulo : node.lo, *hi = uploaded ? node.uhi : node.hi;
+    rows[2 * at] = make_float4(lo[0], lo[1], lo[2], hi[2]);
+    rows[2 * at + 1] = make_float4(hi[0], hi[1], __int_as_float(0), __int_as_float(node.size));
     outStart[(size_t)octant * listLength + at] = 0;
     outOrigin[(size_t)octant * listLength + at] = -1;
 }
@@ -595,7 +698,7 @@ __global__ void k_leafFlags(const float4 *rows, int n, int *flags)
         flags[i] = i < n && __float_as_int(rows[2 * i + 1].z) > 0 ? 1 : 0;
 }
 __global__ void k_leafGather(const float4 *rows, const int *start, const int *before, int n, float *lo, float *hi, float4 *leafRows,
-                             int *leafStart, int *leafOrigin)
+                             int *leafStart, int *leafOrigin, const float4 *prims, float margin, int *anyThin)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
@@ -604,8 +707,9 @@ __global__ void k_leafGather(const float4 *rows, const int *start, const int *be
     if (__float_as_int(b.z) <= 0)
         return;
     const int l = before[i];
-    lo[3 * l] = a.x, lo[3 * l + 1] = a.y, lo[3 * l + 2] = a.z;
-    hi[3 * l] = b.x, hi[3 * l + 1] = b.y, hi[3 * l + 2] = a.w;
+    /* the box the hierarchy is built on (build_bounds.h; without primitive records: the box as uploaded) */
+    if (solreng::leafBuildBounds(a, b, prims, start[i], __float_as_int(b.z), margin, lo + 3 * l, hi + 3 * l))
+        *anyThin = 1; /* (every writer writes the same value) */
     leafRows[2 * l] = a;
     leafRows[2 * l + 1] = b;
     leafStart[l] = start[i];
@@ -619,7 +723,7 @@ inline dim3 blocksFor(size_t n, int block = 256)
 } // namespace
 
 int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const int *origin, int n, double threshold,
-                                    int *nbPruned, hipStream_t stream, SolrDeviceLists *stay)
+                                    int *nbPruned, hipStream_t stream, SolrDeviceLists *stay, const solreng::BuildBounds &build)
 {
     *nbPruned = 0;
     Phase phase;
@@ -650,6 +754,7 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
     Dev<int> dLeafFlags, dLeafBefore;
     Dev<char> dLeafTemp;
     int L = 0;
+    int anyThin = 0; /* a leaf is built on another box than its own: only then is anything built differently */
     if (origin == nullptr)
     {
         /* rows and start are the arena's (device memory), every node its own origin */
@@ -672,8 +777,11 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
             memcpy(&count, &rows[2 * i + 1].z, 4);
             if (count <= 0)
                 continue;
-            llo.insert(llo.end(), {rows[2 * i].x, rows[2 * i].y, rows[2 * i].z});
-            lhi.insert(lhi.end(), {rows[2 * i + 1].x, rows[2 * i + 1].y, rows[2 * i].w});
+            float blo[3], bhi[3];
+            if (solreng::leafBuildBounds(rows[2 * i], rows[2 * i + 1], build.prims, start[i], count, build.margin, blo, bhi))
+                anyThin = 1;
+            llo.insert(llo.end(), {blo[0], blo[1], blo[2]});
+            lhi.insert(lhi.end(), {bhi[0], bhi[1], bhi[2]});
             leafRows.push_back(rows[2 * i]);
             leafRows.push_back(rows[2 * i + 1]);
             leafStart.push_back(start[i]);
@@ -694,7 +802,7 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
     if (!dLo.alloc(3 * (size_t)L) || !dHi.alloc(3 * (size_t)L) || !dLeafRows.alloc(2 * (size_t)L) || !dLeafStart.alloc(L) ||
         !dLeafOrigin.alloc(L) || !dOrder[0].alloc(L) || !dOrder[1].alloc(L) || !dNodeOf[0].alloc(L) || !dNodeOf[1].alloc(L) ||
         !dFlags.alloc((size_t)L + 1) || !dBefore.alloc((size_t)L + 1) || !dNodes.alloc(maxNodes) ||
-        !dBins.alloc(L) || !dPlace.alloc(8 * (size_t)maxNodes) || !dPruned.alloc(2))
+        !dBins.alloc(L) || !dPlace.alloc(8 * (size_t)maxNodes) || !dPruned.alloc(3))
         return -1;
     size_t tempBytes = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tempBytes, dFlags.p, dBefore.p, L + 1, stream);
@@ -702,8 +810,16 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
         return -1;
     phase.mark("allocations");
     if (origin == nullptr)
+    {
+        LISTS_CHECK(hipMemsetAsync(dPruned.p + 2, 0, 4, stream));
         hipLaunchKernelGGL(k_leafGather, blocksFor(n), dim3(256), 0, stream, rows, start, dLeafBefore.p, n, dLo.p, dHi.p, dLeafRows.p,
-                           dLeafStart.p, dLeafOrigin.p);
+                           dLeafStart.p, dLeafOrigin.p, build.prims, build.margin, dPruned.p + 2);
+        if (build.prims)
+        {
+            LISTS_CHECK(hipMemcpyAsync(&anyThin, dPruned.p + 2, 4, hipMemcpyDeviceToHost, stream));
+            LISTS_CHECK(hipStreamSynchronize(stream));
+        }
+    }
     else
     {
         LISTS_CHECK(hipMemcpyAsync(dLo.p, llo.data(), llo.size() * 4, hipMemcpyHostToDevice, stream));
@@ -712,6 +828,9 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
         LISTS_CHECK(hipMemcpyAsync(dLeafStart.p, leafStart.data(), (size_t)L * 4, hipMemcpyHostToDevice, stream));
         LISTS_CHECK(hipMemcpyAsync(dLeafOrigin.p, leafOrigin.data(), (size_t)L * 4, hipMemcpyHostToDevice, stream));
     }
+    /* as the host: build bounds change something only where a leaf has a box of its own */
+    const bool onBuildBounds = build.prims != nullptr && anyThin != 0;
+    const double share = onBuildBounds ? build.dominantShare : 0.0;
     LISTS_CHECK(hipMemsetAsync(dPruned.p, 0, 4, stream));
     hipLaunchKernelGGL(k_iota, blocksFor(L), dim3(256), 0, stream, dOrder[0].p, L, 0, true);
     hipLaunchKernelGGL(k_iota, blocksFor(L), dim3(256), 0, stream, dNodeOf[0].p, L, 0, false);
@@ -734,8 +853,12 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
         hipLaunchKernelGGL(k_open, blocksFor(count, 64), dim3(64), 0, stream, dNodes.p, dBins.p, first, count);
         hipLaunchKernelGGL(k_bounds, blocksFor(L), dim3(256), 0, stream, dNodes.p, dNodeOf[cur].p, dOrder[cur].p, dLo.p, dHi.p, L, first);
         hipLaunchKernelGGL(k_bins, blocksFor(L), dim3(256), 0, stream, dNodes.p, dBins.p, dNodeOf[cur].p, dOrder[cur].p, dLo.p, dHi.p, L, first);
+        if (share > 0.0)
+            for (int pass = 0; pass < 2; ++pass)
+                hipLaunchKernelGGL(k_largest, blocksFor(L), dim3(256), 0, stream, dNodes.p, dNodeOf[cur].p, dOrder[cur].p, dLo.p, dHi.p, L, first, pass);
         LISTS_CHECK(hipMemsetAsync(dPruned.p + 1, 0, 4, stream));
-        hipLaunchKernelGGL(k_split, blocksFor(count, 64), dim3(64), 0, stream, dNodes.p, dBins.p, first, count, nextFree, dPruned.p + 1);
+        hipLaunchKernelGGL(k_split, blocksFor(count, 64), dim3(64), 0, stream, dNodes.p, dBins.p, first, count, nextFree, dPruned.p + 1,
+                           dOrder[cur].p, dLo.p, dHi.p, share);
         int splitting = 0;
         LISTS_CHECK(hipMemcpyAsync(&splitting, dPruned.p + 1, 4, hipMemcpyDeviceToHost, stream));
         LISTS_CHECK(hipStreamSynchronize(stream));
@@ -756,12 +879,18 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
     const int nbNodes = nextFree;
     const int levels = (int)levelFirst.size();
     phase.mark("tree, level by level", levels);
+    /* the sizes in the list the decisions are made on: every inner node but those with a leaf set apart */
+    for (int d = levels - 1; d >= 0; --d)
+        hipLaunchKernelGGL(k_sizes, blocksFor(levelCount[d]), dim3(256), 0, stream, dNodes.p, levelFirst[d], levelCount[d]);
     /* which inner nodes stay: top-down */
     for (int d = 0; d < levels; ++d)
         hipLaunchKernelGGL(k_prune, dim3((unsigned)levelCount[d]), dim3(256), 0, stream, dNodes.p, dOrder[cur].p, dLo.p, dHi.p, levelFirst[d],
                            levelCount[d], threshold, L, dPruned.p);
     for (int d = levels - 1; d >= 0; --d)
         hipLaunchKernelGGL(k_sizes, blocksFor(levelCount[d]), dim3(256), 0, stream, dNodes.p, levelFirst[d], levelCount[d]);
+    if (onBuildBounds)
+        for (int d = levels - 1; d >= 0; --d)
+            hipLaunchKernelGGL(k_unions, blocksFor(levelCount[d]), dim3(256), 0, stream, dNodes.p, dLeafRows.p, levelFirst[d], levelCount[d]);
     LISTS_CHECK(hipMemsetAsync(dPlace.p, 0, 8 * sizeof(int), stream)); /* the root sits at 0 in every list */
     for (int d = 0; d < levels; ++d)
         hipLaunchKernelGGL(k_places, blocksFor((size_t)levelCount[d] * 8), dim3(256), 0, stream, dNodes.p, dPlace.p, levelFirst[d], levelCount[d]);
@@ -777,7 +906,7 @@ int solrBuildOrderFreeListsOnDevice(const float4 *rows, const int *start, const 
         !dOutOrigin.allocOwn(8 * (size_t)listLength))
         return -1;
     hipLaunchKernelGGL(k_emit, blocksFor((size_t)nbNodes * 8), dim3(256), 0, stream, dNodes.p, dPlace.p, dLeafRows.p, dLeafStart.p, dLeafOrigin.p,
-                       dOutRows.p, dOutStart.p, dOutOrigin.p, nbNodes, listLength);
+                       dOutRows.p, dOutStart.p, dOutOrigin.p, nbNodes, listLength, onBuildBounds ? 1 : 0);
     LISTS_CHECK(hipGetLastError());
     LISTS_CHECK(hipStreamSynchronize(stream));
 #undef LISTS_CHECK
