@@ -60,7 +60,9 @@ def assert_parity_pinned(gpu, ora, misround, max_exceptions, what="", marked_bou
     sphere's hit point, and a mis-rounded atan2f / asinf that lands on the other side of a texel boundary selects the
     NEIGHBOURING texel of every map of the material (diffuse, normal, bump ...: TextureMapping.cuh:30-116 fetches them
     all at the diffuse map's index) - what such a pixel shows is another texel's shading, not a rounding of this one's.
-    Those tests say so, pass None and keep the count."""
+    Those tests say so, pass None and keep the count.
+    max_exceptions = None: as many as the oracle marked in this frame (the cap then lies with the reference alone: a test
+    that passes None bounds the marked count of its frames on the CPU)."""
     gpu_pp, gpu_ids, gpu_rgb = gpu
     ora_pp, ora_ids, ora_rgb = ora
     res = compare_frames(gpu_pp, gpu_ids, gpu_rgb, ora_pp, ora_ids, ora_rgb)
@@ -80,6 +82,8 @@ def assert_parity_pinned(gpu, ora, misround, max_exceptions, what="", marked_bou
         assert (ulp[outside] <= marked_bounds[0]).all(), res
     if marked_bounds[1] is not None:
         assert (rgb[outside] <= marked_bounds[1]).all(), res
+    if max_exceptions is None:
+        max_exceptions = res["pixels_with_a_misrounded_libm_result"]
     assert res["pixels_outside_the_bar"] <= max_exceptions, res
     return res
 
@@ -119,6 +123,47 @@ def assert_pass_parity(k, oracle, gpu, previous, max_exceptions=2, what="", firs
                                               misround=misround)
     assert status == 0, "the oracle read outside the random buffer"
     return assert_parity_pinned(gpu, (opp, oids, orgb), misround, max_exceptions, what)
+
+
+def copy_frame(frame):
+    return tuple(np.array(a, copy=True) for a in frame)
+
+
+def same_frames(a, b):
+    """two engine frames (pp, ids, rgb) bit for bit"""
+    return (np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1], b[1]) and
+            np.array_equal(a[2], b[2]))
+
+
+def tiles(mask, tile=8):
+    """per tile x tile tile of a (H, W) boolean mask: (pixels of the tile, pixels of it that are set)"""
+    out = []
+    for y in range(0, mask.shape[0], tile):
+        for x in range(0, mask.shape[1], tile):
+            t = mask[y:y + tile, x:x + tile]
+            out.append((t.size, int(t.sum())))
+    return out
+
+
+def render_passes(k, oracle, passes, max_exceptions=2, after_pass=None):
+    """the passes (pathTracingIteration) of kernel k one after the other, each held to the oracle as pinned over the
+    engine's buffers of the pass before (assert_frame_pinned for a first pass, assert_pass_parity afterwards).
+    after_pass(pass): called when a pass has been rendered and read back, before it is compared.
+    Returns (frames, figures of assert_parity_pinned), one of each per pass."""
+    previous = None
+    frames, figures = [], []
+    for it in passes:
+        k.set_scene_info(pathTracingIteration=it)
+        frame = copy_frame(gpu_frame(k))
+        if after_pass is not None:
+            after_pass(it)
+        if previous is None:
+            figures.append(assert_frame_pinned(k, oracle, frame, max_exceptions, "pass %d" % it))
+        else:
+            figures.append(assert_pass_parity(k, oracle, frame, previous, max_exceptions, "pass %d" % it))
+        previous = (frame[0], frame[1])
+        frames.append(frame)
+    return frames, figures
 
 
 def f3(*v):

@@ -9,7 +9,8 @@ the same frames with solr_hip_set_variant(16), which makes every trip."""
 import numpy as np
 import pytest
 
-from helpers import assert_frame_pinned, assert_pass_parity, gpu_frame, oracle_frame
+from helpers import assert_frame_pinned, gpu_frame, oracle_frame, render_passes
+from helpers import copy_frame as _copy, same_frames as _same_frames, tiles as _tiles
 
 pytestmark = pytest.mark.gpu
 
@@ -17,25 +18,6 @@ W, H = 76, 44            # 10 x 6 tiles of 8 x 8, the last column 4 pixels wide,
 TILE = 8
 NB_MAX_ITERATIONS = 10   # include/solr_types.h
 ALL_TRIPS = 16           # include/solr_hip.h solr_hip_set_variant
-
-
-def _copy(frame):
-    return tuple(np.array(a, copy=True) for a in frame)
-
-
-def _same_frames(a, b):
-    return (np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1], b[1]) and
-            np.array_equal(a[2], b[2]))
-
-
-def _tiles(mask):
-    """per 8 x 8 tile of a (H, W) boolean mask: (pixels of the tile, pixels of it that are set)"""
-    out = []
-    for y in range(0, mask.shape[0], TILE):
-        for x in range(0, mask.shape[1], TILE):
-            t = mask[y:y + TILE, x:x + TILE]
-            out.append((t.size, int(t.sum())))
-    return out
 
 
 def _kinds(k, ids):
@@ -141,19 +123,6 @@ def test_graphics_levels(solr, oracle, level):
         k.finalize()
 
 
-def _passes(solr, oracle, k, passes):
-    """the passes one after the other, each held to the oracle over the engine's buffers of the pass before"""
-    previous = None
-    frames = []
-    for it in passes:
-        k.set_scene_info(pathTracingIteration=it)
-        frame = _copy(gpu_frame(k))
-        assert_pass_parity(k, oracle, frame, previous, what="pass %d" % it)
-        previous = (frame[0], frame[1])
-        frames.append(frame)
-    return frames
-
-
 GI_PASSES = (0, 1, 2, 3, NB_MAX_ITERATIONS, NB_MAX_ITERATIONS + 1)
 
 
@@ -165,7 +134,7 @@ def test_gi_pass_a_dead_phase_1_still_reaches_phase_2(solr, oracle, illumination
     solr.scenes.cornell(k, width=W, height=H, iterations=1, glass=glass, maxPathTracingIterations=40,
                         advancedIllumination=getattr(solr, illumination))
     try:
-        frames = _passes(solr, oracle, k, GI_PASSES)
+        frames, _ = render_passes(k, oracle, GI_PASSES)
         assert not np.array_equal(frames[-2][2], frames[0][2])
     finally:
         k.finalize()
@@ -175,7 +144,7 @@ def test_refinement_passes_take_the_first_hit_s_index_from_the_handed_over_word(
     k = solr.Kernel(engine="hip")
     solr.scenes.cornell(k, width=W, height=H, iterations=1)
     try:
-        frames = _passes(solr, oracle, k, (0, 1, 2, 3))
+        frames, _ = render_passes(k, oracle, (0, 1, 2, 3))
         assert not np.array_equal(frames[0][2], frames[3][2])
         assert (frames[0][1][..., 0] >= 0).all()          # the closed room: every pixel has a first hit, and its index
     finally:
