@@ -543,6 +543,27 @@ int solr_hip_device_rotations(void);
 int solr_hip_read_nodes(int exact, float *rows, int capacityRows);
 int solr_hip_read_primitives(float *rows, int capacityRows);
 
+/* Deforming scenes.  The reference blends the first and the last key frame into the frames between them on the host
+ * (GPUKernel::morphPrimitives, GPUKernel.cpp:1513-1572) and shows them by switching frames and flattening again - a full
+ * upload per displayed frame.  A frame between the keys keeps the shape of its flattened tree when it is blended at another
+ * weight, so the engine can blend the resident scene in place (GPUKernel::morphFrame on the host):
+ *   solr_hip_set_morph_keys     after h2d_scene: the first and the last key frame, nbPrimitives records each in the
+ *                               flattened order of the resident scene (of a record only p0 p1 p2 n0 n1 n2 size are
+ *                               read).  Valid until the next h2d_scene.  1 when the keys are in place, else 0;
+ *   solr_hip_morph_primitives   every resident primitive set to `first + weight * (last - first)` the way the host loop
+ *                               sets it (setPrimitive's sizes and mid-points per type, setPrimitiveNormals' normalised
+ *                               normals; tag, material, index and texture coordinates stay), then the lists refitted as
+ *                               after a rotation.  viewDistance: sceneInfo.viewDistance.  Returns 1 when the resident
+ *                               scene now holds, bit for bit, what the host loop + a fresh h2d_scene would have
+ *                               produced, 0 when it cannot serve the request - whatever solr_hip_rotate_primitives
+ *                               refuses, no keys or keys for another number of primitives, a weight that is not finite,
+ *                               a primitive of an emissive material whose keys differ (the light table would have to
+ *                               follow): nothing changed, take the host route;
+ *   solr_hip_device_morphs      how many requests were served since initialize_scene. */
+int solr_hip_set_morph_keys(const Primitive *first, const Primitive *last, int nbPrimitives);
+int solr_hip_morph_primitives(float weight, float viewDistance);
+int solr_hip_device_morphs(void);
+
 /* Bytes of HBM this engine currently holds for {scene planes, materials,
  * textures, per-pixel buffers}; for DESIGN.md's layout table and tests. */
 void solr_hip_memory_usage(unsigned long long bytes[4]);

@@ -253,6 +253,11 @@ def _declare_hip(L):
     L.solr_hip_rotate_primitives.argtypes = [P(C.c_float), P(C.c_float), P(C.c_float), C.c_float]
     L.solr_hip_rotate_primitives.restype = C.c_int
     L.solr_hip_device_rotations.restype = C.c_int
+    L.solr_hip_set_morph_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.solr_hip_set_morph_keys.restype = C.c_int
+    L.solr_hip_morph_primitives.argtypes = [C.c_float, C.c_float]
+    L.solr_hip_morph_primitives.restype = C.c_int
+    L.solr_hip_device_morphs.restype = C.c_int
     L.solr_hip_read_nodes.argtypes = [C.c_int, C.c_void_p, C.c_int]
     L.solr_hip_read_nodes.restype = C.c_int
     L.solr_hip_read_primitives.argtypes = [C.c_void_p, C.c_int]
@@ -345,6 +350,9 @@ def _declare_host(L):
     L.SolR_LoadMolecule.argtypes = [C.c_char_p, i, d, d, i, d]
     L.SolR_LoadOBJModel.argtypes = [C.c_char_p, i, i, d, i, P(d)]
     L.SolRx_LoadSWCMorphology.argtypes = [C.c_char_p] + [d] * 7 + [i]
+    L.SolRx_SetNbFrames.argtypes = [i]
+    L.SolRx_SetFrame.argtypes = [i]
+    L.SolRx_MorphFrame.argtypes = [d]
 
 
 def _np_from_ptr(ptr, count, dtype):
@@ -473,6 +481,10 @@ class Kernel:
                                  size[1], size[2], material)
         return idx
 
+    def set_movable(self, idx, movable):
+        """GPUKernel::setPrimitiveIsMovable, after add_primitive (SolR_SetPrimitive makes a primitive movable)"""
+        self.L.SolRx_SetPrimitiveIsMovable(idx, int(bool(movable)))
+
     def reset_frame(self):
         """GPUKernel::resetFrame: drop the frame's primitives, boxes and lamps; materials and textures stay"""
         self.L.SolRx_ResetFrame()
@@ -546,6 +558,32 @@ class Kernel:
 
     def pending_rotations(self):
         return self.L.SolRx_PendingRotations()
+
+    # -- key frames ---------------------------------------------------------------------
+    def set_nb_frames(self, n):
+        """GPUKernel::setNbFrames: the scene has frames 0 ... n - 1; the first and the last are the key frames"""
+        return self.L.SolRx_SetNbFrames(n)
+
+    def set_frame(self, frame):
+        """GPUKernel::setFrame: the frame that primitives are added to, flattened and rendered; returns it"""
+        return self.L.SolRx_SetFrame(frame)
+
+    def morph_primitives(self):
+        """GPUKernel::morphPrimitives: every frame between the key frames rebuilt as their blend at weight
+        frame / nbFrames, each with a tree of its own; returns the frame that is current afterwards (the last one
+        made)"""
+        return self.L.SolRx_MorphPrimitives()
+
+    def morph_frame(self, weight):
+        """The current frame - one between the key frames - blended anew at any finite weight (SolRx_MorphFrame): every
+        primitive set in place to first + weight * (last - first) the way morph_primitives sets it, the tree kept in
+        shape and refitted.  With the HIP engine and an unchanged resident scene the blend runs on the device and the
+        host copy follows lazily (pending_morph).  0 when done, -1 when refused (nothing changed)."""
+        return self.L.SolRx_MorphFrame(weight)
+
+    def pending_morph(self):
+        """a morph was applied on the device that the host scene store has not replayed yet"""
+        return bool(self.L.SolRx_PendingMorph())
 
     def sync_host(self):
         self.L.SolRx_SyncHost()

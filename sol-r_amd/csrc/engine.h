@@ -1,11 +1,12 @@
 /*
  * engine.h - the state of the MI355X rendering engine and the helpers every part of its host side uses: what
  * solr_hip.hip (the boundary), solr_uploads.hip (the h2d_* uploads), solr_arena.hip (the arena and the node lists; their
- * host builders: list_builders.h), solr_rotation.hip (rotation and refit on the device), solr_launch.hip (the renderer's
+ * host builders: list_builders.h), solr_rotation.hip (rotation and refit on the device), solr_morph.hip (key-frame
+ * morphing on the device), solr_launch.hip (the renderer's
  * launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined read-back), solr_rccl.hip (strips,
  * communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
- * NodeList (a node list of the resident scene), Scene with Arena, OrderFreeState and Rotation, Lights, Materials, Textures,
+ * NodeList (a node list of the resident scene), Scene with Arena, OrderFreeState, Rotation and Morph, Lights, Materials, Textures,
  * Randoms and SceneFacts (the resident scene, cut by who writes them), KernelTimer, WalkRecording, TileSchedule (the
  * cost-ordered launch), Flight (a frame in flight: its stream and per-pixel buffers; Engine::flight[0] is the one of a
  * process that renders one frame at a time), CopyLane (the device's part of the pipelined read-back) and ImageStreaming (a
@@ -389,6 +390,17 @@ struct Rotation
     float exactStaleViewDistance = 0.f;
     int nbDeviceRotations = 0;
 };
+/* Key-frame morphing on the device (solr_hip_set_morph_keys, solr_hip_morph_primitives; solr_morph.hip): the two key
+ * frames of the resident scene.  Written by setMorphKeysOne and the transitions of Scene; an h2d_scene drops the keys. */
+struct Morph
+{
+    DeviceBuffer first, last;              /* seven planes of nbKeys float4 each: p0 p1 p2 n0 n1 n2 size */
+    int nbKeys = -1;                       /* keys uploaded for that many primitives, -1: none */
+    std::vector<unsigned char> keysDiffer; /* per primitive: its two keys differ in some bit */
+    long lampChecked = -1;                 /* Scene::retags when lampMoves was worked out, -1: not yet */
+    bool lampMoves = false;                /* a primitive tagged PRIM_EMISSIVE has keys that differ: not served here */
+    int nbDeviceMorphs = 0;
+};
 /* The scene proper: what h2d_scene replaces and finalize_scene drops, with the arena it is resident in. */
 struct Scene
 {
@@ -406,11 +418,13 @@ struct Scene
     bool walkEncloses = false;
     OrderFreeState lists;
     Rotation rotation;
+    Morph morph;
+    long retags = 0; /* how often retagPrimitives has run: what was derived from the tags is as old as that */
     Arena arena;
 
     /* h2d_scene has new host images of the lists and the primitives (swapped in by the caller): nothing that was made
-     * from the old ones holds.  The movable flags go, the count of rotations stays; the arena follows with
-     * retagPrimitives (layOutAgain) */
+     * from the old ones holds.  The movable flags and the morph keys go, the counts of rotations and morphs stay; the
+     * arena follows with retagPrimitives (layOutAgain) */
     void newGeometry(int nested_, bool walkEncloses_, int freeCountdown_)
     {
         nested = nested_;
@@ -419,6 +433,7 @@ struct Scene
         rotation.exactStale = false;
         rotation.refitPlanPending = true;
         rotation.nbMovable = -1;
+        morphKeysDropped();
         arena.deviceAhead = false;
         orderFree.reset();
         lists.freeCountdown = freeCountdown_;
@@ -472,8 +487,8 @@ struct Scene
         lists.dropStage(true);
     }
     void hostImagesPulled() { arena.deviceAhead = false; }
-    /* rotatePrimitivesOne has queued a rotation and the refit of the walk-order list (listsFollow: of the order-free
-     * lists too; without a plan for them, rotated scenes walk the reference's order until the next upload); the
+    /* refitMovedScene - behind a rotation or a morph - has queued the refit of the walk-order list (listsFollow: of the order-free
+     * lists too; without a plan for them, moved scenes walk the reference's order until the next upload); the
      * reference's own list follows when somebody needs it (refreshExactList) */
     void rotationQueued(bool listsFollow, float viewDistance)
     {
@@ -493,11 +508,45 @@ struct Scene
             ++rotation.nbDeviceRotations;
         }
     }
+    /* retagPrimitives has joined the materials' facts into the primitives' tags again */
+    void retagged() { ++retags; }
+    /* the morph keys: none (the buffers stay for the next ones) / uploaded for nbKeys primitives */
+    void morphKeysDropped()
+    {
+        morph.nbKeys = -1;
+        morph.keysDiffer.clear();
+        morph.lampChecked = -1;
+        morph.lampMoves = false;
+    }
+    void morphKeysSet(int nbKeys, std::vector<unsigned char> &keysDiffer)
+    {
+        morph.nbKeys = nbKeys;
+        morph.keysDiffer.swap(keysDiffer);
+        morph.lampChecked = -1;
+    }
+    /* canMorphOne has asked the tags as they are now whether a lamp's keys differ */
+    void morphLampChecked(bool moves)
+    {
+        morph.lampMoves = moves;
+        morph.lampChecked = retags;
+    }
+    /* morphPrimitivesOne has blended the keys into the primitives and refitted the lists (rotationQueued); walkHolds,
+     * landed: as for a rotation */
+    void morphServed(bool walkHolds, bool landed)
+    {
+        walkEncloses = walkHolds;
+        if (landed)
+        {
+            arena.deviceAhead = true;
+            ++morph.nbDeviceMorphs;
+        }
+    }
     /* finalize_scene */
     void release()
     {
         lists.dropStage(true);
-        for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag})
+        for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag, &morph.first,
+                                &morph.last})
             solreng::release(*b);
         *this = Scene();
     }
@@ -818,7 +867,12 @@ bool deepNodeList(const SceneArgs &S);
 /* solr_rotation.hip: rotation and refit on the device */
 bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
 int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
+bool refitMovedScene(float viewDistance);
 void refreshExactList();
+/* solr_morph.hip: key-frame morphing on the device */
+int setMorphKeysOne(const Primitive *first, const Primitive *last, int nbPrimitives);
+bool canMorphOne(float weight, float viewDistance);
+int morphPrimitivesOne(float weight, float viewDistance);
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */
 void allocateFrame();
 int neededFeatures(const SceneInfo &sceneInfo, bool full);

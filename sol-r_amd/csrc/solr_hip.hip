@@ -605,5 +605,28 @@ int solr_hip_rotate_primitives(const float center[3], const float cosAngles[3], 
     });
     return status;
 }
+
+int solr_hip_set_morph_keys(const Primitive *first, const Primitive *last, int nbPrimitives)
+{
+    int status = 1;
+    onEveryDevice([&](int) { status = setMorphKeysOne(first, last, nbPrimitives) && status; });
+    return status;
 }
 
+/* (every in-process device holds the scene and the keys and morphs its own copy; 1 only when all of them did) */
+int solr_hip_morph_primitives(float weight, float viewDistance)
+{
+    /* as for a rotation: every resident copy must be able to follow before any of them moves */
+    bool all = true;
+    onEveryDevice([&](int) { all = canMorphOne(weight, viewDistance) && all; });
+    if (!all)
+        return 0;
+    int status = 1; /* 1: morphed on the device */
+    onEveryDevice([&](int) {
+        const int mine = morphPrimitivesOne(weight, viewDistance);
+        if (mine != 1 && status == 1)
+            status = mine;
+    });
+    return status;
+}
+}

@@ -231,6 +231,27 @@ void refreshExactList()
     g.scene.exactRefitted();
 }
 
+/* A kernel that moves the resident primitives (k_rotatePrimitives; solr_morph.hip k_morphPrimitives) is queued on the scene
+ * stream: what follows it, for a rotation and a morph alike - the refit of the walk-order list and, where they can follow, of
+ * the order-free lists, the reference's list marked stale, the leaf records and the copies behind the lists, the enclosure
+ * check, one synchronisation of the scene stream.  Returns whether the walk-order list still holds what it names. */
+bool refitMovedScene(float viewDistance)
+{
+    refitList(g.scene.walk, viewDistance);
+    const bool listsFollow = g.scene.orderFree.nb > 0 && !g.scene.orderFree.refitLevels.empty();
+    if (listsFollow)
+        refitList(g.scene.orderFree, viewDistance);
+    g.scene.rotationQueued(listsFollow, viewDistance);
+    buildLeafRecords(); /* the leaves' copies of their first primitive follow the primitives */
+    /* the refitted list encloses by construction (k_refitNodes); asked all the same, like any list the walks cut off at
+     * the lamp (a scene that failed the check at its upload is not asked again) */
+    const bool walkHolds = g.scene.walkEncloses && listEnclosesInArena(g.scene.walk);
+    HIPCHECK(hipGetLastError());
+    /* the other flights' streams start their next frame only after this */
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
+    return walkHolds;
+}
+
 /* Extension: GPUKernel::rotatePrimitives + compactBoxes(false) + h2d_scene on the resident scene
  * (GPUKernel.cpp:1378-1460, 1151-1281 of the reference), see k_rotatePrimitives.  Returns 1 when the
  * arena now holds the rotated scene, 0 when the request cannot be served here and the caller has to
@@ -275,18 +296,7 @@ int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const f
     hipLaunchKernelGGL(k_rotatePrimitives, dim3((unsigned)((g.scene.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
                        (const unsigned char *)g.scene.rotation.movable.ptr, R);
-    refitList(g.scene.walk, viewDistance);
-    const bool listsFollow = g.scene.orderFree.nb > 0 && !g.scene.orderFree.refitLevels.empty();
-    if (listsFollow)
-        refitList(g.scene.orderFree, viewDistance);
-    g.scene.rotationQueued(listsFollow, viewDistance);
-    buildLeafRecords(); /* the leaves' copies of their first primitive follow the primitives */
-    /* the refitted list encloses by construction (k_refitNodes); asked all the same, like any list the walks cut off at
-     * the lamp (a scene that failed the check at its upload is not asked again) */
-    const bool walkHolds = g.scene.walkEncloses && listEnclosesInArena(g.scene.walk);
-    HIPCHECK(hipGetLastError());
-    /* the other flights' streams start their next frame only after this */
-    HIPCHECK(hipStreamSynchronize(sceneStream()));
+    const bool walkHolds = refitMovedScene(viewDistance);
     g.scene.rotationServed(walkHolds, ok());
     return ok() ? 1 : 0;
 }

@@ -139,6 +139,7 @@ void retagPrimitives()
     g.facts.sceneFeatures = features;
     g.facts.primsContained = contained && n > 0;
     g.facts.opaqueShadows = opaque && n > 0;
+    g.scene.retagged();
     g.scene.arena.layOutAgain();
 }
 

@@ -593,9 +593,9 @@ int GPUKernel::processOutterBoxes(const int boxSize, const int boundingBoxesDept
 /* reference: GPUKernel.cpp:1041-1083 */
 int GPUKernel::compactBoxes(bool reconstructBoxes)
 {
-    /* rotations applied on the device: the flattened scene over there is already what the lines below
-     * would produce and upload */
-    if (!reconstructBoxes && (!m_pendingRotations.empty() || m_unrecordedRotations))
+    /* rotations or a morph applied on the device: the flattened scene over there is already what the lines
+     * below would produce and upload */
+    if (!reconstructBoxes && (!m_pendingRotations.empty() || m_unrecordedRotations || m_morphPending))
         return frameAsIs().nbActiveBoxes;
     m_primitivesTransfered = false;
     if (reconstructBoxes)
@@ -981,6 +981,125 @@ void GPUKernel::morphPrimitives()
     }
 }
 
+bool GPUKernel::morphKeysMatch()
+{
+    PrimitiveContainer &first = m_frames[0].primitives, &last = m_frames[m_nbFrames - 1].primitives;
+    PrimitiveContainer &current = m_frames[m_frame].primitives;
+    if (first.size() != current.size() || last.size() != current.size())
+        return false;
+    PrimitiveContainer::iterator it1 = first.begin(), it2 = last.begin();
+    for (PrimitiveContainer::iterator it = current.begin(); it != current.end(); ++it, ++it1, ++it2)
+        if (it1->second.type != it->second.type || it2->second.type != it->second.type)
+            return false;
+    return true;
+}
+
+/* morphPrimitives' statements (reference: GPUKernel.cpp:1530-1566) with r = weight, on the primitives the frame has */
+void GPUKernel::morphPrimitivesOnly(float weight)
+{
+    PrimitiveContainer &first = m_frames[0].primitives, &last = m_frames[m_nbFrames - 1].primitives;
+    std::vector<unsigned int> ids;
+    ids.reserve(m_frames[m_frame].primitives.size());
+    for (const auto &entry : m_frames[m_frame].primitives)
+        ids.push_back(entry.first);
+    const float r = weight;
+    auto mix = [r](const vec3f &a, const vec3f &b) {
+        return make_vec3f(a.x + r * (b.x - a.x), a.y + r * (b.y - a.y), a.z + r * (b.z - a.z));
+    };
+    PrimitiveContainer::iterator it1 = first.begin(), it2 = last.begin();
+    for (size_t rank = 0; rank < ids.size() && it1 != first.end() && it2 != last.end(); ++rank, ++it1, ++it2)
+    {
+        const CPUPrimitive &a = it1->second, &b = it2->second;
+        const vec3f p0 = mix(a.p0, b.p0), p1 = mix(a.p1, b.p1), p2 = mix(a.p2, b.p2);
+        const vec3f size = mix(a.size, b.size);
+        const int i = (int)ids[rank];
+        setPrimitive(i, p0.x, p0.y, p0.z, p1.x, p1.y, p1.z, p2.x, p2.y, p2.z, size.x, size.y, size.z, a.materialId);
+        setPrimitiveNormals(i, mix(a.n0, b.n0), mix(a.n1, b.n1), mix(a.n2, b.n2));
+        setPrimitiveTextureCoordinates(i, a.vt0, a.vt1, a.vt2);
+        setPrimitiveIsMovable(i, a.movable);
+    }
+}
+
+bool GPUKernel::morphKeys(std::vector<Primitive> &first, std::vector<Primitive> &last)
+{
+    PrimitiveContainer &current = m_frames[m_frame].primitives;
+    if (m_hPrimitives.size() != current.size())
+        return false; /* not the frame the flattened arrays describe */
+    std::vector<unsigned int> ids;
+    std::vector<const CPUPrimitive *> keys[2];
+    ids.reserve(current.size());
+    for (const auto &entry : current)
+        ids.push_back(entry.first);
+    for (int key = 0; key < 2; ++key)
+    {
+        keys[key].reserve(current.size());
+        for (const auto &entry : m_frames[key ? m_nbFrames - 1 : 0].primitives)
+            keys[key].push_back(&entry.second);
+        if (keys[key].size() != ids.size())
+            return false;
+    }
+    first.assign(m_hPrimitives.size(), Primitive());
+    last.assign(m_hPrimitives.size(), Primitive());
+    for (size_t i = 0; i < m_hPrimitives.size(); ++i)
+    {
+        const unsigned int id = (unsigned int)m_hPrimitives[i].index;
+        const size_t rank = std::lower_bound(ids.begin(), ids.end(), id) - ids.begin();
+        const CPUPrimitive *p = current.lookup(id);
+        if (rank >= ids.size() || ids[rank] != id || !p)
+            return false;
+        const CPUPrimitive &a = *keys[0][rank];
+        if (p->materialId != a.materialId || p->movable != a.movable || memcmp(&p->vt0, &a.vt0, sizeof(vec2f)) != 0 ||
+            memcmp(&p->vt1, &a.vt1, sizeof(vec2f)) != 0 || memcmp(&p->vt2, &a.vt2, sizeof(vec2f)) != 0)
+            return false;
+        for (int key = 0; key < 2; ++key)
+        {
+            const CPUPrimitive &k = *keys[key][rank];
+            Primitive &out = key ? last[i] : first[i];
+            memset(&out, 0, sizeof(out));
+            out.index = (int)id;
+            out.type = k.type;
+            out.p0 = k.p0;
+            out.p1 = k.p1;
+            out.p2 = k.p2;
+            out.n0 = k.n0;
+            out.n1 = k.n1;
+            out.n2 = k.n2;
+            out.size = k.size;
+        }
+    }
+    return true;
+}
+
+int GPUKernel::morphFrame(float weight)
+{
+    if (m_nbFrames < 3 || m_frame == 0 || m_frame + 1 >= m_nbFrames || !std::isfinite(weight))
+        return -1;
+    /* the scene the device holds is the one the host holds (plus what is pending): the frames were compared when the
+     * engine got its keys, and nothing has changed the store since */
+    const bool resident = m_primitivesTransfered && !m_hostTouched && m_residentFrame == (long)m_frame;
+    const bool compared = resident && m_morphKeysFrame == (long)m_frame && m_morphKeysNbFrames == (long)m_nbFrames;
+    if (!compared && !morphKeysMatch())
+        return -1;
+    if (resident && deviceMorphFrame(weight))
+    {
+        /* every primitive has been set anew: what was pending before is superseded */
+        m_pendingRotations.clear();
+        m_unrecordedRotations = 0;
+        m_morphPending = true;
+        m_pendingMorphWeight = weight;
+        return 0;
+    }
+    ensureLevels(); /* from the primitives the tree was built with */
+    m_pendingRotations.clear();
+    m_unrecordedRotations = 0;
+    m_morphPending = false;
+    Frame &f = frame();
+    morphPrimitivesOnly(weight);
+    refitBoxes(f);
+    compactBoxes(false);
+    return 0;
+}
+
 /* reference: GPUKernel.cpp:1283-1305 */
 void GPUKernel::resetFrame()
 {
@@ -1114,15 +1233,23 @@ void GPUKernel::refitBoxes(Frame &f)
 
 void GPUKernel::syncHost()
 {
-    if (m_pendingRotations.empty() && !m_unrecordedRotations)
+    if (m_pendingRotations.empty() && !m_unrecordedRotations && !m_morphPending)
         return;
     const bool transfered = m_primitivesTransfered, touched = m_hostTouched;
     ensureLevels(); /* from the primitives as they were built with, before the rotations reach the store */
+
     std::vector<PendingRotation> pending;
     pending.swap(m_pendingRotations);
     const size_t unrecorded = m_unrecordedRotations;
     m_unrecordedRotations = 0;
     Frame &f = m_frames[m_frame];
+    if (m_morphPending)
+    {
+        /* the morph first, always replayed: what the engine hands back (primitivesFromDevice) carries neither sizes
+         * nor the primitives a rotation leaves alone */
+        m_morphPending = false;
+        morphPrimitivesOnly(m_pendingMorphWeight);
+    }
     /* a handful of rotations is replayed (4 ms each for 100 k primitives); a long animation is fetched */
     if (pending.size() <= 8 || !primitivesFromDevice(f))
     {

@@ -458,6 +458,16 @@ public:
     void nextFrame();
     void previousFrame();
     void morphPrimitives();
+    /* The current frame - one strictly between the first and the last key frame, with as many primitives as each of
+     * them, pairwise of the same type by rank in id order - blended anew at any finite weight: every primitive set in
+     * place by morphPrimitives' statements with r = weight (first + r * (last - first), setPrimitive,
+     * setPrimitiveNormals, the first key's texture coordinates, material and movable flag), the boxes refitted in the
+     * shape they have, compactBoxes(false).  An engine that keeps the scene resident may blend it there
+     * (deviceMorphFrame); the host copy then lags behind by that morph (pendingMorph) and the rotations after it, and
+     * syncHost() catches it up.  Returns 0 when done, -1 when the request cannot be served (fewer than three frames, the
+     * current frame is a key frame, counts or types differ, a weight that is not finite): nothing changed. */
+    int morphFrame(float weight);
+    bool pendingMorph() const { return m_morphPending; }
     void resetAddingIndex() { m_addingIndex = 0; }
     void doneWithAdding(const bool &done) { m_doneWithAdding = done; }
     void getPrimitiveOtherCenter(unsigned int index, vec3f &center);
@@ -526,7 +536,7 @@ protected:
          * those of the last full build, GPUKernel.cpp:1378-1460 refits them, it does not re-hash) */
         if (!m_frames[m_frame].levelsBuilt)
             buildLevelsOnHost();
-        if ((!m_pendingRotations.empty() || m_unrecordedRotations) && !m_buildingLevels)
+        if ((!m_pendingRotations.empty() || m_unrecordedRotations || m_morphPending) && !m_buildingLevels)
             syncHost();
         return m_frames[m_frame];
     }
@@ -584,6 +594,22 @@ protected:
     virtual int isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity);
     void rotatePrimitivesOnly(Frame &f, const vec3f &rotationCenter, const vec3f &cosA, const vec3f &sinA);
     void refitBoxes(Frame &f);
+    /* engine hook: blend the resident scene at that weight (the keys handed over first where the engine has none:
+     * morphKeys); false = not done, nothing changed */
+    virtual bool deviceMorphFrame(float) { return false; }
+    /* the current frame against the two key frames: counts, types by rank */
+    bool morphKeysMatch();
+    /* morphFrame's loop over the store of the current frame (no boxes, no flattening) */
+    void morphPrimitivesOnly(float weight);
+    /* the two key frames as records in the order of the flattened primitives (of a record only the geometry is
+     * filled in); false when a primitive of the current frame differs from the first key's in what a morph takes from
+     * that key and a resident scene keeps as it is - material, texture coordinates, movable flag */
+    bool morphKeys(std::vector<Primitive> &first, std::vector<Primitive> &last);
+    /* the frames the engine's keys were made for (morphKeys), -1: it has none; reset with every upload */
+    long m_morphKeysFrame = -1, m_morphKeysNbFrames = -1;
+    /* the frame the engine's resident scene was uploaded from, -1: none (a frame switch without a flatten leaves the
+     * device with another frame than the current one: that one is not morphed over there) */
+    long m_residentFrame = -1;
 
     /* box-tree build (GPUKernel.h:318-324) */
     int processBoxes(const int boxSize, bool simulate);
@@ -649,6 +675,10 @@ protected:
      * catches up from the device's primitives, which it does for more than a handful anyway */
     static constexpr size_t MAX_RECORDED_ROTATIONS = 100000;
     size_t m_unrecordedRotations = 0;
+    /* a morph the engine applied to the resident scene and the store has not replayed (it supersedes what was pending
+     * before it; m_pendingRotations are the rotations since) */
+    bool m_morphPending = false;
+    float m_pendingMorphWeight = 0.f;
 
     SceneInfo m_sceneInfo;
     PostProcessingInfo m_postProcessingInfo;

@@ -152,6 +152,8 @@ void HipKernel::render_begin(const float timer)
             solr_hip_set_movable(m_hMovable.data(), (int)m_hMovable.size());
             m_primitivesTransfered = true;
             m_hostTouched = false; /* device and host hold the same scene from here on */
+            m_morphKeysFrame = -1; /* (the upload dropped the engine's morph keys) */
+            m_residentFrame = (long)m_frame;
             mark("render_begin: lights, movable flags");
         }
         if (!m_randomsTransfered)
@@ -212,6 +214,22 @@ bool HipKernel::deviceRotatePrimitives(const vec3f &center, const vec3f &cosA, c
     const float co[3] = {cosA.x, cosA.y, cosA.z};
     const float si[3] = {sinA.x, sinA.y, sinA.z};
     return solr_hip_rotate_primitives(c, co, si, m_sceneInfo.viewDistance) == 1;
+}
+
+bool HipKernel::deviceMorphFrame(float weight)
+{
+    if (!m_deviceInitialized)
+        return false;
+    if (m_morphKeysFrame != (long)m_frame || m_morphKeysNbFrames != (long)m_nbFrames)
+    {
+        /* the first morph after an upload: the key frames go to the device, in the order of the resident primitives */
+        std::vector<Primitive> first, last;
+        if (!morphKeys(first, last) || solr_hip_set_morph_keys(first.data(), last.data(), (int)first.size()) != 1)
+            return false;
+        m_morphKeysFrame = (long)m_frame;
+        m_morphKeysNbFrames = (long)m_nbFrames;
+    }
+    return solr_hip_morph_primitives(weight, m_sceneInfo.viewDistance) == 1;
 }
 
 bool HipKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb)
@@ -481,11 +499,27 @@ void ReplayKernel::render_begin(const float timer)
         syncHost();
     m_primitivesTransfered = true; /* the upload a real engine does here */
     m_hostTouched = false;
+    m_morphKeysFrame = -1;
+    m_residentFrame = (long)m_frame;
 }
 
 bool ReplayKernel::deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &)
 {
     ++m_claimed;
+    return true;
+}
+
+bool ReplayKernel::deviceMorphFrame(float)
+{
+    if (m_morphKeysFrame != (long)m_frame || m_morphKeysNbFrames != (long)m_nbFrames)
+    {
+        std::vector<Primitive> first, last;
+        if (!morphKeys(first, last))
+            return false;
+        m_morphKeysFrame = (long)m_frame;
+        m_morphKeysNbFrames = (long)m_nbFrames;
+    }
+    ++m_claimedMorphs;
     return true;
 }
 

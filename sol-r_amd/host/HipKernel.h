@@ -58,6 +58,8 @@ public:
 protected:
     /* rotatePrimitives on the resident scene, solr_hip_rotate_primitives (include/solr_hip.h) */
     bool deviceRotatePrimitives(const vec3f &center, const vec3f &cosA, const vec3f &sinA) override;
+    /* morphFrame on the resident scene, solr_hip_set_morph_keys + solr_hip_morph_primitives (include/solr_hip.h) */
+    bool deviceMorphFrame(float weight) override;
     void fetchPrimitiveIds() override;
     void fetchBitmap() override;
     bool primitivesFromDevice(Frame &f) override;
@@ -104,20 +106,22 @@ protected:
     bool m_failed = false;
 };
 
-/* Test double for the animated-scene protocol (GPUKernel::rotatePrimitives / syncHost): a host-only
+/* Test double for the animated-scene protocol (GPUKernel::rotatePrimitives / morphFrame / syncHost): a host-only
  * store that claims, like an engine with a resident scene would, to have uploaded the scene at the first
- * frame and to apply every rotation "over there" - so that the lazy replay of the pending rotations can be
+ * frame and to apply every rotation and every morph "over there" - so that the lazy replay of what is pending can be
  * checked against the eager host route without a GPU.  Renders nothing. */
 class ReplayKernel : public HostOnlyKernel
 {
 public:
     void render_begin(const float timer) override;
     int nbClaimedRotations() const { return m_claimed; }
+    int nbClaimedMorphs() const { return m_claimedMorphs; }
 
 protected:
     bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) override;
+    bool deviceMorphFrame(float weight) override;
 
 private:
-    int m_claimed = 0;
+    int m_claimed = 0, m_claimedMorphs = 0;
 };
 }

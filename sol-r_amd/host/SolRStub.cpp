@@ -416,6 +416,25 @@ int SolRx_MorphPrimitives()
     return SingletonKernel::kernel()->getFrame();
 }
 
+/* Extension: the current frame blended anew from the first and the last key frame at any weight
+ * (GPUKernel::morphFrame); with the HIP engine and an unchanged resident scene the blend runs on the device */
+int SolRx_MorphFrame(double weight)
+{
+    return SingletonKernel::kernel()->morphFrame((float)weight);
+}
+
+/* Extension: GPUKernel::setPrimitiveIsMovable (SolR_SetPrimitive makes a primitive movable again, as setPrimitive does) */
+int SolRx_SetPrimitiveIsMovable(int index, int movable)
+{
+    SingletonKernel::kernel()->setPrimitiveIsMovable(index, movable != 0);
+    return 0;
+}
+
+int SolRx_PendingMorph()
+{
+    return SingletonKernel::kernel()->pendingMorph() ? 1 : 0;
+}
+
 int SolRx_PendingRotations()
 {
     return (int)SingletonKernel::kernel()->nbPendingRotations();

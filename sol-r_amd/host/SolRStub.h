@@ -194,6 +194,14 @@ int SolRx_GetTreeDepth();
 int SolRx_SetNbFrames(int nbFrames);
 int SolRx_SetFrame(int frame);
 int SolRx_MorphPrimitives();
+/* the current frame - one between the key frames, e.g. as SolRx_MorphPrimitives made it - blended anew at any finite weight
+ * (0: the first key frame, 1: the last; beyond: extrapolated), its tree kept in shape and refitted
+ * (GPUKernel::morphFrame).  0 = done, -1 = refused, nothing changed.  SolRx_PendingMorph: 1 while such a morph was
+ * applied on the device and the host scene store has not replayed it yet (SolRx_SyncHost replays it) */
+int SolRx_MorphFrame(double weight);
+/* whether rotations move the primitive, set after SolR_SetPrimitive (which makes it movable); a morph takes the first key's */
+int SolRx_SetPrimitiveIsMovable(int index, int movable);
+int SolRx_PendingMorph();
 int SolRx_PendingRotations();
 int SolRx_SyncHost();
 int SolRx_GetMovable(const unsigned char **flags, int *nbPrimitives);
