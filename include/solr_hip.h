@@ -564,6 +564,43 @@ int solr_hip_set_morph_keys(const Primitive *first, const Primitive *last, int n
 int solr_hip_morph_primitives(float weight, float viewDistance);
 int solr_hip_device_morphs(void);
 
+/* Models that are pushed along, lamps that are dragged.  The reference's scenes translate a model with
+ * GPUKernel::translatePrimitives (GPUKernel.cpp:1462-1511; apps/scenes/Scene.cpp:1546-1548: rotate, translate,
+ * compactBoxes(false)) and its viewer drags a lamp with setPrimitiveCenter + compactBoxes(false) on every mouse event
+ * (apps/solrViewer.cpp:1058-1069) - a flatten and a full upload each.  Neither changes the shape of the flattened tree:
+ *   solr_hip_translate_primitives  every primitive whose movable flag is set (solr_hip_set_movable) gets p0, p1 and p2
+ *                               incremented by `translation` - three binary32 additions a point, the host loop's - and
+ *                               the lists are refitted as after a rotation.  viewDistance: sceneInfo.viewDistance.
+ *                               Returns 1 when the resident scene now holds, bit for bit, what the host translation + a
+ *                               fresh h2d_scene would have produced, 0 when it cannot serve the request - whatever
+ *                               solr_hip_rotate_primitives refuses, no translation, a component that is not finite:
+ *                               nothing changed, take the host route;
+ *   solr_hip_move_lamp          `lamp`: a slot of the resident scene, 0 <= lamp < nbLamps of h2d_scene - the first nbLamps
+ *                               flattened primitives are the lamps, light record `lamp` is that primitive's.  The p0 of
+ *                               the primitive and the location of the light record are set to `center`, and with them the
+ *                               copies the engine keeps of that p0 (leaf records, host images).  No node changes: the lamps'
+ *                               cell keeps the +-viewDistance it was uploaded with.  Returns 1 when the resident scene
+ *                               now holds what setPrimitiveCenter + compactBoxes(false) + fresh h2d_scene and
+ *                               h2d_lightInformation would have produced, 0 when it cannot serve the request - no
+ *                               resident scene, a slot out of range, a centre that is not finite, fewer light records
+ *                               than lamps or a light record `lamp` that names another primitive (primitiveId against
+ *                               the primitive's index), a lamp that is not the first cell's or not a sphere (an axis
+ *                               plane's centre also reaches the thin copies of the lists, which are not made again
+ *                               here), a centre at which the lamp would leave that cell (the walks' short cuts rest on
+ *                               primitives that lie inside their leaves): nothing changed, take the host route.
+ *                               A morph on the device sets every primitive anew and would leave the light record where
+ *                               the drag put it: after a lamp move solr_hip_morph_primitives declines until the next
+ *                               h2d_scene;
+ *   solr_hip_device_translations / _lamp_moves   how many requests were served since initialize_scene;
+ *   solr_hip_read_lights        the resident light records, for tests (float4 rows, 3 per light: { location.xyz,
+ *                               primitiveId } { color } { materialId, 0, 0, 0 }); the conventions of
+ *                               solr_hip_read_primitives. */
+int solr_hip_translate_primitives(const float translation[3], float viewDistance);
+int solr_hip_device_translations(void);
+int solr_hip_move_lamp(int lamp, const float center[3]);
+int solr_hip_device_lamp_moves(void);
+int solr_hip_read_lights(float *rows, int capacityRows);
+
 /* Bytes of HBM this engine currently holds for {scene planes, materials,
  * textures, per-pixel buffers}; for DESIGN.md's layout table and tests. */
 void solr_hip_memory_usage(unsigned long long bytes[4]);

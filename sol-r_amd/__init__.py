@@ -258,6 +258,14 @@ def _declare_hip(L):
     L.solr_hip_morph_primitives.argtypes = [C.c_float, C.c_float]
     L.solr_hip_morph_primitives.restype = C.c_int
     L.solr_hip_device_morphs.restype = C.c_int
+    L.solr_hip_translate_primitives.argtypes = [P(C.c_float), C.c_float]
+    L.solr_hip_translate_primitives.restype = C.c_int
+    L.solr_hip_device_translations.restype = C.c_int
+    L.solr_hip_move_lamp.argtypes = [C.c_int, P(C.c_float)]
+    L.solr_hip_move_lamp.restype = C.c_int
+    L.solr_hip_device_lamp_moves.restype = C.c_int
+    L.solr_hip_read_lights.argtypes = [C.c_void_p, C.c_int]
+    L.solr_hip_read_lights.restype = C.c_int
     L.solr_hip_read_nodes.argtypes = [C.c_int, C.c_void_p, C.c_int]
     L.solr_hip_read_nodes.restype = C.c_int
     L.solr_hip_read_primitives.argtypes = [C.c_void_p, C.c_int]
@@ -353,6 +361,9 @@ def _declare_host(L):
     L.SolRx_SetNbFrames.argtypes = [i]
     L.SolRx_SetFrame.argtypes = [i]
     L.SolRx_MorphFrame.argtypes = [d]
+    L.SolRx_TranslatePrimitives.argtypes = [d, d, d]
+    L.SolRx_SetPrimitiveCenter.argtypes = [i, d, d, d]
+    L.SolRx_PendingMoves.restype = i
 
 
 def _np_from_ptr(ptr, count, dtype):
@@ -559,6 +570,28 @@ class Kernel:
     def pending_rotations(self):
         return self.L.SolRx_PendingRotations()
 
+    def translate_primitives(self, translation):
+        """GPUKernel::translatePrimitives + compactBoxes(false), as the reference's scenes run it behind a rotation
+        (SolRx_TranslatePrimitives): p0, p1 and p2 of every movable primitive incremented.  With the HIP engine and an
+        unchanged scene the translation runs on the resident scene and the host copy follows lazily."""
+        return self.L.SolRx_TranslatePrimitives(translation[0], translation[1], translation[2])
+
+    def set_primitive_center(self, index, center):
+        """GPUKernel::setPrimitiveCenter + compactBoxes(false), the reference viewer's lamp drag
+        (SolRx_SetPrimitiveCenter).  With the HIP engine and an unchanged scene the centre of a lamp is set on the resident
+        scene, with its light record, and the host copy follows lazily; any other primitive takes the host route."""
+        return self.L.SolRx_SetPrimitiveCenter(index, center[0], center[1], center[2])
+
+    def get_primitive_center(self, index):
+        """GPUKernel::getPrimitiveCenter: a look that catches the host copy up and keeps the device route"""
+        x, y, z = C.c_double(), C.c_double(), C.c_double()
+        self.L.SolR_GetPrimitiveCenter(index, C.byref(x), C.byref(y), C.byref(z))
+        return (x.value, y.value, z.value)
+
+    def pending_moves(self):
+        """rotations, translations and lamp moves applied on the device that the host scene store has not replayed yet"""
+        return self.L.SolRx_PendingMoves()
+
     # -- key frames ---------------------------------------------------------------------
     def set_nb_frames(self, n):
         """GPUKernel::setNbFrames: the scene has frames 0 ... n - 1; the first and the last are the key frames"""
@@ -608,6 +641,15 @@ class Kernel:
         if cap < 0 or hip.solr_hip_read_primitives(buf.ctypes.data, cap) != cap:
             raise SolrError("solr_hip_read_primitives failed")
         return buf[:cap].reshape(-1, 8, 4)
+
+    def device_lights(self):
+        """The resident light records (n, 3, 4) float32: { location, primitiveId } { color } { materialId, 0, 0, 0 }."""
+        hip = hip_lib()
+        cap = hip.solr_hip_read_lights(None, 0)
+        buf = np.zeros((max(cap, 1), 4), np.float32)
+        if cap < 0 or hip.solr_hip_read_lights(buf.ctypes.data, cap) != cap:
+            raise SolrError("solr_hip_read_lights failed")
+        return buf[:cap].reshape(-1, 3, 4)
 
     def set_camera(self, eye, look_at=(0, 0, 0), angles=(0, 0, 0), w=6400.0):
         self.L.SolRx_SetCameraW(eye[0], eye[1], eye[2], look_at[0], look_at[1], look_at[2], angles[0], angles[1],

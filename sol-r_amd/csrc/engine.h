@@ -2,7 +2,7 @@
  * engine.h - the state of the MI355X rendering engine and the helpers every part of its host side uses: what
  * solr_hip.hip (the boundary), solr_uploads.hip (the h2d_* uploads), solr_arena.hip (the arena and the node lists; their
  * host builders: list_builders.h), solr_rotation.hip (rotation and refit on the device), solr_morph.hip (key-frame
- * morphing on the device), solr_launch.hip (the renderer's
+ * morphing on the device), solr_moves.hip (translation and lamp moves on the device), solr_launch.hip (the renderer's
  * launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined read-back), solr_rccl.hip (strips,
  * communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
@@ -389,6 +389,10 @@ struct Rotation
     bool exactStale = false;       /* the exact list has not been refitted since the last rotation */
     float exactStaleViewDistance = 0.f;
     int nbDeviceRotations = 0;
+    /* the other rigid moves (solr_moves.hip): translations run the rotation's refit, a lamp move refits nothing */
+    int nbDeviceTranslations = 0;
+    int nbDeviceLampMoves = 0;
+    bool lampMoved = false; /* a lamp was moved on the device since h2d_scene: a morph there would leave its light record behind */
 };
 /* Key-frame morphing on the device (solr_hip_set_morph_keys, solr_hip_morph_primitives; solr_morph.hip): the two key
  * frames of the resident scene.  Written by setMorphKeysOne and the transitions of Scene; an h2d_scene drops the keys. */
@@ -433,6 +437,7 @@ struct Scene
         rotation.exactStale = false;
         rotation.refitPlanPending = true;
         rotation.nbMovable = -1;
+        rotation.lampMoved = false;
         morphKeysDropped();
         arena.deviceAhead = false;
         orderFree.reset();
@@ -506,6 +511,26 @@ struct Scene
         {
             arena.deviceAhead = true;
             ++rotation.nbDeviceRotations;
+        }
+    }
+    /* translatePrimitivesOne has moved the primitives and refitted the lists (rotationQueued); as for a rotation */
+    void translationServed(bool walkHolds, bool landed)
+    {
+        walkEncloses = walkHolds;
+        if (landed)
+        {
+            arena.deviceAhead = true;
+            ++rotation.nbDeviceTranslations;
+        }
+    }
+    /* moveLampOne has set a lamp's p0 and its light record, in the arena and in the host images alike (nothing is ahead
+     * of anything by it) */
+    void lampMoveServed(bool landed)
+    {
+        if (landed)
+        {
+            rotation.lampMoved = true;
+            ++rotation.nbDeviceLampMoves;
         }
     }
     /* retagPrimitives has joined the materials' facts into the primitives' tags again */
@@ -865,7 +890,9 @@ bool shortRayListsChoice();
 SceneArgs prepareScene(const SceneInfo &sceneInfo, bool exactNodes);
 bool deepNodeList(const SceneArgs &S);
 /* solr_rotation.hip: rotation and refit on the device */
-bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
+/* (who: the entry point that asks - a morph and a translation ask what a rotation asks - for the error and debug texts) */
+bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance,
+                  const char *who = "solr_hip_rotate_primitives");
 int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
 bool refitMovedScene(float viewDistance);
 void refreshExactList();
@@ -873,6 +900,11 @@ void refreshExactList();
 int setMorphKeysOne(const Primitive *first, const Primitive *last, int nbPrimitives);
 bool canMorphOne(float weight, float viewDistance);
 int morphPrimitivesOne(float weight, float viewDistance);
+/* solr_moves.hip: translation and lamp moves on the device */
+bool canTranslateOne(const float translation[3], float viewDistance);
+int translatePrimitivesOne(const float translation[3], float viewDistance);
+bool canMoveLampOne(int lamp, const float center[3]);
+int moveLampOne(int lamp, const float center[3]);
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */
 void allocateFrame();
 int neededFeatures(const SceneInfo &sceneInfo, bool full);

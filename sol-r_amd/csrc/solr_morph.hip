@@ -182,14 +182,17 @@ static bool lampWouldMove()
 bool canMorphOne(float weight, float viewDistance)
 {
     static const float none[3] = {0.f, 0.f, 0.f};
-    if (!canRotateOne(none, none, none, viewDistance))
+    if (!canRotateOne(none, none, none, viewDistance, "solr_hip_morph_primitives"))
         return false;
     const Morph &m = g.scene.morph;
-    if (m.nbKeys != g.scene.nbPrimitives || !m.first.ptr || !m.last.ptr || !std::isfinite(weight) || lampWouldMove())
+    /* (a lamp that was moved on the device, solr_moves.hip: the blend would put its p0 back at the keys' place and leave
+     * its light record where the move put it - the host route makes the record from p0 again) */
+    if (m.nbKeys != g.scene.nbPrimitives || !m.first.ptr || !m.last.ptr || !std::isfinite(weight) || lampWouldMove() ||
+        g.scene.rotation.lampMoved)
     {
         if (getenv("SOLR_HIP_DEBUG_TREE"))
-            fprintf(stderr, "solr_hip_morph_primitives refused: keys for %d of %d primitives, weight %g\n", m.nbKeys,
-                    g.scene.nbPrimitives, weight);
+            fprintf(stderr, "solr_hip_morph_primitives refused: keys for %d of %d primitives, weight %g, a lamp moved here: %d\n",
+                    m.nbKeys, g.scene.nbPrimitives, weight, (int)g.scene.rotation.lampMoved);
         return false;
     }
     return true;

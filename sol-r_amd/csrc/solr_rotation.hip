@@ -257,9 +257,9 @@ bool refitMovedScene(float viewDistance)
  * arena now holds the rotated scene, 0 when the request cannot be served here and the caller has to
  * take the host route (nothing was changed). */
 /* can this engine rotate its resident scene?  (makes the refit plan when the lists changed; changes nothing else) */
-bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance)
+bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance, const char *who)
 {
-    if (!ready("solr_hip_rotate_primitives") || !ok())
+    if (!ready(who) || !ok())
         return false;
     if (g.scene.rotation.refitPlanPending)
     {
@@ -273,7 +273,7 @@ bool canRotateOne(const float center[3], const float cosAngles[3], const float s
         !(viewDistance <= 1000000.f) || !(viewDistance > 0.f) || g.scene.exact.nb >= NB_MAX_BOXES || !center || !cosAngles || !sinAngles)
     {
         if (getenv("SOLR_HIP_DEBUG_TREE"))
-            fprintf(stderr, "solr_hip_rotate_primitives refused: plan %d, flags for %d of %d primitives, viewDistance %g, %d nodes\n",
+            fprintf(stderr, "%s refused: plan %d, flags for %d of %d primitives, viewDistance %g, %d nodes\n", who,
                     (int)g.scene.rotation.refitReady, g.scene.rotation.nbMovable, g.scene.nbPrimitives, viewDistance, g.scene.exact.nb);
         return false;
     }

@@ -362,6 +362,28 @@ vec4f GPUKernel::getPrimitiveCenter(unsigned int index)
 
 void GPUKernel::setPrimitiveCenter(unsigned int index, const vec3f &center)
 {
+    /* a lamp of the scene the device holds (the viewer drags one with this and compactBoxes(false) per mouse event):
+     * nothing of what is uploaded follows a lamp's centre but the primitive itself and its light record, so the
+     * engine may set both in place and the store follows when somebody looks (syncHost).  Any other primitive's
+     * centre is the host's: its boxes would have to follow */
+    if (m_primitivesTransfered && !m_hostTouched && m_residentFrame == (long)m_frame)
+    {
+        const int nbLamps = std::min(frameAsIs().nbActiveLamps, (int)m_hLamps.size());
+        for (int slot = 0; slot < nbLamps; ++slot)
+            if (m_hLamps[slot] == (Lamp)index)
+            {
+                if (!deviceMoveLamp(slot, center))
+                    break;
+                PendingMove move;
+                move.kind = PendingMove::LAMP_MOVE;
+                move.v = center;
+                move.cosA = move.sinA = make_vec3f();
+                move.index = index;
+                recordMove(move);
+                m_lampMovedOnDevice = true;
+                return;
+            }
+    }
     m_primitivesTransfered = false;
     if (CPUPrimitive *p = getPrimitive(index))
         p->p0 = center;
@@ -593,9 +615,9 @@ int GPUKernel::processOutterBoxes(const int boxSize, const int boundingBoxesDept
 /* reference: GPUKernel.cpp:1041-1083 */
 int GPUKernel::compactBoxes(bool reconstructBoxes)
 {
-    /* rotations or a morph applied on the device: the flattened scene over there is already what the lines
-     * below would produce and upload */
-    if (!reconstructBoxes && (!m_pendingRotations.empty() || m_unrecordedRotations || m_morphPending))
+    /* rotations, translations, lamp moves or a morph applied on the device: the flattened scene over there is already
+     * what the lines below would produce and upload */
+    if (!reconstructBoxes && hostLags())
         return frameAsIs().nbActiveBoxes;
     m_primitivesTransfered = false;
     if (reconstructBoxes)
@@ -1080,18 +1102,19 @@ int GPUKernel::morphFrame(float weight)
     const bool compared = resident && m_morphKeysFrame == (long)m_frame && m_morphKeysNbFrames == (long)m_nbFrames;
     if (!compared && !morphKeysMatch())
         return -1;
-    if (resident && deviceMorphFrame(weight))
+    if (resident && !m_lampMovedOnDevice && deviceMorphFrame(weight))
     {
-        /* every primitive has been set anew: what was pending before is superseded */
-        m_pendingRotations.clear();
-        m_unrecordedRotations = 0;
+        /* every primitive has been set anew: what was pending before is superseded (no lamp move is among it: a morph
+         * behind one is not offered to the engine) */
+        clearJournal();
         m_morphPending = true;
         m_pendingMorphWeight = weight;
         return 0;
     }
     ensureLevels(); /* from the primitives the tree was built with */
-    m_pendingRotations.clear();
-    m_unrecordedRotations = 0;
+    /* (the lamp moves too: the loop below sets a lamp from its keys like any primitive, and its light record is made
+     * from it when the frame is flattened) */
+    clearJournal();
     m_morphPending = false;
     Frame &f = frame();
     morphPrimitivesOnly(weight);
@@ -1160,16 +1183,13 @@ void GPUKernel::rotatePrimitives(const vec3f &rotationCenter, const vec4f &angle
      * engine may turn it in place, and the host copy follows when somebody looks (syncHost) */
     if (m_primitivesTransfered && !m_hostTouched && deviceRotatePrimitives(rotationCenter, cosA, sinA))
     {
-        if (m_pendingRotations.size() >= MAX_RECORDED_ROTATIONS)
-        {
-            ++m_unrecordedRotations;
-            return;
-        }
-        PendingRotation r;
-        r.center = rotationCenter;
+        PendingMove r;
+        r.kind = PendingMove::ROTATION;
+        r.v = rotationCenter;
         r.cosA = cosA;
         r.sinA = sinA;
-        m_pendingRotations.push_back(r);
+        r.index = 0;
+        recordMove(r);
         return;
     }
     Frame &f = frame();
@@ -1231,17 +1251,44 @@ void GPUKernel::refitBoxes(Frame &f)
             updateOutterBoundingBox(entry.second, b - 1);
 }
 
+void GPUKernel::recordMove(const PendingMove &move)
+{
+    if (m_journal.size() >= MAX_RECORDED_ROTATIONS)
+    {
+        ++(move.kind == PendingMove::ROTATION      ? m_unrecordedRotations
+           : move.kind == PendingMove::TRANSLATION ? m_unrecordedTranslations
+                                                   : m_unrecordedLampMoves);
+        return;
+    }
+    m_journal.push_back(move);
+    if (move.kind == PendingMove::ROTATION)
+        ++m_journalRotations;
+}
+
+void GPUKernel::clearJournal()
+{
+    m_journal.clear();
+    m_journalRotations = 0;
+    m_unrecordedRotations = m_unrecordedTranslations = m_unrecordedLampMoves = 0;
+}
+
 void GPUKernel::syncHost()
 {
-    if (m_pendingRotations.empty() && !m_unrecordedRotations && !m_morphPending)
+    if (!hostLags())
         return;
     const bool transfered = m_primitivesTransfered, touched = m_hostTouched;
-    ensureLevels(); /* from the primitives as they were built with, before the rotations reach the store */
+    ensureLevels(); /* from the primitives as they were built with, before the moves reach the store */
 
-    std::vector<PendingRotation> pending;
-    pending.swap(m_pendingRotations);
-    const size_t unrecorded = m_unrecordedRotations;
-    m_unrecordedRotations = 0;
+    std::vector<PendingMove> pending;
+    pending.swap(m_journal);
+    const size_t unrecorded = m_unrecordedRotations + m_unrecordedTranslations + m_unrecordedLampMoves;
+    size_t nbHeavy = 0; /* rotations and translations: a pass over the primitives each; a lamp move is one assignment */
+    for (const PendingMove &move : pending)
+        nbHeavy += move.kind != PendingMove::LAMP_MOVE;
+    /* lamp moves alone refit nothing, as on the host route: setPrimitiveCenter + compactBoxes(false) leaves every box
+     * as it is, the stale box of another primitive whose centre was set included */
+    const bool refit = m_morphPending || nbHeavy || m_unrecordedRotations || m_unrecordedTranslations;
+    clearJournal();
     Frame &f = m_frames[m_frame];
     if (m_morphPending)
     {
@@ -1250,16 +1297,30 @@ void GPUKernel::syncHost()
         m_morphPending = false;
         morphPrimitivesOnly(m_pendingMorphWeight);
     }
-    /* a handful of rotations is replayed (4 ms each for 100 k primitives); a long animation is fetched */
-    if (pending.size() <= 8 || !primitivesFromDevice(f))
+    /* a handful of rotations and translations is replayed (4 ms each for 100 k primitives); a long animation is
+     * fetched, and so is one whose moves were not all recorded */
+    if ((nbHeavy <= 8 && !unrecorded) || !primitivesFromDevice(f))
     {
         if (unrecorded)
             std::cerr << "GPUKernel::syncHost: the engine did not hand back its primitives and " << unrecorded
-                      << " of the rotations it applied were not recorded: the scene store lags behind" << std::endl;
-        for (const PendingRotation &r : pending)
-            rotatePrimitivesOnly(f, r.center, r.cosA, r.sinA);
+                      << " of the moves it applied were not recorded: the scene store lags behind" << std::endl;
+        for (const PendingMove &move : pending)
+            switch (move.kind)
+            {
+            case PendingMove::ROTATION:
+                rotatePrimitivesOnly(f, move.v, move.cosA, move.sinA);
+                break;
+            case PendingMove::TRANSLATION:
+                translatePrimitivesOnly(f, move.v);
+                break;
+            case PendingMove::LAMP_MOVE:
+                if (CPUPrimitive *p = f.primitives.lookup(move.index))
+                    p->p0 = move.v;
+                break;
+            }
     }
-    refitBoxes(f);
+    if (refit)
+        refitBoxes(f);
     /* the flattened arrays follow.  What they now hold is what the device holds (the same arithmetic
      * ran there), so neither an upload is due nor has the scene been "touched" by this */
     streamDataToGPU();
@@ -1270,13 +1331,30 @@ void GPUKernel::syncHost()
 /* reference: GPUKernel.cpp:1462-1511 */
 void GPUKernel::translatePrimitives(const vec3f &t)
 {
-    m_primitivesTransfered = false;
-    ensureLevels();
+    /* as for a rotation: the scene the device holds is the one the host holds (plus what is pending), the engine may
+     * push it along in place, and the host copy follows when somebody looks (syncHost) */
+    if (m_primitivesTransfered && !m_hostTouched && deviceTranslatePrimitives(t))
+    {
+        PendingMove move;
+        move.kind = PendingMove::TRANSLATION;
+        move.v = t;
+        move.cosA = move.sinA = make_vec3f();
+        move.index = 0;
+        recordMove(move);
+        return;
+    }
     Frame &f = frame();
+    m_primitivesTransfered = false;
+    translatePrimitivesOnly(f, t);
+    refitBoxes(f);
+}
+
+void GPUKernel::translatePrimitivesOnly(Frame &f, const vec3f &t)
+{
+    ensureLevels();
     for (auto &entry : f.boundingBoxes[0])
     {
         CPUBoundingBox &box = entry.second;
-        resetBox(box, false);
         for (long id : box.primitives)
         {
             CPUPrimitive &p = f.primitives[(unsigned int)id];
@@ -1287,11 +1365,7 @@ void GPUKernel::translatePrimitives(const vec3f &t)
                 p.p2 = make_vec3f(p.p2.x + t.x, p.p2.y + t.y, p.p2.z + t.z);
             }
         }
-        updateBoundingBox(box);
     }
-    for (int b = 1; b < BOUNDING_BOXES_TREE_DEPTH; ++b)
-        for (auto &entry : f.boundingBoxes[b])
-            updateOutterBoundingBox(entry.second, b - 1);
 }
 
 /* reference: GPUKernel.cpp:1574-1600 (from/to are ignored there too) */

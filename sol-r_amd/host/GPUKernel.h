@@ -499,12 +499,15 @@ public:
     const std::vector<LightInformation> &hostLights() { syncHost(); return m_lightInformation; }
     /* per flattened primitive: would rotatePrimitives move it (level-0 box, movable, not the camera) */
     const std::vector<unsigned char> &hostMovable() { syncHost(); return m_hMovable; }
-    /* Animated scenes: rotatePrimitives + compactBoxes(false) per frame (MoleculeScene.cpp:75-81).  An
-     * engine that keeps the scene resident may apply the rotation there (deviceRotatePrimitives); the
-     * host copy then lags behind by the rotations listed in m_pendingRotations and is caught up - the same
-     * arithmetic, replayed in order - by syncHost() before anything reads or changes it. */
+    /* Animated scenes: rotatePrimitives + compactBoxes(false) per frame (MoleculeScene.cpp:75-81), translatePrimitives
+     * behind it (Scene.cpp:1546-1548), a lamp dragged with setPrimitiveCenter (solrViewer.cpp:1058-1069).  An
+     * engine that keeps the scene resident may apply such a move there (deviceRotatePrimitives,
+     * deviceTranslatePrimitives, deviceMoveLamp); the host copy then lags behind by the moves listed in m_journal
+     * and is caught up - the same arithmetic, replayed in order - by syncHost() before anything reads or changes it. */
     void syncHost();
-    size_t nbPendingRotations() const { return m_pendingRotations.size() + m_unrecordedRotations; }
+    size_t nbPendingRotations() const { return m_journalRotations + m_unrecordedRotations; }
+    /* ... and the whole journal: rotations, translations and lamp moves */
+    size_t nbPendingMoves() const { return m_journal.size() + m_unrecordedRotations + m_unrecordedTranslations + m_unrecordedLampMoves; }
     int lightInformationSize() const { return m_lightInformationSize; }
     const Material *hostMaterials() const { return m_hMaterials.data(); }
     const std::vector<RandomBuffer> &hostRandoms();
@@ -536,7 +539,7 @@ protected:
          * those of the last full build, GPUKernel.cpp:1378-1460 refits them, it does not re-hash) */
         if (!m_frames[m_frame].levelsBuilt)
             buildLevelsOnHost();
-        if ((!m_pendingRotations.empty() || m_unrecordedRotations || m_morphPending) && !m_buildingLevels)
+        if (hostLags() && !m_buildingLevels)
             syncHost();
         return m_frames[m_frame];
     }
@@ -575,6 +578,10 @@ protected:
     void buildLevelsOnHost();
     /* engine hook: apply the rotation to the resident scene; false = not done, nothing changed */
     virtual bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) { return false; }
+    /* engine hooks: apply the translation to the resident scene; set the centre of lamp `slot` of the resident scene (the
+     * primitive m_hLamps[slot]) and of its light record; false = not done, nothing changed */
+    virtual bool deviceTranslatePrimitives(const vec3f &) { return false; }
+    virtual bool deviceMoveLamp(int, const vec3f &) { return false; }
     /* engine hook: the pixel stage of a JPEG texture (csrc/jpeg_pixels.h) - coefficient blocks as
      * ImageLoader::parseJPEG leaves them to frame.width * frame.height * 3 bytes in `rgb`.  Here: a loop on the CPU;
      * false = the engine failed (its error is pending) */
@@ -593,6 +600,8 @@ protected:
     virtual bool isoField(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field);
     virtual int isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity);
     void rotatePrimitivesOnly(Frame &f, const vec3f &rotationCenter, const vec3f &cosA, const vec3f &sinA);
+    /* translatePrimitives' loop over the level-0 boxes (no box is updated) */
+    void translatePrimitivesOnly(Frame &f, const vec3f &translation);
     void refitBoxes(Frame &f);
     /* engine hook: blend the resident scene at that weight (the keys handed over first where the engine has none:
      * morphKeys); false = not done, nothing changed */
@@ -610,6 +619,10 @@ protected:
     /* the frame the engine's resident scene was uploaded from, -1: none (a frame switch without a flatten leaves the
      * device with another frame than the current one: that one is not morphed over there) */
     long m_residentFrame = -1;
+    /* a lamp was moved on the resident scene since its upload: a morph over there would put the lamp back at its keys'
+     * place and leave its light record behind, so morphFrame does not offer it to the engine (which would decline it,
+     * after the keys were handed over for nothing) and the host route serves it */
+    bool m_lampMovedOnDevice = false;
 
     /* box-tree build (GPUKernel.h:318-324) */
     int processBoxes(const int boxSize, bool simulate);
@@ -666,17 +679,31 @@ protected:
     bool m_texturesTransfered;
     bool m_randomsTransfered;
     bool m_hostTouched = true; /* scene store accessed since the last upload */
-    struct PendingRotation
+    /* the journal: what the engine applied to the resident scene and the store has not replayed, in order */
+    struct PendingMove
     {
-        vec3f center, cosA, sinA;
+        enum Kind
+        {
+            ROTATION,    /* v: the centre, cosA, sinA */
+            TRANSLATION, /* v: the translation */
+            LAMP_MOVE    /* v: the centre of primitive `index` */
+        } kind;
+        vec3f v, cosA, sinA;
+        unsigned int index;
     };
-    std::vector<PendingRotation> m_pendingRotations;
-    /* an animation that runs for hours: past this many the rotations are only counted - the store then
-     * catches up from the device's primitives, which it does for more than a handful anyway */
+    std::vector<PendingMove> m_journal;
+    size_t m_journalRotations = 0; /* the rotations among them */
+    /* an animation that runs for hours: past this many the moves are only counted - the store then
+     * catches up from the device's primitives, which it does for more than a handful of rotations anyway */
     static constexpr size_t MAX_RECORDED_ROTATIONS = 100000;
-    size_t m_unrecordedRotations = 0;
+    size_t m_unrecordedRotations = 0, m_unrecordedTranslations = 0, m_unrecordedLampMoves = 0;
+    /* the store lags behind the resident scene */
+    bool hostLags() const { return nbPendingMoves() > 0 || m_morphPending; }
+    /* a move the engine has served goes into the journal, or past MAX_RECORDED_ROTATIONS into the counts */
+    void recordMove(const PendingMove &move);
+    void clearJournal();
     /* a morph the engine applied to the resident scene and the store has not replayed (it supersedes what was pending
-     * before it; m_pendingRotations are the rotations since) */
+     * before it; m_journal are the moves since) */
     bool m_morphPending = false;
     float m_pendingMorphWeight = 0.f;
 

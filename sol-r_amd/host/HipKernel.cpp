@@ -5,7 +5,9 @@
  */
 #include "HipKernel.h"
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -154,6 +156,7 @@ void HipKernel::render_begin(const float timer)
             m_hostTouched = false; /* device and host hold the same scene from here on */
             m_morphKeysFrame = -1; /* (the upload dropped the engine's morph keys) */
             m_residentFrame = (long)m_frame;
+            m_lampMovedOnDevice = false;
             mark("render_begin: lights, movable flags");
         }
         if (!m_randomsTransfered)
@@ -230,6 +233,22 @@ bool HipKernel::deviceMorphFrame(float weight)
         m_morphKeysNbFrames = (long)m_nbFrames;
     }
     return solr_hip_morph_primitives(weight, m_sceneInfo.viewDistance) == 1;
+}
+
+bool HipKernel::deviceTranslatePrimitives(const vec3f &translation)
+{
+    if (!m_deviceInitialized)
+        return false;
+    const float t[3] = {translation.x, translation.y, translation.z};
+    return solr_hip_translate_primitives(t, m_sceneInfo.viewDistance) == 1;
+}
+
+bool HipKernel::deviceMoveLamp(int slot, const vec3f &center)
+{
+    if (!m_deviceInitialized)
+        return false;
+    const float c[3] = {center.x, center.y, center.z};
+    return solr_hip_move_lamp(slot, c) == 1;
 }
 
 bool HipKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb)
@@ -332,9 +351,11 @@ bool HipKernel::primitivesFromDevice(Frame &f)
         return false;
     /* nothing is written before everything is known to be writable: a half-updated store could not fall back
      * to the replay */
+    /* (the first nbActiveLamps flattened primitives are the lamps: no rotation moves them, a lamp move sets their p0) */
+    const size_t nbLamps = (size_t)std::max(f.nbActiveLamps, 0);
     std::vector<CPUPrimitive *> target(m_hPrimitives.size(), nullptr);
     for (size_t i = 0; i < m_hPrimitives.size(); ++i)
-        if (m_hMovable[i] && !(target[i] = f.primitives.lookup((unsigned int)m_hPrimitives[i].index)))
+        if ((m_hMovable[i] || i < nbLamps) && !(target[i] = f.primitives.lookup((unsigned int)m_hPrimitives[i].index)))
             return false;
     for (size_t i = 0; i < m_hPrimitives.size(); ++i)
     {
@@ -343,6 +364,8 @@ bool HipKernel::primitivesFromDevice(Frame &f)
             continue;
         const float *r = &data[i * 32];
         p->p0 = make_vec3f(r[0], r[1], r[2]);
+        if (!m_hMovable[i])
+            continue;
         p->p1 = make_vec3f(r[8], r[9], r[10]);
         p->p2 = make_vec3f(r[12], r[13], r[14]);
         p->n0 = make_vec3f(r[16], r[17], r[18]);
@@ -496,7 +519,10 @@ void ReplayKernel::render_begin(const float timer)
 {
     HostOnlyKernel::render_begin(timer);
     if (!m_primitivesTransfered)
+    {
         syncHost();
+        m_lampMovedOnDevice = false;
+    }
     m_primitivesTransfered = true; /* the upload a real engine does here */
     m_hostTouched = false;
     m_morphKeysFrame = -1;
@@ -506,6 +532,22 @@ void ReplayKernel::render_begin(const float timer)
 bool ReplayKernel::deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &)
 {
     ++m_claimed;
+    return true;
+}
+
+bool ReplayKernel::deviceTranslatePrimitives(const vec3f &t)
+{
+    if (!std::isfinite(t.x) || !std::isfinite(t.y) || !std::isfinite(t.z))
+        return false;
+    ++m_claimedTranslations;
+    return true;
+}
+
+bool ReplayKernel::deviceMoveLamp(int, const vec3f &c)
+{
+    if (!std::isfinite(c.x) || !std::isfinite(c.y) || !std::isfinite(c.z))
+        return false;
+    ++m_claimedLampMoves;
     return true;
 }
 

@@ -60,6 +60,10 @@ protected:
     bool deviceRotatePrimitives(const vec3f &center, const vec3f &cosA, const vec3f &sinA) override;
     /* morphFrame on the resident scene, solr_hip_set_morph_keys + solr_hip_morph_primitives (include/solr_hip.h) */
     bool deviceMorphFrame(float weight) override;
+    /* translatePrimitives and a lamp's setPrimitiveCenter on the resident scene, solr_hip_translate_primitives and
+     * solr_hip_move_lamp (include/solr_hip.h) */
+    bool deviceTranslatePrimitives(const vec3f &translation) override;
+    bool deviceMoveLamp(int slot, const vec3f &center) override;
     void fetchPrimitiveIds() override;
     void fetchBitmap() override;
     bool primitivesFromDevice(Frame &f) override;
@@ -108,20 +112,24 @@ protected:
 
 /* Test double for the animated-scene protocol (GPUKernel::rotatePrimitives / morphFrame / syncHost): a host-only
  * store that claims, like an engine with a resident scene would, to have uploaded the scene at the first
- * frame and to apply every rotation and every morph "over there" - so that the lazy replay of what is pending can be
- * checked against the eager host route without a GPU.  Renders nothing. */
+ * frame and to apply every rotation, translation, lamp move and morph "over there" - so that the lazy replay of what is
+ * pending can be checked against the eager host route without a GPU.  Renders nothing. */
 class ReplayKernel : public HostOnlyKernel
 {
 public:
     void render_begin(const float timer) override;
     int nbClaimedRotations() const { return m_claimed; }
     int nbClaimedMorphs() const { return m_claimedMorphs; }
+    int nbClaimedTranslations() const { return m_claimedTranslations; }
+    int nbClaimedLampMoves() const { return m_claimedLampMoves; }
 
 protected:
     bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) override;
     bool deviceMorphFrame(float weight) override;
+    bool deviceTranslatePrimitives(const vec3f &) override;
+    bool deviceMoveLamp(int slot, const vec3f &center) override;
 
 private:
-    int m_claimed = 0, m_claimedMorphs = 0;
+    int m_claimed = 0, m_claimedMorphs = 0, m_claimedTranslations = 0, m_claimedLampMoves = 0;
 };
 }

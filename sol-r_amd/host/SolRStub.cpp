@@ -440,6 +440,28 @@ int SolRx_PendingRotations()
     return (int)SingletonKernel::kernel()->nbPendingRotations();
 }
 
+/* Extension: GPUKernel::translatePrimitives + compactBoxes(false), as the reference's scenes run it behind a rotation
+ * (apps/scenes/Scene.cpp:1546-1548) */
+int SolRx_TranslatePrimitives(double x, double y, double z)
+{
+    SingletonKernel::kernel()->translatePrimitives(solr::make_vec3f((float)x, (float)y, (float)z));
+    SingletonKernel::kernel()->compactBoxes(false);
+    return 0;
+}
+
+/* Extension: GPUKernel::setPrimitiveCenter + compactBoxes(false), the viewer's lamp drag (apps/solrViewer.cpp:1058-1069) */
+int SolRx_SetPrimitiveCenter(int index, double x, double y, double z)
+{
+    SingletonKernel::kernel()->setPrimitiveCenter(index, solr::make_vec3f((float)x, (float)y, (float)z));
+    SingletonKernel::kernel()->compactBoxes(false);
+    return 0;
+}
+
+int SolRx_PendingMoves()
+{
+    return (int)SingletonKernel::kernel()->nbPendingMoves();
+}
+
 int SolRx_SyncHost()
 {
     SingletonKernel::kernel()->syncHost();

@@ -203,6 +203,14 @@ int SolRx_MorphFrame(double weight);
 int SolRx_SetPrimitiveIsMovable(int index, int movable);
 int SolRx_PendingMorph();
 int SolRx_PendingRotations();
+/* the other rigid moves of a scene (the reference's stub has no call for either): GPUKernel::translatePrimitives, and
+ * GPUKernel::setPrimitiveCenter - the viewer's lamp drag -, each followed by compactBoxes(false) as the reference's
+ * applications follow them.  With the HIP engine and an unchanged resident scene a translation, and the centre of a
+ * primitive that is a lamp, are applied on the device.  SolRx_PendingMoves: rotations, translations and lamp moves applied
+ * there that the host scene store has not replayed yet (SolRx_PendingRotations: the rotations among them) */
+int SolRx_TranslatePrimitives(double x, double y, double z);
+int SolRx_SetPrimitiveCenter(int index, double x, double y, double z);
+int SolRx_PendingMoves();
 int SolRx_SyncHost();
 int SolRx_GetMovable(const unsigned char **flags, int *nbPrimitives);
 /* float framebuffer of the last frame, W*H records */
