@@ -122,6 +122,28 @@ int solr_hip_probe_intersection_shader(const SceneInfo *sceneInfo, int n, const 
                                        float *attributes, float *color, float *bump, float *specular,
                                        float *ambientOcclusion);
 
+/* The builders of the order-free lists on a nested node list of the CALLER'S (tests/list_builder_cases.py), no resident
+ * scene needed: rows[n][2][4] and start[n] as list_builders.h lays a list out; prims: nbPrims primitive records of 8 rows
+ * with `margin` and `dominantShare` (build_bounds.h BuildBounds), or NULL for the boxes as uploaded; threshold:
+ * pruneInnerNodes'.  route 0: the host's buildFreeOrderLists, no decider, every node its own origin - NO GPU needed;
+ * 1: solrBuildOrderFreeListsOnDevice (solr_lists.hip) from the host arrays with identity origins; 2: the same with
+ * origin == NULL, rows, start indices and records copied to device memory first (the arena's route).  Routes 1 and 2 run
+ * on solr_hip_get_device().  Returns the length of one list with *nbPruned set and the eight lists one behind the other in
+ * outRows (16 floats x 8 x length), outStart and outOrigin (8 x length), each with room for 8 x capacity nodes (outRows ==
+ * NULL: the length alone); 0 where the builder DECLINED (fewer than two leaves; on the device also depth or an allocation
+ * - what the engine leaves to the host), nothing written and no error set; -1 with the error set for a list that is not
+ * nested, records out of range or an error of the runtime's. */
+int solr_hip_probe_free_lists(int route, int n, const float *rows, const int *start, const float *prims, int nbPrims, float margin,
+                              double dominantShare, double threshold, int *nbPruned, float *outRows, int *outStart, int *outOrigin,
+                              int capacity);
+
+/* pruneInnerNodes (list_builders.cpp) on a nested node list of the caller's, every node its own origin.  route 0: the
+ * host's decisions (no GPU needed); 1: solrPruneDecisionsOnDevice (solr_lists.hip) as the decider, *declined = 1 where it
+ * left the decisions to the host (which then made them).  Returns the new node count with *nbPruned set and the list in
+ * outRows / outStart / outOrigin (room for `capacity` nodes; outRows == NULL: the count alone), or -1 with the error set. */
+int solr_hip_probe_prune_list(int route, int n, const float *rows, const int *start, double threshold, int *nbPruned, int *declined,
+                              float *outRows, int *outStart, int *outOrigin, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,19 @@ enum BuildBoundsPlainKind
     BB_KIND_PLANE_XZ = 4
 };
 
+/* The bin of a leaf's centre c among the `bins` bins of a node whose centres begin at `origin`, scale = bins / extent:
+ * the one place where both builders turn a float into an integer.  Clamped in float BEFORE the conversion, so that it
+ * is defined on both sides whatever the product: once the extent of the centres is below about 4.7e-38 the scale is
+ * infinite and the product +inf or (0 x inf) NaN - (int) of those is undefined on the host (x86 gives INT_MIN: bin 0)
+ * and saturates on the device (bin 0 or the last).  Here NaN is bin 0 and +inf the last bin.  Any product in [0, bins),
+ * which is every one of a scene with ordinary extents, gets the bin min(bins - 1, max(0, (int)product)) always gave. */
+SOLR_BUILD_BOUNDS_FN int centreBin(float c, float origin, float scale, int bins)
+{
+    const float at = (c - origin) * scale;
+    const float last = (float)(bins - 1);
+    return (int)(at > 0.f ? (at < last ? at : last) : 0.f);
+}
+
 /* The build box of the leaf { row0, row1 } whose `count` primitives begin at prims[8 * start].  true: the leaf holds
  * nothing but axis-plane rectangles and lo / hi are their thin box cut with the leaf's own; false: lo / hi are the
  * leaf's box as uploaded.  byKind: a rectangle is what the record's tag calls a plain plane, not what its type says -

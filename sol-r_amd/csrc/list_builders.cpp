@@ -613,7 +613,7 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
                     if (!(scale[axis] > 0.f))
                         continue;
                     const float c = 0.5f * (l.lo[axis] + l.hi[axis]);
-                    const int b = std::min(BINS - 1, std::max(0, (int)((c - clo[axis]) * scale[axis])));
+                    const int b = centreBin(c, clo[axis], scale[axis], BINS);
                     ++counts[axis][b];
                     float *lo3 = blo[axis][b], *hi3 = bhi[axis][b];
                     lo3[0] = std::min(lo3[0], l.lo[0]), lo3[1] = std::min(lo3[1], l.lo[1]), lo3[2] = std::min(lo3[2], l.lo[2]);
@@ -674,7 +674,7 @@ int buildFreeOrderLists(const std::vector<float4> &rows, const std::vector<int> 
             mid = (int)(std::stable_partition(leaves.begin() + r.from, leaves.begin() + r.to,
                                        [&](const Leaf &l) {
                                            const float c = 0.5f * (l.lo[axis] + l.hi[axis]);
-                                           return std::min(BINS - 1, std::max(0, (int)((c - origin) * scale))) <= bin;
+                                           return centreBin(c, origin, scale, BINS) <= bin;
                                        }) -
                         leaves.begin());
             if (mid == r.from || mid == r.to)

@@ -3,7 +3,7 @@
  * engine state, no environment, no HIP call.  The engine's scene units (solr_uploads.hip,
  * solr_arena.hip, solr_rotation.hip) call them for the walk-order list of every upload, for the order-free lists where the
  * device builders (solr_lists.hip) are switched off or decline, and for the refit plan; they
- * are the reference the device builders are held to (tests/test_lists_gpu.py), and tests/list_builders_check.cpp runs
+ * are the reference the device builders are held to (tests/test_lists_gpu.py, tests/test_list_builders_device_gpu.py), and tests/list_builders_check.cpp runs
  * them on their own.
  * A node list: two float4 rows per node, { min.xyz, max.z } { max.xy, nbPrimitives, skip } (scene_layout.h); `start`: the
  * first primitive of every node; `origin`: the node of the reference's list every node is, -1 for a node made here.

@@ -27,7 +27,8 @@
  * gives k_emit the unions of the uploaded boxes for the inner nodes.
  * Every quantity is a min, a max, a count or a double-precision expression of those: none depends on the order in
  * which the atomics land, so the lists are the host's BIT FOR BIT (tests/test_lists_gpu.py holds them to the host
- * builder on the BASELINE scenes; SOLR_HIP_LISTS_ON_HOST=1 keeps the host path).  Zeros are canonical (+0) in both
+ * builder on the BASELINE scenes, tests/test_list_builders_device_gpu.py on node lists made to steer each branch below;
+ * SOLR_HIP_LISTS_ON_HOST=1 keeps the host path).  Zeros are canonical (+0) in both
  * builders' inner bounds - std::min keeps whichever zero came first, an atomic cannot.
  *
  * Declined (returns -1, the caller builds on the host): fewer than two leaves, a tree deeper than 64 levels, an
@@ -250,9 +251,10 @@ __global__ __launch_bounds__(256) void k_bounds(Node *nodes, const int *nodeOf, 
     }
 }
 
+/* (build_bounds.h: the host's bin, defined for every product) */
 __device__ inline int binOf(float c, float origin, float scale)
 {
-    return min(BINS - 1, max(0, (int)((c - origin) * scale)));
+    return solreng::centreBin(c, origin, scale, BINS);
 }
 
 __device__ inline void ldsMinF(float *addr, float v)

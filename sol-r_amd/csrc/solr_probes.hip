@@ -3,7 +3,8 @@
  * once per element of arrays of inputs, for the comparison with the reference's own functions on the same arrays
  * (tests/test_engine_probes_gpu.py; the reference side is oracle/ref_probes.cl around RayTracer.cl).  No rendering
  * code lives here: every kernel calls the functions of rt_device.h that k_standardRenderer is built from, in the
- * instantiations the renderer launches.  gfx950 only.
+ * instantiations the renderer launches.  At the end: the list builders (list_builders.cpp, solr_lists.hip) on a node list
+ * of the caller's (tests/test_list_builder_cases.py, tests/test_list_builders_device_gpu.py).  gfx950 only.
  */
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,8 @@
 #include "../../include/solr_hip_probes.h"
 #include "rt_device.h"
 #include "renderer.h"
+#include "list_builders.h"
+#include "lists_device.h"
 
 using namespace solrdev;
 
@@ -649,5 +652,237 @@ int solr_hip_probe_intersection_shader(const SceneInfo *sceneInfo, int n, const 
     hipLaunchKernelGGL(k_probeIntersectionShader<EVERYTHING>, waves(n), dim3(64), 0, stream, S, *sceneInfo, n, dI, dA, dAttr,
                        dC, dB, dS, dAo);
     return a.finish(stream) ? EVERYTHING : -1;
+}
+}
+
+/* ---- the list builders on a node list of the caller's ------------------------------------------------------------------
+ * buildFreeOrderLists and pruneInnerNodes (list_builders.cpp) and their device forms (solr_lists.hip) handed one and the
+ * same nested list: no scene, no arena, no engine state but the device number.  Route 0 makes no HIP call. */
+namespace
+{
+/* on the engine's device whichever thread calls; the caller's current device is restored on the way out */
+struct OnEngineDevice
+{
+    int before = -1;
+    bool fine = false;
+    OnEngineDevice()
+    {
+        if (hipGetDevice(&before) != hipSuccess)
+            before = -1;
+        const hipError_t e = hipSetDevice(solr_hip_get_device());
+        fine = e == hipSuccess;
+        if (!fine)
+            solrprobe::fail((int)e, (std::string("solr_hip_probe: hipSetDevice: ") + hipGetErrorString(e)).c_str());
+    }
+    ~OnEngineDevice()
+    {
+        if (before >= 0)
+            (void)hipSetDevice(before);
+    }
+};
+
+/* a device builder said -1: an error of the runtime's, or has it declined?  false (error set) for the first */
+bool onlyDeclined(const char *who)
+{
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipGetLastError();
+    if (e == hipSuccess)
+        return true;
+    solrprobe::fail((int)e, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
+    return false;
+}
+
+/* the caller's list as the builders take it; false (error set) unless the skip pointers are nested, the counts are not
+ * negative and, where there are primitive records, every leaf's lie among them */
+bool takeList(const char *who, int n, const float *rows, const int *start, int nbPrims, bool withPrims, std::vector<float4> &rowsOut,
+              std::vector<int> &startOut)
+{
+    if (n < 1 || !rows || !start)
+    {
+        solrprobe::fail(-1, (std::string(who) + ": no node list").c_str());
+        return false;
+    }
+    rowsOut.resize(2 * (size_t)n);
+    memcpy(rowsOut.data(), rows, 32 * (size_t)n);
+    startOut.assign(start, start + n);
+    std::vector<int> ends;
+    for (int i = 0; i < n; ++i)
+    {
+        const int count = solreng::bitsi(rowsOut[2 * i + 1].z), skip = solreng::bitsi(rowsOut[2 * i + 1].w);
+        while (!ends.empty() && ends.back() <= i)
+            ends.pop_back();
+        const bool nested = skip >= 1 && (long)i + skip <= n && (ends.empty() || i + skip <= ends.back());
+        const bool held = !withPrims || count == 0 || (start[i] >= 0 && (long)start[i] + count <= nbPrims);
+        if (!nested || count < 0 || !held)
+        {
+            char text[160];
+            snprintf(text, sizeof(text), "%s: node %d (count %d, skip %d, start %d) of %d nodes and %d primitives", who, i, count, skip,
+                     start[i], n, nbPrims);
+            solrprobe::fail(-1, text);
+            return false;
+        }
+        ends.push_back(i + skip);
+    }
+    return true;
+}
+} // namespace
+
+extern "C" {
+
+int solr_hip_probe_free_lists(int route, int n, const float *rows, const int *start, const float *prims, int nbPrims, float margin,
+                              double dominantShare, double threshold, int *nbPruned, float *outRows, int *outStart, int *outOrigin,
+                              int capacity)
+{
+    const char *who = "solr_hip_probe_free_lists";
+    std::vector<float4> list, records;
+    std::vector<int> first;
+    if (nbPruned)
+        *nbPruned = 0;
+    if (route < 0 || route > 2 || nbPrims < 0 || (prims == nullptr && nbPrims > 0))
+    {
+        solrprobe::fail(-1, "solr_hip_probe_free_lists: route 0, 1 or 2; primitive records or none");
+        return -1;
+    }
+    if (!takeList(who, n, rows, start, nbPrims, prims != nullptr, list, first))
+        return -1;
+    if (prims)
+    {
+        records.resize((size_t)solreng::LB_PRIM_ROWS * nbPrims + 1);
+        memcpy(records.data(), prims, 16 * (size_t)solreng::LB_PRIM_ROWS * nbPrims);
+    }
+    solreng::BuildBounds build;
+    if (prims)
+    {
+        build.prims = records.data();
+        build.margin = margin;
+        build.dominantShare = dominantShare;
+    }
+    std::vector<int> identity(n);
+    for (int i = 0; i < n; ++i)
+        identity[i] = i;
+    std::vector<float4> builtRows;
+    std::vector<int> builtStart, builtOrigin;
+    int count = 0, pruned = 0;
+    if (route == 0)
+        count = solreng::buildFreeOrderLists(list, first, identity, builtRows, builtStart, builtOrigin, &pruned, threshold, nullptr, build);
+    else
+    {
+        OnEngineDevice device;
+        if (!device.fine)
+            return -1;
+        Arrays a;
+        SolrDeviceLists stay;
+        if (route == 1)
+            count = solrBuildOrderFreeListsOnDevice(list.data(), first.data(), identity.data(), n, threshold, &pruned, 0, &stay, build);
+        else
+        {
+            const float4 *dRows = a.in(list.data(), list.size());
+            const int *dStart = a.in(first.data(), first.size());
+            if (prims)
+                build.prims = a.in(records.data(), records.size());
+            if (a.failed)
+                return -1;
+            count = solrBuildOrderFreeListsOnDevice(dRows, dStart, nullptr, n, threshold, &pruned, 0, &stay, build);
+        }
+        bool fine = true;
+        if (count < 0)
+        {
+            fine = onlyDeclined(who);
+            count = 0;
+        }
+        else if (outRows && count <= capacity)
+        {
+            builtRows.resize(16 * (size_t)count);
+            builtStart.resize(8 * (size_t)count);
+            builtOrigin.resize(8 * (size_t)count);
+            fine = a.finish(0);
+            bool &failed = a.failed;
+            PROBE_HIP(hipMemcpy(builtRows.data(), stay.rows, builtRows.size() * 16, hipMemcpyDeviceToHost));
+            PROBE_HIP(hipMemcpy(builtStart.data(), stay.start, builtStart.size() * 4, hipMemcpyDeviceToHost));
+            PROBE_HIP(hipMemcpy(builtOrigin.data(), stay.origin, builtOrigin.size() * 4, hipMemcpyDeviceToHost));
+            fine = fine && !failed;
+        }
+        if (stay.rows)
+            (void)hipFree(stay.rows);
+        if (stay.start)
+            (void)hipFree(stay.start);
+        if (stay.origin)
+            (void)hipFree(stay.origin);
+        if (!fine)
+            return -1;
+    }
+    if (nbPruned)
+        *nbPruned = pruned;
+    if (count == 0 || outRows == nullptr)
+        return count; /* declined; or the size alone */
+    if (!outStart || !outOrigin || count > capacity)
+    {
+        solrprobe::fail(-1, "solr_hip_probe_free_lists: capacity too small");
+        return -1;
+    }
+    memcpy(outRows, builtRows.data(), builtRows.size() * 16);
+    memcpy(outStart, builtStart.data(), builtStart.size() * 4);
+    memcpy(outOrigin, builtOrigin.data(), builtOrigin.size() * 4);
+    return count;
+}
+
+int solr_hip_probe_prune_list(int route, int n, const float *rows, const int *start, double threshold, int *nbPruned, int *declined,
+                              float *outRows, int *outStart, int *outOrigin, int capacity)
+{
+    const char *who = "solr_hip_probe_prune_list";
+    std::vector<float4> list;
+    std::vector<int> first;
+    if (nbPruned)
+        *nbPruned = 0;
+    if (declined)
+        *declined = 0;
+    if (route < 0 || route > 1)
+    {
+        solrprobe::fail(-1, "solr_hip_probe_prune_list: route 0 or 1");
+        return -1;
+    }
+    if (!takeList(who, n, rows, start, 0, false, list, first))
+        return -1;
+    std::vector<int> origin(n);
+    for (int i = 0; i < n; ++i)
+        origin[i] = i;
+    int pruned = 0, count = 0;
+    if (route == 0)
+        count = solreng::pruneInnerNodes(list, first, origin, &pruned, threshold);
+    else
+    {
+        OnEngineDevice device;
+        if (!device.fine)
+            return -1;
+        bool fine = true, left = false;
+        count = solreng::pruneInnerNodes(list, first, origin, &pruned, threshold,
+                                         [&](const float4 *r, int nb, double t, std::vector<char> &keep) {
+                                             const int decided = solrPruneDecisionsOnDevice(r, nb, t, keep, 0);
+                                             if (decided < 0)
+                                             {
+                                                 left = true;
+                                                 fine = onlyDeclined(who);
+                                             }
+                                             return decided;
+                                         });
+        if (!fine)
+            return -1;
+        if (declined)
+            *declined = left ? 1 : 0;
+    }
+    if (nbPruned)
+        *nbPruned = pruned;
+    if (outRows == nullptr)
+        return count;
+    if (!outStart || !outOrigin || count > capacity)
+    {
+        solrprobe::fail(-1, "solr_hip_probe_prune_list: capacity too small");
+        return -1;
+    }
+    memcpy(outRows, list.data(), 32 * (size_t)count);
+    memcpy(outStart, first.data(), 4 * (size_t)count);
+    memcpy(outOrigin, origin.data(), 4 * (size_t)count);
+    return count;
 }
 }

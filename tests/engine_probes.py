@@ -55,8 +55,11 @@ def declare(hip):
     hip.solr_hip_probe_last_frame.restype = None
     hip.solr_hip_probe_list_copy.argtypes = [i, i, v, i]
     hip.solr_hip_probe_walk_offer.argtypes = [v, i, v]
+    hip.solr_hip_probe_free_lists.argtypes = [i, i, v, v, v, i, C.c_float, C.c_double, C.c_double, v, v, v, v, i]
+    hip.solr_hip_probe_prune_list.argtypes = [i, i, v, v, C.c_double, v, v, v, v, v, i]
     for name in ("box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "vectors",
-                 "make_color", "skybox", "intersection_shader", "order_tiles", "list_copy", "walk_offer"):
+                 "make_color", "skybox", "intersection_shader", "order_tiles", "list_copy", "walk_offer", "free_lists",
+                 "prune_list"):
         getattr(hip, "solr_hip_probe_" + name).restype = i
     del P
 
@@ -138,6 +141,49 @@ def walk_offer(hip, si, exact=0):
     offer = {k: int(x) for k, x in zip(keys, out[:6])}
     offer["margin"], offer["extent"] = out[6:].view(f32)
     return offer
+
+
+HOST_BUILDER, DEVICE_FROM_HOST_ROWS, DEVICE_FROM_DEVICE_ROWS = 0, 1, 2     # solr_hip_probe_free_lists / _prune_list: route
+
+
+def free_lists(hip, route, rows, start, prims=None, margin=0.0, share=0.25, threshold=1.0):
+    """the eight order-free lists a builder makes of a nested node list (solr_hip_probe_free_lists): None where the builder
+    declined, else dict(count, pruned, rows (8, count, 2, 4) float32, start and origin (8, count) int32).  Route 0 needs no
+    GPU.  An error of the runtime's raises."""
+    declare(hip)
+    rows, start = np.ascontiguousarray(rows, f32), np.ascontiguousarray(start, i32)
+    n = len(start)
+    assert rows.shape == (n, 2, 4)
+    records = None if prims is None else np.ascontiguousarray(prims, f32)
+    assert records is None or records.shape[1:] == (8, 4)
+    capacity = 2 * n                                    # (a binary tree over at most n leaves)
+    out_rows = np.full((8 * capacity, 2, 4), np.nan, f32)
+    out_start, out_origin = np.full(8 * capacity, -7, i32), np.full(8 * capacity, -7, i32)
+    pruned = C.c_int(-1)
+    count = _check(hip, hip.solr_hip_probe_free_lists(route, n, _p(rows), _p(start), None if records is None else _p(records),
+                                                      0 if records is None else len(records), margin, share, threshold,
+                                                      C.byref(pruned), _p(out_rows), _p(out_start), _p(out_origin), capacity),
+                   "probe_free_lists (route %d)" % route)
+    if count == 0:
+        return None
+    return dict(count=count, pruned=pruned.value, rows=out_rows[:8 * count].reshape(8, count, 2, 4).copy(),
+                start=out_start[:8 * count].reshape(8, count).copy(), origin=out_origin[:8 * count].reshape(8, count).copy())
+
+
+def prune_list(hip, route, rows, start, threshold=1.0):
+    """pruneInnerNodes on a nested node list (solr_hip_probe_prune_list): dict(count, pruned, declined, rows, start, origin)"""
+    declare(hip)
+    rows, start = np.ascontiguousarray(rows, f32), np.ascontiguousarray(start, i32)
+    n = len(start)
+    assert rows.shape == (n, 2, 4)
+    out_rows = np.full((n, 2, 4), np.nan, f32)
+    out_start, out_origin = np.full(n, -7, i32), np.full(n, -7, i32)
+    pruned, declined = C.c_int(-1), C.c_int(-1)
+    count = _check(hip, hip.solr_hip_probe_prune_list(route, n, _p(rows), _p(start), threshold, C.byref(pruned), C.byref(declined),
+                                                      _p(out_rows), _p(out_start), _p(out_origin), n),
+                   "probe_prune_list (route %d)" % route)
+    return dict(count=count, pruned=pruned.value, declined=declined.value, rows=out_rows[:count].copy(),
+                start=out_start[:count].copy(), origin=out_origin[:count].copy())
 
 
 def primitive_records(hip):
