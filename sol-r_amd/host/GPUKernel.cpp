@@ -86,7 +86,6 @@ GPUKernel::GPUKernel()
     , m_frame(0)
     , m_nbFrames(0)
     , m_treeDepth(2) /* reference: GPUKernel.cpp:198 */
-    , m_primitivesTransfered(false)
     , m_materialsTransfered(false)
     , m_texturesTransfered(false)
     , m_randomsTransfered(false)
@@ -158,7 +157,7 @@ void GPUKernel::cleanup()
     m_nbActiveTextures = 0;
     m_textureFilenames.clear();
     m_materialsTransfered = false;
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     m_texturesTransfered = false;
     m_randomsTransfered = false;
     m_buffersInitialized = false;
@@ -213,7 +212,7 @@ void GPUKernel::setPrimitive(const int &index, float x0, float y0, float z0, flo
 void GPUKernel::setPrimitive(const int &index, float x0, float y0, float z0, float x1, float y1, float z1, float x2,
                              float y2, float z2, float w, float h, float d, int materialId)
 {
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     CPUPrimitive *pp = (index >= 0) ? getPrimitive(index) : nullptr;
     if (!pp)
     {
@@ -366,7 +365,7 @@ void GPUKernel::setPrimitiveCenter(unsigned int index, const vec3f &center)
      * nothing of what is uploaded follows a lamp's centre but the primitive itself and its light record, so the
      * engine may set both in place and the store follows when somebody looks (syncHost).  Any other primitive's
      * centre is the host's: its boxes would have to follow */
-    if (m_primitivesTransfered && !m_hostTouched && m_residentFrame == (long)m_frame)
+    if (m_resident.offers(m_frame))
     {
         const int nbLamps = std::min(frameAsIs().nbActiveLamps, (int)m_hLamps.size());
         for (int slot = 0; slot < nbLamps; ++slot)
@@ -374,17 +373,11 @@ void GPUKernel::setPrimitiveCenter(unsigned int index, const vec3f &center)
             {
                 if (!deviceMoveLamp(slot, center))
                     break;
-                PendingMove move;
-                move.kind = PendingMove::LAMP_MOVE;
-                move.v = center;
-                move.cosA = move.sinA = make_vec3f();
-                move.index = index;
-                recordMove(move);
-                m_lampMovedOnDevice = true;
+                m_resident.record({ResidentScene::Move::LAMP_MOVE, center, make_vec3f(), make_vec3f(), index});
                 return;
             }
     }
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     if (CPUPrimitive *p = getPrimitive(index))
         p->p0 = center;
 }
@@ -617,9 +610,9 @@ int GPUKernel::compactBoxes(bool reconstructBoxes)
 {
     /* rotations, translations, lamp moves or a morph applied on the device: the flattened scene over there is already
      * what the lines below would produce and upload */
-    if (!reconstructBoxes && hostLags())
+    if (!reconstructBoxes && m_resident.lags())
         return frameAsIs().nbActiveBoxes;
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     if (reconstructBoxes)
     {
         /* the engine builds the same tree on the device (0.2 s of maps and hashing for 100 k primitives on the
@@ -639,8 +632,7 @@ int GPUKernel::compactBoxes(bool reconstructBoxes)
 void GPUKernel::buildLevelsOnHost()
 {
     m_frames[m_frame].levelsBuilt = true; /* first: frame() below asks */
-    const bool outer = !m_buildingLevels;
-    m_buildingLevels = true;
+    const ResidentScene::BuildingLevels building(m_resident);
     Frame &f = frame();
     /* The reference resets only the lights box here
      * (GPUKernel.cpp:1049) and relies on resetFrame() having emptied the
@@ -669,8 +661,6 @@ void GPUKernel::buildLevelsOnHost()
         nbBoxes /= gridDivider;
     } while (nbBoxes > gridGranularity);
     m_frames[m_frame].levelsBuilt = true;
-    if (outer)
-        m_buildingLevels = false;
 }
 
 void GPUKernel::ensureLevels()
@@ -756,7 +746,7 @@ bool GPUKernel::buildTreeOnDevice()
     for (int level = 0; level < BOUNDING_BOXES_TREE_DEPTH; ++level)
         f.boundingBoxes[level].clear();
     m_treeDepth = depth;
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     f.nbActiveBoxes = 0;
     f.nbActivePrimitives = 0;
     f.nbActiveLamps = 0;
@@ -872,7 +862,7 @@ void GPUKernel::recursiveDataStreamToGPU(const int depth, CPUBoundingBox &parent
 void GPUKernel::streamDataToGPU()
 {
     Frame &f = frame();
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     f.nbActiveBoxes = 0;
     f.nbActivePrimitives = 0;
     f.nbActiveLamps = 0;
@@ -1092,30 +1082,42 @@ bool GPUKernel::morphKeys(std::vector<Primitive> &first, std::vector<Primitive> 
     return true;
 }
 
+bool GPUKernel::deviceMorphFrame(float weight)
+{
+    if (!m_resident.hasMorphKeys(m_frame, m_nbFrames))
+    {
+        /* the first morph after an upload: the key frames go to the engine, in the order of the resident primitives */
+        std::vector<Primitive> first, last;
+        if (!morphKeys(first, last) || !deviceSetMorphKeys(first, last))
+            return false;
+        m_resident.morphKeysTaken(m_frame, m_nbFrames);
+    }
+    return deviceMorphPrimitives(weight);
+}
+
 int GPUKernel::morphFrame(float weight)
 {
     if (m_nbFrames < 3 || m_frame == 0 || m_frame + 1 >= m_nbFrames || !std::isfinite(weight))
         return -1;
     /* the scene the device holds is the one the host holds (plus what is pending): the frames were compared when the
      * engine got its keys, and nothing has changed the store since */
-    const bool resident = m_primitivesTransfered && !m_hostTouched && m_residentFrame == (long)m_frame;
-    const bool compared = resident && m_morphKeysFrame == (long)m_frame && m_morphKeysNbFrames == (long)m_nbFrames;
+    const bool resident = m_resident.offers(m_frame);
+    const bool compared = resident && m_resident.hasMorphKeys(m_frame, m_nbFrames);
     if (!compared && !morphKeysMatch())
         return -1;
-    if (resident && !m_lampMovedOnDevice && deviceMorphFrame(weight))
+    /* (a lamp that was moved over there: a morph there would put it back at its keys' place and leave its light record
+     * behind, so such a morph is not offered to the engine - which would decline it, after the keys were handed over for
+     * nothing - and the host route serves it) */
+    if (resident && !m_resident.lampMoved && deviceMorphFrame(weight))
     {
-        /* every primitive has been set anew: what was pending before is superseded (no lamp move is among it: a morph
-         * behind one is not offered to the engine) */
-        clearJournal();
-        m_morphPending = true;
-        m_pendingMorphWeight = weight;
+        /* every primitive has been set anew: what was pending before is superseded (no lamp move is among it) */
+        m_resident.morphServed(weight);
         return 0;
     }
     ensureLevels(); /* from the primitives the tree was built with */
     /* (the lamp moves too: the loop below sets a lamp from its keys like any primitive, and its light record is made
      * from it when the frame is flattened) */
-    clearJournal();
-    m_morphPending = false;
+    m_resident.clear();
     Frame &f = frame();
     morphPrimitivesOnly(weight);
     refitBoxes(f);
@@ -1144,7 +1146,7 @@ void GPUKernel::resetAll()
         resetFrame();
     }
     m_frame = oldFrame;
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     m_nbActiveMaterials = -1;
     m_materialsTransfered = false;
     for (int i = 0; i < NB_MAX_TEXTURES; ++i)
@@ -1181,19 +1183,13 @@ void GPUKernel::rotatePrimitives(const vec3f &rotationCenter, const vec4f &angle
     vec3f sinA = make_vec3f(sinf(angles.x), sinf(angles.y), sinf(angles.z));
     /* the scene the device holds is the one the host holds (plus the rotations already pending): the
      * engine may turn it in place, and the host copy follows when somebody looks (syncHost) */
-    if (m_primitivesTransfered && !m_hostTouched && deviceRotatePrimitives(rotationCenter, cosA, sinA))
+    if (m_resident.offers(m_frame) && deviceRotatePrimitives(rotationCenter, cosA, sinA))
     {
-        PendingMove r;
-        r.kind = PendingMove::ROTATION;
-        r.v = rotationCenter;
-        r.cosA = cosA;
-        r.sinA = sinA;
-        r.index = 0;
-        recordMove(r);
+        m_resident.record({ResidentScene::Move::ROTATION, rotationCenter, cosA, sinA, 0});
         return;
     }
     Frame &f = frame();
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     rotatePrimitivesOnly(f, rotationCenter, cosA, sinA);
     refitBoxes(f);
 }
@@ -1251,52 +1247,20 @@ void GPUKernel::refitBoxes(Frame &f)
             updateOutterBoundingBox(entry.second, b - 1);
 }
 
-void GPUKernel::recordMove(const PendingMove &move)
-{
-    if (m_journal.size() >= MAX_RECORDED_ROTATIONS)
-    {
-        ++(move.kind == PendingMove::ROTATION      ? m_unrecordedRotations
-           : move.kind == PendingMove::TRANSLATION ? m_unrecordedTranslations
-                                                   : m_unrecordedLampMoves);
-        return;
-    }
-    m_journal.push_back(move);
-    if (move.kind == PendingMove::ROTATION)
-        ++m_journalRotations;
-}
-
-void GPUKernel::clearJournal()
-{
-    m_journal.clear();
-    m_journalRotations = 0;
-    m_unrecordedRotations = m_unrecordedTranslations = m_unrecordedLampMoves = 0;
-}
-
 void GPUKernel::syncHost()
 {
-    if (!hostLags())
+    if (!m_resident.lags())
         return;
-    const bool transfered = m_primitivesTransfered, touched = m_hostTouched;
+    ResidentScene::Replaying replaying(m_resident);
     ensureLevels(); /* from the primitives as they were built with, before the moves reach the store */
 
-    std::vector<PendingMove> pending;
-    pending.swap(m_journal);
-    const size_t unrecorded = m_unrecordedRotations + m_unrecordedTranslations + m_unrecordedLampMoves;
-    size_t nbHeavy = 0; /* rotations and translations: a pass over the primitives each; a lamp move is one assignment */
-    for (const PendingMove &move : pending)
-        nbHeavy += move.kind != PendingMove::LAMP_MOVE;
-    /* lamp moves alone refit nothing, as on the host route: setPrimitiveCenter + compactBoxes(false) leaves every box
-     * as it is, the stale box of another primitive whose centre was set included */
-    const bool refit = m_morphPending || nbHeavy || m_unrecordedRotations || m_unrecordedTranslations;
-    clearJournal();
+    const ResidentScene pending = m_resident.take();
+    const size_t nbHeavy = pending.nbHeavy(), unrecorded = pending.nbUnrecorded();
     Frame &f = m_frames[m_frame];
-    if (m_morphPending)
-    {
-        /* the morph first, always replayed: what the engine hands back (primitivesFromDevice) carries neither sizes
-         * nor the primitives a rotation leaves alone */
-        m_morphPending = false;
-        morphPrimitivesOnly(m_pendingMorphWeight);
-    }
+    /* the morph first, always replayed: what the engine hands back (primitivesFromDevice) carries neither sizes
+     * nor the primitives a rotation leaves alone */
+    if (pending.morphPending)
+        morphPrimitivesOnly(pending.pendingMorphWeight);
     /* a handful of rotations and translations is replayed (4 ms each for 100 k primitives); a long animation is
      * fetched, and so is one whose moves were not all recorded */
     if ((nbHeavy <= 8 && !unrecorded) || !primitivesFromDevice(f))
@@ -1304,28 +1268,26 @@ void GPUKernel::syncHost()
         if (unrecorded)
             std::cerr << "GPUKernel::syncHost: the engine did not hand back its primitives and " << unrecorded
                       << " of the moves it applied were not recorded: the scene store lags behind" << std::endl;
-        for (const PendingMove &move : pending)
+        for (const ResidentScene::Move &move : pending.journal)
             switch (move.kind)
             {
-            case PendingMove::ROTATION:
+            case ResidentScene::Move::ROTATION:
                 rotatePrimitivesOnly(f, move.v, move.cosA, move.sinA);
                 break;
-            case PendingMove::TRANSLATION:
+            case ResidentScene::Move::TRANSLATION:
                 translatePrimitivesOnly(f, move.v);
                 break;
-            case PendingMove::LAMP_MOVE:
+            case ResidentScene::Move::LAMP_MOVE:
                 if (CPUPrimitive *p = f.primitives.lookup(move.index))
                     p->p0 = move.v;
                 break;
             }
     }
-    if (refit)
+    if (pending.refits())
         refitBoxes(f);
     /* the flattened arrays follow.  What they now hold is what the device holds (the same arithmetic
-     * ran there), so neither an upload is due nor has the scene been "touched" by this */
+     * ran there), so neither an upload is due nor has the scene been "touched" by this (Replaying) */
     streamDataToGPU();
-    m_primitivesTransfered = transfered;
-    m_hostTouched = touched;
 }
 
 /* reference: GPUKernel.cpp:1462-1511 */
@@ -1333,18 +1295,13 @@ void GPUKernel::translatePrimitives(const vec3f &t)
 {
     /* as for a rotation: the scene the device holds is the one the host holds (plus what is pending), the engine may
      * push it along in place, and the host copy follows when somebody looks (syncHost) */
-    if (m_primitivesTransfered && !m_hostTouched && deviceTranslatePrimitives(t))
+    if (m_resident.offers(m_frame) && deviceTranslatePrimitives(t))
     {
-        PendingMove move;
-        move.kind = PendingMove::TRANSLATION;
-        move.v = t;
-        move.cosA = move.sinA = make_vec3f();
-        move.index = 0;
-        recordMove(move);
+        m_resident.record({ResidentScene::Move::TRANSLATION, t, make_vec3f(), make_vec3f(), 0});
         return;
     }
     Frame &f = frame();
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     translatePrimitivesOnly(f, t);
     refitBoxes(f);
 }
@@ -1371,7 +1328,7 @@ void GPUKernel::translatePrimitivesOnly(Frame &f, const vec3f &t)
 /* reference: GPUKernel.cpp:1574-1600 (from/to are ignored there too) */
 void GPUKernel::scalePrimitives(float scale, unsigned int, unsigned int)
 {
-    m_primitivesTransfered = false;
+    m_resident.setTransfered(false);
     for (auto &entry : frame().primitives)
     {
         CPUPrimitive &p = entry.second;

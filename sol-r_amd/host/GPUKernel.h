@@ -25,6 +25,7 @@
 #include <map>
 #include <unordered_map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/solr_hip.h"
@@ -275,6 +276,128 @@ inline vec2f make_vec2f(float x = 0.f, float y = 0.f) { vec2f v; v.x = x; v.y = 
 inline vec3f make_vec3f(float x = 0.f, float y = 0.f, float z = 0.f) { vec3f v; v.x = x; v.y = y; v.z = z; return v; }
 inline vec4f make_vec4f(float x = 0.f, float y = 0.f, float z = 0.f, float w = 0.f) { vec4f v; v.x = x; v.y = y; v.z = z; v.w = w; return v; }
 
+/* What the host knows about the scene its engine keeps resident: whether the store and that scene are the same one, and by
+ * what the store lags behind it.  Read everywhere, written through the transitions and the two scoped guards below only -
+ * by convention, as csrc/engine.h Scene is.  A default-constructed record: nothing uploaded. */
+struct ResidentScene
+{
+    /* a move the engine applied to the resident scene and the store has not replayed */
+    struct Move
+    {
+        enum Kind
+        {
+            ROTATION,    /* v: the centre, cosA, sinA */
+            TRANSLATION, /* v: the translation */
+            LAMP_MOVE    /* v: the centre of primitive `index` */
+        } kind;
+        vec3f v, cosA, sinA;
+        unsigned int index;
+    };
+    /* an animation that runs for hours: past this many the moves are only counted - the store then catches up from the
+     * device's primitives, which it does for more than a handful of rotations anyway */
+    static constexpr size_t MAX_RECORDED_MOVES = 100000;
+
+    bool primitivesTransfered = false; /* the reference's m_primitivesTransfered: no upload of the scene is due */
+    bool touched = true;               /* the scene store was accessed since the last upload */
+    long frame = -1;                   /* the frame the resident scene was uploaded from, -1: none */
+    bool lampMoved = false;            /* a lamp was moved over there since the upload (morphFrame) */
+    long morphKeysFrame = -1, morphKeysNbFrames = -1; /* the engine's morph keys are for that frame of that many, -1: it has none */
+    bool buildingLevels = false; /* the lazy build of the level maps reads the store as it is: what is pending stays pending */
+    /* the journal: the moves served over there since the upload - or since the morph that superseded what was before
+     * it -, in order, up to the cap; the rotations among them; per kind those beyond the cap */
+    std::vector<Move> journal;
+    size_t journalRotations = 0;
+    size_t unrecorded[3] = {0, 0, 0}; /* by Move::Kind */
+    bool morphPending = false;
+    float pendingMorphWeight = 0.f;
+
+    /* The one offer rule: a move on frame `f` of the store may be offered to the engine when the scene over there was
+     * uploaded, nothing has accessed the store since, and it was uploaded from that frame (a frame switch without a
+     * flatten leaves the device with another frame than the current one) */
+    bool offers(unsigned int f) const { return primitivesTransfered && !touched && frame == (long)f; }
+    bool hasMorphKeys(unsigned int f, unsigned int n) const { return morphKeysFrame == (long)f && morphKeysNbFrames == (long)n; }
+    size_t nbUnrecorded() const { return unrecorded[0] + unrecorded[1] + unrecorded[2]; }
+    size_t nbPendingMoves() const { return journal.size() + nbUnrecorded(); }
+    size_t nbPendingRotations() const { return journalRotations + unrecorded[Move::ROTATION]; }
+    bool pendingMorph() const { return morphPending; }
+    bool lags() const { return nbPendingMoves() > 0 || morphPending; }
+    /* the recorded rotations and translations: a pass over the primitives each to replay; a lamp move is one assignment */
+    size_t nbHeavy() const
+    {
+        return std::count_if(journal.begin(), journal.end(), [](const Move &m) { return m.kind != Move::LAMP_MOVE; });
+    }
+    /* do the boxes follow what is pending?  Lamp moves alone refit nothing, as on the host route: setPrimitiveCenter +
+     * compactBoxes(false) leaves every box as it is, the stale box of another primitive whose centre was set included */
+    bool refits() const { return morphPending || nbHeavy() || unrecorded[Move::ROTATION] || unrecorded[Move::TRANSLATION]; }
+
+    /* the engine has uploaded the scene from frame `f` (render_begin, when an upload was due): device and host hold the same
+     * scene, the engine's morph keys are gone, the lamps are where the store has them */
+    void uploaded(unsigned int f)
+    {
+        primitivesTransfered = true;
+        touched = false;
+        morphKeysFrame = morphKeysNbFrames = -1;
+        frame = (long)f;
+        lampMoved = false;
+    }
+    void setTransfered(bool value) { primitivesTransfered = value; }
+    /* the scene store was accessed (GPUKernel::frame): the fast path ends until the next upload */
+    void touch() { touched = true; }
+    void morphKeysTaken(unsigned int f, unsigned int n) { morphKeysFrame = (long)f, morphKeysNbFrames = (long)n; }
+    /* the engine has served `move`: into the journal, or past the cap into the counts */
+    void record(const Move &move)
+    {
+        if (move.kind == Move::LAMP_MOVE)
+            lampMoved = true;
+        if (journal.size() >= MAX_RECORDED_MOVES)
+        {
+            ++unrecorded[move.kind];
+            return;
+        }
+        journal.push_back(move);
+        journalRotations += move.kind == Move::ROTATION;
+    }
+    /* the store has been set anew, here (morphFrame's host route): nothing is pending */
+    void clear()
+    {
+        journal.clear();
+        journalRotations = 0;
+        unrecorded[0] = unrecorded[1] = unrecorded[2] = 0;
+        morphPending = false;
+    }
+    /* ... or over there, by a morph at that weight: it supersedes what was pending before it */
+    void morphServed(float weight)
+    {
+        clear();
+        morphPending = true;
+        pendingMorphWeight = weight;
+    }
+    /* syncHost: what is pending is handed over - the record as it was, its journal moved out - and the record is caught up */
+    ResidentScene take()
+    {
+        ResidentScene pending = std::move(*this);
+        clear();
+        return pending;
+    }
+    /* While syncHost() brings the store to what the device holds already: its helpers go through frame(), setPrimitive and
+     * streamDataToGPU like any caller and flip `primitivesTransfered` and `touched`; both are put back when the scope ends */
+    struct Replaying
+    {
+        ResidentScene &scene;
+        const bool primitivesTransfered, touched;
+        explicit Replaying(ResidentScene &s) : scene(s), primitivesTransfered(s.primitivesTransfered), touched(s.touched) {}
+        ~Replaying() { scene.primitivesTransfered = primitivesTransfered, scene.touched = touched; }
+    };
+    /* While buildLevelsOnHost() makes the level maps, which may nest: it reads the store as it is (buildingLevels) */
+    struct BuildingLevels
+    {
+        ResidentScene &scene;
+        const bool nested;
+        explicit BuildingLevels(ResidentScene &s) : scene(s), nested(s.buildingLevels) { s.buildingLevels = true; }
+        ~BuildingLevels() { scene.buildingLevels = nested; }
+    };
+};
+
 class GPUKernel
 {
 public:
@@ -467,7 +590,7 @@ public:
      * syncHost() catches it up.  Returns 0 when done, -1 when the request cannot be served (fewer than three frames, the
      * current frame is a key frame, counts or types differ, a weight that is not finite): nothing changed. */
     int morphFrame(float weight);
-    bool pendingMorph() const { return m_morphPending; }
+    bool pendingMorph() const { return m_resident.pendingMorph(); }
     void resetAddingIndex() { m_addingIndex = 0; }
     void doneWithAdding(const bool &done) { m_doneWithAdding = done; }
     void getPrimitiveOtherCenter(unsigned int index, vec3f &center);
@@ -479,7 +602,7 @@ public:
     int compactBoxes(bool reconstructBoxes);
     void streamDataToGPU();
     void resetBoxes(bool resetPrimitives);
-    void setPrimitivesTransfered(const bool value) { m_primitivesTransfered = value; }
+    void setPrimitivesTransfered(const bool value) { m_resident.setTransfered(value); }
 
     vec3f &getViewPos() { return m_viewPos; }
     vec3f &getViewDir() { return m_viewDir; }
@@ -502,12 +625,12 @@ public:
     /* Animated scenes: rotatePrimitives + compactBoxes(false) per frame (MoleculeScene.cpp:75-81), translatePrimitives
      * behind it (Scene.cpp:1546-1548), a lamp dragged with setPrimitiveCenter (solrViewer.cpp:1058-1069).  An
      * engine that keeps the scene resident may apply such a move there (deviceRotatePrimitives,
-     * deviceTranslatePrimitives, deviceMoveLamp); the host copy then lags behind by the moves listed in m_journal
+     * deviceTranslatePrimitives, deviceMoveLamp); the host copy then lags behind by the moves in the journal of m_resident
      * and is caught up - the same arithmetic, replayed in order - by syncHost() before anything reads or changes it. */
     void syncHost();
-    size_t nbPendingRotations() const { return m_journalRotations + m_unrecordedRotations; }
+    size_t nbPendingRotations() const { return m_resident.nbPendingRotations(); }
     /* ... and the whole journal: rotations, translations and lamp moves */
-    size_t nbPendingMoves() const { return m_journal.size() + m_unrecordedRotations + m_unrecordedTranslations + m_unrecordedLampMoves; }
+    size_t nbPendingMoves() const { return m_resident.nbPendingMoves(); }
     int lightInformationSize() const { return m_lightInformationSize; }
     const Material *hostMaterials() const { return m_hMaterials.data(); }
     const std::vector<RandomBuffer> &hostRandoms();
@@ -533,13 +656,13 @@ protected:
      * the next upload (the caller may be about to change what the device holds) */
     Frame &frame()
     {
-        m_hostTouched = true;
+        m_resident.touch();
         /* a tree that came from the device build left the per-level maps empty: they are made now, from the
          * primitives as they still are, before whoever asks can change one (the cells a primitive sits in are
          * those of the last full build, GPUKernel.cpp:1378-1460 refits them, it does not re-hash) */
         if (!m_frames[m_frame].levelsBuilt)
             buildLevelsOnHost();
-        if (hostLags() && !m_buildingLevels)
+        if (m_resident.lags() && !m_resident.buildingLevels)
             syncHost();
         return m_frames[m_frame];
     }
@@ -603,9 +726,13 @@ protected:
     /* translatePrimitives' loop over the level-0 boxes (no box is updated) */
     void translatePrimitivesOnly(Frame &f, const vec3f &translation);
     void refitBoxes(Frame &f);
-    /* engine hook: blend the resident scene at that weight (the keys handed over first where the engine has none:
-     * morphKeys); false = not done, nothing changed */
-    virtual bool deviceMorphFrame(float) { return false; }
+    /* blend the resident scene at that weight, the keys handed over first where the engine has none for this frame
+     * (morphKeys; which frame its keys are for: m_resident); false = not done, nothing changed */
+    bool deviceMorphFrame(float weight);
+    /* engine hooks: take these keys - the two key frames in the order of the resident primitives -; blend the resident
+     * scene between them at that weight; false = not done, nothing changed */
+    virtual bool deviceSetMorphKeys(const std::vector<Primitive> &, const std::vector<Primitive> &) { return false; }
+    virtual bool deviceMorphPrimitives(float) { return false; }
     /* the current frame against the two key frames: counts, types by rank */
     bool morphKeysMatch();
     /* morphFrame's loop over the store of the current frame (no boxes, no flattening) */
@@ -614,15 +741,8 @@ protected:
      * filled in); false when a primitive of the current frame differs from the first key's in what a morph takes from
      * that key and a resident scene keeps as it is - material, texture coordinates, movable flag */
     bool morphKeys(std::vector<Primitive> &first, std::vector<Primitive> &last);
-    /* the frames the engine's keys were made for (morphKeys), -1: it has none; reset with every upload */
-    long m_morphKeysFrame = -1, m_morphKeysNbFrames = -1;
-    /* the frame the engine's resident scene was uploaded from, -1: none (a frame switch without a flatten leaves the
-     * device with another frame than the current one: that one is not morphed over there) */
-    long m_residentFrame = -1;
-    /* a lamp was moved on the resident scene since its upload: a morph over there would put the lamp back at its keys'
-     * place and leave its light record behind, so morphFrame does not offer it to the engine (which would decline it,
-     * after the keys were handed over for nothing) and the host route serves it */
-    bool m_lampMovedOnDevice = false;
+    /* the engine's resident scene against the store: who serves a move, and what the store owes afterwards */
+    ResidentScene m_resident;
 
     /* box-tree build (GPUKernel.h:318-324) */
     int processBoxes(const int boxSize, bool simulate);
@@ -651,7 +771,6 @@ protected:
     std::vector<BitmapBuffer> m_textureAtlas;
     std::vector<RandomBuffer> m_hRandoms;
     bool m_randomsFilled = false;
-    bool m_buildingLevels = false; /* the lazy build reads the store as it is: pending rotations stay pending */
     bool m_hostBuildOnly = false; /* SolRx_HostBuild(1) / SOLR_HOST_BUILD=1: never ask the engine for the tree */
     std::vector<PrimitiveXYIdBuffer> m_hPrimitivesXYIds;
     std::vector<LightInformation> m_lightInformation;
@@ -674,38 +793,9 @@ protected:
     unsigned int m_nbFrames;
     unsigned int m_treeDepth;
 
-    bool m_primitivesTransfered;
     bool m_materialsTransfered;
     bool m_texturesTransfered;
     bool m_randomsTransfered;
-    bool m_hostTouched = true; /* scene store accessed since the last upload */
-    /* the journal: what the engine applied to the resident scene and the store has not replayed, in order */
-    struct PendingMove
-    {
-        enum Kind
-        {
-            ROTATION,    /* v: the centre, cosA, sinA */
-            TRANSLATION, /* v: the translation */
-            LAMP_MOVE    /* v: the centre of primitive `index` */
-        } kind;
-        vec3f v, cosA, sinA;
-        unsigned int index;
-    };
-    std::vector<PendingMove> m_journal;
-    size_t m_journalRotations = 0; /* the rotations among them */
-    /* an animation that runs for hours: past this many the moves are only counted - the store then
-     * catches up from the device's primitives, which it does for more than a handful of rotations anyway */
-    static constexpr size_t MAX_RECORDED_ROTATIONS = 100000;
-    size_t m_unrecordedRotations = 0, m_unrecordedTranslations = 0, m_unrecordedLampMoves = 0;
-    /* the store lags behind the resident scene */
-    bool hostLags() const { return nbPendingMoves() > 0 || m_morphPending; }
-    /* a move the engine has served goes into the journal, or past MAX_RECORDED_ROTATIONS into the counts */
-    void recordMove(const PendingMove &move);
-    void clearJournal();
-    /* a morph the engine applied to the resident scene and the store has not replayed (it supersedes what was pending
-     * before it; m_journal are the moves since) */
-    bool m_morphPending = false;
-    float m_pendingMorphWeight = 0.f;
 
     SceneInfo m_sceneInfo;
     PostProcessingInfo m_postProcessingInfo;

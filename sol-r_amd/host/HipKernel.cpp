@@ -137,7 +137,7 @@ void HipKernel::render_begin(const float timer)
     }
     if (m_refresh)
     {
-        if (!m_primitivesTransfered)
+        if (!m_resident.primitivesTransfered)
             syncHost(); /* somebody asked for a fresh upload while rotations were pending on the device */
         Frame &f = frameAsIs();
         int nbBoxes = f.nbActiveBoxes;
@@ -145,18 +145,14 @@ void HipKernel::render_begin(const float timer)
         int nbLamps = f.nbActiveLamps;
         int nbMaterials = m_nbActiveMaterials + 1;
 
-        if (!m_primitivesTransfered)
+        if (!m_resident.primitivesTransfered)
         {
             h2d_scene(m_occupancyParameters, m_hBoundingBoxes.data(), nbBoxes, m_hPrimitives.data(), nbPrimitives,
                       m_hLamps.data(), nbLamps);
             mark("render_begin: h2d_scene");
             h2d_lightInformation(m_occupancyParameters, m_lightInformation.data(), m_lightInformationSize);
             solr_hip_set_movable(m_hMovable.data(), (int)m_hMovable.size());
-            m_primitivesTransfered = true;
-            m_hostTouched = false; /* device and host hold the same scene from here on */
-            m_morphKeysFrame = -1; /* (the upload dropped the engine's morph keys) */
-            m_residentFrame = (long)m_frame;
-            m_lampMovedOnDevice = false;
+            m_resident.uploaded(m_frame);
             mark("render_begin: lights, movable flags");
         }
         if (!m_randomsTransfered)
@@ -219,20 +215,14 @@ bool HipKernel::deviceRotatePrimitives(const vec3f &center, const vec3f &cosA, c
     return solr_hip_rotate_primitives(c, co, si, m_sceneInfo.viewDistance) == 1;
 }
 
-bool HipKernel::deviceMorphFrame(float weight)
+bool HipKernel::deviceSetMorphKeys(const std::vector<Primitive> &first, const std::vector<Primitive> &last)
 {
-    if (!m_deviceInitialized)
-        return false;
-    if (m_morphKeysFrame != (long)m_frame || m_morphKeysNbFrames != (long)m_nbFrames)
-    {
-        /* the first morph after an upload: the key frames go to the device, in the order of the resident primitives */
-        std::vector<Primitive> first, last;
-        if (!morphKeys(first, last) || solr_hip_set_morph_keys(first.data(), last.data(), (int)first.size()) != 1)
-            return false;
-        m_morphKeysFrame = (long)m_frame;
-        m_morphKeysNbFrames = (long)m_nbFrames;
-    }
-    return solr_hip_morph_primitives(weight, m_sceneInfo.viewDistance) == 1;
+    return m_deviceInitialized && solr_hip_set_morph_keys(first.data(), last.data(), (int)first.size()) == 1;
+}
+
+bool HipKernel::deviceMorphPrimitives(float weight)
+{
+    return m_deviceInitialized && solr_hip_morph_primitives(weight, m_sceneInfo.viewDistance) == 1;
 }
 
 bool HipKernel::deviceTranslatePrimitives(const vec3f &translation)
@@ -468,7 +458,8 @@ void HipKernel::setGpuCount(int n)
     {
         initializeDevice();
         setFramesInFlight(m_flights);
-        m_primitivesTransfered = m_materialsTransfered = m_texturesTransfered = m_randomsTransfered = false;
+        m_resident.setTransfered(false);
+        m_materialsTransfered = m_texturesTransfered = m_randomsTransfered = false;
         m_refresh = true;
     }
 }
@@ -518,15 +509,11 @@ int HostOnlyKernel::lastError(std::string *message)
 void ReplayKernel::render_begin(const float timer)
 {
     HostOnlyKernel::render_begin(timer);
-    if (!m_primitivesTransfered)
+    if (!m_resident.primitivesTransfered)
     {
         syncHost();
-        m_lampMovedOnDevice = false;
+        m_resident.uploaded(m_frame); /* the upload a real engine does here, when one is due */
     }
-    m_primitivesTransfered = true; /* the upload a real engine does here */
-    m_hostTouched = false;
-    m_morphKeysFrame = -1;
-    m_residentFrame = (long)m_frame;
 }
 
 bool ReplayKernel::deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &)
@@ -551,16 +538,8 @@ bool ReplayKernel::deviceMoveLamp(int, const vec3f &c)
     return true;
 }
 
-bool ReplayKernel::deviceMorphFrame(float)
+bool ReplayKernel::deviceMorphPrimitives(float)
 {
-    if (m_morphKeysFrame != (long)m_frame || m_morphKeysNbFrames != (long)m_nbFrames)
-    {
-        std::vector<Primitive> first, last;
-        if (!morphKeys(first, last))
-            return false;
-        m_morphKeysFrame = (long)m_frame;
-        m_morphKeysNbFrames = (long)m_nbFrames;
-    }
     ++m_claimedMorphs;
     return true;
 }

@@ -59,7 +59,8 @@ protected:
     /* rotatePrimitives on the resident scene, solr_hip_rotate_primitives (include/solr_hip.h) */
     bool deviceRotatePrimitives(const vec3f &center, const vec3f &cosA, const vec3f &sinA) override;
     /* morphFrame on the resident scene, solr_hip_set_morph_keys + solr_hip_morph_primitives (include/solr_hip.h) */
-    bool deviceMorphFrame(float weight) override;
+    bool deviceSetMorphKeys(const std::vector<Primitive> &first, const std::vector<Primitive> &last) override;
+    bool deviceMorphPrimitives(float weight) override;
     /* translatePrimitives and a lamp's setPrimitiveCenter on the resident scene, solr_hip_translate_primitives and
      * solr_hip_move_lamp (include/solr_hip.h) */
     bool deviceTranslatePrimitives(const vec3f &translation) override;
@@ -110,10 +111,11 @@ protected:
     bool m_failed = false;
 };
 
-/* Test double for the animated-scene protocol (GPUKernel::rotatePrimitives / morphFrame / syncHost): a host-only
- * store that claims, like an engine with a resident scene would, to have uploaded the scene at the first
- * frame and to apply every rotation, translation, lamp move and morph "over there" - so that the lazy replay of what is
- * pending can be checked against the eager host route without a GPU.  Renders nothing. */
+/* Test double for the animated-scene protocol (GPUKernel::rotatePrimitives / translatePrimitives / setPrimitiveCenter /
+ * morphFrame / syncHost): a host-only store that claims to upload the scene with a frame when an upload is due - the rule of
+ * HipKernel::render_begin, through the same ResidentScene::uploaded - and to apply every move it is offered "over there".
+ * What is offered (ResidentScene::offers) and the morph keys are the base class's business; the double only counts.  So the
+ * lazy replay of what is pending can be checked against the eager host route without a GPU.  Renders nothing. */
 class ReplayKernel : public HostOnlyKernel
 {
 public:
@@ -125,7 +127,8 @@ public:
 
 protected:
     bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) override;
-    bool deviceMorphFrame(float weight) override;
+    bool deviceSetMorphKeys(const std::vector<Primitive> &, const std::vector<Primitive> &) override { return true; }
+    bool deviceMorphPrimitives(float weight) override;
     bool deviceTranslatePrimitives(const vec3f &) override;
     bool deviceMoveLamp(int slot, const vec3f &center) override;
 

@@ -28,7 +28,7 @@ LAMP_1_THERE = (2500.0, 7000.0, -11000.0)
 LAMP_0_THERE = (-3000.0, 6000.0, -12000.5)
 MIXED = [("rotate", TURNS[0]), ("translate", TRANSLATIONS[0]), ("lamp", (1, LAMP_1_THERE)), ("rotate", TURNS[1]),
          ("lamp", (0, LAMP_0_THERE)), ("translate", TRANSLATIONS[1])]
-MAX_RECORDED_ROTATIONS = 100000      # sol-r_amd/host/GPUKernel.h: past this many the moves are counted, not recorded
+MAX_RECORDED_ROTATIONS = 100000      # GPUKernel.h ResidentScene::MAX_RECORDED_MOVES: past it moves are counted, not recorded
 
 
 def _kernel(solr, name, engine):
@@ -412,6 +412,58 @@ def test_touching_the_scene_store_ends_the_fast_path(solr, oracle):
         frame = copy_frame(gpu_frame(k))
         opp, oids, orgb, _, status = oracle_frame(k, oracle)      # catches the host store up
         assert k.pending_moves() == 0
+        assert_parity(compare_frames(*frame, opp, oids, orgb))
+    finally:
+        k.finalize()
+
+
+@pytest.mark.parametrize("what", ["rotate", "translate"])
+def test_moves_on_a_frame_that_is_not_the_resident_one_take_the_host_route(solr, oracle, what):
+    """tests/test_moves_host.py's test of the same name on the engine itself: after a frame switch the device still holds
+    frame 1, so a rotation or a translation of frame 0 is the host's (one offer rule, GPUKernel.h ResidentScene::offers) and
+    the frame that follows shows frame 0 moved, uploaded anew - not frame 1 moved in place"""
+    hip = solr.hip_lib()
+    k = morph_cases.build(solr.Kernel(engine="hip", deterministic_seed=1), "sticks")
+    move = ("rotate", TURNS[1]) if what == "rotate" else ("translate", TRANSLATIONS[0])
+    try:
+        gpu_frame(k)                                   # uploads frame 1
+        served = _counters(hip)
+        k.set_frame(0)
+        _apply(k, move, None)
+        assert k.pending_moves() == 0, "a move of frame 0 was offered to an engine whose resident scene is frame 1"
+        assert _counters(hip) == served
+        frame = copy_frame(gpu_frame(k))               # uploads frame 0, moved on the host
+        opp, oids, orgb, _, status = oracle_frame(k, oracle)
+        assert status == 0
+        assert_parity(compare_frames(*frame, opp, oids, orgb))
+        # ... after which frame 0 is the resident one, and the next rotation is served over there
+        k.rotate_primitives(*TURNS[2])
+        assert k.pending_moves() == 1 and k.pending_rotations() == 1
+        assert _counters(hip) == (served[0] + 1, served[1], served[2])
+        frame = copy_frame(gpu_frame(k))
+        opp, oids, orgb, _, status = oracle_frame(k, oracle)      # catches the host store up
+        assert status == 0 and k.pending_moves() == 0
+        assert_parity(compare_frames(*frame, opp, oids, orgb))
+    finally:
+        k.finalize()
+
+
+def test_a_touch_without_an_upload_keeps_the_fast_path_closed(solr, oracle):
+    """tests/test_moves_host.py test_the_double_uploads_when_the_engine_would, on the engine the double stands in for: the
+    same calls, the same counts at the same points"""
+    k = _kernel(solr, "two_lamps", "hip")
+    try:
+        gpu_frame(k)
+        k.L.SolR_SetPrimitiveMaterial(3, k.L.SolR_GetPrimitiveMaterial(3))
+        gpu_frame(k)                                   # touched, no upload due: nothing is uploaded
+        k.translate_primitives(TRANSLATIONS[0])
+        assert k.pending_moves() == 0, "the fast path was open again without an upload"
+        gpu_frame(k)                                   # the translation on the host made one due
+        k.translate_primitives(TRANSLATIONS[1])
+        assert k.pending_moves() == 1
+        frame = copy_frame(gpu_frame(k))
+        opp, oids, orgb, _, status = oracle_frame(k, oracle)      # catches the host store up
+        assert status == 0 and k.pending_moves() == 0
         assert_parity(compare_frames(*frame, opp, oids, orgb))
     finally:
         k.finalize()

@@ -232,3 +232,96 @@ def test_a_morph_behind_a_lamp_move_puts_the_lamp_and_its_light_back(solr, weigh
     assert np.array_equal(moved.lights["location"][0, :3], np.asarray(SECOND_CENTRE, np.float32))
     assert np.array_equal(eager.lights["location"][0, :3], np.asarray(at_the_keys, np.float32))
     assert _same(lazy.lights, eager.lights) and _same(lazy.primitives, eager.primitives) and _same(lazy.boxes, eager.boxes)
+
+
+def _move(k, what, lamp):
+    if what == "rotate":
+        k.rotate_primitives(*TURNS[1])
+    elif what == "translate":
+        k.translate_primitives(TRANSLATIONS[0])
+    else:
+        k.set_primitive_center(lamp, SECOND_CENTRE)
+
+
+@pytest.mark.parametrize("order", [("rotate", "translate", "lamp"), ("translate", "lamp", "rotate"), ("lamp", "rotate", "translate")],
+                         ids=lambda order: order[0] + "_first")
+def test_moves_on_a_frame_that_is_not_the_resident_one_take_the_host_route(solr, order):
+    """one offer rule (GPUKernel.h ResidentScene::offers): uploaded, untouched since, and uploaded from the current frame.
+    After a frame switch the engine's resident scene is another frame's, so a rotation, a translation and a lamp's centre
+    are the host's until the next upload.  Only the first move after the switch meets a scene that is still transferred
+    and untouched - the host route it takes ends that for the moves behind it - so each of the three goes first once.
+    Before the rule was one, rotatePrimitives and translatePrimitives left the frame out of it: with either of them first the
+    first assertion below failed with 1 - a move of frame 0 offered to an engine that holds frame 1."""
+    scenes = {}
+    for engine in ("host-replay", "host-only"):
+        k = morph_cases.build(solr.Kernel(engine=engine, deterministic_seed=1), "sticks")
+        try:
+            lamp = move_cases.lamp_indices(k)[0]
+            _frame(k)                                # uploads frame 1
+            k.set_frame(0)
+            for what in order:
+                _move(k, what, lamp)
+                assert k.pending_moves() == 0, "a %s of frame 0 was offered to an engine whose resident scene is frame 1" % what
+            assert k.pending_rotations() == 0 and move_cases.lamp_indices(k)[0] == lamp
+            switched = k.flat_scene()
+            _frame(k)                                # uploads frame 0: resident again
+            for what in order:
+                _move(k, what, lamp)
+            assert k.pending_moves() == (3 if engine == "host-replay" else 0)
+            assert k.pending_rotations() == (1 if engine == "host-replay" else 0)
+            scenes[engine] = (switched, k.flat_scene())
+            assert k.pending_moves() == 0
+        finally:
+            k.finalize()
+    for lazy, eager in zip(scenes["host-replay"], scenes["host-only"]):
+        assert _same_scene(lazy, eager), (_differing(lazy.boxes, eager.boxes), _differing(lazy.primitives, eager.primitives),
+                                          _differing(lazy.lights, eager.lights))
+
+
+def test_the_double_uploads_when_the_engine_would(solr):
+    """HipKernel::render_begin uploads the scene - and opens the fast path again - only when an upload is due; a touch that
+    leaves the scene transferred (SolR_SetPrimitiveMaterial) keeps it closed over the frames that follow, until a change of
+    the store makes an upload due.  The double follows the same rule through the same transition"""
+    scenes = {}
+    for engine in ("host-replay", "host-only"):
+        k = _kernel(solr, "two_lamps", engine=engine)
+        try:
+            replay = engine == "host-replay"
+            _frame(k)
+            k.L.SolR_SetPrimitiveMaterial(3, k.L.SolR_GetPrimitiveMaterial(3))
+            _frame(k)                                # touched, no upload due: nothing is uploaded
+            k.translate_primitives(TRANSLATIONS[0])
+            assert k.pending_moves() == 0, "the fast path was open again without an upload"
+            _frame(k)                                # the translation on the host made one due
+            k.translate_primitives(TRANSLATIONS[1])
+            assert k.pending_moves() == (1 if replay else 0)
+            scenes[engine] = k.flat_scene()
+            assert k.pending_moves() == 0
+        finally:
+            k.finalize()
+    lazy, eager = scenes["host-replay"], scenes["host-only"]
+    assert _same_scene(lazy, eager), (_differing(lazy.boxes, eager.boxes), _differing(lazy.primitives, eager.primitives))
+
+
+def test_the_journal_has_a_cap_and_counts_by_kind_beyond_it(solr, capfd):
+    """past ResidentScene::MAX_RECORDED_MOVES (100 000) entries a move is counted by kind and not recorded.  An engine that
+    hands back its primitives makes up for that; the double does not, and the store says that it lags - so the store after
+    this is compared to nothing: only the counts and that line are held"""
+    k = _kernel(solr, "two_lamps", engine="host-replay")
+    try:
+        lamps = move_cases.lamp_indices(k)
+        _frame(k)
+        k.rotate_primitives(*TURNS[0])
+        set_center = k.L.SolRx_SetPrimitiveCenter
+        for n in range(100000):
+            set_center(lamps[n & 1], 100.0, 9000.0, -7000.0 + (n & 7))
+        k.translate_primitives(TRANSLATIONS[0])
+        k.rotate_primitives(*TURNS[1])
+        assert k.pending_moves() == 100003
+        assert k.pending_rotations() == 2
+        capfd.readouterr()
+        k.flat_scene()
+        assert k.pending_moves() == 0 and k.pending_rotations() == 0
+        assert " 3 of the moves it applied were not recorded" in capfd.readouterr().err
+    finally:
+        k.finalize()
