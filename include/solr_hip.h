@@ -254,11 +254,18 @@ void solr_hip_set_depth_halo(const float *above, int nbAbove, const float *below
  *   order        out: nbPrimitives ints: order[k] = index of the primitive streamed k-th; the first *nbLamps
  *                are the lamps (the host fills its Primitive records, lamp and light lists from it)
  * Returns the tree depth (>= 1); -2 when the scene is one of the few cases left to the host builder (no
- * emissive primitive, key collisions with the lamp box, more than NB_MAX_BOXES nodes: solr_tree.hip lists
- * them); -1 on an error, text in solr_hip_build_tree_message(). */
+ * emissive primitive, key collisions with the lamp box, more nodes than NB_MAX_BOXES or boxCapacity, one or
+ * two primitives, a cell number outside int: solr_tree.hip lists them); -1 on an error (nbPrimitives <= 0 and
+ * null pointers among them), text in solr_hip_build_tree_message(). */
 int solr_hip_build_tree(const Primitive *primitives, const unsigned char *emissive, int nbPrimitives,
                         const float minPos[3], const float maxPos[3], float viewDistance, BoundingBox *boxes,
                         int boxCapacity, int *order, int *nbBoxes, int *nbLamps);
+/* The same for a kernel that has built before: depthBefore is the depth of its last tree.  The reference resets - and so
+ * creates - box 0 of that level before it builds (GPUKernel.cpp:1049); where the new tree is deeper, that empty box is
+ * hashed into the level above by its centre (0, 0, 0).  solr_hip_build_tree is this with the constructor's depth, 2. */
+int solr_hip_build_tree_after(const Primitive *primitives, const unsigned char *emissive, int nbPrimitives,
+                              const float minPos[3], const float maxPos[3], float viewDistance, int depthBefore,
+                              BoundingBox *boxes, int boxCapacity, int *order, int *nbBoxes, int *nbLamps);
 const char *solr_hip_build_tree_message(void);
 
 /* The pixel stage of the JPEG texture loader on the device (sol-r_amd/csrc/solr_textures.hip; the arithmetic is

@@ -15,13 +15,21 @@
  * keys, the maps' order reproduced by stable radix sorts of (key, position below), box bounds by the same
  * comparisons in the same order (one thread per box walks its members: the sign of a zero and the first of two
  * equal values are decided by that order), the depth-first positions by subtree sizes summed bottom-up and
- * offsets handed down.  tests/test_tree_build_gpu.py holds it to the host builder node for node.
+ * offsets handed down; and the one box the reference leaves in the levels before it builds (:1049 resets box 0 of the level
+ * that was the top one before - level 2 on a fresh kernel - and operator[] creates it): empty, centre 0, hashed into the
+ * level above where the new tree is deeper (k_resetBox).  tests/test_tree_build_gpu.py holds it to the host builder node
+ * for node, word for word, on the scenes of tests/tree_builder_cases.py too: one for each of these places.
  *
  * Declined (return -2, the caller builds on the host): no emissive primitive (the reference then treats the
  * first ordinary top-level box as the lamp box and streams its child KEYS as primitive indices), a top-level
  * child hashing to key 0 (the lamp box's), a lamp's index equal to a key of the level below the top (the
  * reference recurses into the lamp box as if it held child keys, GPUKernel.cpp:1252: that subtree is then
- * emitted twice), more boxes than NB_MAX_BOXES.
+ * emitted twice), more boxes than NB_MAX_BOXES or than the caller has room for, one or two primitives (the reference
+ * works out the depth twice, GPUKernel.cpp:1056-1062 with `while` - 0 for them - and :1068-1075 with `do ... while` - 1:
+ * the lamps land in box 0 of LEVEL 0 and the top level has no lamp box), a cell number that int does not hold or a
+ * NaN, at any level (primitives moved far out of the extent setPrimitive grew: the reference's static_cast<int> is
+ * undefined there, the host's compiled code yields 0x80000000 and this device's conversion saturates).
+ * tests/tree_builder_cases.py has a scene for each, tests/test_builder_reference_model.py declines() the list again.
  */
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -130,32 +138,43 @@ struct Level
 __device__ inline float minStd(float a, float b) { return (b < a) ? b : a; }
 __device__ inline float maxStd(float a, float b) { return (a < b) ? b : a; }
 
+/* static_cast<int> of a cell number; one that int does not hold (or a NaN) is reported: the build is declined */
+__device__ inline int cellNumber(float q, int *__restrict__ outsideInt)
+{
+    if (!(q >= -2147483648.f && q < 2147483648.f))
+    {
+        atomicExch(outsideInt, 1);
+        return 0;
+    }
+    return (int)q;
+}
+
 /* GPUKernel.cpp:938-941 */
 __global__ void k_level0Keys(const Primitive *__restrict__ prims, int n, f3 minPos, f3 steps, unsigned *__restrict__ key,
-                             int *__restrict__ id)
+                             int *__restrict__ id, int *__restrict__ outsideInt)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
     const vec3f c = prims[i].p0;
-    const unsigned X = (unsigned)(int)((c.x - minPos.x) / steps.x);
-    const unsigned Y = (unsigned)(int)((c.y - minPos.y) / steps.y);
-    const unsigned Z = (unsigned)(int)((c.z - minPos.z) / steps.z);
+    const unsigned X = (unsigned)cellNumber((c.x - minPos.x) / steps.x, outsideInt);
+    const unsigned Y = (unsigned)cellNumber((c.y - minPos.y) / steps.y, outsideInt);
+    const unsigned Z = (unsigned)cellNumber((c.z - minPos.z) / steps.z, outsideInt);
     key[i] = 1u + 1000u * (X * AABB_MAGIC_NUMBER * AABB_MAGIC_NUMBER + Y * AABB_MAGIC_NUMBER + Z);
     id[i] = i;
 }
 
 /* GPUKernel.cpp:1011-1017; the key is held as unsigned by the map */
 __global__ void k_outerKeys(const f3 *__restrict__ centre, int n, f3 minPos, f3 steps, int boxSize, unsigned *__restrict__ key,
-                            int *__restrict__ id)
+                            int *__restrict__ id, int *__restrict__ outsideInt)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
     const f3 c = centre[i];
-    const int X = (int)((c.x - minPos.x) / steps.x);
-    const int Y = (int)((c.y - minPos.y) / steps.y);
-    const int Z = (int)((c.z - minPos.z) / steps.z);
+    const int X = cellNumber((c.x - minPos.x) / steps.x, outsideInt);
+    const int Y = cellNumber((c.y - minPos.y) / steps.y, outsideInt);
+    const int Z = cellNumber((c.z - minPos.z) / steps.z, outsideInt);
     const unsigned u = (unsigned)X * (unsigned)boxSize * (unsigned)boxSize + (unsigned)Y * (unsigned)boxSize + (unsigned)Z;
     key[i] = u + 1u;
     id[i] = i;
@@ -265,6 +284,22 @@ __global__ void k_outerBounds(const int *__restrict__ first, const int *__restri
     centre[b] = f3{(mn.x + mx.x) / 2.f, (mn.y + mx.y) / 2.f, (mn.z + mx.z) / 2.f};
     nodes[b] = n;
     prims[b] = p;
+}
+
+/* the box the reference resets before it builds (GPUKernel.cpp:1049: resetBox of box 0 of the level that was the top one
+ * before, which operator[] creates): no children, bounds at the inside-out seed, centre 0.  It stands behind the boxes
+ * of its level, is hashed into the level above with them and emits nothing */
+__global__ void k_resetBox(f3 *__restrict__ lo, f3 *__restrict__ hi, f3 *__restrict__ centre, int *__restrict__ nodes,
+                           int *__restrict__ prims, float vd)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+    {
+        *lo = f3{vd, vd, vd};
+        *hi = f3{-vd, -vd, -vd};
+        *centre = f3{0.f, 0.f, 0.f};
+        *nodes = 0;
+        *prims = 0;
+    }
 }
 
 __global__ void k_leafSizes(const int *__restrict__ count, int nbBoxes, int *__restrict__ nodes, int *__restrict__ prims)
@@ -451,6 +486,15 @@ extern "C" int solr_hip_build_tree(const Primitive *primitives, const unsigned c
                                    const float minPos[3], const float maxPos[3], float viewDistance, BoundingBox *boxes,
                                    int boxCapacity, int *order, int *nbBoxesOut, int *nbLampsOut)
 {
+    /* a fresh kernel: the constructor's depth (GPUKernel.cpp:198) */
+    return solr_hip_build_tree_after(primitives, emissive, nbPrimitives, minPos, maxPos, viewDistance, 2, boxes, boxCapacity, order,
+                                     nbBoxesOut, nbLampsOut);
+}
+
+extern "C" int solr_hip_build_tree_after(const Primitive *primitives, const unsigned char *emissive, int nbPrimitives,
+                                         const float minPos[3], const float maxPos[3], float viewDistance, int depthBefore,
+                                         BoundingBox *boxes, int boxCapacity, int *order, int *nbBoxesOut, int *nbLampsOut)
+{
     message[0] = 0;
     solrTuneHostAllocator();
     if (!primitives || !emissive || nbPrimitives <= 0 || !minPos || !maxPos || !boxes || !order || !nbBoxesOut || !nbLampsOut)
@@ -459,6 +503,10 @@ extern "C" int solr_hip_build_tree(const Primitive *primitives, const unsigned c
         return -1;
     }
     const int n = nbPrimitives;
+    *nbLampsOut = 0;
+    *nbBoxesOut = 0;
+    if (n <= 2)
+        return -2; /* declined: the reference's two depths differ */
     hipStream_t stream = nullptr;
     /* on the engine's device, whichever thread calls (one process per GPU: a tree built on the calling thread's
      * current device - GPU 0 in a fresh thread - would put every rank's build, and a context, there); the caller's
@@ -519,7 +567,7 @@ extern "C" int solr_hip_build_tree(const Primitive *primitives, const unsigned c
         Sorter sorter;
         std::vector<Level> level(depth + 1);
         if (!dPrims.reserve(n) || !dEmissive.reserve(n) || !key.reserve(n) || !id.reserve(n) || !lampFlag.reserve(n) ||
-            !lampScan.reserve(n) || !dOrder.reserve(n) || !found.reserve(1))
+            !lampScan.reserve(n) || !dOrder.reserve(n) || !found.reserve(2))
         {
             snprintf(message, sizeof(message), "solr_hip_build_tree: out of device memory");
             return false;
@@ -544,8 +592,10 @@ extern "C" int solr_hip_build_tree(const Primitive *primitives, const unsigned c
                            dOrder.ptr);
 
         /* level 0 */
+        int *const aliasFound = found.ptr, *const outsideInt = found.ptr + 1;
+        TREE_CHECK(hipMemsetAsync(found.ptr, 0, 2 * sizeof(int), stream));
         hipLaunchKernelGGL(k_level0Keys, blocks(n), dim3(256), 0, stream, (const Primitive *)dPrims.ptr, n, mn,
-                           stepsFor((int)AABB_MAGIC_NUMBER), key.ptr, id.ptr);
+                           stepsFor((int)AABB_MAGIC_NUMBER), key.ptr, id.ptr, outsideInt);
         {
             Level &L = level[0];
             const int nb = sorter.run(key, id, n, stream);
@@ -572,18 +622,32 @@ extern "C" int solr_hip_build_tree(const Primitive *primitives, const unsigned c
         for (int d = 1; d <= depth; ++d)
         {
             Level &B = level[d - 1], &L = level[d];
-            const int m = B.nbBoxes;
+            int m = B.nbBoxes;
+            if (d - 1 == depthBefore && d - 1 >= 1)
+            {
+                /* unless a box of the level hashed to key 0 itself (the keys are sorted): the reference resets that one */
+                unsigned lowestKey = 0;
+                TREE_CHECK(hipMemcpyAsync(&lowestKey, B.key.ptr, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+                TREE_CHECK(hipStreamSynchronize(stream));
+                if (lowestKey != 0u)
+                {
+                    /* (every array of an outer level has room for one box more) */
+                    hipLaunchKernelGGL(k_resetBox, dim3(1), dim3(64), 0, stream, B.lo.ptr + m, B.hi.ptr + m, B.centre.ptr + m,
+                                       B.nodes.ptr + m, B.prims.ptr + m, viewDistance);
+                    ++m;
+                }
+            }
             if (!key.reserve(m) || !id.reserve(m))
                 return false;
             hipLaunchKernelGGL(k_outerKeys, blocks(m), dim3(256), 0, stream, (const f3 *)B.centre.ptr, m, mn, stepsFor(gridSize[d]),
-                               gridSize[d], key.ptr, id.ptr);
+                               gridSize[d], key.ptr, id.ptr, outsideInt);
             const int nb = sorter.run(key, id, m, stream);
             if (nb <= 0)
                 return false;
             L.nbBoxes = nb;
-            if (!L.key.reserve(nb) || !L.first.reserve(nb + 1) || !L.member.reserve(m) || !L.lo.reserve(nb) || !L.hi.reserve(nb) ||
-                !L.centre.reserve(nb) || !L.nodes.reserve(nb) || !L.prims.reserve(nb) || !L.position.reserve(nb) ||
-                !L.primStart.reserve(nb))
+            if (!L.key.reserve(nb) || !L.first.reserve(nb + 1) || !L.member.reserve(m) || !L.lo.reserve(nb + 1) ||
+                !L.hi.reserve(nb + 1) || !L.centre.reserve(nb + 1) || !L.nodes.reserve(nb + 1) || !L.prims.reserve(nb + 1) ||
+                !L.position.reserve(nb + 1) || !L.primStart.reserve(nb + 1))
                 return false;
             hipLaunchKernelGGL(k_segments, blocks(m), dim3(256), 0, stream, (const unsigned *)sorter.keyOut.ptr,
                                (const int *)sorter.head.ptr, (const int *)sorter.rank.ptr, m, L.key.ptr, L.first.ptr, nb);
@@ -597,13 +661,12 @@ extern "C" int solr_hip_build_tree(const Primitive *primitives, const unsigned c
         Level &T = level[depth];
         unsigned firstKey = 1;
         TREE_CHECK(hipMemcpyAsync(&firstKey, T.key.ptr, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        TREE_CHECK(hipMemsetAsync(found.ptr, 0, sizeof(int), stream));
         hipLaunchKernelGGL(k_lampAliases, blocks(nbLamps), dim3(256), 0, stream, (const int *)dOrder.ptr, nbLamps,
-                           (const unsigned *)level[depth - 1].key.ptr, level[depth - 1].nbBoxes, found.ptr);
-        int aliased = 0;
-        TREE_CHECK(hipMemcpyAsync(&aliased, found.ptr, sizeof(int), hipMemcpyDeviceToHost, stream));
+                           (const unsigned *)level[depth - 1].key.ptr, level[depth - 1].nbBoxes, aliasFound);
+        int declined[2] = {0, 0}; /* a lamp aliased, a cell number outside int */
+        TREE_CHECK(hipMemcpyAsync(declined, found.ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
         TREE_CHECK(hipStreamSynchronize(stream));
-        if (firstKey == 0u || aliased)
+        if (firstKey == 0u || declined[0] || declined[1])
         {
             *nbLampsOut = -1; /* declined */
             return true;
@@ -659,8 +722,6 @@ extern "C" int solr_hip_build_tree(const Primitive *primitives, const unsigned c
         boxes[0].indexForNextBox.x = 1;
         return true;
     };
-    *nbLampsOut = 0;
-    *nbBoxesOut = 0;
     /* the primitive records, five arrays per primitive, eleven per box of a level (the levels shrink by four or so
      * each), the sorter's: what a first build asks for; later ones know (device_pool.h) */
     SolrScratchPool &pool = solrScratchPool();

@@ -615,6 +615,7 @@ int GPUKernel::compactBoxes(bool reconstructBoxes)
     m_resident.setTransfered(false);
     if (reconstructBoxes)
     {
+        m_depthBeforeBuild = m_treeDepth;
         /* the engine builds the same tree on the device (0.2 s of maps and hashing for 100 k primitives on the
          * host, 1.4-1.6 s in the reference; a few milliseconds there): the flattened arrays come back, the
          * per-level maps are left for whoever needs them (ensureLevels) */
@@ -640,6 +641,11 @@ void GPUKernel::buildLevelsOnHost()
      * every primitive into its cell twice.  Rebuild from empty levels. */
     for (int level = 0; level < BOUNDING_BOXES_TREE_DEPTH; ++level)
         f.boundingBoxes[level].clear();
+    /* ... and from the one box that statement leaves in them: box 0 of the level that was the top one before - on a
+     * fresh kernel level 2, the constructor's depth.  Where the tree grows beyond that level the box is hashed into the
+     * level above like any other, by its centre (0, 0, 0), and an empty cell of that level becomes a node */
+    if (m_depthBeforeBuild < (unsigned int)BOUNDING_BOXES_TREE_DEPTH)
+        resetBox(f.boundingBoxes[m_depthBeforeBuild][0], true);
     const int gridGranularity = 2;
     const int gridDivider = 4;
 
@@ -737,7 +743,8 @@ bool GPUKernel::buildTreeOnDevice()
     std::vector<int> order;
     int nbLamps = 0;
     phase.mark("compactBoxes: primitive records");
-    const int depth = deviceBuildTree(prims, emissive, f.minPos, f.maxPos, m_sceneInfo.viewDistance, boxes, order, nbLamps);
+    const int depth = deviceBuildTree(prims, emissive, f.minPos, f.maxPos, m_sceneInfo.viewDistance, (int)m_depthBeforeBuild, boxes,
+                                      order, nbLamps);
     phase.mark("compactBoxes: device build");
     if (depth < 1 || (int)order.size() != n || boxes.empty() || boxes.size() >= (size_t)NB_MAX_BOXES)
         return false;

@@ -690,7 +690,8 @@ protected:
      * frame's primitives in index order.  Returns the tree depth, or a negative value when the engine has no
      * such thing or leaves this scene to the host builder */
     virtual int deviceBuildTree(const std::vector<Primitive> &, const std::vector<unsigned char> &, const vec3f &,
-                                const vec3f &, float, std::vector<BoundingBox> &, std::vector<int> &, int &)
+                                const vec3f &, float, int /* depthBefore */, std::vector<BoundingBox> &, std::vector<int> &,
+                                int &)
     {
         return -2;
     }
@@ -792,6 +793,9 @@ protected:
     unsigned int m_frame;
     unsigned int m_nbFrames;
     unsigned int m_treeDepth;
+    /* m_treeDepth as the last compactBoxes(true) found it (the constructor's 2, or the depth of the build before): the
+     * level whose box 0 the reference resets - and so creates - before it builds (GPUKernel.cpp:1049) */
+    unsigned int m_depthBeforeBuild = 2;
 
     bool m_materialsTransfered;
     bool m_texturesTransfered;

@@ -302,7 +302,7 @@ int HipKernel::isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIso
 }
 
 int HipKernel::deviceBuildTree(const std::vector<Primitive> &primitives, const std::vector<unsigned char> &emissive,
-                               const vec3f &minPos, const vec3f &maxPos, float viewDistance,
+                               const vec3f &minPos, const vec3f &maxPos, float viewDistance, int depthBefore,
                                std::vector<BoundingBox> &boxes, std::vector<int> &order, int &nbLamps)
 {
     if (solr_hip_device_count() < 1)
@@ -316,8 +316,8 @@ int HipKernel::deviceBuildTree(const std::vector<Primitive> &primitives, const s
     order.resize((size_t)n);
     const float mn[3] = {minPos.x, minPos.y, minPos.z}, mx[3] = {maxPos.x, maxPos.y, maxPos.z};
     int nbBoxes = 0;
-    const int depth = solr_hip_build_tree(primitives.data(), emissive.data(), n, mn, mx, viewDistance, raw.get(), (int)capacity,
-                                          order.data(), &nbBoxes, &nbLamps);
+    const int depth = solr_hip_build_tree_after(primitives.data(), emissive.data(), n, mn, mx, viewDistance, depthBefore, raw.get(),
+                                                (int)capacity, order.data(), &nbBoxes, &nbLamps);
     if (depth < 1)
     {
         boxes.clear();

@@ -69,8 +69,8 @@ protected:
     void fetchBitmap() override;
     bool primitivesFromDevice(Frame &f) override;
     int deviceBuildTree(const std::vector<Primitive> &primitives, const std::vector<unsigned char> &emissive,
-                        const vec3f &minPos, const vec3f &maxPos, float viewDistance, std::vector<BoundingBox> &boxes,
-                        std::vector<int> &order, int &nbLamps) override;
+                        const vec3f &minPos, const vec3f &maxPos, float viewDistance, int depthBefore,
+                        std::vector<BoundingBox> &boxes, std::vector<int> &order, int &nbLamps) override;
     /* solr_hip_jpeg_to_rgb (include/solr_hip.h) where there is a device, the base class's loop where there is none */
     bool jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb) override;
     /* solr_hip_rgb_to_jpeg_blocks (include/solr_hip.h) where there is a device, the base class's loop where there is none */

@@ -19,7 +19,12 @@ primitive order, the lamps and the light list.  What the model spells out, becau
     list emitted as primitives, then recursed into AS IF it held child keys (:1169-1252);
   * the scene extent a fresh kernel starts from is whatever its allocation holds - the members are only set by
     cleanup() (:394-399) - zeros in the mirror, so the grid spans the primitives and the origin;
-  * boxes without entries are not emitted; skip pointer = size of the subtree (:1096, 1143).
+  * boxes without entries are not emitted; skip pointer = size of the subtree (:1096, 1143);
+  * before it builds, the reference resets box 0 of the level that was the top one so far (:1049) - level 2 on a fresh
+    kernel (:198) - and operator[] creates that box: a deeper tree hashes it, empty, into the level above by its centre 0;
+  * static_cast<int> of a cell number that int does not hold is undefined in the reference: cast_int() says what the
+    model takes, and declines() which scenes the DEVICE builder (sol-r_amd/csrc/solr_tree.hip) leaves to the host.
+tests/tree_builder_cases.py has scenes that steer each of these; tests/test_tree_builder_cases.py runs them.
 The first scene below is small enough to follow by hand; its expected tree is also written out literally.
 """
 import numpy as np
@@ -39,8 +44,21 @@ def u32(v):
     return int(v) & 0xFFFFFFFF
 
 
+INT_INDEFINITE = -(1 << 31)      # 0x80000000
+
+
+def fits_int(f):
+    """can an int hold the truncated value?  (False for a NaN too)"""
+    f = np.float64(f)
+    return bool(-2147483649.0 < f < 2147483648.0)
+
+
 def cast_int(f):
-    """static_cast<int>(float): truncation toward zero"""
+    """static_cast<int>(float): truncation toward zero.  For a value outside int, or a NaN, the reference leaves the
+    result undefined; the model yields what the host builder's compiled code does on x86-64 (cvttss2si's "integer
+    indefinite"), 0x80000000 - another machine's conversion saturates to 0x7FFFFFFF, or gives 0 for a NaN"""
+    if not fits_int(f):
+        return INT_INDEFINITE
     return int(np.trunc(np.float64(f)))
 
 
@@ -55,7 +73,7 @@ class Box:
 class ReferenceBuilder:
     """GPUKernel::compactBoxes(true) + streamDataToGPU of a fresh kernel, statement by statement"""
 
-    def __init__(self, solr, view_distance, primitives, emissive):
+    def __init__(self, solr, view_distance, primitives, emissive, extent=None):
         self.solr = solr
         self.vd = F(view_distance)
         self.prims = primitives            # index -> dict(type, p0, p1, p2, size, material)
@@ -70,8 +88,16 @@ class ReferenceBuilder:
             for a in range(3):
                 self.min[a] = min(F(p["p0"][a]), self.min[a])
                 self.max[a] = max(F(p["p0"][a]), self.max[a])
+        if extent is not None:
+            # the primitives were moved after they were set (translatePrimitives, :1462-1511): the extent is still the
+            # one setPrimitive grew from where they were then
+            self.min, self.max = [F(v) for v in extent[0]], [F(v) for v in extent[1]]
         self.levels = {}                   # depth -> {key: Box}
         self.wrapped = False
+        self.outside_int = False           # a quotient no int holds (or a NaN) went through cast_int
+        self.negative_cells = set()        # axes on which a cell number came out negative
+        self.hashed = {}                   # depth -> the keys its primitives or the boxes of the level below hashed to
+        self.cells = {}                    # depth -> {primitive or key of the level below: its cell (X, Y, Z)}
 
     def level(self, d):
         return self.levels.setdefault(d, {})
@@ -81,7 +107,12 @@ class ReferenceBuilder:
         return [F(1) if v == 0 else v for v in s]                               # :924-926
 
     def cell(self, point, s):
-        return [cast_int((F(point[a]) - self.min[a]) / s[a]) for a in range(3)]   # :938-940, :1011-1013
+        with np.errstate(all="ignore"):
+            q = [(F(point[a]) - self.min[a]) / s[a] for a in range(3)]            # :938-940, :1011-1013
+        self.outside_int = self.outside_int or not all(fits_int(v) for v in q)
+        out = [cast_int(v) for v in q]
+        self.negative_cells.update(a for a in range(3) if out[a] < 0)
+        return out
 
     def update_bounding_box(self, box):                                          # :741-839
         solr = self.solr
@@ -121,9 +152,11 @@ class ReferenceBuilder:
                     box.hi[a] = child.hi[a]
         box.center = [(box.lo[a] + box.hi[a]) / F(2) for a in range(3)]
 
-    def compact_boxes(self):
+    def compact_boxes(self, depth_before=2):
+        """depth_before: m_treeDepth as the build finds it - :198, the constructor's value, or the depth of the tree the
+        kernel built before (the host builder starts every build from empty levels, GPUKernel.cpp buildLevelsOnHost)"""
         n = len(self.prims)
-        tree_depth = 2                                                           # :198, the constructor's value
+        tree_depth = depth_before
         self.level(tree_depth).setdefault(0, Box(self.vd))                      # :1049 resetBox(levels[depth][0])
         tree_depth, nb = 0, n                                                    # :1056-1062
         while nb > 2:
@@ -133,8 +166,10 @@ class ReferenceBuilder:
         s = self.steps(AABB_MAGIC_NUMBER)
         for p in sorted(self.prims):                                             # the std::map of primitives, by index
             prim = self.prims[p]
-            X, Y, Z = (u32(v) for v in self.cell(prim["p0"], s))                 # unsigned int X = static_cast<int>(...)
+            self.cells.setdefault(0, {})[p] = self.cell(prim["p0"], s)
+            X, Y, Z = (u32(v) for v in self.cells[0][p])                         # unsigned int X = static_cast<int>(...)
             B = u32(1 + 1000 * u32(u32(X * AABB_MAGIC_NUMBER) * AABB_MAGIC_NUMBER + Y * AABB_MAGIC_NUMBER + Z))
+            self.hashed.setdefault(0, set()).add(B)
             if B not in self.level(0):
                 self.level(0)[B] = Box(self.vd)                                  # :947-960
             if self.emissive[prim["material"]]:
@@ -157,11 +192,12 @@ class ReferenceBuilder:
         s = self.steps(box_size)
         below = self.level(depth - 1)
         for key in sorted(below):
-            X, Y, Z = self.cell(below[key].center, s)
+            X, Y, Z = self.cells.setdefault(depth, {})[key] = self.cell(below[key].center, s)
             B = i32(i32(i32(X * box_size) * box_size) + i32(Y * box_size) + Z)   # int arithmetic: it wraps
             B = i32(B + 1)
             self.wrapped = self.wrapped or B < 0
             B = u32(B)                                                           # std::map<unsigned int, ...>
+            self.hashed.setdefault(depth, set()).add(B)
             box = self.level(depth).setdefault(B, Box(self.vd))
             box.lo, box.hi = [self.vd] * 3, [-self.vd] * 3
             box.entries.append(key)
@@ -256,27 +292,118 @@ SCENES = {
 }
 
 
-def _build_both(solr, spec, view_distance=50000.0):
+NB_MAX_BOXES = 2500000           # include/solr_types.h
+
+
+def declines(model, capacity=None):
+    """Is the scene one that sol-r_amd/csrc/solr_tree.hip leaves to the host builder?  The conditions of its header,
+    literally; a list of the ones that hold (empty: the device builds).  To be asked BEFORE stream(): stream() and
+    recurse() insert the boxes they miss, as operator[] does, and every lamp index is a key afterwards."""
+    assert not hasattr(model, "nodes"), "declines() after stream(): the levels hold the boxes stream() inserted"
+    lamps = [p for p in sorted(model.prims) if model.emissive[model.prims[p]["material"]]]
+    top = model.tree_depth
+    why = []
+    if not lamps:
+        why.append("no emissive primitive")
+    if 0 in model.hashed.get(top, ()):
+        why.append("a top-level child hashes to key 0")
+    # (the keys that were hashed to: updateOutterBoundingBox has by now looked the lamps up in the level below as if they
+    # were child keys, and operator[] has inserted an empty box for each)
+    below = model.hashed.get(top - 1, ())
+    if any(p in below for p in lamps):
+        why.append("a lamp's index is a key of the level below the top")
+
+    def nodes(depth, key):                 # what recursiveDataStreamToGPU emits for a box, without inserting it
+        box = model.levels.get(depth, {}).get(key)
+        if box is None or not box.entries:
+            return 0
+        return 1 if depth == 0 else 1 + sum(nodes(depth - 1, k) for k in box.entries)
+    count = 1 + sum(1 + sum(nodes(top - 1, k) for k in box.entries)
+                    for key, box in model.levels.get(top, {}).items() if key != 0)
+    if count >= NB_MAX_BOXES or (capacity is not None and count > capacity):
+        why.append("more boxes than the caller has room for")
+    if len(model.prims) <= 2:
+        why.append("one or two primitives")
+    if model.outside_int:
+        why.append("a cell number no int holds")
+    return why
+
+
+def records_of(solr, spec, plain, glow, move=None, movable=None):
+    """What GPUKernel::setPrimitive stores of a case (:539-684: a sphere's radius on every axis, a cylinder's too and
+    its centre in p2), and translatePrimitives makes of it (:1462-1511: the primitives of the level-0 cells, so no lamp,
+    and no camera) - for the scenes whose flattened arrays no longer hold every primitive"""
+    prims = {}
+    for i, (t, p0, p1, p2, size, lamp) in enumerate(spec):
+        p0, p1, p2 = (np.array(v or (0, 0, 0), F) for v in (p0, p1, p2))
+        size = np.array(size, F)
+        if t in (solr.ptSphere, solr.ptCylinder, solr.ptCone):
+            size = np.array([size[0]] * 3, F)
+        if t in (solr.ptCylinder, solr.ptCone):
+            p2 = (p0 + p1) / F(2)
+        if move is not None and not lamp and t != solr.ptCamera and (movable is None or movable[i]):
+            p0, p1, p2 = (v + np.array(move, F) for v in (p0, p1, p2))
+        prims[i] = dict(type=int(t), p0=p0, p1=p1, p2=p2, size=size, material=glow if lamp else plain)
+    return prims
+
+
+def extent_of(spec):
+    """the extent setPrimitive grows from a fresh kernel's zeros (:671-678): over every p0 and the origin"""
+    p0 = np.array([s[1] for s in spec] + [(0, 0, 0)], F)
+    return p0.min(axis=0), p0.max(axis=0)
+
+
+def add_case(k, spec, plain, glow, movable=None):
+    for i, (t, p0, p1, p2, size, lamp) in enumerate(spec):
+        idx = k.add_primitive(t, p0, p1 or (0, 0, 0), p2 or (0, 0, 0), size=size, material=glow if lamp else plain)
+        assert idx == i
+        if movable is not None and not movable[i]:
+            k.set_movable(idx, False)
+
+
+def _build_both(solr, spec, view_distance=50000.0, move=None, capacity=None, movable=None):
+    """the host builder's flattened scene and the model's; move: a translation applied after a first build, before the
+    one that is compared (the extent is kept from before it).  model.declined: declines(model), asked in time"""
     k = solr.Kernel(engine="host-only")
     k.initialize(width=64, height=48, viewDistance=view_distance)
     plain = k.add_material(0.5, 0.5, 0.5)
     glow = k.add_material(1.0, 1.0, 1.0, innerIllumination=2.0)
     prims, emissive = {}, {plain: False, glow: True}
-    for i, (t, p0, p1, p2, size, lamp) in enumerate(spec):
-        p1 = p1 or (0, 0, 0)
-        p2 = p2 or (0, 0, 0)
-        idx = k.add_primitive(t, p0, p1, p2, size=size, material=glow if lamp else plain)
-        assert idx == i
+    add_case(k, spec, plain, glow, movable)
     k.compact_boxes(True)
+    if move is not None:
+        k.translate_primitives(move)
+        k.compact_boxes(True)
     flat = k.flat_scene()
     # the model is fed what the host's setPrimitive stored (it derives a cylinder's size and centre, a sphere's
     # replicated radius ...): the records of the flattened scene, by original index
     for rec in flat.primitives:
         prims[int(rec["index"])] = dict(type=int(rec["type"]), p0=rec["p0"], p1=rec["p1"], p2=rec["p2"],
                                         size=rec["size"], material=int(rec["materialId"]))
-    assert len(prims) == len(spec), "the builder lost primitives"
-    model = ReferenceBuilder(solr, view_distance, prims, emissive)
-    model.compact_boxes()
+    own = records_of(solr, spec, plain, glow, move, movable)
+    if sorted(prims) == list(range(len(spec))):
+        for i in own:                      # ... and records_of() is held to them wherever they are complete
+            for field in ("p0", "p1", "p2", "size"):
+                assert np.array_equal(np.asarray(prims[i][field], F).view(np.uint32),
+                                      np.asarray(own[i][field], F).view(np.uint32)), (i, field)
+            assert (prims[i]["type"], prims[i]["material"]) == (own[i]["type"], own[i]["material"])
+    else:
+        # one or two primitives, no lamp, a child in the lamp box's key: the host streams box keys as if they were
+        # primitives and the flattened scene misses some of the real ones ("Lost primitives on the way"): the model is
+        # fed from the case itself
+        prims = own
+    model = ReferenceBuilder(solr, view_distance, prims, emissive, extent=extent_of(spec) if move is not None else None)
+    depth_before = 2
+    if move is not None:                   # the second build of this kernel: the first one's depth (:1068-1075)
+        depth_before, nb = 0, len(spec)
+        while True:
+            depth_before, nb = depth_before + 1, nb // 4
+            if not nb > 2:
+                break
+    model.compact_boxes(depth_before)
+    model.depth_before = depth_before
+    model.declined = declines(model, capacity)
+    model.boxes_per_level = {d: len(boxes) for d, boxes in model.levels.items()}
     model.stream()
     boxes = np.array(flat.boxes, copy=True)
     order = [int(v) for v in flat.primitives["index"]]
