@@ -608,6 +608,29 @@ int solr_hip_move_lamp(int lamp, const float center[3]);
 int solr_hip_device_lamp_moves(void);
 int solr_hip_read_lights(float *rows, int capacityRows);
 
+/* Scenes that set some of their primitives anew every frame.  The reference's water scene runs 1152 triangles through
+ * setPrimitive + setPrimitiveNormals + setPrimitiveTextureCoordinates per frame, then the box updates and compactBoxes(false)
+ * (apps/scenes/animation/WaterScene.cpp doAnimate) - a flatten and a full upload for a batch of edits that leaves the
+ * flattened tree in shape (GPUKernel::setPrimitives on the host):
+ *   solr_hip_set_primitives     `edits`: n records, `slots`: per record the place of its primitive in the flattened order of
+ *                               the resident scene, no slot twice.  Every edited primitive is set the way the host's setters
+ *                               set it - setPrimitive's statements by the resident type (sizes, the cylinder's axis and
+ *                               mid-point, the planes' and the triangle's face normals), setPrimitiveNormals' normalised
+ *                               normals with SOLR_EDIT_NORMALS, the texture coordinates with
+ *                               SOLR_EDIT_TEXTURE_COORDINATES and zeros without; tag, material, index and colour key stay;
+ *                               its movable flag is set unless it is the camera primitive - then the lists are refitted as
+ *                               after a rotation.  viewDistance: sceneInfo.viewDistance.  Returns 1 when the resident scene
+ *                               now holds, bit for bit, what the setters + the box updates + a fresh h2d_scene would have
+ *                               produced, 0 when it cannot serve the request - whatever solr_hip_rotate_primitives
+ *                               refuses, no records, a slot out of range or twice, a slot among the lamps', a record whose
+ *                               index or materialId is not the resident primitive's, a primitive of an emissive material
+ *                               (its light record would have to follow), a float that is not finite: nothing changed, take
+ *                               the host route.  A morph on the device would leave an edit's texture coordinates behind:
+ *                               after an edit solr_hip_morph_primitives declines until the next h2d_scene;
+ *   solr_hip_device_edits       how many requests were served since initialize_scene. */
+int solr_hip_set_primitives(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance);
+int solr_hip_device_edits(void);
+
 /* Bytes of HBM this engine currently holds for {scene planes, materials,
  * textures, per-pixel buffers}; for DESIGN.md's layout table and tests. */
 void solr_hip_memory_usage(unsigned long long bytes[4]);

@@ -186,6 +186,19 @@ typedef struct SOLR_ALIGN(16) PostProcessingInfo_s
     vec1i param3;
 } PostProcessingInfo;
 
+/* ---- extension: one primitive of the store set anew (GPUKernel::setPrimitives, solr_hip_set_primitives): the arguments of
+ * setPrimitive and, by flag, of setPrimitiveNormals and setPrimitiveTextureCoordinates behind it */
+enum SolrEditFlags { SOLR_EDIT_NORMALS = 1, SOLR_EDIT_TEXTURE_COORDINATES = 2 };
+typedef struct SolrPrimitiveEdit_s
+{
+    vec1i index;        /* of the primitive in the scene store */
+    vec1i materialId;
+    unsigned int flags; /* SolrEditFlags: n0 n1 n2 / vt0 vt1 vt2 are set too (else setPrimitive's own stay) */
+    vec3f p0, p1, p2, size;
+    vec3f n0, n1, n2;
+    vec2f vt0, vt1, vt2;
+} SolrPrimitiveEdit;
+
 #ifdef __cplusplus
 #define SOLR_SA(c, m) static_assert(c, m)
 #else
@@ -206,5 +219,8 @@ SOLR_SA(offsetof(Material, attributes) == 64 && offsetof(Material, mappingOffset
 SOLR_SA(offsetof(BoundingBox, nbPrimitives) == 24 && offsetof(BoundingBox, indexForNextBox) == 32, "BoundingBox");
 SOLR_SA(offsetof(Primitive, size) == 72 && offsetof(Primitive, type) == 84 && offsetof(Primitive, vt0) == 96,
         "Primitive offsets");
+SOLR_SA(sizeof(SolrPrimitiveEdit) == 120, "SolrPrimitiveEdit layout");
+SOLR_SA(offsetof(SolrPrimitiveEdit, p0) == 12 && offsetof(SolrPrimitiveEdit, n0) == 60 && offsetof(SolrPrimitiveEdit, vt0) == 96,
+        "SolrPrimitiveEdit offsets");
 
 #endif /* SOLR_TYPES_H */

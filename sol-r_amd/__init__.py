@@ -102,6 +102,14 @@ class IsoTriangle(C.Structure):
                 ("cube", C.c_int), ("edge", C.c_int * 3)]
 
 
+class PrimitiveEdit(C.Structure):
+    """SolrPrimitiveEdit of include/solr_types.h: one primitive of the store set anew (EDIT_DTYPE is its numpy view)"""
+    _fields_ = [("index", C.c_int), ("materialId", C.c_int), ("flags", C.c_uint)] + \
+               [(name, C.c_float * 3) for name in ("p0", "p1", "p2", "size", "n0", "n1", "n2")] + \
+               [(name, C.c_float * 2) for name in ("vt0", "vt1", "vt2")]
+
+
+assert C.sizeof(PrimitiveEdit) == 120
 assert C.sizeof(SceneInfo) == 112 and C.sizeof(PostProcessingInfo) == 16
 assert C.sizeof(IsoGrid) == 48 and C.sizeof(IsoTriangle) == 112
 
@@ -114,6 +122,12 @@ PRIMITIVE_DTYPE = np.dtype({"names": ["p0", "p1", "p2", "n0", "n1", "n2", "size"
                                       "vt0", "vt1", "vt2"],
                             "formats": [(f4, 3)] * 7 + [i4, i4, i4] + [(f4, 2)] * 3,
                             "offsets": [0, 12, 24, 36, 48, 60, 72, 84, 88, 92, 96, 104, 112], "itemsize": 128})
+# SolrPrimitiveEdit of include/solr_types.h: one primitive set anew (Kernel.set_primitives)
+EDIT_NORMALS, EDIT_TEXTURE_COORDINATES = 1, 2
+EDIT_DTYPE = np.dtype({"names": ["index", "materialId", "flags", "p0", "p1", "p2", "size", "n0", "n1", "n2",
+                                 "vt0", "vt1", "vt2"],
+                       "formats": [i4, i4, np.uint32] + [(f4, 3)] * 7 + [(f4, 2)] * 3,
+                       "offsets": [0, 4, 8, 12, 24, 36, 48, 60, 72, 84, 96, 104, 112], "itemsize": 120})
 MATERIAL_DTYPE = np.dtype({"names": ["innerIllumination", "color", "specular", "reflection", "refraction",
                                      "transparency", "opacity", "attributes", "textureMapping", "textureOffset",
                                      "textureIds", "advancedTextureOffset", "advancedTextureIds", "mappingOffset"],
@@ -266,6 +280,9 @@ def _declare_hip(L):
     L.solr_hip_device_lamp_moves.restype = C.c_int
     L.solr_hip_read_lights.argtypes = [C.c_void_p, C.c_int]
     L.solr_hip_read_lights.restype = C.c_int
+    L.solr_hip_set_primitives.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+    L.solr_hip_set_primitives.restype = C.c_int
+    L.solr_hip_device_edits.restype = C.c_int
     L.solr_hip_read_nodes.argtypes = [C.c_int, C.c_void_p, C.c_int]
     L.solr_hip_read_nodes.restype = C.c_int
     L.solr_hip_read_primitives.argtypes = [C.c_void_p, C.c_int]
@@ -364,6 +381,28 @@ def _declare_host(L):
     L.SolRx_TranslatePrimitives.argtypes = [d, d, d]
     L.SolRx_SetPrimitiveCenter.argtypes = [i, d, d, d]
     L.SolRx_PendingMoves.restype = i
+    L.SolRx_SetPrimitives.argtypes = [C.c_void_p, i]
+    L.SolRx_SetPrimitives.restype = i
+    L.SolRx_SizeofPrimitiveEdit.restype = i
+
+
+def edit_records(edits):
+    """a contiguous array of EDIT_DTYPE from such an array or from a list of dicts (Kernel.set_primitives)"""
+    if isinstance(edits, np.ndarray):
+        if edits.dtype != EDIT_DTYPE:
+            raise SolrError("set_primitives: a structured array has to be of EDIT_DTYPE")
+        return np.ascontiguousarray(edits).reshape(-1)
+    batch = np.zeros(len(edits), EDIT_DTYPE)
+    for record, edit in zip(batch, edits):
+        unknown = set(edit) - set(EDIT_DTYPE.names)
+        if unknown or "index" not in edit or "materialId" not in edit:
+            raise SolrError("set_primitives: a record needs index and materialId and knows no %s" % sorted(unknown))
+        for field, value in edit.items():
+            record[field] = value
+        if "flags" not in edit:
+            record["flags"] = ((EDIT_NORMALS if any(f in edit for f in ("n0", "n1", "n2")) else 0) |
+                               (EDIT_TEXTURE_COORDINATES if any(f in edit for f in ("vt0", "vt1", "vt2")) else 0))
+    return batch
 
 
 def _np_from_ptr(ptr, count, dtype):
@@ -588,8 +627,21 @@ class Kernel:
         self.L.SolR_GetPrimitiveCenter(index, C.byref(x), C.byref(y), C.byref(z))
         return (x.value, y.value, z.value)
 
+    def set_primitives(self, edits):
+        """A batch of primitives set anew, then compactBoxes(false) (SolRx_SetPrimitives): per record setPrimitive(index,
+        p0, p1, p2, size, materialId), with EDIT_NORMALS in its flags setPrimitiveNormals(n0, n1, n2), with
+        EDIT_TEXTURE_COORDINATES setPrimitiveTextureCoordinates(vt0, vt1, vt2), then the box updates a rotation runs - what
+        a scene that animates its own vertices does per frame with the three setters.  edits: an array of EDIT_DTYPE, or a
+        list of dicts with its field names (index and materialId required; points, size, normals and texture coordinates
+        zero where left out; without "flags" the flags follow from whether any of n0 n1 n2 / vt0 vt1 vt2 is given).  With the
+        HIP engine and an unchanged resident scene the batch is applied on the device and the host copy follows lazily
+        (pending_moves).  0 when done, -1 when an index is not in the store (nothing changed)."""
+        batch = edit_records(edits)
+        return self.L.SolRx_SetPrimitives(batch.ctypes.data, len(batch))
+
     def pending_moves(self):
-        """rotations, translations and lamp moves applied on the device that the host scene store has not replayed yet"""
+        """rotations, translations, lamp moves and batches of edits applied on the device that the host scene store has not
+        replayed yet"""
         return self.L.SolRx_PendingMoves()
 
     # -- key frames ---------------------------------------------------------------------

@@ -2,7 +2,8 @@
  * engine.h - the state of the MI355X rendering engine and the helpers every part of its host side uses: what
  * solr_hip.hip (the boundary), solr_uploads.hip (the h2d_* uploads), solr_arena.hip (the arena and the node lists; their
  * host builders: list_builders.h), solr_rotation.hip (rotation and refit on the device), solr_morph.hip (key-frame
- * morphing on the device), solr_moves.hip (translation and lamp moves on the device), solr_launch.hip (the renderer's
+ * morphing on the device), solr_moves.hip (translation and lamp moves on the device), solr_edits.hip (primitives set anew on
+ * the device), solr_launch.hip (the renderer's
  * launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined read-back), solr_rccl.hip (strips,
  * communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
@@ -393,6 +394,10 @@ struct Rotation
     int nbDeviceTranslations = 0;
     int nbDeviceLampMoves = 0;
     bool lampMoved = false; /* a lamp was moved on the device since h2d_scene: a morph there would leave its light record behind */
+    /* primitives set anew (solr_edits.hip): the batch's planes as uploaded last; an edit runs the rotation's refit */
+    DeviceBuffer edits;
+    int nbDeviceEdits = 0;
+    bool edited = false; /* ... since h2d_scene: a morph there would leave the edit's texture coordinates behind */
 };
 /* Key-frame morphing on the device (solr_hip_set_morph_keys, solr_hip_morph_primitives; solr_morph.hip): the two key
  * frames of the resident scene.  Written by setMorphKeysOne and the transitions of Scene; an h2d_scene drops the keys. */
@@ -438,6 +443,7 @@ struct Scene
         rotation.refitPlanPending = true;
         rotation.nbMovable = -1;
         rotation.lampMoved = false;
+        rotation.edited = false;
         morphKeysDropped();
         arena.deviceAhead = false;
         orderFree.reset();
@@ -533,6 +539,17 @@ struct Scene
             ++rotation.nbDeviceLampMoves;
         }
     }
+    /* setPrimitivesOne has set the batch's primitives anew and refitted the lists (rotationQueued); as for a morph */
+    void editServed(bool walkHolds, bool landed)
+    {
+        walkEncloses = walkHolds;
+        if (landed)
+        {
+            arena.deviceAhead = true;
+            rotation.edited = true;
+            ++rotation.nbDeviceEdits;
+        }
+    }
     /* retagPrimitives has joined the materials' facts into the primitives' tags again */
     void retagged() { ++retags; }
     /* the morph keys: none (the buffers stay for the next ones) / uploaded for nbKeys primitives */
@@ -570,8 +587,8 @@ struct Scene
     void release()
     {
         lists.dropStage(true);
-        for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag, &morph.first,
-                                &morph.last})
+        for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag, &rotation.edits,
+                                &morph.first, &morph.last})
             solreng::release(*b);
         *this = Scene();
     }
@@ -905,6 +922,9 @@ bool canTranslateOne(const float translation[3], float viewDistance);
 int translatePrimitivesOne(const float translation[3], float viewDistance);
 bool canMoveLampOne(int lamp, const float center[3]);
 int moveLampOne(int lamp, const float center[3]);
+/* solr_edits.hip: a batch of primitives set anew on the device */
+bool canSetPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance);
+int setPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance);
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */
 void allocateFrame();
 int neededFeatures(const SceneInfo &sceneInfo, bool full);

@@ -2,8 +2,8 @@
  * solr_hip.hip - the C ABI of the MI355X rendering engine (include/solr_hip.h): the reference's ten entry points
  * (CudaRayTracer.h:25-67) once per in-process device, device / stream / strip selection, the life of an engine
  * (initialize_scene ... finalize_scene).  The rest of the engine's host side: engine.h (state), solr_uploads.hip,
- * solr_arena.hip, solr_rotation.hip, solr_morph.hip and solr_moves.hip (the resident scene: its uploads, its arena and lists,
- * rotation, morphing, translation and lamp moves on the device),
+ * solr_arena.hip, solr_rotation.hip, solr_morph.hip, solr_moves.hip and solr_edits.hip (the resident scene: its uploads, its
+ * arena and lists, rotation, morphing, translation, lamp moves and edited primitives on the device),
  * solr_launch.hip (a frame), solr_post.hip, solr_image_ring.hip, solr_rccl.hip, solr_diag.hip; the kernels: rt_device.h,
  * renderer_kernel.h, rows/.  gfx950 only.
  */
@@ -658,6 +658,23 @@ int solr_hip_move_lamp(int lamp, const float center[3])
     int status = 1; /* 1: moved on the device */
     onEveryDevice([&](int) {
         const int mine = moveLampOne(lamp, center);
+        if (mine != 1 && status == 1)
+            status = mine;
+    });
+    return status;
+}
+
+/* (... and every one of them sets the batch's primitives of its own copy; 1 only when all of them did) */
+int solr_hip_set_primitives(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance)
+{
+    /* as for a rotation: every resident copy must be able to follow before any of them changes */
+    bool all = true;
+    onEveryDevice([&](int) { all = canSetPrimitivesOne(edits, slots, n, viewDistance) && all; });
+    if (!all)
+        return 0;
+    int status = 1; /* 1: set on the device */
+    onEveryDevice([&](int) {
+        const int mine = setPrimitivesOne(edits, slots, n, viewDistance);
         if (mine != 1 && status == 1)
             status = mine;
     });

@@ -186,9 +186,10 @@ bool canMorphOne(float weight, float viewDistance)
         return false;
     const Morph &m = g.scene.morph;
     /* (a lamp that was moved on the device, solr_moves.hip: the blend would put its p0 back at the keys' place and leave
-     * its light record where the move put it - the host route makes the record from p0 again) */
+     * its light record where the move put it - the host route makes the record from p0 again; primitives that were set
+     * anew on the device, solr_edits.hip: the blend would leave their texture coordinates and movable flags behind) */
     if (m.nbKeys != g.scene.nbPrimitives || !m.first.ptr || !m.last.ptr || !std::isfinite(weight) || lampWouldMove() ||
-        g.scene.rotation.lampMoved)
+        g.scene.rotation.lampMoved || g.scene.rotation.edited)
     {
         if (getenv("SOLR_HIP_DEBUG_TREE"))
             fprintf(stderr, "solr_hip_morph_primitives refused: keys for %d of %d primitives, weight %g, a lamp moved here: %d\n",

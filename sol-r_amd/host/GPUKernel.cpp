@@ -323,6 +323,98 @@ void GPUKernel::setPrimitiveNormals(unsigned int index, vec3f n0, vec3f n1, vec3
     }
 }
 
+int GPUKernel::setPrimitives(const SolrPrimitiveEdit *edits, int n)
+{
+    if (n == 0)
+        return 0;
+    if (!edits || n < 0)
+        return -1;
+    /* (which indices the store has is not a matter of what is pending: no move adds or removes a primitive) */
+    PrimitiveContainer &primitives = frameAsIs().primitives;
+    for (int i = 0; i < n; ++i)
+        if (edits[i].index < 0 || !primitives.lookup((unsigned int)edits[i].index))
+            return -1;
+    /* as for a translation: the scene the device holds is the one the host holds (plus what is pending), the engine may
+     * set the primitives in place, and the host copy follows when somebody looks (syncHost).  An edit is never merely
+     * counted: what the engine hands back could not restore it */
+    if (m_resident.offers(m_frame) && m_resident.journalEditRecords + (size_t)n > ResidentScene::MAX_JOURNALLED_EDIT_RECORDS)
+        syncHost(); /* the journal's batches have grown large: replayed now, which leaves the fast path open */
+    if (m_resident.offers(m_frame) && m_resident.recordsEdits() && deviceSetPrimitives(edits, n))
+    {
+        m_resident.recordEdit(edits, n);
+        return 0;
+    }
+    Frame &f = frame();
+    m_resident.setTransfered(false);
+    setPrimitivesOnly(edits, n);
+    refitBoxes(f);
+    return 0;
+}
+
+void GPUKernel::setPrimitivesOnly(const SolrPrimitiveEdit *edits, int n)
+{
+    for (int i = 0; i < n; ++i)
+    {
+        const SolrPrimitiveEdit &e = edits[i];
+        setPrimitive(e.index, e.p0.x, e.p0.y, e.p0.z, e.p1.x, e.p1.y, e.p1.z, e.p2.x, e.p2.y, e.p2.z, e.size.x, e.size.y,
+                     e.size.z, e.materialId);
+        if (e.flags & SOLR_EDIT_NORMALS)
+            setPrimitiveNormals((unsigned int)e.index, e.n0, e.n1, e.n2);
+        if (e.flags & SOLR_EDIT_TEXTURE_COORDINATES)
+            setPrimitiveTextureCoordinates((unsigned int)e.index, e.vt0, e.vt1, e.vt2);
+    }
+}
+
+bool GPUKernel::editSlots(const SolrPrimitiveEdit *edits, int n, std::vector<SolrPrimitiveEdit> &last, std::vector<int> &slots)
+{
+    if (m_slotOfUpload != m_resident.uploads)
+    {
+        /* the flattened order of the resident scene: that of the upload, which the replays of syncHost keep */
+        int top = -1;
+        for (const Primitive &p : m_hPrimitives)
+            top = std::max(top, p.index);
+        m_slotOf.assign((size_t)(top + 1), -1);
+        for (size_t slot = 0; slot < m_hPrimitives.size(); ++slot)
+            if (m_hPrimitives[slot].index >= 0)
+            {
+                int &at = m_slotOf[(size_t)m_hPrimitives[slot].index];
+                at = (at == -1) ? (int)slot : -2;
+            }
+        m_slotOfUpload = m_resident.uploads;
+    }
+    auto finite3 = [](const vec3f &v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
+    auto finite2 = [](const vec2f &v) { return std::isfinite(v.x) && std::isfinite(v.y); };
+    const int nbLamps = frameAsIs().nbActiveLamps;
+    last.clear();
+    slots.clear();
+    last.reserve((size_t)n);
+    slots.reserve((size_t)n);
+    /* per slot the place of its record in `last` + 1 (0: none yet) */
+    std::vector<int> placed(m_hPrimitives.size(), 0);
+    for (int i = 0; i < n; ++i)
+    {
+        const SolrPrimitiveEdit &e = edits[i];
+        if (e.index < 0 || (size_t)e.index >= m_slotOf.size() || m_slotOf[(size_t)e.index] < 0)
+            return false;
+        const int slot = m_slotOf[(size_t)e.index];
+        if (slot < nbLamps || m_hPrimitives[(size_t)slot].materialId != e.materialId || e.materialId < 0 ||
+            (size_t)e.materialId >= m_hMaterials.size() || m_hMaterials[(size_t)e.materialId].innerIllumination.x != 0.f)
+            return false;
+        if (!finite3(e.p0) || !finite3(e.p1) || !finite3(e.p2) || !finite3(e.size) || !finite3(e.n0) || !finite3(e.n1) ||
+            !finite3(e.n2) || !finite2(e.vt0) || !finite2(e.vt1) || !finite2(e.vt2))
+            return false;
+        if (placed[(size_t)slot])
+            last[(size_t)placed[(size_t)slot] - 1] = e;
+        else
+        {
+            last.push_back(e);
+            slots.push_back(slot);
+            placed[(size_t)slot] = (int)last.size();
+        }
+    }
+    return true;
+}
+
 /* reference: GPUKernel.cpp:729-739 */
 unsigned int GPUKernel::getPrimitiveAt(int x, int y)
 {
@@ -1114,8 +1206,9 @@ int GPUKernel::morphFrame(float weight)
         return -1;
     /* (a lamp that was moved over there: a morph there would put it back at its keys' place and leave its light record
      * behind, so such a morph is not offered to the engine - which would decline it, after the keys were handed over for
-     * nothing - and the host route serves it) */
-    if (resident && !m_resident.lampMoved && deviceMorphFrame(weight))
+     * nothing - and the host route serves it.  Nor behind primitives that were set anew over there: the blend would
+     * leave their texture coordinates and movable flags as the edit set them, where the host loop takes the first key's) */
+    if (resident && !m_resident.lampMoved && !m_resident.edited && deviceMorphFrame(weight))
     {
         /* every primitive has been set anew: what was pending before is superseded (no lamp move is among it) */
         m_resident.morphServed(weight);
@@ -1269,8 +1362,10 @@ void GPUKernel::syncHost()
     if (pending.morphPending)
         morphPrimitivesOnly(pending.pendingMorphWeight);
     /* a handful of rotations and translations is replayed (4 ms each for 100 k primitives); a long animation is
-     * fetched, and so is one whose moves were not all recorded */
-    if ((nbHeavy <= 8 && !unrecorded) || !primitivesFromDevice(f))
+     * fetched, and so is one whose moves were not all recorded.  A journal that holds an edit is always replayed: what
+     * is fetched carries neither sizes nor texture coordinates, and not the primitives the store believes unmovable
+     * (all its moves are recorded: ResidentScene::offers) */
+    if ((nbHeavy <= 8 && !unrecorded) || pending.journalEdits || !primitivesFromDevice(f))
     {
         if (unrecorded)
             std::cerr << "GPUKernel::syncHost: the engine did not hand back its primitives and " << unrecorded
@@ -1287,6 +1382,12 @@ void GPUKernel::syncHost()
             case ResidentScene::Move::LAMP_MOVE:
                 if (CPUPrimitive *p = f.primitives.lookup(move.index))
                     p->p0 = move.v;
+                break;
+            case ResidentScene::Move::EDIT:
+                /* the setters; the boxes follow below, with everybody's */
+                setPrimitivesOnly(pending.editBatches[move.index].data(), (int)pending.editBatches[move.index].size());
+                break;
+            case ResidentScene::Move::NB_KINDS:
                 break;
             }
     }

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <map>
+#include <numeric>
 #include <unordered_map>
 #include <string>
 #include <utility>
@@ -288,7 +289,9 @@ struct ResidentScene
         {
             ROTATION,    /* v: the centre, cosA, sinA */
             TRANSLATION, /* v: the translation */
-            LAMP_MOVE    /* v: the centre of primitive `index` */
+            LAMP_MOVE,   /* v: the centre of primitive `index` */
+            EDIT,        /* a batch of primitives set anew: editBatches[index] */
+            NB_KINDS
         } kind;
         vec3f v, cosA, sinA;
         unsigned int index;
@@ -300,35 +303,58 @@ struct ResidentScene
     bool primitivesTransfered = false; /* the reference's m_primitivesTransfered: no upload of the scene is due */
     bool touched = true;               /* the scene store was accessed since the last upload */
     long frame = -1;                   /* the frame the resident scene was uploaded from, -1: none */
+    unsigned long uploads = 0;         /* how often the scene was uploaded: what was made from the flattened order is as old as that */
     bool lampMoved = false;            /* a lamp was moved over there since the upload (morphFrame) */
+    bool edited = false;               /* primitives were set anew over there since the upload (morphFrame) */
     long morphKeysFrame = -1, morphKeysNbFrames = -1; /* the engine's morph keys are for that frame of that many, -1: it has none */
     bool buildingLevels = false; /* the lazy build of the level maps reads the store as it is: what is pending stays pending */
     /* the journal: the moves served over there since the upload - or since the morph that superseded what was before
      * it -, in order, up to the cap; the rotations among them; per kind those beyond the cap */
     std::vector<Move> journal;
     size_t journalRotations = 0;
-    size_t unrecorded[3] = {0, 0, 0}; /* by Move::Kind */
+    size_t unrecorded[Move::NB_KINDS] = {}; /* by Move::Kind */
+    /* the batches of the journal's edits, as given, and how many edits the journal holds.  What the engine hands back
+     * (primitivesFromDevice) carries neither sizes nor texture coordinates and leaves out what the store believes unmovable,
+     * so it cannot restore an edit: a journal that holds one is always replayed, and is therefore never merely counted -
+     * at the cap an edit is declined (recordsEdits), and behind an edit so is every other move (offers) */
+    std::vector<std::vector<SolrPrimitiveEdit>> editBatches;
+    size_t journalEdits = 0;
+    /* ... and the records in them: a scene that edits a thousand triangles a frame for hours must not grow the journal
+     * without bound.  Past this many (120 MB of records) the store catches up before the next batch is offered
+     * (GPUKernel::setPrimitives) - a replay, which leaves the fast path open */
+    static constexpr size_t MAX_JOURNALLED_EDIT_RECORDS = size_t(1) << 20;
+    size_t journalEditRecords = 0;
     bool morphPending = false;
     float pendingMorphWeight = 0.f;
 
     /* The one offer rule: a move on frame `f` of the store may be offered to the engine when the scene over there was
      * uploaded, nothing has accessed the store since, and it was uploaded from that frame (a frame switch without a
      * flatten leaves the device with another frame than the current one) */
-    bool offers(unsigned int f) const { return primitivesTransfered && !touched && frame == (long)f; }
+    bool offers(unsigned int f) const
+    {
+        return primitivesTransfered && !touched && frame == (long)f && !(journalEdits && journal.size() >= MAX_RECORDED_MOVES);
+    }
+    /* ... and a batch of edits only while the journal records: an edit is never merely counted */
+    bool recordsEdits() const { return journal.size() < MAX_RECORDED_MOVES; }
     bool hasMorphKeys(unsigned int f, unsigned int n) const { return morphKeysFrame == (long)f && morphKeysNbFrames == (long)n; }
-    size_t nbUnrecorded() const { return unrecorded[0] + unrecorded[1] + unrecorded[2]; }
+    size_t nbUnrecorded() const { return std::accumulate(unrecorded, unrecorded + Move::NB_KINDS, (size_t)0); }
     size_t nbPendingMoves() const { return journal.size() + nbUnrecorded(); }
     size_t nbPendingRotations() const { return journalRotations + unrecorded[Move::ROTATION]; }
     bool pendingMorph() const { return morphPending; }
     bool lags() const { return nbPendingMoves() > 0 || morphPending; }
-    /* the recorded rotations and translations: a pass over the primitives each to replay; a lamp move is one assignment */
+    /* the recorded rotations and translations: a pass over the primitives each to replay; a lamp move is one assignment,
+     * an edit a few per primitive of its batch */
     size_t nbHeavy() const
     {
-        return std::count_if(journal.begin(), journal.end(), [](const Move &m) { return m.kind != Move::LAMP_MOVE; });
+        return std::count_if(journal.begin(), journal.end(),
+                             [](const Move &m) { return m.kind == Move::ROTATION || m.kind == Move::TRANSLATION; });
     }
     /* do the boxes follow what is pending?  Lamp moves alone refit nothing, as on the host route: setPrimitiveCenter +
      * compactBoxes(false) leaves every box as it is, the stale box of another primitive whose centre was set included */
-    bool refits() const { return morphPending || nbHeavy() || unrecorded[Move::ROTATION] || unrecorded[Move::TRANSLATION]; }
+    bool refits() const
+    {
+        return morphPending || nbHeavy() || journalEdits || unrecorded[Move::ROTATION] || unrecorded[Move::TRANSLATION];
+    }
 
     /* the engine has uploaded the scene from frame `f` (render_begin, when an upload was due): device and host hold the same
      * scene, the engine's morph keys are gone, the lamps are where the store has them */
@@ -339,6 +365,8 @@ struct ResidentScene
         morphKeysFrame = morphKeysNbFrames = -1;
         frame = (long)f;
         lampMoved = false;
+        edited = false;
+        ++uploads;
     }
     void setTransfered(bool value) { primitivesTransfered = value; }
     /* the scene store was accessed (GPUKernel::frame): the fast path ends until the next upload */
@@ -357,12 +385,24 @@ struct ResidentScene
         journal.push_back(move);
         journalRotations += move.kind == Move::ROTATION;
     }
+    /* the engine has set these primitives anew (offered only while recordsEdits): the batch as given, into the journal */
+    void recordEdit(const SolrPrimitiveEdit *edits, int n)
+    {
+        edited = true;
+        editBatches.emplace_back(edits, edits + n);
+        journal.push_back({Move::EDIT, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, (unsigned int)editBatches.size() - 1});
+        ++journalEdits;
+        journalEditRecords += (size_t)n;
+    }
     /* the store has been set anew, here (morphFrame's host route): nothing is pending */
     void clear()
     {
         journal.clear();
         journalRotations = 0;
-        unrecorded[0] = unrecorded[1] = unrecorded[2] = 0;
+        std::fill(unrecorded, unrecorded + Move::NB_KINDS, (size_t)0);
+        editBatches.clear();
+        journalEdits = 0;
+        journalEditRecords = 0;
         morphPending = false;
     }
     /* ... or over there, by a morph at that weight: it supersedes what was pending before it */
@@ -471,6 +511,15 @@ public:
                                         const vec2f &vt2);
     void setPrimitiveNormals(unsigned int index, vec3f n0, vec3f n1, vec3f n2);
     CPUPrimitive *getPrimitive(const unsigned int index);
+    /* extension: a batch of primitives of the store set anew - what a scene that animates its own vertices does per frame
+     * with the three setters (the reference's WaterScene::doAnimate: 1152 triangles).  Every index is looked up first: one
+     * that is not in the store refuses the batch, -1, nothing changed.  Then per record, in order: setPrimitive(index, p0,
+     * p1, p2, size, materialId), with SOLR_EDIT_NORMALS setPrimitiveNormals, with SOLR_EDIT_TEXTURE_COORDINATES
+     * setPrimitiveTextureCoordinates; then the box updates a rotation or a translation runs (refitBoxes).  The caller
+     * flattens with compactBoxes(false), as after translatePrimitives.  An engine that keeps the scene resident may set the
+     * primitives there (deviceSetPrimitives); the host copy then lags behind by that batch, in the journal with the other
+     * moves, and syncHost() catches it up.  Returns 0 when done; n == 0 is done and records nothing */
+    int setPrimitives(const SolrPrimitiveEdit *edits, int n);
     /* extension: the iso-surface of a field of metaballs appended as triangles - what the reference's MetaballsScene makes
      * per frame with two host loops and the fake-GL entry points (apps/scenes/animation/MetaballsScene.cpp:247-400).
      * balls: nbBalls records of x, y, z, squared radius.  The triangles come from the engine (the isoSurface hook) and are
@@ -706,6 +755,17 @@ protected:
      * primitive m_hLamps[slot]) and of its light record; false = not done, nothing changed */
     virtual bool deviceTranslatePrimitives(const vec3f &) { return false; }
     virtual bool deviceMoveLamp(int, const vec3f &) { return false; }
+    /* engine hook: set these primitives of the resident scene anew (every index is in the store); false = not done, nothing
+     * changed */
+    virtual bool deviceSetPrimitives(const SolrPrimitiveEdit *, int) { return false; }
+    /* for that hook: the batch as the engine takes it - of several records for one index the last one only (setPrimitive
+     * resets everything a record can set), each with the slot of its primitive in the flattened order, from a map made
+     * once per upload.  False when the store's side of the engine's conditions fails: an index without exactly one slot,
+     * a slot among the lamps', another material than the primitive has (tags and colour keys are a join with the
+     * materials made at upload), an emissive material (the light record would have to follow), a float that is not finite */
+    bool editSlots(const SolrPrimitiveEdit *edits, int n, std::vector<SolrPrimitiveEdit> &last, std::vector<int> &slots);
+    /* setPrimitives' loop over the records (no box is updated) */
+    void setPrimitivesOnly(const SolrPrimitiveEdit *edits, int n);
     /* engine hook: the pixel stage of a JPEG texture (csrc/jpeg_pixels.h) - coefficient blocks as
      * ImageLoader::parseJPEG leaves them to frame.width * frame.height * 3 bytes in `rgb`.  Here: a loop on the CPU;
      * false = the engine failed (its error is pending) */
@@ -744,6 +804,9 @@ protected:
     bool morphKeys(std::vector<Primitive> &first, std::vector<Primitive> &last);
     /* the engine's resident scene against the store: who serves a move, and what the store owes afterwards */
     ResidentScene m_resident;
+    /* editSlots: store index -> slot of the flattened order (-1: none, -2: several), of upload number m_slotOfUpload */
+    std::vector<int> m_slotOf;
+    unsigned long m_slotOfUpload = 0;
 
     /* box-tree build (GPUKernel.h:318-324) */
     int processBoxes(const int boxSize, bool simulate);

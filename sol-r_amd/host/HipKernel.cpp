@@ -241,6 +241,17 @@ bool HipKernel::deviceMoveLamp(int slot, const vec3f &center)
     return solr_hip_move_lamp(slot, c) == 1;
 }
 
+bool HipKernel::deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n)
+{
+    if (!m_deviceInitialized)
+        return false;
+    std::vector<SolrPrimitiveEdit> last;
+    std::vector<int> slots;
+    if (!editSlots(edits, n, last, slots))
+        return false;
+    return solr_hip_set_primitives(last.data(), slots.data(), (int)last.size(), m_sceneInfo.viewDistance) == 1;
+}
+
 bool HipKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb)
 {
     if (solr_hip_device_count() < 1)
@@ -535,6 +546,16 @@ bool ReplayKernel::deviceMoveLamp(int, const vec3f &c)
     if (!std::isfinite(c.x) || !std::isfinite(c.y) || !std::isfinite(c.z))
         return false;
     ++m_claimedLampMoves;
+    return true;
+}
+
+bool ReplayKernel::deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n)
+{
+    std::vector<SolrPrimitiveEdit> last;
+    std::vector<int> slots;
+    if (!editSlots(edits, n, last, slots))
+        return false;
+    ++m_claimedEdits;
     return true;
 }
 

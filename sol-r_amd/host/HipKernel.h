@@ -65,6 +65,8 @@ protected:
      * solr_hip_move_lamp (include/solr_hip.h) */
     bool deviceTranslatePrimitives(const vec3f &translation) override;
     bool deviceMoveLamp(int slot, const vec3f &center) override;
+    /* setPrimitives on the resident scene, solr_hip_set_primitives (include/solr_hip.h): store indices to slots first */
+    bool deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n) override;
     void fetchPrimitiveIds() override;
     void fetchBitmap() override;
     bool primitivesFromDevice(Frame &f) override;
@@ -124,6 +126,7 @@ public:
     int nbClaimedMorphs() const { return m_claimedMorphs; }
     int nbClaimedTranslations() const { return m_claimedTranslations; }
     int nbClaimedLampMoves() const { return m_claimedLampMoves; }
+    int nbClaimedEdits() const { return m_claimedEdits; }
 
 protected:
     bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) override;
@@ -131,8 +134,10 @@ protected:
     bool deviceMorphPrimitives(float weight) override;
     bool deviceTranslatePrimitives(const vec3f &) override;
     bool deviceMoveLamp(int slot, const vec3f &center) override;
+    /* (claimed where the store's side of the engine's conditions holds: GPUKernel::editSlots) */
+    bool deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n) override;
 
 private:
-    int m_claimed = 0, m_claimedMorphs = 0, m_claimedTranslations = 0, m_claimedLampMoves = 0;
+    int m_claimed = 0, m_claimedMorphs = 0, m_claimedTranslations = 0, m_claimedLampMoves = 0, m_claimedEdits = 0;
 };
 }

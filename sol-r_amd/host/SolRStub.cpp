@@ -457,6 +457,22 @@ int SolRx_SetPrimitiveCenter(int index, double x, double y, double z)
     return 0;
 }
 
+/* Extension: GPUKernel::setPrimitives + compactBoxes(false): a batch of primitives set anew, what a scene that animates its
+ * own vertices does per frame (apps/scenes/animation/WaterScene.cpp doAnimate).  -1: an index is not in the store, nothing
+ * changed */
+int SolRx_SetPrimitives(const SolrPrimitiveEdit *edits, int n)
+{
+    const int status = SingletonKernel::kernel()->setPrimitives(edits, n);
+    if (status == 0 && n > 0)
+        SingletonKernel::kernel()->compactBoxes(false);
+    return status;
+}
+
+int SolRx_SizeofPrimitiveEdit()
+{
+    return (int)sizeof(SolrPrimitiveEdit);
+}
+
 int SolRx_PendingMoves()
 {
     return (int)SingletonKernel::kernel()->nbPendingMoves();

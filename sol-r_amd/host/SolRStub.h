@@ -210,6 +210,12 @@ int SolRx_PendingRotations();
  * there that the host scene store has not replayed yet (SolRx_PendingRotations: the rotations among them) */
 int SolRx_TranslatePrimitives(double x, double y, double z);
 int SolRx_SetPrimitiveCenter(int index, double x, double y, double z);
+/* a batch of primitives of the store set anew (GPUKernel::setPrimitives: per record setPrimitive and, by flag,
+ * setPrimitiveNormals and setPrimitiveTextureCoordinates; then the box updates) + compactBoxes(false).  With the HIP engine
+ * and an unchanged resident scene the batch is applied on the device and counts among SolRx_PendingMoves.  0 = done, -1 =
+ * an index is not in the store: nothing changed.  SolRx_SizeofPrimitiveEdit: the record's size, for bindings */
+int SolRx_SetPrimitives(const SolrPrimitiveEdit *edits, int n);
+int SolRx_SizeofPrimitiveEdit();
 int SolRx_PendingMoves();
 int SolRx_SyncHost();
 int SolRx_GetMovable(const unsigned char **flags, int *nbPrimitives);

@@ -298,3 +298,68 @@ def metaballs_surroundings(k):
     for (ptype, p0), material in zip(walls, m["walls"]):
         k.add_primitive(ptype, p0, size=(w, h, d), material=material)
     k.add_primitive(ptSphere, (-10000.0, 10000.0, -10000.0), size=(500.0, 0, 0), material=m["lamp"], movable=0)
+
+
+WATER_CELLS = 24
+
+
+def water_edits(timer, first=0, material=0, cells=WATER_CELLS, scale=(4000.0, 1200.0, 4000.0)):
+    """One frame of the reference's torus animation (apps/scenes/animation/WaterScene.cpp: a torus of cells x cells cells whose
+    height follows sin(u + timer) + cos(t + 2 timer)) as a batch for Kernel.set_primitives: 2 cells^2 records of EDIT_DTYPE -
+    1152 triangles at 24 x 24 - with per-vertex normals and texture coordinates, for the primitives first, first + 1 ... in
+    cell order.  The vertices are worked out here, in binary64 and rounded once, so whoever takes the batch - the three
+    setters one record at a time, or set_primitives on either route - gets the same floats."""
+    import numpy as np
+    from . import EDIT_DTYPE, EDIT_NORMALS, EDIT_TEXTURE_COORDINATES
+    step = 2.0 * math.pi / cells
+    grid = -math.pi + step * np.arange(cells + 1)
+    t, u = np.meshgrid(grid, grid, indexing="ij")
+
+    def surface(t, u):
+        ring = scale[0] + scale[1] * np.cos(u)
+        return np.stack([np.cos(t) * ring, scale[1] * (np.sin(u + timer) + np.cos(t + 2.0 * timer)),
+                         np.sin(t) * (scale[2] + scale[1] * np.cos(u))], axis=-1)
+
+    points = surface(t, u)
+    e = 1.0e-3
+    normals = np.cross(surface(t, u + e) - surface(t, u - e), surface(t + e, u) - surface(t - e, u))
+    uv = np.stack([(t + math.pi) / (2.0 * math.pi), (u + math.pi) / (2.0 * math.pi)], axis=-1)
+    batch = np.zeros(2 * cells * cells, EDIT_DTYPE)
+    batch["index"] = first + np.arange(len(batch))
+    batch["materialId"] = material
+    batch["flags"] = EDIT_NORMALS | EDIT_TEXTURE_COORDINATES
+    # per cell the triangles (a, b, c) and (a, c, d) of its corners a (i, j), b (i + 1, j), c (i + 1, j + 1), d (i, j + 1)
+    corners = {"a": (slice(0, -1), slice(0, -1)), "b": (slice(1, None), slice(0, -1)), "c": (slice(1, None), slice(1, None)),
+               "d": (slice(0, -1), slice(1, None))}
+    for half, names in enumerate(("abc", "acd")):
+        for vertex, name in enumerate(names):
+            at = corners[name]
+            batch["p%d" % vertex][half::2] = points[at].reshape(-1, 3)
+            batch["n%d" % vertex][half::2] = normals[at].reshape(-1, 3)
+            batch["vt%d" % vertex][half::2] = uv[at].reshape(-1, 2)
+    return batch
+
+
+def water(k, timer=0.0, width=1920, height=1080, iterations=2, seed=77, **scene_info):
+    """The reference's WaterScene restated: the torus of water_edits at `timer` as 1152 textured triangles - the
+    primitives k.water["first"] ... of material k.water["material"] -, a floor under it and one light.  A frame of the
+    animation is k.set_primitives(water_edits(t, **k.water))."""
+    import numpy as np
+    rng = LCG(seed)
+    k.initialize(width=width, height=height, nbRayIterations=iterations, graphicsLevel=glFull, **scene_info)
+    k.set_texture(0, np.fromfunction(lambda y, x, c: ((x // 8 + y // 8) % 2) * 120 + 60 + 25 * c, (64, 64, 3)).astype(np.uint8))
+    surface = k.add_material(*_wall_color(rng), reflection=0.2, specValue=1.0, specPower=100.0, diffuseTextureId=0)
+    floor = k.add_material(*_wall_color(rng), specValue=0.1, specPower=200.0)
+    batch = water_edits(timer, 0, surface)
+    first = None
+    for e in batch:
+        t = k.add_primitive(ptTriangle, e["p0"], e["p1"], e["p2"], material=surface)
+        k.set_normals(t, e["n0"], e["n1"], e["n2"])
+        k.set_texture_coordinates(t, e["vt0"], e["vt1"], e["vt2"])
+        first = t if first is None else first
+    k.add_primitive(ptXZPlane, (0.0, -4000.0, 0.0), size=(12000.0, 0.0, 12000.0), material=floor)
+    add_light(k)
+    k.water = dict(first=first, material=surface)
+    k.compact_boxes(True)
+    k.set_camera((0.0, 5000.0, -14000.0))
+    return k
