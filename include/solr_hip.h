@@ -571,6 +571,30 @@ int solr_hip_set_morph_keys(const Primitive *first, const Primitive *last, int n
 int solr_hip_morph_primitives(float weight, float viewDistance);
 int solr_hip_device_morphs(void);
 
+/* Key-frame tracks.  The reference's animation scene loads one mesh per frame - every frame a key - and shows them with
+ * setFrame + compactBoxes(false) (apps/scenes/animation/AnimationScene.cpp:55-109): a flatten and a full upload per displayed
+ * frame.  With one more frame as the stage, the resident scene can be blended from any two of up to
+ * SOLR_MORPH_TRACK_MAX_KEYS key frames of it (GPUKernel::morphBetween on the host); a key frame is handed over once, packed
+ * on the device, and blended from as often as the animation passes it:
+ *   solr_hip_set_morph_track_key  after h2d_scene: the key frame of `slot`.  Of a record only p0 p1 p2 n0 n1 n2 size are
+ *                               read.  Valid until the next h2d_scene.  Refused before anything is launched, the slots
+ *                               left as they are: a slot outside 0 ... SOLR_MORPH_TRACK_MAX_KEYS - 1, a null pointer,
+ *                               nbPrimitives other than the resident scene's, a rank outside 0 ... nbPrimitives - 1.  An
+ *                               allocation that fails declines the key (the slot then holds none);
+ *   solr_hip_morph_between      what solr_hip_morph_primitives does, with the keys of the two slots as first and last (the
+ *                               same slot twice is allowed).  It declines what that declines - "no keys" being a slot
+ *                               that holds none, the emissive primitives compared between these two slots -: nothing
+ *                               changed, take the host route. */
+#define SOLR_MORPH_TRACK_MAX_KEYS 256
+/* key: the key frame's primitives in ID order (rank order), nbPrimitives records; rankOf[i]: the rank of the primitive
+ * that is i-th in the flattened order of the resident scene.  Host pointers. 1 = the slot holds the key, 0 = not. */
+int solr_hip_set_morph_track_key(int slot, const Primitive *key, const int *rankOf, int nbPrimitives);
+/* every resident primitive set to keyA + weight * (keyB - keyA), lists refitted; 1 = done on the device,
+ * 0 = cannot be served here, nothing was changed */
+int solr_hip_morph_between(int slotA, int slotB, float weight, float viewDistance);
+int solr_hip_morph_track_keys(void);    /* slots that hold a key of the resident scene */
+int solr_hip_device_track_morphs(void); /* requests served since initialize_scene */
+
 /* Models that are pushed along, lamps that are dragged.  The reference's scenes translate a model with
  * GPUKernel::translatePrimitives (GPUKernel.cpp:1462-1511; apps/scenes/Scene.cpp:1546-1548: rotate, translate,
  * compactBoxes(false)) and its viewer drags a lamp with setPrimitiveCenter + compactBoxes(false) on every mouse event

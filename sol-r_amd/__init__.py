@@ -18,6 +18,7 @@ The directory name contains a hyphen, so import it with::
     import importlib; solr = importlib.import_module("sol-r_amd")
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -272,6 +273,12 @@ def _declare_hip(L):
     L.solr_hip_morph_primitives.argtypes = [C.c_float, C.c_float]
     L.solr_hip_morph_primitives.restype = C.c_int
     L.solr_hip_device_morphs.restype = C.c_int
+    L.solr_hip_set_morph_track_key.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.solr_hip_set_morph_track_key.restype = C.c_int
+    L.solr_hip_morph_between.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float]
+    L.solr_hip_morph_between.restype = C.c_int
+    L.solr_hip_morph_track_keys.restype = C.c_int
+    L.solr_hip_device_track_morphs.restype = C.c_int
     L.solr_hip_translate_primitives.argtypes = [P(C.c_float), C.c_float]
     L.solr_hip_translate_primitives.restype = C.c_int
     L.solr_hip_device_translations.restype = C.c_int
@@ -378,6 +385,9 @@ def _declare_host(L):
     L.SolRx_SetNbFrames.argtypes = [i]
     L.SolRx_SetFrame.argtypes = [i]
     L.SolRx_MorphFrame.argtypes = [d]
+    L.SolRx_MorphBetween.argtypes = [i, i, d]
+    L.SolRx_MorphBetween.restype = i
+    L.SolRx_GetNbFrames.restype = i
     L.SolRx_TranslatePrimitives.argtypes = [d, d, d]
     L.SolRx_SetPrimitiveCenter.argtypes = [i, d, d, d]
     L.SolRx_PendingMoves.restype = i
@@ -665,6 +675,28 @@ class Kernel:
         shape and refitted.  With the HIP engine and an unchanged resident scene the blend runs on the device and the
         host copy follows lazily (pending_morph).  0 when done, -1 when refused (nothing changed)."""
         return self.L.SolRx_MorphFrame(weight)
+
+    def morph_between(self, frame_a, frame_b, weight):
+        """The current frame - a stage that is neither key - set to frame_a + weight * (frame_b - frame_a), primitive by
+        primitive paired by rank in id order (SolRx_MorphBetween); material, texture coordinates and movable flag are
+        frame_a's, the stage's tree is kept in shape and refitted, the frame is flattened.  Any finite weight (beyond
+        0 ... 1: extrapolated), frame_a == frame_b allowed.  With the HIP engine and an unchanged resident stage the blend
+        runs on the device - a key frame is handed over the first time a request names it - and the host copy follows
+        lazily (pending_morph).  0 when done, -1 when refused (nothing changed)."""
+        return self.L.SolRx_MorphBetween(frame_a, frame_b, weight)
+
+    def play(self, t):
+        """An animation of K key frames of one mesh at time t, in key frames: the scene has K + 1 frames, the keys in
+        0 ... K - 1 and the stage - the current frame - last; keys floor(t) and floor(t) + 1 are blended at weight
+        t - floor(t) (morph_between).  t is clamped to 0 ... K - 1: before the first key the first key is shown, from the
+        last key on the last one (as keys K - 2 and K - 1 at weight 1).  Returns morph_between's status, -1 also for a t
+        that is not finite or a scene with fewer than two keys."""
+        keys = self.L.SolRx_GetNbFrames() - 1
+        if keys < 2 or not math.isfinite(t):
+            return -1
+        t = min(max(float(t), 0.0), float(keys - 1))
+        first = min(int(math.floor(t)), keys - 2)
+        return self.morph_between(first, first + 1, t - first)
 
     def pending_morph(self):
         """a morph was applied on the device that the host scene store has not replayed yet"""

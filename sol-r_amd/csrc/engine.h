@@ -399,16 +399,35 @@ struct Rotation
     int nbDeviceEdits = 0;
     bool edited = false; /* ... since h2d_scene: a morph there would leave the edit's texture coordinates behind */
 };
-/* Key-frame morphing on the device (solr_hip_set_morph_keys, solr_hip_morph_primitives; solr_morph.hip): the two key
- * frames of the resident scene.  Written by setMorphKeysOne and the transitions of Scene; an h2d_scene drops the keys. */
+/* Key-frame morphing on the device (solr_morph.hip): the key frames of the resident scene the engine holds, one per slot -
+ * the slots of a track (solr_hip_set_morph_track_key, solr_hip_morph_between), then the two of the two-key interface
+ * (solr_hip_set_morph_keys, solr_hip_morph_primitives).  Written by the transitions of Scene only; an h2d_scene drops the keys. */
+enum MorphSlot
+{
+    MORPH_SLOT_FIRST = SOLR_MORPH_TRACK_MAX_KEYS, /* solr_hip_set_morph_keys' first key frame */
+    MORPH_SLOT_LAST,                              /* ... and its last */
+    MORPH_SLOTS
+};
+struct MorphKey
+{
+    DeviceBuffer planes;   /* seven planes of nbPrimitives float4 each: p0 p1 p2 n0 n1 n2 size (the buffer stays for the next key) */
+    int nbPrimitives = -1; /* the key is for that many primitives, -1: the slot holds none */
+};
+/* the lamp rule's answer for an ordered pair of slots: a primitive tagged PRIM_EMISSIVE has rows that differ between them */
+struct MorphLampAnswer
+{
+    int slotA, slotB;
+    bool moves;
+};
 struct Morph
 {
-    DeviceBuffer first, last;              /* seven planes of nbKeys float4 each: p0 p1 p2 n0 n1 n2 size */
-    int nbKeys = -1;                       /* keys uploaded for that many primitives, -1: none */
-    std::vector<unsigned char> keysDiffer; /* per primitive: its two keys differ in some bit */
-    long lampChecked = -1;                 /* Scene::retags when lampMoves was worked out, -1: not yet */
-    bool lampMoves = false;                /* a primitive tagged PRIM_EMISSIVE has keys that differ: not served here */
-    int nbDeviceMorphs = 0;
+    MorphKey keys[MORPH_SLOTS];
+    int nbTrackKeys = 0;                      /* of the track's slots, those that hold a key */
+    std::vector<MorphLampAnswer> lampAnswers; /* as asked since the slots last changed, by the tags of ... */
+    long lampChecked = -1;                    /* ... that Scene::retags */
+    DeviceBuffer lampFlag;                    /* k_lampKeysDiffer's answer */
+    int nbDeviceMorphs = 0;                   /* requests served: through the two-key interface / for a track */
+    int nbDeviceTrackMorphs = 0;
 };
 /* The scene proper: what h2d_scene replaces and finalize_scene drops, with the arena it is resident in. */
 struct Scene
@@ -552,35 +571,46 @@ struct Scene
     }
     /* retagPrimitives has joined the materials' facts into the primitives' tags again */
     void retagged() { ++retags; }
-    /* the morph keys: none (the buffers stay for the next ones) / uploaded for nbKeys primitives */
+    /* the morph keys: every slot empty (the buffers stay for the next keys) / one slot empty / one slot packed for
+     * nbPrimitives primitives.  What was answered about lamps held for the slots as they were */
     void morphKeysDropped()
     {
-        morph.nbKeys = -1;
-        morph.keysDiffer.clear();
-        morph.lampChecked = -1;
-        morph.lampMoves = false;
+        for (MorphKey &key : morph.keys)
+            key.nbPrimitives = -1;
+        morph.nbTrackKeys = 0;
+        morph.lampAnswers.clear();
     }
-    void morphKeysSet(int nbKeys, std::vector<unsigned char> &keysDiffer)
+    void morphKeyDropped(int slot)
     {
-        morph.nbKeys = nbKeys;
-        morph.keysDiffer.swap(keysDiffer);
-        morph.lampChecked = -1;
+        if (slot < SOLR_MORPH_TRACK_MAX_KEYS && morph.keys[slot].nbPrimitives >= 0)
+            --morph.nbTrackKeys;
+        morph.keys[slot].nbPrimitives = -1;
+        morph.lampAnswers.clear();
     }
-    /* canMorphOne has asked the tags as they are now whether a lamp's keys differ */
-    void morphLampChecked(bool moves)
+    void morphKeySet(int slot, int nbPrimitives_)
     {
-        morph.lampMoves = moves;
+        morphKeyDropped(slot);
+        morph.keys[slot].nbPrimitives = nbPrimitives_;
+        if (slot < SOLR_MORPH_TRACK_MAX_KEYS)
+            ++morph.nbTrackKeys;
+    }
+    /* canMorphOne has asked the tags as they are now whether a lamp's rows differ between the two slots */
+    void morphLampNoted(int slotA, int slotB, bool moves)
+    {
+        if (morph.lampChecked != retags)
+            morph.lampAnswers.clear();
         morph.lampChecked = retags;
+        morph.lampAnswers.push_back({slotA, slotB, moves});
     }
-    /* morphPrimitivesOne has blended the keys into the primitives and refitted the lists (rotationQueued); walkHolds,
-     * landed: as for a rotation */
-    void morphServed(bool walkHolds, bool landed)
+    /* morphKeysOne has blended two keys into the primitives and refitted the lists (rotationQueued); walkHolds, landed: as
+     * for a rotation; track: asked through solr_hip_morph_between */
+    void morphServed(bool walkHolds, bool landed, bool track)
     {
         walkEncloses = walkHolds;
         if (landed)
         {
             arena.deviceAhead = true;
-            ++morph.nbDeviceMorphs;
+            ++(track ? morph.nbDeviceTrackMorphs : morph.nbDeviceMorphs);
         }
     }
     /* finalize_scene */
@@ -588,8 +618,10 @@ struct Scene
     {
         lists.dropStage(true);
         for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag, &rotation.edits,
-                                &morph.first, &morph.last})
+                                &morph.lampFlag})
             solreng::release(*b);
+        for (MorphKey &key : morph.keys)
+            solreng::release(key.planes);
         *this = Scene();
     }
 };
@@ -914,9 +946,11 @@ int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const f
 bool refitMovedScene(float viewDistance);
 void refreshExactList();
 /* solr_morph.hip: key-frame morphing on the device */
+/* (slots: MorphSlot; who: the entry point that asks) */
 int setMorphKeysOne(const Primitive *first, const Primitive *last, int nbPrimitives);
-bool canMorphOne(float weight, float viewDistance);
-int morphPrimitivesOne(float weight, float viewDistance);
+int setMorphTrackKeyOne(int slot, const Primitive *key, const int *rankOf, int nbPrimitives);
+bool canMorphOne(int slotA, int slotB, float weight, float viewDistance, const char *who);
+int morphKeysOne(int slotA, int slotB, float weight, float viewDistance, const char *who);
 /* solr_moves.hip: translation and lamp moves on the device */
 bool canTranslateOne(const float translation[3], float viewDistance);
 int translatePrimitivesOne(const float translation[3], float viewDistance);
@@ -966,6 +1000,13 @@ struct HaloDebt
 void launchPostProcess(const SceneInfo &sceneInfo, const PostProcessingInfo &ppInfo, int flight, hipStream_t stream, int firstRow,
                        int nbRows, unsigned char *bitmap, HaloDebt &debt);
 } // namespace solreng
+
+/* solr_morph.hip: k_packMorphKeys behind a plain launcher, as setMorphTrackKeyOne calls it (also what the test-only
+ * solr_hip_probe_pack_morph_key runs) */
+namespace solrmorph
+{
+void packMorphKeys(hipStream_t stream, const Primitive *key, const int *rankOf, int nbPrimitives, float4 *planes);
+} // namespace solrmorph
 
 /* solr_post.hip: the post-processing kernels of cudaRender (CRT:1057-1358) and the tile sort, behind plain launchers */
 namespace solrpost

@@ -614,21 +614,41 @@ int solr_hip_set_morph_keys(const Primitive *first, const Primitive *last, int n
     return status;
 }
 
+/* (every in-process device holds the scene and its own slots; 1 only when all of them took the key) */
+int solr_hip_set_morph_track_key(int slot, const Primitive *key, const int *rankOf, int nbPrimitives)
+{
+    int status = 1;
+    onEveryDevice([&](int) { status = setMorphTrackKeyOne(slot, key, rankOf, nbPrimitives) && status; });
+    return status;
+}
+
 /* (every in-process device holds the scene and the keys and morphs its own copy; 1 only when all of them did) */
-int solr_hip_morph_primitives(float weight, float viewDistance)
+static int morphOnEveryDevice(int slotA, int slotB, float weight, float viewDistance, const char *who)
 {
     /* as for a rotation: every resident copy must be able to follow before any of them moves */
     bool all = true;
-    onEveryDevice([&](int) { all = canMorphOne(weight, viewDistance) && all; });
+    onEveryDevice([&](int) { all = canMorphOne(slotA, slotB, weight, viewDistance, who) && all; });
     if (!all)
         return 0;
     int status = 1; /* 1: morphed on the device */
     onEveryDevice([&](int) {
-        const int mine = morphPrimitivesOne(weight, viewDistance);
+        const int mine = morphKeysOne(slotA, slotB, weight, viewDistance, who);
         if (mine != 1 && status == 1)
             status = mine;
     });
     return status;
+}
+
+int solr_hip_morph_primitives(float weight, float viewDistance)
+{
+    return morphOnEveryDevice(MORPH_SLOT_FIRST, MORPH_SLOT_LAST, weight, viewDistance, "solr_hip_morph_primitives");
+}
+
+int solr_hip_morph_between(int slotA, int slotB, float weight, float viewDistance)
+{
+    if (slotA < 0 || slotA >= SOLR_MORPH_TRACK_MAX_KEYS || slotB < 0 || slotB >= SOLR_MORPH_TRACK_MAX_KEYS)
+        return 0;
+    return morphOnEveryDevice(slotA, slotB, weight, viewDistance, "solr_hip_morph_between");
 }
 
 /* (every in-process device holds the scene and translates its own copy; 1 only when all of them did) */

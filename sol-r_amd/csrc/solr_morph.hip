@@ -1,14 +1,18 @@
 /*
- * solr_morph.hip - key-frame morphing of the MI355X rendering engine: solr_hip_set_morph_keys hands over the two key
- * frames of the resident scene, solr_hip_morph_primitives blends them into the resident primitives at any weight and
- * refits the node lists in the arena (engine.h Morph; the refit and what follows it: solr_rotation.hip refitMovedScene).
+ * solr_morph.hip - key-frame morphing of the MI355X rendering engine: solr_hip_set_morph_track_key hands over one key frame
+ * of the resident scene per slot (k_packMorphKeys packs it on the device), solr_hip_morph_between blends any two of them into
+ * the resident primitives at any weight and refits the node lists in the arena; solr_hip_set_morph_keys and
+ * solr_hip_morph_primitives are the same with two slots of their own (engine.h Morph; the refit and what follows it:
+ * solr_rotation.hip refitMovedScene).
  * Part of the engine's host side (engine.h); the boundary that calls into it is solr_hip.hip.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 
 #include "../../include/solr_hip.h"
+#include "device_pool.h"
 #include "rt_device.h"
 
 using namespace solrdev;
@@ -121,90 +125,211 @@ __global__ __launch_bounds__(256) void k_morphPrimitives(float4 *__restrict__ ar
     storeXyz(rows + ROW_N2, n2);
 }
 
-/* solr_hip_set_morph_keys on one engine: the keys re-packed into planes and uploaded; per primitive whether its keys differ
- * (a lamp must not move: the light table would have to follow).  Keys for another number of primitives than the resident
- * scene's are kept all the same - the request is what gets refused, like a rotation with flags for another scene */
+/* A key frame's records into its seven planes: lane i gathers the geometry of key[rankOf[i]] - the 21 floats p0 p1 p2 n0 n1 n2
+ * size at the head of a 128-byte, 16-byte aligned record, read as six 16-byte loads of which the last 12 bytes (type, index,
+ * materialId) are dropped - and stores seven float4 next to lane i - 1's.  The gather is the one access that is not
+ * coalesced (a record per lane, wherever its rank lies); it is paid once per key, and every frame blended from the key
+ * afterwards reads the planes lane next to lane.  rankOf == nullptr: the records are in the resident order already. */
+__global__ __launch_bounds__(256) void k_packMorphKeys(const Primitive *__restrict__ key, const int *__restrict__ rankOf,
+                                                       int nbPrimitives, float4 *__restrict__ planes)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbPrimitives)
+        return;
+    const size_t plane = (size_t)nbPrimitives;
+    const int rank = rankOf ? rankOf[i] : i;
+    const float4 *record = (const float4 *)(key + rank);
+    const float4 a = record[0], b = record[1], c = record[2], d = record[3], e = record[4], f = record[5];
+    planes[MORPH_KEY_P0 * plane + i] = make_float4(a.x, a.y, a.z, 0.f);
+    planes[MORPH_KEY_P1 * plane + i] = make_float4(a.w, b.x, b.y, 0.f);
+    planes[MORPH_KEY_P2 * plane + i] = make_float4(b.z, b.w, c.x, 0.f);
+    planes[MORPH_KEY_N0 * plane + i] = make_float4(c.y, c.z, c.w, 0.f);
+    planes[MORPH_KEY_N1 * plane + i] = make_float4(d.x, d.y, d.z, 0.f);
+    planes[MORPH_KEY_N2 * plane + i] = make_float4(d.w, e.x, e.y, 0.f);
+    planes[MORPH_KEY_SIZE * plane + i] = make_float4(e.z, e.w, f.x, 0.f);
+}
+static_assert(offsetof(Primitive, p0) == 0 && offsetof(Primitive, p1) == 12 && offsetof(Primitive, p2) == 24 &&
+                  offsetof(Primitive, n0) == 36 && offsetof(Primitive, n1) == 48 && offsetof(Primitive, n2) == 60 &&
+                  offsetof(Primitive, size) == 72 && sizeof(Primitive) == 128 && alignof(Primitive) == 16,
+              "k_packMorphKeys reads a record's geometry as six float4");
+
+/* The lamp rule: does a primitive that lights the scene - by the tag the arena holds for it - have rows that differ, in any
+ * bit, between two keys?  Such a pair is not blended here: the light table would have to follow. */
+__global__ __launch_bounds__(256) void k_lampKeysDiffer(const float4 *__restrict__ arena, unsigned offPrims, int nbPrimitives,
+                                                        const float4 *__restrict__ keyA, const float4 *__restrict__ keyB,
+                                                        int *__restrict__ differ)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbPrimitives)
+        return;
+    if (!(__float_as_int(arena[offPrims + (size_t)PRIM_ROWS * i + ROW_P0_TYPE].w) & PRIM_EMISSIVE))
+        return;
+    const size_t plane = (size_t)nbPrimitives;
+    bool same = true;
+    for (int row = 0; row < MORPH_KEY_ROWS; ++row)
+    {
+        const float4 a = keyA[row * plane + i], b = keyB[row * plane + i];
+        same = same && __float_as_int(a.x) == __float_as_int(b.x) && __float_as_int(a.y) == __float_as_int(b.y) &&
+               __float_as_int(a.z) == __float_as_int(b.z) && __float_as_int(a.w) == __float_as_int(b.w);
+    }
+    if (!same)
+        *differ = 1; /* (every lane that writes, writes the same word) */
+}
+
+/* one slot's key on one engine: the records and the ranks go up with one copy each, into scratch that is given back before
+ * this returns, and k_packMorphKeys makes the planes.  The slot holds no key until they are in place; an allocation that
+ * fails declines the key (no error state: the caller takes the host route) */
+static int packKeyOne(int slot, const Primitive *key, const int *rankOf, int nbPrimitives)
+{
+    g.scene.morphKeyDropped(slot);
+    quiesce();
+    HIPCHECK(hipSetDevice(g.device));
+    if (!ok())
+        return 0;
+    const size_t n = (size_t)nbPrimitives;
+    DeviceBuffer &planes = g.scene.morph.keys[slot].planes;
+    const size_t bytes = (size_t)MORPH_KEY_ROWS * n * sizeof(float4);
+    if (!planes.ptr || planes.bytes < bytes)
+    {
+        release(planes);
+        if (hipMalloc(&planes.ptr, bytes) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            planes.ptr = nullptr;
+            return 0;
+        }
+        planes.bytes = bytes;
+    }
+    SolrScratchPool &pool = solrScratchPool();
+    std::lock_guard<std::mutex> oneBuild(pool.busy);
+    pool.begin(n * (sizeof(Primitive) + sizeof(int)) + 1024);
+    void *own[2] = {nullptr, nullptr};
+    auto scratch = [&](int which, size_t size) -> void * {
+        void *p = pool.take(size);
+        if (!p && hipMalloc(&own[which], size) == hipSuccess)
+            p = own[which];
+        return p;
+    };
+    Primitive *records = (Primitive *)scratch(0, n * sizeof(Primitive));
+    int *ranks = rankOf ? (int *)scratch(1, n * sizeof(int)) : nullptr;
+    const bool fits = records && (ranks || !rankOf);
+    if (fits)
+    {
+        /* pageable sources: the copies are complete for the caller when the stream has been waited for */
+        HIPCHECK(hipMemcpyAsync(records, key, n * sizeof(Primitive), hipMemcpyHostToDevice, sceneStream()));
+        if (ranks)
+            HIPCHECK(hipMemcpyAsync(ranks, rankOf, n * sizeof(int), hipMemcpyHostToDevice, sceneStream()));
+        if (ok())
+            solrmorph::packMorphKeys(sceneStream(), records, ranks, nbPrimitives, (float4 *)planes.ptr);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(sceneStream()));
+    }
+    else
+        (void)hipGetLastError();
+    pool.end();
+    for (void *p : own)
+        if (p)
+            (void)hipFree(p);
+    if (!fits || !ok())
+        return 0;
+    g.scene.morphKeySet(slot, nbPrimitives);
+    return 1;
+}
+
+/* solr_hip_set_morph_keys on one engine: its two slots, the records in the resident order already.  Keys for another
+ * number of primitives than the resident scene's are kept all the same - the request is what gets refused, like a rotation
+ * with flags for another scene */
 int setMorphKeysOne(const Primitive *first, const Primitive *last, int nbPrimitives)
 {
     if (!ready("solr_hip_set_morph_keys"))
         return 0;
-    g.scene.morphKeysDropped();
+    g.scene.morphKeyDropped(MORPH_SLOT_FIRST);
+    g.scene.morphKeyDropped(MORPH_SLOT_LAST);
     if (!first || !last || nbPrimitives <= 0)
         return 0;
-    quiesce();
-    HIPCHECK(hipSetDevice(g.device));
-    const size_t n = (size_t)nbPrimitives;
-    std::vector<float4> planes[2];
-    std::vector<unsigned char> differ(n, 0);
-    for (int key = 0; key < 2; ++key)
-    {
-        const Primitive *p = key ? last : first;
-        std::vector<float4> &out = planes[key];
-        out.resize(MORPH_KEY_ROWS * n);
-        for (size_t i = 0; i < n; ++i)
-        {
-            out[MORPH_KEY_P0 * n + i] = make_float4(p[i].p0.x, p[i].p0.y, p[i].p0.z, 0.f);
-            out[MORPH_KEY_P1 * n + i] = make_float4(p[i].p1.x, p[i].p1.y, p[i].p1.z, 0.f);
-            out[MORPH_KEY_P2 * n + i] = make_float4(p[i].p2.x, p[i].p2.y, p[i].p2.z, 0.f);
-            out[MORPH_KEY_N0 * n + i] = make_float4(p[i].n0.x, p[i].n0.y, p[i].n0.z, 0.f);
-            out[MORPH_KEY_N1 * n + i] = make_float4(p[i].n1.x, p[i].n1.y, p[i].n1.z, 0.f);
-            out[MORPH_KEY_N2 * n + i] = make_float4(p[i].n2.x, p[i].n2.y, p[i].n2.z, 0.f);
-            out[MORPH_KEY_SIZE * n + i] = make_float4(p[i].size.x, p[i].size.y, p[i].size.z, 0.f);
-        }
-    }
-    for (size_t i = 0; i < n; ++i)
-        for (int row = 0; row < MORPH_KEY_ROWS && !differ[i]; ++row)
-            differ[i] = memcmp(&planes[0][row * n + i], &planes[1][row * n + i], sizeof(float4)) != 0;
-    upload(g.scene.morph.first, planes[0]);
-    upload(g.scene.morph.last, planes[1]);
-    if (!ok())
-        return 0;
-    g.scene.morphKeysSet(nbPrimitives, differ);
-    return 1;
+    return packKeyOne(MORPH_SLOT_FIRST, first, nullptr, nbPrimitives) && packKeyOne(MORPH_SLOT_LAST, last, nullptr, nbPrimitives);
 }
 
-/* does a primitive that lights the scene have keys that differ?  By the tags as they are now (a change of materials
- * retags the primitives: asked again then) */
-static bool lampWouldMove()
+/* solr_hip_set_morph_track_key on one engine: what cannot be a key of the resident scene is refused before anything is
+ * launched, and leaves the slots as they are */
+int setMorphTrackKeyOne(int slot, const Primitive *key, const int *rankOf, int nbPrimitives)
 {
-    const Morph &m = g.scene.morph;
-    if (m.lampChecked == g.scene.retags)
-        return m.lampMoves;
-    bool moves = false;
-    const size_t n = std::min(m.keysDiffer.size(), g.scene.hostPrims.size() / PRIM_ROWS);
-    for (size_t i = 0; i < n && !moves; ++i)
-        moves = m.keysDiffer[i] && (bitsi(g.scene.hostPrims[PRIM_ROWS * i + ROW_P0_TYPE].w) & PRIM_EMISSIVE);
-    g.scene.morphLampChecked(moves);
-    return moves;
+    if (!ready("solr_hip_set_morph_track_key"))
+        return 0;
+    if (slot < 0 || slot >= SOLR_MORPH_TRACK_MAX_KEYS || !key || !rankOf || nbPrimitives <= 0 || nbPrimitives != g.scene.nbPrimitives)
+        return 0;
+    for (int i = 0; i < nbPrimitives; ++i)
+        if (rankOf[i] < 0 || rankOf[i] >= nbPrimitives)
+            return 0;
+    return packKeyOne(slot, key, rankOf, nbPrimitives);
 }
 
-/* can this engine morph its resident scene?  (what canRotateOne asks, and the keys; changes nothing but the refit plan) */
-bool canMorphOne(float weight, float viewDistance)
+/* does a primitive that lights the scene have rows that differ between the two slots (both hold keys of the resident
+ * scene)?  By the tags as they are now (a change of materials retags the primitives: asked again then), once per ordered
+ * pair of slots.  Asked on the device, where the planes are: a host-side answer would need a host copy of every key */
+static bool lampWouldMove(int slotA, int slotB)
+{
+    Morph &m = g.scene.morph;
+    if (m.lampChecked == g.scene.retags)
+        for (const MorphLampAnswer &answer : m.lampAnswers)
+            if (answer.slotA == slotA && answer.slotB == slotB)
+                return answer.moves;
+    if (slotA == slotB)
+    {
+        g.scene.morphLampNoted(slotA, slotB, false);
+        return false;
+    }
+    HIPCHECK(hipSetDevice(g.device));
+    flushGeometry(); /* the tags, where a host image has changed */
+    reserve(m.lampFlag, sizeof(int));
+    if (!ok() || !g.scene.arena.geometry.ptr)
+        return true;
+    quiesce();
+    int differ = 0;
+    HIPCHECK(hipMemsetAsync(m.lampFlag.ptr, 0, sizeof(int), sceneStream()));
+    hipLaunchKernelGGL(k_lampKeysDiffer, dim3((unsigned)((g.scene.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
+                       (const float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
+                       (const float4 *)m.keys[slotA].planes.ptr, (const float4 *)m.keys[slotB].planes.ptr, (int *)m.lampFlag.ptr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(&differ, m.lampFlag.ptr, sizeof(int), hipMemcpyDeviceToHost, sceneStream()));
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
+    if (!ok())
+        return true;
+    g.scene.morphLampNoted(slotA, slotB, differ != 0);
+    return differ != 0;
+}
+
+/* can this engine blend these two slots into its resident scene?  (what canRotateOne asks, and the keys; changes nothing
+ * but the refit plan and what is known about lamps) */
+bool canMorphOne(int slotA, int slotB, float weight, float viewDistance, const char *who)
 {
     static const float none[3] = {0.f, 0.f, 0.f};
-    if (!canRotateOne(none, none, none, viewDistance, "solr_hip_morph_primitives"))
+    if (!canRotateOne(none, none, none, viewDistance, who))
+        return false;
+    if (slotA < 0 || slotA >= MORPH_SLOTS || slotB < 0 || slotB >= MORPH_SLOTS)
         return false;
     const Morph &m = g.scene.morph;
+    const MorphKey &a = m.keys[slotA], &b = m.keys[slotB];
     /* (a lamp that was moved on the device, solr_moves.hip: the blend would put its p0 back at the keys' place and leave
      * its light record where the move put it - the host route makes the record from p0 again; primitives that were set
      * anew on the device, solr_edits.hip: the blend would leave their texture coordinates and movable flags behind) */
-    if (m.nbKeys != g.scene.nbPrimitives || !m.first.ptr || !m.last.ptr || !std::isfinite(weight) || lampWouldMove() ||
-        g.scene.rotation.lampMoved || g.scene.rotation.edited)
+    if (a.nbPrimitives != g.scene.nbPrimitives || b.nbPrimitives != g.scene.nbPrimitives || !a.planes.ptr || !b.planes.ptr ||
+        !std::isfinite(weight) || g.scene.rotation.lampMoved || g.scene.rotation.edited || lampWouldMove(slotA, slotB))
     {
         if (getenv("SOLR_HIP_DEBUG_TREE"))
-            fprintf(stderr, "solr_hip_morph_primitives refused: keys for %d of %d primitives, weight %g, a lamp moved here: %d\n",
-                    m.nbKeys, g.scene.nbPrimitives, weight, (int)g.scene.rotation.lampMoved);
+            fprintf(stderr, "%s refused: keys for %d and %d of %d primitives, weight %g, a lamp moved here: %d\n", who, a.nbPrimitives,
+                    b.nbPrimitives, g.scene.nbPrimitives, weight, (int)g.scene.rotation.lampMoved);
         return false;
     }
     return true;
 }
 
-/* Extension: GPUKernel::morphFrame + h2d_scene on the resident scene, see k_morphPrimitives.  Returns 1 when the arena now
+/* Extension: GPUKernel::morphBetween + h2d_scene on the resident scene, see k_morphPrimitives.  Returns 1 when the arena now
  * holds the morphed scene, 0 when the request cannot be served here and the caller has to take the host route (nothing
  * was changed). */
-int morphPrimitivesOne(float weight, float viewDistance)
+int morphKeysOne(int slotA, int slotB, float weight, float viewDistance, const char *who)
 {
-    if (!canMorphOne(weight, viewDistance))
+    if (!canMorphOne(slotA, slotB, weight, viewDistance, who))
         return 0;
     HIPCHECK(hipSetDevice(g.device));
     flushGeometry();
@@ -213,17 +338,37 @@ int morphPrimitivesOne(float weight, float viewDistance)
     quiesce();
     hipLaunchKernelGGL(k_morphPrimitives, dim3((unsigned)((g.scene.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
-                       (const float4 *)g.scene.morph.first.ptr, (const float4 *)g.scene.morph.last.ptr, weight);
+                       (const float4 *)g.scene.morph.keys[slotA].planes.ptr, (const float4 *)g.scene.morph.keys[slotB].planes.ptr,
+                       weight);
     const bool walkHolds = refitMovedScene(viewDistance);
-    g.scene.morphServed(walkHolds, ok());
+    g.scene.morphServed(walkHolds, ok(), slotA < SOLR_MORPH_TRACK_MAX_KEYS);
     return ok() ? 1 : 0;
 }
 
 } // namespace solreng
 
+namespace solrmorph
+{
+void packMorphKeys(hipStream_t stream, const Primitive *key, const int *rankOf, int nbPrimitives, float4 *planes)
+{
+    hipLaunchKernelGGL(solreng::k_packMorphKeys, dim3((unsigned)((nbPrimitives + 255) / 256)), dim3(256), 0, stream, key, rankOf,
+                       nbPrimitives, planes);
+}
+} // namespace solrmorph
+
 extern "C" {
 int solr_hip_device_morphs(void)
 {
     return g.scene.morph.nbDeviceMorphs;
+}
+
+int solr_hip_device_track_morphs(void)
+{
+    return g.scene.morph.nbDeviceTrackMorphs;
+}
+
+int solr_hip_morph_track_keys(void)
+{
+    return g.scene.morph.nbTrackKeys;
 }
 } // extern "C"

@@ -4,7 +4,8 @@
  * (tests/test_engine_probes_gpu.py; the reference side is oracle/ref_probes.cl around RayTracer.cl).  No rendering
  * code lives here: every kernel calls the functions of rt_device.h that k_standardRenderer is built from, in the
  * instantiations the renderer launches.  At the end: the list builders (list_builders.cpp, solr_lists.hip) on a node list
- * of the caller's (tests/test_list_builder_cases.py, tests/test_list_builders_device_gpu.py).  gfx950 only.
+ * of the caller's (tests/test_list_builder_cases.py, tests/test_list_builders_device_gpu.py), and the pack kernel of the key-frame
+ * tracks (include/solr_hip_probes_morph.h, tests/test_track_gpu.py).  gfx950 only.
  */
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,7 @@
 
 #include "../../include/solr_hip.h"
 #include "../../include/solr_hip_probes.h"
+#include "../../include/solr_hip_probes_morph.h"
 #include "rt_device.h"
 #include "renderer.h"
 #include "list_builders.h"
@@ -42,6 +44,12 @@ namespace solrpost
 void orderTiles(hipStream_t stream, const unsigned *cost, unsigned *snapshot, unsigned *order, int nbTiles,
                 volatile unsigned *hostStats, int flights, const BandCuts &cuts);
 } // namespace solrpost
+
+/* solr_morph.hip: k_packMorphKeys behind its launcher, as solr_hip_set_morph_track_key calls it */
+namespace solrmorph
+{
+void packMorphKeys(hipStream_t stream, const Primitive *key, const int *rankOf, int nbPrimitives, float4 *planes);
+} // namespace solrmorph
 
 namespace
 {
@@ -884,5 +892,29 @@ int solr_hip_probe_prune_list(int route, int n, const float *rows, const int *st
     memcpy(outStart, first.data(), 4 * (size_t)count);
     memcpy(outOrigin, origin.data(), 4 * (size_t)count);
     return count;
+}
+
+int solr_hip_probe_pack_morph_key(const Primitive *key, const int *rankOf, int n, float *planes)
+{
+    bool inRange = key && rankOf && planes && n > 0;
+    for (int i = 0; inRange && i < n; ++i)
+        inRange = rankOf[i] >= 0 && rankOf[i] < n;
+    if (!inRange)
+    {
+        solrprobe::fail(-1, "solr_hip_probe_pack_morph_key: n records, n ranks within them and room for 7 * n float4");
+        return -1;
+    }
+    OnEngineDevice device;
+    if (!device.fine)
+        return -1;
+    Arrays a;
+    const Primitive *dKey = a.in(key, (size_t)n);
+    const int *dRankOf = a.in(rankOf, (size_t)n);
+    memset(planes, 0xff, (size_t)7 * n * sizeof(float4)); /* what the kernel does not write shows */
+    float4 *dPlanes = a.out((float4 *)planes, (size_t)7 * n);
+    if (a.failed)
+        return -1;
+    solrmorph::packMorphKeys(0, dKey, dRankOf, n, dPlanes);
+    return a.finish(0) ? 0 : -1;
 }
 }

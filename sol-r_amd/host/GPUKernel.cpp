@@ -1092,9 +1092,9 @@ void GPUKernel::morphPrimitives()
     }
 }
 
-bool GPUKernel::morphKeysMatch()
+bool GPUKernel::morphKeysMatch(unsigned int frameA, unsigned int frameB)
 {
-    PrimitiveContainer &first = m_frames[0].primitives, &last = m_frames[m_nbFrames - 1].primitives;
+    PrimitiveContainer &first = m_frames[frameA].primitives, &last = m_frames[frameB].primitives;
     PrimitiveContainer &current = m_frames[m_frame].primitives;
     if (first.size() != current.size() || last.size() != current.size())
         return false;
@@ -1106,9 +1106,9 @@ bool GPUKernel::morphKeysMatch()
 }
 
 /* morphPrimitives' statements (reference: GPUKernel.cpp:1530-1566) with r = weight, on the primitives the frame has */
-void GPUKernel::morphPrimitivesOnly(float weight)
+void GPUKernel::morphPrimitivesOnly(unsigned int frameA, unsigned int frameB, float weight)
 {
-    PrimitiveContainer &first = m_frames[0].primitives, &last = m_frames[m_nbFrames - 1].primitives;
+    PrimitiveContainer &first = m_frames[frameA].primitives, &last = m_frames[frameB].primitives;
     std::vector<unsigned int> ids;
     ids.reserve(m_frames[m_frame].primitives.size());
     for (const auto &entry : m_frames[m_frame].primitives)
@@ -1131,87 +1131,140 @@ void GPUKernel::morphPrimitivesOnly(float weight)
     }
 }
 
-bool GPUKernel::morphKeys(std::vector<Primitive> &first, std::vector<Primitive> &last)
+bool GPUKernel::morphKey(unsigned int frame, bool compare, std::vector<Primitive> &key)
 {
-    PrimitiveContainer &current = m_frames[m_frame].primitives;
-    if (m_hPrimitives.size() != current.size())
-        return false; /* not the frame the flattened arrays describe */
-    std::vector<unsigned int> ids;
-    std::vector<const CPUPrimitive *> keys[2];
-    ids.reserve(current.size());
-    for (const auto &entry : current)
-        ids.push_back(entry.first);
-    for (int key = 0; key < 2; ++key)
+    /* (read from m_frames directly: handing a key over does not touch the store) */
+    PrimitiveContainer &current = m_frames[m_frame].primitives, &source = m_frames[frame].primitives;
+    if (source.size() != current.size())
+        return false;
+    key.assign(source.size(), Primitive());
+    size_t rank = 0;
+    PrimitiveContainer::iterator it = current.begin();
+    for (PrimitiveContainer::iterator itKey = source.begin(); itKey != source.end() && it != current.end(); ++itKey, ++it, ++rank)
     {
-        keys[key].reserve(current.size());
-        for (const auto &entry : m_frames[key ? m_nbFrames - 1 : 0].primitives)
-            keys[key].push_back(&entry.second);
-        if (keys[key].size() != ids.size())
+        const CPUPrimitive &k = itKey->second, &p = it->second;
+        if (compare && (p.materialId != k.materialId || p.movable != k.movable || memcmp(&p.vt0, &k.vt0, sizeof(vec2f)) != 0 ||
+                        memcmp(&p.vt1, &k.vt1, sizeof(vec2f)) != 0 || memcmp(&p.vt2, &k.vt2, sizeof(vec2f)) != 0))
             return false;
-    }
-    first.assign(m_hPrimitives.size(), Primitive());
-    last.assign(m_hPrimitives.size(), Primitive());
-    for (size_t i = 0; i < m_hPrimitives.size(); ++i)
-    {
-        const unsigned int id = (unsigned int)m_hPrimitives[i].index;
-        const size_t rank = std::lower_bound(ids.begin(), ids.end(), id) - ids.begin();
-        const CPUPrimitive *p = current.lookup(id);
-        if (rank >= ids.size() || ids[rank] != id || !p)
-            return false;
-        const CPUPrimitive &a = *keys[0][rank];
-        if (p->materialId != a.materialId || p->movable != a.movable || memcmp(&p->vt0, &a.vt0, sizeof(vec2f)) != 0 ||
-            memcmp(&p->vt1, &a.vt1, sizeof(vec2f)) != 0 || memcmp(&p->vt2, &a.vt2, sizeof(vec2f)) != 0)
-            return false;
-        for (int key = 0; key < 2; ++key)
-        {
-            const CPUPrimitive &k = *keys[key][rank];
-            Primitive &out = key ? last[i] : first[i];
-            memset(&out, 0, sizeof(out));
-            out.index = (int)id;
-            out.type = k.type;
-            out.p0 = k.p0;
-            out.p1 = k.p1;
-            out.p2 = k.p2;
-            out.n0 = k.n0;
-            out.n1 = k.n1;
-            out.n2 = k.n2;
-            out.size = k.size;
-        }
+        Primitive &out = key[rank];
+        memset(&out, 0, sizeof(out));
+        out.index = (int)itKey->first;
+        out.type = k.type;
+        out.p0 = k.p0;
+        out.p1 = k.p1;
+        out.p2 = k.p2;
+        out.n0 = k.n0;
+        out.n1 = k.n1;
+        out.n2 = k.n2;
+        out.size = k.size;
     }
     return true;
 }
 
-bool GPUKernel::deviceMorphFrame(float weight)
+const std::vector<int> *GPUKernel::residentRanks()
 {
-    if (!m_resident.hasMorphKeys(m_frame, m_nbFrames))
+    PrimitiveContainer &current = m_frames[m_frame].primitives;
+    if (m_hPrimitives.size() != current.size())
+        return nullptr; /* not the frame the flattened arrays describe */
+    if (m_rankOfUpload == m_resident.uploads && m_rankOf.size() == m_hPrimitives.size())
+        return &m_rankOf;
+    /* the flattened order of the resident scene: that of the upload, which the replays of syncHost keep */
+    std::vector<unsigned int> ids;
+    ids.reserve(current.size());
+    for (const auto &entry : current)
+        ids.push_back(entry.first);
+    m_rankOf.assign(m_hPrimitives.size(), -1);
+    m_rankOfUpload = 0;
+    for (size_t i = 0; i < m_hPrimitives.size(); ++i)
     {
-        /* the first morph after an upload: the key frames go to the engine, in the order of the resident primitives */
-        std::vector<Primitive> first, last;
-        if (!morphKeys(first, last) || !deviceSetMorphKeys(first, last))
-            return false;
-        m_resident.morphKeysTaken(m_frame, m_nbFrames);
+        const unsigned int id = (unsigned int)m_hPrimitives[i].index;
+        const size_t rank = std::lower_bound(ids.begin(), ids.end(), id) - ids.begin();
+        if (rank >= ids.size() || ids[rank] != id)
+            return nullptr;
+        m_rankOf[i] = (int)rank;
     }
-    return deviceMorphPrimitives(weight);
+    m_rankOfUpload = m_resident.uploads;
+    return &m_rankOf;
+}
+
+bool GPUKernel::morphKeys(unsigned int frameA, unsigned int frameB, std::vector<Primitive> &first, std::vector<Primitive> &last)
+{
+    const std::vector<int> *rankOf = residentRanks();
+    std::vector<Primitive> keys[2];
+    if (!rankOf || !morphKey(frameA, true, keys[0]) || !morphKey(frameB, false, keys[1]))
+        return false;
+    first.resize(rankOf->size());
+    last.resize(rankOf->size());
+    for (size_t i = 0; i < rankOf->size(); ++i)
+    {
+        first[i] = keys[0][(size_t)(*rankOf)[i]];
+        last[i] = keys[1][(size_t)(*rankOf)[i]];
+    }
+    return true;
+}
+
+bool GPUKernel::deviceMorphKeyFrames(unsigned int frameA, unsigned int frameB, float weight, bool track)
+{
+    if (!track)
+    {
+        if (!m_resident.holdsPairKeys(frameA, frameB))
+        {
+            /* the first morph after an upload: the key frames go to the engine, in the order of the resident primitives */
+            std::vector<Primitive> first, last;
+            if (!morphKeys(frameA, frameB, first, last) || !deviceSetMorphKeys(first, last))
+                return false;
+            m_resident.pairKeysTaken(frameA, frameB);
+        }
+        return deviceMorphPrimitives(weight);
+    }
+    if (frameA >= SOLR_MORPH_TRACK_MAX_KEYS || frameB >= SOLR_MORPH_TRACK_MAX_KEYS)
+        return false; /* the engine has no slot for it */
+    for (unsigned int frame : {frameA, frameB})
+        if (!m_resident.holdsTrackKey(frame))
+        {
+            /* the first request after an upload that names this key frame: it goes to the engine as it lies in the store,
+             * with the ranks of the resident primitives.  Every key is compared: it may be the next request's first */
+            std::vector<Primitive> key;
+            const std::vector<int> *rankOf = residentRanks();
+            if (!rankOf || !morphKey(frame, true, key) || !deviceSetMorphTrackKey(frame, key, *rankOf))
+                return false;
+            m_resident.trackKeyTaken(frame);
+        }
+    return deviceMorphBetween(frameA, frameB, weight);
 }
 
 int GPUKernel::morphFrame(float weight)
 {
-    if (m_nbFrames < 3 || m_frame == 0 || m_frame + 1 >= m_nbFrames || !std::isfinite(weight))
+    if (m_nbFrames < 3 || m_frame == 0 || m_frame + 1 >= m_nbFrames)
+        return -1;
+    return morphKeyFrames(0, m_nbFrames - 1, weight, false);
+}
+
+int GPUKernel::morphBetween(unsigned int frameA, unsigned int frameB, float weight)
+{
+    return morphKeyFrames(frameA, frameB, weight, true);
+}
+
+int GPUKernel::morphKeyFrames(unsigned int frameA, unsigned int frameB, float weight, bool track)
+{
+    /* (the stage must not be a key: the blend would overwrite what the next request blends from) */
+    if (frameA >= m_nbFrames || frameB >= m_nbFrames || frameA == m_frame || frameB == m_frame || !std::isfinite(weight))
         return -1;
     /* the scene the device holds is the one the host holds (plus what is pending): the frames were compared when the
      * engine got its keys, and nothing has changed the store since */
     const bool resident = m_resident.offers(m_frame);
-    const bool compared = resident && m_resident.hasMorphKeys(m_frame, m_nbFrames);
-    if (!compared && !morphKeysMatch())
+    const bool compared = resident && (track ? m_resident.holdsTrackKey(frameA) && m_resident.holdsTrackKey(frameB)
+                                             : m_resident.holdsPairKeys(frameA, frameB));
+    if (!compared && !morphKeysMatch(frameA, frameB))
         return -1;
     /* (a lamp that was moved over there: a morph there would put it back at its keys' place and leave its light record
      * behind, so such a morph is not offered to the engine - which would decline it, after the keys were handed over for
      * nothing - and the host route serves it.  Nor behind primitives that were set anew over there: the blend would
      * leave their texture coordinates and movable flags as the edit set them, where the host loop takes the first key's) */
-    if (resident && !m_resident.lampMoved && !m_resident.edited && deviceMorphFrame(weight))
+    if (resident && !m_resident.lampMoved && !m_resident.edited && deviceMorphKeyFrames(frameA, frameB, weight, track))
     {
         /* every primitive has been set anew: what was pending before is superseded (no lamp move is among it) */
-        m_resident.morphServed(weight);
+        m_resident.morphServed(frameA, frameB, weight);
         return 0;
     }
     ensureLevels(); /* from the primitives the tree was built with */
@@ -1219,7 +1272,7 @@ int GPUKernel::morphFrame(float weight)
      * from it when the frame is flattened) */
     m_resident.clear();
     Frame &f = frame();
-    morphPrimitivesOnly(weight);
+    morphPrimitivesOnly(frameA, frameB, weight);
     refitBoxes(f);
     compactBoxes(false);
     return 0;
@@ -1360,7 +1413,7 @@ void GPUKernel::syncHost()
     /* the morph first, always replayed: what the engine hands back (primitivesFromDevice) carries neither sizes
      * nor the primitives a rotation leaves alone */
     if (pending.morphPending)
-        morphPrimitivesOnly(pending.pendingMorphWeight);
+        morphPrimitivesOnly(pending.pendingMorphKeys[0], pending.pendingMorphKeys[1], pending.pendingMorphWeight);
     /* a handful of rotations and translations is replayed (4 ms each for 100 k primitives); a long animation is
      * fetched, and so is one whose moves were not all recorded.  A journal that holds an edit is always replayed: what
      * is fetched carries neither sizes nor texture coordinates, and not the primitives the store believes unmovable

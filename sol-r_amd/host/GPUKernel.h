@@ -306,7 +306,10 @@ struct ResidentScene
     unsigned long uploads = 0;         /* how often the scene was uploaded: what was made from the flattened order is as old as that */
     bool lampMoved = false;            /* a lamp was moved over there since the upload (morphFrame) */
     bool edited = false;               /* primitives were set anew over there since the upload (morphFrame) */
-    long morphKeysFrame = -1, morphKeysNbFrames = -1; /* the engine's morph keys are for that frame of that many, -1: it has none */
+    /* the frames the engine holds as keys of that scene since the upload: in the slots of a track (morphBetween; the slot is
+     * the frame's number), and the two of its two-key interface (morphFrame; -1: it has none) */
+    std::vector<unsigned int> trackKeys;
+    long pairKeys[2] = {-1, -1};
     bool buildingLevels = false; /* the lazy build of the level maps reads the store as it is: what is pending stays pending */
     /* the journal: the moves served over there since the upload - or since the morph that superseded what was before
      * it -, in order, up to the cap; the rotations among them; per kind those beyond the cap */
@@ -325,6 +328,7 @@ struct ResidentScene
     static constexpr size_t MAX_JOURNALLED_EDIT_RECORDS = size_t(1) << 20;
     size_t journalEditRecords = 0;
     bool morphPending = false;
+    unsigned int pendingMorphKeys[2] = {0, 0}; /* the two key frames of the pending morph */
     float pendingMorphWeight = 0.f;
 
     /* The one offer rule: a move on frame `f` of the store may be offered to the engine when the scene over there was
@@ -336,7 +340,8 @@ struct ResidentScene
     }
     /* ... and a batch of edits only while the journal records: an edit is never merely counted */
     bool recordsEdits() const { return journal.size() < MAX_RECORDED_MOVES; }
-    bool hasMorphKeys(unsigned int f, unsigned int n) const { return morphKeysFrame == (long)f && morphKeysNbFrames == (long)n; }
+    bool holdsTrackKey(unsigned int f) const { return std::find(trackKeys.begin(), trackKeys.end(), f) != trackKeys.end(); }
+    bool holdsPairKeys(unsigned int a, unsigned int b) const { return pairKeys[0] == (long)a && pairKeys[1] == (long)b; }
     size_t nbUnrecorded() const { return std::accumulate(unrecorded, unrecorded + Move::NB_KINDS, (size_t)0); }
     size_t nbPendingMoves() const { return journal.size() + nbUnrecorded(); }
     size_t nbPendingRotations() const { return journalRotations + unrecorded[Move::ROTATION]; }
@@ -362,7 +367,8 @@ struct ResidentScene
     {
         primitivesTransfered = true;
         touched = false;
-        morphKeysFrame = morphKeysNbFrames = -1;
+        trackKeys.clear();
+        pairKeys[0] = pairKeys[1] = -1;
         frame = (long)f;
         lampMoved = false;
         edited = false;
@@ -371,7 +377,8 @@ struct ResidentScene
     void setTransfered(bool value) { primitivesTransfered = value; }
     /* the scene store was accessed (GPUKernel::frame): the fast path ends until the next upload */
     void touch() { touched = true; }
-    void morphKeysTaken(unsigned int f, unsigned int n) { morphKeysFrame = (long)f, morphKeysNbFrames = (long)n; }
+    void trackKeyTaken(unsigned int f) { trackKeys.push_back(f); }
+    void pairKeysTaken(unsigned int a, unsigned int b) { pairKeys[0] = (long)a, pairKeys[1] = (long)b; }
     /* the engine has served `move`: into the journal, or past the cap into the counts */
     void record(const Move &move)
     {
@@ -405,11 +412,12 @@ struct ResidentScene
         journalEditRecords = 0;
         morphPending = false;
     }
-    /* ... or over there, by a morph at that weight: it supersedes what was pending before it */
-    void morphServed(float weight)
+    /* ... or over there, by a morph of those two key frames at that weight: it supersedes what was pending before it */
+    void morphServed(unsigned int frameA, unsigned int frameB, float weight)
     {
         clear();
         morphPending = true;
+        pendingMorphKeys[0] = frameA, pendingMorphKeys[1] = frameB;
         pendingMorphWeight = weight;
     }
     /* syncHost: what is pending is handed over - the record as it was, its journal moved out - and the record is caught up */
@@ -635,10 +643,19 @@ public:
      * place by morphPrimitives' statements with r = weight (first + r * (last - first), setPrimitive,
      * setPrimitiveNormals, the first key's texture coordinates, material and movable flag), the boxes refitted in the
      * shape they have, compactBoxes(false).  An engine that keeps the scene resident may blend it there
-     * (deviceMorphFrame); the host copy then lags behind by that morph (pendingMorph) and the rotations after it, and
+     * (deviceMorphKeyFrames); the host copy then lags behind by that morph (pendingMorph) and the rotations after it, and
      * syncHost() catches it up.  Returns 0 when done, -1 when the request cannot be served (fewer than three frames, the
      * current frame is a key frame, counts or types differ, a weight that is not finite): nothing changed. */
     int morphFrame(float weight);
+    /* The same with any two frames as the keys: the current frame - the stage - set anew, primitive by primitive in id
+     * order, to A + weight * (B - A), the primitives of frames A and B paired by rank; material, texture coordinates and
+     * movable flag are A's.  Any finite weight is served (outside 0 ... 1 it extrapolates), frameA == frameB is allowed.
+     * Returns 0 when done - the stage's tree refitted in the shape it has, the frame flattened -, -1 when the request cannot
+     * be served: a key that is no frame (not below getNbFrames()) or is the stage itself (the blend would destroy its own
+     * key), counts or types that differ among the three frames, a weight that is not finite: nothing changed.  An engine
+     * that keeps the stage resident blends it there from key frames it is handed once per upload (deviceMorphKeyFrames);
+     * what morphFrame says about the host copy holds. */
+    int morphBetween(unsigned int frameA, unsigned int frameB, float weight);
     bool pendingMorph() const { return m_resident.pendingMorph(); }
     void resetAddingIndex() { m_addingIndex = 0; }
     void doneWithAdding(const bool &done) { m_doneWithAdding = done; }
@@ -787,26 +804,39 @@ protected:
     /* translatePrimitives' loop over the level-0 boxes (no box is updated) */
     void translatePrimitivesOnly(Frame &f, const vec3f &translation);
     void refitBoxes(Frame &f);
-    /* blend the resident scene at that weight, the keys handed over first where the engine has none for this frame
-     * (morphKeys; which frame its keys are for: m_resident); false = not done, nothing changed */
-    bool deviceMorphFrame(float weight);
-    /* engine hooks: take these keys - the two key frames in the order of the resident primitives -; blend the resident
-     * scene between them at that weight; false = not done, nothing changed */
+    /* morphBetween's body; track: an engine serves it from the slots of a track, else through its two-key interface */
+    int morphKeyFrames(unsigned int frameA, unsigned int frameB, float weight, bool track);
+    /* blend the resident scene between these key frames at that weight, the keys the engine does not hold yet handed over
+     * first (morphKey, morphKeys; which ones it holds: m_resident); false = not done, nothing changed */
+    bool deviceMorphKeyFrames(unsigned int frameA, unsigned int frameB, float weight, bool track);
+    /* engine hooks of the two-key interface: take these keys - the two key frames in the order of the resident primitives -;
+     * blend the resident scene between them at that weight; false = not done, nothing changed */
     virtual bool deviceSetMorphKeys(const std::vector<Primitive> &, const std::vector<Primitive> &) { return false; }
     virtual bool deviceMorphPrimitives(float) { return false; }
+    /* engine hooks of a track: take this key frame - its primitives in id order, and per resident primitive its rank in
+     * that order - into that slot; blend the resident scene between two slots; false = not done, nothing changed */
+    virtual bool deviceSetMorphTrackKey(unsigned int, const std::vector<Primitive> &, const std::vector<int> &) { return false; }
+    virtual bool deviceMorphBetween(unsigned int, unsigned int, float) { return false; }
     /* the current frame against the two key frames: counts, types by rank */
-    bool morphKeysMatch();
-    /* morphFrame's loop over the store of the current frame (no boxes, no flattening) */
-    void morphPrimitivesOnly(float weight);
-    /* the two key frames as records in the order of the flattened primitives (of a record only the geometry is
-     * filled in); false when a primitive of the current frame differs from the first key's in what a morph takes from
-     * that key and a resident scene keeps as it is - material, texture coordinates, movable flag */
-    bool morphKeys(std::vector<Primitive> &first, std::vector<Primitive> &last);
+    bool morphKeysMatch(unsigned int frameA, unsigned int frameB);
+    /* morphBetween's loop over the store of the current frame (no boxes, no flattening) */
+    void morphPrimitivesOnly(unsigned int frameA, unsigned int frameB, float weight);
+    /* a key frame as records in id order (of a record only the geometry, the type and the index are filled in); compare:
+     * false when a primitive of the current frame differs from the key's in what a morph takes from its first key and a
+     * resident scene keeps as it is - material, texture coordinates, movable flag */
+    bool morphKey(unsigned int frame, bool compare, std::vector<Primitive> &key);
+    /* per primitive of the flattened order its rank in id order, of upload number m_rankOfUpload; nullptr when the flattened
+     * arrays do not describe the current frame */
+    const std::vector<int> *residentRanks();
+    /* the two key frames in the order of the flattened primitives, the first one compared (morphKey) */
+    bool morphKeys(unsigned int frameA, unsigned int frameB, std::vector<Primitive> &first, std::vector<Primitive> &last);
     /* the engine's resident scene against the store: who serves a move, and what the store owes afterwards */
     ResidentScene m_resident;
     /* editSlots: store index -> slot of the flattened order (-1: none, -2: several), of upload number m_slotOfUpload */
     std::vector<int> m_slotOf;
     unsigned long m_slotOfUpload = 0;
+    std::vector<int> m_rankOf;
+    unsigned long m_rankOfUpload = 0;
 
     /* box-tree build (GPUKernel.h:318-324) */
     int processBoxes(const int boxSize, bool simulate);

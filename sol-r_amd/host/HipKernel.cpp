@@ -225,6 +225,17 @@ bool HipKernel::deviceMorphPrimitives(float weight)
     return m_deviceInitialized && solr_hip_morph_primitives(weight, m_sceneInfo.viewDistance) == 1;
 }
 
+bool HipKernel::deviceSetMorphTrackKey(unsigned int slot, const std::vector<Primitive> &key, const std::vector<int> &rankOf)
+{
+    return m_deviceInitialized && key.size() == rankOf.size() &&
+           solr_hip_set_morph_track_key((int)slot, key.data(), rankOf.data(), (int)key.size()) == 1;
+}
+
+bool HipKernel::deviceMorphBetween(unsigned int slotA, unsigned int slotB, float weight)
+{
+    return m_deviceInitialized && solr_hip_morph_between((int)slotA, (int)slotB, weight, m_sceneInfo.viewDistance) == 1;
+}
+
 bool HipKernel::deviceTranslatePrimitives(const vec3f &translation)
 {
     if (!m_deviceInitialized)
@@ -562,6 +573,20 @@ bool ReplayKernel::deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n)
 bool ReplayKernel::deviceMorphPrimitives(float)
 {
     ++m_claimedMorphs;
+    return true;
+}
+
+bool ReplayKernel::deviceSetMorphTrackKey(unsigned int slot, const std::vector<Primitive> &key, const std::vector<int> &rankOf)
+{
+    if (slot >= SOLR_MORPH_TRACK_MAX_KEYS || key.size() != rankOf.size())
+        return false;
+    ++m_claimedTrackKeys;
+    return true;
+}
+
+bool ReplayKernel::deviceMorphBetween(unsigned int, unsigned int, float)
+{
+    ++m_claimedTrackMorphs;
     return true;
 }
 

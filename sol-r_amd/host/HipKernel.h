@@ -61,6 +61,9 @@ protected:
     /* morphFrame on the resident scene, solr_hip_set_morph_keys + solr_hip_morph_primitives (include/solr_hip.h) */
     bool deviceSetMorphKeys(const std::vector<Primitive> &first, const std::vector<Primitive> &last) override;
     bool deviceMorphPrimitives(float weight) override;
+    /* morphBetween on the resident scene, solr_hip_set_morph_track_key + solr_hip_morph_between (include/solr_hip.h) */
+    bool deviceSetMorphTrackKey(unsigned int slot, const std::vector<Primitive> &key, const std::vector<int> &rankOf) override;
+    bool deviceMorphBetween(unsigned int slotA, unsigned int slotB, float weight) override;
     /* translatePrimitives and a lamp's setPrimitiveCenter on the resident scene, solr_hip_translate_primitives and
      * solr_hip_move_lamp (include/solr_hip.h) */
     bool deviceTranslatePrimitives(const vec3f &translation) override;
@@ -114,7 +117,7 @@ protected:
 };
 
 /* Test double for the animated-scene protocol (GPUKernel::rotatePrimitives / translatePrimitives / setPrimitiveCenter /
- * morphFrame / syncHost): a host-only store that claims to upload the scene with a frame when an upload is due - the rule of
+ * morphFrame / morphBetween / syncHost): a host-only store that claims to upload the scene with a frame when an upload is due - the rule of
  * HipKernel::render_begin, through the same ResidentScene::uploaded - and to apply every move it is offered "over there".
  * What is offered (ResidentScene::offers) and the morph keys are the base class's business; the double only counts.  So the
  * lazy replay of what is pending can be checked against the eager host route without a GPU.  Renders nothing. */
@@ -124,6 +127,8 @@ public:
     void render_begin(const float timer) override;
     int nbClaimedRotations() const { return m_claimed; }
     int nbClaimedMorphs() const { return m_claimedMorphs; }
+    int nbClaimedTrackMorphs() const { return m_claimedTrackMorphs; }
+    int nbClaimedTrackKeys() const { return m_claimedTrackKeys; }
     int nbClaimedTranslations() const { return m_claimedTranslations; }
     int nbClaimedLampMoves() const { return m_claimedLampMoves; }
     int nbClaimedEdits() const { return m_claimedEdits; }
@@ -132,6 +137,9 @@ protected:
     bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) override;
     bool deviceSetMorphKeys(const std::vector<Primitive> &, const std::vector<Primitive> &) override { return true; }
     bool deviceMorphPrimitives(float weight) override;
+    /* (a slot for every frame number a real engine has one for) */
+    bool deviceSetMorphTrackKey(unsigned int slot, const std::vector<Primitive> &key, const std::vector<int> &rankOf) override;
+    bool deviceMorphBetween(unsigned int slotA, unsigned int slotB, float weight) override;
     bool deviceTranslatePrimitives(const vec3f &) override;
     bool deviceMoveLamp(int slot, const vec3f &center) override;
     /* (claimed where the store's side of the engine's conditions holds: GPUKernel::editSlots) */
@@ -139,5 +147,6 @@ protected:
 
 private:
     int m_claimed = 0, m_claimedMorphs = 0, m_claimedTranslations = 0, m_claimedLampMoves = 0, m_claimedEdits = 0;
+    int m_claimedTrackMorphs = 0, m_claimedTrackKeys = 0;
 };
 }

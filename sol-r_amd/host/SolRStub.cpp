@@ -404,6 +404,11 @@ int SolRx_SetNbFrames(int nbFrames)
     return 0;
 }
 
+int SolRx_GetNbFrames()
+{
+    return SingletonKernel::kernel()->getNbFrames();
+}
+
 int SolRx_SetFrame(int frame)
 {
     SingletonKernel::kernel()->setFrame(frame);
@@ -421,6 +426,15 @@ int SolRx_MorphPrimitives()
 int SolRx_MorphFrame(double weight)
 {
     return SingletonKernel::kernel()->morphFrame((float)weight);
+}
+
+/* Extension: the current frame blended anew from any two other frames at any weight (GPUKernel::morphBetween); with the
+ * HIP engine and an unchanged resident scene the blend runs on the device, each key frame handed over once */
+int SolRx_MorphBetween(int frameA, int frameB, double weight)
+{
+    if (frameA < 0 || frameB < 0)
+        return -1;
+    return SingletonKernel::kernel()->morphBetween((unsigned int)frameA, (unsigned int)frameB, (float)weight);
 }
 
 /* Extension: GPUKernel::setPrimitiveIsMovable (SolR_SetPrimitive makes a primitive movable again, as setPrimitive does) */

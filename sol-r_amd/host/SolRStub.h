@@ -192,6 +192,7 @@ int SolRx_GetTreeDepth();
 /* rotations applied on the device that the host scene store has not replayed yet; SolRx_SyncHost replays them */
 /* key frames (GPUKernel::setNbFrames / setFrame / morphPrimitives; the reference's scenes call them directly) */
 int SolRx_SetNbFrames(int nbFrames);
+int SolRx_GetNbFrames();
 int SolRx_SetFrame(int frame);
 int SolRx_MorphPrimitives();
 /* the current frame - one between the key frames, e.g. as SolRx_MorphPrimitives made it - blended anew at any finite weight
@@ -199,6 +200,11 @@ int SolRx_MorphPrimitives();
  * (GPUKernel::morphFrame).  0 = done, -1 = refused, nothing changed.  SolRx_PendingMorph: 1 while such a morph was
  * applied on the device and the host scene store has not replayed it yet (SolRx_SyncHost replays it) */
 int SolRx_MorphFrame(double weight);
+/* the same with any two frames as the keys: the current frame - a stage that is neither of them - set to
+ * frameA + weight * (frameB - frameA), material, texture coordinates and movable flag those of frameA
+ * (GPUKernel::morphBetween).  An animation of K key frames of one mesh plays through it: SolRx_MorphBetween(k, k + 1, t).
+ * 0 = done and flattened, -1 = refused, nothing changed; SolRx_PendingMorph as above */
+int SolRx_MorphBetween(int frameA, int frameB, double weight);
 /* whether rotations move the primitive, set after SolR_SetPrimitive (which makes it movable); a morph takes the first key's */
 int SolRx_SetPrimitiveIsMovable(int index, int movable);
 int SolRx_PendingMorph();
