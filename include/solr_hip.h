@@ -502,7 +502,9 @@ void solr_hip_render_counting(const SceneInfo *sceneInfo, const vec4i *objects,
  * reference's cut-off alone (no lamp cut-off, rt_device.h shadowWalk); 16 = the trace makes the trips that no lane takes
  * (the deferred-reflection trip of a wave without one, the material gather and the shader call of a trip in which every
  * lane missed; rt_device.h launchRayTracing); 17 = the hierarchy of the order-free lists is built on the leaves' boxes
- * as uploaded, no leaf set apart (csrc/build_bounds.h; lists that exist are built again with the next frame).  Every
+ * as uploaded, no leaf set apart (csrc/build_bounds.h; lists that exist are built again with the next frame); 18 = the
+ * thin copies of the lists keep the boxes of leaves of spheres as uploaded - the lamps' cell its +-viewDistance, which
+ * every walk enters (csrc/build_bounds.h sphereBuildExtent; the copies are made again with the next frame).  Every
  * setting renders the same frame. */
 void solr_hip_set_variant(int variant);
 /* Bounce rays (|direction| = 1 - rayEpsilon) of the long-list triangle kernels on the order-free lists, checked: lanes

@@ -287,8 +287,10 @@ enum Variant
     VARIANT_NO_LAMP_CUTOFF = 15, /* shadow walks in the reference's order keep the reference's cut-off alone */
     VARIANT_ALL_TRIPS = 16,      /* the trace makes the trips no lane takes: the deferred-reflection trip of a wave without
                                   * one, the gather and the shader call of a trip in which every lane missed */
-    VARIANT_UPLOADED_BUILD_BOXES = 17 /* the order-free hierarchy is built on the leaves' boxes as uploaded, no leaf set
-                                       * apart (build_bounds.h); the lists are built again with the next frame */
+    VARIANT_UPLOADED_BUILD_BOXES = 17, /* the order-free hierarchy is built on the leaves' boxes as uploaded, no leaf set
+                                        * apart (build_bounds.h); the lists are built again with the next frame */
+    VARIANT_UPLOADED_SPHERE_LEAVES = 18 /* the thin copies keep the boxes of sphere leaves as uploaded (the lamps' cell:
+                                         * +-viewDistance); the copies are made again with the next frame */
 };
 
 /* A node list of the resident scene: its host image, the count a frame is told, where the arena holds it (the layout
@@ -686,6 +688,12 @@ struct SceneFacts
     bool opaqueShadows = false;  /* no transparent primitive, no textured plane */
     bool plainPlanes = false;    /* the scene holds a plain axis plane: thin copies are worth making (tightenList) */
     float sceneExtent = 1.f;     /* max |coordinate| + |size| over the primitives, at least 1 */
+    bool looseSpheres = false;   /* a leaf of nothing but KIND_SPHEREs is boxed larger than they are (the lamps' cell) */
+    /* the reach the thin boxes of sphere leaves are made for (build_bounds.h sphereBuildExtent; solr_arena.hip
+     * thinReachWanted): the scene's extent, or the viewDistance beyond it of the frame that last walked them (prepareScene
+     * has the copies made again); 0: such leaves keep their boxes */
+    float thinReach = 0.f;
+    float frameViewDistance = 0.f; /* of the frame prepared last (prepareScene), 0: none yet - the reach a retag starts from */
     int sceneFeatures = F_ALL & ~F_FULL; /* rt_device.h enum Feature */
 };
 /* The kernel timer (solr_hip_enable_timing: Engine::timing; solr_launch.hip, solr_diag.hip) */
@@ -930,6 +938,8 @@ void flushGeometry();
 void pullGeometry();
 void ensureHostFreeLists();
 void buildLeafRecords();
+void tightenListsAgain();
+float thinReachWanted(float viewDistance);
 bool listEnclosesInArena(const NodeList &list);
 ListKnobs listKnobs();
 PruneDecider pruneDecider();

@@ -1618,7 +1618,23 @@ SOLR_DEV bool longRay(v3 d)
  * hit lies in (for the bounce rays, |direction| = 0.95, which box is entered FIRST decides: the thin copy is not for
  * them); the origin within viewDistance of zero.  The host offers the copy (S.tightLists) only with extended geometry
  * (without it a plane record is tested as a triangle) and viewDistance <= 64 E.  Same frames bit for bit
- * (solr_hip_set_variant(8) walks the reference's boxes; tests/test_gpu_parity.py), 0.2865 -> see DESIGN.md section 5. */
+ * (solr_hip_set_variant(8) walks the reference's boxes; tests/test_gpu_parity.py), 0.2865 -> see DESIGN.md section 5.
+ * LEAVES OF SPHERES.  The reference's builder boxes the lamps' cell +-viewDistance (GPUKernel.cpp:1189): every ray of a
+ * frame starts inside that box and entered the leaf, to test a lamp of radius 10.  In the thin copies a leaf that holds
+ * nothing but KIND_SPHERE records is the union of its spheres' boxes (build_bounds.h sphereBuildExtent), cut with the
+ * reference's box; a leaf the builder boxed p0 +- r comes out of the cut as it was.  What carries over from the planes: a
+ * test that misses has no effect; the conditions on the ray are tightRay's, unchanged; the bounce rays (tightShort /
+ * fatCheck) make the reference's own test on the reference's own box at every thin leaf they enter; the order-free cut-off
+ * and the lamp's (lampCut, point 2 of its argument) need "a hit lies inside its leaf's thin box" - which holds for the box
+ * WITH THE ALLOWANCE below, not for p0 +- (r + margin); with several lamps another lamp's sphere can shadow, and it is entered by every ray that crosses its box; the slab
+ * test's own rounding is covered by the margin as before.  What does NOT carry over is "the hit point lies inside the box
+ * up to a handful of roundings of M": a plane's hit is a quotient, a sphere's is decided by the sign of d = b b - 2 a c, a
+ * difference of two numbers of the size 4 s^2 (s = |o - p0|), so sphereHit calls rays hits that pass a lamp of radius 10
+ * at tens of units from 100 000 units away - and the reference, with its box, finds them.  The thin box allows for that:
+ * 2^-21 s^2 / r around the sphere and 2^-10 s along the ray, with s bounded through the REACH the copies are made for
+ * (origins within it on every axis: solr_arena.hip thinReachWanted - the scene's extent, or the frame's viewDistance where
+ * that is larger, in which case prepareScene has the copies made again).  The derivation stands above sphereBuildExtent;
+ * tests/test_sphere_leaf_margin.py puts it to grazing rays.  solr_hip_set_variant(18) keeps such leaves as uploaded. */
 SOLR_DEV bool tightRay(const WalkRay &r, const SceneInfo &si)
 {
     return longRay(r.d) && r.d.x != 0.f && r.d.y != 0.f && r.d.z != 0.f && fabsf(r.o.x) <= si.viewDistance &&
@@ -1657,7 +1673,7 @@ SOLR_DEV bool closestHitWalk(const Scene &S_, const SceneInfo &si_, bool active,
     const bool freeOrder =
         tidy && S.nbBoxesFree > 0 && ballot(active && !longRay(r.d)) == 0ull;
     /* the thin copy of the list this walk takes (tightRay above) */
-    constexpr bool thinLeaves = (FEAT & F_PLANE) != 0; /* (thin copies exist for leaves of plain axis planes only) */
+    constexpr bool thinLeaves = (FEAT & F_PLANE) != 0; /* (thin copies are made for scenes with planes: leaves of plain axis planes, and of spheres boxed larger than they are) */
     const bool tight = thinLeaves && tidy && S.tightLists && ballot(active && !tightRay(r, si)) == 0ull;
     /* ... and the SHORT rays (the bounce rays, |direction| = L = 1 - rayEpsilon) in the reference's order: for them the
      * reference's cut-off - slab parameter t against closest DISTANCE - decides by WHEN a box is entered, and a thin
@@ -2106,8 +2122,9 @@ SOLR_DEV float shadowWalk(const Scene &S_, const SceneInfo &si_, bool active, v3
      * enter the boxes that BEGIN BEYOND THE LAMP either, in any scene:
      *   1. a hit counts only if l < lengthOL below, i.e. its parameter along the un-normalised direction is below 1;
      *   2. it lies inside its leaf's box (the host's certificate, SHADOWS_LAMP_CUTOFF: every primitive of the list inside
-     *      its leaf's box) - in the thin copy inside the rectangle's box up to the margin, tightRay's argument, and the
-     *      thin copy is only walked by rays that argument holds for;
+     *      its leaf's box) - in the thin copy inside the rectangle's box up to the margin, or inside the sphere's box with
+     *      its allowance (build_bounds.h sphereBuildExtent), tightRay's argument, and the thin copy is only walked by rays
+     *      that argument holds for;
      *   3. so that leaf's entry parameter is below farFree = 1.0002 + 1e-4 sum|o| / lengthOL, the margins of the
      *      order-free cut-off above (2e-4 of the distance, 1e-4 of the origin's coordinates for the cancellation in
      *      bound - origin; a zero direction component has the reciprocal 1 and, the origin inside that slab, an entry

@@ -64,9 +64,11 @@ __global__ __launch_bounds__(256) void k_buildLeafRecords(float4 *__restrict__ a
 /* The thin copy of a node list (rt_device.h tightRay; scene_layout.h SceneArgs::tightLists): leaf by leaf.  A leaf
  * whose primitives are all plain axis planes becomes the union of their rectangles, `margin` thick and `margin` wider,
  * cut with the reference's box (never larger than it: a ray the thin box lets in, the reference's let in as well);
+ * with a `reach`, a leaf whose primitives are all KIND_SPHERE becomes the union of their boxes for rays from within
+ * that reach (build_bounds.h sphereBuildExtent), cut alike - the lamps' cell is the one the reference boxes larger;
  * every other node is copied.  k_tightenInner then makes the inner nodes the unions of the leaves below them. */
 __global__ __launch_bounds__(256) void k_tightenLeaves(float4 *__restrict__ arena, unsigned offNodes, unsigned offTight,
-                                                      unsigned offStart, unsigned offPrims, int nbNodes, float margin)
+                                                      unsigned offStart, unsigned offPrims, int nbNodes, float margin, float reach)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nbNodes)
@@ -76,13 +78,13 @@ __global__ __launch_bounds__(256) void k_tightenLeaves(float4 *__restrict__ aren
     if (nb > 0)
     {
         /* (build_bounds.h: the rectangles' union cut with the box, finite and ordered, or the reference's box stays; by the
-         * records' kinds - a plane that is textured, transparent or emissive keeps its box) */
+         * records' kinds - a plane that is textured, transparent or emissive keeps its box, and so does a procedural sphere) */
         static_assert(BB_KIND_SHIFT == PRIM_KIND_SHIFT && BB_KIND_PLANE_XY == KIND_PLANE_XY && BB_KIND_PLANE_YZ == KIND_PLANE_YZ &&
-                          BB_KIND_PLANE_XZ == KIND_PLANE_XZ && ROW_P0_TYPE == 0 && ROW_SIZE_MAT == 1,
+                          BB_KIND_PLANE_XZ == KIND_PLANE_XZ && BB_KIND_SPHERE == KIND_SPHERE && ROW_P0_TYPE == 0 && ROW_SIZE_MAT == 1,
                       "build_bounds.h reads the primitive records as scene_layout.h lays them out");
         const int start = ((const int *)arena)[offStart + (unsigned)i];
         float lo[3], hi[3];
-        if (leafBuildBounds(row0, row1, arena + offPrims, start, nb, margin, lo, hi, true))
+        if (leafBuildBounds(row0, row1, arena + offPrims, start, nb, margin, lo, hi, true, reach))
         {
             row0 = make_float4(lo[0], lo[1], lo[2], hi[2]);
             row1 = make_float4(hi[0], hi[1], row1.z, row1.w);
@@ -237,20 +239,32 @@ void pullGeometry()
     g.scene.hostImagesPulled();
 }
 
+/* The reach the thin boxes of sphere leaves are made for (build_bounds.h sphereBuildExtent): the origins of the rays that
+ * take the thin copies lie within the frame's viewDistance of zero (rt_device.h tightRay), the scene's extent where no
+ * frame has said more.  0: sphere leaves keep their boxes (VARIANT_UPLOADED_SPHERE_LEAVES). */
+float thinReachWanted(float viewDistance)
+{
+    if (g.variant == VARIANT_UPLOADED_SPHERE_LEAVES)
+        return 0.f;
+    return viewDistance > g.facts.sceneExtent ? viewDistance : g.facts.sceneExtent;
+}
+
 /* The thin copy of a node list behind it (NodeList::offThin; rt_device.h tightRay): made where the scene has
- * plain axis planes at all and the list is short enough for an inner node's thread to read its whole subtree (the
+ * plain axis planes at all - or spheres that a kernel which walks thin copies tests (thinLeaves there: the F_PLANE rows) -
+ * and the list is short enough for an inner node's thread to read its whole subtree (the
  * room of a 100 k-triangle model keeps the reference's boxes).  false: there is no copy to walk. */
 static bool tightenList(const NodeList &list)
 {
     static const bool off = getenv("SOLR_HIP_NO_TIGHT_LEAVES") != nullptr;
     const int nbNodes = (int)list.nodes(), listLength = list.nb;
-    if (off || !g.facts.plainPlanes || nbNodes <= 0 || listLength <= 0 || listLength > 65536 || !ok())
+    const bool worth = g.facts.plainPlanes || (g.facts.looseSpheres && (g.facts.sceneFeatures & F_PLANE) != 0);
+    if (off || !worth || nbNodes <= 0 || listLength <= 0 || listLength > 65536 || !ok())
         return false;
     float4 *arena = (float4 *)g.scene.arena.geometry.ptr;
     const float margin = g.facts.sceneExtent * (1.f / 1024.f);
     const dim3 grid((unsigned)((nbNodes + 255) / 256));
     hipLaunchKernelGGL(k_tightenLeaves, grid, dim3(256), 0, sceneStream(), arena, list.offRows, list.offThin(), list.offStart, g.scene.arena.offPrims,
-                       nbNodes, margin);
+                       nbNodes, margin, g.facts.thinReach);
     hipLaunchKernelGGL(k_tightenInner, grid, dim3(256), 0, sceneStream(), arena, list.offThin(), nbNodes, listLength);
     HIPCHECK(hipGetLastError());
     return ok();
@@ -331,6 +345,19 @@ void buildLeafRecords()
         return;
     for (NodeList *list : {&g.scene.exact, &g.scene.walk, &g.scene.orderFree})
         deriveList(*list);
+    HIPCHECK(hipStreamSynchronize(sceneStream()));
+}
+
+/* The thin copies alone, from the node rows and the primitive records as the arena holds them now: a sphere's thin box
+ * follows its centre (solr_moves.hip moveLampOne: the lamps' cell is never refitted, its thin box moves with the lamp) and
+ * the reach it was made for (prepareScene).  Nothing may be walking the copies (quiesce). */
+void tightenListsAgain()
+{
+    if (!ok() || !g.scene.arena.geometry.ptr)
+        return;
+    for (NodeList *list : {&g.scene.walk, &g.scene.orderFree})
+        if (list->tight)
+            list->tight = tightenList(*list);
     HIPCHECK(hipStreamSynchronize(sceneStream()));
 }
 
@@ -685,6 +712,17 @@ SceneArgs prepareScene(const SceneInfo &sceneInfo, bool exactNodes)
         return SceneArgs();
     SceneArgs S = makeScene(exactNodes);
     S.tightLists = tightListsFor(S, sceneInfo, exactNodes);
+    /* the thin boxes of sphere leaves are made for a reach: a frame with another one (its viewDistance beyond the scene's
+     * extent, VARIANT_UPLOADED_SPHERE_LEAVES set or taken back) has them made again before it walks them */
+    g.facts.frameViewDistance = sceneInfo.viewDistance;
+    if (S.tightLists && thinReachWanted(sceneInfo.viewDistance) != g.facts.thinReach)
+    {
+        quiesce();
+        g.facts.thinReach = thinReachWanted(sceneInfo.viewDistance);
+        tightenListsAgain();
+        if (!ok())
+            return SceneArgs();
+    }
     return S;
 }
 

@@ -541,6 +541,7 @@ void solr_hip_set_variant(int variant)
     onEveryDevice([&](int) {
         if ((g.variant == VARIANT_UPLOADED_BUILD_BOXES) != (variant == VARIANT_UPLOADED_BUILD_BOXES))
             g.scene.orderFreeBuildAgain();
+        /* (VARIANT_UPLOADED_SPHERE_LEAVES set or taken back: the next frame has the thin copies made again - prepareScene) */
         g.variant = variant;
         g.grouping = (variant != VARIANT_NO_GROUPING); /* takes effect at the next h2d_scene */
     });

@@ -159,8 +159,8 @@ bool canMoveLampOne(int lamp, const float center[3])
         /* the lamp has to stay inside its leaf (lampCutoffUsable, tightListsFor: the facts are not derived again): the first
          * node - the lamps' cell, which no refit touches, so its host image is what the arena holds - by the extent
          * k_listEncloses takes for a sphere.  A lamp of another cell is the host's, and so is one of another type: an axis
-         * plane's p0 also reaches the thin copies of the lists (tightenList: a leaf of plain axis planes becomes their
-         * rectangles - a leaf with a sphere in it keeps its box), which k_moveLamp does not make again */
+         * plane's p0 reaches the thin copies of the lists through another clause (tightenList: a leaf of plain axis planes
+         * becomes their rectangles); a sphere's does too, and moveLampOne has the copies made again (tightenListsAgain) */
         const float4 a = s.exact.rows[0], b = s.exact.rows[1];
         const float grow = fabsf(s.hostPrims[(size_t)PRIM_ROWS * lamp + ROW_SIZE_MAT].x);
         const int type = bitsi(s.hostPrims[(size_t)PRIM_ROWS * lamp + ROW_P0_TYPE].w) & PRIM_TYPE_MASK;
@@ -206,7 +206,9 @@ int moveLampOne(int lamp, const float center[3])
     M.x = center[0], M.y = center[1], M.z = center[2];
     hipLaunchKernelGGL(k_moveLamp, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sceneStream(), (float4 *)g.scene.arena.geometry.ptr, M);
     HIPCHECK(hipGetLastError());
-    /* the other flights' streams start their next frame only after this */
+    /* the lamps' cell is refitted by nobody, but its box in the thin copies is its spheres' (build_bounds.h): made again
+     * from the centre as it is now, on the same stream; the other flights' streams start their next frame only after this */
+    tightenListsAgain();
     HIPCHECK(hipStreamSynchronize(sceneStream()));
     if (ok())
     {

@@ -61,7 +61,7 @@ void retagPrimitives()
     const size_t n = g.scene.hostPrims.size() / PRIM_ROWS;
     const bool noKinds = getenv("SOLR_HIP_NO_KINDS") != nullptr; /* tests: every primitive through the general tests */
     int features = 0;
-    bool contained = true, opaque = true, planes = false;
+    bool contained = true, opaque = true, planes = false, spheres = false;
     float extent = 1.f;
     for (size_t i = 0; i < n; ++i)
     {
@@ -91,6 +91,7 @@ void retagPrimitives()
             kind = KIND_CYLINDER;
         r[ROW_P0_TYPE].w = bitsf(type | facts | (kind << PRIM_KIND_SHIFT));
         planes = planes || kind == KIND_PLANE_XY || kind == KIND_PLANE_YZ || kind == KIND_PLANE_XZ;
+        spheres = spheres || kind == KIND_SPHERE;
         /* inside the box the reference's builder gives its leaf (GPUKernel.cpp:762-830: the vertices of a triangle,
          * p0 +- radius of a sphere, min / max (p0, p1) +- radius of a cylinder, p0 +- size of a plane; a cone's box
          * is built around p0 alone, a procedural sphere's surface is displaced, the others are not bounded by
@@ -136,6 +137,33 @@ void retagPrimitives()
                 reach = std::max(reach, fabsf(c));
     g.facts.sceneExtent = extent + reach;
     g.facts.plainPlanes = planes;
+    /* ... and is a leaf of nothing but such spheres boxed larger than they are?  (The reference's builder does that to the
+     * lamps' cell alone; every list has the leaves of the reference's.)  Only then is a thin copy worth making for them. */
+    bool loose = false;
+    const std::vector<float4> &rows = g.scene.exact.rows;
+    const std::vector<int> &start = g.scene.exact.start;
+    for (size_t i = 0; spheres && !loose && i < start.size() && 2 * i + 1 < rows.size(); ++i)
+    {
+        const float4 a = rows[2 * i], b = rows[2 * i + 1];
+        const int count = bitsi(b.z);
+        if (count <= 0 || start[i] < 0 || (size_t)start[i] + (size_t)count > n)
+            continue;
+        bool all = true;
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int k = 0; k < count && all; ++k)
+        {
+            const float4 p = g.scene.hostPrims[PRIM_ROWS * ((size_t)start[i] + k) + ROW_P0_TYPE];
+            const float r = fabsf(g.scene.hostPrims[PRIM_ROWS * ((size_t)start[i] + k) + ROW_SIZE_MAT].x);
+            all = ((bitsi(p.w) >> PRIM_KIND_SHIFT) & 15) == KIND_SPHERE;
+            lo[0] = std::min(lo[0], p.x - r), lo[1] = std::min(lo[1], p.y - r), lo[2] = std::min(lo[2], p.z - r);
+            hi[0] = std::max(hi[0], p.x + r), hi[1] = std::max(hi[1], p.y + r), hi[2] = std::max(hi[2], p.z + r);
+        }
+        loose = all && (a.x < lo[0] || a.y < lo[1] || a.z < lo[2] || b.x > hi[0] || b.y > hi[1] || a.w > hi[2]);
+    }
+    g.facts.looseSpheres = loose;
+    /* (for the viewDistance of the frame prepared last, so that a host which uploads every frame has the copies made once;
+     * a frame with another one has them made again: prepareScene) */
+    g.facts.thinReach = thinReachWanted(g.facts.frameViewDistance);
     g.facts.sceneFeatures = features;
     g.facts.primsContained = contained && n > 0;
     g.facts.opaqueShadows = opaque && n > 0;
