@@ -657,6 +657,34 @@ int solr_hip_read_lights(float *rows, int capacityRows);
 int solr_hip_set_primitives(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance);
 int solr_hip_device_edits(void);
 
+/* Primitives that are given another material: a sample that is marked, a picked primitive that is highlighted, atoms that are
+ * recoloured.  The reference's SWC scene gives the sample before its material back and the next one the light material with
+ * setPrimitiveMaterial, moves the lamp and calls compactBoxes(false) per frame (apps/scenes/science/SwcScene.cpp:66-89) - a
+ * flatten and a full upload for three words of two primitive records:
+ *   solr_hip_set_primitive_materials   `slots`: per record the place of its primitive in the flattened order of the resident
+ *                               scene, no slot twice; `materialIds`: per record the id of a material of the last
+ *                               h2d_materials.  Every named primitive gets what h2d_scene joins into its record from the
+ *                               material - the tag (type, the material's facts, the kind), the id, the colour key - and so do
+ *                               the copies the engine keeps of those words (leaf records, host image); no geometry word is
+ *                               written, no node, no light record; the facts of the scene a frame is told (its features,
+ *                               whether every shadow is opaque) follow in place.  Returns 1 when the resident scene now
+ *                               holds, bit for bit, what setPrimitiveMaterial per record + compactBoxes(false) + a fresh
+ *                               h2d_scene of the same flattened order would have produced, 0 when it cannot serve the
+ *                               request - no resident scene, no records, a slot out of range or twice, a slot among the
+ *                               lamps' (its light record carries the material), a material id that is negative or not among
+ *                               the uploaded ones, a record after which the primitive's kind would differ (the thin copies
+ *                               of the lists and the order-free hierarchy were made from the kinds: a YZ plane turned
+ *                               emissive, a plain sphere turned procedural, a plane turned textured), a batch after which
+ *                               the primitives would all lie inside their leaves where they did not before, or the other
+ *                               way round (that decides whether order-free lists exist): nothing changed, take the host
+ *                               route.  A primitive elsewhere than in the lamps' cell that gets an emissive material glows
+ *                               and lights nothing, as after compactBoxes(false).  A morph on the device would keep the
+ *                               materials, where the host's takes its first key's: after a served batch
+ *                               solr_hip_morph_primitives and solr_hip_morph_between decline until the next h2d_scene;
+ *   solr_hip_device_material_sets   how many requests were served since initialize_scene. */
+int solr_hip_set_primitive_materials(const int *slots, const int *materialIds, int n);
+int solr_hip_device_material_sets(void);
+
 /* Bytes of HBM this engine currently holds for {scene planes, materials,
  * textures, per-pixel buffers}; for DESIGN.md's layout table and tests. */
 void solr_hip_memory_usage(unsigned long long bytes[4]);

@@ -129,6 +129,10 @@ EDIT_DTYPE = np.dtype({"names": ["index", "materialId", "flags", "p0", "p1", "p2
                                  "vt0", "vt1", "vt2"],
                        "formats": [i4, i4, np.uint32] + [(f4, 3)] * 7 + [(f4, 2)] * 3,
                        "offsets": [0, 4, 8, 12, 24, 36, 48, 60, 72, 84, 96, 104, 112], "itemsize": 120})
+# SolrSwcSample of host/SolRStub.h: one sample of an SWC morphology (Kernel.swc_samples)
+SWC_SAMPLE_DTYPE = np.dtype({"names": ["id", "branch", "x", "y", "z", "radius", "parent", "primitiveId"],
+                             "formats": [i4, i4, f4, f4, f4, f4, i4, i4], "offsets": [0, 4, 8, 12, 16, 20, 24, 28],
+                             "itemsize": 32})
 MATERIAL_DTYPE = np.dtype({"names": ["innerIllumination", "color", "specular", "reflection", "refraction",
                                      "transparency", "opacity", "attributes", "textureMapping", "textureOffset",
                                      "textureIds", "advancedTextureOffset", "advancedTextureIds", "mappingOffset"],
@@ -290,6 +294,9 @@ def _declare_hip(L):
     L.solr_hip_set_primitives.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
     L.solr_hip_set_primitives.restype = C.c_int
     L.solr_hip_device_edits.restype = C.c_int
+    L.solr_hip_set_primitive_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.solr_hip_set_primitive_materials.restype = C.c_int
+    L.solr_hip_device_material_sets.restype = C.c_int
     L.solr_hip_read_nodes.argtypes = [C.c_int, C.c_void_p, C.c_int]
     L.solr_hip_read_nodes.restype = C.c_int
     L.solr_hip_read_primitives.argtypes = [C.c_void_p, C.c_int]
@@ -394,6 +401,10 @@ def _declare_host(L):
     L.SolRx_SetPrimitives.argtypes = [C.c_void_p, i]
     L.SolRx_SetPrimitives.restype = i
     L.SolRx_SizeofPrimitiveEdit.restype = i
+    L.SolRx_SetPrimitiveMaterials.argtypes = [C.c_void_p, C.c_void_p, i]
+    L.SolRx_SetPrimitiveMaterials.restype = i
+    L.SolRx_GetMorphologies.argtypes = [C.c_void_p, i]
+    L.SolRx_GetMorphologies.restype = i
 
 
 def edit_records(edits):
@@ -649,9 +660,38 @@ class Kernel:
         batch = edit_records(edits)
         return self.L.SolRx_SetPrimitives(batch.ctypes.data, len(batch))
 
+    def set_primitive_materials(self, indices, material_ids):
+        """A batch of primitives given another material, then compactBoxes(false) (SolRx_SetPrimitiveMaterials): per record
+        setPrimitiveMaterial(index, materialId), in order - of several records for one index the last one wins - what the
+        reference's SwcScene does per frame to mark a sample, a viewer to highlight a picked primitive.  indices and
+        material_ids: as many integers each.  With the HIP engine and an unchanged resident scene the batch is applied on
+        the device - tag, material id and colour key of each primitive in place - and the host copy follows lazily
+        (pending_moves); a lamp, a material that was not uploaded or a primitive the walks would have to treat as another
+        kind afterwards take the host route.  0 when done, -1 when an index is not in the store (nothing changed)."""
+        indices = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        material_ids = np.ascontiguousarray(material_ids, np.int32).reshape(-1)
+        if len(indices) != len(material_ids):
+            raise SolrError("set_primitive_materials: as many material ids as indices")
+        return self.L.SolRx_SetPrimitiveMaterials(indices.ctypes.data, material_ids.ctypes.data, len(indices))
+
+    def get_primitive_material(self, index):
+        """GPUKernel::getPrimitiveMaterial: the material id the primitive has now, what set_primitive_materials left pending
+        included; -1 when the store has no such primitive"""
+        return self.L.SolR_GetPrimitiveMaterial(index)
+
+    def swc_samples(self):
+        """The samples the SWC reader kept of the morphology loaded last (SolRx_GetMorphologies), by ascending id: an array
+        of SWC_SAMPLE_DTYPE - id, branch, x, y, z, radius (as scaled by the load), parent, primitiveId (the primitive the
+        reader stored with the sample)."""
+        n = self.L.SolRx_GetMorphologies(None, 0)
+        samples = np.zeros(max(n, 0), SWC_SAMPLE_DTYPE)
+        if n > 0 and self.L.SolRx_GetMorphologies(samples.ctypes.data, n) != n:
+            raise SolrError("SolRx_GetMorphologies: the samples changed between two calls")
+        return samples
+
     def pending_moves(self):
-        """rotations, translations, lamp moves and batches of edits applied on the device that the host scene store has not
-        replayed yet"""
+        """rotations, translations, lamp moves, batches of edits and batches of material sets applied on the device that the
+        host scene store has not replayed yet"""
         return self.L.SolRx_PendingMoves()
 
     # -- key frames ---------------------------------------------------------------------

@@ -3,7 +3,7 @@
  * solr_hip.hip (the boundary), solr_uploads.hip (the h2d_* uploads), solr_arena.hip (the arena and the node lists; their
  * host builders: list_builders.h), solr_rotation.hip (rotation and refit on the device), solr_morph.hip (key-frame
  * morphing on the device), solr_moves.hip (translation and lamp moves on the device), solr_edits.hip (primitives set anew on
- * the device), solr_launch.hip (the renderer's
+ * the device), solr_materials.hip (primitives' materials set on the device), solr_launch.hip (the renderer's
  * launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined read-back), solr_rccl.hip (strips,
  * communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
@@ -293,6 +293,67 @@ enum Variant
                                          * +-viewDistance); the copies are made again with the next frame */
 };
 
+/* ---- what a primitive's type and the facts of its material (materialTag, solr_uploads.hip) say about it.  Stated once:
+ * retagPrimitives joins them into every tag on the host, k_setPrimitiveMaterials (solr_materials.hip) into the tags of a batch
+ * on the device, and canSetPrimitiveMaterialsOne asks them what a batch would change. */
+/* PrimKind (scene_layout.h): the short path the walks may take through the primitive */
+__host__ __device__ inline int primitiveKind(int type, int facts)
+{
+    if (!(facts & PRIM_FAST0))
+        return KIND_GENERAL; /* the closest-hit walk lets every lane of the leaf test a primitive with a kind */
+    if (type == ptSphere && !(facts & PRIM_PROCEDURAL))
+        return KIND_SPHERE;
+    if ((type == ptXYPlane || type == ptYZPlane || type == ptXZPlane) && !(facts & (PRIM_TEXTURED | PRIM_WIRE2)) &&
+        !(type == ptYZPlane && (facts & PRIM_EMISSIVE)))
+        return type == ptXYPlane ? KIND_PLANE_XY : (type == ptYZPlane ? KIND_PLANE_YZ : KIND_PLANE_XZ);
+    if (type == ptTriangle)
+        return KIND_TRIANGLE;
+    if (type == ptCylinder || type == ptCone)
+        return KIND_CYLINDER;
+    return KIND_GENERAL;
+}
+/* the tag word; noKinds (SOLR_HIP_NO_KINDS, tests): every primitive through the general tests */
+__host__ __device__ inline int primitiveTag(int type, int facts, bool noKinds)
+{
+    return type | facts | ((noKinds ? (int)KIND_GENERAL : primitiveKind(type, facts)) << PRIM_KIND_SHIFT);
+}
+/* inside the box the reference's builder gives its leaf (GPUKernel.cpp:762-830: the vertices of a triangle, p0 +- radius of
+ * a sphere, min / max (p0, p1) +- radius of a cylinder, p0 +- size of a plane; a cone's box is built around p0 alone, a
+ * procedural sphere's surface is displaced, the others are not bounded by their size) */
+inline bool primitiveContained(int type, int facts)
+{
+    return type == ptTriangle || type == ptCylinder || (type == ptSphere && !(facts & PRIM_PROCEDURAL)) || type == ptXYPlane ||
+           type == ptYZPlane || type == ptXZPlane;
+}
+/* every occluder saturates a shadow (GI:880: intensity 1 x sceneInfo.shadowIntensity) unless it is transparent (GI:881-892
+ * scales and tints) or a textured plane (its texel's alpha is the intensity, GI:553-558) */
+inline bool primitiveShadowOpaque(int type, int facts)
+{
+    return !(facts & PRIM_TRANSPARENT) && !(facts & PRIM_TEXTURED) && type != ptCamera;
+}
+/* the features (rt_device.h enum Feature) a frame needs for it */
+inline int primitiveFeatures(int type, int facts)
+{
+    int features = (facts & PRIM_TEXTURED) ? F_TEX : 0;
+    switch (type)
+    {
+    case ptSphere:
+    case ptEnvironment:
+        return features | ((facts & PRIM_PROCEDURAL) ? F_PROC : F_SPHERE);
+    case ptCylinder:
+    case ptCone:
+        return features | F_CYL;
+    case ptEllipsoid:
+        return features | F_ELL;
+    case ptTriangle:
+        return features | F_TRI;
+    case ptCamera:
+        return features | F_PLANE | F_TEX;
+    default:
+        return features | F_PLANE;
+    }
+}
+
 /* A node list of the resident scene: its host image, the count a frame is told, where the arena holds it (the layout
  * itself is scene_layout.h's), and what is known about it.  Behind its rows the arena holds one pad record - the walk
  * requests the record after the node it tests (rt_device.h advanceTidy), after the last node too - then, for a list
@@ -400,6 +461,10 @@ struct Rotation
     DeviceBuffer edits;
     int nbDeviceEdits = 0;
     bool edited = false; /* ... since h2d_scene: a morph there would leave the edit's texture coordinates behind */
+    /* materials set (solr_materials.hip): the batch as uploaded last; nothing is refitted */
+    DeviceBuffer materialSets;
+    int nbDeviceMaterialSets = 0;
+    bool materialsSet = false; /* ... since h2d_scene: a morph there would keep them, where the host's takes its first key's */
 };
 /* Key-frame morphing on the device (solr_morph.hip): the key frames of the resident scene the engine holds, one per slot -
  * the slots of a track (solr_hip_set_morph_track_key, solr_hip_morph_between), then the two of the two-key interface
@@ -465,6 +530,7 @@ struct Scene
         rotation.nbMovable = -1;
         rotation.lampMoved = false;
         rotation.edited = false;
+        rotation.materialsSet = false;
         morphKeysDropped();
         arena.deviceAhead = false;
         orderFree.reset();
@@ -571,7 +637,18 @@ struct Scene
             ++rotation.nbDeviceEdits;
         }
     }
-    /* retagPrimitives has joined the materials' facts into the primitives' tags again */
+    /* setPrimitiveMaterialsOne has set the batch's tags, material ids and colour keys, in the arena, in the leaf records and
+     * in the host image alike (nothing is ahead of anything by it, no bound moved); whoever derived something from the tags
+     * hears of it through retagged() */
+    void materialSetsServed(bool landed)
+    {
+        if (landed)
+        {
+            rotation.materialsSet = true;
+            ++rotation.nbDeviceMaterialSets;
+        }
+    }
+    /* retagPrimitives has joined the materials' facts into the primitives' tags again (setPrimitiveMaterialsOne: into some) */
     void retagged() { ++retags; }
     /* the morph keys: every slot empty (the buffers stay for the next keys) / one slot empty / one slot packed for
      * nbPrimitives primitives.  What was answered about lamps held for the slots as they were */
@@ -620,13 +697,37 @@ struct Scene
     {
         lists.dropStage(true);
         for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag, &rotation.edits,
-                                &morph.lampFlag})
+                                &rotation.materialSets, &morph.lampFlag})
             solreng::release(*b);
         for (MorphKey &key : morph.keys)
             solreng::release(key.planes);
         *this = Scene();
     }
 };
+/* Where the arena holds the leaf records of the resident node lists, for a kernel that patches them in place behind a
+ * change of some primitives' words (solr_moves.hip k_moveLamp, solr_materials.hip k_followLeafRecords): one thread per node,
+ * one list behind the other. */
+struct LeafRecordsOf
+{
+    unsigned offRows, offStart, offLeaf; /* of a node list (NodeList) */
+    int nodes;                           /* 0: the arena holds no leaf records of that list */
+};
+/* ... of the exact, the walk-order and the order-free lists of `scene`; returns the nodes in all */
+inline int leafRecordsOfLists(const Scene &scene, LeafRecordsOf out[3])
+{
+    int total = 0, l = 0;
+    for (const NodeList *list : {&scene.exact, &scene.walk, &scene.orderFree})
+    {
+        const bool none = list == &scene.orderFree && scene.lists.freeStale; /* (deriveList: a stale list has none) */
+        out[l].offRows = list->offRows;
+        out[l].offStart = list->offStart;
+        out[l].offLeaf = list->offLeaf;
+        out[l].nodes = none ? 0 : (int)list->nodes();
+        total += out[l].nodes;
+        ++l;
+    }
+    return total;
+}
 /* Lights (h2d_lightInformation): their records lie in the arena behind the primitives'.  h2d_scene keeps them,
  * finalize_scene drops them. */
 struct Lights
@@ -695,6 +796,38 @@ struct SceneFacts
     float thinReach = 0.f;
     float frameViewDistance = 0.f; /* of the frame prepared last (prepareScene), 0: none yet - the reach a retag starts from */
     int sceneFeatures = F_ALL & ~F_FULL; /* rt_device.h enum Feature */
+    /* the counts behind primsContained, opaqueShadows and sceneFeatures, kept by retagPrimitives: a batch of materials set
+     * on the resident scene (solr_materials.hip) takes its primitives out with their old facts and in with their new ones,
+     * and the three are exact again without a pass over the primitives */
+    static const int FEATURE_BITS = 7; /* F_SPHERE ... F_TEX */
+    int nbCounted = 0, nbUncontained = 0, nbShadowTinting = 0;
+    int featureUsers[FEATURE_BITS] = {};
+    void forgetCounts()
+    {
+        nbCounted = nbUncontained = nbShadowTinting = 0;
+        for (int &users : featureUsers)
+            users = 0;
+    }
+    /* by: +1 a primitive of that type and those facts joins the scene, -1 it leaves */
+    void count(int type, int facts, int by)
+    {
+        nbCounted += by;
+        nbUncontained += primitiveContained(type, facts) ? 0 : by;
+        nbShadowTinting += primitiveShadowOpaque(type, facts) ? 0 : by;
+        const int features = primitiveFeatures(type, facts);
+        for (int bit = 0; bit < FEATURE_BITS; ++bit)
+            if (features & (1 << bit))
+                featureUsers[bit] += by;
+    }
+    void deriveFromCounts()
+    {
+        primsContained = nbUncontained == 0 && nbCounted > 0;
+        opaqueShadows = nbShadowTinting == 0 && nbCounted > 0;
+        sceneFeatures = 0;
+        for (int bit = 0; bit < FEATURE_BITS; ++bit)
+            if (featureUsers[bit] > 0)
+                sceneFeatures |= 1 << bit;
+    }
 };
 /* The kernel timer (solr_hip_enable_timing: Engine::timing; solr_launch.hip, solr_diag.hip) */
 struct KernelTimer
@@ -969,6 +1102,9 @@ int moveLampOne(int lamp, const float center[3]);
 /* solr_edits.hip: a batch of primitives set anew on the device */
 bool canSetPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance);
 int setPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance);
+/* solr_materials.hip: a batch of primitives' materials set on the device */
+bool canSetPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n);
+int setPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n);
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */
 void allocateFrame();
 int neededFeatures(const SceneInfo &sceneInfo, bool full);

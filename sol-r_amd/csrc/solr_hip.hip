@@ -2,8 +2,8 @@
  * solr_hip.hip - the C ABI of the MI355X rendering engine (include/solr_hip.h): the reference's ten entry points
  * (CudaRayTracer.h:25-67) once per in-process device, device / stream / strip selection, the life of an engine
  * (initialize_scene ... finalize_scene).  The rest of the engine's host side: engine.h (state), solr_uploads.hip,
- * solr_arena.hip, solr_rotation.hip, solr_morph.hip, solr_moves.hip and solr_edits.hip (the resident scene: its uploads, its
- * arena and lists, rotation, morphing, translation, lamp moves and edited primitives on the device),
+ * solr_arena.hip, solr_rotation.hip, solr_morph.hip, solr_moves.hip, solr_edits.hip and solr_materials.hip (the resident scene: its
+ * uploads, its arena and lists, rotation, morphing, translation, lamp moves, edited primitives and materials set on the device),
  * solr_launch.hip (a frame), solr_post.hip, solr_image_ring.hip, solr_rccl.hip, solr_diag.hip; the kernels: rt_device.h,
  * renderer_kernel.h, rows/.  gfx950 only.
  */
@@ -695,6 +695,22 @@ int solr_hip_set_primitives(const SolrPrimitiveEdit *edits, const int *slots, in
     int status = 1; /* 1: set on the device */
     onEveryDevice([&](int) {
         const int mine = setPrimitivesOne(edits, slots, n, viewDistance);
+        if (mine != 1 && status == 1)
+            status = mine;
+    });
+    return status;
+}
+
+/* (... and every one of them sets the batch's materials in its own copy; 1 only when all of them did) */
+int solr_hip_set_primitive_materials(const int *slots, const int *materialIds, int n)
+{
+    bool all = true;
+    onEveryDevice([&](int) { all = canSetPrimitiveMaterialsOne(slots, materialIds, n) && all; });
+    if (!all)
+        return 0;
+    int status = 1; /* 1: set on the device */
+    onEveryDevice([&](int) {
+        const int mine = setPrimitiveMaterialsOne(slots, materialIds, n);
         if (mine != 1 && status == 1)
             status = mine;
     });

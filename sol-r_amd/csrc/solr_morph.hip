@@ -312,9 +312,12 @@ bool canMorphOne(int slotA, int slotB, float weight, float viewDistance, const c
     const MorphKey &a = m.keys[slotA], &b = m.keys[slotB];
     /* (a lamp that was moved on the device, solr_moves.hip: the blend would put its p0 back at the keys' place and leave
      * its light record where the move put it - the host route makes the record from p0 again; primitives that were set
-     * anew on the device, solr_edits.hip: the blend would leave their texture coordinates and movable flags behind) */
+     * anew on the device, solr_edits.hip: the blend would leave their texture coordinates and movable flags behind;
+     * materials that were set on the device, solr_materials.hip: the blend would keep them, where the host's takes its
+     * first key's) */
     if (a.nbPrimitives != g.scene.nbPrimitives || b.nbPrimitives != g.scene.nbPrimitives || !a.planes.ptr || !b.planes.ptr ||
-        !std::isfinite(weight) || g.scene.rotation.lampMoved || g.scene.rotation.edited || lampWouldMove(slotA, slotB))
+        !std::isfinite(weight) || g.scene.rotation.lampMoved || g.scene.rotation.edited || g.scene.rotation.materialsSet ||
+        lampWouldMove(slotA, slotB))
     {
         if (getenv("SOLR_HIP_DEBUG_TREE"))
             fprintf(stderr, "%s refused: keys for %d and %d of %d primitives, weight %g, a lamp moved here: %d\n", who, a.nbPrimitives,

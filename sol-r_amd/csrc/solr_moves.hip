@@ -95,14 +95,9 @@ int translatePrimitivesOne(const float translation[3], float viewDistance)
  * is uploaded, the move changes the p0 of one primitive and the location of one light record (:1218-1220).  Here those two
  * are written in the arena, and with them what the engine derives from that p0 and keeps elsewhere - the leaf records of the
  * leaves whose first primitive the lamp is (k_buildLeafRecords: record 0 is the primitive's first row), the host images. */
-struct LeafRecordsOf
-{
-    unsigned offRows, offStart, offLeaf; /* of a node list (NodeList) */
-    int nodes;                           /* 0: the arena holds no leaf records of that list */
-};
 struct LampMove
 {
-    LeafRecordsOf list[3];
+    LeafRecordsOf list[3]; /* (engine.h) */
     unsigned offPrims, offLights;
     int lamp;
     float x, y, z;
@@ -188,18 +183,7 @@ int moveLampOne(int lamp, const float center[3])
         return 0;
     quiesce(); /* no frame in flight reads a lamp that is half here and half there */
     LampMove M;
-    int total = 1;
-    int l = 0;
-    for (const NodeList *list : {&g.scene.exact, &g.scene.walk, &g.scene.orderFree})
-    {
-        const bool none = list == &g.scene.orderFree && g.scene.lists.freeStale; /* (deriveList: a stale list has none) */
-        M.list[l].offRows = list->offRows;
-        M.list[l].offStart = list->offStart;
-        M.list[l].offLeaf = list->offLeaf;
-        M.list[l].nodes = none ? 0 : (int)list->nodes();
-        total += M.list[l].nodes;
-        ++l;
-    }
+    const int total = 1 + leafRecordsOfLists(g.scene, M.list);
     M.offPrims = g.scene.arena.offPrims;
     M.offLights = g.scene.arena.offLights;
     M.lamp = lamp;

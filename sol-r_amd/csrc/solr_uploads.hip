@@ -60,9 +60,9 @@ void retagPrimitives()
     pullGeometry();
     const size_t n = g.scene.hostPrims.size() / PRIM_ROWS;
     const bool noKinds = getenv("SOLR_HIP_NO_KINDS") != nullptr; /* tests: every primitive through the general tests */
-    int features = 0;
-    bool contained = true, opaque = true, planes = false, spheres = false;
+    bool planes = false, spheres = false;
     float extent = 1.f;
+    g.facts.forgetCounts();
     for (size_t i = 0; i < n; ++i)
     {
         float4 *r = &g.scene.hostPrims[PRIM_ROWS * i];
@@ -77,56 +77,14 @@ void retagPrimitives()
         /* a material that was never uploaded reads as all zeros on the device */
         const int facts = (mat >= 0 && (size_t)mat < g.materials.materialTags.size()) ? g.materials.materialTags[mat]
                                                                                       : (PRIM_FAST0 | (1 << PRIM_WIDTH_SHIFT));
-        int kind = KIND_GENERAL;
-        if (noKinds || !(facts & PRIM_FAST0))
-            kind = KIND_GENERAL; /* the closest-hit walk lets every lane of the leaf test a primitive with a kind */
-        else if (type == ptSphere && !(facts & PRIM_PROCEDURAL))
-            kind = KIND_SPHERE;
-        else if ((type == ptXYPlane || type == ptYZPlane || type == ptXZPlane) && !(facts & (PRIM_TEXTURED | PRIM_WIRE2)) &&
-                 !(type == ptYZPlane && (facts & PRIM_EMISSIVE)))
-            kind = type == ptXYPlane ? KIND_PLANE_XY : (type == ptYZPlane ? KIND_PLANE_YZ : KIND_PLANE_XZ);
-        else if (type == ptTriangle)
-            kind = KIND_TRIANGLE;
-        else if (type == ptCylinder || type == ptCone)
-            kind = KIND_CYLINDER;
-        r[ROW_P0_TYPE].w = bitsf(type | facts | (kind << PRIM_KIND_SHIFT));
+        /* the kind, and what the primitive says about the scene - contained, opaque to shadows, features -: engine.h */
+        const int retagged = primitiveTag(type, facts, noKinds);
+        const int kind = (retagged >> PRIM_KIND_SHIFT) & 15;
+        r[ROW_P0_TYPE].w = bitsf(retagged);
         planes = planes || kind == KIND_PLANE_XY || kind == KIND_PLANE_YZ || kind == KIND_PLANE_XZ;
         spheres = spheres || kind == KIND_SPHERE;
-        /* inside the box the reference's builder gives its leaf (GPUKernel.cpp:762-830: the vertices of a triangle,
-         * p0 +- radius of a sphere, min / max (p0, p1) +- radius of a cylinder, p0 +- size of a plane; a cone's box
-         * is built around p0 alone, a procedural sphere's surface is displaced, the others are not bounded by
-         * their size) */
-        /* every occluder saturates a shadow (GI:880: intensity 1 x sceneInfo.shadowIntensity) unless it is transparent
-         * (GI:881-892 scales and tints) or a textured plane (its texel's alpha is the intensity, GI:553-558) */
-        opaque = opaque && !(facts & PRIM_TRANSPARENT) && !(facts & PRIM_TEXTURED) && type != ptCamera;
-        contained = contained && (type == ptTriangle || type == ptCylinder || (type == ptSphere && !(facts & PRIM_PROCEDURAL)) ||
-                                  type == ptXYPlane || type == ptYZPlane || type == ptXZPlane);
+        g.facts.count(type, facts, +1);
         r[ROW_P2].w = (mat >= 0 && (size_t)mat < g.materials.materialAverage.size()) ? g.materials.materialAverage[mat] : 0.f;
-        switch (type)
-        {
-        case ptSphere:
-        case ptEnvironment:
-            features |= (facts & PRIM_PROCEDURAL) ? F_PROC : F_SPHERE;
-            break;
-        case ptCylinder:
-        case ptCone:
-            features |= F_CYL;
-            break;
-        case ptEllipsoid:
-            features |= F_ELL;
-            break;
-        case ptTriangle:
-            features |= F_TRI;
-            break;
-        case ptCamera:
-            features |= F_PLANE | F_TEX;
-            break;
-        default:
-            features |= F_PLANE;
-            break;
-        }
-        if (facts & PRIM_TEXTURED)
-            features |= F_TEX;
     }
     /* |p0| + |size| of the largest primitive, at least: the scale the thin leaves' margin is a 2^-10 of */
     float reach = 0.f;
@@ -164,9 +122,7 @@ void retagPrimitives()
     /* (for the viewDistance of the frame prepared last, so that a host which uploads every frame has the copies made once;
      * a frame with another one has them made again: prepareScene) */
     g.facts.thinReach = thinReachWanted(g.facts.frameViewDistance);
-    g.facts.sceneFeatures = features;
-    g.facts.primsContained = contained && n > 0;
-    g.facts.opaqueShadows = opaque && n > 0;
+    g.facts.deriveFromCounts(); /* sceneFeatures, primsContained, opaqueShadows */
     g.scene.retagged();
     g.scene.arena.layOutAgain();
 }

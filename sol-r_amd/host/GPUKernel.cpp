@@ -365,23 +365,27 @@ void GPUKernel::setPrimitivesOnly(const SolrPrimitiveEdit *edits, int n)
     }
 }
 
+void GPUKernel::ensureSlotMap()
+{
+    if (m_slotOfUpload == m_resident.uploads)
+        return;
+    /* the flattened order of the resident scene: that of the upload, which the replays of syncHost keep */
+    int top = -1;
+    for (const Primitive &p : m_hPrimitives)
+        top = std::max(top, p.index);
+    m_slotOf.assign((size_t)(top + 1), -1);
+    for (size_t slot = 0; slot < m_hPrimitives.size(); ++slot)
+        if (m_hPrimitives[slot].index >= 0)
+        {
+            int &at = m_slotOf[(size_t)m_hPrimitives[slot].index];
+            at = (at == -1) ? (int)slot : -2;
+        }
+    m_slotOfUpload = m_resident.uploads;
+}
+
 bool GPUKernel::editSlots(const SolrPrimitiveEdit *edits, int n, std::vector<SolrPrimitiveEdit> &last, std::vector<int> &slots)
 {
-    if (m_slotOfUpload != m_resident.uploads)
-    {
-        /* the flattened order of the resident scene: that of the upload, which the replays of syncHost keep */
-        int top = -1;
-        for (const Primitive &p : m_hPrimitives)
-            top = std::max(top, p.index);
-        m_slotOf.assign((size_t)(top + 1), -1);
-        for (size_t slot = 0; slot < m_hPrimitives.size(); ++slot)
-            if (m_hPrimitives[slot].index >= 0)
-            {
-                int &at = m_slotOf[(size_t)m_hPrimitives[slot].index];
-                at = (at == -1) ? (int)slot : -2;
-            }
-        m_slotOfUpload = m_resident.uploads;
-    }
+    ensureSlotMap();
     auto finite3 = [](const vec3f &v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
     auto finite2 = [](const vec2f &v) { return std::isfinite(v.x) && std::isfinite(v.y); };
     const int nbLamps = frameAsIs().nbActiveLamps;
@@ -397,7 +401,11 @@ bool GPUKernel::editSlots(const SolrPrimitiveEdit *edits, int n, std::vector<Sol
         if (e.index < 0 || (size_t)e.index >= m_slotOf.size() || m_slotOf[(size_t)e.index] < 0)
             return false;
         const int slot = m_slotOf[(size_t)e.index];
-        if (slot < nbLamps || m_hPrimitives[(size_t)slot].materialId != e.materialId || e.materialId < 0 ||
+        /* (the material the primitive has now: what a material set left pending, else the flattened array's) */
+        const auto pendingMaterial = m_resident.pendingMaterials.find((unsigned int)e.index);
+        const int materialNow =
+            pendingMaterial != m_resident.pendingMaterials.end() ? pendingMaterial->second : m_hPrimitives[(size_t)slot].materialId;
+        if (slot < nbLamps || materialNow != e.materialId || e.materialId < 0 ||
             (size_t)e.materialId >= m_hMaterials.size() || m_hMaterials[(size_t)e.materialId].innerIllumination.x != 0.f)
             return false;
         if (!finite3(e.p0) || !finite3(e.p1) || !finite3(e.p2) || !finite3(e.size) || !finite3(e.n0) || !finite3(e.n1) ||
@@ -433,8 +441,69 @@ void GPUKernel::setPrimitiveMaterial(unsigned int index, int materialId)
         p->materialId = materialId;
 }
 
+int GPUKernel::setPrimitiveMaterials(const int *indices, const int *materialIds, int n)
+{
+    if (n == 0)
+        return 0;
+    if (!indices || !materialIds || n < 0)
+        return -1;
+    /* (which indices the store has is not a matter of what is pending: no move adds or removes a primitive) */
+    PrimitiveContainer &primitives = frameAsIs().primitives;
+    for (int i = 0; i < n; ++i)
+        if (indices[i] < 0 || !primitives.lookup((unsigned int)indices[i]))
+            return -1;
+    /* as for a batch of edits: the engine may set the materials of the scene it holds in place, and the host copy follows
+     * when somebody looks (syncHost).  A material set is never merely counted: what the engine hands back could not
+     * restore it */
+    if (m_resident.offers(m_frame) && m_resident.journalEditRecords + (size_t)n > ResidentScene::MAX_JOURNALLED_EDIT_RECORDS)
+        syncHost(); /* the journal's batches have grown large: replayed now, which leaves the fast path open */
+    if (m_resident.offers(m_frame) && m_resident.recordsEdits() && deviceSetPrimitiveMaterials(indices, materialIds, n))
+    {
+        m_resident.recordMaterials(indices, materialIds, n);
+        return 0;
+    }
+    frame();
+    m_resident.setTransfered(false);
+    for (int i = 0; i < n; ++i)
+        setPrimitiveMaterial((unsigned int)indices[i], materialIds[i]);
+    return 0;
+}
+
+bool GPUKernel::materialSlots(const int *indices, const int *materialIds, int n, std::vector<int> &slots, std::vector<int> &lastIds)
+{
+    ensureSlotMap();
+    const int nbLamps = frameAsIs().nbActiveLamps;
+    slots.clear();
+    lastIds.clear();
+    slots.reserve((size_t)n);
+    lastIds.reserve((size_t)n);
+    /* per slot the place of its record in `slots` + 1 (0: none yet) */
+    std::vector<int> placed(m_hPrimitives.size(), 0);
+    for (int i = 0; i < n; ++i)
+    {
+        if (indices[i] < 0 || (size_t)indices[i] >= m_slotOf.size() || m_slotOf[(size_t)indices[i]] < 0)
+            return false;
+        const int slot = m_slotOf[(size_t)indices[i]];
+        if (slot < nbLamps || materialIds[i] < 0 || materialIds[i] > m_nbActiveMaterials || (size_t)materialIds[i] >= m_hMaterials.size())
+            return false;
+        if (placed[(size_t)slot])
+            lastIds[(size_t)placed[(size_t)slot] - 1] = materialIds[i];
+        else
+        {
+            slots.push_back(slot);
+            lastIds.push_back(materialIds[i]);
+            placed[(size_t)slot] = (int)slots.size();
+        }
+    }
+    return true;
+}
+
 int GPUKernel::getPrimitiveMaterial(unsigned int index)
 {
+    /* a material that was set over there and is still pending: the journal knows it, the store need not wake */
+    const auto pending = m_resident.pendingMaterials.find(index);
+    if (pending != m_resident.pendingMaterials.end())
+        return pending->second;
     const CPUPrimitive *p = peekPrimitive(index);
     return p ? p->materialId : -1;
 }
@@ -1260,8 +1329,10 @@ int GPUKernel::morphKeyFrames(unsigned int frameA, unsigned int frameB, float we
     /* (a lamp that was moved over there: a morph there would put it back at its keys' place and leave its light record
      * behind, so such a morph is not offered to the engine - which would decline it, after the keys were handed over for
      * nothing - and the host route serves it.  Nor behind primitives that were set anew over there: the blend would
-     * leave their texture coordinates and movable flags as the edit set them, where the host loop takes the first key's) */
-    if (resident && !m_resident.lampMoved && !m_resident.edited && deviceMorphKeyFrames(frameA, frameB, weight, track))
+     * leave their texture coordinates and movable flags as the edit set them, where the host loop takes the first key's;
+     * nor behind materials that were set over there, which the blend would keep where the host loop takes the first key's) */
+    if (resident && !m_resident.lampMoved && !m_resident.edited && !m_resident.materialsSet &&
+        deviceMorphKeyFrames(frameA, frameB, weight, track))
     {
         /* every primitive has been set anew: what was pending before is superseded (no lamp move is among it) */
         m_resident.morphServed(frameA, frameB, weight);
@@ -1417,8 +1488,8 @@ void GPUKernel::syncHost()
     /* a handful of rotations and translations is replayed (4 ms each for 100 k primitives); a long animation is
      * fetched, and so is one whose moves were not all recorded.  A journal that holds an edit is always replayed: what
      * is fetched carries neither sizes nor texture coordinates, and not the primitives the store believes unmovable
-     * (all its moves are recorded: ResidentScene::offers) */
-    if ((nbHeavy <= 8 && !unrecorded) || pending.journalEdits || !primitivesFromDevice(f))
+     * (all its moves are recorded: ResidentScene::offers); nor does it carry materials, so a material set is replayed too */
+    if ((nbHeavy <= 8 && !unrecorded) || pending.nbReplayedOnly() || !primitivesFromDevice(f))
     {
         if (unrecorded)
             std::cerr << "GPUKernel::syncHost: the engine did not hand back its primitives and " << unrecorded
@@ -1439,6 +1510,12 @@ void GPUKernel::syncHost()
             case ResidentScene::Move::EDIT:
                 /* the setters; the boxes follow below, with everybody's */
                 setPrimitivesOnly(pending.editBatches[move.index].data(), (int)pending.editBatches[move.index].size());
+                break;
+            case ResidentScene::Move::MATERIALS:
+                /* the setter per record; no box follows a material */
+                for (const ResidentScene::MaterialSet &set : pending.materialBatches[move.index])
+                    if (CPUPrimitive *p = f.primitives.lookup(set.index))
+                        p->materialId = set.materialId;
                 break;
             case ResidentScene::Move::NB_KINDS:
                 break;

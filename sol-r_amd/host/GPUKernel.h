@@ -291,6 +291,7 @@ struct ResidentScene
             TRANSLATION, /* v: the translation */
             LAMP_MOVE,   /* v: the centre of primitive `index` */
             EDIT,        /* a batch of primitives set anew: editBatches[index] */
+            MATERIALS,   /* a batch of primitives' materials set: materialBatches[index] */
             NB_KINDS
         } kind;
         vec3f v, cosA, sinA;
@@ -327,6 +328,20 @@ struct ResidentScene
      * (GPUKernel::setPrimitives) - a replay, which leaves the fast path open */
     static constexpr size_t MAX_JOURNALLED_EDIT_RECORDS = size_t(1) << 20;
     size_t journalEditRecords = 0;
+    /* the batches of the journal's material sets, as given, and how many the journal holds.  What the engine hands back
+     * carries no material either: like an edit, a material set is always replayed and never merely counted, and its
+     * records count towards the same cap.  No box follows a material: such a journal alone refits nothing (refits) */
+    struct MaterialSet
+    {
+        unsigned int index;
+        int materialId;
+    };
+    std::vector<std::vector<MaterialSet>> materialBatches;
+    size_t journalMaterialSets = 0;
+    /* ... and per primitive the material the journal's sets leave it with, for whoever asks what a primitive's material is
+     * now without waking the store (getPrimitiveMaterial, editSlots) */
+    std::map<unsigned int, int> pendingMaterials;
+    bool materialsSet = false; /* materials were set over there since the upload (morphFrame) */
     bool morphPending = false;
     unsigned int pendingMorphKeys[2] = {0, 0}; /* the two key frames of the pending morph */
     float pendingMorphWeight = 0.f;
@@ -336,8 +351,10 @@ struct ResidentScene
      * flatten leaves the device with another frame than the current one) */
     bool offers(unsigned int f) const
     {
-        return primitivesTransfered && !touched && frame == (long)f && !(journalEdits && journal.size() >= MAX_RECORDED_MOVES);
+        return primitivesTransfered && !touched && frame == (long)f && !(nbReplayedOnly() && journal.size() >= MAX_RECORDED_MOVES);
     }
+    /* the moves of the journal that only a replay restores: edits and material sets */
+    size_t nbReplayedOnly() const { return journalEdits + journalMaterialSets; }
     /* ... and a batch of edits only while the journal records: an edit is never merely counted */
     bool recordsEdits() const { return journal.size() < MAX_RECORDED_MOVES; }
     bool holdsTrackKey(unsigned int f) const { return std::find(trackKeys.begin(), trackKeys.end(), f) != trackKeys.end(); }
@@ -372,6 +389,7 @@ struct ResidentScene
         frame = (long)f;
         lampMoved = false;
         edited = false;
+        materialsSet = false;
         ++uploads;
     }
     void setTransfered(bool value) { primitivesTransfered = value; }
@@ -401,6 +419,20 @@ struct ResidentScene
         ++journalEdits;
         journalEditRecords += (size_t)n;
     }
+    /* the engine has set these primitives' materials (offered only while recordsEdits): the batch as given, into the journal */
+    void recordMaterials(const int *indices, const int *materialIds, int n)
+    {
+        materialsSet = true;
+        materialBatches.emplace_back();
+        for (int i = 0; i < n; ++i)
+        {
+            materialBatches.back().push_back({(unsigned int)indices[i], materialIds[i]});
+            pendingMaterials[(unsigned int)indices[i]] = materialIds[i];
+        }
+        journal.push_back({Move::MATERIALS, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, (unsigned int)materialBatches.size() - 1});
+        ++journalMaterialSets;
+        journalEditRecords += (size_t)n;
+    }
     /* the store has been set anew, here (morphFrame's host route): nothing is pending */
     void clear()
     {
@@ -410,6 +442,9 @@ struct ResidentScene
         editBatches.clear();
         journalEdits = 0;
         journalEditRecords = 0;
+        materialBatches.clear();
+        journalMaterialSets = 0;
+        pendingMaterials.clear();
         morphPending = false;
     }
     /* ... or over there, by a morph of those two key frames at that weight: it supersedes what was pending before it */
@@ -528,6 +563,15 @@ public:
      * primitives there (deviceSetPrimitives); the host copy then lags behind by that batch, in the journal with the other
      * moves, and syncHost() catches it up.  Returns 0 when done; n == 0 is done and records nothing */
     int setPrimitives(const SolrPrimitiveEdit *edits, int n);
+    /* extension: a batch of primitives given another material - what a scene that marks or recolours some of its primitives
+     * does per frame with setPrimitiveMaterial (the reference's SwcScene::doAnimate: the sample before gets its material back,
+     * the next one the light material).  Every index is looked up first: one that is not in the store refuses the batch,
+     * -1, nothing changed.  Then per record, in order, setPrimitiveMaterial(index, materialId): of several records for one
+     * index the last one wins.  No box follows a material.  The caller flattens with compactBoxes(false), as after
+     * setPrimitives.  An engine that keeps the scene resident may set the materials there (deviceSetPrimitiveMaterials); the
+     * host copy then lags behind by that batch, in the journal with the other moves, and syncHost() catches it up;
+     * getPrimitiveMaterial answers what is pending.  Returns 0 when done; n == 0 is done and records nothing */
+    int setPrimitiveMaterials(const int *indices, const int *materialIds, int n);
     /* extension: the iso-surface of a field of metaballs appended as triangles - what the reference's MetaballsScene makes
      * per frame with two host loops and the fake-GL entry points (apps/scenes/animation/MetaballsScene.cpp:247-400).
      * balls: nbBalls records of x, y, z, squared radius.  The triangles come from the engine (the isoSurface hook) and are
@@ -778,11 +822,21 @@ protected:
     /* for that hook: the batch as the engine takes it - of several records for one index the last one only (setPrimitive
      * resets everything a record can set), each with the slot of its primitive in the flattened order, from a map made
      * once per upload.  False when the store's side of the engine's conditions fails: an index without exactly one slot,
-     * a slot among the lamps', another material than the primitive has (tags and colour keys are a join with the
-     * materials made at upload), an emissive material (the light record would have to follow), a float that is not finite */
+     * a slot among the lamps', another material than the primitive has now - with what is pending - (tags and colour keys
+     * are a join with the materials), an emissive material (the light record would have to follow), a float that is not finite */
     bool editSlots(const SolrPrimitiveEdit *edits, int n, std::vector<SolrPrimitiveEdit> &last, std::vector<int> &slots);
     /* setPrimitives' loop over the records (no box is updated) */
     void setPrimitivesOnly(const SolrPrimitiveEdit *edits, int n);
+    /* engine hook: give these primitives of the resident scene these materials (every index is in the store); false = not
+     * done, nothing changed */
+    virtual bool deviceSetPrimitiveMaterials(const int *, const int *, int) { return false; }
+    /* for that hook: the batch as the engine takes it - each slot of the flattened order once, with the material the last
+     * record for its primitive names.  False when the store's side of the engine's conditions fails: an index without
+     * exactly one slot, a slot among the lamps' (the light record carries the material), a material id that is negative or
+     * beyond the active ones */
+    bool materialSlots(const int *indices, const int *materialIds, int n, std::vector<int> &slots, std::vector<int> &lastIds);
+    /* store index -> slot of the flattened order of the resident scene (m_slotOf), made once per upload */
+    void ensureSlotMap();
     /* engine hook: the pixel stage of a JPEG texture (csrc/jpeg_pixels.h) - coefficient blocks as
      * ImageLoader::parseJPEG leaves them to frame.width * frame.height * 3 bytes in `rgb`.  Here: a loop on the CPU;
      * false = the engine failed (its error is pending) */

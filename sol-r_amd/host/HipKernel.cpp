@@ -263,6 +263,16 @@ bool HipKernel::deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n)
     return solr_hip_set_primitives(last.data(), slots.data(), (int)last.size(), m_sceneInfo.viewDistance) == 1;
 }
 
+bool HipKernel::deviceSetPrimitiveMaterials(const int *indices, const int *materialIds, int n)
+{
+    if (!m_deviceInitialized)
+        return false;
+    std::vector<int> slots, lastIds;
+    if (!materialSlots(indices, materialIds, n, slots, lastIds))
+        return false;
+    return solr_hip_set_primitive_materials(slots.data(), lastIds.data(), (int)slots.size()) == 1;
+}
+
 bool HipKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb)
 {
     if (solr_hip_device_count() < 1)
@@ -567,6 +577,15 @@ bool ReplayKernel::deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n)
     if (!editSlots(edits, n, last, slots))
         return false;
     ++m_claimedEdits;
+    return true;
+}
+
+bool ReplayKernel::deviceSetPrimitiveMaterials(const int *indices, const int *materialIds, int n)
+{
+    std::vector<int> slots, lastIds;
+    if (!materialSlots(indices, materialIds, n, slots, lastIds))
+        return false;
+    ++m_claimedMaterialSets;
     return true;
 }
 

@@ -70,6 +70,9 @@ protected:
     bool deviceMoveLamp(int slot, const vec3f &center) override;
     /* setPrimitives on the resident scene, solr_hip_set_primitives (include/solr_hip.h): store indices to slots first */
     bool deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n) override;
+    /* setPrimitiveMaterials on the resident scene, solr_hip_set_primitive_materials (include/solr_hip.h): store indices to
+     * slots first, each slot once */
+    bool deviceSetPrimitiveMaterials(const int *indices, const int *materialIds, int n) override;
     void fetchPrimitiveIds() override;
     void fetchBitmap() override;
     bool primitivesFromDevice(Frame &f) override;
@@ -132,6 +135,7 @@ public:
     int nbClaimedTranslations() const { return m_claimedTranslations; }
     int nbClaimedLampMoves() const { return m_claimedLampMoves; }
     int nbClaimedEdits() const { return m_claimedEdits; }
+    int nbClaimedMaterialSets() const { return m_claimedMaterialSets; }
 
 protected:
     bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) override;
@@ -144,8 +148,11 @@ protected:
     bool deviceMoveLamp(int slot, const vec3f &center) override;
     /* (claimed where the store's side of the engine's conditions holds: GPUKernel::editSlots) */
     bool deviceSetPrimitives(const SolrPrimitiveEdit *edits, int n) override;
+    /* (claimed where the store's side of the engine's conditions holds: GPUKernel::materialSlots) */
+    bool deviceSetPrimitiveMaterials(const int *indices, const int *materialIds, int n) override;
 
 private:
+    int m_claimedMaterialSets = 0;
     int m_claimed = 0, m_claimedMorphs = 0, m_claimedTranslations = 0, m_claimedLampMoves = 0, m_claimedEdits = 0;
     int m_claimedTrackMorphs = 0, m_claimedTrackKeys = 0;
 };

@@ -373,6 +373,9 @@ int SolR_LoadOBJModel(char *filename, int materialId, int autoScale, double scal
     return (int)SingletonKernel::kernel()->getNbActivePrimitives();
 }
 
+/* the samples of the morphology SolRx_LoadSWCMorphology read last (SolRx_GetMorphologies) */
+static solr::Morphologies gMorphologies;
+
 int SolRx_LoadSWCMorphology(const char *filename, double px, double py, double pz, double sx, double sy, double sz,
                             double sw, int materialId)
 {
@@ -380,7 +383,23 @@ int SolRx_LoadSWCMorphology(const char *filename, double px, double py, double p
     reader.loadMorphologyFromFile(filename ? filename : "", *SingletonKernel::kernel(),
                                   solr::make_vec4f((float)px, (float)py, (float)pz),
                                   solr::make_vec4f((float)sx, (float)sy, (float)sz, (float)sw), materialId);
-    return (int)reader.getMorphologies().size();
+    gMorphologies = reader.getMorphologies();
+    return (int)gMorphologies.size();
+}
+
+int SolRx_GetMorphologies(SolrSwcSample *samples, int capacity)
+{
+    int n = 0;
+    for (const auto &entry : gMorphologies)
+    {
+        if (samples && n < capacity)
+        {
+            const solr::Morphology &m = entry.second;
+            samples[n] = {entry.first, m.branch, m.x, m.y, m.z, m.radius, m.parent, m.primitiveId};
+        }
+        ++n;
+    }
+    return n;
 }
 
 int SolR_SaveToFile(char *filename)
@@ -477,6 +496,17 @@ int SolRx_SetPrimitiveCenter(int index, double x, double y, double z)
 int SolRx_SetPrimitives(const SolrPrimitiveEdit *edits, int n)
 {
     const int status = SingletonKernel::kernel()->setPrimitives(edits, n);
+    if (status == 0 && n > 0)
+        SingletonKernel::kernel()->compactBoxes(false);
+    return status;
+}
+
+/* Extension: GPUKernel::setPrimitiveMaterials + compactBoxes(false): a batch of primitives given another material, what a
+ * scene that marks some of its primitives does per frame (apps/scenes/science/SwcScene.cpp doAnimate).  -1: an index is not
+ * in the store, nothing changed */
+int SolRx_SetPrimitiveMaterials(const int *indices, const int *materialIds, int n)
+{
+    const int status = SingletonKernel::kernel()->setPrimitiveMaterials(indices, materialIds, n);
     if (status == 0 && n > 0)
         SingletonKernel::kernel()->compactBoxes(false);
     return status;

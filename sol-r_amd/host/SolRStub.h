@@ -108,6 +108,17 @@ int SolR_LoadOBJModel(char *filename, int materialId, int autoScale, double scal
  * returns the number of samples read. */
 int SolRx_LoadSWCMorphology(const char *filename, double px, double py, double pz, double sx, double sy, double sz,
                             double sw, int materialId);
+/* ... and the samples the reader kept of the morphology loaded last (SWCReader::getMorphologies, what the reference's
+ * SwcScene walks along), by ascending id: coordinates and radius as scaled by the load, primitiveId the primitive the reader
+ * stored with the sample (the root's sphere, the cylinder of a sample that has children below the root's; 0 where it made
+ * none).  Writes the first min(count, capacity) records and returns the count; samples == NULL: the count alone */
+typedef struct SolrSwcSample
+{
+    int id, branch;
+    float x, y, z, radius;
+    int parent, primitiveId;
+} SolrSwcSample;
+int SolRx_GetMorphologies(SolrSwcSample *samples, int capacity);
 int SolR_SaveToFile(char *filename);
 int SolR_LoadFromFile(char *filename, double scale);
 
@@ -221,6 +232,12 @@ int SolRx_SetPrimitiveCenter(int index, double x, double y, double z);
  * and an unchanged resident scene the batch is applied on the device and counts among SolRx_PendingMoves.  0 = done, -1 =
  * an index is not in the store: nothing changed.  SolRx_SizeofPrimitiveEdit: the record's size, for bindings */
 int SolRx_SetPrimitives(const SolrPrimitiveEdit *edits, int n);
+/* a batch of primitives of the store given another material (GPUKernel::setPrimitiveMaterials: per record
+ * setPrimitiveMaterial, of several records for one index the last one wins) + compactBoxes(false): what the reference's
+ * SwcScene does per frame, a viewer to highlight a picked primitive, a molecule scene to recolour atoms.  With the HIP engine
+ * and an unchanged resident scene the batch is applied on the device and counts among SolRx_PendingMoves;
+ * SolR_GetPrimitiveMaterial answers what is pending.  0 = done, -1 = an index is not in the store: nothing changed */
+int SolRx_SetPrimitiveMaterials(const int *indices, const int *materialIds, int n);
 int SolRx_SizeofPrimitiveEdit();
 int SolRx_PendingMoves();
 int SolRx_SyncHost();

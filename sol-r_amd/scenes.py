@@ -211,6 +211,37 @@ def swc_morphology(k, path, width=1920, height=1080, iterations=3, scale=40.0, *
     return n
 
 
+def swc_walk(k, samples, lamp, light_material, step, state):
+    """One frame of the reference's SwcScene::doAnimate (apps/scenes/science/SwcScene.cpp:66-89): the primitive marked by
+    the frame before gets its material back, the primitive of sample `step % len(samples)` gets `light_material`, and the
+    lamp - primitive `lamp`, SolR_GetLight(0) - is moved next to that sample, to (x, y, z - 50) in binary32; both requests
+    flatten with compactBoxes(false).  samples: Kernel.swc_samples().  The reference looks the sample up by that number as
+    its id; an id the morphology has none for reads as a sample of zeros there (primitive 0 at the origin), and so it does
+    here.  state: a dict the caller keeps between the frames, empty before the first; it holds what is marked and, read once
+    before anything is pending, the materials of the samples' primitives - valid while nobody else sets those.  With the HIP
+    engine and an untouched resident scene both requests run on the device (Kernel.set_primitive_materials,
+    Kernel.set_primitive_center).  Returns the index of the primitive that is marked now."""
+    import numpy as np
+    if "materials" not in state:
+        state["by_id"] = {int(s["id"]): s for s in samples}
+        state["materials"] = {p: k.get_primitive_material(p) for p in sorted({0} | {int(s["primitiveId"]) for s in samples})}
+        state["marked"] = None
+    sample = state["by_id"].get(step % max(len(samples), 1))
+    primitive = int(sample["primitiveId"]) if sample is not None else 0
+    x, y, z = (np.float32(sample[c]) if sample is not None else np.float32(0.0) for c in "xyz")
+    indices, materials = [], []
+    if state["marked"] is not None:
+        indices.append(state["marked"])
+        materials.append(state["materials"][state["marked"]])
+    indices.append(primitive)
+    materials.append(light_material)
+    if k.set_primitive_materials(indices, materials) != 0:
+        raise RuntimeError("swc_walk: primitive %s is not in the store" % indices)
+    state["marked"] = primitive
+    k.set_primitive_center(lamp, (float(x), float(y), float(np.float32(z - np.float32(50.0)))))
+    return primitive
+
+
 def pdb_molecule(k, path, width=1920, height=1080, iterations=3, geometry_type=3, scale=200.0, **scene_info):
     """A scene around a PDB molecule (reference: PDBReader::loadAtomsFromFile as its MoleculeScene calls it:
     atom size 100, stick size 10, scale 200, materials by element; light at (-5000, 5000, -15000))."""
