@@ -685,7 +685,48 @@ int solr_hip_device_edits(void);
 int solr_hip_set_primitive_materials(const int *slots, const int *materialIds, int n);
 int solr_hip_device_material_sets(void);
 
-/* Bytes of HBM this engine currently holds for {scene planes, materials,
+/* An animation of whole meshes: the reference's AnimationScene loads one OBJ file per frame, every frame a mesh of its own with
+ * its own primitive count and its own tree, and shows them with setFrame + compactBoxes(false) once per displayed frame
+ * (apps/scenes/animation/AnimationScene.cpp:55-109) - a flatten, a walk-order list and a full upload per displayed frame, and
+ * the order-free lists, thin copies and sorted copies are dropped before they are made.  The scene bank keeps the scenes the
+ * engine has been given, one per key (the host's frame number), and puts one back with no upload:
+ *   solr_hip_park_scene         sets the resident scene - what h2d_scene, h2d_lightInformation and solr_hip_set_movable
+ *                               made, with everything derived from it or applied to it since: the arena, the node lists
+ *                               with their thin and sorted copies, the leaf records, the refit plan, the movable flags, the
+ *                               light records, the facts of the scene, the order-free lists or their countdown, the morph
+ *                               keys, every move served on the device - aside under `key` >= 0.  The records are moved:
+ *                               nothing is copied, launched, freed or waited for, and a frame in flight that still reads
+ *                               the arena finishes.  The engine then holds no scene, as after initialize_scene.  A scene
+ *                               already parked under `key` is dropped first.  Returns 1 when parked, 0 when declined - no
+ *                               resident scene, an error pending, or the bank would hold more than its limit: nothing
+ *                               changed, the scene stays resident and the next h2d_scene replaces it as ever.  With several
+ *                               in-process devices every engine parks or none does;
+ *   solr_hip_resume_scene       makes the scene parked under `key` the resident one and takes it out of the bank; 0 when
+ *                               there is none (not an error).  A scene that is resident at that moment goes as h2d_scene
+ *                               would drop it - that alone waits for the frames in flight; a host that wants it parks it
+ *                               first.  After an h2d_materials since the park the scene is pulled, retagged and laid out
+ *                               again under the new table, as h2d_materials does it for the resident scene: slower than a
+ *                               plain resume, and still no flatten and no list build.  The texture atlas, the materials and
+ *                               the randoms are the engine's, not a scene's;
+ *   solr_hip_drop_parked_scenes drops the scene parked under `key`, or every one with -1 (waits for the frames in flight,
+ *                               then frees).  initialize_scene, finalize_scene and solr_hip_set_variant drop them all;
+ *   solr_hip_set_scene_bank_bytes  the most the parked scenes may hold; 0, the default: every park is declined.  Lowering it
+ *                               drops nothing;
+ *   solr_hip_parked_scenes      how many scenes are parked;
+ *   solr_hip_parked_bytes       the bytes of every device buffer they own (morph keys and staged order-free lists too);
+ *   solr_hip_scene_switches     how many resumes were served since initialize_scene;
+ *   solr_hip_scene_uploads      how many h2d_scene calls were served since initialize_scene.
+ * solr_hip_device_rotations and its siblings count for the engine and go on counting across parks and resumes. */
+int solr_hip_park_scene(int key);
+int solr_hip_resume_scene(int key);
+void solr_hip_drop_parked_scenes(int key);
+void solr_hip_set_scene_bank_bytes(unsigned long long bytes);
+int solr_hip_parked_scenes(void);
+unsigned long long solr_hip_parked_bytes(void);
+int solr_hip_scene_switches(void);
+int solr_hip_scene_uploads(void);
+
+/* Bytes of HBM (the resident scene's, not the parked ones': solr_hip_parked_bytes) this engine currently holds for {scene planes, materials,
  * textures, per-pixel buffers}; for DESIGN.md's layout table and tests. */
 void solr_hip_memory_usage(unsigned long long bytes[4]);
 

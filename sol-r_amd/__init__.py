@@ -297,6 +297,15 @@ def _declare_hip(L):
     L.solr_hip_set_primitive_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.solr_hip_set_primitive_materials.restype = C.c_int
     L.solr_hip_device_material_sets.restype = C.c_int
+    for name in ("solr_hip_park_scene", "solr_hip_resume_scene", "solr_hip_drop_parked_scenes"):
+        getattr(L, name).argtypes = [C.c_int]
+    for name in ("solr_hip_park_scene", "solr_hip_resume_scene", "solr_hip_parked_scenes", "solr_hip_scene_switches",
+                 "solr_hip_scene_uploads"):
+        getattr(L, name).restype = C.c_int
+    L.solr_hip_drop_parked_scenes.restype = None
+    L.solr_hip_set_scene_bank_bytes.argtypes = [C.c_ulonglong]
+    L.solr_hip_set_scene_bank_bytes.restype = None
+    L.solr_hip_parked_bytes.restype = C.c_ulonglong
     L.solr_hip_read_nodes.argtypes = [C.c_int, C.c_void_p, C.c_int]
     L.solr_hip_read_nodes.restype = C.c_int
     L.solr_hip_read_primitives.argtypes = [C.c_void_p, C.c_int]
@@ -398,6 +407,10 @@ def _declare_host(L):
     L.SolRx_TranslatePrimitives.argtypes = [d, d, d]
     L.SolRx_SetPrimitiveCenter.argtypes = [i, d, d, d]
     L.SolRx_PendingMoves.restype = i
+    L.SolRx_SetFrameBank.argtypes = [C.c_ulonglong]
+    L.SolRx_SetFrameBank.restype = i
+    for name in ("SolRx_ParkedFrames", "SolRx_FrameSwitches", "SolRx_SceneUploads"):
+        getattr(L, name).restype = i
     L.SolRx_SetPrimitives.argtypes = [C.c_void_p, i]
     L.SolRx_SetPrimitives.restype = i
     L.SolRx_SizeofPrimitiveEdit.restype = i
@@ -702,6 +715,27 @@ class Kernel:
     def set_frame(self, frame):
         """GPUKernel::setFrame: the frame that primitives are added to, flattened and rendered; returns it"""
         return self.L.SolRx_SetFrame(frame)
+
+    def set_frame_bank(self, nbytes):
+        """The frame bank (SolRx_SetFrameBank): an animation of whole meshes, one per frame, is shown with set_frame +
+        compact_boxes(False) - a flatten and a full upload per displayed frame.  With nbytes > 0 a frame the HIP engine
+        holds untouched is set aside when set_frame leaves it - up to nbytes of device memory for all of them - and put
+        back when it is entered again: nothing is flattened, uploaded or launched, and everything made for that scene
+        (lists, copies, morph keys, moves applied on the device) comes back with it.  0, the default: off."""
+        return self.L.SolRx_SetFrameBank(int(nbytes))
+
+    def parked_frames(self):
+        """frames the frame bank holds now (never the current one)"""
+        return self.L.SolRx_ParkedFrames()
+
+    def frame_switches(self):
+        """frame switches served from the frame bank since the kernel was made"""
+        return self.L.SolRx_FrameSwitches()
+
+    def scene_uploads(self):
+        """uploads of the scene to the engine since the kernel was made (the host-replay double counts those a real
+        engine would make)"""
+        return self.L.SolRx_SceneUploads()
 
     def morph_primitives(self):
         """GPUKernel::morphPrimitives: every frame between the key frames rebuilt as their blend at weight

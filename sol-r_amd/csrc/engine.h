@@ -3,7 +3,8 @@
  * solr_hip.hip (the boundary), solr_uploads.hip (the h2d_* uploads), solr_arena.hip (the arena and the node lists; their
  * host builders: list_builders.h), solr_rotation.hip (rotation and refit on the device), solr_morph.hip (key-frame
  * morphing on the device), solr_moves.hip (translation and lamp moves on the device), solr_edits.hip (primitives set anew on
- * the device), solr_materials.hip (primitives' materials set on the device), solr_launch.hip (the renderer's
+ * the device), solr_materials.hip (primitives' materials set on the device), solr_bank.hip (resident scenes set aside
+ * and put back), solr_launch.hip (the renderer's
  * launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined read-back), solr_rccl.hip (strips,
  * communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
@@ -26,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/solr_hip.h"
@@ -517,6 +519,42 @@ struct Scene
     long retags = 0; /* how often retagPrimitives has run: what was derived from the tags is as old as that */
     Arena arena;
 
+    /* the requests served since initialize_scene (solr_hip_device_rotations and its siblings): they count for the engine,
+     * not for the scene that happens to be resident, and are carried from record to record when scenes change places
+     * (ParkedScene) */
+    struct Served
+    {
+        int rotations, translations, lampMoves, edits, materialSets, morphs, trackMorphs;
+    };
+    Served served() const
+    {
+        return {rotation.nbDeviceRotations, rotation.nbDeviceTranslations, rotation.nbDeviceLampMoves, rotation.nbDeviceEdits,
+                rotation.nbDeviceMaterialSets, morph.nbDeviceMorphs, morph.nbDeviceTrackMorphs};
+    }
+    void servedCarried(const Served &s)
+    {
+        rotation.nbDeviceRotations = s.rotations;
+        rotation.nbDeviceTranslations = s.translations;
+        rotation.nbDeviceLampMoves = s.lampMoves;
+        rotation.nbDeviceEdits = s.edits;
+        rotation.nbDeviceMaterialSets = s.materialSets;
+        morph.nbDeviceMorphs = s.morphs;
+        morph.nbDeviceTrackMorphs = s.trackMorphs;
+    }
+    /* every byte of device memory the record owns (the staged order-free lists by what the builder leaves per node:
+     * lists_device.h) */
+    size_t deviceBytes() const
+    {
+        size_t bytes = arena.geometry.bytes + lamps.bytes + rotation.movable.bytes + rotation.refitPlan.bytes +
+                       rotation.enclosesFlag.bytes + rotation.edits.bytes + rotation.materialSets.bytes + morph.lampFlag.bytes;
+        for (const MorphKey &key : morph.keys)
+            bytes += key.planes.bytes;
+        const size_t nodes = orderFree.nodes();
+        bytes += (lists.freeStage.rows ? nodes * 32 : 0) + (lists.freeStage.start ? nodes * 4 : 0) +
+                 (lists.freeStage.origin ? nodes * 4 : 0);
+        return bytes;
+    }
+
     /* h2d_scene has new host images of the lists and the primitives (swapped in by the caller): nothing that was made
      * from the old ones holds.  The movable flags and the morph keys go, the counts of rotations and morphs stay; the
      * arena follows with retagPrimitives (layOutAgain) */
@@ -751,6 +789,7 @@ struct Materials
     std::vector<int> materialTags;      /* PRIM_* bits per material id */
     std::vector<float> materialAverage; /* (r + g + b) / 3.f per material id (plane colour key, GI:561) */
     std::vector<TextureUse> textureUses;
+    long generation = 0; /* how often h2dMaterialsOne has run: a scene's tags are those of one table (ParkedScene) */
     void release()
     {
         solreng::release(table);
@@ -829,6 +868,71 @@ struct SceneFacts
                 sceneFeatures |= 1 << bit;
     }
 };
+/* A resident scene set aside (solr_hip_park_scene, solr_bank.hip): the three records h2d_scene, h2d_lightInformation and
+ * retagPrimitives write, moved - a DeviceBuffer is a plain pointer, the vectors move - with everything made from them or
+ * applied to them since.  Nothing is copied, launched, freed or waited for: a frame in flight that still reads the arena
+ * finishes, because the arena stays allocated.  The two transitions leave the counts of requests served with the engine. */
+struct ParkedScene
+{
+    int key = -1;
+    Scene scene;
+    Lights lights;
+    SceneFacts facts;
+    long materialsGeneration = 0; /* Materials::generation the tags were joined under */
+    size_t bytes = 0;             /* Scene::deviceBytes when it was parked */
+    /* the resident records move in; the engine holds no scene, as after initialize_scene */
+    void park(int key_, Scene &resident, Lights &residentLights, SceneFacts &residentFacts, long generation)
+    {
+        const Scene::Served served = resident.served();
+        key = key_;
+        bytes = resident.deviceBytes();
+        materialsGeneration = generation;
+        scene = std::move(resident);
+        lights = std::move(residentLights);
+        facts = residentFacts;
+        resident = Scene();
+        resident.servedCarried(served);
+        residentLights = Lights();
+        residentFacts = SceneFacts();
+    }
+    /* ... and out again, over records that hold no buffer (the caller has released them) */
+    void resume(Scene &resident, Lights &residentLights, SceneFacts &residentFacts)
+    {
+        const Scene::Served served = resident.served();
+        resident = std::move(scene);
+        resident.servedCarried(served);
+        residentLights = std::move(lights);
+        residentFacts = facts;
+        scene = Scene();
+        lights = Lights();
+        facts = SceneFacts();
+        bytes = 0;
+        key = -1;
+    }
+};
+/* The scene bank (solr_bank.hip): the parked scenes of this engine, its limit - a knob - and what it has counted since
+ * initialize_scene */
+struct SceneBank
+{
+    std::vector<ParkedScene> parked;
+    unsigned long long limitBytes = 0; /* solr_hip_set_scene_bank_bytes; 0: every park is declined */
+    int nbSwitches = 0;                /* resumes served */
+    int nbUploads = 0;                 /* h2d_scene calls served */
+    int find(int key) const
+    {
+        for (size_t i = 0; i < parked.size(); ++i)
+            if (parked[i].key == key)
+                return (int)i;
+        return -1;
+    }
+    unsigned long long bytes() const
+    {
+        unsigned long long sum = 0;
+        for (const ParkedScene &p : parked)
+            sum += p.bytes;
+        return sum;
+    }
+};
 /* The kernel timer (solr_hip_enable_timing: Engine::timing; solr_launch.hip, solr_diag.hip) */
 struct KernelTimer
 {
@@ -884,6 +988,7 @@ struct Engine
     Textures textures;
     Randoms randoms;
     SceneFacts facts;
+    SceneBank bank; /* the scenes set aside (its limit is a knob) */
 
     DeviceBuffer counters, tileClock;
     /* ambient occlusion across strips: the depths of the neighbours' rows a host hands over itself (the ones traded over
@@ -1064,6 +1169,7 @@ void h2dRandomsSizedOne(const float *randoms, long count);
 void h2dTexturesOne(int activeTextures, TextureInfo *textureInfos);
 void h2dLightInformationOne(LightInformation *lightInformation, int lightInformationSize);
 void setMovableOne(const unsigned char *flags, int nbPrimitives);
+void retagPrimitives();
 void checkTextureTables();
 /* solr_arena.hip: the arena the scene is resident in, its lists, what a frame is told of them */
 void maybeBuildOrderFreeLists();
@@ -1105,6 +1211,8 @@ int setPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, fl
 /* solr_materials.hip: a batch of primitives' materials set on the device */
 bool canSetPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n);
 int setPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n);
+/* solr_bank.hip: resident scenes set aside and put back */
+void dropParkedOne(int key); /* (-1: all of them; waits for the frames in flight first, the only call of the bank that frees) */
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */
 void allocateFrame();
 int neededFeatures(const SceneInfo &sceneInfo, bool full);

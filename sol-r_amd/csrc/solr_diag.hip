@@ -539,6 +539,9 @@ int solr_hip_short_ray_lists(void)
 void solr_hip_set_variant(int variant)
 {
     onEveryDevice([&](int) {
+        /* several variants change how lists are built "at the next h2d_scene": a parked scene would come back with the lists
+         * of another variant, so the bank goes (nothing to do, and nothing waited for, while it is empty) */
+        dropParkedOne(-1);
         if ((g.variant == VARIANT_UPLOADED_BUILD_BOXES) != (variant == VARIANT_UPLOADED_BUILD_BOXES))
             g.scene.orderFreeBuildAgain();
         /* (VARIANT_UPLOADED_SPHERE_LEAVES set or taken back: the next frame has the thin copies made again - prepareScene) */

@@ -2,8 +2,9 @@
  * solr_hip.hip - the C ABI of the MI355X rendering engine (include/solr_hip.h): the reference's ten entry points
  * (CudaRayTracer.h:25-67) once per in-process device, device / stream / strip selection, the life of an engine
  * (initialize_scene ... finalize_scene).  The rest of the engine's host side: engine.h (state), solr_uploads.hip,
- * solr_arena.hip, solr_rotation.hip, solr_morph.hip, solr_moves.hip, solr_edits.hip and solr_materials.hip (the resident scene: its
- * uploads, its arena and lists, rotation, morphing, translation, lamp moves, edited primitives and materials set on the device),
+ * solr_arena.hip, solr_rotation.hip, solr_morph.hip, solr_moves.hip, solr_edits.hip, solr_materials.hip and solr_bank.hip (the
+ * resident scene: its uploads, its arena and lists, rotation, morphing, translation, lamp moves, edited primitives and materials set
+ * on the device, scenes set aside and put back),
  * solr_launch.hip (a frame), solr_post.hip, solr_image_ring.hip, solr_rccl.hip, solr_diag.hip; the kernels: rt_device.h,
  * renderer_kernel.h, rows/.  gfx950 only.
  */
@@ -234,6 +235,8 @@ static void initializeOne(const SceneInfo &sceneInfo)
                 HIPCHECK(hipStreamCreate(&g.flight[f].stream));
     }
     g.initialized = ok();
+    dropParkedOne(-1); /* (an engine that was up already: its bank is of the scene before) */
+    g.bank.nbSwitches = g.bank.nbUploads = 0;
     g.width = sceneInfo.size.x;
     g.height = sceneInfo.size.y;
 }
@@ -275,6 +278,8 @@ static void finalizeOne()
     /* the scene: every record back to what initialize_scene finds (the knobs stay).  The staged lists go before the
      * builders' scratch */
     g.scene.lists.dropStage(true);
+    dropParkedOne(-1);
+    g.bank.nbSwitches = g.bank.nbUploads = 0;
     {
         SolrScratchPool &pool = solrScratchPool(); /* the builders' scratch goes with the scene */
         std::lock_guard<std::mutex> nobodyBuilding(pool.busy);
@@ -350,6 +355,7 @@ void ensureEngines(int n)
         e.flights = gFirst.flights;
         e.sched.mode = gFirst.sched.mode;
         e.timing = gFirst.timing;
+        e.bank.limitBytes = gFirst.bank.limitBytes;
     }
 }
 

@@ -265,6 +265,7 @@ void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primi
     {
         g.scene.nbPrimitives = nbPrimitives;
         g.scene.nbLamps = nbLamps;
+        ++g.bank.nbUploads;
     }
 }
 
@@ -313,6 +314,7 @@ void h2dMaterialsOne(Material *materials, int nbActiveMaterials)
     g.materials.materialAverage.assign(capacity, 0.f);
     g.materials.textureUses.clear();
     g.textures.textureTablesChecked = false;
+    ++g.materials.generation; /* (a parked scene keeps the tags of the table it was parked under: solr_bank.hip) */
     for (int i = 0; i < nbActiveMaterials && i < capacity; ++i)
     {
         Material m = materials[i];

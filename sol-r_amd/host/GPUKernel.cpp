@@ -135,6 +135,7 @@ void GPUKernel::initBuffers()
 /* reference: GPUKernel.cpp:372-471 */
 void GPUKernel::cleanup()
 {
+    dropFrameBank();
     m_frames.clear();
     for (unsigned int f = 0; f < 1; ++f)
     {
@@ -156,7 +157,7 @@ void GPUKernel::cleanup()
     m_nbActiveMaterials = -1;
     m_nbActiveTextures = 0;
     m_textureFilenames.clear();
-    m_materialsTransfered = false;
+    materialsChanged();
     m_resident.setTransfered(false);
     m_texturesTransfered = false;
     m_randomsTransfered = false;
@@ -773,6 +774,9 @@ int GPUKernel::compactBoxes(bool reconstructBoxes)
      * what the lines below would produce and upload */
     if (!reconstructBoxes && m_resident.lags())
         return frameAsIs().nbActiveBoxes;
+    /* ... and so it is when the frame has come back from the frame bank and nothing has touched it since */
+    if (!reconstructBoxes && m_resident.asResumed(m_frame) && m_flattenedSerial == m_materialsSerial)
+        return frameAsIs().nbActiveBoxes;
     m_resident.setTransfered(false);
     if (reconstructBoxes)
     {
@@ -960,6 +964,8 @@ bool GPUKernel::buildTreeOnDevice()
     for (const BoundingBox &b : m_hBoundingBoxes)
         m_maxPrimitivesPerBox = std::max(m_maxPrimitivesPerBox, (size_t)std::max(b.nbPrimitives, 0));
     m_frames[m_frame].levelsBuilt = false; /* the maps follow when somebody needs them (frame()) */
+    m_flattenDue = false;
+    m_flattenedSerial = m_materialsSerial;
     phase.mark("compactBoxes: flattened arrays");
     return true;
 }
@@ -1031,6 +1037,8 @@ void GPUKernel::streamDataToGPU()
 {
     Frame &f = frame();
     m_resident.setTransfered(false);
+    m_flattenDue = false;
+    m_flattenedSerial = m_materialsSerial; /* (the light records below take the materials' colours as they are now) */
     f.nbActiveBoxes = 0;
     f.nbActivePrimitives = 0;
     f.nbActiveLamps = 0;
@@ -1106,17 +1114,121 @@ void GPUKernel::streamDataToGPU()
 /* reference: GPUKernel.cpp:2764-2775 */
 void GPUKernel::nextFrame()
 {
-    syncHost();
-    ++m_frame;
-    if (m_frame >= m_nbFrames)
-        m_frame = m_nbFrames ? m_nbFrames - 1 : 0;
+    unsigned int next = m_frame + 1;
+    if (next >= m_nbFrames)
+        next = m_nbFrames ? m_nbFrames - 1 : 0;
+    switchFrame(next);
 }
 
 void GPUKernel::previousFrame()
 {
+    switchFrame(m_frame > 0 ? m_frame - 1 : m_frame);
+}
+
+/* The frame bank (GPUKernel.h setFrameBank).  What is parked never lags - the store is caught up first, and its Replaying
+ * guard keeps `primitivesTransfered` and `touched` as they were, so a sync does not end the fast path - hence nothing that
+ * reads another frame's store (morphKey, morphPrimitives, saveToFile) can see a stale one. */
+void GPUKernel::switchFrame(unsigned int frame)
+{
     syncHost();
-    if (m_frame > 0)
-        --m_frame;
+    if (frame == m_frame)
+        return;
+    if (m_frameBankBytes == 0)
+    {
+        m_frame = frame; /* the device still holds the frame that is left, until the next upload */
+        return;
+    }
+    /* the frame that is left: aside when the engine holds it untouched and no material has changed since it was flattened
+     * (its light records, here and over there, carry the materials' colours), else as ever */
+    bool parked = false;
+    m_parked.erase(m_frame);
+    if (m_resident.offers(m_frame) && m_flattenedSerial == m_materialsSerial && deviceParkScene(m_frame))
+    {
+        ParkedFrame &record = m_parked[m_frame];
+        record.resident = std::move(m_resident);
+        record.boundingBoxes.swap(m_hBoundingBoxes);
+        record.primitives.swap(m_hPrimitives);
+        record.lamps.swap(m_hLamps);
+        record.movable.swap(m_hMovable);
+        record.lightInformation.swap(m_lightInformation);
+        record.lightInformationSize = m_lightInformationSize;
+        record.maxPrimitivesPerBox = m_maxPrimitivesPerBox;
+        record.materialsSerial = m_flattenedSerial;
+        parked = true;
+    }
+    m_frame = frame;
+    /* the frame that is entered: back from the bank when it is there and no material has changed since (the light
+     * records of the flattened frame carry the materials' colours: such a frame is flattened and uploaded again) */
+    auto held = m_parked.find(frame);
+    if (held != m_parked.end() && held->second.materialsSerial != m_materialsSerial)
+    {
+        deviceDropParked((long)frame);
+        m_parked.erase(held);
+        held = m_parked.end();
+    }
+    if (held != m_parked.end())
+    {
+        if (deviceResumeScene(frame))
+        {
+            ParkedFrame &record = held->second;
+            m_resident = std::move(record.resident);
+            m_hBoundingBoxes.swap(record.boundingBoxes);
+            m_hPrimitives.swap(record.primitives);
+            m_hLamps.swap(record.lamps);
+            m_hMovable.swap(record.movable);
+            m_lightInformation.swap(record.lightInformation);
+            m_lightInformationSize = record.lightInformationSize;
+            m_maxPrimitivesPerBox = record.maxPrimitivesPerBox;
+            m_flattenedSerial = record.materialsSerial;
+            m_parked.erase(held);
+            m_resident.resumedFromBank();
+            m_flattenDue = false;
+            ++m_nbFrameSwitches;
+            return;
+        }
+        dropFrameBank(); /* the two sides disagree about what is parked */
+    }
+    if (parked)
+    {
+        m_resident = ResidentScene(); /* nothing uploaded, frame == -1 */
+        m_flattenDue = true;          /* ... and nothing flattened: compactBoxes(false), or the next frame, does it */
+        m_hBoundingBoxes.clear();
+        m_hPrimitives.clear();
+        m_hLamps.clear();
+        m_hMovable.clear();
+        m_lightInformation.clear();
+        m_lightInformationSize = 0;
+    }
+}
+
+void GPUKernel::setFrameBank(unsigned long long bytes)
+{
+    if (bytes == 0 && m_frameBankBytes != 0)
+        dropFrameBank();
+    m_frameBankBytes = bytes;
+    deviceSetBankBytes(bytes);
+}
+
+void GPUKernel::dropFrameBank()
+{
+    if (m_parked.empty())
+        return;
+    m_parked.clear();
+    deviceDropParked(-1);
+}
+
+void GPUKernel::setNbFrames(const int nbFrames)
+{
+    m_nbFrames = nbFrames;
+    /* a parked frame whose number is no frame any more */
+    for (auto it = m_parked.begin(); it != m_parked.end();)
+        if (it->first >= m_nbFrames)
+        {
+            deviceDropParked((long)it->first);
+            it = m_parked.erase(it);
+        }
+        else
+            ++it;
 }
 
 /* reference: GPUKernel.cpp:1686-1690 */
@@ -1370,9 +1482,10 @@ void GPUKernel::resetAll()
         resetFrame();
     }
     m_frame = oldFrame;
+    dropFrameBank();
     m_resident.setTransfered(false);
     m_nbActiveMaterials = -1;
-    m_materialsTransfered = false;
+    materialsChanged();
     for (int i = 0; i < NB_MAX_TEXTURES; ++i)
         delete[] m_hTextures[i].buffer;
     memset(m_hTextures, 0, sizeof(m_hTextures));
@@ -1611,7 +1724,7 @@ void GPUKernel::setMaterial(unsigned int index, const Material &material)
     if (index < NB_MAX_MATERIALS && index < m_hMaterials.size())
     {
         m_hMaterials[index] = material;
-        m_materialsTransfered = false;
+        materialsChanged();
     }
 }
 
@@ -1660,7 +1773,7 @@ void GPUKernel::setMaterial(unsigned int index, float r, float g, float b, float
         m.textureIds = make_vec4i(diffuseTextureId, TEXTURE_NONE, TEXTURE_NONE, TEXTURE_NONE);
         m.textureOffset = make_vec4i();
     }
-    m_materialsTransfered = false;
+    materialsChanged();
 }
 
 /* reference: GPUKernel.cpp:1911-1930 */
@@ -1671,7 +1784,7 @@ void GPUKernel::setMaterialColor(unsigned int index, float r, float g, float b)
         m_hMaterials[index].color.x = r;
         m_hMaterials[index].color.y = g;
         m_hMaterials[index].color.z = b;
-        m_materialsTransfered = false;
+        materialsChanged();
     }
 }
 
@@ -1697,7 +1810,7 @@ void GPUKernel::setMaterialTextureId(unsigned int textureId)
         m.textureMapping = make_vec4i(m_hTextures[textureId].size.x, m_hTextures[textureId].size.y, TEXTURE_NONE,
                                       m_hTextures[textureId].size.z);
         m.textureIds = make_vec4i((int)textureId, TEXTURE_NONE, TEXTURE_NONE, TEXTURE_NONE);
-        m_materialsTransfered = false;
+        materialsChanged();
     }
 }
 
@@ -1792,7 +1905,7 @@ bool GPUKernel::loadTextureFromFile(const int index, const std::string &filename
      * (CudaKernel.cpp:214-230): a texture loaded between two frames would then be packed over the first one in the
      * atlas.  As setTexture does: every slot gets its place now, and the materials follow with the next frame */
     realignTexturesAndMaterials();
-    m_materialsTransfered = false;
+    materialsChanged();
     return true;
 }
 
@@ -2153,6 +2266,11 @@ void GPUKernel::render_end(BitmapBuffer *image)
 
 void GPUKernel::render_begin(const float)
 {
+    if (m_flattenDue) /* a frame entered through the bank without compactBoxes(false): its flattened arrays are not there yet */
+    {
+        ensureLevels();
+        streamDataToGPU();
+    }
     if (m_deterministicSeed < 0)
         m_sceneInfo.timestamp = rand() % 10000;
     const bool periodic = (m_deterministicSeed < 0) && (m_sceneInfo.pathTracingIteration % 50 == 1);

@@ -304,7 +304,8 @@ struct ResidentScene
     bool primitivesTransfered = false; /* the reference's m_primitivesTransfered: no upload of the scene is due */
     bool touched = true;               /* the scene store was accessed since the last upload */
     long frame = -1;                   /* the frame the resident scene was uploaded from, -1: none */
-    unsigned long uploads = 0;         /* how often the scene was uploaded: what was made from the flattened order is as old as that */
+    unsigned long uploads = 0;         /* the serial of its upload (one counter per kernel, 0: none): what was made from the flattened order is as old as that */
+    bool resumed = false;              /* put back from the frame bank, neither touched nor uploaded since (compactBoxes) */
     bool lampMoved = false;            /* a lamp was moved over there since the upload (morphFrame) */
     bool edited = false;               /* primitives were set anew over there since the upload (morphFrame) */
     /* the frames the engine holds as keys of that scene since the upload: in the slots of a track (morphBetween; the slot is
@@ -380,21 +381,34 @@ struct ResidentScene
 
     /* the engine has uploaded the scene from frame `f` (render_begin, when an upload was due): device and host hold the same
      * scene, the engine's morph keys are gone, the lamps are where the store has them */
-    void uploaded(unsigned int f)
+    void uploaded(unsigned int f, unsigned long serial)
     {
         primitivesTransfered = true;
         touched = false;
+        resumed = false;
         trackKeys.clear();
         pairKeys[0] = pairKeys[1] = -1;
         frame = (long)f;
         lampMoved = false;
         edited = false;
         materialsSet = false;
-        ++uploads;
+        uploads = serial;
     }
-    void setTransfered(bool value) { primitivesTransfered = value; }
+    void setTransfered(bool value)
+    {
+        primitivesTransfered = value;
+        resumed = resumed && value;
+    }
     /* the scene store was accessed (GPUKernel::frame): the fast path ends until the next upload */
-    void touch() { touched = true; }
+    void touch()
+    {
+        touched = true;
+        resumed = false;
+    }
+    /* the record has come back from the frame bank with its flattened arrays, and the engine holds its scene again
+     * (GPUKernel::switchFrame): both sides are what compactBoxes(false) and an upload would produce */
+    void resumedFromBank() { resumed = true; }
+    bool asResumed(unsigned int f) const { return resumed && primitivesTransfered && !touched && frame == (long)f; }
     void trackKeyTaken(unsigned int f) { trackKeys.push_back(f); }
     void pairKeysTaken(unsigned int a, unsigned int b) { pairKeys[0] = (long)a, pairKeys[1] = (long)b; }
     /* the engine has served `move`: into the journal, or past the cap into the counts */
@@ -467,9 +481,12 @@ struct ResidentScene
     struct Replaying
     {
         ResidentScene &scene;
-        const bool primitivesTransfered, touched;
-        explicit Replaying(ResidentScene &s) : scene(s), primitivesTransfered(s.primitivesTransfered), touched(s.touched) {}
-        ~Replaying() { scene.primitivesTransfered = primitivesTransfered, scene.touched = touched; }
+        const bool primitivesTransfered, touched, resumed;
+        explicit Replaying(ResidentScene &s)
+            : scene(s), primitivesTransfered(s.primitivesTransfered), touched(s.touched), resumed(s.resumed)
+        {
+        }
+        ~Replaying() { scene.primitivesTransfered = primitivesTransfered, scene.touched = touched, scene.resumed = resumed; }
     };
     /* While buildLevelsOnHost() makes the level maps, which may nest: it reads the store as it is (buildingLevels) */
     struct BuildingLevels
@@ -669,13 +686,25 @@ public:
     unsigned int getNbActiveTextures();
     void resetFrame();
     void resetAll();
-    void setNbFrames(const int nbFrames) { m_nbFrames = nbFrames; }
+    void setNbFrames(const int nbFrames);
     void setFrame(const int frame)
     {
         if ((unsigned int)frame != m_frame)
-            syncHost();
-        m_frame = frame;
+            switchFrame((unsigned int)frame);
     }
+    /* extension: the frame bank.  The reference's AnimationScene holds one mesh per frame and shows them with setFrame +
+     * compactBoxes(false) once per displayed frame (AnimationScene.cpp:55-109): a flatten and a full upload each.  With a
+     * bank of `bytes` > 0 a frame switch sets the frame that is left aside instead - its resident scene on the engine
+     * (deviceParkScene), its flattened arrays and its ResidentScene here, provided the engine holds that frame untouched -
+     * and puts the frame that is entered back (deviceResumeScene): compactBoxes(false) then returns at once and render_begin
+     * uploads nothing.  0, the default: off - setFrame, nextFrame and previousFrame do what they always did.  Engines
+     * without a device keep nothing */
+    void setFrameBank(unsigned long long bytes);
+    unsigned long long getFrameBank() const { return m_frameBankBytes; }
+    size_t nbParkedFrames() const { return m_parked.size(); }
+    /* frame switches served from the bank / scene uploads (ResidentScene::uploaded) since this kernel was made */
+    unsigned long nbFrameSwitches() const { return m_nbFrameSwitches; }
+    unsigned long nbSceneUploads() const { return m_nbSceneUploads; }
     int getNbFrames() { return m_nbFrames; }
     int getFrame() { return m_frame; }
     /* key-frame animation (GPUKernel.h:275-298 of the reference) */
@@ -810,6 +839,27 @@ protected:
     void ensureLevels();
     bool buildTreeOnDevice();
     void buildLevelsOnHost();
+    /* engine hooks of the frame bank: set the resident scene aside under that frame's number; make the scene set aside
+     * under it the resident one; drop the one of that frame (-1: all of them).  false = not done, nothing changed */
+    virtual bool deviceParkScene(unsigned int) { return false; }
+    virtual bool deviceResumeScene(unsigned int) { return false; }
+    virtual void deviceDropParked(long) {}
+    /* ... and the most the engine may hold of them (setFrameBank hands it on, the 0 too) */
+    virtual void deviceSetBankBytes(unsigned long long) {}
+    /* setFrame, nextFrame, previousFrame: the store caught up, then the switch - through the bank when it is on */
+    void switchFrame(unsigned int frame);
+    /* every parked frame forgotten on both sides (resetAll, cleanup, an engine that goes down or is set up anew, a resume
+     * that failed) */
+    void dropFrameBank();
+    /* the engine has uploaded the scene of the current frame (render_begin, when an upload was due) */
+    void sceneUploaded() { m_resident.uploaded(m_frame, ++m_nbSceneUploads); }
+    /* a material was set: the table is uploaded again with the next frame, and a parked frame flattened under the table
+     * before is flattened again when it is entered (its light records carry the materials' colours) */
+    void materialsChanged()
+    {
+        m_materialsTransfered = false;
+        ++m_materialsSerial;
+    }
     /* engine hook: apply the rotation to the resident scene; false = not done, nothing changed */
     virtual bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) { return false; }
     /* engine hooks: apply the translation to the resident scene; set the centre of lamp `slot` of the resident scene (the
@@ -891,6 +941,28 @@ protected:
     unsigned long m_slotOfUpload = 0;
     std::vector<int> m_rankOf;
     unsigned long m_rankOfUpload = 0;
+    /* the frame bank: per parked frame - never the current one - what the host knows of the scene the engine has set aside
+     * and the flattened arrays of that frame, everything streamDataToGPU writes */
+    struct ParkedFrame
+    {
+        ResidentScene resident;
+        std::vector<BoundingBox> boundingBoxes;
+        std::vector<Primitive> primitives;
+        std::vector<Lamp> lamps;
+        std::vector<unsigned char> movable;
+        std::vector<LightInformation> lightInformation;
+        int lightInformationSize = 0;
+        size_t maxPrimitivesPerBox = 0;
+        unsigned long materialsSerial = 0; /* m_flattenedSerial of its arrays: their light records carry colours */
+    };
+    std::map<unsigned int, ParkedFrame> m_parked;
+    unsigned long long m_frameBankBytes = 0;
+    unsigned long m_nbFrameSwitches = 0, m_nbSceneUploads = 0; /* (the latter is also the serial ResidentScene::uploads draws) */
+    unsigned long m_materialsSerial = 0; /* how often the materials were changed */
+    /* ... and m_materialsSerial when the flattened arrays were made (streamDataToGPU, the device build): their light
+     * records carry the materials' colours.  A frame flattened under another table is neither parked nor taken as resumed */
+    unsigned long m_flattenedSerial = 0;
+    bool m_flattenDue = false; /* the flattened arrays went into the bank and the frame entered had none there */
 
     /* box-tree build (GPUKernel.h:318-324) */
     int processBoxes(const int boxSize, bool simulate);

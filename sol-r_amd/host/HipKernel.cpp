@@ -32,6 +32,8 @@ HipKernel::HipKernel()
 
 HipKernel::~HipKernel()
 {
+    if (m_frameBankBytes != 0)
+        deviceSetBankBytes(0); /* the engine's knob outlives finalize_scene: not this kernel's limit for whoever comes next */
     releaseDevice();
 }
 
@@ -58,6 +60,7 @@ void HipKernel::initializeDevice()
 {
     if (m_deviceInitialized)
         releaseDevice();
+    dropFrameBank(); /* (initialize_scene drops the engine's) */
     initialize_scene(m_occupancyParameters, m_sceneInfo, NB_MAX_PRIMITIVES, NB_MAX_LAMPS, NB_MAX_MATERIALS);
     reshape_scene(m_occupancyParameters, m_sceneInfo);
     m_deviceInitialized = true;
@@ -77,6 +80,7 @@ void HipKernel::releaseDevice()
         memcpy(m_bitmap.data(), m_bitmapView, frame < m_bitmap.size() ? frame : m_bitmap.size());
     }
     m_bitmapView = nullptr;
+    dropFrameBank(); /* (finalize_scene drops the engine's) */
     if (m_deviceInitialized)
         finalize_scene(m_occupancyParameters);
     m_deviceInitialized = false;
@@ -152,7 +156,7 @@ void HipKernel::render_begin(const float timer)
             mark("render_begin: h2d_scene");
             h2d_lightInformation(m_occupancyParameters, m_lightInformation.data(), m_lightInformationSize);
             solr_hip_set_movable(m_hMovable.data(), (int)m_hMovable.size());
-            m_resident.uploaded(m_frame);
+            sceneUploaded();
             mark("render_begin: lights, movable flags");
         }
         if (!m_randomsTransfered)
@@ -544,8 +548,54 @@ void ReplayKernel::render_begin(const float timer)
     if (!m_resident.primitivesTransfered)
     {
         syncHost();
-        m_resident.uploaded(m_frame); /* the upload a real engine does here, when one is due */
+        sceneUploaded(); /* the upload a real engine does here, when one is due */
     }
+}
+
+/* the frame bank on the engine (include/solr_hip.h): the frame's number is the key; the limit is the engine's knob, set when
+ * the host's is (setFrameBank), the 0 that turns the bank off too */
+bool HipKernel::deviceParkScene(unsigned int frame)
+{
+    return m_deviceInitialized && solr_hip_park_scene((int)frame) == 1;
+}
+
+void HipKernel::deviceSetBankBytes(unsigned long long bytes)
+{
+    solr_hip_set_scene_bank_bytes(bytes);
+}
+
+bool HipKernel::deviceResumeScene(unsigned int frame)
+{
+    return m_deviceInitialized && solr_hip_resume_scene((int)frame) == 1;
+}
+
+void HipKernel::deviceDropParked(long frame)
+{
+    if (m_deviceInitialized)
+        solr_hip_drop_parked_scenes((int)frame);
+}
+
+bool ReplayKernel::deviceParkScene(unsigned int frame)
+{
+    m_parkedOverThere.insert(frame);
+    ++m_claimedParks;
+    return true;
+}
+
+bool ReplayKernel::deviceResumeScene(unsigned int frame)
+{
+    if (!m_parkedOverThere.erase(frame))
+        return false;
+    ++m_claimedResumes;
+    return true;
+}
+
+void ReplayKernel::deviceDropParked(long frame)
+{
+    if (frame < 0)
+        m_parkedOverThere.clear();
+    else
+        m_parkedOverThere.erase((unsigned int)frame);
 }
 
 bool ReplayKernel::deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &)

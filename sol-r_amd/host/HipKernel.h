@@ -12,6 +12,7 @@
 #pragma once
 
 #include <deque>
+#include <set>
 
 #include "GPUKernel.h"
 
@@ -73,6 +74,12 @@ protected:
     /* setPrimitiveMaterials on the resident scene, solr_hip_set_primitive_materials (include/solr_hip.h): store indices to
      * slots first, each slot once */
     bool deviceSetPrimitiveMaterials(const int *indices, const int *materialIds, int n) override;
+    /* the frame bank on the engine: solr_hip_park_scene, solr_hip_resume_scene, solr_hip_drop_parked_scenes
+     * (include/solr_hip.h), the frame's number as the key */
+    bool deviceParkScene(unsigned int frame) override;
+    bool deviceResumeScene(unsigned int frame) override;
+    void deviceDropParked(long frame) override;
+    void deviceSetBankBytes(unsigned long long bytes) override;
     void fetchPrimitiveIds() override;
     void fetchBitmap() override;
     bool primitivesFromDevice(Frame &f) override;
@@ -136,8 +143,14 @@ public:
     int nbClaimedLampMoves() const { return m_claimedLampMoves; }
     int nbClaimedEdits() const { return m_claimedEdits; }
     int nbClaimedMaterialSets() const { return m_claimedMaterialSets; }
+    int nbClaimedParks() const { return m_claimedParks; }
+    int nbClaimedResumes() const { return m_claimedResumes; }
 
 protected:
+    /* the frame bank: every park is claimed, a resume when that frame was parked and not dropped since */
+    bool deviceParkScene(unsigned int frame) override;
+    bool deviceResumeScene(unsigned int frame) override;
+    void deviceDropParked(long frame) override;
     bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) override;
     bool deviceSetMorphKeys(const std::vector<Primitive> &, const std::vector<Primitive> &) override { return true; }
     bool deviceMorphPrimitives(float weight) override;
@@ -155,5 +168,7 @@ private:
     int m_claimedMaterialSets = 0;
     int m_claimed = 0, m_claimedMorphs = 0, m_claimedTranslations = 0, m_claimedLampMoves = 0, m_claimedEdits = 0;
     int m_claimedTrackMorphs = 0, m_claimedTrackKeys = 0;
+    int m_claimedParks = 0, m_claimedResumes = 0;
+    std::set<unsigned int> m_parkedOverThere;
 };
 }

@@ -522,6 +522,30 @@ int SolRx_PendingMoves()
     return (int)SingletonKernel::kernel()->nbPendingMoves();
 }
 
+/* Extension: the frame bank (GPUKernel::setFrameBank) - an animation of whole meshes, one per frame, shown with
+ * SolRx_SetFrame + SolR_CompactBoxes(false): the frames the engine has been given stay there, and a switch back uploads
+ * nothing */
+int SolRx_SetFrameBank(unsigned long long bytes)
+{
+    SingletonKernel::kernel()->setFrameBank(bytes);
+    return engineStatus();
+}
+
+int SolRx_ParkedFrames()
+{
+    return (int)SingletonKernel::kernel()->nbParkedFrames();
+}
+
+int SolRx_FrameSwitches()
+{
+    return (int)SingletonKernel::kernel()->nbFrameSwitches();
+}
+
+int SolRx_SceneUploads()
+{
+    return (int)SingletonKernel::kernel()->nbSceneUploads();
+}
+
 int SolRx_SyncHost()
 {
     SingletonKernel::kernel()->syncHost();

@@ -240,6 +240,14 @@ int SolRx_SetPrimitives(const SolrPrimitiveEdit *edits, int n);
 int SolRx_SetPrimitiveMaterials(const int *indices, const int *materialIds, int n);
 int SolRx_SizeofPrimitiveEdit();
 int SolRx_PendingMoves();
+/* the frame bank (GPUKernel::setFrameBank): with `bytes` > 0 a frame that SolRx_SetFrame leaves stays on the engine - up to
+ * that many bytes of device memory in all - and comes back with no flatten and no upload when it is entered again; 0, the
+ * default, is off.  SolRx_ParkedFrames: frames set aside now; SolRx_FrameSwitches: switches served from the bank;
+ * SolRx_SceneUploads: uploads of the scene, both since the kernel was made */
+int SolRx_SetFrameBank(unsigned long long bytes);
+int SolRx_ParkedFrames();
+int SolRx_FrameSwitches();
+int SolRx_SceneUploads();
 int SolRx_SyncHost();
 int SolRx_GetMovable(const unsigned char **flags, int *nbPrimitives);
 /* float framebuffer of the last frame, W*H records */

@@ -331,6 +331,69 @@ def metaballs_surroundings(k):
     k.add_primitive(ptSphere, (-10000.0, 10000.0, -10000.0), size=(500.0, 0, 0), material=m["lamp"], movable=0)
 
 
+def _animation_depth(count):
+    """the depth GPUKernel::compactBoxes(true) gives a tree of `count` primitives (GPUKernel.cpp:1062-1071 of the reference)"""
+    depth = 0
+    while True:
+        depth += 1
+        count //= 4
+        if count <= 2:
+            return depth
+
+
+def animation(k, frames=4, cells=5, width=203, height=131, iterations=2, seed=2019, **scene_info):
+    """The reference's AnimationScene restated (apps/scenes/animation/AnimationScene.cpp:55-109): `frames` frames, each a
+    mesh of its own - there one OBJ file per frame, here a height field of (cells + frame) x (cells + frame) cells, so every
+    frame has another primitive count and another tree - with the reference's Cornell box and lamp sphere, and
+    compactBoxes(true) per frame.  A displayed frame is animation_step.  compactBoxes(false) flattens with the depth of the
+    tree built last, here as in the reference, so the frames must all come to the same depth: ValueError otherwise.
+    Leaves frame 0 current; k.animation holds the number of frames, the primitives per frame and the lamp's material."""
+    rng = LCG(seed)
+    counts = [2 * (cells + f) ** 2 + 7 for f in range(frames)]
+    if len({_animation_depth(c) for c in counts}) != 1:
+        raise ValueError("animation: frames of %s primitives come to trees of different depths" % counts)
+    scene_info.setdefault("graphicsLevel", glFull)
+    k.initialize(width=width, height=height, nbRayIterations=iterations, **scene_info)
+    surface = k.add_material(*_wall_color(rng), reflection=0.3, specValue=1.0, specPower=100.0)
+    walls = [k.add_material(*_wall_color(rng), specValue=0.1, specPower=200.0) for _ in range(6)]
+    lamp = k.add_material(1.0, 1.0, 1.0, innerIllumination=2.0)
+    k.set_nb_frames(frames)
+    x, y, z, w, h, d = 0.0, 15000.0, 0.0, 20000.0, 20000.0, 20000.0
+    box = ((ptXYPlane, (x, y, z + d)), (ptXYPlane, (x, y, z - d)), (ptYZPlane, (x - w, y, z)),
+           (ptYZPlane, (x + w, y, z)), (ptXZPlane, (x, y + h, z)), (ptXZPlane, (x, y - h, z)))
+    for f in range(frames):
+        k.set_frame(f)
+        n = cells + f
+        phase = 0.7 * f
+
+        def point(i, j):
+            u, v = (i / n) * 2.0 - 1.0, (j / n) * 2.0 - 1.0
+            return (u * 7000.0, 1500.0 * math.sin(3.0 * u + phase) * math.cos(2.0 * v - phase) - 2500.0, v * 7000.0)
+
+        for i in range(n):
+            for j in range(n):
+                a, b, c, e = point(i, j), point(i + 1, j), point(i + 1, j + 1), point(i, j + 1)
+                k.add_primitive(ptTriangle, a, b, c, material=surface)
+                k.add_primitive(ptTriangle, a, c, e, material=surface)
+        for (ptype, p0), material in zip(box, walls):
+            k.add_primitive(ptype, p0, size=(w, h, d), material=material)
+        k.add_primitive(ptSphere, (-10000.0, 10000.0, -10000.0), size=(500.0, 0, 0), material=lamp, movable=0)
+        k.compact_boxes(True)
+    k.set_frame(0)
+    k.set_camera((0.0, 3000.0, -15000.0))
+    k.animation = dict(frames=frames, counts=counts, lamp_material=lamp)
+    return k
+
+
+def animation_step(k, i):
+    """One displayed frame of the reference's AnimationScene::doAnimate: setFrame(i mod frames), compactBoxes(false).  With the
+    frame bank on (Kernel.set_frame_bank) a frame the engine was given before comes back with no flatten and no upload."""
+    frame = i % k.animation["frames"]
+    k.set_frame(frame)
+    k.compact_boxes(False)
+    return frame
+
+
 WATER_CELLS = 24
 
 
