@@ -109,6 +109,44 @@ int solr_hip_probe_walk_offer(const SceneInfo *sceneInfo, int exactNodes, int ou
 int solr_hip_probe_vectors(int n, const float *incident, const float *normals, const float *n1, const float *n2,
                            float *refracted, float *reflected);
 
+/* The device math stand-ins at the top of rt_device.h, one call per element, no resident scene and no feature template
+ * (tests/test_math_standins_gpu.py holds them to high-precision references of tests/golden/math_standins.npz and to the
+ * numpy models of tests/math_cases.py).  Element e runs in lane e mod 64 of wave e / 64, so the caller decides which 64
+ * inputs share a wave - pow_f sends a whole wave to pow_general when one lane is outside its lean domain.
+ * Both return 0, or -1 with solr_hip_last_error set for an unknown op, n < 1 or a null array. */
+enum SolrProbeMathOp
+{
+    SOLR_PROBE_POW = 0,        /* pow_f(a, b) */
+    SOLR_PROBE_POW_GENERAL,    /* pow_general(a, b) */
+    SOLR_PROBE_SIN,            /* sin_f(a) */
+    SOLR_PROBE_COS,            /* cos_f(a) */
+    SOLR_PROBE_ATAN2,          /* atan2_f(a, b) */
+    SOLR_PROBE_ASIN,           /* asin_f(a) */
+    SOLR_PROBE_SQRT,           /* sqrt_ieee(a) */
+    SOLR_PROBE_DIVIDE,         /* a / b */
+    SOLR_PROBE_RECIPROCAL,     /* 1.0f / a, as makeWalkRay and normalize write it */
+    SOLR_PROBE_TO_INT,         /* (int)a as the texture mappers write it; out holds the int's bits */
+    SOLR_PROBE_MATH_OPS
+};
+int solr_hip_probe_math(int op, int n, const float *a, const float *b, float *out);
+
+/* u, v: 3 n floats, s: n, out: 3 n (a scalar result in x, y and z zero) */
+enum SolrProbeVectorOp
+{
+    SOLR_PROBE_V_ADD = 0,      /* u + v */
+    SOLR_PROBE_V_SUB,          /* u - v */
+    SOLR_PROBE_V_SCALE,        /* u * s */
+    SOLR_PROBE_V_DOT,          /* dot(u, v) */
+    SOLR_PROBE_V_CROSS,        /* cross(u, v) */
+    SOLR_PROBE_V_LENGTH,       /* length(u) */
+    SOLR_PROBE_V_NORMALIZE,    /* normalize(u) */
+    SOLR_PROBE_V_DIVIDE,       /* vdivs(u, s) */
+    SOLR_PROBE_V_PROJECT,      /* project(u, v) */
+    SOLR_PROBE_V_REFLECTION,   /* vectorReflection(u, v) */
+    SOLR_PROBE_VECTOR_OPS
+};
+int solr_hip_probe_vector_math(int op, int n, const float *u, const float *v, const float *s, float *out);
+
 /* makeColor (GS:132-165) for pixel i of an image as sceneInfo.size says; bitmap: 3 n bytes */
 int solr_hip_probe_make_color(const SceneInfo *sceneInfo, int n, const float *colors, unsigned char *bitmap);
 

@@ -2,7 +2,7 @@
  * solr_hip_probes_morph.h - TEST-ONLY entry point of libsolr_hip.so for the key-frame tracks (sol-r_amd/csrc/solr_probes.hip).
  *
  * Like the entry points of solr_hip_probes.h it is not part of the drop-in boundary (include/solr_hip.h) and not used by
- * the product.  solr_hip_probes.h declares the nineteen probes of the renderer's device functions, of a frame and of the
+ * the product.  solr_hip_probes.h declares the twenty-one probes of the renderer's device functions, of a frame and of the
  * list builders, a set that tests/test_engine_probes_gpu.py holds closed; the probes of the morph kernels are a set of their
  * own, held by tests/test_abi_track.py and used by tests/test_track_gpu.py.
  */

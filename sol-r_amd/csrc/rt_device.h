@@ -161,9 +161,19 @@ SOLR_DEV v3 project(v3 A, v3 B) { return B * (dot(A, B) / dot(B, B)); }
 /* pow for the Blinn term (GS:1021), evaluated in binary64 and rounded once like the other stand-ins,
  * but without the generality of the library routine (which is two hundred instructions): for a normal
  * positive base and an exponent in (0, 4096], log2 by a 128-interval table + degree-8 polynomial,
- * exp2 by a degree-10 polynomial, relative error < 2^-41 (tools/gen_pow_table.py checks the binary32
- * results against pow() on 200 000 inputs: none differs).  +0 gives +0.  Anything else - negative,
- * infinite, NaN, subnormal bases, other exponents - sends the whole wave to the library routine. */
+ * exp2 by a degree-10 polynomial (the table holds thirteen exp2 coefficients; the Horner chain below starts at the
+ * eleventh), relative error < 2^-41 over the results binary32 can hold - nearly all of it the truncated exp2 series:
+ * (ln 2 / 2)^11 / 11! = 2^-42.1 at f = -1/2, which is 2^-41.6 of 2^f; the emulation's worst against mpmath is 2^-41.6.
+ * +0 gives +0.  Anything else - negative, infinite, NaN, subnormal bases,
+ * other exponents - sends the whole wave to the library routine.
+ * 2^-41 is not 2^-53: where the exact power lies closer than that to the midpoint of two floats, this path and the
+ * library routine (or the host's pow, the oracle's stand-in) may round to different neighbours.  Measured on the device
+ * over arrays of inputs (tests/test_math_standins_gpu.py, profiles/r23/math_standins.txt): 6 of 2^25 bases in [0.3, 1)
+ * with exponents in [1, 300], about 2 in 10^7 calls, every one of them within 2^-41 of a midpoint and one ULP apart;
+ * none among the 2^20 of the suite's sweep.  As one lane outside the domain sends its whole wave to the library routine,
+ * a lane's bits can at such inputs depend on its neighbours - inside the 1-ULP bar of the frames, and the 8 x 8 tiles
+ * keep a wave's composition fixed.  (tools/gen_pow_table.py emulates this path in binary64 with these degrees;
+ * tests/test_math_fixture.py holds the emulation to mpmath by the rule the device is held to.) */
 /* out of line: never taken on sane inputs, and inlining it doubles the live registers at its call site */
 __device__ __attribute__((noinline)) float pow_general(float a, float b) { return (float)pow((double)a, (double)b); }
 

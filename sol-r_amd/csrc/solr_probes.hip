@@ -5,7 +5,8 @@
  * code lives here: every kernel calls the functions of rt_device.h that k_standardRenderer is built from, in the
  * instantiations the renderer launches.  At the end: the list builders (list_builders.cpp, solr_lists.hip) on a node list
  * of the caller's (tests/test_list_builder_cases.py, tests/test_list_builders_device_gpu.py), and the pack kernel of the key-frame
- * tracks (include/solr_hip_probes_morph.h, tests/test_track_gpu.py).  gfx950 only.
+ * tracks (include/solr_hip_probes_morph.h, tests/test_track_gpu.py).  k_probeMath / k_probeVectorMath: the math stand-ins at the
+ * top of rt_device.h, one call per element and no scene (tests/test_math_standins_gpu.py).  gfx950 only.
  */
 #include <hip/hip_runtime.h>
 
@@ -326,6 +327,96 @@ __global__ __launch_bounds__(64) void k_probeVectors(int n, const float *inciden
     put3(reflected, e, vectorReflection(at3(incident, e), at3(normals, e)));
 }
 
+/* the device math stand-ins, one call per element (tests/test_math_standins_gpu.py): `op` is wave-uniform, so the ballot of
+ * pow_f sees exactly the lanes of the caller's 64 elements that are in range */
+__global__ __launch_bounds__(64) void k_probeMath(int op, int n, const float *a, const float *b, float *out)
+{
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n)
+        return;
+    const float x = a[e], y = b[e];
+    float r = 0.f;
+    switch (op)
+    {
+    case SOLR_PROBE_POW:
+        r = pow_f(x, y);
+        break;
+    case SOLR_PROBE_POW_GENERAL:
+        r = pow_general(x, y);
+        break;
+    case SOLR_PROBE_SIN:
+        r = sin_f(x);
+        break;
+    case SOLR_PROBE_COS:
+        r = cos_f(x);
+        break;
+    case SOLR_PROBE_ATAN2:
+        r = atan2_f(x, y);
+        break;
+    case SOLR_PROBE_ASIN:
+        r = asin_f(x);
+        break;
+    case SOLR_PROBE_SQRT:
+        r = sqrt_ieee(x);
+        break;
+    case SOLR_PROBE_DIVIDE:
+        r = x / y;
+        break;
+    case SOLR_PROBE_RECIPROCAL:
+        r = 1.0f / x;
+        break;
+    case SOLR_PROBE_TO_INT:
+        r = __int_as_float((int)x);
+        break;
+    }
+    out[e] = r;
+}
+
+__global__ __launch_bounds__(64) void k_probeVectorMath(int op, int n, const float *u, const float *v, const float *s,
+                                                       float *out)
+{
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n)
+        return;
+    const v3 A = at3(u, e), B = at3(v, e);
+    const float k = s[e];
+    v3 r = V(0.f, 0.f, 0.f);
+    switch (op)
+    {
+    case SOLR_PROBE_V_ADD:
+        r = A + B;
+        break;
+    case SOLR_PROBE_V_SUB:
+        r = A - B;
+        break;
+    case SOLR_PROBE_V_SCALE:
+        r = A * k;
+        break;
+    case SOLR_PROBE_V_DOT:
+        r.x = dot(A, B);
+        break;
+    case SOLR_PROBE_V_CROSS:
+        r = cross(A, B);
+        break;
+    case SOLR_PROBE_V_LENGTH:
+        r.x = length(A);
+        break;
+    case SOLR_PROBE_V_NORMALIZE:
+        r = normalize(A);
+        break;
+    case SOLR_PROBE_V_DIVIDE:
+        r = vdivs(A, k);
+        break;
+    case SOLR_PROBE_V_PROJECT:
+        r = project(A, B);
+        break;
+    case SOLR_PROBE_V_REFLECTION:
+        r = vectorReflection(A, B);
+        break;
+    }
+    put3(out, e, r);
+}
+
 __global__ __launch_bounds__(64) void k_probeMakeColor(const SceneInfo si, int n, const float *colors, unsigned char *bitmap)
 {
     const int e = blockIdx.x * 64 + threadIdx.x;
@@ -606,6 +697,38 @@ int solr_hip_probe_vectors(int n, const float *incident, const float *normals, c
         return -1;
     hipLaunchKernelGGL(k_probeVectors, waves(n), dim3(64), 0, 0, n, dI, dN, d1, d2, dR, dF);
     return a.finish(0) ? 1 : -1;
+}
+
+int solr_hip_probe_math(int op, int n, const float *a, const float *b, float *out)
+{
+    if (op < 0 || op >= SOLR_PROBE_MATH_OPS || n <= 0 || !a || !b || !out)
+    {
+        solrprobe::fail(-1, "solr_hip_probe_math: an op of SolrProbeMathOp, n > 0 and three arrays of n floats");
+        return -1;
+    }
+    Arrays arrays;
+    const float *dA = arrays.in(a, (size_t)n), *dB = arrays.in(b, (size_t)n);
+    float *dOut = arrays.out(out, (size_t)n);
+    if (arrays.failed)
+        return -1;
+    hipLaunchKernelGGL(k_probeMath, waves(n), dim3(64), 0, 0, op, n, dA, dB, dOut);
+    return arrays.finish(0) ? 0 : -1;
+}
+
+int solr_hip_probe_vector_math(int op, int n, const float *u, const float *v, const float *s, float *out)
+{
+    if (op < 0 || op >= SOLR_PROBE_VECTOR_OPS || n <= 0 || !u || !v || !s || !out)
+    {
+        solrprobe::fail(-1, "solr_hip_probe_vector_math: an op of SolrProbeVectorOp, n > 0, u and v of 3 n floats, s of n, out of 3 n");
+        return -1;
+    }
+    Arrays arrays;
+    const float *dU = arrays.in(u, 3 * (size_t)n), *dV = arrays.in(v, 3 * (size_t)n), *dS = arrays.in(s, (size_t)n);
+    float *dOut = arrays.out(out, 3 * (size_t)n);
+    if (arrays.failed)
+        return -1;
+    hipLaunchKernelGGL(k_probeVectorMath, waves(n), dim3(64), 0, 0, op, n, dU, dV, dS, dOut);
+    return arrays.finish(0) ? 0 : -1;
 }
 
 int solr_hip_probe_make_color(const SceneInfo *sceneInfo, int n, const float *colors, unsigned char *bitmap)

@@ -46,6 +46,8 @@ def declare(hip):
     hip.solr_hip_probe_image_serial.argtypes = [C.c_longlong]
     hip.solr_hip_probe_image_serial.restype = C.c_longlong
     hip.solr_hip_probe_vectors.argtypes = [i, v, v, v, v, v, v]
+    hip.solr_hip_probe_math.argtypes = [i, i, v, v, v]
+    hip.solr_hip_probe_vector_math.argtypes = [i, i, v, v, v, v]
     hip.solr_hip_probe_make_color.argtypes = [v, i, v, v]
     hip.solr_hip_probe_skybox.argtypes = [v, i, v, v, v]
     hip.solr_hip_probe_intersection_shader.argtypes = [v, i, v, v, v, v, v, v, v]
@@ -59,7 +61,7 @@ def declare(hip):
     hip.solr_hip_probe_prune_list.argtypes = [i, i, v, v, C.c_double, v, v, v, v, v, i]
     for name in ("box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "vectors",
                  "make_color", "skybox", "intersection_shader", "order_tiles", "list_copy", "walk_offer", "free_lists",
-                 "prune_list"):
+                 "prune_list", "math", "vector_math"):
         getattr(hip, "solr_hip_probe_" + name).restype = i
     del P
 
@@ -71,6 +73,29 @@ def _check(hip, status, what):
         hip.solr_hip_clear_error()
         raise RuntimeError("%s failed (status %d, error %d): %s" % (what, status, code, buf.value.decode(errors="replace")))
     return status
+
+
+def probe_math(hip, op, a, b=None):
+    """one of the device math stand-ins (enum SolrProbeMathOp of include/solr_hip_probes.h) per element: element e runs in
+    lane e % 64 of wave e // 64.  Returns binary32 (the int's bits for the cast)."""
+    declare(hip)
+    a = np.ascontiguousarray(a, f32)
+    b = np.zeros(len(a), f32) if b is None else np.ascontiguousarray(b, f32)
+    assert a.shape == b.shape == (len(a),)
+    out = np.full(len(a), np.nan, f32)
+    _check(hip, hip.solr_hip_probe_math(op, len(a), _p(a), _p(b), _p(out)), "probe_math (op %d)" % op)
+    return out
+
+
+def probe_vector_math(hip, op, u, v, s):
+    """one of the v3 operators (enum SolrProbeVectorOp) per element: (n, 3) binary32, a scalar result in column 0"""
+    declare(hip)
+    u, v, s = np.ascontiguousarray(u, f32), np.ascontiguousarray(v, f32), np.ascontiguousarray(s, f32)
+    n = len(s)
+    assert u.shape == v.shape == (n, 3)
+    out = np.full((n, 3), np.nan, f32)
+    _check(hip, hip.solr_hip_probe_vector_math(op, n, _p(u), _p(v), _p(s), _p(out)), "probe_vector_math (op %d)" % op)
+    return out
 
 
 class Resident:
