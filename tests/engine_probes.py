@@ -364,18 +364,18 @@ def engine_outputs(solr, case, features=0, exact=0):
         prims = np.zeros(1, solr.PRIMITIVE_DTYPE)
         prims["size"][:, 0] = 1.0
         with Resident(solr, si, one_leaf(solr, prims), prims, case["materials"], case["textures"]):
-            _check(hip, hip.solr_hip_probe_skybox(C.byref(si), n, _p(case["origins"]), _p(case["targets"]), _p(color)),
-                   "probe_skybox")
-        return dict(color=color)
+            used = _check(hip, hip.solr_hip_probe_skybox(C.byref(si), n, _p(case["origins"]), _p(case["targets"]), _p(color)),
+                          "probe_skybox")
+        return dict(color=color, features=used)
     if name == "intersection_shader":
         n = len(case["inter"])
         at = case["attributes"].copy()
         color, bump, spec, ao = np.zeros((n, 4), f32), np.zeros((n, 3), f32), np.zeros((n, 3), f32), np.zeros((n, 1), f32)
         with Resident(solr, si, one_leaf(solr, case["prims"]), case["prims"], case["materials"], case["textures"]):
-            _check(hip, hip.solr_hip_probe_intersection_shader(C.byref(si), n, _p(case["inter"]), _p(case["areas"]), _p(at),
-                                                               _p(color), _p(bump), _p(spec), _p(ao)),
-                   "probe_intersection_shader")
-        return dict(color=color, bump=bump, specular=spec, advanced=ao, attributes=at)
+            used = _check(hip, hip.solr_hip_probe_intersection_shader(C.byref(si), n, _p(case["inter"]), _p(case["areas"]),
+                                                                      _p(at), _p(color), _p(bump), _p(spec), _p(ao)),
+                          "probe_intersection_shader")
+        return dict(color=color, bump=bump, specular=spec, advanced=ao, attributes=at, features=used)
     raise KeyError(name)
 
 
