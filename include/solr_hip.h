@@ -685,6 +685,38 @@ int solr_hip_device_edits(void);
 int solr_hip_set_primitive_materials(const int *slots, const int *materialIds, int n);
 int solr_hip_device_material_sets(void);
 
+/* A material that is edited: a colour that pulses, glass that fades in, a wireframe toggled, a texture swapped, a material
+ * panel in a host (SolR_SetMaterial, GPUKernel::setMaterialColor, setMaterialTextureId).  The reference's hosts then call
+ * h2d_materials, which here builds and copies every active record, retags every primitive on the host - the geometry pulled
+ * back first if a move was served on the device - and has the whole arena laid out and uploaded again.  Of all that a
+ * material reaches its two records of the table and, in every primitive that has it, the tag and the colour key with their
+ * copies in the leaf records:
+ *   solr_hip_edit_materials     the arguments of h2d_materials.  The records are built as h2d_materials builds them and
+ *                               compared with those of the last upload or served edit; the ones that differ are overwritten
+ *                               in the device table, one kernel rewrites tag and colour key of every primitive of the
+ *                               resident scene that has a material whose facts (what a tag carries of it) or colour key
+ *                               changed, the leaf records and the host image follow, and the facts of the scene a frame is
+ *                               told follow by counts; where only other values changed - reflection, specular, refraction -
+ *                               no kernel is launched at all.  Nothing is pulled, laid out, uploaded or refitted; the light
+ *                               records keep the colours of the flatten, as they do behind h2d_materials; the texture tables
+ *                               are checked against the atlas again before the next frame.  Returns 1 when the table and the
+ *                               resident scene now hold, bit for bit, what h2d_materials with the same table would have left,
+ *                               0 when it cannot serve the request - no initialised engine or an error pending, no resident
+ *                               scene, a layout of the arena due anyway (the first frame after an upload), a scene with axis
+ *                               planes that was moved on the device since (its thin copies take their margin from the
+ *                               extent of the moved scene, which only the upload's retag reads), another number of
+ *                               materials than the table holds, no upload of the table yet, a changed material held by a
+ *                               primitive whose kind would differ (a sphere's material turned procedural, a YZ plane's
+ *                               emissive, a plane's given a diffuse texture: the thin copies and the order-free hierarchy
+ *                               were made from the kinds), an edit after which the primitives would all lie inside their
+ *                               leaves where they did not before, or the other way round: nothing changed, call
+ *                               h2d_materials.  With several in-process devices every engine follows or none does;
+ *   solr_hip_device_material_edits    how many requests were served since initialize_scene;
+ *   solr_hip_device_material_retags   ... and how many of them launched the kernel. */
+int solr_hip_edit_materials(Material *materials, int nbActiveMaterials);
+int solr_hip_device_material_edits(void);
+int solr_hip_device_material_retags(void);
+
 /* An animation of whole meshes: the reference's AnimationScene loads one OBJ file per frame, every frame a mesh of its own with
  * its own primitive count and its own tree, and shows them with setFrame + compactBoxes(false) once per displayed frame
  * (apps/scenes/animation/AnimationScene.cpp:55-109) - a flatten, a walk-order list and a full upload per displayed frame, and

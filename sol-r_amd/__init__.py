@@ -297,6 +297,10 @@ def _declare_hip(L):
     L.solr_hip_set_primitive_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.solr_hip_set_primitive_materials.restype = C.c_int
     L.solr_hip_device_material_sets.restype = C.c_int
+    L.solr_hip_edit_materials.argtypes = [C.c_void_p, C.c_int]
+    L.solr_hip_edit_materials.restype = C.c_int
+    L.solr_hip_device_material_edits.restype = C.c_int
+    L.solr_hip_device_material_retags.restype = C.c_int
     for name in ("solr_hip_park_scene", "solr_hip_resume_scene", "solr_hip_drop_parked_scenes"):
         getattr(L, name).argtypes = [C.c_int]
     for name in ("solr_hip_park_scene", "solr_hip_resume_scene", "solr_hip_parked_scenes", "solr_hip_scene_switches",
@@ -416,6 +420,9 @@ def _declare_host(L):
     L.SolRx_SizeofPrimitiveEdit.restype = i
     L.SolRx_SetPrimitiveMaterials.argtypes = [C.c_void_p, C.c_void_p, i]
     L.SolRx_SetPrimitiveMaterials.restype = i
+    L.SolRx_SetMaterialEdits.argtypes = [i]
+    L.SolRx_SetMaterialEdits.restype = i
+    L.SolRx_MaterialEdits.restype = i
     L.SolRx_GetMorphologies.argtypes = [C.c_void_p, i]
     L.SolRx_GetMorphologies.restype = i
 
@@ -558,6 +565,40 @@ class Kernel:
                                 ambientOcclusionTextureId, specValue, specPower, specCoef, innerIllumination,
                                 illuminationDiffusion, illuminationPropagation, int(fastTransparency))
         return idx
+
+    def set_material(self, index, r=1.0, g=1.0, b=1.0, noise=0.0, reflection=0.0, refraction=0.0, procedural=False,
+                     wireframe=False, wireframeWidth=0, transparency=0.0, opacity=0.0, diffuseTextureId=TEXTURE_NONE,
+                     normalTextureId=TEXTURE_NONE, bumpTextureId=TEXTURE_NONE, specularTextureId=TEXTURE_NONE,
+                     reflectionTextureId=TEXTURE_NONE, transparencyTextureId=TEXTURE_NONE,
+                     ambientOcclusionTextureId=TEXTURE_NONE, specValue=0.1, specPower=200.0, specCoef=0.0,
+                     innerIllumination=0.0, illuminationDiffusion=None, illuminationPropagation=None,
+                     fastTransparency=False):
+        """SolR_SetMaterial on a material that exists: every value of material `index` set anew, with add_material's
+        keywords and defaults.  The table goes to the engine with the next frame - uploaded, which retags and lays out the
+        whole resident scene again, or with set_material_edits(True) followed in place."""
+        vd = self.info["viewDistance"]
+        if illuminationDiffusion is None:
+            illuminationDiffusion = vd * 10
+        if illuminationPropagation is None:
+            illuminationPropagation = vd
+        return self.L.SolR_SetMaterial(index, r, g, b, noise, reflection, refraction, int(procedural), int(wireframe),
+                                       wireframeWidth, transparency, opacity, diffuseTextureId, normalTextureId,
+                                       bumpTextureId, specularTextureId, reflectionTextureId, transparencyTextureId,
+                                       ambientOcclusionTextureId, specValue, specPower, specCoef, innerIllumination,
+                                       illuminationDiffusion, illuminationPropagation, int(fastTransparency))
+
+    def set_material_edits(self, on):
+        """Material edits on the resident scene (SolRx_SetMaterialEdits): with on, a material set between two frames
+        (set_material, SolR_SetMaterial and its kin) is followed by the HIP engine in place - the changed records of its
+        table, tag and colour key of the primitives that have the material, nothing retagged on the host, laid out or
+        uploaded - where it can; where it declines (the first frame after an upload of the scene, a table that has grown, a
+        primitive the walks would have to treat as another kind) the table is uploaded as ever.  Off, the default: the
+        upload as ever.  Lamps' light records keep the colours of the last flatten either way."""
+        return self.L.SolRx_SetMaterialEdits(int(bool(on)))
+
+    def material_edits(self):
+        """edits of the table of materials the engine followed in place since the kernel was made"""
+        return self.L.SolRx_MaterialEdits()
 
     def add_primitive(self, ptype, p0, p1=(0, 0, 0), p2=(0, 0, 0), size=(0, 0, 0), material=0, movable=1):
         idx = self.L.SolR_AddPrimitive(ptype, movable)

@@ -790,11 +790,30 @@ struct Materials
     std::vector<float> materialAverage; /* (r + g + b) / 3.f per material id (plane colour key, GI:561) */
     std::vector<TextureUse> textureUses;
     long generation = 0; /* how often h2dMaterialsOne has run: a scene's tags are those of one table (ParkedScene) */
+    /* host image of the active records as the table holds them (h2dMaterialsOne, editMaterialsOne: solr_materials.hip),
+     * zero-filled before it was filled; nbImaged records of each, -1: no image */
+    std::vector<solrdev::MaterialHot> imageHot;
+    std::vector<solrdev::MaterialCold> imageCold;
+    int nbImaged = -1;
+    /* materials edited in the table and on the resident scene (solr_materials.hip): the batch of changed materials as
+     * uploaded last; requests served since initialize_scene, and those among them that launched k_retagMaterials */
+    DeviceBuffer editBatch;
+    int nbDeviceEdits = 0, nbDeviceRetags = 0;
     void release()
     {
         solreng::release(table);
+        solreng::release(editBatch);
         *this = Materials();
     }
+};
+/* what h2d_materials makes of one material (solr_uploads.hip materialRecord): its two records of the table, the facts its
+ * primitives' tags carry, their colour key, and - textured: the tables checkTextureTables holds against the atlas */
+struct MaterialRecord
+{
+    int facts;
+    float average;
+    bool textured;
+    TextureUse use;
 };
 /* Textures (h2d_textures): the atlas, and whether the materials' texture tables have been checked against it - before the
  * first frame that follows either upload (checkTextureTables; kept here: the atlas is what the check protects) */
@@ -1164,6 +1183,8 @@ inline int stripRows()
 /* solr_uploads.hip: one engine's share of the boundary's h2d_* calls */
 void h2dSceneOne(BoundingBox *boundingBoxes, int nbActiveBoxes, Primitive *primitives, int nbPrimitives, Lamp *lamps, int nbLamps);
 void h2dMaterialsOne(Material *materials, int nbActiveMaterials);
+/* material i of a table as the device gets it: `hot` and `cold` (zero-filled by the caller) filled in, the rest returned */
+MaterialRecord materialRecord(const Material &material, int i, solrdev::MaterialHot &hot, solrdev::MaterialCold &cold);
 void h2dRandomsOne(float *randoms);
 void h2dRandomsSizedOne(const float *randoms, long count);
 void h2dTexturesOne(int activeTextures, TextureInfo *textureInfos);
@@ -1211,6 +1232,9 @@ int setPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, fl
 /* solr_materials.hip: a batch of primitives' materials set on the device */
 bool canSetPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n);
 int setPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n);
+/* ... and an edited table of materials followed in the table and on the resident scene */
+bool canEditMaterialsOne(const Material *materials, int nbActiveMaterials);
+int editMaterialsOne(const Material *materials, int nbActiveMaterials);
 /* solr_bank.hip: resident scenes set aside and put back */
 void dropParkedOne(int key); /* (-1: all of them; waits for the frames in flight first, the only call of the bank that frees) */
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */

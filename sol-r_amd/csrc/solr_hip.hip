@@ -722,4 +722,20 @@ int solr_hip_set_primitive_materials(const int *slots, const int *materialIds, i
     });
     return status;
 }
+
+/* (... and every one of them follows the edit in its own table and its own copy; 1 only when all of them did) */
+int solr_hip_edit_materials(Material *materials, int nbActiveMaterials)
+{
+    bool all = true;
+    onEveryDevice([&](int) { all = canEditMaterialsOne(materials, nbActiveMaterials) && all; });
+    if (!all)
+        return 0;
+    int status = 1; /* 1: edited on the device */
+    onEveryDevice([&](int) {
+        const int mine = editMaterialsOne(materials, nbActiveMaterials);
+        if (mine != 1 && status == 1)
+            status = mine;
+    });
+    return status;
+}
 }

@@ -291,6 +291,60 @@ void setMovableOne(const unsigned char *flags, int nbPrimitives)
         g.scene.rotation.nbMovable = nbPrimitives;
 }
 
+/* One material of the table as the device gets it - h2dMaterialsOne for every active one, editMaterialsOne
+ * (solr_materials.hip) to see which of them an edit changed. */
+MaterialRecord materialRecord(const Material &material, int i, MaterialHot &h, MaterialCold &c)
+{
+    Material m = material;
+    MaterialRecord record;
+    /* A diffuse texture id that was never loaded: GPUKernel::setMaterial then leaves the "computed texture"
+     * mapping (40000 x 40000 at offset 0, GPUKernel.cpp:1893-1896) next to the id, and the mappers would
+     * index gigabytes past the atlas (the reference reads whatever is there; a memory fault here).  Such a
+     * material is untextured on the device. */
+    if (m.textureIds.x >= 0 && m.textureMapping.x == 40000 && m.textureMapping.y == 40000 && m.textureOffset.x == 0)
+        m.textureIds.x = TEXTURE_NONE;
+    record.facts = materialTag(m);
+    /* the mappers fetch only for 0 <= u < mapping.x (rt_device.h): a mapping without columns - what
+     * realignTexturesAndMaterials gives a material whose texture nobody loaded - never reaches the atlas */
+    record.textured = m.textureIds.x >= 0 && m.textureMapping.x > 0; /* procedural ids (Mandelbrot, Julia) are negative */
+    record.use = TextureUse();
+    if (record.textured)
+    {
+        TextureUse &use = record.use;
+        use.material = i;
+        use.texels = (long)m.textureMapping.x * (long)m.textureMapping.y * (long)m.textureMapping.w;
+        if (m.textureMapping.y <= 0 || m.textureMapping.w <= 0 || m.textureOffset.x < 0)
+            use.texels = 0; /* fetchTexel takes an index modulo this: refused by checkTextureTables */
+        const int ids[7] = {m.textureIds.x, m.textureIds.y, m.textureIds.z, m.textureIds.w,
+                            m.advancedTextureIds.x, m.advancedTextureIds.y, m.advancedTextureIds.z};
+        const int offs[7] = {m.textureOffset.x, m.textureOffset.y, m.textureOffset.z, m.textureOffset.w,
+                             m.advancedTextureOffset.x, m.advancedTextureOffset.y, m.advancedTextureOffset.z};
+        for (int t = 0; t < 7; ++t)
+            use.offsets[t] = ids[t] != TEXTURE_NONE ? (long)offs[t] : -1L;
+    }
+    record.average = (m.color.x + m.color.y + m.color.z) / 3.f; /* same expression, same rounding */
+    h.innerIllumination = make_float4(m.innerIllumination.x, m.innerIllumination.y, m.innerIllumination.z,
+                                      m.innerIllumination.w);
+    h.color = make_float4(m.color.x, m.color.y, m.color.z, m.color.w);
+    h.specular = make_float4(m.specular.x, m.specular.y, m.specular.z, m.specular.w);
+    h.reflection = m.reflection;
+    h.refraction = m.refraction;
+    h.transparency = m.transparency;
+    h.opacity = m.opacity;
+    h.attributes = make_int4(m.attributes.x, m.attributes.y, m.attributes.z, m.attributes.w);
+    h.ids = make_int4(m.textureIds.x, m.advancedTextureIds.z, 0, 0);
+    c.textureMapping = make_int4(m.textureMapping.x, m.textureMapping.y, m.textureMapping.z, m.textureMapping.w);
+    c.textureOffset = make_int4(m.textureOffset.x, m.textureOffset.y, m.textureOffset.z, m.textureOffset.w);
+    c.textureIds = make_int4(m.textureIds.x, m.textureIds.y, m.textureIds.z, m.textureIds.w);
+    c.advancedTextureOffset = make_int4(m.advancedTextureOffset.x, m.advancedTextureOffset.y,
+                                        m.advancedTextureOffset.z, m.advancedTextureOffset.w);
+    c.advancedTextureIds = make_int4(m.advancedTextureIds.x, m.advancedTextureIds.y, m.advancedTextureIds.z,
+                                     m.advancedTextureIds.w);
+    c.mappingOffset = make_float2(m.mappingOffset.x, m.mappingOffset.y);
+    c.pad = make_float2(0.f, 0.f);
+    return record;
+}
+
 void h2dMaterialsOne(Material *materials, int nbActiveMaterials)
 {
     if (!ready("h2d_materials"))
@@ -313,57 +367,16 @@ void h2dMaterialsOne(Material *materials, int nbActiveMaterials)
     g.materials.materialTags.assign(capacity, PRIM_FAST0 | (1 << PRIM_WIDTH_SHIFT));
     g.materials.materialAverage.assign(capacity, 0.f);
     g.materials.textureUses.clear();
+    g.materials.nbImaged = -1; /* (the image is this call's records once they have landed) */
     g.textures.textureTablesChecked = false;
     ++g.materials.generation; /* (a parked scene keeps the tags of the table it was parked under: solr_bank.hip) */
     for (int i = 0; i < nbActiveMaterials && i < capacity; ++i)
     {
-        Material m = materials[i];
-        /* A diffuse texture id that was never loaded: GPUKernel::setMaterial then leaves the "computed texture"
-         * mapping (40000 x 40000 at offset 0, GPUKernel.cpp:1893-1896) next to the id, and the mappers would
-         * index gigabytes past the atlas (the reference reads whatever is there; a memory fault here).  Such a
-         * material is untextured on the device. */
-        if (m.textureIds.x >= 0 && m.textureMapping.x == 40000 && m.textureMapping.y == 40000 && m.textureOffset.x == 0)
-            m.textureIds.x = TEXTURE_NONE;
-        g.materials.materialTags[i] = materialTag(m);
-        /* the mappers fetch only for 0 <= u < mapping.x (rt_device.h): a mapping without columns - what
-         * realignTexturesAndMaterials gives a material whose texture nobody loaded - never reaches the atlas */
-        if (m.textureIds.x >= 0 && m.textureMapping.x > 0) /* procedural ids (Mandelbrot, Julia) are negative */
-        {
-            TextureUse use;
-            use.material = i;
-            use.texels = (long)m.textureMapping.x * (long)m.textureMapping.y * (long)m.textureMapping.w;
-            if (m.textureMapping.y <= 0 || m.textureMapping.w <= 0 || m.textureOffset.x < 0)
-                use.texels = 0; /* fetchTexel takes an index modulo this: refused by checkTextureTables */
-            const int ids[7] = {m.textureIds.x, m.textureIds.y, m.textureIds.z, m.textureIds.w,
-                                m.advancedTextureIds.x, m.advancedTextureIds.y, m.advancedTextureIds.z};
-            const int offs[7] = {m.textureOffset.x, m.textureOffset.y, m.textureOffset.z, m.textureOffset.w,
-                                 m.advancedTextureOffset.x, m.advancedTextureOffset.y, m.advancedTextureOffset.z};
-            for (int t = 0; t < 7; ++t)
-                use.offsets[t] = ids[t] != TEXTURE_NONE ? (long)offs[t] : -1L;
-            g.materials.textureUses.push_back(use);
-        }
-        g.materials.materialAverage[i] = (m.color.x + m.color.y + m.color.z) / 3.f; /* same expression, same rounding */
-        MaterialHot &h = hot[i];
-        h.innerIllumination = make_float4(m.innerIllumination.x, m.innerIllumination.y, m.innerIllumination.z,
-                                          m.innerIllumination.w);
-        h.color = make_float4(m.color.x, m.color.y, m.color.z, m.color.w);
-        h.specular = make_float4(m.specular.x, m.specular.y, m.specular.z, m.specular.w);
-        h.reflection = m.reflection;
-        h.refraction = m.refraction;
-        h.transparency = m.transparency;
-        h.opacity = m.opacity;
-        h.attributes = make_int4(m.attributes.x, m.attributes.y, m.attributes.z, m.attributes.w);
-        h.ids = make_int4(m.textureIds.x, m.advancedTextureIds.z, 0, 0);
-        MaterialCold &c = cold[i];
-        c.textureMapping = make_int4(m.textureMapping.x, m.textureMapping.y, m.textureMapping.z, m.textureMapping.w);
-        c.textureOffset = make_int4(m.textureOffset.x, m.textureOffset.y, m.textureOffset.z, m.textureOffset.w);
-        c.textureIds = make_int4(m.textureIds.x, m.textureIds.y, m.textureIds.z, m.textureIds.w);
-        c.advancedTextureOffset = make_int4(m.advancedTextureOffset.x, m.advancedTextureOffset.y,
-                                            m.advancedTextureOffset.z, m.advancedTextureOffset.w);
-        c.advancedTextureIds = make_int4(m.advancedTextureIds.x, m.advancedTextureIds.y, m.advancedTextureIds.z,
-                                         m.advancedTextureIds.w);
-        c.mappingOffset = make_float2(m.mappingOffset.x, m.mappingOffset.y);
-        c.pad = make_float2(0.f, 0.f);
+        const MaterialRecord record = materialRecord(materials[i], i, hot[i], cold[i]);
+        g.materials.materialTags[i] = record.facts;
+        if (record.textured)
+            g.materials.textureUses.push_back(record.use);
+        g.materials.materialAverage[i] = record.average;
     }
     HIPCHECK(hipSetDevice(g.device));
     const size_t tableBytes = 12 * (size_t)capacity * sizeof(float4);
@@ -395,6 +408,10 @@ void h2dMaterialsOne(Material *materials, int nbActiveMaterials)
     {
         g.materials.offMatCold = 6u * (unsigned)capacity;
         g.materials.nbMaterials = nbActiveMaterials;
+        /* what the table holds now, for the next edit to be compared with (editMaterialsOne) */
+        g.materials.imageHot.swap(hot);
+        g.materials.imageCold.swap(cold);
+        g.materials.nbImaged = active;
         retagPrimitives();
     }
 }

@@ -705,6 +705,14 @@ public:
     /* frame switches served from the bank / scene uploads (ResidentScene::uploaded) since this kernel was made */
     unsigned long nbFrameSwitches() const { return m_nbFrameSwitches; }
     unsigned long nbSceneUploads() const { return m_nbSceneUploads; }
+    /* extension: material edits on the resident scene.  A host that sets a material (setMaterial, setMaterialColor,
+     * setMaterialTextureId) has the table uploaded with the next frame, which has the engine retag every primitive and lay
+     * out and upload the whole scene again.  With the switch on, the engine is first asked to follow the edit in place
+     * (deviceEditMaterials: the changed records, the tags and colour keys of the primitives that have them), and the table is
+     * uploaded as ever when it declines.  Off, the default: the upload as ever.  materialEdits: edits the engine followed
+     * since this kernel was made */
+    void setMaterialEdits(bool on) { m_materialEdits = on; }
+    unsigned long materialEdits() const { return m_nbMaterialEdits; }
     int getNbFrames() { return m_nbFrames; }
     int getFrame() { return m_frame; }
     /* key-frame animation (GPUKernel.h:275-298 of the reference) */
@@ -860,6 +868,11 @@ protected:
         m_materialsTransfered = false;
         ++m_materialsSerial;
     }
+    /* engine hook: follow the table of materials as it is now (m_hMaterials, realigned) in the engine's table and on its
+     * resident scene; false = not done, nothing changed: the table is uploaded */
+    virtual bool deviceEditMaterials() { return false; }
+    bool m_materialEdits = false;
+    unsigned long m_nbMaterialEdits = 0;
     /* engine hook: apply the rotation to the resident scene; false = not done, nothing changed */
     virtual bool deviceRotatePrimitives(const vec3f &, const vec3f &, const vec3f &) { return false; }
     /* engine hooks: apply the translation to the resident scene; set the centre of lamp `slot` of the resident scene (the

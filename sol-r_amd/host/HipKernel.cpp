@@ -171,7 +171,10 @@ void HipKernel::render_begin(const float timer)
         if (!m_materialsTransfered)
         {
             realignTexturesAndMaterials();
-            h2d_materials(m_occupancyParameters, m_hMaterials.data(), nbMaterials);
+            if (m_materialEdits && deviceEditMaterials())
+                ++m_nbMaterialEdits; /* the engine followed the edit in place: nothing is retagged or laid out again */
+            else
+                h2d_materials(m_occupancyParameters, m_hMaterials.data(), nbMaterials);
             m_materialsTransfered = true;
             mark("render_begin: materials");
         }
@@ -275,6 +278,11 @@ bool HipKernel::deviceSetPrimitiveMaterials(const int *indices, const int *mater
     if (!materialSlots(indices, materialIds, n, slots, lastIds))
         return false;
     return solr_hip_set_primitive_materials(slots.data(), lastIds.data(), (int)slots.size()) == 1;
+}
+
+bool HipKernel::deviceEditMaterials()
+{
+    return m_deviceInitialized && solr_hip_edit_materials(m_hMaterials.data(), m_nbActiveMaterials + 1) == 1;
 }
 
 bool HipKernel::jpegPixels(const SolrJpegFrame &frame, const std::vector<short> &coefficients, unsigned char *rgb)

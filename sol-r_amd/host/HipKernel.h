@@ -74,6 +74,8 @@ protected:
     /* setPrimitiveMaterials on the resident scene, solr_hip_set_primitive_materials (include/solr_hip.h): store indices to
      * slots first, each slot once */
     bool deviceSetPrimitiveMaterials(const int *indices, const int *materialIds, int n) override;
+    /* an edited table of materials on the resident scene, solr_hip_edit_materials (include/solr_hip.h) */
+    bool deviceEditMaterials() override;
     /* the frame bank on the engine: solr_hip_park_scene, solr_hip_resume_scene, solr_hip_drop_parked_scenes
      * (include/solr_hip.h), the frame's number as the key */
     bool deviceParkScene(unsigned int frame) override;

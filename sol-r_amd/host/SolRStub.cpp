@@ -546,6 +546,19 @@ int SolRx_SceneUploads()
     return (int)SingletonKernel::kernel()->nbSceneUploads();
 }
 
+/* Extension: material edits on the resident scene (GPUKernel::setMaterialEdits) - a host that sets a material per frame has
+ * the engine follow it in place where it can, instead of the upload of the table that retags and lays out the whole scene */
+int SolRx_SetMaterialEdits(int on)
+{
+    SingletonKernel::kernel()->setMaterialEdits(on != 0);
+    return 0;
+}
+
+int SolRx_MaterialEdits()
+{
+    return (int)SingletonKernel::kernel()->materialEdits();
+}
+
 int SolRx_SyncHost()
 {
     SingletonKernel::kernel()->syncHost();

@@ -248,6 +248,14 @@ int SolRx_SetFrameBank(unsigned long long bytes);
 int SolRx_ParkedFrames();
 int SolRx_FrameSwitches();
 int SolRx_SceneUploads();
+/* material edits on the resident scene (GPUKernel::setMaterialEdits): with `on` != 0 a material set between two frames
+ * (SolR_SetMaterial and its kin) is followed by the HIP engine in place - the changed records of its table, the tags and
+ * colour keys of the primitives that have the material - where it can, and the table is uploaded as ever where it declines
+ * (the first frame after an upload of the scene, a table that has grown, a primitive the walks would have to treat as another
+ * kind, see include/solr_hip.h solr_hip_edit_materials); 0, the default, is off: the upload as ever.  The lamps' light records
+ * keep the colours of the last flatten either way.  SolRx_MaterialEdits: edits followed in place since the kernel was made */
+int SolRx_SetMaterialEdits(int on);
+int SolRx_MaterialEdits();
 int SolRx_SyncHost();
 int SolRx_GetMovable(const unsigned char **flags, int *nbPrimitives);
 /* float framebuffer of the last frame, W*H records */

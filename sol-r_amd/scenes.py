@@ -242,6 +242,23 @@ def swc_walk(k, samples, lamp, light_material, step, state):
     return primitive
 
 
+def material_pulse(k, material, timer, **values):
+    """One frame of a host that edits one material per frame (SolR_SetMaterial): material `material` gets a colour along a
+    sine of `timer` - a frame count - and, every other frame, transparency 0.5 with a refraction index, else 0: the colour
+    alone changes the colour key of the primitives that have the material, the transparency what their tags carry of it, which
+    is also another row of the renderer's launch table for a scene that had nothing transparent.  values: further keywords
+    of Kernel.set_material, the same every frame.  With Kernel.set_material_edits(True) the HIP engine follows the edit on the
+    resident scene.  Returns the keywords the material was set with."""
+    step = int(timer)
+    clear = step % 2 == 1
+    edit = dict(values)
+    edit.update(r=0.5 + 0.5 * math.sin(0.37 * timer), g=0.5 + 0.5 * math.sin(0.37 * timer + 2.1),
+                b=0.5 + 0.5 * math.sin(0.37 * timer + 4.2), transparency=0.5 if clear else 0.0,
+                refraction=1.1 if clear else 0.0, opacity=0.1 if clear else 0.0)
+    k.set_material(material, **edit)
+    return edit
+
+
 def pdb_molecule(k, path, width=1920, height=1080, iterations=3, geometry_type=3, scale=200.0, **scene_info):
     """A scene around a PDB molecule (reference: PDBReader::loadAtomsFromFile as its MoleculeScene calls it:
     atom size 100, stick size 10, scale 200, materials by element; light at (-5000, 5000, -15000))."""
