@@ -421,8 +421,12 @@ def plane_intersection(si, s, p, r, reverse=False):   # GI:424-567 (untextured m
     if not collision:
         return None, (ix, iy, iz), normal
     shadow = F(1)
-    assert t != ptCamera and m["texture"] == TEXTURE_NONE, "textured planes are outside this model"
     color = m["color"]
+    if t == ptCamera or m["texture"] != TEXTURE_NONE:
+        # GI:551-558: cubeMapping.  Of a material whose mapping is 0 x 0 it fetches no texel - u < textureMapping.x fails for
+        # every u (TM:393-398) - and returns the material's colour: the shadow intensity is its w
+        assert m["mapping"][0] == 0 and m["mapping"][1] == 0, "textured planes are outside this model"
+        shadow = color[3]
     if (color[0] + color[1] + color[2]) / F(3) >= F(si.transparentColor):      # GI:561
         return None, (ix, iy, iz), normal
     return ((ix, iy, iz), normal, shadow), (ix, iy, iz), normal
@@ -547,6 +551,24 @@ def intersection_with_primitives(si, s, origin, target, iteration, current_mater
     return (found,) + best
 
 
+def _dispatch_shadow(si, s, p, r):               # the switch of GI:835-864
+    """-> None or (intersection, normal, shadowIntensity, ...) of the test the shadow walk makes of primitive p"""
+    if not si.extendedGeometry:
+        return triangle_intersection(si, s, p, r, True)
+    t = p["type"]
+    if t == ptSphere:
+        return sphere_intersection(si, s, p, r)
+    if t == ptEllipsoid:
+        return ellipsoid_intersection(si, s, p, r)
+    if t == ptCylinder or t == ptCone:
+        return cylinder_intersection(si, s, p, r)
+    if t == ptTriangle:
+        return triangle_intersection(si, s, p, r, True)
+    if t == ptCamera:
+        return None
+    return plane_intersection(si, s, p, r)[0]
+
+
 def process_shadows(si, s, lamp_center, origin, light_id, iteration, object_id):   # GI:798-908
     """-> (shadow, (r, g, b) of the shadow colour)"""
     result = F(0)
@@ -565,23 +587,7 @@ def process_shadows(si, s, lamp_center, origin, light_id, iteration, object_id):
                 p = s.P[box["start"] + k]
                 m = s.material(p["mat"])
                 if p["index"] != light_id and p["index"] != object_id and m["attributes"][0] == 0:
-                    hit = None
-                    if si.extendedGeometry:
-                        t = p["type"]
-                        if t == ptSphere:
-                            hit = sphere_intersection(si, s, p, r)
-                        elif t == ptEllipsoid:
-                            hit = ellipsoid_intersection(si, s, p, r)
-                        elif t == ptCylinder or t == ptCone:
-                            hit = cylinder_intersection(si, s, p, r)
-                        elif t == ptTriangle:
-                            hit = triangle_intersection(si, s, p, r, True)
-                        elif t == ptCamera:
-                            hit = None
-                        else:
-                            hit = plane_intersection(si, s, p, r)[0]
-                    else:
-                        hit = triangle_intersection(si, s, p, r, True)
+                    hit = _dispatch_shadow(si, s, p, r)
                     if hit:
                         inter, normal, shadow = hit[0], hit[1], hit[2]
                         O_I = sub(inter, r.origin)
