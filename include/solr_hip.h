@@ -314,8 +314,37 @@ typedef struct
 } SolrJpegSource;
 int solr_hip_rgb_to_jpeg_blocks(const SolrJpegSource *source, const unsigned char *rgb, short *coefficients,
                                 long nbBlocks);
-/* coefficient blocks the device has produced since the library was loaded */
+/* coefficient blocks the device has produced since the library was loaded (wherever the pixel stage ran: the three
+ * entries below that start from pixels count here too) */
 unsigned long long solr_hip_jpeg_encoded_blocks(void);
+
+/* The entropy stage of the JPEG writer on the device (sol-r_amd/csrc/solr_jpeg_entropy.hip; the arithmetic is
+ * sol-r_amd/csrc/jpeg_entropy.h, the one-pass coder of the reference encoder, solr/images/jpge.cpp, byte for byte):
+ * the bits of every block, their prefix sum, every block emitted at its bit offset, the 0xFF bytes counted per chunk,
+ * their prefix sum, and the stuffed bytes written.  What comes out is the entropy-coded segment of the file - stuffed,
+ * its last byte completed with one-bits - without the headers in front (JpegWriter::header) and the EOI behind.
+ *   solr_hip_jpeg_blocks_to_scan   the stage alone: `coefficients` is the caller's host buffer of nbBlocks * 64 shorts in
+ *                  the order solr_hip_rgb_to_jpeg_blocks leaves; of `source` the size and the sampling are used (nbBlocks
+ *                  must match them) and the rest checked
+ *   solr_hip_rgb_to_jpeg_scan      the pixel stage, then this one; the coefficients never leave the device
+ *   solr_hip_frame_to_jpeg_scan    the same from the device image of the frame rendered last, behind that frame on its
+ *                  stream: read as a screenshot reads it - turned, first and third channel swapped unless the frame
+ *                  buffer is ftRGB.  A frame rendered in strips or on several devices, and an engine that has not
+ *                  rendered yet, are declined: -1, no error, nothing launched
+ *   scan, capacity the caller's host buffer and its size in bytes; *nbBytes receives the size of the segment.  With a
+ *                  capacity too small the call returns -1 with the size needed in *nbBytes, no error, nothing written
+ * The argument checks are those of solr_hip_rgb_to_jpeg_blocks (plus: scan and nbBytes not null, capacity >= 0), before
+ * anything is launched.  A block outside what the standard tables code - a DC difference beyond +-2047, an AC coefficient
+ * beyond +-1023; the pixel stage makes none - gives -1 with the error set and `scan` untouched.  Synchronous; the first
+ * two run on the device of solr_hip_get_device() on a stream of their own, with or without an initialised scene; all give
+ * their device buffers back before they return.  0, or -1. */
+int solr_hip_jpeg_blocks_to_scan(const SolrJpegSource *source, const short *coefficients, long nbBlocks,
+                                 unsigned char *scan, long capacity, long *nbBytes);
+int solr_hip_rgb_to_jpeg_scan(const SolrJpegSource *source, const unsigned char *rgb, unsigned char *scan, long capacity,
+                              long *nbBytes);
+int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char *scan, long capacity, long *nbBytes);
+/* blocks the device has entropy-coded since the library was loaded */
+unsigned long long solr_hip_jpeg_coded_blocks(void);
 
 /* The iso-surface of a field of metaballs as triangles, on the device (sol-r_amd/csrc/solr_iso.hip; the arithmetic is
  * sol-r_amd/csrc/iso_surface.h, that of the reference's apps/scenes/animation/MetaballsScene.cpp, in IEEE binary32 in

@@ -320,6 +320,13 @@ def _declare_hip(L):
     L.solr_hip_rgb_to_jpeg_blocks.argtypes = [P(JpegSource), C.c_void_p, C.c_void_p, C.c_long]
     L.solr_hip_rgb_to_jpeg_blocks.restype = C.c_int
     L.solr_hip_jpeg_encoded_blocks.restype = C.c_ulonglong
+    L.solr_hip_jpeg_blocks_to_scan.argtypes = [P(JpegSource), C.c_void_p, C.c_long, C.c_void_p, C.c_long, P(C.c_long)]
+    L.solr_hip_jpeg_blocks_to_scan.restype = C.c_int
+    L.solr_hip_rgb_to_jpeg_scan.argtypes = [P(JpegSource), C.c_void_p, C.c_void_p, C.c_long, P(C.c_long)]
+    L.solr_hip_rgb_to_jpeg_scan.restype = C.c_int
+    L.solr_hip_frame_to_jpeg_scan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, P(C.c_long)]
+    L.solr_hip_frame_to_jpeg_scan.restype = C.c_int
+    L.solr_hip_jpeg_coded_blocks.restype = C.c_ulonglong
     L.solr_hip_iso_field.argtypes = [P(IsoGrid), C.c_void_p, C.c_int, C.c_void_p]
     L.solr_hip_iso_field.restype = C.c_int
     L.solr_hip_iso_surface.argtypes = [P(IsoGrid), C.c_void_p, C.c_void_p, C.c_int]
@@ -371,6 +378,13 @@ def _declare_host(L):
     L.SolRx_JpegCoefficients.argtypes = [C.c_void_p, i, i, i, i, i, i, i, C.c_void_p, C.c_long]
     L.SolRx_JpegFromCoefficients.argtypes = [C.c_char_p, C.c_void_p, C.c_long, i, i, i, i, i]
     L.SolRx_JpegQuantise.argtypes = [i, i, i, i, C.c_void_p]
+    L.SolRx_RenderJpeg.argtypes = [d, i, i, i, C.c_void_p, C.c_long, P(C.c_long)]
+    L.SolRx_JpegFileFromCoefficients.argtypes = [C.c_void_p, C.c_long, i, i, i, i, i, C.c_void_p, C.c_long, P(C.c_long)]
+    L.SolRx_JpegEntropyGranularity.argtypes = [P(i)]
+    L.SolRx_JpegEntropyGranularity.restype = None
+    L.SolRx_JpegEntropyPrefix.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
+    L.SolRx_JpegEntropyPrefix.restype = None
+    L.SolRx_JpegBlockBits.argtypes = [C.c_void_p, i, i]
     L.SolRx_AddMetaballs.argtypes = [P(IsoGrid), C.c_void_p, i, i]
     L.SolRx_IsoField.argtypes = [P(IsoGrid), C.c_void_p, i, C.c_void_p]
     L.SolRx_IsoSurface.argtypes = [P(IsoGrid), C.c_void_p, C.c_void_p, i]
@@ -887,6 +901,43 @@ class Kernel:
                                          sampling[0], sampling[1], int(bool(turned)), int(bool(swap_red_blue)))
         if status != 0:
             raise SolrError("SolRx_EncodeJpeg refused its arguments or could not write %s" % path)
+
+    def _jpeg_file(self, call, what, room=1 << 16):
+        """`call(buffer address, capacity, byref(size))` until the file fits: the bytes."""
+        for _ in range(2):
+            buf = np.empty(room, np.uint8)
+            size = C.c_long(0)
+            status = call(buf.ctypes.data, room, C.byref(size))
+            if status == 0:
+                return buf[:size.value].tobytes()
+            if size.value <= room:
+                break
+            room = size.value
+        text = C.create_string_buffer(512)
+        if self.L.SolRx_LastError(text, 512) != 0:
+            raise SolrError("%s failed: %s" % (what, text.value.decode()))
+        raise SolrError("%s refused its arguments (out of range, or a block outside what the standard tables code)" % what)
+
+    def render_jpeg(self, quality=85, sampling=(2, 2), **scene_info):
+        """One frame as render() renders it, returned as the bytes of a baseline JPEG file (SolRx_RenderJpeg) - the file a
+        one-pass screenshot of the same size and settings would be.  quality: JPEG quality 1 ... 100; sampling: luma
+        (H, V), one of (1, 1), (2, 1), (2, 2).  With the HIP engine the frame is coded on the device and only the file
+        comes to the host: the host bitmap (SolRx_GetBitmap) is not refreshed.  A file larger than the first buffer costs
+        a second frame: the call is repeated with the size the first one reported."""
+        if scene_info:
+            self.set_scene_info(**scene_info)
+        room = max(1 << 16, self.info["width"] * self.info["height"] // 2)
+        return self._jpeg_file(lambda to, n, size: self.L.SolRx_RenderJpeg(0.0, quality, sampling[0], sampling[1], to, n, size),
+                               "SolRx_RenderJpeg", room)
+
+    def jpeg_from_coefficients(self, blocks, width, height, quality=85, sampling=(2, 2)):
+        """The bytes of the JPEG file of quantised coefficient `blocks` (n, 64) int16 in MCU and zigzag order, coded by
+        the engine's entropy stage (SolRx_JpegFileFromCoefficients): the device's kernels with the HIP engine, the same
+        steps in loops without a device."""
+        a = np.ascontiguousarray(blocks, dtype=np.int16).reshape(-1, 64)
+        return self._jpeg_file(lambda to, n, size: self.L.SolRx_JpegFileFromCoefficients(
+            a.ctypes.data, a.shape[0], width, height, quality, sampling[0], sampling[1], to, n, size),
+            "SolRx_JpegFileFromCoefficients", max(1 << 16, a.shape[0] * 64))
 
     def postprocessing_buffer(self):
         """Float framebuffer of the last frame: (H, W, 8) = colorInfo.xyzw, sceneInfo.xyzw."""

@@ -1027,6 +1027,7 @@ struct Engine
     int nbTilesTimed = 0;
     void *boundBitmap = nullptr;
     int width = 0, height = 0;       /* full image */
+    int frameBufferType = -1;        /* the channel order of the frame rendered last (-1: none yet); solr_hip_frame_to_jpeg_scan */
     int firstRow = 0, nbRows = -1;   /* strip; nbRows < 0 -> full frame, 0 -> this process renders no row */
     int allocW = 0, allocRows = 0;
 

@@ -1,0 +1,323 @@
+/*
+ * jpeg_entropy.h - the entropy stage of the JPEG writer: quantised coefficient blocks in zigzag order, as the pixel stage
+ * (jpeg_encode.h) leaves them, to the entropy-coded segment of a baseline file.  Integer arithmetic only, written once for
+ * both sides: the host-only engine runs it in loops (host/JpegWriter.cpp, JpegWriter::scan), the HIP engine in kernels
+ * (csrc/solr_jpeg_entropy.hip).
+ *
+ * The bytes are those of the reference encoder's one-pass coder, solr/images/jpge.cpp: put_bits (:817-835),
+ * code_coefficients_pass_two (:883-952) and terminate_pass_two (:1032-1039).  That coder walks the blocks once with a bit
+ * buffer; here the same stream is made in steps none of which depends on the block before it:
+ *   bits      blockBits: how many bits each block takes
+ *   prefix    exclusiveSum of them: the bit offset of every block, 64 bits wide
+ *   emit      blockEmit: every block at its offset of an UNSTUFFED stream of 32-bit words (bit 31 of word 0 is the first
+ *             bit).  Neighbours share words; bits only ever go in by OR, which commutes
+ *   tail      tailBits: the one-bits that complete a started last byte
+ *   count     countFF: the 0xFF bytes of every chunk of the unstuffed stream; exclusiveSum of those
+ *   stuff     stuffWord: every chunk to its offset plus the number of 0xFF before it, a zero byte behind each 0xFF
+ * tests/golden/jpeg_encoder.npz holds jpge's own files; tests/test_jpeg_entropy.py holds the steps to them and to the
+ * one-pass writer (JpegWriter::encode).
+ *
+ * The domain is what the four standard tables can code: a DC difference of category 0 ... 11 (|d| <= 2047) and AC
+ * coefficients of category 1 ... 10 (|a| <= 1023).  blockBits reports a block outside it.  The pixel stage cannot make
+ * one: its forward DCT is the orthonormal one (DC = sum / 8) of samples - 128 in -128 ... 127, so a DC lies in
+ * -1024 ... 1016 and two of them differ by at most 2040; an AC output is at most 128 * (sum over x of |cos((2x + 1) u pi / 16)|
+ * / 2)^2 <= 128 * (5.126 / 2)^2 = 841 for u, v > 0 and 128 * 8 * 5.126 / (4 * sqrt(2)) = 928 in row or column 0, and the
+ * rounding of the fixed-point passes adds a few units; quantisation divides by at least 1.  Blocks from elsewhere
+ * (SolRx_JpegFileFromCoefficients, solr_hip_jpeg_blocks_to_scan) are checked.
+ */
+#pragma once
+
+#include "jpeg_encode.h"
+
+namespace jpn
+{
+typedef unsigned int u32;
+typedef unsigned long long u64;
+typedef unsigned char u8;
+
+/* The granularities of the device's kernels, for the tests to put block counts and stream lengths around.  (The two
+ * prefix sums are hipcub's DeviceScan, as in solr_iso.hip: its tile is the library's, not a constant of this stage.) */
+constexpr int BLOCKS_PER_GROUP = 64;   /* blocks one workgroup assembles in LDS, one per lane */
+constexpr int STUFF_CHUNK_BYTES = 256; /* unstuffed bytes one workgroup counts and scatters, one word per lane */
+
+/* ITU T.81 tables K.3 - K.6: the number of codes of each length 1..16, then the symbols in code order */
+constexpr u8 DC_LUMA_BITS[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+constexpr u8 DC_CHROMA_BITS[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+constexpr u8 DC_VALUES[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr u8 AC_LUMA_BITS[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+constexpr u8 AC_LUMA_VALUES[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
+    0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
+    0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+    0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+    0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
+    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+    0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+constexpr u8 AC_CHROMA_BITS[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+constexpr u8 AC_CHROMA_VALUES[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
+    0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
+    0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+    0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+    0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
+    0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+    0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+
+constexpr int MAX_DC_CATEGORY = 11, MAX_AC_CATEGORY = 10;
+constexpr int EOB = 0x00, ZRL = 0xF0;
+
+/* code and length per symbol of the four tables, luma then chroma: code | length << 16 (a length of 0: no such symbol) */
+struct Tables
+{
+    u32 dc[2][12];
+    u32 ac[2][256];
+};
+
+/* annex C: codes of one length count upwards, the next length continues from twice the last code + 2 (the rule of
+ * JpegWriter.cpp's tables before this header took them over) */
+constexpr void fillTable(const u8 bits[16], const u8 *values, u32 *entries)
+{
+    u32 next = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l)
+    {
+        for (int i = 0; i < bits[l - 1]; ++i, ++k)
+            entries[values[k]] = next++ | ((u32)l << 16);
+        next <<= 1;
+    }
+}
+
+constexpr Tables makeTables()
+{
+    Tables t = {};
+    fillTable(DC_LUMA_BITS, DC_VALUES, t.dc[0]);
+    fillTable(DC_CHROMA_BITS, DC_VALUES, t.dc[1]);
+    fillTable(AC_LUMA_BITS, AC_LUMA_VALUES, t.ac[0]);
+    fillTable(AC_CHROMA_BITS, AC_CHROMA_VALUES, t.ac[1]);
+    return t;
+}
+
+/* The most bits a block can take.  DC: the longest code plus its amplitude.  AC: every one of the 63 positions holds a
+ * coefficient with the longest code plus amplitude - a zero costs less: sixteen of them are one ZRL, and the end of block
+ * is not coded when position 63 is taken.  A bound, 1660: its DC term is the chroma tables' (11 + 11) and its AC term the
+ * luma tables' (16 + 10), so the longest block there is is a luma block of 20 + 63 * 26 = 1658 bits. */
+constexpr int maxBlockBits(const Tables &t)
+{
+    int dc = 0, ac = 0;
+    for (int table = 0; table < 2; ++table)
+    {
+        for (int size = 0; size <= MAX_DC_CATEGORY; ++size)
+            if ((int)(t.dc[table][size] >> 16) + size > dc)
+                dc = (int)(t.dc[table][size] >> 16) + size;
+        for (int run = 0; run < 16; ++run)
+            for (int size = 1; size <= MAX_AC_CATEGORY; ++size)
+                if ((int)(t.ac[table][(run << 4) + size] >> 16) + size > ac)
+                    ac = (int)(t.ac[table][(run << 4) + size] >> 16) + size;
+    }
+    return dc + 63 * ac;
+}
+constexpr int MAX_BLOCK_BITS = 22 + 63 * 26;
+static_assert(maxBlockBits(makeTables()) == MAX_BLOCK_BITS && MAX_BLOCK_BITS == 1660, "the standard tables' longest block");
+/* ... and a ZRL or an EOB must not cost more than the coefficients they stand for could */
+static_assert((makeTables().ac[0][ZRL] >> 16) <= 26 && (makeTables().ac[1][ZRL] >> 16) <= 26 &&
+                  (makeTables().ac[0][EOB] >> 16) <= 26 && (makeTables().ac[1][EOB] >> 16) <= 26,
+              "run symbols are shorter than a coefficient");
+
+JPE_HD inline const Tables &tables()
+{
+    static constexpr Tables t = makeTables();
+    return t;
+}
+
+/* ---- which block precedes which ------------------------------------------------------------------------------------- */
+/* The blocks come MCU by MCU, inside an MCU the lumaBlocks (1, 2 or 4) luma blocks, then Cb, then Cr
+ * (solr_hip_rgb_to_jpeg_blocks).  0 for luma, 1 for chroma: the tables of block `index` */
+JPE_HD inline int chromaOf(long index, int lumaBlocks)
+{
+    return (int)(index % (lumaBlocks + 2)) >= lumaBlocks ? 1 : 0;
+}
+/* the block whose DC the DC of block `index` is coded against - the last block of the same component (jpge.cpp:883-900,
+ * m_last_dc_val per component) - or -1 for the first of each */
+JPE_HD inline long predecessor(long index, int lumaBlocks)
+{
+    const int perMcu = lumaBlocks + 2;
+    const long mcu = index / perMcu;
+    const int within = (int)(index - mcu * perMcu);
+    if (within > 0 && within < lumaBlocks)
+        return index - 1;
+    if (mcu == 0)
+        return -1;
+    return within == 0 ? index - 3 : index - perMcu; /* the last luma block of the MCU before; the same chroma block of it */
+}
+
+/* ---- one block ------------------------------------------------------------------------------------------------------ */
+JPE_HD inline int bitLength(int magnitude)
+{
+    return magnitude ? 32 - __builtin_clz((unsigned)magnitude) : 0;
+}
+
+/* F.1.2.1 / F.1.2.2: the low `size` bits of the value, of the value - 1 when it is negative */
+JPE_HD inline u32 amplitude(int value, int size)
+{
+    return (u32)(value < 0 ? value - 1 : value) & ((1u << size) - 1u);
+}
+
+/* The walk over a block (jpge.cpp:883-952), handing every symbol with its amplitude - at most 16 + 11 bits - to
+ * sink.put(bits, n).  Returns whether the block is inside the domain; outside it the category is held at the tables' last,
+ * so that the walk still takes the bits blockBits counted and no others. */
+template <class Sink>
+JPE_HD inline bool walkBlock(const short *block, int previousDc, int chroma, Sink &sink)
+{
+    const Tables &t = tables();
+    bool inside = true;
+    const int difference = block[0] - previousDc;
+    int size = bitLength(difference < 0 ? -difference : difference);
+    if (size > MAX_DC_CATEGORY)
+    {
+        inside = false;
+        size = MAX_DC_CATEGORY;
+    }
+    u32 entry = t.dc[chroma][size];
+    sink.put(((entry & 0xffffu) << size) | amplitude(difference, size), (int)(entry >> 16) + size);
+    int run = 0;
+    for (int k = 1; k < 64; ++k)
+    {
+        const int value = block[k];
+        if (value == 0)
+        {
+            ++run;
+            continue;
+        }
+        entry = t.ac[chroma][ZRL];
+        for (; run >= 16; run -= 16)
+            sink.put(entry & 0xffffu, (int)(entry >> 16));
+        size = bitLength(value < 0 ? -value : value);
+        if (size > MAX_AC_CATEGORY)
+        {
+            inside = false;
+            size = MAX_AC_CATEGORY;
+        }
+        entry = t.ac[chroma][(run << 4) + size];
+        sink.put(((entry & 0xffffu) << size) | amplitude(value, size), (int)(entry >> 16) + size);
+        run = 0;
+    }
+    if (run)
+    {
+        entry = t.ac[chroma][EOB];
+        sink.put(entry & 0xffffu, (int)(entry >> 16));
+    }
+    return inside;
+}
+
+struct BitCounter
+{
+    u32 bits = 0;
+    JPE_HD void put(u32, int n) { bits += (u32)n; }
+};
+
+/* bits: DC category and amplitude, a ZRL per sixteen zeros in front of a coefficient, a symbol and an amplitude per
+ * coefficient, EOB unless position 63 is taken; at most MAX_BLOCK_BITS.  false: the block is outside the domain */
+JPE_HD inline bool blockBits(const short *block, int previousDc, int chroma, u32 *bits)
+{
+    BitCounter counter;
+    const bool inside = walkBlock(block, previousDc, chroma, counter);
+    *bits = counter.bits;
+    return inside;
+}
+
+/* the two words that n (1 ... 32) bits at bit offset `at` of the stream touch, and what goes into each */
+JPE_HD inline void placeBits(u64 at, u32 bits, int n, u64 *word, u32 *first, u32 *second)
+{
+    const u64 window = (u64)bits << (64 - n - (int)(at & 31u));
+    *word = at >> 5;
+    *first = (u32)(window >> 32);
+    *second = (u32)window;
+}
+
+struct WordWriter
+{
+    u32 *words;
+    u64 at;
+    JPE_HD void put(u32 bits, int n)
+    {
+        u64 word;
+        u32 first, second;
+        placeBits(at, bits, n, &word, &first, &second);
+        words[word] |= first;
+        if (second)
+            words[word + 1] |= second;
+        at += (u64)n;
+    }
+};
+
+/* the same walk, the bits ORed into `words` from bit offset `at` on */
+JPE_HD inline void blockEmit(const short *block, int previousDc, int chroma, u64 at, u32 *words)
+{
+    WordWriter writer = {words, at};
+    walkBlock(block, previousDc, chroma, writer);
+}
+
+/* ---- the end of the stream -------------------------------------------------------------------------------------------- */
+/* jpge.cpp:1032-1039, put_bits(0x7F, 7): a started last byte is completed with one-bits, a complete one gets nothing.  How
+ * many one-bits follow a stream of totalBits; the completed byte is stuffed like any other when it comes out as 0xFF */
+JPE_HD inline int tailBits(u64 totalBits)
+{
+    return (int)((8u - (u32)(totalBits & 7u)) & 7u);
+}
+JPE_HD inline u64 streamBytes(u64 totalBits)
+{
+    return (totalBits + 7u) >> 3;
+}
+JPE_HD inline u64 streamWords(u64 totalBits)
+{
+    return (totalBits + 31u) >> 5;
+}
+
+/* ---- stuffing --------------------------------------------------------------------------------------------------------- */
+/* byte j of the stream is bits 31 - 8 (j & 3) ... 24 - 8 (j & 3) of word j >> 2.  The 0xFF among the first nbBytes (0 ... 4)
+ * bytes of a word */
+JPE_HD inline u32 countFF(u32 word, int nbBytes)
+{
+    u32 n = 0;
+    for (int i = 0; i < nbBytes; ++i)
+        n += ((word >> (24 - 8 * i)) & 0xffu) == 0xffu ? 1u : 0u;
+    return n;
+}
+/* those bytes to `to`, a zero behind every 0xFF (B.1.1.5); returns how many were written: nbBytes + countFF */
+JPE_HD inline u32 stuffWord(u32 word, int nbBytes, u8 *to)
+{
+    u32 n = 0;
+    for (int i = 0; i < nbBytes; ++i)
+    {
+        const u8 b = (u8)(word >> (24 - 8 * i));
+        to[n++] = b;
+        if (b == 0xffu)
+            to[n++] = 0;
+    }
+    return n;
+}
+/* how many of the stream's nbBytes bytes word `index` holds */
+JPE_HD inline int bytesOfWord(u64 index, u64 nbBytes)
+{
+    const u64 from = index * 4u;
+    return from >= nbBytes ? 0 : (nbBytes - from < 4u ? (int)(nbBytes - from) : 4);
+}
+
+/* ---- prefix sums ------------------------------------------------------------------------------------------------------ */
+/* offsets[i] = lengths[0] + ... + lengths[i - 1] for i = 0 ... n (n + 1 results, the last the total), 64 bits wide:
+ * SOLR_JPEG_MAX_PIXELS is 2^26 pixels, 1.5 M blocks of up to 1660 bits pass 2^32 */
+inline void exclusiveSum(const u32 *lengths, long n, u64 *offsets)
+{
+    u64 sum = 0;
+    for (long i = 0; i < n; ++i)
+    {
+        offsets[i] = sum;
+        sum += lengths[i];
+    }
+    offsets[n] = sum;
+}
+} // namespace jpn

@@ -25,6 +25,7 @@
 #include <string>
 
 #include "engine.h"
+#include "jpeg_device.h"
 #include "jpeg_encode.h"
 
 namespace
@@ -38,12 +39,7 @@ struct JpegEncodeGeometry
     int width, height, lumaH, lumaV, turned, swapRedBlue, mcusPerRow;
 };
 
-/* what the quantise step reads: the luma and the chroma table in zigzag order, then their reciprocals */
-struct JpegEncodeTables
-{
-    unsigned short quant[2][64];
-    unsigned recip[2][64];
-};
+using solreng::JpegEncodeTables;
 
 __global__ __launch_bounds__(64) void k_jpegCoefficients(const JpegEncodeGeometry geo,
                                                          const JpegEncodeTables *__restrict__ tables,
@@ -128,6 +124,60 @@ std::atomic<unsigned long long> gEncodedBlocks{0};
 inline size_t roundUp(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 }
 
+namespace solreng
+{
+bool jpegSourceAccepted(const char *who, const SolrJpegSource *source, long *nbBlocks)
+{
+    const std::string name(who);
+    if (!jpe::samplingSupported(source->lumaH, source->lumaV))
+    {
+        setError(-1, (name + ": luma sampling must be 1x1, 2x1 or 2x2").c_str(), __FILE__, __LINE__);
+        return false;
+    }
+    if (source->width < 1 || source->height < 1 || source->width > SOLR_JPEG_MAX_SIDE ||
+        source->height > SOLR_JPEG_MAX_SIDE || (long)source->width * source->height > SOLR_JPEG_MAX_PIXELS)
+    {
+        setError(-1, (name + ": image size out of range").c_str(), __FILE__, __LINE__);
+        return false;
+    }
+    if (source->quality < 1 || source->quality > 100)
+    {
+        setError(-1, (name + ": the JPEG quality must be 1 ... 100").c_str(), __FILE__, __LINE__);
+        return false;
+    }
+    const int mcusPerRow = (source->width + 8 * source->lumaH - 1) / (8 * source->lumaH);
+    const int mcuRows = (source->height + 8 * source->lumaV - 1) / (8 * source->lumaV);
+    *nbBlocks = (long)mcusPerRow * mcuRows * jpe::blocksPerMcu(source->lumaH, source->lumaV);
+    return true;
+}
+
+void launchJpegCoefficients(const SolrJpegSource &source, JpegEncodeTables &tables, JpegEncodeTables *dTables,
+                            const unsigned char *dRgb, short *dCoefficients, long nbBlocks, hipStream_t stream)
+{
+    for (int t = 0; t < 2; ++t)
+    {
+        jpe::quantTable(source.quality, t, tables.quant[t]);
+        for (int k = 0; k < 64; ++k)
+            tables.recip[t][k] = jpe::reciprocal(tables.quant[t][k]);
+    }
+    const int mcusPerRow = (source.width + 8 * source.lumaH - 1) / (8 * source.lumaH);
+    const int mcuRows = (source.height + 8 * source.lumaV - 1) / (8 * source.lumaV);
+    HIPCHECK(hipMemcpyAsync(dTables, &tables, sizeof(tables), hipMemcpyHostToDevice, stream));
+    if (!ok())
+        return;
+    const JpegEncodeGeometry geo = {source.width,       source.height,           source.lumaH, source.lumaV,
+                                    source.turned != 0, source.swapRedBlue != 0, mcusPerRow};
+    const dim3 grid((unsigned)((mcusPerRow + MCUS_PER_GROUP - 1) / MCUS_PER_GROUP), (unsigned)mcuRows);
+    k_jpegCoefficients<<<grid, dim3(64), 0, stream>>>(geo, dTables, dRgb, dCoefficients);
+    HIPCHECK(hipGetLastError());
+}
+
+void countJpegEncodedBlocks(long nbBlocks)
+{
+    gEncodedBlocks += (unsigned long long)nbBlocks;
+}
+}
+
 extern "C" {
 
 int solr_hip_rgb_to_jpeg_blocks(const SolrJpegSource *source, const unsigned char *rgb, short *coefficients,
@@ -142,40 +192,16 @@ int solr_hip_rgb_to_jpeg_blocks(const SolrJpegSource *source, const unsigned cha
         setError(-1, "solr_hip_rgb_to_jpeg_blocks: null source, rgb or coefficients", __FILE__, __LINE__);
         return -1;
     }
-    if (!jpe::samplingSupported(source->lumaH, source->lumaV))
-    {
-        setError(-1, "solr_hip_rgb_to_jpeg_blocks: luma sampling must be 1x1, 2x1 or 2x2", __FILE__, __LINE__);
+    long expected = 0;
+    if (!jpegSourceAccepted("solr_hip_rgb_to_jpeg_blocks", source, &expected))
         return -1;
-    }
-    if (source->width < 1 || source->height < 1 || source->width > SOLR_JPEG_MAX_SIDE ||
-        source->height > SOLR_JPEG_MAX_SIDE || (long)source->width * source->height > SOLR_JPEG_MAX_PIXELS)
-    {
-        setError(-1, "solr_hip_rgb_to_jpeg_blocks: image size out of range", __FILE__, __LINE__);
-        return -1;
-    }
-    if (source->quality < 1 || source->quality > 100)
-    {
-        setError(-1, "solr_hip_rgb_to_jpeg_blocks: the JPEG quality must be 1 ... 100", __FILE__, __LINE__);
-        return -1;
-    }
-    const int perMcu = jpe::blocksPerMcu(source->lumaH, source->lumaV);
-    const int mcusPerRow = (source->width + 8 * source->lumaH - 1) / (8 * source->lumaH);
-    const int mcuRows = (source->height + 8 * source->lumaV - 1) / (8 * source->lumaV);
-    const long nbMcus = (long)mcusPerRow * mcuRows;
-    if (nbBlocks != nbMcus * perMcu)
+    if (nbBlocks != expected)
     {
         setError(-1, "solr_hip_rgb_to_jpeg_blocks: nbBlocks does not match the image size and sampling", __FILE__,
                  __LINE__);
         return -1;
     }
-
     JpegEncodeTables tables;
-    for (int t = 0; t < 2; ++t)
-    {
-        jpe::quantTable(source->quality, t, tables.quant[t]);
-        for (int k = 0; k < 64; ++k)
-            tables.recip[t][k] = jpe::reciprocal(tables.quant[t][k]);
-    }
 
     /* on the engine's device whichever thread calls; the caller's current device is restored on the way out */
     int before = -1;
@@ -197,21 +223,14 @@ int solr_hip_rgb_to_jpeg_blocks(const SolrJpegSource *source, const unsigned cha
         JpegEncodeTables *dTables = reinterpret_cast<JpegEncodeTables *>(device);
         short *dCoefficients = reinterpret_cast<short *>(device + tableBytes);
         unsigned char *dRgb = device + tableBytes + roundUp(coefficientBytes);
-        HIPCHECK(hipMemcpyAsync(dTables, &tables, sizeof(tables), hipMemcpyHostToDevice, stream));
         HIPCHECK(hipMemcpyAsync(dRgb, rgb, rgbBytes, hipMemcpyHostToDevice, stream));
         if (ok())
-        {
-            const JpegEncodeGeometry geo = {source->width,       source->height,           source->lumaH, source->lumaV,
-                                            source->turned != 0, source->swapRedBlue != 0, mcusPerRow};
-            const dim3 grid((unsigned)((mcusPerRow + MCUS_PER_GROUP - 1) / MCUS_PER_GROUP), (unsigned)mcuRows);
-            k_jpegCoefficients<<<grid, dim3(64), 0, stream>>>(geo, dTables, dRgb, dCoefficients);
-            HIPCHECK(hipGetLastError());
-        }
+            launchJpegCoefficients(*source, tables, dTables, dRgb, dCoefficients, nbBlocks, stream);
         if (ok())
             HIPCHECK(hipMemcpyAsync(coefficients, dCoefficients, coefficientBytes, hipMemcpyDeviceToHost, stream));
         HIPCHECK(hipStreamSynchronize(stream));
         if (ok())
-            gEncodedBlocks += (unsigned long long)nbBlocks;
+            countJpegEncodedBlocks(nbBlocks);
     }
     if (device)
         (void)hipFree(device);

@@ -1,0 +1,459 @@
+/*
+ * solr_jpeg_entropy.hip - the entropy stage of the JPEG writer on the device (include/solr_hip.h,
+ * solr_hip_jpeg_blocks_to_scan, solr_hip_rgb_to_jpeg_scan, solr_hip_frame_to_jpeg_scan): quantised coefficient blocks to
+ * the entropy-coded segment of a baseline file, the bytes of the one-pass coder (host/JpegWriter.cpp, the reference's
+ * solr/images/jpge.cpp).  The arithmetic is jpeg_entropy.h, and this file is only its lane mapping.  gfx950 only.
+ *
+ *   k_jpegBlockBits   a lane per block: the walk of jpn::blockBits, the count as a 64-bit item; a block outside the tables'
+ *                     domain raises the flag word
+ *   (scan)            hipcub::DeviceScan::ExclusiveSum over n + 1 items - the scan solr_iso.hip uses, with 64-bit items: the
+ *                     bit offset of every block and, as item n, the total
+ *   k_jpegEmit        a wave64 workgroup per jpn::BLOCKS_PER_GROUP consecutive blocks, a lane per block: the same walk, the
+ *                     bits ORed (LDS atomics - neighbouring lanes share words) into the group's piece of the stream in LDS.
+ *                     The piece then goes out word by word: the words strictly inside it are all this group's and leave as
+ *                     plain stores, the first and the last may be shared with the groups on either side and are ORed into
+ *                     the zeroed stream with a vector atomic.  OR commutes: the stream does not depend on who comes first.
+ *                     The lane of the last block also puts the tail's one-bits
+ *   k_jpegCountFF     a workgroup per jpn::STUFF_CHUNK_BYTES bytes of the unstuffed stream, a lane per word: the 0xFF bytes
+ *                     of the chunk, summed across the wave
+ *   (scan)            the same scan over the chunks: the 0xFF bytes before each, and their total
+ *   k_jpegStuff       the same mapping: a lane's word goes to the chunk's offset plus the 0xFF before the chunk plus the
+ *                     0xFF of the lanes below it (a scan across the wave), a zero behind every 0xFF
+ * A block's coefficients are read once per walk from LDS, where the group's blocks are staged with coalesced loads, a block
+ * 33 words apart: the lanes of a 32-lane half then read 32 different banks.  The predecessor's DC (jpn::predecessor) is one
+ * global load.  Nothing is indexed by a run-time value in registers: no scratch.
+ */
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <atomic>
+#include <string>
+
+#include "engine.h"
+#include "jpeg_device.h"
+#include "jpeg_encode.h"
+#include "jpeg_entropy.h"
+
+namespace
+{
+using jpn::u32;
+using jpn::u64;
+using jpn::u8;
+
+constexpr int GROUP = 64;
+static_assert(jpn::BLOCKS_PER_GROUP == GROUP, "a lane per block");
+static_assert(jpn::STUFF_CHUNK_BYTES == GROUP * 4, "a lane per word of a chunk");
+constexpr int STAGE_PITCH = 33; /* words between two staged blocks of 32 words, see above */
+/* the words a group's piece can touch: its bits, the tail's (at most 7), and a start anywhere in a word */
+constexpr u32 GROUP_BITS = (u32)jpn::BLOCKS_PER_GROUP * jpn::MAX_BLOCK_BITS + 7u;
+constexpr int GROUP_WORDS = (int)((GROUP_BITS + 31u + 31u) / 32u);
+
+/* the group's blocks from `coefficients` (block `first` on, `count` of them) into `staged`, STAGE_PITCH words apart */
+__device__ inline void stageBlocks(const short *__restrict__ coefficients, long first, int count, u32 *staged)
+{
+    const u32 *from = reinterpret_cast<const u32 *>(coefficients + first * 64);
+    for (int i = threadIdx.x; i < count * 32; i += GROUP)
+        staged[(i >> 5) * STAGE_PITCH + (i & 31)] = from[i];
+    __syncthreads();
+}
+
+__device__ inline int previousDc(const short *__restrict__ coefficients, long index, int lumaBlocks)
+{
+    const long before = jpn::predecessor(index, lumaBlocks);
+    return before < 0 ? 0 : (int)coefficients[before * 64];
+}
+
+__global__ __launch_bounds__(GROUP) void k_jpegBlockBits(const short *__restrict__ coefficients, const int nbBlocks,
+                                                         const int lumaBlocks, u64 *__restrict__ bits,
+                                                         u32 *__restrict__ flag)
+{
+    __shared__ u32 staged[GROUP * STAGE_PITCH];
+    const long first = (long)blockIdx.x * GROUP;
+    const int count = nbBlocks - first < GROUP ? (int)(nbBlocks - first) : GROUP;
+    stageBlocks(coefficients, first, count, staged);
+    const int lane = threadIdx.x;
+    if (blockIdx.x == 0 && lane == 0)
+        bits[nbBlocks] = 0; /* item n of the scan: its result is the total */
+    if (lane >= count)
+        return;
+    const long index = first + lane;
+    u32 n = 0;
+    const bool inside = jpn::blockBits(reinterpret_cast<const short *>(staged + lane * STAGE_PITCH),
+                                       previousDc(coefficients, index, lumaBlocks), jpn::chromaOf(index, lumaBlocks), &n);
+    bits[index] = n;
+    if (!inside)
+        atomicOr(flag, 1u);
+}
+
+/* jpn::WordWriter on words that other lanes write too */
+struct SharedWriter
+{
+    u32 *words;
+    u32 at;
+    __device__ void put(u32 bits, int n)
+    {
+        u64 word;
+        u32 first, second;
+        jpn::placeBits(at, bits, n, &word, &first, &second);
+        atomicOr(&words[word], first);
+        if (second)
+            atomicOr(&words[word + 1], second);
+        at += (u32)n;
+    }
+};
+
+__global__ __launch_bounds__(GROUP) void k_jpegEmit(const short *__restrict__ coefficients, const int nbBlocks,
+                                                    const int lumaBlocks, const u64 *__restrict__ offsets,
+                                                    u32 *__restrict__ stream)
+{
+    __shared__ u32 staged[GROUP * STAGE_PITCH];
+    __shared__ u32 piece[GROUP_WORDS];
+    const int lane = threadIdx.x;
+    const long first = (long)blockIdx.x * GROUP;
+    const int count = nbBlocks - first < GROUP ? (int)(nbBlocks - first) : GROUP;
+    const bool last = first + count == nbBlocks;
+    const u64 from = offsets[first];
+    u64 to = offsets[first + count];
+    if (last)
+        to += (u64)jpn::tailBits(to);
+    /* (what k_jpegBlockBits counted cannot be more: the guard is against offsets that are not its scan) */
+    if (to <= from || to - from > GROUP_BITS)
+        return;
+    const u64 firstWord = from >> 5;
+    const int nbWords = (int)(((to - 1) >> 5) - firstWord) + 1;
+    for (int w = lane; w < nbWords; w += GROUP)
+        piece[w] = 0;
+    stageBlocks(coefficients, first, count, staged); /* (ends in a barrier) */
+    if (lane < count)
+    {
+        const long index = first + lane;
+        SharedWriter writer = {piece, (u32)(offsets[index] - (firstWord << 5))};
+        jpn::walkBlock(reinterpret_cast<const short *>(staged + lane * STAGE_PITCH),
+                       previousDc(coefficients, index, lumaBlocks), jpn::chromaOf(index, lumaBlocks), writer);
+        if (index == nbBlocks - 1)
+            if (const int tail = jpn::tailBits(offsets[nbBlocks]))
+                writer.put((1u << tail) - 1u, tail);
+    }
+    __syncthreads();
+    for (int w = lane; w < nbWords; w += GROUP)
+    {
+        const u32 value = piece[w];
+        if (w == 0 || w == nbWords - 1)
+            atomicOr(&stream[firstWord + w], value);
+        else
+            stream[firstWord + w] = value;
+    }
+}
+
+/* the sum of `value` over the wave, in every lane */
+__device__ inline u32 waveSum(u32 value)
+{
+    for (int step = 1; step < GROUP; step <<= 1)
+        value += __shfl_xor(value, step, GROUP);
+    return value;
+}
+
+__global__ __launch_bounds__(GROUP) void k_jpegCountFF(const u32 *__restrict__ stream, const u64 nbBytes,
+                                                       u64 *__restrict__ counts, const long nbChunks)
+{
+    const int lane = threadIdx.x;
+    const u64 index = (u64)blockIdx.x * GROUP + lane;
+    const int n = jpn::bytesOfWord(index, nbBytes);
+    const u32 total = waveSum(n ? jpn::countFF(stream[index], n) : 0u);
+    if (lane == 0)
+    {
+        counts[blockIdx.x] = total;
+        if (blockIdx.x == 0)
+            counts[nbChunks] = 0; /* item n of the scan */
+    }
+}
+
+__global__ __launch_bounds__(GROUP) void k_jpegStuff(const u32 *__restrict__ stream, const u64 nbBytes,
+                                                     const u64 *__restrict__ before, u8 *__restrict__ out)
+{
+    const int lane = threadIdx.x;
+    const u64 index = (u64)blockIdx.x * GROUP + lane;
+    const int n = jpn::bytesOfWord(index, nbBytes);
+    const u32 word = n ? stream[index] : 0u;
+    const u32 mine = jpn::countFF(word, n);
+    /* the 0xFF of the lanes below: an inclusive scan across the wave, less this lane's */
+    u32 below = mine;
+    for (int step = 1; step < GROUP; step <<= 1)
+    {
+        const u32 other = __shfl_up(below, step, GROUP);
+        if (lane >= step)
+            below += other;
+    }
+    below -= mine;
+    if (n)
+        jpn::stuffWord(word, n, out + (index * 4u + before[blockIdx.x] + below));
+}
+
+std::atomic<unsigned long long> gCodedBlocks{0};
+
+inline size_t roundUp(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+hipError_t exclusiveSum(void *temporary, size_t &temporaryBytes, const u64 *in, u64 *out, long n, hipStream_t stream)
+{
+    return hipcub::DeviceScan::ExclusiveSum(temporary, temporaryBytes, in, out, (int)n, stream);
+}
+
+/* The stage on `stream`: dCoefficients (nbBlocks blocks on the device) to the caller's `scan`.  0; or -1 - with the error
+ * set for a block outside the domain or a failed call, without for a capacity too small (*nbBytes then says what it
+ * takes).  `scan` is written only by the last copy, when everything before it went well. */
+int codeBlocks(const char *who, const short *dCoefficients, long nbBlocks, int lumaBlocks, hipStream_t stream,
+               unsigned char *scan, long capacity, long *nbBytes)
+{
+    using namespace solreng;
+    const long nbGroups = (nbBlocks + GROUP - 1) / GROUP;
+    unsigned char *first = nullptr, *second = nullptr, *third = nullptr;
+    int result = -1;
+    do
+    {
+        /* ---- bits, prefix ---- */
+        const size_t itemBytes = roundUp((size_t)(nbBlocks + 1) * sizeof(u64));
+        size_t scanBytes = 0;
+        HIPCHECK(exclusiveSum(nullptr, scanBytes, nullptr, nullptr, nbBlocks + 1, stream));
+        if (!ok())
+            break;
+        HIPCHECK(hipMalloc((void **)&first, 2 * itemBytes + roundUp(scanBytes) + 256));
+        if (!ok())
+            break;
+        u64 *dBits = reinterpret_cast<u64 *>(first), *dOffsets = reinterpret_cast<u64 *>(first + itemBytes);
+        unsigned char *dScan = first + 2 * itemBytes;
+        u32 *dFlag = reinterpret_cast<u32 *>(first + 2 * itemBytes + roundUp(scanBytes));
+        HIPCHECK(hipMemsetAsync(dFlag, 0, sizeof(u32), stream));
+        if (!ok())
+            break;
+        k_jpegBlockBits<<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks, lumaBlocks,
+                                                                              dBits, dFlag);
+        HIPCHECK(hipGetLastError());
+        if (ok())
+            HIPCHECK(exclusiveSum(dScan, scanBytes, dBits, dOffsets, nbBlocks + 1, stream));
+        u64 totalBits = 0;
+        u32 flag = 0;
+        if (ok())
+            HIPCHECK(hipMemcpyAsync(&totalBits, dOffsets + nbBlocks, sizeof(u64), hipMemcpyDeviceToHost, stream));
+        if (ok())
+            HIPCHECK(hipMemcpyAsync(&flag, dFlag, sizeof(u32), hipMemcpyDeviceToHost, stream));
+        if (ok())
+            HIPCHECK(hipStreamSynchronize(stream));
+        if (!ok())
+            break;
+        if (flag)
+        {
+            setError(-1, (std::string(who) + ": a block is outside what the standard tables code (|DC difference| <= 2047, "
+                                             "|AC| <= 1023)").c_str(), __FILE__, __LINE__);
+            break;
+        }
+        /* ---- emit, count, prefix ---- */
+        const u64 unstuffedBytes = jpn::streamBytes(totalBits);
+        const long nbChunks = (long)((unstuffedBytes + jpn::STUFF_CHUNK_BYTES - 1) / jpn::STUFF_CHUNK_BYTES);
+        const size_t streamBytes = roundUp((size_t)jpn::streamWords(totalBits + (u64)jpn::tailBits(totalBits)) * sizeof(u32));
+        const size_t chunkBytes = roundUp((size_t)(nbChunks + 1) * sizeof(u64));
+        size_t chunkScanBytes = 0;
+        HIPCHECK(exclusiveSum(nullptr, chunkScanBytes, nullptr, nullptr, nbChunks + 1, stream));
+        if (!ok())
+            break;
+        HIPCHECK(hipMalloc((void **)&second, streamBytes + 2 * chunkBytes + roundUp(chunkScanBytes)));
+        if (!ok())
+            break;
+        u32 *dStream = reinterpret_cast<u32 *>(second);
+        u64 *dCounts = reinterpret_cast<u64 *>(second + streamBytes);
+        u64 *dBefore = reinterpret_cast<u64 *>(second + streamBytes + chunkBytes);
+        unsigned char *dChunkScan = second + streamBytes + 2 * chunkBytes;
+        HIPCHECK(hipMemsetAsync(dStream, 0, streamBytes, stream));
+        if (!ok())
+            break;
+        k_jpegEmit<<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks, lumaBlocks, dOffsets,
+                                                                         dStream);
+        HIPCHECK(hipGetLastError());
+        if (!ok())
+            break;
+        k_jpegCountFF<<<dim3((unsigned)nbChunks), dim3(GROUP), 0, stream>>>(dStream, unstuffedBytes, dCounts, nbChunks);
+        HIPCHECK(hipGetLastError());
+        if (ok())
+            HIPCHECK(exclusiveSum(dChunkScan, chunkScanBytes, dCounts, dBefore, nbChunks + 1, stream));
+        u64 nbStuffed = 0;
+        if (ok())
+            HIPCHECK(hipMemcpyAsync(&nbStuffed, dBefore + nbChunks, sizeof(u64), hipMemcpyDeviceToHost, stream));
+        if (ok())
+            HIPCHECK(hipStreamSynchronize(stream));
+        if (!ok())
+            break;
+        *nbBytes = (long)(unstuffedBytes + nbStuffed);
+        if (*nbBytes > capacity)
+            break; /* (no error: the caller comes back with a buffer of that size) */
+        /* ---- stuff ---- */
+        HIPCHECK(hipMalloc((void **)&third, roundUp((size_t)*nbBytes)));
+        if (!ok())
+            break;
+        k_jpegStuff<<<dim3((unsigned)nbChunks), dim3(GROUP), 0, stream>>>(dStream, unstuffedBytes, dBefore, third);
+        HIPCHECK(hipGetLastError());
+        if (ok())
+            HIPCHECK(hipMemcpyAsync(scan, third, (size_t)*nbBytes, hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        if (!ok())
+            break;
+        gCodedBlocks += (unsigned long long)nbBlocks;
+        result = 0;
+    } while (false);
+    if (!ok())
+        (void)hipStreamSynchronize(stream); /* nothing of ours may still run when the buffers go */
+    for (unsigned char *buffer : {first, second, third})
+        if (buffer)
+            (void)hipFree(buffer);
+    return result;
+}
+
+/* what the three entries ask of the caller's buffer */
+bool outputAccepted(const char *who, const unsigned char *scan, long capacity, long *nbBytes)
+{
+    if (scan && capacity >= 0 && nbBytes)
+        return true;
+    solreng::setError(-1, (std::string(who) + ": null scan or nbBytes, or a negative capacity").c_str(), __FILE__, __LINE__);
+    return false;
+}
+
+/* solr_hip_jpeg_blocks_to_scan and solr_hip_rgb_to_jpeg_scan: exactly one of hostBlocks and hostRgb */
+int fromHost(const char *who, const SolrJpegSource *source, const short *hostBlocks, const unsigned char *hostRgb,
+             long nbBlocks, unsigned char *scan, long capacity, long *nbBytes)
+{
+    using namespace solreng;
+    int before = -1;
+    if (hipGetDevice(&before) != hipSuccess)
+        before = -1;
+    HIPCHECK(hipSetDevice(solr_hip_get_device()));
+    JpegEncodeTables tables;
+    const size_t tableBytes = roundUp(sizeof(tables));
+    const size_t coefficientBytes = (size_t)nbBlocks * 64 * sizeof(short);
+    const size_t rgbBytes = hostRgb ? (size_t)source->width * source->height * 3 : 0;
+    unsigned char *device = nullptr;
+    hipStream_t stream = nullptr;
+    int result = -1;
+    if (ok())
+        HIPCHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (ok())
+        HIPCHECK(hipMalloc((void **)&device, tableBytes + roundUp(coefficientBytes) + roundUp(rgbBytes)));
+    if (ok())
+    {
+        short *dCoefficients = reinterpret_cast<short *>(device + tableBytes);
+        unsigned char *dRgb = device + tableBytes + roundUp(coefficientBytes);
+        if (hostRgb)
+        {
+            HIPCHECK(hipMemcpyAsync(dRgb, hostRgb, rgbBytes, hipMemcpyHostToDevice, stream));
+            if (ok())
+                launchJpegCoefficients(*source, tables, reinterpret_cast<JpegEncodeTables *>(device), dRgb, dCoefficients,
+                                       nbBlocks, stream);
+        }
+        else
+            HIPCHECK(hipMemcpyAsync(dCoefficients, hostBlocks, coefficientBytes, hipMemcpyHostToDevice, stream));
+        if (ok())
+            result = codeBlocks(who, dCoefficients, nbBlocks, source->lumaH * source->lumaV, stream, scan, capacity, nbBytes);
+        (void)hipStreamSynchronize(stream);
+        if (hostRgb && ok() && result == 0)
+            countJpegEncodedBlocks(nbBlocks);
+    }
+    if (device)
+        (void)hipFree(device);
+    if (stream)
+        (void)hipStreamDestroy(stream);
+    if (before >= 0)
+        (void)hipSetDevice(before);
+    return ok() ? result : -1;
+}
+}
+
+extern "C" {
+
+int solr_hip_jpeg_blocks_to_scan(const SolrJpegSource *source, const short *coefficients, long nbBlocks,
+                                 unsigned char *scan, long capacity, long *nbBytes)
+{
+    using namespace solreng;
+    if (!ok())
+        return -1;
+    /* ---- arguments: nothing is launched for a call that fails here ---- */
+    if (!source || !coefficients)
+    {
+        setError(-1, "solr_hip_jpeg_blocks_to_scan: null source or coefficients", __FILE__, __LINE__);
+        return -1;
+    }
+    long expected = 0;
+    if (!outputAccepted("solr_hip_jpeg_blocks_to_scan", scan, capacity, nbBytes) ||
+        !jpegSourceAccepted("solr_hip_jpeg_blocks_to_scan", source, &expected))
+        return -1;
+    if (nbBlocks != expected)
+    {
+        setError(-1, "solr_hip_jpeg_blocks_to_scan: nbBlocks does not match the image size and sampling", __FILE__,
+                 __LINE__);
+        return -1;
+    }
+    return fromHost("solr_hip_jpeg_blocks_to_scan", source, coefficients, nullptr, nbBlocks, scan, capacity, nbBytes);
+}
+
+int solr_hip_rgb_to_jpeg_scan(const SolrJpegSource *source, const unsigned char *rgb, unsigned char *scan, long capacity,
+                              long *nbBytes)
+{
+    using namespace solreng;
+    if (!ok())
+        return -1;
+    if (!source || !rgb)
+    {
+        setError(-1, "solr_hip_rgb_to_jpeg_scan: null source or rgb", __FILE__, __LINE__);
+        return -1;
+    }
+    long nbBlocks = 0;
+    if (!outputAccepted("solr_hip_rgb_to_jpeg_scan", scan, capacity, nbBytes) ||
+        !jpegSourceAccepted("solr_hip_rgb_to_jpeg_scan", source, &nbBlocks))
+        return -1;
+    return fromHost("solr_hip_rgb_to_jpeg_scan", source, nullptr, rgb, nbBlocks, scan, capacity, nbBytes);
+}
+
+int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char *scan, long capacity, long *nbBytes)
+{
+    using namespace solreng;
+    if (!ready("solr_hip_frame_to_jpeg_scan"))
+        return -1;
+    /* declined, and no error: a frame in strips or on several devices is not in one image, and before the first frame
+     * there is none */
+    Flight &set = g.flight[g.current];
+    const unsigned char *image = reinterpret_cast<const unsigned char *>(g.boundBitmap ? g.boundBitmap : set.shown().ptr);
+    if (gDevices > 1 || g.nbRows >= 0 || g.frameBufferType < 0 || !image)
+        return -1;
+    const SolrJpegSource source = {g.width, g.height, lumaH, lumaV, quality, 1, g.frameBufferType != (int)ftRGB ? 1 : 0};
+    long nbBlocks = 0;
+    if (!outputAccepted("solr_hip_frame_to_jpeg_scan", scan, capacity, nbBytes) ||
+        !jpegSourceAccepted("solr_hip_frame_to_jpeg_scan", &source, &nbBlocks))
+        return -1;
+    HIPCHECK(hipSetDevice(g.device));
+    /* behind the frame, on its stream */
+    const hipStream_t stream = set.stream;
+    JpegEncodeTables tables;
+    const size_t tableBytes = roundUp(sizeof(tables));
+    unsigned char *device = nullptr;
+    int result = -1;
+    if (ok())
+        HIPCHECK(hipMalloc((void **)&device, tableBytes + roundUp((size_t)nbBlocks * 64 * sizeof(short))));
+    if (ok())
+    {
+        short *dCoefficients = reinterpret_cast<short *>(device + tableBytes);
+        launchJpegCoefficients(source, tables, reinterpret_cast<JpegEncodeTables *>(device), image, dCoefficients, nbBlocks,
+                               stream);
+        if (ok())
+            result = codeBlocks("solr_hip_frame_to_jpeg_scan", dCoefficients, nbBlocks, lumaH * lumaV, stream, scan, capacity,
+                                nbBytes);
+        (void)hipStreamSynchronize(stream);
+        if (ok() && result == 0)
+            countJpegEncodedBlocks(nbBlocks);
+    }
+    if (device)
+        (void)hipFree(device);
+    return ok() ? result : -1;
+}
+
+unsigned long long solr_hip_jpeg_coded_blocks(void)
+{
+    return gCodedBlocks.load();
+}
+
+} /* extern "C" */

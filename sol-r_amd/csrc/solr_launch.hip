@@ -201,6 +201,7 @@ static bool frameReady(const SceneInfo &sceneInfo, const vec4i &objects)
     HIPCHECK(hipSetDevice(g.device));
     g.width = sceneInfo.size.x;
     g.height = sceneInfo.size.y;
+    g.frameBufferType = (int)sceneInfo.frameBufferType;
     allocateFrame();
     return ok() && stripRows() != 0;
 }

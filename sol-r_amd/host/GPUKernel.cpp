@@ -1929,6 +1929,12 @@ static bool jpegSourceInRange(const SolrJpegSource &s)
            jpe::samplingSupported(s.lumaH, s.lumaV);
 }
 
+static long jpegBlocksOf(const SolrJpegSource &s)
+{
+    return (long)((s.width + 8 * s.lumaH - 1) / (8 * s.lumaH)) * ((s.height + 8 * s.lumaV - 1) / (8 * s.lumaV)) *
+           jpe::blocksPerMcu(s.lumaH, s.lumaV);
+}
+
 bool GPUKernel::jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb, std::vector<short> &coefficients)
 {
     if (!rgb || !jpegSourceInRange(source))
@@ -2002,20 +2008,96 @@ int GPUKernel::addMetaballs(const SolrIsoGrid &grid, const float *balls, int nbB
     return (int)triangles.size();
 }
 
-bool GPUKernel::encodeJpeg(const std::string &filename, const unsigned char *pixels, int width, int height,
+bool GPUKernel::jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks,
+                         std::vector<unsigned char> &scan)
+{
+    if (!coefficients || !jpegSourceInRange(source) || nbBlocks != jpegBlocksOf(source))
+        return false;
+    return JpegWriter::scan(source.lumaH, source.lumaV, coefficients, nbBlocks, scan);
+}
+
+bool GPUKernel::jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan)
+{
+    std::vector<short> coefficients;
+    return jpegCoefficients(source, rgb, coefficients) &&
+           jpegScan(source, coefficients.data(), (long)(coefficients.size() / 64), scan);
+}
+
+bool GPUKernel::jpegScanOfFrame(int, int, int, std::vector<unsigned char> &)
+{
+    return false;
+}
+
+/* SOI ... SOS of the file `source` describes, the segment, EOI */
+static void jpegFileAround(const SolrJpegSource &source, const std::vector<unsigned char> &scan,
+                           std::vector<unsigned char> &file)
+{
+    unsigned short quant[2][64];
+    jpe::quantTable(source.quality, 0, quant[0]);
+    jpe::quantTable(source.quality, 1, quant[1]);
+    file = JpegWriter::header(source.width, source.height, source.lumaH, source.lumaV, quant);
+    file.insert(file.end(), scan.begin(), scan.end());
+    file.push_back(0xFF);
+    file.push_back(0xD9);
+}
+
+bool GPUKernel::encodeJpeg(std::vector<unsigned char> &file, const unsigned char *pixels, int width, int height,
                            int jpegQuality, int lumaH, int lumaV, bool turned, bool swapRedBlue)
 {
     const SolrJpegSource source = {width, height, lumaH, lumaV, jpegQuality, turned ? 1 : 0, swapRedBlue ? 1 : 0};
-    if (filename.empty() || !pixels || !jpegSourceInRange(source))
+    if (!pixels || !jpegSourceInRange(source))
         return false;
-    std::vector<short> coefficients;
-    if (!jpegCoefficients(source, pixels, coefficients))
+    std::vector<unsigned char> scan;
+    if (!jpegScanOf(source, pixels, scan))
         return false;
-    unsigned short quant[2][64];
-    jpe::quantTable(jpegQuality, 0, quant[0]);
-    jpe::quantTable(jpegQuality, 1, quant[1]);
-    return JpegWriter::writeFile(filename, JpegWriter::encode(width, height, lumaH, lumaV, quant, coefficients.data(),
-                                                              (long)(coefficients.size() / 64)));
+    jpegFileAround(source, scan, file);
+    return true;
+}
+
+bool GPUKernel::encodeJpeg(const std::string &filename, const unsigned char *pixels, int width, int height,
+                           int jpegQuality, int lumaH, int lumaV, bool turned, bool swapRedBlue)
+{
+    std::vector<unsigned char> file;
+    return !filename.empty() && encodeJpeg(file, pixels, width, height, jpegQuality, lumaH, lumaV, turned, swapRedBlue) &&
+           JpegWriter::writeFile(filename, file);
+}
+
+bool GPUKernel::jpegFileFromCoefficients(std::vector<unsigned char> &file, const short *coefficients, long nbBlocks,
+                                         int width, int height, int jpegQuality, int lumaH, int lumaV)
+{
+    const SolrJpegSource source = {width, height, lumaH, lumaV, jpegQuality, 0, 0};
+    std::vector<unsigned char> scan;
+    if (!jpegScan(source, coefficients, nbBlocks, scan))
+        return false;
+    jpegFileAround(source, scan, file);
+    return true;
+}
+
+bool GPUKernel::renderJpeg(const float timer, int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &file)
+{
+    const SolrJpegSource source = {m_sceneInfo.size.x, m_sceneInfo.size.y, lumaH, lumaV, jpegQuality, 1,
+                                   m_sceneInfo.frameBufferType != ftRGB ? 1 : 0};
+    if (!jpegSourceInRange(source))
+        return false;
+    flushFrames();
+    m_jpegFrame = true; /* (the frame's image is wanted on the device, whole: render_begin sends no bands off) */
+    render_begin(timer);
+    m_jpegFrame = false;
+    if (lastError() != 0)
+        return false;
+    std::vector<unsigned char> scan;
+    if (jpegScanOfFrame(jpegQuality, lumaH, lumaV, scan))
+    {
+        jpegFileAround(source, scan, file);
+        return true;
+    }
+    if (lastError() != 0)
+        return false;
+    render_end();
+    flushFrames(); /* with frames in flight the image on show lags behind: wait for this frame's */
+    const BitmapBuffer *bitmap = getBitmap();
+    return lastError() == 0 && bitmap &&
+           encodeJpeg(file, bitmap, source.width, source.height, jpegQuality, lumaH, lumaV, true, source.swapRedBlue != 0);
 }
 
 /* reference: GPUKernel.cpp:2792-2852; what differs is said in GPUKernel.h */

@@ -196,7 +196,7 @@ void HipKernel::render_begin(const float timer)
         /* one frame at a time: the frame's waves say when a band of rows is complete, and render_end sends every band
          * off to the host - m_bitmap or SolR_RunKernel's array - while the rows below still render (include/solr_hip.h,
          * solr_hip_stream_next_image) */
-        const bool stream = m_flights == 1 && solr_hip_stream_next_image(1) == 1;
+        const bool stream = m_flights == 1 && !m_jpegFrame && solr_hip_stream_next_image(1) == 1;
         cudaRender(m_occupancyParameters, m_blockSize, sceneInfo, objects, m_postProcessingInfo, m_viewPos, m_viewDir,
                    m_angles);
         mark("render_begin: cudaRender");
@@ -305,6 +305,65 @@ bool HipKernel::jpegCoefficients(const SolrJpegSource &source, const unsigned ch
                    ((source.height + 8 * source.lumaV - 1) / (8 * source.lumaV)) * (source.lumaH * source.lumaV + 2);
     coefficients.resize((size_t)nbBlocks * 64);
     return solr_hip_rgb_to_jpeg_blocks(&source, rgb, coefficients.data(), nbBlocks) == 0;
+}
+
+/* the engine's entry with a buffer the segment fits in: the last one's size is tried first, and the call repeated only
+ * when the segment has outgrown it (the engine then says what it takes and has written nothing) */
+template <class Entry>
+static bool jpegScanInto(std::vector<unsigned char> &scan, size_t &capacity, Entry &&entry)
+{
+    scan.resize(capacity);
+    long nbBytes = 0;
+    int status = entry(scan.data(), (long)scan.size(), &nbBytes);
+    if (status != 0 && nbBytes > (long)scan.size())
+    {
+        scan.resize((size_t)nbBytes);
+        status = entry(scan.data(), (long)scan.size(), &nbBytes);
+    }
+    if (status != 0)
+    {
+        scan.clear();
+        return false;
+    }
+    scan.resize((size_t)nbBytes);
+    capacity = (size_t)nbBytes + (size_t)nbBytes / 8 + 4096;
+    return true;
+}
+
+bool HipKernel::jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks,
+                         std::vector<unsigned char> &scan)
+{
+    if (solr_hip_device_count() < 1)
+        return GPUKernel::jpegScan(source, coefficients, nbBlocks, scan);
+    return jpegScanInto(scan, m_jpegCapacity, [&](unsigned char *to, long capacity, long *nbBytes) {
+        return solr_hip_jpeg_blocks_to_scan(&source, coefficients, nbBlocks, to, capacity, nbBytes);
+    });
+}
+
+bool HipKernel::jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan)
+{
+    if (solr_hip_device_count() < 1)
+        return GPUKernel::jpegScanOf(source, rgb, scan);
+    return jpegScanInto(scan, m_jpegCapacity, [&](unsigned char *to, long capacity, long *nbBytes) {
+        return solr_hip_rgb_to_jpeg_scan(&source, rgb, to, capacity, nbBytes);
+    });
+}
+
+bool HipKernel::jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan)
+{
+    /* frames in flight: the image ring has this frame's copy under way and the engine's images alternate - not this way */
+    if (!m_deviceInitialized || m_flights > 1)
+        return false;
+    if (!jpegScanInto(scan, m_jpegCapacity, [&](unsigned char *to, long capacity, long *nbBytes) {
+            return solr_hip_frame_to_jpeg_scan(jpegQuality, lumaH, lumaV, to, capacity, nbBytes);
+        }))
+        return false;
+    /* what render_end would have left, but for the image: m_bitmap is not brought up to date, now or when asked */
+    m_bitmapView = nullptr;
+    m_streamed = false;
+    m_idsOnDevice = true;
+    m_bitmapOnDevice = false;
+    return true;
 }
 
 bool HipKernel::isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,

@@ -93,6 +93,12 @@ protected:
     /* solr_hip_rgb_to_jpeg_blocks (include/solr_hip.h) where there is a device, the base class's loop where there is none */
     bool jpegCoefficients(const SolrJpegSource &source, const unsigned char *rgb,
                           std::vector<short> &coefficients) override;
+    /* solr_hip_jpeg_blocks_to_scan, solr_hip_rgb_to_jpeg_scan (include/solr_hip.h) where there is a device, the base
+     * class's loops where there is none; solr_hip_frame_to_jpeg_scan for a frame rendered one at a time on one device */
+    bool jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks,
+                  std::vector<unsigned char> &scan) override;
+    bool jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan) override;
+    bool jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan) override;
     /* solr_hip_metaballs, solr_hip_iso_field, solr_hip_iso_surface (include/solr_hip.h) where there is a device, the base
      * class's loops where there is none */
     bool isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,
@@ -106,7 +112,8 @@ private:
     bool m_deviceInitialized;
     bool m_idsOnDevice = false;
     size_t m_isoCapacity = 4096; /* triangles the buffer of the next isoSurface call starts with */
-    bool m_streamed = false;       /* the frame render_begin launched counts its tiles: render_end takes its image band by band */
+    size_t m_jpegCapacity = 65536; /* bytes the buffer of the next entropy-coded segment starts with */
+    bool m_streamed = false;      /* the frame render_begin launched counts its tiles: render_end takes its image band by band */
     bool m_bitmapOnDevice = false; /* render_end(image) delivered to the caller's array: m_bitmap follows when asked */
     unsigned m_sharedSeed = 0, m_sharedState = 0; /* solr_hip_comm_shared_seed and the generator it seeds (render_begin) */
     int m_flights = 1;            /* frames in flight through render_begin / render_end (setFramesInFlight) */

@@ -6,38 +6,22 @@
 
 #include <cstdio>
 
+#include "../csrc/jpeg_entropy.h"
+
 namespace solr
 {
 namespace
 {
 typedef unsigned char u8;
 
-/* ITU T.81 tables K.3 - K.6: the number of codes of each length 1..16, then the symbols in code order */
-const u8 DC_LUMA_BITS[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
-const u8 DC_CHROMA_BITS[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-const u8 DC_VALUES[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const u8 AC_LUMA_BITS[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
-const u8 AC_LUMA_VALUES[162] = {
-    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
-    0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
-    0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
-    0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
-    0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
-    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
-    0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
-    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
-const u8 AC_CHROMA_BITS[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
-const u8 AC_CHROMA_VALUES[162] = {
-    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
-    0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
-    0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
-    0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
-    0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
-    0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
-    0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
-    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+/* ITU T.81 tables K.3 - K.6 (csrc/jpeg_entropy.h has them, for the decomposed coder too) */
+using jpn::AC_CHROMA_BITS;
+using jpn::AC_CHROMA_VALUES;
+using jpn::AC_LUMA_BITS;
+using jpn::AC_LUMA_VALUES;
+using jpn::DC_CHROMA_BITS;
+using jpn::DC_LUMA_BITS;
+using jpn::DC_VALUES;
 
 struct HuffmanTable
 {
@@ -125,16 +109,22 @@ void table(Stream &s, const HuffmanTable &t, int index)
     for (int i = 0; i < t.nbValues; ++i)
         s.byte(t.values[i]);
 }
-}
 
-std::vector<unsigned char> JpegWriter::encode(int width, int height, int lumaH, int lumaV,
-                                              const unsigned short quant[2][64], const short *blocks, long nbBlocks)
+const HuffmanTable &dcTable(int chroma)
 {
     static const HuffmanTable dc[2] = {HuffmanTable(DC_LUMA_BITS, DC_VALUES, 12), HuffmanTable(DC_CHROMA_BITS, DC_VALUES, 12)};
+    return dc[chroma];
+}
+const HuffmanTable &acTable(int chroma)
+{
     static const HuffmanTable ac[2] = {HuffmanTable(AC_LUMA_BITS, AC_LUMA_VALUES, 162),
                                        HuffmanTable(AC_CHROMA_BITS, AC_CHROMA_VALUES, 162)};
-    Stream s;
-    s.out.reserve(1024 + (size_t)nbBlocks * 32);
+    return ac[chroma];
+}
+
+void headerInto(Stream &s, int width, int height, int lumaH, int lumaV, const unsigned short quant[2][64])
+{
+    const HuffmanTable *dc = &dcTable(0), *ac = &acTable(0);
     /* jpge.cpp:517-525 emit_markers */
     s.marker(0xD8);
     s.marker(0xE0); /* JFIF 1.1, no density unit, aspect 1:1, no thumbnail (:418-434) */
@@ -184,6 +174,24 @@ std::vector<unsigned char> JpegWriter::encode(int width, int height, int lumaH, 
     s.byte(0);
     s.byte(63);
     s.byte(0);
+}
+}
+
+std::vector<unsigned char> JpegWriter::header(int width, int height, int lumaH, int lumaV,
+                                              const unsigned short quant[2][64])
+{
+    Stream s;
+    headerInto(s, width, height, lumaH, lumaV, quant);
+    return s.out;
+}
+
+std::vector<unsigned char> JpegWriter::encode(int width, int height, int lumaH, int lumaV,
+                                              const unsigned short quant[2][64], const short *blocks, long nbBlocks)
+{
+    const HuffmanTable *dc = &dcTable(0), *ac = &acTable(0);
+    Stream s;
+    s.out.reserve(1024 + (size_t)nbBlocks * 32);
+    headerInto(s, width, height, lumaH, lumaV, quant);
 
     /* the scan: :883-952 */
     const int lumaBlocks = lumaH * lumaV, perMcu = lumaBlocks + 2;
@@ -225,6 +233,63 @@ std::vector<unsigned char> JpegWriter::encode(int width, int height, int lumaH, 
     s.put(0x7F, 7);
     s.marker(0xD9);
     return s.out;
+}
+
+/* The same segment in the order the device takes (csrc/jpeg_entropy.h): every loop below runs over independent items */
+bool JpegWriter::scan(int lumaH, int lumaV, const short *blocks, long nbBlocks, std::vector<unsigned char> &out)
+{
+    const int lumaBlocks = lumaH * lumaV;
+    auto previousDc = [&](long index) {
+        const long before = jpn::predecessor(index, lumaBlocks);
+        return before < 0 ? 0 : (int)blocks[before * 64];
+    };
+    /* bits */
+    std::vector<jpn::u32> bits((size_t)nbBlocks);
+    bool inside = true;
+    for (long i = 0; i < nbBlocks; ++i)
+        inside &= jpn::blockBits(blocks + i * 64, previousDc(i), jpn::chromaOf(i, lumaBlocks), &bits[(size_t)i]);
+    if (!inside)
+        return false;
+    /* prefix */
+    std::vector<jpn::u64> offsets((size_t)nbBlocks + 1);
+    jpn::exclusiveSum(bits.data(), nbBlocks, offsets.data());
+    const jpn::u64 totalBits = offsets[(size_t)nbBlocks];
+    /* emit, and the tail */
+    std::vector<jpn::u32> words((size_t)jpn::streamWords(totalBits), 0u);
+    for (long i = 0; i < nbBlocks; ++i)
+        jpn::blockEmit(blocks + i * 64, previousDc(i), jpn::chromaOf(i, lumaBlocks), offsets[(size_t)i], words.data());
+    if (const int tail = jpn::tailBits(totalBits))
+    {
+        jpn::WordWriter writer = {words.data(), totalBits};
+        writer.put((1u << tail) - 1u, tail);
+    }
+    /* count */
+    const jpn::u64 nbBytes = jpn::streamBytes(totalBits);
+    const int wordsPerChunk = jpn::STUFF_CHUNK_BYTES / 4;
+    const long nbChunks = (long)((nbBytes + jpn::STUFF_CHUNK_BYTES - 1) / jpn::STUFF_CHUNK_BYTES);
+    std::vector<jpn::u32> counts((size_t)nbChunks, 0u);
+    for (long c = 0; c < nbChunks; ++c)
+        for (int w = 0; w < wordsPerChunk; ++w)
+        {
+            const jpn::u64 index = (jpn::u64)c * wordsPerChunk + w;
+            if (const int n = jpn::bytesOfWord(index, nbBytes))
+                counts[(size_t)c] += jpn::countFF(words[(size_t)index], n);
+        }
+    std::vector<jpn::u64> before((size_t)nbChunks + 1);
+    jpn::exclusiveSum(counts.data(), nbChunks, before.data());
+    /* stuff */
+    out.assign((size_t)(nbBytes + before[(size_t)nbChunks]), 0);
+    for (long c = 0; c < nbChunks; ++c)
+    {
+        jpn::u64 to = (jpn::u64)c * jpn::STUFF_CHUNK_BYTES + before[(size_t)c];
+        for (int w = 0; w < wordsPerChunk; ++w)
+        {
+            const jpn::u64 index = (jpn::u64)c * wordsPerChunk + w;
+            if (const int n = jpn::bytesOfWord(index, nbBytes))
+                to += jpn::stuffWord(words[(size_t)index], n, out.data() + to);
+        }
+    }
+    return true;
 }
 
 bool JpegWriter::writeFile(const std::string &filename, const std::vector<unsigned char> &bytes)

@@ -5,7 +5,9 @@
  * The file is the one the reference's encoder writes in its one-pass mode (solr/images/jpge.cpp): the markers in the
  * order of emit_markers (:517-525) - SOI, JFIF APP0, one DQT per table, SOF0, four DHT segments with the standard tables
  * of ITU T.81 annex K.3, SOS - then one interleaved scan coded as code_coefficients_pass_two does (:883-952), closed by
- * terminate_pass_two (:1032-1039).  Serial work: it stays on the host with either engine.
+ * terminate_pass_two (:1032-1039).  encode is that one-pass coder.  scan makes the same entropy-coded segment in the steps of
+ * csrc/jpeg_entropy.h - bits, prefix sum, emit, count, stuff - which is how the device codes it (csrc/solr_jpeg_entropy.hip)
+ * and what the host-only engine runs; a file is then header + scan + EOI.
  */
 #pragma once
 
@@ -22,6 +24,13 @@ public:
      * 2x2.  Returns the file's bytes. */
     static std::vector<unsigned char> encode(int width, int height, int lumaH, int lumaV,
                                              const unsigned short quant[2][64], const short *blocks, long nbBlocks);
+    /* everything encode writes in front of the entropy-coded segment: SOI ... SOS */
+    static std::vector<unsigned char> header(int width, int height, int lumaH, int lumaV,
+                                             const unsigned short quant[2][64]);
+    /* the entropy-coded segment of the same blocks - stuffed, the last byte completed, no EOI - by the loops of
+     * csrc/jpeg_entropy.h in the decomposed order.  false, `out` untouched, when a block is outside what the standard
+     * tables code (a DC difference beyond 2047, an AC coefficient beyond 1023) */
+    static bool scan(int lumaH, int lumaV, const short *blocks, long nbBlocks, std::vector<unsigned char> &out);
     static bool writeFile(const std::string &filename, const std::vector<unsigned char> &bytes);
 };
 }

@@ -15,6 +15,7 @@
 #include "GPUKernel.h"
 #include "JpegWriter.h"
 #include "../csrc/jpeg_encode.h"
+#include "../csrc/jpeg_entropy.h"
 #include "../csrc/iso_surface.h"
 #include "OBJReader.h"
 #include "PDBReader.h"
@@ -240,6 +241,74 @@ int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, 
                                                                           coefficients, nbBlocks))
                ? 0
                : -1;
+}
+
+/* a file in memory into the caller's buffer: 0; -1 with *nbBytes = the size needed when it does not fit (nothing is
+ * written) */
+static int jpegFileOut(const std::vector<unsigned char> &bytes, unsigned char *file, long capacity, long *nbBytes)
+{
+    *nbBytes = (long)bytes.size();
+    if (*nbBytes > capacity)
+        return -1;
+    memcpy(file, bytes.data(), bytes.size());
+    return 0;
+}
+
+/* Extension: the file of SolRx_JpegFromCoefficients in memory, its entropy-coded segment by the engine's entropy stage
+ * (GPUKernel::jpegFileFromCoefficients: the device's kernels, or the same steps in loops).  -1 with *nbBytes = 0: an
+ * argument out of range, a block outside what the standard tables code, or the engine failed */
+int SolRx_JpegFileFromCoefficients(const short *coefficients, long nbBlocks, int width, int height, int jpegQuality,
+                                   int lumaH, int lumaV, unsigned char *file, long capacity, long *nbBytes)
+{
+    if (!nbBytes)
+        return -1;
+    *nbBytes = 0;
+    std::vector<unsigned char> bytes;
+    if (!coefficients || !file || capacity < 0 ||
+        !SingletonKernel::kernel()->jpegFileFromCoefficients(bytes, coefficients, nbBlocks, width, height, jpegQuality,
+                                                             lumaH, lumaV))
+        return -1;
+    return jpegFileOut(bytes, file, capacity, nbBytes);
+}
+
+/* Extension: one frame as SolR_RunKernel renders it, delivered as a JPEG file in memory (GPUKernel::renderJpeg): with
+ * the HIP engine the frame is coded on the device and only the file crosses to the host; SolRx_GetBitmap() is not
+ * refreshed.  A file that does not fit is not kept: the next call renders the next frame */
+int SolRx_RenderJpeg(double timer, int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                     long *nbBytes)
+{
+    if (!nbBytes)
+        return -1;
+    *nbBytes = 0;
+    if (!file || capacity < 0)
+        return -1;
+    solr::GPUKernel *kernel = SingletonKernel::kernel();
+    kernel->setSceneInfo(gSceneInfoStub);
+    kernel->setPostProcessingInfo(gPostProcessingInfoStub);
+    std::vector<unsigned char> bytes;
+    if (!kernel->renderJpeg(static_cast<float>(timer), jpegQuality, lumaH, lumaV, bytes))
+        return -1;
+    return jpegFileOut(bytes, file, capacity, nbBytes);
+}
+
+/* Extensions for the tests of csrc/jpeg_entropy.h: its granularities {blocks per workgroup, bytes per stuffing chunk};
+ * its prefix sum (n lengths to n + 1 offsets of 64 bits); the bits one block takes after a predecessor's DC (-1 when
+ * the block is outside the domain) */
+void SolRx_JpegEntropyGranularity(int out[2])
+{
+    out[0] = jpn::BLOCKS_PER_GROUP;
+    out[1] = jpn::STUFF_CHUNK_BYTES;
+}
+
+void SolRx_JpegEntropyPrefix(const unsigned int *lengths, long n, unsigned long long *offsets)
+{
+    jpn::exclusiveSum(lengths, n, offsets);
+}
+
+int SolRx_JpegBlockBits(const short *block, int previousDc, int chroma)
+{
+    jpn::u32 bits = 0;
+    return jpn::blockBits(block, previousDc, chroma != 0, &bits) ? (int)bits : -1;
 }
 
 int SolRx_JpegQuantise(int q, int first, int count, int negative, short *out)

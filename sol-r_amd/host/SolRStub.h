@@ -151,6 +151,20 @@ int SolRx_JpegCoefficients(const unsigned char *pixels, int width, int height, i
 int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, long nbBlocks, int width, int height,
                                int jpegQuality, int lumaH, int lumaV);
 int SolRx_JpegQuantise(int q, int first, int count, int negative, short *out);
+/* one frame as SolR_RunKernel renders it, as a JPEG file in the caller's `file` of `capacity` bytes (*nbBytes its size):
+ * JPEG quality 1..100, luma sampling 1x1, 2x1 or 2x2, read as a screenshot reads a frame.  With the HIP engine the frame
+ * is coded on the device and only the file's bytes come to the host; SolRx_GetBitmap() is not refreshed.  0; -1 for
+ * arguments out of range, a failed frame (*nbBytes = 0), or a file that does not fit (*nbBytes = what it takes) */
+int SolRx_RenderJpeg(double timer, int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                     long *nbBytes);
+/* the file of SolRx_JpegFromCoefficients in memory, its entropy-coded segment by the engine's entropy stage
+ * (csrc/jpeg_entropy.h: kernels with the HIP engine, loops without a device); same returns */
+int SolRx_JpegFileFromCoefficients(const short *coefficients, long nbBlocks, int width, int height, int jpegQuality,
+                                   int lumaH, int lumaV, unsigned char *file, long capacity, long *nbBytes);
+/* csrc/jpeg_entropy.h for the tests (SolRStub.cpp) */
+void SolRx_JpegEntropyGranularity(int out[2]);
+void SolRx_JpegEntropyPrefix(const unsigned int *lengths, long n, unsigned long long *offsets);
+int SolRx_JpegBlockBits(const short *block, int previousDc, int chroma);
 /* GPUKernel::resetFrame: the current frame's primitives, boxes and lamps dropped, materials and textures kept - what a
  * scene that makes its geometry anew every frame begins a frame with */
 int SolRx_ResetFrame();
