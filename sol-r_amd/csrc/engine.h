@@ -8,8 +8,9 @@
  * launch), solr_diag.hip (knobs and diagnostics), solr_image_ring.hip (the pipelined read-back), solr_rccl.hip (strips,
  * communicator, gather, halo) and solr_post.hip (the post-processing kernels) share.
  * One Engine per device this process renders on; `g` is the engine a function works on.  The records an Engine is made of:
- * NodeList (a node list of the resident scene), Scene with Arena, OrderFreeState, Rotation and Morph, Lights, Materials, Textures,
- * Randoms and SceneFacts (the resident scene, cut by who writes them), KernelTimer, WalkRecording, TileSchedule (the
+ * NodeList (a node list of the resident scene), Scene with Arena, OrderFreeState, Refit and Morph, Lights, Materials, Textures,
+ * Randoms and SceneFacts (the resident scene, cut by who writes them; what a request on it changes: RequestKind and
+ * Scene::requestServed, how many an engine has served: Engine::served), KernelTimer, WalkRecording, TileSchedule (the
  * cost-ordered launch), Flight (a frame in flight: its stream and per-pixel buffers; Engine::flight[0] is the one of a
  * process that renders one frame at a time), CopyLane (the device's part of the pipelined read-back) and ImageStreaming (a
  * frame read back in bands); ImageRing - the page-locked host images of the pipelined read-back and their tickets - exists
@@ -23,6 +24,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -372,7 +374,7 @@ struct NodeList
     unsigned offStart = 0;             /* ints of the arena: start indices */
     int ordered = 0;                /* sign-free slab test allowed on it */
     bool tight = false;             /* the thin copy behind it is up to date */
-    std::vector<int> refitLevels;   /* [offset, count] per height, offsets into Rotation::refitPlan (ints) */
+    std::vector<int> refitLevels;   /* [offset, count] per height, offsets into Refit::refitPlan (ints) */
 
     void reset() { *this = NodeList(copies, lists); }
     unsigned nodes() const { return (unsigned)lists * (unsigned)nb; }
@@ -405,7 +407,7 @@ struct NodeList
 
 /* The arena of the geometry (scene_layout.h) against its host images.  Written by flushGeometry / appendFreeLists; told
  * that it is out of date by whoever changes a host image (retagPrimitives, h2d_lightInformation).  Part of Scene: no
- * transition moves its flags without moving the lists' or the rotation's. */
+ * transition moves its flags without moving the lists' or the refit's. */
 struct Arena
 {
     DeviceBuffer geometry;
@@ -443,31 +445,50 @@ struct OrderFreeState
         }
     }
 };
-/* Rotation on the device (solr_hip_rotate_primitives): what to refit, in which order.  Written by solr_hip_set_movable,
- * buildRefitPlan and the transitions of Scene. */
-struct Rotation
+/* The refit of the node lists behind primitives that moved on the device (refitMovedScene, solr_rotation.hip): which
+ * primitives move, what to refit, in which order.  Written by solr_hip_set_movable, buildRefitPlan and the transitions of
+ * Scene. */
+struct Refit
 {
     DeviceBuffer movable, refitPlan;
     DeviceBuffer enclosesFlag;     /* k_listEncloses' answer */
     int nbMovable = -1;            /* flags uploaded for that many primitives, -1: none */
     bool refitReady = false;       /* refitPlan is the plan of the lists as they are (buildRefitPlan) */
-    bool refitPlanPending = false; /* the lists changed: the plan is made when the first rotation asks (canRotateOne) */
-    bool exactStale = false;       /* the exact list has not been refitted since the last rotation */
+    bool refitPlanPending = false; /* the lists changed: the plan is made when the first request asks (canRefitOne) */
+    bool exactStale = false;       /* the exact list has not been refitted since the last move */
     float exactStaleViewDistance = 0.f;
-    int nbDeviceRotations = 0;
-    /* the other rigid moves (solr_moves.hip): translations run the rotation's refit, a lamp move refits nothing */
-    int nbDeviceTranslations = 0;
-    int nbDeviceLampMoves = 0;
-    bool lampMoved = false; /* a lamp was moved on the device since h2d_scene: a morph there would leave its light record behind */
-    /* primitives set anew (solr_edits.hip): the batch's planes as uploaded last; an edit runs the rotation's refit */
-    DeviceBuffer edits;
-    int nbDeviceEdits = 0;
-    bool edited = false; /* ... since h2d_scene: a morph there would leave the edit's texture coordinates behind */
-    /* materials set (solr_materials.hip): the batch as uploaded last; nothing is refitted */
-    DeviceBuffer materialSets;
-    int nbDeviceMaterialSets = 0;
-    bool materialsSet = false; /* ... since h2d_scene: a morph there would keep them, where the host's takes its first key's */
 };
+/* The requests a host makes on the resident scene in place of a new upload, and what each of them does to the scene's
+ * record when it has been served (Scene::requestServed reads the table; the engine counts them: Engine::served).
+ * movesBounds: primitives moved and refitMovedScene refitted the lists - the walk-order list was checked again and the arena
+ * is ahead of the host images.  barsMorph: a morph on that scene would undo part of it, and is declined until the next
+ * h2d_scene - a moved lamp's p0 would go back to the keys' place and leave its light record behind (the host route makes
+ * the record from p0 again), set primitives would lose their texture coordinates and movable flags, set materials would
+ * stay where the host's morph takes its first key's.  A lamp move and a batch of materials are written to the arena and
+ * the host images alike: nothing is ahead of anything by them. */
+enum RequestKind
+{
+    REQUEST_ROTATION = 0,
+    REQUEST_TRANSLATION,
+    REQUEST_LAMP_MOVE,
+    REQUEST_EDIT,          /* primitives set anew (solr_edits.hip) */
+    REQUEST_MATERIAL_SETS, /* primitives' materials set (solr_materials.hip) */
+    REQUEST_MORPH,         /* through the two-key interface */
+    REQUEST_TRACK_MORPH,   /* between two slots of a track */
+    REQUEST_KINDS
+};
+struct RequestFacts
+{
+    bool movesBounds, barsMorph;
+};
+constexpr RequestFacts REQUEST_FACTS[REQUEST_KINDS] = {
+    {true, false},  /* rotation */
+    {true, false},  /* translation */
+    {false, true},  /* lamp move */
+    {true, true},   /* edit */
+    {false, true},  /* material sets */
+    {true, false},  /* morph */
+    {true, false}}; /* track morph */
 /* Key-frame morphing on the device (solr_morph.hip): the key frames of the resident scene the engine holds, one per slot -
  * the slots of a track (solr_hip_set_morph_track_key, solr_hip_morph_between), then the two of the two-key interface
  * (solr_hip_set_morph_keys, solr_hip_morph_primitives).  Written by the transitions of Scene only; an h2d_scene drops the keys. */
@@ -495,8 +516,6 @@ struct Morph
     std::vector<MorphLampAnswer> lampAnswers; /* as asked since the slots last changed, by the tags of ... */
     long lampChecked = -1;                    /* ... that Scene::retags */
     DeviceBuffer lampFlag;                    /* k_lampKeysDiffer's answer */
-    int nbDeviceMorphs = 0;                   /* requests served: through the two-key interface / for a track */
-    int nbDeviceTrackMorphs = 0;
 };
 /* The scene proper: what h2d_scene replaces and finalize_scene drops, with the arena it is resident in. */
 struct Scene
@@ -514,39 +533,20 @@ struct Scene
      * (checked at h2d_scene and again after every rotation on the device; lampCutoffUsable, tightListsFor) */
     bool walkEncloses = false;
     OrderFreeState lists;
-    Rotation rotation;
+    Refit refit;
     Morph morph;
+    unsigned morphBarredBy = 0; /* the kinds (1 << RequestKind) served since h2d_scene that bar a morph (REQUEST_FACTS) */
+    /* the batches as uploaded last: of primitives set anew (solr_edits.hip: its planes), of materials set (solr_materials.hip) */
+    DeviceBuffer editBatch, materialSetBatch;
     long retags = 0; /* how often retagPrimitives has run: what was derived from the tags is as old as that */
     Arena arena;
 
-    /* the requests served since initialize_scene (solr_hip_device_rotations and its siblings): they count for the engine,
-     * not for the scene that happens to be resident, and are carried from record to record when scenes change places
-     * (ParkedScene) */
-    struct Served
-    {
-        int rotations, translations, lampMoves, edits, materialSets, morphs, trackMorphs;
-    };
-    Served served() const
-    {
-        return {rotation.nbDeviceRotations, rotation.nbDeviceTranslations, rotation.nbDeviceLampMoves, rotation.nbDeviceEdits,
-                rotation.nbDeviceMaterialSets, morph.nbDeviceMorphs, morph.nbDeviceTrackMorphs};
-    }
-    void servedCarried(const Served &s)
-    {
-        rotation.nbDeviceRotations = s.rotations;
-        rotation.nbDeviceTranslations = s.translations;
-        rotation.nbDeviceLampMoves = s.lampMoves;
-        rotation.nbDeviceEdits = s.edits;
-        rotation.nbDeviceMaterialSets = s.materialSets;
-        morph.nbDeviceMorphs = s.morphs;
-        morph.nbDeviceTrackMorphs = s.trackMorphs;
-    }
     /* every byte of device memory the record owns (the staged order-free lists by what the builder leaves per node:
      * lists_device.h) */
     size_t deviceBytes() const
     {
-        size_t bytes = arena.geometry.bytes + lamps.bytes + rotation.movable.bytes + rotation.refitPlan.bytes +
-                       rotation.enclosesFlag.bytes + rotation.edits.bytes + rotation.materialSets.bytes + morph.lampFlag.bytes;
+        size_t bytes = arena.geometry.bytes + lamps.bytes + refit.movable.bytes + refit.refitPlan.bytes +
+                       refit.enclosesFlag.bytes + editBatch.bytes + materialSetBatch.bytes + morph.lampFlag.bytes;
         for (const MorphKey &key : morph.keys)
             bytes += key.planes.bytes;
         const size_t nodes = orderFree.nodes();
@@ -556,19 +556,17 @@ struct Scene
     }
 
     /* h2d_scene has new host images of the lists and the primitives (swapped in by the caller): nothing that was made
-     * from the old ones holds.  The movable flags and the morph keys go, the counts of rotations and morphs stay; the
-     * arena follows with retagPrimitives (layOutAgain) */
+     * from the old ones holds.  The movable flags and the morph keys go, and nothing bars a morph any more; the arena
+     * follows with retagPrimitives (layOutAgain) */
     void newGeometry(int nested_, bool walkEncloses_, int freeCountdown_)
     {
         nested = nested_;
         walkEncloses = walkEncloses_;
-        rotation.refitReady = false;
-        rotation.exactStale = false;
-        rotation.refitPlanPending = true;
-        rotation.nbMovable = -1;
-        rotation.lampMoved = false;
-        rotation.edited = false;
-        rotation.materialsSet = false;
+        refit.refitReady = false;
+        refit.exactStale = false;
+        refit.refitPlanPending = true;
+        refit.nbMovable = -1;
+        morphBarredBy = 0;
         morphKeysDropped();
         arena.deviceAhead = false;
         orderFree.reset();
@@ -597,8 +595,8 @@ struct Scene
         orderFree = built;
         lists.freeHostValid = !stayed;
         lists.freeStale = false;
-        rotation.refitReady = false;
-        rotation.refitPlanPending = true; /* 8-12 ms for 100 k primitives: only scenes that are rotated on the device pay them */
+        refit.refitReady = false;
+        refit.refitPlanPending = true; /* 8-12 ms for 100 k primitives: only scenes that are rotated on the device pay them */
         if (stayed && fromArena)
             lists.freeDirty = true;
         else
@@ -623,68 +621,32 @@ struct Scene
         lists.dropStage(true);
     }
     void hostImagesPulled() { arena.deviceAhead = false; }
-    /* refitMovedScene - behind a rotation or a morph - has queued the refit of the walk-order list (listsFollow: of the order-free
-     * lists too; without a plan for them, moved scenes walk the reference's order until the next upload); the
-     * reference's own list follows when somebody needs it (refreshExactList) */
-    void rotationQueued(bool listsFollow, float viewDistance)
+    /* refitMovedScene - behind a request that moves primitives - has queued the refit of the walk-order list (listsFollow:
+     * of the order-free lists too; without a plan for them, moved scenes walk the reference's order until the next upload);
+     * the reference's own list follows when somebody needs it (refreshExactList) */
+    void refitQueued(bool listsFollow, float viewDistance)
     {
         if (!listsFollow)
             lists.freeStale = orderFree.nb > 0;
-        rotation.exactStale = true;
-        rotation.exactStaleViewDistance = viewDistance;
+        refit.exactStale = true;
+        refit.exactStaleViewDistance = viewDistance;
     }
-    void exactRefitted() { rotation.exactStale = false; }
-    /* ... and has served it; walkHolds: the refitted walk-order list passed the check again, landed: without an error */
-    void rotationServed(bool walkHolds, bool landed)
+    void exactRefitted() { refit.exactStale = false; }
+    /* a ...One (solr_rotation.hip, solr_moves.hip, solr_edits.hip, solr_materials.hip, solr_morph.hip) has served a request
+     * of that kind.  walkHolds - asked of a kind that moves bounds only -: the refitted walk-order list passed the check
+     * again, and that is taken whether or not the request landed; landed: without an error.  The engine counts it
+     * (finishRequest).  A batch of materials also retags: whoever derived something from the tags hears through retagged() */
+    void requestServed(RequestKind kind, bool walkHolds, bool landed)
     {
-        walkEncloses = walkHolds;
-        if (landed)
-        {
+        const RequestFacts &facts = REQUEST_FACTS[kind];
+        if (facts.movesBounds)
+            walkEncloses = walkHolds;
+        if (!landed)
+            return;
+        if (facts.movesBounds)
             arena.deviceAhead = true;
-            ++rotation.nbDeviceRotations;
-        }
-    }
-    /* translatePrimitivesOne has moved the primitives and refitted the lists (rotationQueued); as for a rotation */
-    void translationServed(bool walkHolds, bool landed)
-    {
-        walkEncloses = walkHolds;
-        if (landed)
-        {
-            arena.deviceAhead = true;
-            ++rotation.nbDeviceTranslations;
-        }
-    }
-    /* moveLampOne has set a lamp's p0 and its light record, in the arena and in the host images alike (nothing is ahead
-     * of anything by it) */
-    void lampMoveServed(bool landed)
-    {
-        if (landed)
-        {
-            rotation.lampMoved = true;
-            ++rotation.nbDeviceLampMoves;
-        }
-    }
-    /* setPrimitivesOne has set the batch's primitives anew and refitted the lists (rotationQueued); as for a morph */
-    void editServed(bool walkHolds, bool landed)
-    {
-        walkEncloses = walkHolds;
-        if (landed)
-        {
-            arena.deviceAhead = true;
-            rotation.edited = true;
-            ++rotation.nbDeviceEdits;
-        }
-    }
-    /* setPrimitiveMaterialsOne has set the batch's tags, material ids and colour keys, in the arena, in the leaf records and
-     * in the host image alike (nothing is ahead of anything by it, no bound moved); whoever derived something from the tags
-     * hears of it through retagged() */
-    void materialSetsServed(bool landed)
-    {
-        if (landed)
-        {
-            rotation.materialsSet = true;
-            ++rotation.nbDeviceMaterialSets;
-        }
+        if (facts.barsMorph)
+            morphBarredBy |= 1u << kind;
     }
     /* retagPrimitives has joined the materials' facts into the primitives' tags again (setPrimitiveMaterialsOne: into some) */
     void retagged() { ++retags; }
@@ -719,23 +681,12 @@ struct Scene
         morph.lampChecked = retags;
         morph.lampAnswers.push_back({slotA, slotB, moves});
     }
-    /* morphKeysOne has blended two keys into the primitives and refitted the lists (rotationQueued); walkHolds, landed: as
-     * for a rotation; track: asked through solr_hip_morph_between */
-    void morphServed(bool walkHolds, bool landed, bool track)
-    {
-        walkEncloses = walkHolds;
-        if (landed)
-        {
-            arena.deviceAhead = true;
-            ++(track ? morph.nbDeviceTrackMorphs : morph.nbDeviceMorphs);
-        }
-    }
     /* finalize_scene */
     void release()
     {
         lists.dropStage(true);
-        for (DeviceBuffer *b : {&arena.geometry, &lamps, &rotation.movable, &rotation.refitPlan, &rotation.enclosesFlag, &rotation.edits,
-                                &rotation.materialSets, &morph.lampFlag})
+        for (DeviceBuffer *b : {&arena.geometry, &lamps, &refit.movable, &refit.refitPlan, &refit.enclosesFlag, &editBatch,
+                                &materialSetBatch, &morph.lampFlag})
             solreng::release(*b);
         for (MorphKey &key : morph.keys)
             solreng::release(key.planes);
@@ -890,7 +841,8 @@ struct SceneFacts
 /* A resident scene set aside (solr_hip_park_scene, solr_bank.hip): the three records h2d_scene, h2d_lightInformation and
  * retagPrimitives write, moved - a DeviceBuffer is a plain pointer, the vectors move - with everything made from them or
  * applied to them since.  Nothing is copied, launched, freed or waited for: a frame in flight that still reads the arena
- * finishes, because the arena stays allocated.  The two transitions leave the counts of requests served with the engine. */
+ * finishes, because the arena stays allocated.  (The counts of requests served are the engine's - Engine::served - and no
+ * scene's: nothing of them moves.) */
 struct ParkedScene
 {
     int key = -1;
@@ -902,7 +854,6 @@ struct ParkedScene
     /* the resident records move in; the engine holds no scene, as after initialize_scene */
     void park(int key_, Scene &resident, Lights &residentLights, SceneFacts &residentFacts, long generation)
     {
-        const Scene::Served served = resident.served();
         key = key_;
         bytes = resident.deviceBytes();
         materialsGeneration = generation;
@@ -910,16 +861,13 @@ struct ParkedScene
         lights = std::move(residentLights);
         facts = residentFacts;
         resident = Scene();
-        resident.servedCarried(served);
         residentLights = Lights();
         residentFacts = SceneFacts();
     }
     /* ... and out again, over records that hold no buffer (the caller has released them) */
     void resume(Scene &resident, Lights &residentLights, SceneFacts &residentFacts)
     {
-        const Scene::Served served = resident.served();
         resident = std::move(scene);
-        resident.servedCarried(served);
         residentLights = std::move(lights);
         residentFacts = facts;
         scene = Scene();
@@ -1008,6 +956,10 @@ struct Engine
     Randoms randoms;
     SceneFacts facts;
     SceneBank bank; /* the scenes set aside (its limit is a knob) */
+    /* the requests on the resident scene this engine has served, per RequestKind (solr_hip_device_rotations and its
+     * siblings): counted by finishRequest, zeroed by finalize_scene and by nothing else - not by a second initialize_scene
+     * on an engine that is up, not by h2d_scene, not when scenes change places in the bank */
+    int served[REQUEST_KINDS] = {};
 
     DeviceBuffer counters, tileClock;
     /* ambient occlusion across strips: the depths of the neighbours' rows a host hands over itself (the ones traded over
@@ -1210,9 +1162,10 @@ bool shortRayListsChoice();
 SceneArgs prepareScene(const SceneInfo &sceneInfo, bool exactNodes);
 bool deepNodeList(const SceneArgs &S);
 /* solr_rotation.hip: rotation and refit on the device */
-/* (who: the entry point that asks - a morph and a translation ask what a rotation asks - for the error and debug texts) */
-bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance,
-                  const char *who = "solr_hip_rotate_primitives");
+/* (who: the entry point that asks - a rotation, a translation, an edit and a morph all move primitives - for the error and
+ * debug texts) */
+bool canRefitOne(float viewDistance, const char *who);
+bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
 int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance);
 bool refitMovedScene(float viewDistance);
 void refreshExactList();
@@ -1236,6 +1189,43 @@ int setPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n);
 /* ... and an edited table of materials followed in the table and on the resident scene */
 bool canEditMaterialsOne(const Material *materials, int nbActiveMaterials);
 int editMaterialsOne(const Material *materials, int nbActiveMaterials);
+/* ---- what every request on the resident scene shares.  A ...One runs: its can...One, beginRequest, its own work - the
+ * batch, the launch, refitMovedScene where primitives moved, the host images' follow-up - and finishRequest. */
+/* SOLR_HIP_DEBUG_TREE=1: why an entry point declined a request, on stderr */
+__attribute__((format(printf, 2, 3))) inline void noteRefusal(const char *who, const char *why, ...)
+{
+    if (!getenv("SOLR_HIP_DEBUG_TREE"))
+        return;
+    char text[256];
+    va_list args;
+    va_start(args, why);
+    vsnprintf(text, sizeof text, why, args);
+    va_end(args);
+    fprintf(stderr, "%s refused: %s\n", who, text);
+}
+/* the engine's device current, the arena up to date with the host images, no frame in flight that reads what is about to
+ * change.  False: an error is pending, nothing was changed.  (The pointer cannot be null behind a flush that left no
+ * error, whatever the scene: Arena::geometryDirty is true from the record's birth and false only after arenaFlushed,
+ * which follows a reserve of at least 16 bytes that succeeded, and only Scene::release - back to a new record, dirty -
+ * gives the arena back.  It is asked all the same: the launches below write through it.) */
+inline bool beginRequest()
+{
+    HIPCHECK(hipSetDevice(g.device));
+    flushGeometry();
+    if (!ok() || !g.scene.arena.geometry.ptr)
+        return false;
+    quiesce();
+    return true;
+}
+/* the scene's transition, the engine's count, and the status a ...One returns: 1 served, 0 an error is pending */
+inline int finishRequest(RequestKind kind, bool walkHolds = false)
+{
+    g.scene.requestServed(kind, walkHolds, ok());
+    if (!ok())
+        return 0;
+    ++g.served[kind];
+    return 1;
+}
 /* solr_bank.hip: resident scenes set aside and put back */
 void dropParkedOne(int key); /* (-1: all of them; waits for the frames in flight first, the only call of the bank that frees) */
 /* solr_launch.hip: a frame - buffers, the launch, post-processing, read-back */

@@ -467,16 +467,16 @@ bool listEnclosesInArena(const NodeList &list)
 {
     const int n = (int)list.nodes();
     HIPCHECK(hipSetDevice(g.device));
-    reserve(g.scene.rotation.enclosesFlag, sizeof(int));
+    reserve(g.scene.refit.enclosesFlag, sizeof(int));
     if (!ok())
         return false;
     int found = 1;
-    HIPCHECK(hipMemsetAsync(g.scene.rotation.enclosesFlag.ptr, 0, sizeof(int), sceneStream()));
+    HIPCHECK(hipMemsetAsync(g.scene.refit.enclosesFlag.ptr, 0, sizeof(int), sceneStream()));
     hipLaunchKernelGGL(k_listEncloses, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sceneStream(),
                        (const float4 *)g.scene.arena.geometry.ptr, list.offRows, list.offStart, g.scene.arena.offPrims, n,
-                       (int)(g.scene.hostPrims.size() / PRIM_ROWS), (int *)g.scene.rotation.enclosesFlag.ptr);
+                       (int)(g.scene.hostPrims.size() / PRIM_ROWS), (int *)g.scene.refit.enclosesFlag.ptr);
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(&found, g.scene.rotation.enclosesFlag.ptr, sizeof(int), hipMemcpyDeviceToHost, sceneStream()));
+    HIPCHECK(hipMemcpyAsync(&found, g.scene.refit.enclosesFlag.ptr, sizeof(int), hipMemcpyDeviceToHost, sceneStream()));
     HIPCHECK(hipStreamSynchronize(sceneStream()));
     return ok() && found == 0;
 }
@@ -535,7 +535,7 @@ void maybeBuildOrderFreeLists()
     const bool onHost = getenv("SOLR_HIP_LISTS_ON_HOST") != nullptr;
     /* with the arena laid out as the host images are (the usual case: the scene has been rendered once), the checks
      * and the builder read the exact list and the primitive records there */
-    const bool fromArena = !g.scene.arena.geometryDirty && g.scene.arena.geometry.ptr != nullptr && !g.scene.rotation.exactStale &&
+    const bool fromArena = !g.scene.arena.geometryDirty && g.scene.arena.geometry.ptr != nullptr && !g.scene.refit.exactStale &&
                            !g.scene.arena.deviceAhead && !onHost;
     const float4 *arena = (const float4 *)g.scene.arena.geometry.ptr;
     const bool encloses = fromArena ? listEnclosesInArena(g.scene.exact) : listEnclosesOnHost(rows, start, g.scene.hostPrims);

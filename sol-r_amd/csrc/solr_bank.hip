@@ -29,13 +29,11 @@ static bool sceneResident()
     return g.initialized && !g.scene.hostPrims.empty() && g.scene.exact.nb + g.scene.nbPrimitives > 0;
 }
 
-/* the resident scene's buffers given back as finalize_scene gives them back; the counts of requests served stay */
+/* the resident scene's buffers given back as finalize_scene gives them back */
 static void dropResident()
 {
-    const Scene::Served served = g.scene.served();
     quiesce();
     g.scene.release();
-    g.scene.servedCarried(served);
     g.lights = Lights();
     g.facts = SceneFacts();
 }

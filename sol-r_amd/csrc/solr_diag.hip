@@ -557,7 +557,7 @@ int solr_hip_get_variant(void)
 
 void solr_hip_memory_usage(unsigned long long bytes[4])
 {
-    bytes[0] = g.scene.arena.geometry.bytes + g.scene.lamps.bytes + g.scene.rotation.movable.bytes + g.scene.rotation.refitPlan.bytes;
+    bytes[0] = g.scene.arena.geometry.bytes + g.scene.lamps.bytes + g.scene.refit.movable.bytes + g.scene.refit.refitPlan.bytes;
     bytes[1] = g.materials.table.bytes;
     bytes[2] = g.textures.atlas.bytes;
     bytes[3] = g.randoms.values.bytes;

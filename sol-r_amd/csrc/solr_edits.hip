@@ -1,8 +1,8 @@
 /*
  * solr_edits.hip - primitives set anew on the resident scene of the MI355X rendering engine: solr_hip_set_primitives takes a
  * batch of edited primitives, derives what GPUKernel::setPrimitive derives per type, scatters them into the arena and refits
- * the node lists (engine.h Rotation: the batch's buffer, the counter, edited; the refit and what follows it: solr_rotation.hip
- * refitMovedScene).
+ * the node lists (engine.h Scene::editBatch: the batch's buffer, RequestKind and Scene::requestServed: what a served batch
+ * changes in the scene's record, Engine::served: the counter; the refit and what follows it: solr_rotation.hip refitMovedScene).
  * Part of the engine's host side (engine.h); the boundary that calls into it is solr_hip.hip.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
@@ -202,12 +202,11 @@ static bool finite2(const vec2f &v)
     return std::isfinite(v.x) && std::isfinite(v.y);
 }
 
-/* can this engine set these primitives of its resident scene?  (what canRotateOne asks, and every record against the resident
+/* can this engine set these primitives of its resident scene?  (canRefitOne, and every record against the resident
  * primitive it names; changes nothing but the refit plan) */
 bool canSetPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance)
 {
-    static const float none[3] = {0.f, 0.f, 0.f};
-    if (!canRotateOne(none, none, none, viewDistance, "solr_hip_set_primitives"))
+    if (!canRefitOne(viewDistance, "solr_hip_set_primitives"))
         return false;
     const Scene &s = g.scene;
     const char *why = nullptr;
@@ -244,8 +243,8 @@ bool canSetPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n
                 why = "a float that is not finite";
         }
     }
-    if (why && getenv("SOLR_HIP_DEBUG_TREE"))
-        fprintf(stderr, "solr_hip_set_primitives refused: %s (record %d of %d)\n", why, at, n);
+    if (why)
+        noteRefusal("solr_hip_set_primitives", "%s (record %d of %d)", why, at, n);
     return why == nullptr;
 }
 
@@ -254,13 +253,8 @@ bool canSetPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n
  * route (nothing was changed). */
 int setPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance)
 {
-    if (!canSetPrimitivesOne(edits, slots, n, viewDistance))
-        return 0;
-    HIPCHECK(hipSetDevice(g.device));
-    flushGeometry();
-    if (!ok() || !g.scene.arena.geometry.ptr || !g.scene.rotation.movable.ptr)
-        return 0;
-    quiesce();
+    if (!canSetPrimitivesOne(edits, slots, n, viewDistance) || !beginRequest() || !g.scene.refit.movable.ptr)
+        return 0; /* (the kernel writes the flags too) */
     const size_t plane = (size_t)n;
     /* (float4 planes first, so that the plane of floats behind them needs no padding) */
     std::vector<float> batch((size_t)EDIT_PLANES * 4 * plane + plane);
@@ -278,15 +272,13 @@ int setPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, fl
         planes[EDIT_N2_VT2X * plane + i] = make_float4(e.n2.x, e.n2.y, e.n2.z, e.vt2.x);
         last[i] = e.vt2.y;
     }
-    upload(g.scene.rotation.edits, batch);
+    upload(g.scene.editBatch, batch);
     if (!ok())
         return 0;
     hipLaunchKernelGGL(k_setPrimitives, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
-                       (unsigned char *)g.scene.rotation.movable.ptr, (const float4 *)g.scene.rotation.edits.ptr, n);
-    const bool walkHolds = refitMovedScene(viewDistance);
-    g.scene.editServed(walkHolds, ok());
-    return ok() ? 1 : 0;
+                       (unsigned char *)g.scene.refit.movable.ptr, (const float4 *)g.scene.editBatch.ptr, n);
+    return finishRequest(REQUEST_EDIT, refitMovedScene(viewDistance));
 }
 
 } // namespace solreng
@@ -294,6 +286,6 @@ int setPrimitivesOne(const SolrPrimitiveEdit *edits, const int *slots, int n, fl
 extern "C" {
 int solr_hip_device_edits(void)
 {
-    return g.scene.rotation.nbDeviceEdits;
+    return g.served[REQUEST_EDIT];
 }
 } // extern "C"

@@ -286,6 +286,8 @@ static void finalizeOne()
         pool.release();
     }
     g.scene.release();
+    for (int &count : g.served)
+        count = 0;
     g.materials.release();
     g.textures.release();
     g.randoms.release();
@@ -401,6 +403,29 @@ bool sameOccupancy(const vec2i &occ, const char *who)
                         "serve this and every later call (noted once)\n", who, occ.x, gRequested, gDevices);
     noted = true;
     return true;
+}
+
+/* A request on the resident scene (rotation, morph, translation, lamp move, primitives, their materials, an edited table of
+ * materials).  Every in-process device holds the scene and changes its own copy, and every copy must be able to follow
+ * before any of them changes: "0: nothing was changed" then holds on several devices as well (one engine
+ * declining used to leave the others rotated).  So every engine is asked first - all of them, whatever the ones before
+ * said: canRefitOne makes the refit plan as it answers - and one refusal declines the request for all.  Then every engine
+ * serves.  Returns 1 when all of them did, else the first status that is not 1 (a device error past the check: the
+ * engine's error state says which). */
+template <class Can, class Serve>
+int askThenServe(Can &&can, Serve &&serve)
+{
+    bool all = true;
+    onEveryDevice([&](int) { all = can() && all; });
+    if (!all)
+        return 0;
+    int status = 1;
+    onEveryDevice([&](int) {
+        const int mine = serve();
+        if (mine != 1 && status == 1)
+            status = mine;
+    });
+    return status;
 }
 } // namespace
 
@@ -595,22 +620,11 @@ void solr_hip_set_movable(const unsigned char *flags, int nbPrimitives)
     onEveryDevice([&](int) { setMovableOne(flags, nbPrimitives); });
 }
 
-/* (every in-process device holds the scene and rotates its own copy; 1 only when all of them did) */
+/* the requests on the resident scene (askThenServe) */
 int solr_hip_rotate_primitives(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance)
 {
-    /* every resident copy must be able to follow before any of them moves: "0: nothing was changed" then holds on
-     * several devices as well (one engine declining used to leave the others rotated) */
-    bool all = true;
-    onEveryDevice([&](int) { all = canRotateOne(center, cosAngles, sinAngles, viewDistance) && all; });
-    if (!all)
-        return 0;
-    int status = 1; /* 1: rotated on the device */
-    onEveryDevice([&](int) {
-        const int mine = rotatePrimitivesOne(center, cosAngles, sinAngles, viewDistance);
-        if (mine != 1 && status == 1)
-            status = mine; /* (a device error past the check: the engine's error state says which) */
-    });
-    return status;
+    return askThenServe([&] { return canRotateOne(center, cosAngles, sinAngles, viewDistance); },
+                        [&] { return rotatePrimitivesOne(center, cosAngles, sinAngles, viewDistance); });
 }
 
 int solr_hip_set_morph_keys(const Primitive *first, const Primitive *last, int nbPrimitives)
@@ -628,114 +642,49 @@ int solr_hip_set_morph_track_key(int slot, const Primitive *key, const int *rank
     return status;
 }
 
-/* (every in-process device holds the scene and the keys and morphs its own copy; 1 only when all of them did) */
-static int morphOnEveryDevice(int slotA, int slotB, float weight, float viewDistance, const char *who)
-{
-    /* as for a rotation: every resident copy must be able to follow before any of them moves */
-    bool all = true;
-    onEveryDevice([&](int) { all = canMorphOne(slotA, slotB, weight, viewDistance, who) && all; });
-    if (!all)
-        return 0;
-    int status = 1; /* 1: morphed on the device */
-    onEveryDevice([&](int) {
-        const int mine = morphKeysOne(slotA, slotB, weight, viewDistance, who);
-        if (mine != 1 && status == 1)
-            status = mine;
-    });
-    return status;
-}
-
 int solr_hip_morph_primitives(float weight, float viewDistance)
 {
-    return morphOnEveryDevice(MORPH_SLOT_FIRST, MORPH_SLOT_LAST, weight, viewDistance, "solr_hip_morph_primitives");
+    const char *const who = "solr_hip_morph_primitives";
+    return askThenServe([&] { return canMorphOne(MORPH_SLOT_FIRST, MORPH_SLOT_LAST, weight, viewDistance, who); },
+                        [&] { return morphKeysOne(MORPH_SLOT_FIRST, MORPH_SLOT_LAST, weight, viewDistance, who); });
 }
 
 int solr_hip_morph_between(int slotA, int slotB, float weight, float viewDistance)
 {
     if (slotA < 0 || slotA >= SOLR_MORPH_TRACK_MAX_KEYS || slotB < 0 || slotB >= SOLR_MORPH_TRACK_MAX_KEYS)
         return 0;
-    return morphOnEveryDevice(slotA, slotB, weight, viewDistance, "solr_hip_morph_between");
+    const char *const who = "solr_hip_morph_between";
+    return askThenServe([&] { return canMorphOne(slotA, slotB, weight, viewDistance, who); },
+                        [&] { return morphKeysOne(slotA, slotB, weight, viewDistance, who); });
 }
 
-/* (every in-process device holds the scene and translates its own copy; 1 only when all of them did) */
 int solr_hip_translate_primitives(const float translation[3], float viewDistance)
 {
-    /* as for a rotation: every resident copy must be able to follow before any of them moves */
-    bool all = true;
-    onEveryDevice([&](int) { all = canTranslateOne(translation, viewDistance) && all; });
-    if (!all)
-        return 0;
-    int status = 1; /* 1: translated on the device */
-    onEveryDevice([&](int) {
-        const int mine = translatePrimitivesOne(translation, viewDistance);
-        if (mine != 1 && status == 1)
-            status = mine;
-    });
-    return status;
+    return askThenServe([&] { return canTranslateOne(translation, viewDistance); },
+                        [&] { return translatePrimitivesOne(translation, viewDistance); });
 }
 
-/* (... and every one of them moves the lamp of its own copy) */
 int solr_hip_move_lamp(int lamp, const float center[3])
 {
-    bool all = true;
-    onEveryDevice([&](int) { all = canMoveLampOne(lamp, center) && all; });
-    if (!all)
-        return 0;
-    int status = 1; /* 1: moved on the device */
-    onEveryDevice([&](int) {
-        const int mine = moveLampOne(lamp, center);
-        if (mine != 1 && status == 1)
-            status = mine;
-    });
-    return status;
+    return askThenServe([&] { return canMoveLampOne(lamp, center); }, [&] { return moveLampOne(lamp, center); });
 }
 
-/* (... and every one of them sets the batch's primitives of its own copy; 1 only when all of them did) */
 int solr_hip_set_primitives(const SolrPrimitiveEdit *edits, const int *slots, int n, float viewDistance)
 {
-    /* as for a rotation: every resident copy must be able to follow before any of them changes */
-    bool all = true;
-    onEveryDevice([&](int) { all = canSetPrimitivesOne(edits, slots, n, viewDistance) && all; });
-    if (!all)
-        return 0;
-    int status = 1; /* 1: set on the device */
-    onEveryDevice([&](int) {
-        const int mine = setPrimitivesOne(edits, slots, n, viewDistance);
-        if (mine != 1 && status == 1)
-            status = mine;
-    });
-    return status;
+    return askThenServe([&] { return canSetPrimitivesOne(edits, slots, n, viewDistance); },
+                        [&] { return setPrimitivesOne(edits, slots, n, viewDistance); });
 }
 
-/* (... and every one of them sets the batch's materials in its own copy; 1 only when all of them did) */
 int solr_hip_set_primitive_materials(const int *slots, const int *materialIds, int n)
 {
-    bool all = true;
-    onEveryDevice([&](int) { all = canSetPrimitiveMaterialsOne(slots, materialIds, n) && all; });
-    if (!all)
-        return 0;
-    int status = 1; /* 1: set on the device */
-    onEveryDevice([&](int) {
-        const int mine = setPrimitiveMaterialsOne(slots, materialIds, n);
-        if (mine != 1 && status == 1)
-            status = mine;
-    });
-    return status;
+    return askThenServe([&] { return canSetPrimitiveMaterialsOne(slots, materialIds, n); },
+                        [&] { return setPrimitiveMaterialsOne(slots, materialIds, n); });
 }
 
-/* (... and every one of them follows the edit in its own table and its own copy; 1 only when all of them did) */
+/* (every engine follows the edit in its own table as well as in its own copy of the scene) */
 int solr_hip_edit_materials(Material *materials, int nbActiveMaterials)
 {
-    bool all = true;
-    onEveryDevice([&](int) { all = canEditMaterialsOne(materials, nbActiveMaterials) && all; });
-    if (!all)
-        return 0;
-    int status = 1; /* 1: edited on the device */
-    onEveryDevice([&](int) {
-        const int mine = editMaterialsOne(materials, nbActiveMaterials);
-        if (mine != 1 && status == 1)
-            status = mine;
-    });
-    return status;
+    return askThenServe([&] { return canEditMaterialsOne(materials, nbActiveMaterials); },
+                        [&] { return editMaterialsOne(materials, nbActiveMaterials); });
 }
 }

@@ -2,7 +2,8 @@
  * solr_materials.hip - primitives' materials set on the resident scene of the MI355X rendering engine:
  * solr_hip_set_primitive_materials takes a batch of (slot, material id), joins the materials' facts into the tags of those
  * primitives as retagPrimitives does for all of them at an upload, and sets tag, material id and colour key in the arena, in
- * the leaf records and in the host image (engine.h Rotation: the batch's buffer, the counter, materialsSet; SceneFacts: the
+ * the leaf records and in the host image (engine.h Scene::materialSetBatch: the batch's buffer, RequestKind and
+ * Scene::requestServed: what a served batch changes in the scene's record, Engine::served: the counter; SceneFacts: the
  * counts the scene's facts follow by).  Nothing is pulled, laid out, uploaded or refitted.
  * And the other direction of that join: solr_hip_edit_materials takes a table of which some materials were given other
  * values, overwrites their records in the device table and rewrites tag and colour key of every primitive that has one of
@@ -91,6 +92,18 @@ __global__ __launch_bounds__(256) void k_followLeafRecords(float4 *__restrict__ 
         t -= L.nodes;
     }
 }
+/* ... queued on the scene stream, behind the kernel that changed the primitives' words */
+static void followLeafRecords()
+{
+    LeafMaterialsFollow M;
+    const int nodes = leafRecordsOfLists(g.scene, M.list);
+    M.offPrims = g.scene.arena.offPrims;
+    M.nbPrimitives = g.scene.nbPrimitives;
+    if (nodes > 0)
+        hipLaunchKernelGGL(k_followLeafRecords, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, sceneStream(),
+                           (float4 *)g.scene.arena.geometry.ptr, M);
+    HIPCHECK(hipGetLastError());
+}
 
 /* the facts and the colour key of an uploaded material, as retagPrimitives takes them */
 static int factsOfMaterial(int materialId)
@@ -162,8 +175,8 @@ bool canSetPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n
         if (after.primsContained != g.facts.primsContained)
             why = "a batch after which the primitives lie inside their leaves where they did not, or the other way round";
     }
-    if (why && getenv("SOLR_HIP_DEBUG_TREE"))
-        fprintf(stderr, "solr_hip_set_primitive_materials refused: %s (record %d of %d)\n", why, at, n);
+    if (why)
+        noteRefusal("solr_hip_set_primitive_materials", "%s (record %d of %d)", why, at, n);
     return why == nullptr;
 }
 
@@ -172,33 +185,22 @@ bool canSetPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n
  * served here and the caller has to take the host route (nothing was changed). */
 int setPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n)
 {
-    if (!canSetPrimitiveMaterialsOne(slots, materialIds, n))
+    /* (no frame in flight reads a tag that says one material next to the id of another) */
+    if (!canSetPrimitiveMaterialsOne(slots, materialIds, n) || !beginRequest())
         return 0;
-    HIPCHECK(hipSetDevice(g.device));
-    flushGeometry();
-    if (!ok() || !g.scene.arena.geometry.ptr)
-        return 0;
-    quiesce(); /* no frame in flight reads a tag that says one material next to the id of another */
     const bool general = noKinds();
     std::vector<int4> batch((size_t)n);
     for (int i = 0; i < n; ++i)
         batch[(size_t)i] = make_int4(slots[i], materialIds[i], factsOfMaterial(materialIds[i]), bitsi(colourKeyOfMaterial(materialIds[i])));
-    reserve(g.scene.rotation.materialSets, batch.size() * sizeof(int4));
+    reserve(g.scene.materialSetBatch, batch.size() * sizeof(int4));
     if (!ok())
         return 0;
     /* (a pageable source: `batch` lives until the one synchronisation below) */
-    HIPCHECK(hipMemcpyAsync(g.scene.rotation.materialSets.ptr, batch.data(), batch.size() * sizeof(int4), hipMemcpyHostToDevice, sceneStream()));
+    HIPCHECK(hipMemcpyAsync(g.scene.materialSetBatch.ptr, batch.data(), batch.size() * sizeof(int4), hipMemcpyHostToDevice, sceneStream()));
     hipLaunchKernelGGL(k_setPrimitiveMaterials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
-                       (const int4 *)g.scene.rotation.materialSets.ptr, n, general ? 1 : 0);
-    LeafMaterialsFollow M;
-    const int nodes = leafRecordsOfLists(g.scene, M.list);
-    M.offPrims = g.scene.arena.offPrims;
-    M.nbPrimitives = g.scene.nbPrimitives;
-    if (nodes > 0)
-        hipLaunchKernelGGL(k_followLeafRecords, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, sceneStream(),
-                           (float4 *)g.scene.arena.geometry.ptr, M);
-    HIPCHECK(hipGetLastError());
+                       (const int4 *)g.scene.materialSetBatch.ptr, n, general ? 1 : 0);
+    followLeafRecords();
     HIPCHECK(hipStreamSynchronize(sceneStream()));
     if (ok())
     {
@@ -216,8 +218,7 @@ int setPrimitiveMaterialsOne(const int *slots, const int *materialIds, int n)
         g.facts.deriveFromCounts();
         g.scene.retagged(); /* (the morph's lamp answers were given for the tags as they were) */
     }
-    g.scene.materialSetsServed(ok());
-    return ok() ? 1 : 0;
+    return finishRequest(REQUEST_MATERIAL_SETS);
 }
 
 /* ---- a colour that pulses, glass that fades in, a wireframe toggled, a texture swapped -----------------------------------
@@ -384,8 +385,8 @@ bool canEditMaterialsOne(const Material *materials, int nbActiveMaterials)
 {
     MaterialEditPlan plan;
     const char *why = planMaterialEdit(materials, nbActiveMaterials, plan);
-    if (why && getenv("SOLR_HIP_DEBUG_TREE"))
-        fprintf(stderr, "solr_hip_edit_materials refused: %s (%d materials)\n", why, nbActiveMaterials);
+    if (why)
+        noteRefusal("solr_hip_edit_materials", "%s (%d materials)", why, nbActiveMaterials);
     return why == nullptr;
 }
 
@@ -406,13 +407,11 @@ int editMaterialsOne(const Material *materials, int nbActiveMaterials)
         ++M.nbDeviceEdits; /* the table holds it already */
         return 1;
     }
-    HIPCHECK(hipSetDevice(g.device));
-    /* (no layout is due - planMaterialEdit -: this takes order-free lists the builder has just left into the arena, where
-     * the next frame would, so that their leaf records follow with the others') */
-    flushGeometry();
-    if (!ok() || !g.scene.arena.geometry.ptr)
+    /* (no layout is due - planMaterialEdit -: the flush takes order-free lists the builder has just left into the arena,
+     * where the next frame would, so that their leaf records follow with the others'; no frame in flight reads a record next
+     * to a tag of the material as it was) */
+    if (!beginRequest())
         return 0;
-    quiesce(); /* no frame in flight reads a record next to a tag of the material as it was */
     char *table = (char *)M.table.ptr;
     const size_t coldAt = (size_t)M.offMatCold * sizeof(float4);
     for (size_t a = 0, b; a < plan.ids.size(); a = b)
@@ -437,14 +436,7 @@ int editMaterialsOne(const Material *materials, int nbActiveMaterials)
             hipLaunchKernelGGL(k_retagMaterials, dim3((unsigned)((g.scene.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
                                (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
                                (const int4 *)M.editBatch.ptr, (int)plan.batch.size(), general ? 1 : 0);
-            LeafMaterialsFollow F;
-            const int nodes = leafRecordsOfLists(g.scene, F.list);
-            F.offPrims = g.scene.arena.offPrims;
-            F.nbPrimitives = g.scene.nbPrimitives;
-            if (nodes > 0)
-                hipLaunchKernelGGL(k_followLeafRecords, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, sceneStream(),
-                                   (float4 *)g.scene.arena.geometry.ptr, F);
-            HIPCHECK(hipGetLastError());
+            followLeafRecords();
         }
     }
     HIPCHECK(hipStreamSynchronize(sceneStream()));
@@ -507,7 +499,7 @@ int editMaterialsOne(const Material *materials, int nbActiveMaterials)
 extern "C" {
 int solr_hip_device_material_sets(void)
 {
-    return g.scene.rotation.nbDeviceMaterialSets;
+    return g.served[REQUEST_MATERIAL_SETS];
 }
 int solr_hip_device_material_edits(void)
 {

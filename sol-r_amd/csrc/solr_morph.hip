@@ -2,8 +2,9 @@
  * solr_morph.hip - key-frame morphing of the MI355X rendering engine: solr_hip_set_morph_track_key hands over one key frame
  * of the resident scene per slot (k_packMorphKeys packs it on the device), solr_hip_morph_between blends any two of them into
  * the resident primitives at any weight and refits the node lists in the arena; solr_hip_set_morph_keys and
- * solr_hip_morph_primitives are the same with two slots of their own (engine.h Morph; the refit and what follows it:
- * solr_rotation.hip refitMovedScene).
+ * solr_hip_morph_primitives are the same with two slots of their own (engine.h Morph: the keys, RequestKind and
+ * Scene::requestServed: what a served morph changes and which requests bar one, Engine::served: the counters; the refit and
+ * what follows it: solr_rotation.hip refitMovedScene).
  * Part of the engine's host side (engine.h); the boundary that calls into it is solr_hip.hip.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
@@ -299,29 +300,23 @@ static bool lampWouldMove(int slotA, int slotB)
     return differ != 0;
 }
 
-/* can this engine blend these two slots into its resident scene?  (what canRotateOne asks, and the keys; changes nothing
- * but the refit plan and what is known about lamps) */
+/* can this engine blend these two slots into its resident scene?  (canRefitOne, and the keys; changes nothing but the
+ * refit plan and what is known about lamps) */
 bool canMorphOne(int slotA, int slotB, float weight, float viewDistance, const char *who)
 {
-    static const float none[3] = {0.f, 0.f, 0.f};
-    if (!canRotateOne(none, none, none, viewDistance, who))
+    if (!canRefitOne(viewDistance, who))
         return false;
     if (slotA < 0 || slotA >= MORPH_SLOTS || slotB < 0 || slotB >= MORPH_SLOTS)
         return false;
     const Morph &m = g.scene.morph;
     const MorphKey &a = m.keys[slotA], &b = m.keys[slotB];
-    /* (a lamp that was moved on the device, solr_moves.hip: the blend would put its p0 back at the keys' place and leave
-     * its light record where the move put it - the host route makes the record from p0 again; primitives that were set
-     * anew on the device, solr_edits.hip: the blend would leave their texture coordinates and movable flags behind;
-     * materials that were set on the device, solr_materials.hip: the blend would keep them, where the host's takes its
-     * first key's) */
+    /* (morphBarredBy: a lamp move, an edit or a batch of materials served since h2d_scene, which the blend would undo in
+     * part - engine.h RequestKind says how) */
     if (a.nbPrimitives != g.scene.nbPrimitives || b.nbPrimitives != g.scene.nbPrimitives || !a.planes.ptr || !b.planes.ptr ||
-        !std::isfinite(weight) || g.scene.rotation.lampMoved || g.scene.rotation.edited || g.scene.rotation.materialsSet ||
-        lampWouldMove(slotA, slotB))
+        !std::isfinite(weight) || g.scene.morphBarredBy != 0 || lampWouldMove(slotA, slotB))
     {
-        if (getenv("SOLR_HIP_DEBUG_TREE"))
-            fprintf(stderr, "%s refused: keys for %d and %d of %d primitives, weight %g, a lamp moved here: %d\n", who, a.nbPrimitives,
-                    b.nbPrimitives, g.scene.nbPrimitives, weight, (int)g.scene.rotation.lampMoved);
+        noteRefusal(who, "keys for %d and %d of %d primitives, weight %g, barred by the request kinds of mask 0x%x", a.nbPrimitives,
+                    b.nbPrimitives, g.scene.nbPrimitives, weight, g.scene.morphBarredBy);
         return false;
     }
     return true;
@@ -332,20 +327,14 @@ bool canMorphOne(int slotA, int slotB, float weight, float viewDistance, const c
  * was changed). */
 int morphKeysOne(int slotA, int slotB, float weight, float viewDistance, const char *who)
 {
-    if (!canMorphOne(slotA, slotB, weight, viewDistance, who))
+    if (!canMorphOne(slotA, slotB, weight, viewDistance, who) || !beginRequest())
         return 0;
-    HIPCHECK(hipSetDevice(g.device));
-    flushGeometry();
-    if (!ok())
-        return 0;
-    quiesce();
     hipLaunchKernelGGL(k_morphPrimitives, dim3((unsigned)((g.scene.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
                        (const float4 *)g.scene.morph.keys[slotA].planes.ptr, (const float4 *)g.scene.morph.keys[slotB].planes.ptr,
                        weight);
-    const bool walkHolds = refitMovedScene(viewDistance);
-    g.scene.morphServed(walkHolds, ok(), slotA < SOLR_MORPH_TRACK_MAX_KEYS);
-    return ok() ? 1 : 0;
+    /* (a track's slots come first: asked through solr_hip_morph_between) */
+    return finishRequest(slotA < SOLR_MORPH_TRACK_MAX_KEYS ? REQUEST_TRACK_MORPH : REQUEST_MORPH, refitMovedScene(viewDistance));
 }
 
 } // namespace solreng
@@ -362,12 +351,12 @@ void packMorphKeys(hipStream_t stream, const Primitive *key, const int *rankOf, 
 extern "C" {
 int solr_hip_device_morphs(void)
 {
-    return g.scene.morph.nbDeviceMorphs;
+    return g.served[REQUEST_MORPH];
 }
 
 int solr_hip_device_track_morphs(void)
 {
-    return g.scene.morph.nbDeviceTrackMorphs;
+    return g.served[REQUEST_TRACK_MORPH];
 }
 
 int solr_hip_morph_track_keys(void)

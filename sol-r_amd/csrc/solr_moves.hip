@@ -1,8 +1,9 @@
 /*
  * solr_moves.hip - the rigid moves of the MI355X rendering engine besides the rotation: solr_hip_translate_primitives pushes
  * the resident primitives along and refits the node lists in the arena (the refit and what follows it: solr_rotation.hip
- * refitMovedScene), solr_hip_move_lamp sets a lamp's centre and its light record in place (engine.h Rotation: the counters,
- * lampMoved), solr_hip_read_lights hands the resident light records to the tests.
+ * refitMovedScene), solr_hip_move_lamp sets a lamp's centre and its light record in place (engine.h RequestKind and
+ * Scene::requestServed: what either changes in the scene's record; Engine::served: the counters), solr_hip_read_lights hands
+ * the resident light records to the tests.
  * Part of the engine's host side (engine.h); the boundary that calls into it is solr_hip.hip.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
@@ -52,17 +53,15 @@ __global__ __launch_bounds__(256) void k_translatePrimitives(float4 *__restrict_
     r[ROW_P2] = p2;
 }
 
-/* can this engine translate its resident scene?  (what canRotateOne asks, and a translation of three numbers; changes
- * nothing but the refit plan) */
+/* can this engine translate its resident scene?  (canRefitOne, and a translation of three numbers; changes nothing but
+ * the refit plan) */
 bool canTranslateOne(const float translation[3], float viewDistance)
 {
-    static const float none[3] = {0.f, 0.f, 0.f};
-    if (!canRotateOne(none, none, none, viewDistance, "solr_hip_translate_primitives"))
+    if (!canRefitOne(viewDistance, "solr_hip_translate_primitives"))
         return false;
     if (!translation || !std::isfinite(translation[0]) || !std::isfinite(translation[1]) || !std::isfinite(translation[2]))
     {
-        if (getenv("SOLR_HIP_DEBUG_TREE"))
-            fprintf(stderr, "solr_hip_translate_primitives refused: no translation, or a component that is not finite\n");
+        noteRefusal("solr_hip_translate_primitives", "no translation, or a component that is not finite");
         return false;
     }
     return true;
@@ -73,19 +72,12 @@ bool canTranslateOne(const float translation[3], float viewDistance)
  * and the caller has to take the host route (nothing was changed). */
 int translatePrimitivesOne(const float translation[3], float viewDistance)
 {
-    if (!canTranslateOne(translation, viewDistance))
+    if (!canTranslateOne(translation, viewDistance) || !beginRequest())
         return 0;
-    HIPCHECK(hipSetDevice(g.device));
-    flushGeometry();
-    if (!ok())
-        return 0;
-    quiesce();
     hipLaunchKernelGGL(k_translatePrimitives, dim3((unsigned)((g.scene.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
-                       (const unsigned char *)g.scene.rotation.movable.ptr, translation[0], translation[1], translation[2]);
-    const bool walkHolds = refitMovedScene(viewDistance);
-    g.scene.translationServed(walkHolds, ok());
-    return ok() ? 1 : 0;
+                       (const unsigned char *)g.scene.refit.movable.ptr, translation[0], translation[1], translation[2]);
+    return finishRequest(REQUEST_TRANSLATION, refitMovedScene(viewDistance));
 }
 
 /* ---- a lamp that is dragged: its centre and its light record in place ----------------------------------
@@ -165,8 +157,8 @@ bool canMoveLampOne(int lamp, const float center[3])
                    b.y >= center[1] + grow && a.w >= center[2] + grow))
             why = "the lamp would leave its cell";
     }
-    if (why && getenv("SOLR_HIP_DEBUG_TREE"))
-        fprintf(stderr, "solr_hip_move_lamp refused: %s (lamp %d of %d, %d light records)\n", why, lamp, s.nbLamps, g.lights.nbLights);
+    if (why)
+        noteRefusal("solr_hip_move_lamp", "%s (lamp %d of %d, %d light records)", why, lamp, s.nbLamps, g.lights.nbLights);
     return why == nullptr;
 }
 
@@ -175,13 +167,8 @@ bool canMoveLampOne(int lamp, const float center[3])
  * served here and the caller has to take the host route (nothing was changed). */
 int moveLampOne(int lamp, const float center[3])
 {
-    if (!canMoveLampOne(lamp, center))
+    if (!canMoveLampOne(lamp, center) || !beginRequest()) /* (no frame in flight reads a lamp that is half here and half there) */
         return 0;
-    HIPCHECK(hipSetDevice(g.device));
-    flushGeometry();
-    if (!ok() || !g.scene.arena.geometry.ptr)
-        return 0;
-    quiesce(); /* no frame in flight reads a lamp that is half here and half there */
     LampMove M;
     const int total = 1 + leafRecordsOfLists(g.scene, M.list);
     M.offPrims = g.scene.arena.offPrims;
@@ -201,8 +188,7 @@ int moveLampOne(int lamp, const float center[3])
         p0.y = location.y = center[1];
         p0.z = location.z = center[2];
     }
-    g.scene.lampMoveServed(ok());
-    return ok() ? 1 : 0;
+    return finishRequest(REQUEST_LAMP_MOVE);
 }
 
 } // namespace solreng
@@ -210,12 +196,12 @@ int moveLampOne(int lamp, const float center[3])
 extern "C" {
 int solr_hip_device_translations(void)
 {
-    return g.scene.rotation.nbDeviceTranslations;
+    return g.served[REQUEST_TRANSLATION];
 }
 
 int solr_hip_device_lamp_moves(void)
 {
-    return g.scene.rotation.nbDeviceLampMoves;
+    return g.served[REQUEST_LAMP_MOVE];
 }
 
 /* Diagnostics / tests: the resident arena's light records as the device holds them now, three float4 rows a light.

@@ -1,6 +1,7 @@
 /*
  * solr_rotation.hip - animated scenes of the MI355X rendering engine: solr_hip_rotate_primitives rotates the resident
- * primitives and refits the node lists in the arena (engine.h Rotation; the arena: solr_arena.hip).
+ * primitives and refits the node lists in the arena (engine.h Refit: the plan and the flags, Scene::requestServed: what a
+ * served request changes, Engine::served: the counters; the arena: solr_arena.hip).
  * Part of the engine's host side (engine.h); the boundary that calls into it is solr_hip.hip.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
@@ -195,9 +196,9 @@ __global__ __launch_bounds__(256) void k_refitNodes(float4 *__restrict__ arena, 
  * nesting.  Node 0, the light cell, keeps its +-viewDistance (GPUKernel.cpp:1189). */
 static void buildRefitPlan()
 {
-    g.scene.rotation.refitPlanPending = false;
-    g.scene.rotation.refitReady = false;
-    g.scene.rotation.exactStale = false;
+    g.scene.refit.refitPlanPending = false;
+    g.scene.refit.refitReady = false;
+    g.scene.refit.exactStale = false;
     for (NodeList *list : {&g.scene.exact, &g.scene.walk, &g.scene.orderFree})
         list->refitLevels.clear();
     if (!g.scene.nested)
@@ -205,14 +206,14 @@ static void buildRefitPlan()
     std::vector<int> plan;
     planRefit(g.scene.exact.rows, g.scene.walk.rows, g.scene.walk.origin, g.scene.orderFree.rows, g.scene.orderFree.origin, plan,
               g.scene.exact.refitLevels, g.scene.walk.refitLevels, g.scene.orderFree.refitLevels);
-    upload(g.scene.rotation.refitPlan, plan);
-    g.scene.rotation.refitReady = ok();
+    upload(g.scene.refit.refitPlan, plan);
+    g.scene.refit.refitReady = ok();
 }
 
 static void refitList(const NodeList &list, float viewDistance)
 {
     float4 *arena = (float4 *)g.scene.arena.geometry.ptr;
-    const int *plan = (const int *)g.scene.rotation.refitPlan.ptr;
+    const int *plan = (const int *)g.scene.refit.refitPlan.ptr;
     const std::vector<int> &levels = list.refitLevels;
     for (size_t l = 0; l + 1 < levels.size(); l += 2)
         hipLaunchKernelGGL(k_refitNodes, dim3((unsigned)((levels[l + 1] + 255) / 256)), dim3(256), 0, sceneStream(), arena,
@@ -222,10 +223,10 @@ static void refitList(const NodeList &list, float viewDistance)
 /* the reference's node list is wanted: refit it from the primitives as they are now */
 void refreshExactList()
 {
-    if (!g.scene.rotation.exactStale || !g.scene.arena.geometry.ptr)
+    if (!g.scene.refit.exactStale || !g.scene.arena.geometry.ptr)
         return;
     quiesce();
-    refitList(g.scene.exact, g.scene.rotation.exactStaleViewDistance);
+    refitList(g.scene.exact, g.scene.refit.exactStaleViewDistance);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(sceneStream()));
     g.scene.exactRefitted();
@@ -241,7 +242,7 @@ bool refitMovedScene(float viewDistance)
     const bool listsFollow = g.scene.orderFree.nb > 0 && !g.scene.orderFree.refitLevels.empty();
     if (listsFollow)
         refitList(g.scene.orderFree, viewDistance);
-    g.scene.rotationQueued(listsFollow, viewDistance);
+    g.scene.refitQueued(listsFollow, viewDistance);
     buildLeafRecords(); /* the leaves' copies of their first primitive follow the primitives */
     /* the refitted list encloses by construction (k_refitNodes); asked all the same, like any list the walks cut off at
      * the lamp (a scene that failed the check at its upload is not asked again) */
@@ -252,53 +253,59 @@ bool refitMovedScene(float viewDistance)
     return walkHolds;
 }
 
-/* Extension: GPUKernel::rotatePrimitives + compactBoxes(false) + h2d_scene on the resident scene
- * (GPUKernel.cpp:1378-1460, 1151-1281 of the reference), see k_rotatePrimitives.  Returns 1 when the
- * arena now holds the rotated scene, 0 when the request cannot be served here and the caller has to
- * take the host route (nothing was changed). */
-/* can this engine rotate its resident scene?  (makes the refit plan when the lists changed; changes nothing else) */
-bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance, const char *who)
+/* can this engine move primitives of its resident scene and refit the lists behind them?  What a rotation, a translation,
+ * an edit and a morph all ask first.  (Makes the refit plan when the lists changed; changes nothing else.) */
+bool canRefitOne(float viewDistance, const char *who)
 {
-    if (!ready(who) || !ok())
+    if (!ready(who))
         return false;
-    if (g.scene.rotation.refitPlanPending)
+    if (g.scene.refit.refitPlanPending)
     {
-        /* which nodes to refit, in which order: made for the first rotation after the lists changed */
+        /* which nodes to refit, in which order: made for the first request after the lists changed */
         ensureHostFreeLists();
         buildRefitPlan();
     }
     /* the seeds of the two box updates only commute with the unions while viewDistance <= 1e6, and a
      * tree cut off at NB_MAX_BOXES has host-side children the flattened list does not show */
-    if (!g.scene.rotation.refitReady || g.scene.rotation.nbMovable != g.scene.nbPrimitives || g.scene.nbPrimitives <= 0 ||
-        !(viewDistance <= 1000000.f) || !(viewDistance > 0.f) || g.scene.exact.nb >= NB_MAX_BOXES || !center || !cosAngles || !sinAngles)
+    if (!g.scene.refit.refitReady || g.scene.refit.nbMovable != g.scene.nbPrimitives || g.scene.nbPrimitives <= 0 ||
+        !(viewDistance <= 1000000.f) || !(viewDistance > 0.f) || g.scene.exact.nb >= NB_MAX_BOXES)
     {
-        if (getenv("SOLR_HIP_DEBUG_TREE"))
-            fprintf(stderr, "%s refused: plan %d, flags for %d of %d primitives, viewDistance %g, %d nodes\n", who,
-                    (int)g.scene.rotation.refitReady, g.scene.rotation.nbMovable, g.scene.nbPrimitives, viewDistance, g.scene.exact.nb);
+        noteRefusal(who, "plan %d, flags for %d of %d primitives, viewDistance %g, %d nodes", (int)g.scene.refit.refitReady,
+                    g.scene.refit.nbMovable, g.scene.nbPrimitives, viewDistance, g.scene.exact.nb);
         return false;
     }
     return true;
 }
 
+/* can this engine rotate its resident scene?  (canRefitOne, and the rotation's own three arrays) */
+bool canRotateOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance)
+{
+    if (!canRefitOne(viewDistance, "solr_hip_rotate_primitives"))
+        return false;
+    if (!center || !cosAngles || !sinAngles)
+    {
+        noteRefusal("solr_hip_rotate_primitives", "no centre, cosines or sines");
+        return false;
+    }
+    return true;
+}
+
+/* Extension: GPUKernel::rotatePrimitives + compactBoxes(false) + h2d_scene on the resident scene
+ * (GPUKernel.cpp:1378-1460, 1151-1281 of the reference), see k_rotatePrimitives.  Returns 1 when the
+ * arena now holds the rotated scene, 0 when the request cannot be served here and the caller has to
+ * take the host route (nothing was changed). */
 int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const float sinAngles[3], float viewDistance)
 {
-    if (!canRotateOne(center, cosAngles, sinAngles, viewDistance))
+    if (!canRotateOne(center, cosAngles, sinAngles, viewDistance) || !beginRequest())
         return 0;
-    HIPCHECK(hipSetDevice(g.device));
-    flushGeometry();
-    if (!ok())
-        return 0;
-    quiesce();
     RotationArgs R;
     R.cx = center[0], R.cy = center[1], R.cz = center[2];
     R.cosx = cosAngles[0], R.cosy = cosAngles[1], R.cosz = cosAngles[2];
     R.sinx = sinAngles[0], R.siny = sinAngles[1], R.sinz = sinAngles[2];
     hipLaunchKernelGGL(k_rotatePrimitives, dim3((unsigned)((g.scene.nbPrimitives + 255) / 256)), dim3(256), 0, sceneStream(),
                        (float4 *)g.scene.arena.geometry.ptr, g.scene.arena.offPrims, g.scene.nbPrimitives,
-                       (const unsigned char *)g.scene.rotation.movable.ptr, R);
-    const bool walkHolds = refitMovedScene(viewDistance);
-    g.scene.rotationServed(walkHolds, ok());
-    return ok() ? 1 : 0;
+                       (const unsigned char *)g.scene.refit.movable.ptr, R);
+    return finishRequest(REQUEST_ROTATION, refitMovedScene(viewDistance));
 }
 
 } // namespace solreng
@@ -306,6 +313,6 @@ int rotatePrimitivesOne(const float center[3], const float cosAngles[3], const f
 extern "C" {
 int solr_hip_device_rotations(void)
 {
-    return g.scene.rotation.nbDeviceRotations;
+    return g.served[REQUEST_ROTATION];
 }
 } // extern "C"

@@ -278,7 +278,7 @@ void setMovableOne(const unsigned char *flags, int nbPrimitives)
     ARGCHECK(nbPrimitives >= 0 && (nbPrimitives == 0 || flags), "solr_hip_set_movable: null flags");
     if (!ok())
         return;
-    g.scene.rotation.nbMovable = -1;
+    g.scene.refit.nbMovable = -1;
     if (nbPrimitives != g.scene.nbPrimitives)
         return;
     quiesce();
@@ -286,9 +286,9 @@ void setMovableOne(const unsigned char *flags, int nbPrimitives)
     std::vector<unsigned char> f(flags, flags + nbPrimitives);
     if (f.empty())
         f.push_back(0);
-    upload(g.scene.rotation.movable, f);
+    upload(g.scene.refit.movable, f);
     if (ok())
-        g.scene.rotation.nbMovable = nbPrimitives;
+        g.scene.refit.nbMovable = nbPrimitives;
 }
 
 /* One material of the table as the device gets it - h2dMaterialsOne for every active one, editMaterialsOne

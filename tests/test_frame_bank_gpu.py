@@ -303,6 +303,36 @@ def test_device_moves_survive_a_round_trip(solr):
         assert hip.solr_hip_scene_switches() == 1 and hip.solr_hip_scene_uploads() == 2 and hip.solr_hip_parked_scenes() == 1
 
 
+def test_the_counters_are_the_engines_not_a_scenes(solr):
+    """the two lifetimes the round trip above does not reach: an h2d_scene over a moved scene, and a resume over a resident
+    scene (which is dropped for it) - neither moves a counter, and the request after them adds exactly one"""
+    with Boundary(solr) as b:
+        hip = b.hip
+        b.upload("A")
+        b.settle("A")
+        assert b.counters() == (0,) * 7
+        assert b.rotate() == 1 and b.translate() == 1, "a move was declined"
+        moved = b.counters()
+        assert moved == (1, 1, 0, 0, 0, 0, 0)
+        b.upload("B")                                   # over the moved A, which goes
+        assert b.counters() == moved, "the counters jumped at h2d_scene"
+        b.settle("B")
+        assert b.counters() == moved
+        assert hip.solr_hip_park_scene(3) == 1
+        b.upload("A")
+        b.settle("A")
+        assert b.rotate() == 1
+        rotated = b.counters()
+        assert rotated == (2,) + moved[1:]
+        assert hip.solr_hip_resume_scene(3) == 1        # over the resident A: dropped, not parked
+        assert hip.solr_hip_parked_scenes() == 0 and hip.solr_hip_scene_switches() == 1
+        assert b.counters() == rotated, "the counters jumped at a resume that dropped the resident scene"
+        b.render("B")
+        assert b.rotate((0.0, 0.3, 0.0)) == 1
+        assert b.counters() == (3,) + moved[1:]
+        b.render("B")
+
+
 def test_the_order_free_countdown_is_parked_with_the_scene(solr, monkeypatch):
     monkeypatch.setenv("SOLR_HIP_FREE_AFTER", "3")      # (read at h2d_scene)
     with Boundary(solr) as b:
