@@ -346,6 +346,27 @@ int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char
 /* blocks the device has entropy-coded since the library was loaded */
 unsigned long long solr_hip_jpeg_coded_blocks(void);
 
+/* The same three with optimised Huffman tables - the reference encoder's two-pass mode (jpge.cpp, m_two_pass_flag): the
+ * symbols of the blocks are counted on the device (k_jpegSymbolCounts), four tables are built there for exactly those
+ * counts (k_jpegOptimiseTables: jpge's optimize_huffman_table, ties and all) and the segment is coded with them by the
+ * steps above.  `tables` receives what the file's four DHT segments must say, in their order - DC luma, AC luma, DC
+ * chroma, AC chroma: bits[t] the number of codes of each length 1 ... 16, values[t] the symbols in code order,
+ * nbValues[t] how many there are (JpegWriter::header takes them).  Arguments, returns, the capacity protocol and the
+ * refusals are those of the entries above, plus: tables not null.  `tables` is written only by a call that returns 0.
+ * The domain is the same: categories up to 11 (DC) and 10 (AC). */
+typedef struct
+{
+    unsigned char bits[4][16];
+    unsigned char values[4][256];
+    int nbValues[4];
+} SolrJpegHuffman;
+int solr_hip_jpeg_blocks_to_scan_optimised(const SolrJpegSource *source, const short *coefficients, long nbBlocks,
+                                           unsigned char *scan, long capacity, long *nbBytes, SolrJpegHuffman *tables);
+int solr_hip_rgb_to_jpeg_scan_optimised(const SolrJpegSource *source, const unsigned char *rgb, unsigned char *scan,
+                                        long capacity, long *nbBytes, SolrJpegHuffman *tables);
+int solr_hip_frame_to_jpeg_scan_optimised(int quality, int lumaH, int lumaV, unsigned char *scan, long capacity,
+                                          long *nbBytes, SolrJpegHuffman *tables);
+
 /* The iso-surface of a field of metaballs as triangles, on the device (sol-r_amd/csrc/solr_iso.hip; the arithmetic is
  * sol-r_amd/csrc/iso_surface.h, that of the reference's apps/scenes/animation/MetaballsScene.cpp, in IEEE binary32 in
  * source order; the host-only engine runs the same header in loops and gives the same bits).

@@ -91,6 +91,11 @@ class JpegSource(C.Structure):
                 ("quality", C.c_int), ("turned", C.c_int), ("swapRedBlue", C.c_int)]
 
 
+class JpegHuffman(C.Structure):
+    """SolrJpegHuffman of include/solr_hip.h: the four tables of an optimised file in the order of its DHT segments"""
+    _fields_ = [("bits", (C.c_ubyte * 16) * 4), ("values", (C.c_ubyte * 256) * 4), ("nbValues", C.c_int * 4)]
+
+
 class IsoGrid(C.Structure):
     """SolrIsoGrid of include/solr_hip.h: the grid the field of metaballs is sampled on and how its surface is placed"""
     _fields_ = [("gridSize", C.c_int), ("size", C.c_float * 3), ("threshold", C.c_float), ("center", C.c_float * 3),
@@ -327,6 +332,14 @@ def _declare_hip(L):
     L.solr_hip_frame_to_jpeg_scan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, P(C.c_long)]
     L.solr_hip_frame_to_jpeg_scan.restype = C.c_int
     L.solr_hip_jpeg_coded_blocks.restype = C.c_ulonglong
+    L.solr_hip_jpeg_blocks_to_scan_optimised.argtypes = L.solr_hip_jpeg_blocks_to_scan.argtypes + [P(JpegHuffman)]
+    L.solr_hip_rgb_to_jpeg_scan_optimised.argtypes = L.solr_hip_rgb_to_jpeg_scan.argtypes + [P(JpegHuffman)]
+    L.solr_hip_frame_to_jpeg_scan_optimised.argtypes = L.solr_hip_frame_to_jpeg_scan.argtypes + [P(JpegHuffman)]
+    L.solr_hip_probe_jpeg_census.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p]
+    L.solr_hip_probe_jpeg_tables.argtypes = [C.c_void_p, P(JpegHuffman)]
+    for name in ("jpeg_blocks_to_scan_optimised", "rgb_to_jpeg_scan_optimised", "frame_to_jpeg_scan_optimised",
+                 "probe_jpeg_census", "probe_jpeg_tables"):
+        getattr(L, "solr_hip_" + name).restype = C.c_int
     L.solr_hip_iso_field.argtypes = [P(IsoGrid), C.c_void_p, C.c_int, C.c_void_p]
     L.solr_hip_iso_field.restype = C.c_int
     L.solr_hip_iso_surface.argtypes = [P(IsoGrid), C.c_void_p, C.c_void_p, C.c_int]
@@ -380,6 +393,12 @@ def _declare_host(L):
     L.SolRx_JpegQuantise.argtypes = [i, i, i, i, C.c_void_p]
     L.SolRx_RenderJpeg.argtypes = [d, i, i, i, C.c_void_p, C.c_long, P(C.c_long)]
     L.SolRx_JpegFileFromCoefficients.argtypes = [C.c_void_p, C.c_long, i, i, i, i, i, C.c_void_p, C.c_long, P(C.c_long)]
+    L.SolRx_EncodeJpegOptimised.argtypes = L.SolRx_EncodeJpeg.argtypes
+    L.SolRx_RenderJpegOptimised.argtypes = L.SolRx_RenderJpeg.argtypes
+    L.SolRx_JpegFileFromCoefficientsOptimised.argtypes = L.SolRx_JpegFileFromCoefficients.argtypes
+    L.SolRx_JpegFromCoefficientsOptimised.argtypes = [C.c_char_p, C.c_void_p, C.c_long, i, i, i, i, i]
+    L.SolRx_JpegOptimiseTable.argtypes = [C.c_void_p, i, C.c_void_p, C.c_void_p]
+    L.SolRx_JpegCensus.argtypes = [C.c_void_p, C.c_long, i, C.c_void_p]
     L.SolRx_JpegEntropyGranularity.argtypes = [P(i)]
     L.SolRx_JpegEntropyGranularity.restype = None
     L.SolRx_JpegEntropyPrefix.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
@@ -889,16 +908,19 @@ class Kernel:
         status = self.L.SolR_GenerateScreenshot(os.fsencode(path), width, height, quality)
         self.check(status, "SolR_GenerateScreenshot")
 
-    def encode_jpeg(self, path, pixels, quality=85, sampling=(2, 2), turned=False, swap_red_blue=False):
+    def encode_jpeg(self, path, pixels, quality=85, sampling=(2, 2), turned=False, swap_red_blue=False, optimise=False):
         """The screenshot's encoder alone (SolRx_EncodeJpeg): `pixels` (H, W, 3) uint8 to a baseline JPEG file, byte for
         byte the reference encoder's.  quality: JPEG quality 1 ... 100; sampling: luma (H, V), one of (1, 1), (2, 1),
         (2, 2); turned / swap_red_blue read the pixels as a screenshot reads a frame: pixel p from pixel N - p (N = W * H;
-        N itself is read as N - 1), first and third channel swapped."""
+        N itself is read as N - 1), first and third channel swapped.  optimise: Huffman tables built for the picture's own
+        symbols in place of the standard ones (SolRx_EncodeJpegOptimised, the reference encoder's two-pass mode): a smaller
+        file of the same pixels."""
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("pixels must be (height, width, 3)")
-        status = self.L.SolRx_EncodeJpeg(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0], quality,
-                                         sampling[0], sampling[1], int(bool(turned)), int(bool(swap_red_blue)))
+        entry = self.L.SolRx_EncodeJpegOptimised if optimise else self.L.SolRx_EncodeJpeg
+        status = entry(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0], quality, sampling[0], sampling[1],
+                       int(bool(turned)), int(bool(swap_red_blue)))
         if status != 0:
             raise SolrError("SolRx_EncodeJpeg refused its arguments or could not write %s" % path)
 
@@ -918,26 +940,32 @@ class Kernel:
             raise SolrError("%s failed: %s" % (what, text.value.decode()))
         raise SolrError("%s refused its arguments (out of range, or a block outside what the standard tables code)" % what)
 
-    def render_jpeg(self, quality=85, sampling=(2, 2), **scene_info):
+    def render_jpeg(self, quality=85, sampling=(2, 2), optimise=False, **scene_info):
         """One frame as render() renders it, returned as the bytes of a baseline JPEG file (SolRx_RenderJpeg) - the file a
         one-pass screenshot of the same size and settings would be.  quality: JPEG quality 1 ... 100; sampling: luma
         (H, V), one of (1, 1), (2, 1), (2, 2).  With the HIP engine the frame is coded on the device and only the file
         comes to the host: the host bitmap (SolRx_GetBitmap) is not refreshed.  A file larger than the first buffer costs
-        a second frame: the call is repeated with the size the first one reported."""
+        a second frame: the call is repeated with the size the first one reported.  optimise: the file's Huffman tables are
+        built for the frame's own symbols (SolRx_RenderJpegOptimised) - counted and built on the device with the HIP engine
+        - and the file is smaller; it decodes to the same pixels."""
         if scene_info:
             self.set_scene_info(**scene_info)
         room = max(1 << 16, self.info["width"] * self.info["height"] // 2)
-        return self._jpeg_file(lambda to, n, size: self.L.SolRx_RenderJpeg(0.0, quality, sampling[0], sampling[1], to, n, size),
-                               "SolRx_RenderJpeg", room)
+        entry = self.L.SolRx_RenderJpegOptimised if optimise else self.L.SolRx_RenderJpeg
+        return self._jpeg_file(lambda to, n, size: entry(0.0, quality, sampling[0], sampling[1], to, n, size),
+                               "SolRx_RenderJpegOptimised" if optimise else "SolRx_RenderJpeg", room)
 
-    def jpeg_from_coefficients(self, blocks, width, height, quality=85, sampling=(2, 2)):
+    def jpeg_from_coefficients(self, blocks, width, height, quality=85, sampling=(2, 2), optimise=False):
         """The bytes of the JPEG file of quantised coefficient `blocks` (n, 64) int16 in MCU and zigzag order, coded by
         the engine's entropy stage (SolRx_JpegFileFromCoefficients): the device's kernels with the HIP engine, the same
-        steps in loops without a device."""
+        steps in loops without a device.  optimise: with tables built for the blocks' own symbols
+        (SolRx_JpegFileFromCoefficientsOptimised)."""
         a = np.ascontiguousarray(blocks, dtype=np.int16).reshape(-1, 64)
-        return self._jpeg_file(lambda to, n, size: self.L.SolRx_JpegFileFromCoefficients(
-            a.ctypes.data, a.shape[0], width, height, quality, sampling[0], sampling[1], to, n, size),
-            "SolRx_JpegFileFromCoefficients", max(1 << 16, a.shape[0] * 64))
+        entry = self.L.SolRx_JpegFileFromCoefficientsOptimised if optimise else self.L.SolRx_JpegFileFromCoefficients
+        return self._jpeg_file(lambda to, n, size: entry(a.ctypes.data, a.shape[0], width, height, quality, sampling[0],
+                                                         sampling[1], to, n, size),
+                               "SolRx_JpegFileFromCoefficientsOptimised" if optimise else "SolRx_JpegFileFromCoefficients",
+                               max(1 << 16, a.shape[0] * 64))
 
     def postprocessing_buffer(self):
         """Float framebuffer of the last frame: (H, W, 8) = colorInfo.xyzw, sceneInfo.xyzw."""

@@ -17,6 +17,11 @@
  * tests/golden/jpeg_encoder.npz holds jpge's own files; tests/test_jpeg_entropy.py holds the steps to them and to the
  * one-pass writer (JpegWriter::encode).
  *
+ * The tables are the four standard ones, or - the reference encoder's two-pass mode, see "optimised tables" below - four
+ * built for the symbols of the blocks themselves: a census by the same walk (blockCensus), optimiseTable per table, and the
+ * steps above with the result as their tables.  tests/golden/jpeg_two_pass.npz holds jpge's own tables and two-pass files;
+ * tests/test_jpeg_two_pass.py holds census, builder and writer to them.
+ *
  * The domain is what the four standard tables can code: a DC difference of category 0 ... 11 (|d| <= 2047) and AC
  * coefficients of category 1 ... 10 (|a| <= 1023).  blockBits reports a block outside it.  The pixel stage cannot make
  * one: its forward DCT is the orthonormal one (DC = sum / 8) of samples - 128 in -128 ... 127, so a DC lies in
@@ -127,6 +132,12 @@ static_assert((makeTables().ac[0][ZRL] >> 16) <= 26 && (makeTables().ac[1][ZRL] 
                   (makeTables().ac[0][EOB] >> 16) <= 26 && (makeTables().ac[1][EOB] >> 16) <= 26,
               "run symbols are shorter than a coefficient");
 
+/* ... and with ANY table whose codes have at most 16 bits (an optimised one): the DC of category 11 may have a 16-bit
+ * code too.  The same two static conditions hold of any such table: a run symbol's 16 bits are fewer than 26 */
+constexpr int MAX_CODE_BITS = 16;
+constexpr int MAX_BLOCK_BITS_ANY_TABLE = (MAX_CODE_BITS + MAX_DC_CATEGORY) + 63 * (MAX_CODE_BITS + MAX_AC_CATEGORY);
+static_assert(MAX_BLOCK_BITS_ANY_TABLE == 1665 && MAX_BLOCK_BITS_ANY_TABLE >= MAX_BLOCK_BITS, "any table's longest block");
+
 JPE_HD inline const Tables &tables()
 {
     static constexpr Tables t = makeTables();
@@ -166,13 +177,13 @@ JPE_HD inline u32 amplitude(int value, int size)
     return (u32)(value < 0 ? value - 1 : value) & ((1u << size) - 1u);
 }
 
-/* The walk over a block (jpge.cpp:883-952), handing every symbol with its amplitude - at most 16 + 11 bits - to
- * sink.put(bits, n).  Returns whether the block is inside the domain; outside it the category is held at the tables' last,
- * so that the walk still takes the bits blockBits counted and no others. */
-template <class Sink>
-JPE_HD inline bool walkBlock(const short *block, int previousDc, int chroma, Sink &sink)
+/* The walk over a block (jpge.cpp:883-952; the same decisions as its census, code_coefficients_pass_one, :837-881),
+ * handing every symbol to the visitor: dc(category, difference), then ac(symbol, category, value) per (run, size) symbol
+ * - and per ZRL and EOB, with category 0 and value 0.  Returns whether the block is inside the domain; outside it the
+ * category is held at the tables' last, so that every walk takes the same symbols whoever visits. */
+template <class Visitor>
+JPE_HD inline bool walkSymbols(const short *block, int previousDc, Visitor &visitor)
 {
-    const Tables &t = tables();
     bool inside = true;
     const int difference = block[0] - previousDc;
     int size = bitLength(difference < 0 ? -difference : difference);
@@ -181,8 +192,7 @@ JPE_HD inline bool walkBlock(const short *block, int previousDc, int chroma, Sin
         inside = false;
         size = MAX_DC_CATEGORY;
     }
-    u32 entry = t.dc[chroma][size];
-    sink.put(((entry & 0xffffu) << size) | amplitude(difference, size), (int)(entry >> 16) + size);
+    visitor.dc(size, difference);
     int run = 0;
     for (int k = 1; k < 64; ++k)
     {
@@ -192,25 +202,54 @@ JPE_HD inline bool walkBlock(const short *block, int previousDc, int chroma, Sin
             ++run;
             continue;
         }
-        entry = t.ac[chroma][ZRL];
         for (; run >= 16; run -= 16)
-            sink.put(entry & 0xffffu, (int)(entry >> 16));
+            visitor.ac(ZRL, 0, 0);
         size = bitLength(value < 0 ? -value : value);
         if (size > MAX_AC_CATEGORY)
         {
             inside = false;
             size = MAX_AC_CATEGORY;
         }
-        entry = t.ac[chroma][(run << 4) + size];
-        sink.put(((entry & 0xffffu) << size) | amplitude(value, size), (int)(entry >> 16) + size);
+        visitor.ac((run << 4) + size, size, value);
         run = 0;
     }
     if (run)
-    {
-        entry = t.ac[chroma][EOB];
-        sink.put(entry & 0xffffu, (int)(entry >> 16));
-    }
+        visitor.ac(EOB, 0, 0);
     return inside;
+}
+
+/* a visitor that codes: the symbol's code from the tables `t`, the amplitude behind it - at most 16 + 11 bits - to
+ * sink.put(bits, n) */
+template <class Sink>
+struct Coder
+{
+    const Tables &t;
+    int chroma;
+    Sink &sink;
+    JPE_HD void dc(int size, int difference)
+    {
+        const u32 entry = t.dc[chroma][size];
+        sink.put(((entry & 0xffffu) << size) | amplitude(difference, size), (int)(entry >> 16) + size);
+    }
+    JPE_HD void ac(int symbol, int size, int value)
+    {
+        const u32 entry = t.ac[chroma][symbol];
+        sink.put(((entry & 0xffffu) << size) | amplitude(value, size), (int)(entry >> 16) + size);
+    }
+};
+
+/* The walk with the tables of a provider: tables() for the four standard ones, or tables that came as data (an optimised
+ * set, on the device its copy in LDS) */
+template <class Sink>
+JPE_HD inline bool walkBlock(const Tables &t, const short *block, int previousDc, int chroma, Sink &sink)
+{
+    Coder<Sink> coder = {t, chroma, sink};
+    return walkSymbols(block, previousDc, coder);
+}
+template <class Sink>
+JPE_HD inline bool walkBlock(const short *block, int previousDc, int chroma, Sink &sink)
+{
+    return walkBlock(tables(), block, previousDc, chroma, sink);
 }
 
 struct BitCounter
@@ -220,13 +259,18 @@ struct BitCounter
 };
 
 /* bits: DC category and amplitude, a ZRL per sixteen zeros in front of a coefficient, a symbol and an amplitude per
- * coefficient, EOB unless position 63 is taken; at most MAX_BLOCK_BITS.  false: the block is outside the domain */
-JPE_HD inline bool blockBits(const short *block, int previousDc, int chroma, u32 *bits)
+ * coefficient, EOB unless position 63 is taken; at most MAX_BLOCK_BITS with the standard tables, MAX_BLOCK_BITS_ANY_TABLE
+ * with any.  false: the block is outside the domain */
+JPE_HD inline bool blockBits(const Tables &t, const short *block, int previousDc, int chroma, u32 *bits)
 {
     BitCounter counter;
-    const bool inside = walkBlock(block, previousDc, chroma, counter);
+    const bool inside = walkBlock(t, block, previousDc, chroma, counter);
     *bits = counter.bits;
     return inside;
+}
+JPE_HD inline bool blockBits(const short *block, int previousDc, int chroma, u32 *bits)
+{
+    return blockBits(tables(), block, previousDc, chroma, bits);
 }
 
 /* the two words that n (1 ... 32) bits at bit offset `at` of the stream touch, and what goes into each */
@@ -255,10 +299,225 @@ struct WordWriter
 };
 
 /* the same walk, the bits ORed into `words` from bit offset `at` on */
-JPE_HD inline void blockEmit(const short *block, int previousDc, int chroma, u64 at, u32 *words)
+JPE_HD inline void blockEmit(const Tables &t, const short *block, int previousDc, int chroma, u64 at, u32 *words)
 {
     WordWriter writer = {words, at};
-    walkBlock(block, previousDc, chroma, writer);
+    walkBlock(t, block, previousDc, chroma, writer);
+}
+JPE_HD inline void blockEmit(const short *block, int previousDc, int chroma, u64 at, u32 *words)
+{
+    blockEmit(tables(), block, previousDc, chroma, at, words);
+}
+
+/* ---- optimised tables ------------------------------------------------------------------------------------------------ */
+/* The reference encoder's two-pass mode (jpge.cpp, params::m_two_pass_flag): the symbols of the picture are counted
+ * (code_coefficients_pass_one, :837-881), four tables are built for exactly those counts (optimize_huffman_table, :353-397)
+ * and written in the file's DHT segments, and the blocks are coded with them.  Restated here in steps that the host runs
+ * in loops and the device in lanes; tests/golden/jpeg_two_pass.npz holds jpge's own tables and files. */
+
+/* how often every symbol of the four tables occurs: the shape of Tables, a counter where that has a code */
+struct Census
+{
+    u32 dc[2][12];
+    u32 ac[2][256];
+};
+constexpr int CENSUS_COUNTERS = 2 * 12 + 2 * 256;
+static_assert(sizeof(Census) == CENSUS_COUNTERS * sizeof(u32) && sizeof(Tables) == sizeof(Census), "counters as entries");
+
+struct Counter
+{
+    Census &census;
+    int chroma;
+    JPE_HD void dc(int size, int) { ++census.dc[chroma][size]; }
+    JPE_HD void ac(int symbol, int, int) { ++census.ac[chroma][symbol]; }
+};
+
+/* the symbols of one block added to `census`: the walk of blockBits, so what is counted is what will be coded.  false:
+ * the block is outside the domain (its symbols are counted as the walk holds them) */
+JPE_HD inline bool blockCensus(const short *block, int previousDc, int chroma, Census &census)
+{
+    Counter counter = {census, chroma};
+    return walkSymbols(block, previousDc, counter);
+}
+
+/* The four tables of a file in the order of its DHT segments (jpge.cpp:486-495): DC luma, AC luma, DC chroma, AC chroma.
+ * bits: the number of codes of each length 1 ... 16; values: the symbols in code order, nbValues of them */
+constexpr int TABLE_SLOTS = 4;
+struct Huffman
+{
+    u8 bits[TABLE_SLOTS][16];
+    u8 values[TABLE_SLOTS][256];
+    int nbValues[TABLE_SLOTS];
+};
+JPE_HD inline int slotIsAc(int slot) { return slot & 1; }
+JPE_HD inline int slotChroma(int slot) { return slot >> 1; }
+JPE_HD inline int slotLength(int slot) { return slotIsAc(slot) ? 256 : 12; } /* DC_LUM_CODES, AC_LUM_CODES */
+JPE_HD inline const u32 *slotCounts(const Census &census, int slot)
+{
+    return slotIsAc(slot) ? census.ac[slotChroma(slot)] : census.dc[slotChroma(slot)];
+}
+JPE_HD inline u32 *slotEntries(Tables &t, int slot)
+{
+    return slotIsAc(slot) ? t.ac[slotChroma(slot)] : t.dc[slotChroma(slot)];
+}
+
+/* jpge sorts the used symbols by count with an LSD radix sort (radix_sort_syms, :226-264), which is stable, over the
+ * symbols in index order behind a dummy of count 1 (:356-365): the order of (count, index) pairs, the dummy - whose count
+ * no used symbol's is below - first.  The place of used symbol i behind the dummy: the used symbols whose pair is below
+ * its own.  (Ties and the dummy's place decide bytes.) */
+constexpr int MAX_TABLE_SYMBOLS = 1 + 256; /* the dummy and a whole AC table */
+JPE_HD inline int symbolRank(const u32 *counts, int tableLen, int i)
+{
+    const u32 mine = counts[i];
+    int below = 0;
+    for (int j = 0; j < tableLen; ++j)
+    {
+        const u32 other = counts[j];
+        below += (other != 0u && (other < mine || (other == mine && j < i))) ? 1 : 0;
+    }
+    return below;
+}
+
+/* calculate_minimum_redundancy (:266-321; Moffat and Katajainen, "In-place calculation of minimum-redundancy codes",
+ * 1995): a[0 ... n - 1] holds counts in ascending order and receives the code length of each.  Three passes in place:
+ * the tree's internal nodes with parent links, the internal nodes' depths, the leaves' depths. */
+JPE_HD inline void codeLengths(u32 *a, int n)
+{
+    if (n == 0)
+        return;
+    if (n == 1)
+    {
+        a[0] = 1;
+        return;
+    }
+    a[0] += a[1];
+    int root = 0, leaf = 2;
+    for (int next = 1; next < n - 1; ++next)
+    {
+        /* the two smallest of the unused leaves and the unlinked internal nodes, a leaf on a tie */
+        if (leaf >= n || a[root] < a[leaf])
+        {
+            a[next] = a[root];
+            a[root++] = (u32)next;
+        }
+        else
+            a[next] = a[leaf++];
+        if (leaf >= n || (root < next && a[root] < a[leaf]))
+        {
+            a[next] += a[root];
+            a[root++] = (u32)next;
+        }
+        else
+            a[next] += a[leaf++];
+    }
+    a[n - 2] = 0;
+    for (int next = n - 3; next >= 0; --next)
+        a[next] = a[a[next]] + 1;
+    int available = 1, used = 0, depth = 0, next = n - 1;
+    root = n - 2;
+    while (available > 0)
+    {
+        while (root >= 0 && (int)a[root] == depth)
+        {
+            ++used;
+            --root;
+        }
+        while (available > used)
+        {
+            a[next--] = (u32)depth;
+            --available;
+        }
+        available = 2 * used;
+        ++depth;
+        used = 0;
+    }
+}
+
+/* huffman_enforce_max_code_size (:323-350) with the limit of 16: numCodes[l] codes of length l, l up to n - 1 for n
+ * symbols.  The longer ones are counted as 16 bits; while the Kraft sum is above one, a code of 16 bits goes and the
+ * longest code below 16 bits becomes two one bit longer */
+JPE_HD inline void limitCodeLengths(int *numCodes, int n)
+{
+    if (n <= 1)
+        return;
+    for (int l = MAX_CODE_BITS + 1; l < MAX_TABLE_SYMBOLS; ++l)
+    {
+        numCodes[MAX_CODE_BITS] += numCodes[l];
+        numCodes[l] = 0;
+    }
+    u32 total = 0;
+    for (int l = MAX_CODE_BITS; l > 0; --l)
+        total += (u32)numCodes[l] << (MAX_CODE_BITS - l);
+    for (; total != (1u << MAX_CODE_BITS); --total)
+    {
+        --numCodes[MAX_CODE_BITS];
+        for (int l = MAX_CODE_BITS - 1; l > 0; --l)
+            if (numCodes[l])
+            {
+                --numCodes[l];
+                numCodes[l + 1] += 2;
+                break;
+            }
+    }
+}
+
+/* :367-392 - sorted[0 ... n - 1]: the counts in sorted order, the dummy's 1 first; numCodes: MAX_TABLE_SYMBOLS ints of
+ * room.  bits[l - 1] = the codes of length l, the dummy - which is in the longest occupied length, so that no symbol's
+ * code is all ones - taken out */
+JPE_HD inline void bitsOfSorted(u32 *sorted, int n, int *numCodes, u8 bits[16])
+{
+    codeLengths(sorted, n);
+    for (int l = 0; l < MAX_TABLE_SYMBOLS; ++l)
+        numCodes[l] = 0;
+    for (int i = 0; i < n; ++i)
+        ++numCodes[sorted[i]];
+    limitCodeLengths(numCodes, n);
+    for (int l = 1; l <= MAX_CODE_BITS; ++l)
+        bits[l - 1] = (u8)numCodes[l];
+    for (int l = MAX_CODE_BITS; l >= 1; --l)
+        if (bits[l - 1])
+        {
+            --bits[l - 1];
+            break;
+        }
+}
+
+/* optimize_huffman_table (:353-397) for counts[0 ... tableLen - 1], tableLen at most 256: bits[16] and the values - the
+ * sorted symbols without the dummy, the most frequent first (:394-396).  Returns how many values there are: the symbols
+ * with a count */
+inline int optimiseTable(const u32 *counts, int tableLen, u8 bits[16], u8 *values)
+{
+    u32 sorted[MAX_TABLE_SYMBOLS];
+    int numCodes[MAX_TABLE_SYMBOLS];
+    int n = 1;
+    for (int i = 0; i < tableLen; ++i)
+        n += counts[i] ? 1 : 0;
+    sorted[0] = 1;
+    for (int i = 0; i < tableLen; ++i)
+        if (counts[i])
+        {
+            const int at = 1 + symbolRank(counts, tableLen, i);
+            sorted[at] = counts[i];
+            values[n - 1 - at] = (u8)i;
+        }
+    bitsOfSorted(sorted, n, numCodes, bits);
+    return n - 1;
+}
+
+/* the four tables of a census (:1022-1027) */
+inline void optimiseTables(const Census &census, Huffman &huffman)
+{
+    for (int slot = 0; slot < TABLE_SLOTS; ++slot)
+        huffman.nbValues[slot] = optimiseTable(slotCounts(census, slot), slotLength(slot), huffman.bits[slot],
+                                               huffman.values[slot]);
+}
+
+/* code and length per symbol of tables that came as data (compute_huffman_table, :528-562) */
+inline void tablesOf(const Huffman &huffman, Tables &t)
+{
+    t = Tables();
+    for (int slot = 0; slot < TABLE_SLOTS; ++slot)
+        fillTable(huffman.bits[slot], huffman.values[slot], slotEntries(t, slot));
 }
 
 /* ---- the end of the stream -------------------------------------------------------------------------------------------- */

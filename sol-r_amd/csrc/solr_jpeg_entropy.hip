@@ -19,6 +19,16 @@
  *   (scan)            the same scan over the chunks: the 0xFF bytes before each, and their total
  *   k_jpegStuff       the same mapping: a lane's word goes to the chunk's offset plus the 0xFF before the chunk plus the
  *                     0xFF of the lanes below it (a scan across the wave), a zero behind every 0xFF
+ * With optimised tables (the solr_hip_*_to_jpeg_scan_optimised entries; jpge's two-pass mode) two kernels go in front, and
+ * k_jpegBlockBits and k_jpegEmit run in a second instantiation whose tables are an LDS copy of what the second one made:
+ *   k_jpegSymbolCounts    the same mapping as k_jpegBlockBits: the walk of jpn::blockCensus into a histogram of the group in
+ *                     LDS (LDS atomics: lanes meet on the frequent symbols), whose non-zero counters are then added to the
+ *                     histogram in device memory
+ *   k_jpegOptimiseTables  a wave64 workgroup per table: every lane ranks its symbols among the (count, index) pairs
+ *                     (jpn::symbolRank, at most 256 comparisons each), one lane runs the three serial passes of the length
+ *                     computation and the 16-bit limit over LDS (jpn::bitsOfSorted), and all lanes write bits, values and
+ *                     the code | length << 16 entries.  No host round trip sits between census and coding: bits and values
+ *                     come to the host with the total and the flag
  * A block's coefficients are read once per walk from LDS, where the group's blocks are staged with coalesced loads, a block
  * 33 words apart: the lanes of a 32-lane half then read 32 different banks.  The predecessor's DC (jpn::predecessor) is one
  * global load.  Nothing is indexed by a run-time value in registers: no scratch.
@@ -27,12 +37,15 @@
 #include <hipcub/hipcub.hpp>
 
 #include <atomic>
+#include <cstddef>
+#include <cstring>
 #include <string>
 
 #include "engine.h"
 #include "jpeg_device.h"
 #include "jpeg_encode.h"
 #include "jpeg_entropy.h"
+#include "../../include/solr_hip_probes_jpeg.h"
 
 namespace
 {
@@ -44,9 +57,30 @@ constexpr int GROUP = 64;
 static_assert(jpn::BLOCKS_PER_GROUP == GROUP, "a lane per block");
 static_assert(jpn::STUFF_CHUNK_BYTES == GROUP * 4, "a lane per word of a chunk");
 constexpr int STAGE_PITCH = 33; /* words between two staged blocks of 32 words, see above */
-/* the words a group's piece can touch: its bits, the tail's (at most 7), and a start anywhere in a word */
-constexpr u32 GROUP_BITS = (u32)jpn::BLOCKS_PER_GROUP * jpn::MAX_BLOCK_BITS + 7u;
-constexpr int GROUP_WORDS = (int)((GROUP_BITS + 31u + 31u) / 32u);
+/* the words a group's piece can touch: its bits, the tail's (at most 7), and a start anywhere in a word.  DATA: the
+ * tables came as data and a block is bounded by what any table of 16-bit codes allows, not by the standard ones */
+template <bool DATA>
+constexpr u32 GROUP_BITS = (u32)jpn::BLOCKS_PER_GROUP * (DATA ? jpn::MAX_BLOCK_BITS_ANY_TABLE : jpn::MAX_BLOCK_BITS) + 7u;
+template <bool DATA>
+constexpr int GROUP_WORDS = (int)((GROUP_BITS<DATA> + 31u + 31u) / 32u);
+static_assert(GROUP_BITS<false> == 64u * 1660u + 7u && GROUP_BITS<true> == 64u * 1665u + 7u, "the two bounds");
+static_assert((GROUP * 33 + GROUP_WORDS<true>) * sizeof(u32) + sizeof(jpn::Tables) <= 64u * 1024u, "k_jpegEmit's LDS");
+
+/* the tables of an instantiation: the standard ones, or the group's LDS copy of the device's (2 144 bytes; every lane
+ * takes part, and a barrier must follow before the walk - stageBlocks ends in one) */
+template <bool DATA>
+__device__ inline const jpn::Tables &groupTables(u32 *own, const jpn::Tables *__restrict__ device)
+{
+    if constexpr (DATA)
+    {
+        const u32 *from = reinterpret_cast<const u32 *>(device);
+        for (int i = threadIdx.x; i < jpn::CENSUS_COUNTERS; i += GROUP)
+            own[i] = from[i];
+        return *reinterpret_cast<const jpn::Tables *>(own);
+    }
+    else
+        return jpn::tables();
+}
 
 /* the group's blocks from `coefficients` (block `first` on, `count` of them) into `staged`, STAGE_PITCH words apart */
 __device__ inline void stageBlocks(const short *__restrict__ coefficients, long first, int count, u32 *staged)
@@ -63,11 +97,14 @@ __device__ inline int previousDc(const short *__restrict__ coefficients, long in
     return before < 0 ? 0 : (int)coefficients[before * 64];
 }
 
+template <bool DATA>
 __global__ __launch_bounds__(GROUP) void k_jpegBlockBits(const short *__restrict__ coefficients, const int nbBlocks,
                                                          const int lumaBlocks, u64 *__restrict__ bits,
-                                                         u32 *__restrict__ flag)
+                                                         u32 *__restrict__ flag, const jpn::Tables *__restrict__ dTables)
 {
     __shared__ u32 staged[GROUP * STAGE_PITCH];
+    __shared__ u32 own[DATA ? jpn::CENSUS_COUNTERS : 1];
+    const jpn::Tables &t = groupTables<DATA>(own, dTables);
     const long first = (long)blockIdx.x * GROUP;
     const int count = nbBlocks - first < GROUP ? (int)(nbBlocks - first) : GROUP;
     stageBlocks(coefficients, first, count, staged);
@@ -78,7 +115,7 @@ __global__ __launch_bounds__(GROUP) void k_jpegBlockBits(const short *__restrict
         return;
     const long index = first + lane;
     u32 n = 0;
-    const bool inside = jpn::blockBits(reinterpret_cast<const short *>(staged + lane * STAGE_PITCH),
+    const bool inside = jpn::blockBits(t, reinterpret_cast<const short *>(staged + lane * STAGE_PITCH),
                                        previousDc(coefficients, index, lumaBlocks), jpn::chromaOf(index, lumaBlocks), &n);
     bits[index] = n;
     if (!inside)
@@ -102,12 +139,14 @@ struct SharedWriter
     }
 };
 
+template <bool DATA>
 __global__ __launch_bounds__(GROUP) void k_jpegEmit(const short *__restrict__ coefficients, const int nbBlocks,
                                                     const int lumaBlocks, const u64 *__restrict__ offsets,
-                                                    u32 *__restrict__ stream)
+                                                    u32 *__restrict__ stream, const jpn::Tables *__restrict__ dTables)
 {
     __shared__ u32 staged[GROUP * STAGE_PITCH];
-    __shared__ u32 piece[GROUP_WORDS];
+    __shared__ u32 piece[GROUP_WORDS<DATA>];
+    __shared__ u32 own[DATA ? jpn::CENSUS_COUNTERS : 1];
     const int lane = threadIdx.x;
     const long first = (long)blockIdx.x * GROUP;
     const int count = nbBlocks - first < GROUP ? (int)(nbBlocks - first) : GROUP;
@@ -117,8 +156,9 @@ __global__ __launch_bounds__(GROUP) void k_jpegEmit(const short *__restrict__ co
     if (last)
         to += (u64)jpn::tailBits(to);
     /* (what k_jpegBlockBits counted cannot be more: the guard is against offsets that are not its scan) */
-    if (to <= from || to - from > GROUP_BITS)
+    if (to <= from || to - from > GROUP_BITS<DATA>)
         return;
+    const jpn::Tables &t = groupTables<DATA>(own, dTables);
     const u64 firstWord = from >> 5;
     const int nbWords = (int)(((to - 1) >> 5) - firstWord) + 1;
     for (int w = lane; w < nbWords; w += GROUP)
@@ -128,7 +168,7 @@ __global__ __launch_bounds__(GROUP) void k_jpegEmit(const short *__restrict__ co
     {
         const long index = first + lane;
         SharedWriter writer = {piece, (u32)(offsets[index] - (firstWord << 5))};
-        jpn::walkBlock(reinterpret_cast<const short *>(staged + lane * STAGE_PITCH),
+        jpn::walkBlock(t, reinterpret_cast<const short *>(staged + lane * STAGE_PITCH),
                        previousDc(coefficients, index, lumaBlocks), jpn::chromaOf(index, lumaBlocks), writer);
         if (index == nbBlocks - 1)
             if (const int tail = jpn::tailBits(offsets[nbBlocks]))
@@ -151,6 +191,112 @@ __device__ inline u32 waveSum(u32 value)
     for (int step = 1; step < GROUP; step <<= 1)
         value += __shfl_xor(value, step, GROUP);
     return value;
+}
+
+/* ---- optimised tables ---- */
+/* jpn::Counter on counters that other lanes count in too: the group's histogram in LDS, laid out as jpn::Census */
+static_assert(offsetof(jpn::Census, dc) == 0 && offsetof(jpn::Census, ac) == 2 * 12 * sizeof(u32), "dc[2][12], ac[2][256]");
+struct SharedCounter
+{
+    u32 *counts;
+    int chroma;
+    __device__ void dc(int size, int) { atomicAdd(&counts[chroma * 12 + size], 1u); }
+    __device__ void ac(int symbol, int, int) { atomicAdd(&counts[24 + chroma * 256 + symbol], 1u); }
+};
+
+__global__ __launch_bounds__(GROUP) void k_jpegSymbolCounts(const short *__restrict__ coefficients, const int nbBlocks,
+                                                            const int lumaBlocks, u32 *__restrict__ histogram,
+                                                            u32 *__restrict__ flag)
+{
+    __shared__ u32 staged[GROUP * STAGE_PITCH];
+    __shared__ u32 counts[jpn::CENSUS_COUNTERS];
+    const int lane = threadIdx.x;
+    const long first = (long)blockIdx.x * GROUP;
+    const int count = nbBlocks - first < GROUP ? (int)(nbBlocks - first) : GROUP;
+    for (int i = lane; i < jpn::CENSUS_COUNTERS; i += GROUP)
+        counts[i] = 0;
+    stageBlocks(coefficients, first, count, staged); /* (ends in a barrier) */
+    if (lane < count)
+    {
+        const long index = first + lane;
+        SharedCounter counter = {counts, jpn::chromaOf(index, lumaBlocks)};
+        if (!jpn::walkSymbols(reinterpret_cast<const short *>(staged + lane * STAGE_PITCH),
+                              previousDc(coefficients, index, lumaBlocks), counter))
+            atomicOr(flag, 1u);
+    }
+    __syncthreads();
+    for (int i = lane; i < jpn::CENSUS_COUNTERS; i += GROUP)
+        if (const u32 n = counts[i])
+            atomicAdd(&histogram[i], n);
+}
+
+/* one workgroup per table slot (jpn::TABLE_SLOTS of them): `histogram` as jpn::Census to the slot's part of `huffman`
+ * (values behind the last one are zero) and of `tables` */
+__global__ __launch_bounds__(GROUP) void k_jpegOptimiseTables(const u32 *__restrict__ histogram,
+                                                              jpn::Tables *__restrict__ tables,
+                                                              jpn::Huffman *__restrict__ huffman)
+{
+    __shared__ u32 counts[256];
+    __shared__ u32 sorted[jpn::MAX_TABLE_SYMBOLS];
+    __shared__ int numCodes[jpn::MAX_TABLE_SYMBOLS];
+    __shared__ u8 values[256];
+    __shared__ u8 bits[16];
+    const int lane = threadIdx.x;
+    const int slot = blockIdx.x;
+    const int length = jpn::slotLength(slot);
+    const u32 *from = jpn::slotCounts(*reinterpret_cast<const jpn::Census *>(histogram), slot);
+    u32 mine = 0;
+    for (int i = lane; i < 256; i += GROUP)
+    {
+        counts[i] = i < length ? from[i] : 0u;
+        values[i] = 0;
+        mine += counts[i] ? 1u : 0u;
+    }
+    const int n = 1 + (int)waveSum(mine); /* the dummy and the used symbols */
+    __syncthreads();
+    /* the sort: every used symbol to its place behind the dummy; the values are that order reversed, without the dummy */
+    if (lane == 0)
+        sorted[0] = 1;
+    for (int i = lane; i < length; i += GROUP)
+        if (counts[i])
+        {
+            const int at = 1 + jpn::symbolRank(counts, length, i);
+            sorted[at] = counts[i];
+            values[n - 1 - at] = (u8)i;
+        }
+    __syncthreads();
+    if (lane == 0)
+        jpn::bitsOfSorted(sorted, n, numCodes, bits);
+    __syncthreads();
+    if (lane < 16)
+        huffman->bits[slot][lane] = bits[lane];
+    if (lane == 0)
+        huffman->nbValues[slot] = n - 1;
+    u32 *entries = jpn::slotEntries(*tables, slot);
+    for (int i = lane; i < 256; i += GROUP)
+    {
+        huffman->values[slot][i] = values[i];
+        if (i < length)
+            entries[i] = 0;
+    }
+    __syncthreads(); /* (the zeros above and the entries below are different lanes') */
+    /* annex C, as jpn::fillTable: value k's code counts up from the first code of its length */
+    for (int k = lane; k < n - 1; k += GROUP)
+    {
+        u32 code = 0;
+        int firstOfLength = 0;
+        for (int l = 1; l <= jpn::MAX_CODE_BITS; ++l)
+        {
+            const int codes = bits[l - 1];
+            if (k < firstOfLength + codes)
+            {
+                entries[values[k]] = (code + (u32)(k - firstOfLength)) | ((u32)l << 16);
+                break;
+            }
+            code = (code + (u32)codes) << 1;
+            firstOfLength += codes;
+        }
+    }
 }
 
 __global__ __launch_bounds__(GROUP) void k_jpegCountFF(const u32 *__restrict__ stream, const u64 nbBytes,
@@ -198,11 +344,35 @@ hipError_t exclusiveSum(void *temporary, size_t &temporaryBytes, const u64 *in, 
     return hipcub::DeviceScan::ExclusiveSum(temporary, temporaryBytes, in, out, (int)n, stream);
 }
 
+static_assert(sizeof(SolrJpegHuffman) == sizeof(jpn::Huffman) && offsetof(SolrJpegHuffman, values) == offsetof(jpn::Huffman, values) &&
+                  offsetof(SolrJpegHuffman, nbValues) == offsetof(jpn::Huffman, nbValues),
+              "SolrJpegHuffman is jpn::Huffman");
+
+/* census and tables on `stream`: dCoefficients to dHistogram (zeroed here), dTables and dHuffman; a block outside the
+ * domain raises dFlag */
+void launchOptimisedTables(const short *dCoefficients, long nbBlocks, int lumaBlocks, hipStream_t stream, u32 *dHistogram,
+                           jpn::Tables *dTables, jpn::Huffman *dHuffman, u32 *dFlag)
+{
+    using namespace solreng;
+    HIPCHECK(hipMemsetAsync(dHistogram, 0, sizeof(jpn::Census), stream));
+    if (!ok())
+        return;
+    k_jpegSymbolCounts<<<dim3((unsigned)((nbBlocks + GROUP - 1) / GROUP)), dim3(GROUP), 0, stream>>>(
+        dCoefficients, (int)nbBlocks, lumaBlocks, dHistogram, dFlag);
+    HIPCHECK(hipGetLastError());
+    if (!ok())
+        return;
+    k_jpegOptimiseTables<<<dim3(jpn::TABLE_SLOTS), dim3(GROUP), 0, stream>>>(dHistogram, dTables, dHuffman);
+    HIPCHECK(hipGetLastError());
+}
+
 /* The stage on `stream`: dCoefficients (nbBlocks blocks on the device) to the caller's `scan`.  0; or -1 - with the error
  * set for a block outside the domain or a failed call, without for a capacity too small (*nbBytes then says what it
- * takes).  `scan` is written only by the last copy, when everything before it went well. */
+ * takes).  `scan` is written only by the last copy, when everything before it went well.  optimised not null: census and
+ * tables first, the steps with those tables, and *optimised - written only with result 0 - is what the DHTs must say; it
+ * comes with the first read-back, so the call synchronises as often as without */
 int codeBlocks(const char *who, const short *dCoefficients, long nbBlocks, int lumaBlocks, hipStream_t stream,
-               unsigned char *scan, long capacity, long *nbBytes)
+               unsigned char *scan, long capacity, long *nbBytes, jpn::Huffman *optimised)
 {
     using namespace solreng;
     const long nbGroups = (nbBlocks + GROUP - 1) / GROUP;
@@ -216,22 +386,40 @@ int codeBlocks(const char *who, const short *dCoefficients, long nbBlocks, int l
         HIPCHECK(exclusiveSum(nullptr, scanBytes, nullptr, nullptr, nbBlocks + 1, stream));
         if (!ok())
             break;
-        HIPCHECK(hipMalloc((void **)&first, 2 * itemBytes + roundUp(scanBytes) + 256));
+        const size_t tableBytes = optimised ? 2 * roundUp(sizeof(jpn::Tables)) + roundUp(sizeof(jpn::Huffman)) : 0;
+        HIPCHECK(hipMalloc((void **)&first, 2 * itemBytes + roundUp(scanBytes) + 256 + tableBytes));
         if (!ok())
             break;
         u64 *dBits = reinterpret_cast<u64 *>(first), *dOffsets = reinterpret_cast<u64 *>(first + itemBytes);
         unsigned char *dScan = first + 2 * itemBytes;
         u32 *dFlag = reinterpret_cast<u32 *>(first + 2 * itemBytes + roundUp(scanBytes));
+        u32 *dHistogram = reinterpret_cast<u32 *>(first + 2 * itemBytes + roundUp(scanBytes) + 256);
+        jpn::Tables *dTables = reinterpret_cast<jpn::Tables *>(reinterpret_cast<unsigned char *>(dHistogram) +
+                                                               roundUp(sizeof(jpn::Tables)));
+        jpn::Huffman *dHuffman = reinterpret_cast<jpn::Huffman *>(reinterpret_cast<unsigned char *>(dTables) +
+                                                                  roundUp(sizeof(jpn::Tables)));
         HIPCHECK(hipMemsetAsync(dFlag, 0, sizeof(u32), stream));
         if (!ok())
             break;
-        k_jpegBlockBits<<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks, lumaBlocks,
-                                                                              dBits, dFlag);
+        if (optimised)
+        {
+            launchOptimisedTables(dCoefficients, nbBlocks, lumaBlocks, stream, dHistogram, dTables, dHuffman, dFlag);
+            if (!ok())
+                break;
+            k_jpegBlockBits<true><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks,
+                                                                                        lumaBlocks, dBits, dFlag, dTables);
+        }
+        else
+            k_jpegBlockBits<false><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks,
+                                                                                         lumaBlocks, dBits, dFlag, nullptr);
         HIPCHECK(hipGetLastError());
         if (ok())
             HIPCHECK(exclusiveSum(dScan, scanBytes, dBits, dOffsets, nbBlocks + 1, stream));
         u64 totalBits = 0;
         u32 flag = 0;
+        jpn::Huffman fetched;
+        if (ok() && optimised)
+            HIPCHECK(hipMemcpyAsync(&fetched, dHuffman, sizeof(fetched), hipMemcpyDeviceToHost, stream));
         if (ok())
             HIPCHECK(hipMemcpyAsync(&totalBits, dOffsets + nbBlocks, sizeof(u64), hipMemcpyDeviceToHost, stream));
         if (ok())
@@ -265,8 +453,12 @@ int codeBlocks(const char *who, const short *dCoefficients, long nbBlocks, int l
         HIPCHECK(hipMemsetAsync(dStream, 0, streamBytes, stream));
         if (!ok())
             break;
-        k_jpegEmit<<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks, lumaBlocks, dOffsets,
-                                                                         dStream);
+        if (optimised)
+            k_jpegEmit<true><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks, lumaBlocks,
+                                                                                   dOffsets, dStream, dTables);
+        else
+            k_jpegEmit<false><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks,
+                                                                                    lumaBlocks, dOffsets, dStream, nullptr);
         HIPCHECK(hipGetLastError());
         if (!ok())
             break;
@@ -296,6 +488,8 @@ int codeBlocks(const char *who, const short *dCoefficients, long nbBlocks, int l
         if (!ok())
             break;
         gCodedBlocks += (unsigned long long)nbBlocks;
+        if (optimised)
+            *optimised = fetched;
         result = 0;
     } while (false);
     if (!ok())
@@ -315,9 +509,18 @@ bool outputAccepted(const char *who, const unsigned char *scan, long capacity, l
     return false;
 }
 
+/* ... and the optimised entries of theirs */
+bool tablesAccepted(const char *who, const SolrJpegHuffman *tables)
+{
+    if (tables)
+        return true;
+    solreng::setError(-1, (std::string(who) + ": null tables").c_str(), __FILE__, __LINE__);
+    return false;
+}
+
 /* solr_hip_jpeg_blocks_to_scan and solr_hip_rgb_to_jpeg_scan: exactly one of hostBlocks and hostRgb */
 int fromHost(const char *who, const SolrJpegSource *source, const short *hostBlocks, const unsigned char *hostRgb,
-             long nbBlocks, unsigned char *scan, long capacity, long *nbBytes)
+             long nbBlocks, unsigned char *scan, long capacity, long *nbBytes, SolrJpegHuffman *optimised = nullptr)
 {
     using namespace solreng;
     int before = -1;
@@ -349,7 +552,8 @@ int fromHost(const char *who, const SolrJpegSource *source, const short *hostBlo
         else
             HIPCHECK(hipMemcpyAsync(dCoefficients, hostBlocks, coefficientBytes, hipMemcpyHostToDevice, stream));
         if (ok())
-            result = codeBlocks(who, dCoefficients, nbBlocks, source->lumaH * source->lumaV, stream, scan, capacity, nbBytes);
+            result = codeBlocks(who, dCoefficients, nbBlocks, source->lumaH * source->lumaV, stream, scan, capacity, nbBytes,
+                                reinterpret_cast<jpn::Huffman *>(optimised));
         (void)hipStreamSynchronize(stream);
         if (hostRgb && ok() && result == 0)
             countJpegEncodedBlocks(nbBlocks);
@@ -362,12 +566,9 @@ int fromHost(const char *who, const SolrJpegSource *source, const short *hostBlo
         (void)hipSetDevice(before);
     return ok() ? result : -1;
 }
-}
-
-extern "C" {
-
-int solr_hip_jpeg_blocks_to_scan(const SolrJpegSource *source, const short *coefficients, long nbBlocks,
-                                 unsigned char *scan, long capacity, long *nbBytes)
+/* the three entries and their optimised variants: `optimised` null for the standard tables */
+int blocksToScan(const char *who, const SolrJpegSource *source, const short *coefficients, long nbBlocks,
+                 unsigned char *scan, long capacity, long *nbBytes, SolrJpegHuffman *optimised, bool wantsTables)
 {
     using namespace solreng;
     if (!ok())
@@ -375,44 +576,45 @@ int solr_hip_jpeg_blocks_to_scan(const SolrJpegSource *source, const short *coef
     /* ---- arguments: nothing is launched for a call that fails here ---- */
     if (!source || !coefficients)
     {
-        setError(-1, "solr_hip_jpeg_blocks_to_scan: null source or coefficients", __FILE__, __LINE__);
+        setError(-1, (std::string(who) + ": null source or coefficients").c_str(), __FILE__, __LINE__);
         return -1;
     }
     long expected = 0;
-    if (!outputAccepted("solr_hip_jpeg_blocks_to_scan", scan, capacity, nbBytes) ||
-        !jpegSourceAccepted("solr_hip_jpeg_blocks_to_scan", source, &expected))
+    if (!outputAccepted(who, scan, capacity, nbBytes) || (wantsTables && !tablesAccepted(who, optimised)) ||
+        !jpegSourceAccepted(who, source, &expected))
         return -1;
     if (nbBlocks != expected)
     {
-        setError(-1, "solr_hip_jpeg_blocks_to_scan: nbBlocks does not match the image size and sampling", __FILE__,
+        setError(-1, (std::string(who) + ": nbBlocks does not match the image size and sampling").c_str(), __FILE__,
                  __LINE__);
         return -1;
     }
-    return fromHost("solr_hip_jpeg_blocks_to_scan", source, coefficients, nullptr, nbBlocks, scan, capacity, nbBytes);
+    return fromHost(who, source, coefficients, nullptr, nbBlocks, scan, capacity, nbBytes, optimised);
 }
 
-int solr_hip_rgb_to_jpeg_scan(const SolrJpegSource *source, const unsigned char *rgb, unsigned char *scan, long capacity,
-                              long *nbBytes)
+int rgbToScan(const char *who, const SolrJpegSource *source, const unsigned char *rgb, unsigned char *scan, long capacity,
+              long *nbBytes, SolrJpegHuffman *optimised, bool wantsTables)
 {
     using namespace solreng;
     if (!ok())
         return -1;
     if (!source || !rgb)
     {
-        setError(-1, "solr_hip_rgb_to_jpeg_scan: null source or rgb", __FILE__, __LINE__);
+        setError(-1, (std::string(who) + ": null source or rgb").c_str(), __FILE__, __LINE__);
         return -1;
     }
     long nbBlocks = 0;
-    if (!outputAccepted("solr_hip_rgb_to_jpeg_scan", scan, capacity, nbBytes) ||
-        !jpegSourceAccepted("solr_hip_rgb_to_jpeg_scan", source, &nbBlocks))
+    if (!outputAccepted(who, scan, capacity, nbBytes) || (wantsTables && !tablesAccepted(who, optimised)) ||
+        !jpegSourceAccepted(who, source, &nbBlocks))
         return -1;
-    return fromHost("solr_hip_rgb_to_jpeg_scan", source, nullptr, rgb, nbBlocks, scan, capacity, nbBytes);
+    return fromHost(who, source, nullptr, rgb, nbBlocks, scan, capacity, nbBytes, optimised);
 }
 
-int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char *scan, long capacity, long *nbBytes)
+int frameToScan(const char *who, int quality, int lumaH, int lumaV, unsigned char *scan, long capacity, long *nbBytes,
+                SolrJpegHuffman *optimised, bool wantsTables)
 {
     using namespace solreng;
-    if (!ready("solr_hip_frame_to_jpeg_scan"))
+    if (!ready(who))
         return -1;
     /* declined, and no error: a frame in strips or on several devices is not in one image, and before the first frame
      * there is none */
@@ -422,8 +624,8 @@ int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char
         return -1;
     const SolrJpegSource source = {g.width, g.height, lumaH, lumaV, quality, 1, g.frameBufferType != (int)ftRGB ? 1 : 0};
     long nbBlocks = 0;
-    if (!outputAccepted("solr_hip_frame_to_jpeg_scan", scan, capacity, nbBytes) ||
-        !jpegSourceAccepted("solr_hip_frame_to_jpeg_scan", &source, &nbBlocks))
+    if (!outputAccepted(who, scan, capacity, nbBytes) || (wantsTables && !tablesAccepted(who, optimised)) ||
+        !jpegSourceAccepted(who, &source, &nbBlocks))
         return -1;
     HIPCHECK(hipSetDevice(g.device));
     /* behind the frame, on its stream */
@@ -440,8 +642,8 @@ int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char
         launchJpegCoefficients(source, tables, reinterpret_cast<JpegEncodeTables *>(device), image, dCoefficients, nbBlocks,
                                stream);
         if (ok())
-            result = codeBlocks("solr_hip_frame_to_jpeg_scan", dCoefficients, nbBlocks, lumaH * lumaV, stream, scan, capacity,
-                                nbBytes);
+            result = codeBlocks(who, dCoefficients, nbBlocks, lumaH * lumaV, stream, scan, capacity, nbBytes,
+                                reinterpret_cast<jpn::Huffman *>(optimised));
         (void)hipStreamSynchronize(stream);
         if (ok() && result == 0)
             countJpegEncodedBlocks(nbBlocks);
@@ -449,6 +651,151 @@ int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char
     if (device)
         (void)hipFree(device);
     return ok() ? result : -1;
+}
+}
+
+extern "C" {
+
+int solr_hip_jpeg_blocks_to_scan(const SolrJpegSource *source, const short *coefficients, long nbBlocks,
+                                 unsigned char *scan, long capacity, long *nbBytes)
+{
+    return blocksToScan("solr_hip_jpeg_blocks_to_scan", source, coefficients, nbBlocks, scan, capacity, nbBytes, nullptr,
+                        false);
+}
+
+int solr_hip_rgb_to_jpeg_scan(const SolrJpegSource *source, const unsigned char *rgb, unsigned char *scan, long capacity,
+                              long *nbBytes)
+{
+    return rgbToScan("solr_hip_rgb_to_jpeg_scan", source, rgb, scan, capacity, nbBytes, nullptr, false);
+}
+
+int solr_hip_frame_to_jpeg_scan(int quality, int lumaH, int lumaV, unsigned char *scan, long capacity, long *nbBytes)
+{
+    return frameToScan("solr_hip_frame_to_jpeg_scan", quality, lumaH, lumaV, scan, capacity, nbBytes, nullptr, false);
+}
+
+int solr_hip_jpeg_blocks_to_scan_optimised(const SolrJpegSource *source, const short *coefficients, long nbBlocks,
+                                           unsigned char *scan, long capacity, long *nbBytes, SolrJpegHuffman *tables)
+{
+    return blocksToScan("solr_hip_jpeg_blocks_to_scan_optimised", source, coefficients, nbBlocks, scan, capacity, nbBytes,
+                        tables, true);
+}
+
+int solr_hip_rgb_to_jpeg_scan_optimised(const SolrJpegSource *source, const unsigned char *rgb, unsigned char *scan,
+                                        long capacity, long *nbBytes, SolrJpegHuffman *tables)
+{
+    return rgbToScan("solr_hip_rgb_to_jpeg_scan_optimised", source, rgb, scan, capacity, nbBytes, tables, true);
+}
+
+int solr_hip_frame_to_jpeg_scan_optimised(int quality, int lumaH, int lumaV, unsigned char *scan, long capacity,
+                                          long *nbBytes, SolrJpegHuffman *tables)
+{
+    return frameToScan("solr_hip_frame_to_jpeg_scan_optimised", quality, lumaH, lumaV, scan, capacity, nbBytes, tables,
+                       true);
+}
+
+/* ---- the probes of include/solr_hip_probes_jpeg.h ---- */
+namespace
+{
+/* the two kernels of the optimised tables on a stream of their own; exactly one of hostBlocks and hostCounts */
+int probeTables(const char *who, const short *hostBlocks, long nbBlocks, int lumaBlocks, const unsigned int *hostCounts,
+                unsigned int *counts, SolrJpegHuffman *tables)
+{
+    using namespace solreng;
+    int before = -1;
+    if (hipGetDevice(&before) != hipSuccess)
+        before = -1;
+    HIPCHECK(hipSetDevice(solr_hip_get_device()));
+    const size_t blockBytes = hostBlocks ? roundUp((size_t)nbBlocks * 64 * sizeof(short)) : 0;
+    const size_t part = roundUp(sizeof(jpn::Tables));
+    unsigned char *device = nullptr;
+    hipStream_t stream = nullptr;
+    jpn::Census census;
+    jpn::Huffman huffman;
+    u32 flag = 0;
+    if (ok())
+        HIPCHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (ok())
+        HIPCHECK(hipMalloc((void **)&device, blockBytes + 3 * part + 256));
+    if (ok())
+    {
+        short *dBlocks = reinterpret_cast<short *>(device);
+        u32 *dHistogram = reinterpret_cast<u32 *>(device + blockBytes);
+        jpn::Tables *dTables = reinterpret_cast<jpn::Tables *>(device + blockBytes + part);
+        jpn::Huffman *dHuffman = reinterpret_cast<jpn::Huffman *>(device + blockBytes + 2 * part);
+        u32 *dFlag = reinterpret_cast<u32 *>(device + blockBytes + 3 * part);
+        HIPCHECK(hipMemsetAsync(dFlag, 0, sizeof(u32), stream));
+        if (ok() && hostBlocks)
+        {
+            HIPCHECK(hipMemcpyAsync(dBlocks, hostBlocks, (size_t)nbBlocks * 64 * sizeof(short), hipMemcpyHostToDevice, stream));
+            if (ok())
+                launchOptimisedTables(dBlocks, nbBlocks, lumaBlocks, stream, dHistogram, dTables, dHuffman, dFlag);
+        }
+        else if (ok())
+        {
+            HIPCHECK(hipMemcpyAsync(dHistogram, hostCounts, sizeof(jpn::Census), hipMemcpyHostToDevice, stream));
+            if (ok())
+            {
+                k_jpegOptimiseTables<<<dim3(jpn::TABLE_SLOTS), dim3(GROUP), 0, stream>>>(dHistogram, dTables, dHuffman);
+                HIPCHECK(hipGetLastError());
+            }
+        }
+        if (ok())
+            HIPCHECK(hipMemcpyAsync(&census, dHistogram, sizeof(census), hipMemcpyDeviceToHost, stream));
+        if (ok())
+            HIPCHECK(hipMemcpyAsync(&huffman, dHuffman, sizeof(huffman), hipMemcpyDeviceToHost, stream));
+        if (ok())
+            HIPCHECK(hipMemcpyAsync(&flag, dFlag, sizeof(u32), hipMemcpyDeviceToHost, stream));
+        (void)hipStreamSynchronize(stream);
+    }
+    if (device)
+        (void)hipFree(device);
+    if (stream)
+        (void)hipStreamDestroy(stream);
+    if (before >= 0)
+        (void)hipSetDevice(before);
+    if (!ok())
+        return -1;
+    if (flag)
+    {
+        setError(-1, (std::string(who) + ": a block is outside the domain (|DC difference| <= 2047, |AC| <= 1023)").c_str(),
+                 __FILE__, __LINE__);
+        return -1;
+    }
+    if (counts)
+        memcpy(counts, &census, sizeof(census));
+    if (tables)
+        memcpy(tables, &huffman, sizeof(huffman));
+    return 0;
+}
+}
+
+int solr_hip_probe_jpeg_census(const short *coefficients, long nbBlocks, int lumaBlocks, unsigned int *counts)
+{
+    using namespace solreng;
+    if (!ok())
+        return -1;
+    if (!coefficients || !counts || nbBlocks < 1 || nbBlocks > (1L << 24) ||
+        (lumaBlocks != 1 && lumaBlocks != 2 && lumaBlocks != 4))
+    {
+        setError(-1, "solr_hip_probe_jpeg_census: null blocks or counts, a block count outside 1 ... 2^24, or luma blocks "
+                     "per MCU other than 1, 2 or 4", __FILE__, __LINE__);
+        return -1;
+    }
+    return probeTables("solr_hip_probe_jpeg_census", coefficients, nbBlocks, lumaBlocks, nullptr, counts, nullptr);
+}
+
+int solr_hip_probe_jpeg_tables(const unsigned int *counts, SolrJpegHuffman *tables)
+{
+    using namespace solreng;
+    if (!ok())
+        return -1;
+    if (!counts || !tables)
+    {
+        setError(-1, "solr_hip_probe_jpeg_tables: null counts or tables", __FILE__, __LINE__);
+        return -1;
+    }
+    return probeTables("solr_hip_probe_jpeg_tables", nullptr, 0, 0, counts, nullptr, tables);
 }
 
 unsigned long long solr_hip_jpeg_coded_blocks(void)

@@ -11,9 +11,11 @@
 #include "ImageLoader.h"
 #include "JpegWriter.h"
 #include "../csrc/jpeg_encode.h"
+#include "../csrc/jpeg_entropy.h"
 #include "../csrc/iso_surface.h"
 
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 
 #include <algorithm>
@@ -2008,72 +2010,86 @@ int GPUKernel::addMetaballs(const SolrIsoGrid &grid, const float *balls, int nbB
     return (int)triangles.size();
 }
 
+/* the boundary's record of a file's four tables is the header's */
+static_assert(sizeof(SolrJpegHuffman) == sizeof(jpn::Huffman) && offsetof(SolrJpegHuffman, values) == offsetof(jpn::Huffman, values) &&
+                  offsetof(SolrJpegHuffman, nbValues) == offsetof(jpn::Huffman, nbValues),
+              "SolrJpegHuffman is jpn::Huffman");
+
 bool GPUKernel::jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks,
-                         std::vector<unsigned char> &scan)
+                         std::vector<unsigned char> &scan, SolrJpegHuffman *optimised)
 {
     if (!coefficients || !jpegSourceInRange(source) || nbBlocks != jpegBlocksOf(source))
         return false;
-    return JpegWriter::scan(source.lumaH, source.lumaV, coefficients, nbBlocks, scan);
+    return JpegWriter::scan(source.lumaH, source.lumaV, coefficients, nbBlocks, scan,
+                            reinterpret_cast<jpn::Huffman *>(optimised));
 }
 
-bool GPUKernel::jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan)
+bool GPUKernel::jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan,
+                           SolrJpegHuffman *optimised)
 {
     std::vector<short> coefficients;
     return jpegCoefficients(source, rgb, coefficients) &&
-           jpegScan(source, coefficients.data(), (long)(coefficients.size() / 64), scan);
+           jpegScan(source, coefficients.data(), (long)(coefficients.size() / 64), scan, optimised);
 }
 
-bool GPUKernel::jpegScanOfFrame(int, int, int, std::vector<unsigned char> &)
+bool GPUKernel::jpegScanOfFrame(int, int, int, std::vector<unsigned char> &, SolrJpegHuffman *)
 {
     return false;
 }
 
-/* SOI ... SOS of the file `source` describes, the segment, EOI */
+/* SOI ... SOS of the file `source` describes - with the tables the segment was coded with, the standard ones when null -
+ * the segment, EOI.  The header's length depends on the tables, which are known only once the segment is: the segment
+ * is copied behind a header of the right length */
 static void jpegFileAround(const SolrJpegSource &source, const std::vector<unsigned char> &scan,
-                           std::vector<unsigned char> &file)
+                           std::vector<unsigned char> &file, const SolrJpegHuffman *tables = nullptr)
 {
     unsigned short quant[2][64];
     jpe::quantTable(source.quality, 0, quant[0]);
     jpe::quantTable(source.quality, 1, quant[1]);
-    file = JpegWriter::header(source.width, source.height, source.lumaH, source.lumaV, quant);
+    file = JpegWriter::header(source.width, source.height, source.lumaH, source.lumaV, quant,
+                              reinterpret_cast<const jpn::Huffman *>(tables));
     file.insert(file.end(), scan.begin(), scan.end());
     file.push_back(0xFF);
     file.push_back(0xD9);
 }
 
 bool GPUKernel::encodeJpeg(std::vector<unsigned char> &file, const unsigned char *pixels, int width, int height,
-                           int jpegQuality, int lumaH, int lumaV, bool turned, bool swapRedBlue)
+                           int jpegQuality, int lumaH, int lumaV, bool turned, bool swapRedBlue, bool optimise)
 {
     const SolrJpegSource source = {width, height, lumaH, lumaV, jpegQuality, turned ? 1 : 0, swapRedBlue ? 1 : 0};
     if (!pixels || !jpegSourceInRange(source))
         return false;
     std::vector<unsigned char> scan;
-    if (!jpegScanOf(source, pixels, scan))
+    SolrJpegHuffman tables;
+    if (!jpegScanOf(source, pixels, scan, optimise ? &tables : nullptr))
         return false;
-    jpegFileAround(source, scan, file);
+    jpegFileAround(source, scan, file, optimise ? &tables : nullptr);
     return true;
 }
 
 bool GPUKernel::encodeJpeg(const std::string &filename, const unsigned char *pixels, int width, int height,
-                           int jpegQuality, int lumaH, int lumaV, bool turned, bool swapRedBlue)
+                           int jpegQuality, int lumaH, int lumaV, bool turned, bool swapRedBlue, bool optimise)
 {
     std::vector<unsigned char> file;
-    return !filename.empty() && encodeJpeg(file, pixels, width, height, jpegQuality, lumaH, lumaV, turned, swapRedBlue) &&
+    return !filename.empty() &&
+           encodeJpeg(file, pixels, width, height, jpegQuality, lumaH, lumaV, turned, swapRedBlue, optimise) &&
            JpegWriter::writeFile(filename, file);
 }
 
 bool GPUKernel::jpegFileFromCoefficients(std::vector<unsigned char> &file, const short *coefficients, long nbBlocks,
-                                         int width, int height, int jpegQuality, int lumaH, int lumaV)
+                                         int width, int height, int jpegQuality, int lumaH, int lumaV, bool optimise)
 {
     const SolrJpegSource source = {width, height, lumaH, lumaV, jpegQuality, 0, 0};
     std::vector<unsigned char> scan;
-    if (!jpegScan(source, coefficients, nbBlocks, scan))
+    SolrJpegHuffman tables;
+    if (!jpegScan(source, coefficients, nbBlocks, scan, optimise ? &tables : nullptr))
         return false;
-    jpegFileAround(source, scan, file);
+    jpegFileAround(source, scan, file, optimise ? &tables : nullptr);
     return true;
 }
 
-bool GPUKernel::renderJpeg(const float timer, int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &file)
+bool GPUKernel::renderJpeg(const float timer, int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &file,
+                           bool optimise)
 {
     const SolrJpegSource source = {m_sceneInfo.size.x, m_sceneInfo.size.y, lumaH, lumaV, jpegQuality, 1,
                                    m_sceneInfo.frameBufferType != ftRGB ? 1 : 0};
@@ -2086,9 +2102,10 @@ bool GPUKernel::renderJpeg(const float timer, int jpegQuality, int lumaH, int lu
     if (lastError() != 0)
         return false;
     std::vector<unsigned char> scan;
-    if (jpegScanOfFrame(jpegQuality, lumaH, lumaV, scan))
+    SolrJpegHuffman tables;
+    if (jpegScanOfFrame(jpegQuality, lumaH, lumaV, scan, optimise ? &tables : nullptr))
     {
-        jpegFileAround(source, scan, file);
+        jpegFileAround(source, scan, file, optimise ? &tables : nullptr);
         return true;
     }
     if (lastError() != 0)
@@ -2097,7 +2114,8 @@ bool GPUKernel::renderJpeg(const float timer, int jpegQuality, int lumaH, int lu
     flushFrames(); /* with frames in flight the image on show lags behind: wait for this frame's */
     const BitmapBuffer *bitmap = getBitmap();
     return lastError() == 0 && bitmap &&
-           encodeJpeg(file, bitmap, source.width, source.height, jpegQuality, lumaH, lumaV, true, source.swapRedBlue != 0);
+           encodeJpeg(file, bitmap, source.width, source.height, jpegQuality, lumaH, lumaV, true, source.swapRedBlue != 0,
+                      optimise);
 }
 
 /* reference: GPUKernel.cpp:2792-2852; what differs is said in GPUKernel.h */

@@ -664,15 +664,17 @@ public:
     {
         return jpegCoefficients(source, rgb, coefficients);
     }
+    /* optimise (here and below): the file of the reference encoder's two-pass mode - four Huffman tables built for the
+     * picture's own symbols, written in its DHT segments - in place of the standard tables; the same pixels decode from it */
     bool encodeJpeg(const std::string &filename, const unsigned char *pixels, int width, int height, int jpegQuality,
-                    int lumaH, int lumaV, bool turned, bool swapRedBlue);
+                    int lumaH, int lumaV, bool turned, bool swapRedBlue, bool optimise = false);
     /* the same file in memory: the header, the engine's entropy-coded segment (the jpegScanOf hook), EOI */
     bool encodeJpeg(std::vector<unsigned char> &file, const unsigned char *pixels, int width, int height, int jpegQuality,
-                    int lumaH, int lumaV, bool turned, bool swapRedBlue);
+                    int lumaH, int lumaV, bool turned, bool swapRedBlue, bool optimise = false);
     /* the file of coefficient blocks somebody else made, through the engine's entropy stage alone (the jpegScan hook);
      * for the tests, next to JpegWriter::encode */
     bool jpegFileFromCoefficients(std::vector<unsigned char> &file, const short *coefficients, long nbBlocks, int width,
-                                  int height, int jpegQuality, int lumaH, int lumaV);
+                                  int height, int jpegQuality, int lumaH, int lumaV, bool optimise = false);
     /* extension for whoever streams frames: one frame as SolR_RunKernel renders it (render_begin with `timer`), returned
      * as a JPEG file in memory - the file a one-pass screenshot of the same size and settings would be: JPEG quality
      * 1 ... 100, luma sampling 1x1, 2x1 or 2x2, the frame turned, red and blue swapped unless the frame buffer is ftRGB.
@@ -680,7 +682,8 @@ public:
      * the file's bytes; getBitmap() is then NOT refreshed - it stays what it was before the call.  Where the engine
      * declines (no device, frames in flight, strips, several devices) the frame comes back through render_end and is
      * encoded from the host's bitmap: the same bytes.  false: an argument out of range or a failed frame */
-    bool renderJpeg(const float timer, int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &file);
+    bool renderJpeg(const float timer, int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &file,
+                    bool optimise = false);
 
     /* ---------- Scene (GPUKernel.h:208-221) ---------- */
     void setSceneInfo(int width, int height, float transparentColor, int graphicsLevel, float viewDistance,
@@ -929,14 +932,17 @@ protected:
      * completed, no EOI (`scan` is resized).  jpegScan: of nbBlocks coefficient blocks as jpegCoefficients leaves them (of
      * `source` the size and sampling matter); jpegScanOf: of a picture, both stages.  Here: JpegWriter::scan, the header's
      * loops in the decomposed order; false = the arguments are out of range, a block is outside what the standard tables
-     * code, or the engine failed (its error is pending) */
+     * code, or the engine failed (its error is pending).  optimised (here and in jpegScanOfFrame) not null: the segment is
+     * coded with tables built for its own symbols, which come back there for the header */
     virtual bool jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks,
-                          std::vector<unsigned char> &scan);
-    virtual bool jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan);
+                          std::vector<unsigned char> &scan, SolrJpegHuffman *optimised = nullptr);
+    virtual bool jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan,
+                            SolrJpegHuffman *optimised = nullptr);
     /* engine hook of renderJpeg: the frame render_begin has just launched as the entropy-coded segment of its JPEG, taken
      * from the device's image - the frame never reaches the host as pixels, m_bitmap is left alone.  false (here, always):
      * not this way; the caller goes through render_end and encodeJpeg */
-    virtual bool jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan);
+    virtual bool jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan,
+                                 SolrJpegHuffman *optimised = nullptr);
     /* engine hooks: the iso-surface of a field of metaballs (csrc/iso_surface.h).  isoSurface: balls to triangles, cubes in
      * index order (`triangles` is resized); isoField: balls to (N+1)^3 records of {nx, ny, nz, value}; isoTriangles: such
      * a field to triangles - the number the surface has, the first min(count, capacity) written, -1 on failure.  Here:

@@ -331,31 +331,38 @@ static bool jpegScanInto(std::vector<unsigned char> &scan, size_t &capacity, Ent
 }
 
 bool HipKernel::jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks,
-                         std::vector<unsigned char> &scan)
+                         std::vector<unsigned char> &scan, SolrJpegHuffman *optimised)
 {
     if (solr_hip_device_count() < 1)
-        return GPUKernel::jpegScan(source, coefficients, nbBlocks, scan);
+        return GPUKernel::jpegScan(source, coefficients, nbBlocks, scan, optimised);
     return jpegScanInto(scan, m_jpegCapacity, [&](unsigned char *to, long capacity, long *nbBytes) {
-        return solr_hip_jpeg_blocks_to_scan(&source, coefficients, nbBlocks, to, capacity, nbBytes);
+        return optimised ? solr_hip_jpeg_blocks_to_scan_optimised(&source, coefficients, nbBlocks, to, capacity, nbBytes,
+                                                                  optimised)
+                         : solr_hip_jpeg_blocks_to_scan(&source, coefficients, nbBlocks, to, capacity, nbBytes);
     });
 }
 
-bool HipKernel::jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan)
+bool HipKernel::jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan,
+                           SolrJpegHuffman *optimised)
 {
     if (solr_hip_device_count() < 1)
-        return GPUKernel::jpegScanOf(source, rgb, scan);
+        return GPUKernel::jpegScanOf(source, rgb, scan, optimised);
     return jpegScanInto(scan, m_jpegCapacity, [&](unsigned char *to, long capacity, long *nbBytes) {
-        return solr_hip_rgb_to_jpeg_scan(&source, rgb, to, capacity, nbBytes);
+        return optimised ? solr_hip_rgb_to_jpeg_scan_optimised(&source, rgb, to, capacity, nbBytes, optimised)
+                         : solr_hip_rgb_to_jpeg_scan(&source, rgb, to, capacity, nbBytes);
     });
 }
 
-bool HipKernel::jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan)
+bool HipKernel::jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan,
+                                SolrJpegHuffman *optimised)
 {
     /* frames in flight: the image ring has this frame's copy under way and the engine's images alternate - not this way */
     if (!m_deviceInitialized || m_flights > 1)
         return false;
     if (!jpegScanInto(scan, m_jpegCapacity, [&](unsigned char *to, long capacity, long *nbBytes) {
-            return solr_hip_frame_to_jpeg_scan(jpegQuality, lumaH, lumaV, to, capacity, nbBytes);
+            return optimised ? solr_hip_frame_to_jpeg_scan_optimised(jpegQuality, lumaH, lumaV, to, capacity, nbBytes,
+                                                                     optimised)
+                             : solr_hip_frame_to_jpeg_scan(jpegQuality, lumaH, lumaV, to, capacity, nbBytes);
         }))
         return false;
     /* what render_end would have left, but for the image: m_bitmap is not brought up to date, now or when asked */

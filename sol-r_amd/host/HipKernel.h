@@ -95,10 +95,12 @@ protected:
                           std::vector<short> &coefficients) override;
     /* solr_hip_jpeg_blocks_to_scan, solr_hip_rgb_to_jpeg_scan (include/solr_hip.h) where there is a device, the base
      * class's loops where there is none; solr_hip_frame_to_jpeg_scan for a frame rendered one at a time on one device */
-    bool jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks,
-                  std::vector<unsigned char> &scan) override;
-    bool jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan) override;
-    bool jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan) override;
+    bool jpegScan(const SolrJpegSource &source, const short *coefficients, long nbBlocks, std::vector<unsigned char> &scan,
+                  SolrJpegHuffman *optimised = nullptr) override;
+    bool jpegScanOf(const SolrJpegSource &source, const unsigned char *rgb, std::vector<unsigned char> &scan,
+                    SolrJpegHuffman *optimised = nullptr) override;
+    bool jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan,
+                         SolrJpegHuffman *optimised = nullptr) override;
     /* solr_hip_metaballs, solr_hip_iso_field, solr_hip_iso_surface (include/solr_hip.h) where there is a device, the base
      * class's loops where there is none */
     bool isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,

@@ -5,6 +5,7 @@
 #include "JpegWriter.h"
 
 #include <cstdio>
+#include <memory>
 
 #include "../csrc/jpeg_entropy.h"
 
@@ -122,9 +123,20 @@ const HuffmanTable &acTable(int chroma)
     return ac[chroma];
 }
 
-void headerInto(Stream &s, int width, int height, int lumaH, int lumaV, const unsigned short quant[2][64])
+/* the tables of an optimised file, in the order of its DHT segments */
+struct OptimisedTables
 {
-    const HuffmanTable *dc = &dcTable(0), *ac = &acTable(0);
+    HuffmanTable dc[2], ac[2];
+    explicit OptimisedTables(const jpn::Huffman &h)
+        : dc{HuffmanTable(h.bits[0], h.values[0], h.nbValues[0]), HuffmanTable(h.bits[2], h.values[2], h.nbValues[2])},
+          ac{HuffmanTable(h.bits[1], h.values[1], h.nbValues[1]), HuffmanTable(h.bits[3], h.values[3], h.nbValues[3])}
+    {
+    }
+};
+
+void headerInto(Stream &s, int width, int height, int lumaH, int lumaV, const unsigned short quant[2][64],
+                const HuffmanTable *dc, const HuffmanTable *ac)
+{
     /* jpge.cpp:517-525 emit_markers */
     s.marker(0xD8);
     s.marker(0xE0); /* JFIF 1.1, no density unit, aspect 1:1, no thumbnail (:418-434) */
@@ -178,23 +190,49 @@ void headerInto(Stream &s, int width, int height, int lumaH, int lumaV, const un
 }
 
 std::vector<unsigned char> JpegWriter::header(int width, int height, int lumaH, int lumaV,
-                                              const unsigned short quant[2][64])
+                                              const unsigned short quant[2][64], const jpn::Huffman *tables)
 {
     Stream s;
-    headerInto(s, width, height, lumaH, lumaV, quant);
+    if (tables)
+    {
+        const OptimisedTables optimised(*tables);
+        headerInto(s, width, height, lumaH, lumaV, quant, optimised.dc, optimised.ac);
+    }
+    else
+        headerInto(s, width, height, lumaH, lumaV, quant, &dcTable(0), &acTable(0));
     return s.out;
 }
 
 std::vector<unsigned char> JpegWriter::encode(int width, int height, int lumaH, int lumaV,
-                                              const unsigned short quant[2][64], const short *blocks, long nbBlocks)
+                                              const unsigned short quant[2][64], const short *blocks, long nbBlocks,
+                                              bool optimise)
 {
+    const int lumaBlocks = lumaH * lumaV, perMcu = lumaBlocks + 2;
     const HuffmanTable *dc = &dcTable(0), *ac = &acTable(0);
+    std::unique_ptr<OptimisedTables> optimised;
+    jpn::Huffman huffman; /* (the tables point into it) */
+    if (optimise)
+    {
+        /* the first pass (:837-881, :1022-1027): the census with one predictor per component, as the second pass codes */
+        jpn::Census census = {};
+        int lastDc[3] = {0, 0, 0};
+        for (long index = 0; index < nbBlocks; ++index)
+        {
+            const int inMcu = (int)(index % perMcu);
+            const int c = inMcu < lumaBlocks ? 0 : inMcu - lumaBlocks + 1;
+            jpn::blockCensus(blocks + index * 64, lastDc[c], c > 0, census);
+            lastDc[c] = blocks[index * 64];
+        }
+        jpn::optimiseTables(census, huffman);
+        optimised.reset(new OptimisedTables(huffman));
+        dc = optimised->dc;
+        ac = optimised->ac;
+    }
     Stream s;
     s.out.reserve(1024 + (size_t)nbBlocks * 32);
-    headerInto(s, width, height, lumaH, lumaV, quant);
+    headerInto(s, width, height, lumaH, lumaV, quant, dc, ac);
 
     /* the scan: :883-952 */
-    const int lumaBlocks = lumaH * lumaV, perMcu = lumaBlocks + 2;
     int lastDc[3] = {0, 0, 0};
     int inMcu = 0;
     for (long index = 0; index < nbBlocks; ++index)
@@ -236,20 +274,35 @@ std::vector<unsigned char> JpegWriter::encode(int width, int height, int lumaH, 
 }
 
 /* The same segment in the order the device takes (csrc/jpeg_entropy.h): every loop below runs over independent items */
-bool JpegWriter::scan(int lumaH, int lumaV, const short *blocks, long nbBlocks, std::vector<unsigned char> &out)
+bool JpegWriter::scan(int lumaH, int lumaV, const short *blocks, long nbBlocks, std::vector<unsigned char> &out,
+                      jpn::Huffman *optimised)
 {
     const int lumaBlocks = lumaH * lumaV;
     auto previousDc = [&](long index) {
         const long before = jpn::predecessor(index, lumaBlocks);
         return before < 0 ? 0 : (int)blocks[before * 64];
     };
+    /* census, tables: only for an optimised file */
+    jpn::Tables own;
+    jpn::Huffman huffman;
+    if (optimised)
+    {
+        jpn::Census census = {};
+        for (long i = 0; i < nbBlocks; ++i)
+            jpn::blockCensus(blocks + i * 64, previousDc(i), jpn::chromaOf(i, lumaBlocks), census);
+        jpn::optimiseTables(census, huffman);
+        jpn::tablesOf(huffman, own);
+    }
+    const jpn::Tables &t = optimised ? own : jpn::tables();
     /* bits */
     std::vector<jpn::u32> bits((size_t)nbBlocks);
     bool inside = true;
     for (long i = 0; i < nbBlocks; ++i)
-        inside &= jpn::blockBits(blocks + i * 64, previousDc(i), jpn::chromaOf(i, lumaBlocks), &bits[(size_t)i]);
+        inside &= jpn::blockBits(t, blocks + i * 64, previousDc(i), jpn::chromaOf(i, lumaBlocks), &bits[(size_t)i]);
     if (!inside)
         return false;
+    if (optimised)
+        *optimised = huffman;
     /* prefix */
     std::vector<jpn::u64> offsets((size_t)nbBlocks + 1);
     jpn::exclusiveSum(bits.data(), nbBlocks, offsets.data());
@@ -257,7 +310,7 @@ bool JpegWriter::scan(int lumaH, int lumaV, const short *blocks, long nbBlocks, 
     /* emit, and the tail */
     std::vector<jpn::u32> words((size_t)jpn::streamWords(totalBits), 0u);
     for (long i = 0; i < nbBlocks; ++i)
-        jpn::blockEmit(blocks + i * 64, previousDc(i), jpn::chromaOf(i, lumaBlocks), offsets[(size_t)i], words.data());
+        jpn::blockEmit(t, blocks + i * 64, previousDc(i), jpn::chromaOf(i, lumaBlocks), offsets[(size_t)i], words.data());
     if (const int tail = jpn::tailBits(totalBits))
     {
         jpn::WordWriter writer = {words.data(), totalBits};

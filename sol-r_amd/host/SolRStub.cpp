@@ -198,15 +198,28 @@ int SolR_GenerateScreenshot(char *filename, int width, int height, int quality)
 
 /* Extension: the screenshot's encoder alone on the caller's pixels (GPUKernel::encodeJpeg): 0, or -1 when an argument is
  * out of range - nothing is written then - or the file could not be written */
-int SolRx_EncodeJpeg(const char *filename, const unsigned char *pixels, int width, int height, int jpegQuality,
-                     int lumaH, int lumaV, int turned, int swapRedBlue)
+static int encodeJpegFile(const char *filename, const unsigned char *pixels, int width, int height, int jpegQuality,
+                          int lumaH, int lumaV, int turned, int swapRedBlue, bool optimise)
 {
     if (!filename || !pixels)
         return -1;
     return SingletonKernel::kernel()->encodeJpeg(filename, pixels, width, height, jpegQuality, lumaH, lumaV,
-                                                 turned != 0, swapRedBlue != 0)
+                                                 turned != 0, swapRedBlue != 0, optimise)
                ? 0
                : -1;
+}
+
+int SolRx_EncodeJpeg(const char *filename, const unsigned char *pixels, int width, int height, int jpegQuality,
+                     int lumaH, int lumaV, int turned, int swapRedBlue)
+{
+    return encodeJpegFile(filename, pixels, width, height, jpegQuality, lumaH, lumaV, turned, swapRedBlue, false);
+}
+
+/* ... with optimised Huffman tables (GPUKernel.h, encodeJpeg) */
+int SolRx_EncodeJpegOptimised(const char *filename, const unsigned char *pixels, int width, int height, int jpegQuality,
+                              int lumaH, int lumaV, int turned, int swapRedBlue)
+{
+    return encodeJpegFile(filename, pixels, width, height, jpegQuality, lumaH, lumaV, turned, swapRedBlue, true);
 }
 
 /* Extensions for the tests of the encoder's two halves.  SolRx_JpegCoefficients: the engine's pixel stage alone
@@ -226,8 +239,8 @@ int SolRx_JpegCoefficients(const unsigned char *pixels, int width, int height, i
     return 0;
 }
 
-int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, long nbBlocks, int width, int height,
-                               int jpegQuality, int lumaH, int lumaV)
+static int jpegFromCoefficients(const char *filename, const short *coefficients, long nbBlocks, int width, int height,
+                                int jpegQuality, int lumaH, int lumaV, bool optimise)
 {
     if (!filename || !coefficients || width < 1 || height < 1 || jpegQuality < 1 || jpegQuality > 100 ||
         !jpe::samplingSupported(lumaH, lumaV) ||
@@ -238,9 +251,21 @@ int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, 
     jpe::quantTable(jpegQuality, 0, quant[0]);
     jpe::quantTable(jpegQuality, 1, quant[1]);
     return solr::JpegWriter::writeFile(filename, solr::JpegWriter::encode(width, height, lumaH, lumaV, quant,
-                                                                          coefficients, nbBlocks))
+                                                                          coefficients, nbBlocks, optimise))
                ? 0
                : -1;
+}
+
+int SolRx_JpegFromCoefficients(const char *filename, const short *coefficients, long nbBlocks, int width, int height,
+                               int jpegQuality, int lumaH, int lumaV)
+{
+    return jpegFromCoefficients(filename, coefficients, nbBlocks, width, height, jpegQuality, lumaH, lumaV, false);
+}
+
+int SolRx_JpegFromCoefficientsOptimised(const char *filename, const short *coefficients, long nbBlocks, int width,
+                                        int height, int jpegQuality, int lumaH, int lumaV)
+{
+    return jpegFromCoefficients(filename, coefficients, nbBlocks, width, height, jpegQuality, lumaH, lumaV, true);
 }
 
 /* a file in memory into the caller's buffer: 0; -1 with *nbBytes = the size needed when it does not fit (nothing is
@@ -257,8 +282,8 @@ static int jpegFileOut(const std::vector<unsigned char> &bytes, unsigned char *f
 /* Extension: the file of SolRx_JpegFromCoefficients in memory, its entropy-coded segment by the engine's entropy stage
  * (GPUKernel::jpegFileFromCoefficients: the device's kernels, or the same steps in loops).  -1 with *nbBytes = 0: an
  * argument out of range, a block outside what the standard tables code, or the engine failed */
-int SolRx_JpegFileFromCoefficients(const short *coefficients, long nbBlocks, int width, int height, int jpegQuality,
-                                   int lumaH, int lumaV, unsigned char *file, long capacity, long *nbBytes)
+static int jpegFileFromCoefficients(const short *coefficients, long nbBlocks, int width, int height, int jpegQuality,
+                                    int lumaH, int lumaV, unsigned char *file, long capacity, long *nbBytes, bool optimise)
 {
     if (!nbBytes)
         return -1;
@@ -266,16 +291,31 @@ int SolRx_JpegFileFromCoefficients(const short *coefficients, long nbBlocks, int
     std::vector<unsigned char> bytes;
     if (!coefficients || !file || capacity < 0 ||
         !SingletonKernel::kernel()->jpegFileFromCoefficients(bytes, coefficients, nbBlocks, width, height, jpegQuality,
-                                                             lumaH, lumaV))
+                                                             lumaH, lumaV, optimise))
         return -1;
     return jpegFileOut(bytes, file, capacity, nbBytes);
+}
+
+int SolRx_JpegFileFromCoefficients(const short *coefficients, long nbBlocks, int width, int height, int jpegQuality,
+                                   int lumaH, int lumaV, unsigned char *file, long capacity, long *nbBytes)
+{
+    return jpegFileFromCoefficients(coefficients, nbBlocks, width, height, jpegQuality, lumaH, lumaV, file, capacity,
+                                    nbBytes, false);
+}
+
+int SolRx_JpegFileFromCoefficientsOptimised(const short *coefficients, long nbBlocks, int width, int height,
+                                            int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                                            long *nbBytes)
+{
+    return jpegFileFromCoefficients(coefficients, nbBlocks, width, height, jpegQuality, lumaH, lumaV, file, capacity,
+                                    nbBytes, true);
 }
 
 /* Extension: one frame as SolR_RunKernel renders it, delivered as a JPEG file in memory (GPUKernel::renderJpeg): with
  * the HIP engine the frame is coded on the device and only the file crosses to the host; SolRx_GetBitmap() is not
  * refreshed.  A file that does not fit is not kept: the next call renders the next frame */
-int SolRx_RenderJpeg(double timer, int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
-                     long *nbBytes)
+static int renderJpeg(double timer, int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                      long *nbBytes, bool optimise)
 {
     if (!nbBytes)
         return -1;
@@ -286,9 +326,48 @@ int SolRx_RenderJpeg(double timer, int jpegQuality, int lumaH, int lumaV, unsign
     kernel->setSceneInfo(gSceneInfoStub);
     kernel->setPostProcessingInfo(gPostProcessingInfoStub);
     std::vector<unsigned char> bytes;
-    if (!kernel->renderJpeg(static_cast<float>(timer), jpegQuality, lumaH, lumaV, bytes))
+    if (!kernel->renderJpeg(static_cast<float>(timer), jpegQuality, lumaH, lumaV, bytes, optimise))
         return -1;
     return jpegFileOut(bytes, file, capacity, nbBytes);
+}
+
+int SolRx_RenderJpeg(double timer, int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                     long *nbBytes)
+{
+    return renderJpeg(timer, jpegQuality, lumaH, lumaV, file, capacity, nbBytes, false);
+}
+
+int SolRx_RenderJpegOptimised(double timer, int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                              long *nbBytes)
+{
+    return renderJpeg(timer, jpegQuality, lumaH, lumaV, file, capacity, nbBytes, true);
+}
+
+/* Extensions for the tests of the optimised tables (csrc/jpeg_entropy.h): the table builder on a histogram of the
+ * caller's; the census of the caller's blocks, in the order of jpn::Census */
+int SolRx_JpegOptimiseTable(const unsigned int *counts, int len, unsigned char *bits, unsigned char *values)
+{
+    if (!counts || !bits || !values || len < 1 || len > 256)
+        return -1;
+    return jpn::optimiseTable(counts, len, bits, values);
+}
+
+int SolRx_JpegCensus(const short *coefficients, long nbBlocks, int lumaBlocks, unsigned int *counts)
+{
+    if (!coefficients || !counts || nbBlocks < 0 || (lumaBlocks != 1 && lumaBlocks != 2 && lumaBlocks != 4))
+        return -1;
+    jpn::Census census = {};
+    bool inside = true;
+    for (long i = 0; i < nbBlocks; ++i)
+    {
+        const long before = jpn::predecessor(i, lumaBlocks);
+        inside &= jpn::blockCensus(coefficients + i * 64, before < 0 ? 0 : (int)coefficients[before * 64],
+                                   jpn::chromaOf(i, lumaBlocks), census);
+    }
+    if (!inside)
+        return -1;
+    memcpy(counts, &census, sizeof(census));
+    return 0;
 }
 
 /* Extensions for the tests of csrc/jpeg_entropy.h: its granularities {blocks per workgroup, bytes per stuffing chunk};

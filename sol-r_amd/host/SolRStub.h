@@ -161,6 +161,26 @@ int SolRx_RenderJpeg(double timer, int jpegQuality, int lumaH, int lumaV, unsign
  * (csrc/jpeg_entropy.h: kernels with the HIP engine, loops without a device); same returns */
 int SolRx_JpegFileFromCoefficients(const short *coefficients, long nbBlocks, int width, int height, int jpegQuality,
                                    int lumaH, int lumaV, unsigned char *file, long capacity, long *nbBytes);
+/* SolRx_EncodeJpeg, SolRx_RenderJpeg and SolRx_JpegFileFromCoefficients with optimised Huffman tables: the file of the
+ * reference encoder's two-pass mode - four tables built for the picture's own symbols (csrc/jpeg_entropy.h, optimiseTable;
+ * with the HIP engine counted and built on the device) in its DHT segments - which decodes to the same pixels and is
+ * smaller.  Same arguments and returns */
+int SolRx_EncodeJpegOptimised(const char *filename, const unsigned char *pixels, int width, int height, int jpegQuality,
+                              int lumaH, int lumaV, int turned, int swapRedBlue);
+int SolRx_RenderJpegOptimised(double timer, int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                              long *nbBytes);
+int SolRx_JpegFileFromCoefficientsOptimised(const short *coefficients, long nbBlocks, int width, int height,
+                                            int jpegQuality, int lumaH, int lumaV, unsigned char *file, long capacity,
+                                            long *nbBytes);
+/* the host's table builder: counts[0 ... len - 1] (len 1 ... 256) to bits[16] and values[len]; returns the number of
+ * values, or -1 for arguments out of range.  SolRx_JpegCensus: the symbols of nbBlocks blocks with lumaBlocks (1, 2 or 4)
+ * luma blocks per MCU, added up in counts[536] - DC luma 12, DC chroma 12, AC luma 256, AC chroma 256; 0, or -1 when a
+ * block is outside the domain (nothing written).  SolRx_JpegEncodeTwoPass: the one-pass bit-buffer writer
+ * (JpegWriter::encode) in its optimised mode, to a file - next to SolRx_JpegFromCoefficients */
+int SolRx_JpegOptimiseTable(const unsigned int *counts, int len, unsigned char *bits, unsigned char *values);
+int SolRx_JpegCensus(const short *coefficients, long nbBlocks, int lumaBlocks, unsigned int *counts);
+int SolRx_JpegFromCoefficientsOptimised(const char *filename, const short *coefficients, long nbBlocks, int width,
+                                        int height, int jpegQuality, int lumaH, int lumaV);
 /* csrc/jpeg_entropy.h for the tests (SolRStub.cpp) */
 void SolRx_JpegEntropyGranularity(int out[2]);
 void SolRx_JpegEntropyPrefix(const unsigned int *lengths, long n, unsigned long long *offsets);
