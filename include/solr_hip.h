@@ -367,6 +367,41 @@ int solr_hip_rgb_to_jpeg_scan_optimised(const SolrJpegSource *source, const unsi
 int solr_hip_frame_to_jpeg_scan_optimised(int quality, int lumaH, int lumaV, unsigned char *scan, long capacity,
                                           long *nbBytes, SolrJpegHuffman *tables);
 
+/* JPEG frames in flight: a frame is submitted for delivery as a JPEG and collected later; nothing waits for the device in
+ * between.  The steps are those of the entries above on resident buffers - four slots, the most frames in flight, each
+ * allocated at its first use for a frame size and sampling and kept until reshape_scene, finalize_scene or a frame of more
+ * blocks.  A slot is sized for the worst frame any table of 16-bit codes allows (1665 bits a block and seven: at
+ * 1920 x 1080, 2x2, 10.2 MB unstuffed and 20.4 MB stuffed, 38.3 MB a slot with the blocks and the items, 153 MB for
+ * four), so no frame overflows it; launches are sized by the number of blocks, and one wave on the device turns the prefix
+ * sum's total into the extents the later steps read.
+ *   solr_hip_frame_to_jpeg_async   behind the frame rendered last, on its stream: the pixel stage from that frame's device
+ *                  image (turned, first and third channel swapped unless the frame buffer is ftRGB), every entropy step, the
+ *                  read-back of a small record (flag, total bits, size, the optimised tables), an event.  optimised != 0:
+ *                  with tables built for the frame.  Returns a ticket >= 0.  Waits for nothing, and allocates nothing once
+ *                  the slot exists.  The argument checks (-1, error set) and the declines (strips, several devices, no frame
+ *                  yet: -1, no error, nothing launched) are those of solr_hip_frame_to_jpeg_scan
+ *   solr_hip_jpeg_wait   waits for that ticket's event alone and copies exactly the segment's bytes to `scan`; a ticket of
+ *                  an optimised submission also writes `tables` (not null then).  Capacity too small: -1 with the size in
+ *                  *nbBytes, no error, nothing written - and the ticket stays good: a second wait with room succeeds
+ *                  without another frame.  A ticket may be waited for any number of times until three more have been
+ *                  handed out; it carries its generation, and a stale or never-issued one gives -1 with the error set,
+ *                  never another frame's bytes.  A block outside the domain: -1, error set, `scan` untouched (every step of
+ *                  that ticket behind the plan wrote nothing).  solr_hip_jpeg_coded_blocks and
+ *                  solr_hip_jpeg_encoded_blocks advance at a ticket's first successful wait
+ *   solr_hip_jpeg_stream_offered   1 when solr_hip_frame_to_jpeg_async would take a frame of this engine as it is set up
+ *                  (initialised, one device, no strip), else 0: a host decides by it before it renders
+ *   solr_hip_jpeg_stream_stats   out[0] tickets issued, out[1] allocations the pipeline made (a slot is one device
+ *                  allocation and one page-locked record), out[2] host waits made while submitting - 0: a slot that is made
+ *                  anew for a frame of more blocks sets its old memory aside until its last use is through, asked and
+ *                  not waited for; only more than eight such at once would be waited for, and counted - out[3] bytes
+ *                  delivered by first waits.  Since the library was loaded.
+ * A slot's next use may run on another flight's stream: it is ordered behind the slot's event (hipStreamWaitEvent).
+ * The synchronous entries above are as they were, with frames in flight too. */
+int solr_hip_frame_to_jpeg_async(int quality, int lumaH, int lumaV, int optimised);
+int solr_hip_jpeg_wait(int ticket, unsigned char *scan, long capacity, long *nbBytes, SolrJpegHuffman *tables);
+int solr_hip_jpeg_stream_offered(void);
+void solr_hip_jpeg_stream_stats(unsigned long long out[4]);
+
 /* The iso-surface of a field of metaballs as triangles, on the device (sol-r_amd/csrc/solr_iso.hip; the arithmetic is
  * sol-r_amd/csrc/iso_surface.h, that of the reference's apps/scenes/animation/MetaballsScene.cpp, in IEEE binary32 in
  * source order; the host-only engine runs the same header in loops and gives the same bits).

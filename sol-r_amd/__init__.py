@@ -337,8 +337,14 @@ def _declare_hip(L):
     L.solr_hip_frame_to_jpeg_scan_optimised.argtypes = L.solr_hip_frame_to_jpeg_scan.argtypes + [P(JpegHuffman)]
     L.solr_hip_probe_jpeg_census.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p]
     L.solr_hip_probe_jpeg_tables.argtypes = [C.c_void_p, P(JpegHuffman)]
+    L.solr_hip_frame_to_jpeg_async.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.solr_hip_jpeg_wait.argtypes = [C.c_int, C.c_void_p, C.c_long, P(C.c_long), P(JpegHuffman)]
+    L.solr_hip_jpeg_stream_stats.argtypes = [P(C.c_ulonglong)]
+    L.solr_hip_jpeg_stream_stats.restype = None
+    L.solr_hip_probe_jpeg_stream_blocks.argtypes = [P(JpegSource), C.c_void_p, C.c_long, C.c_int]
     for name in ("jpeg_blocks_to_scan_optimised", "rgb_to_jpeg_scan_optimised", "frame_to_jpeg_scan_optimised",
-                 "probe_jpeg_census", "probe_jpeg_tables"):
+                 "probe_jpeg_census", "probe_jpeg_tables", "frame_to_jpeg_async", "jpeg_wait", "jpeg_stream_offered",
+                 "probe_jpeg_stream_blocks"):
         getattr(L, "solr_hip_" + name).restype = C.c_int
     L.solr_hip_iso_field.argtypes = [P(IsoGrid), C.c_void_p, C.c_int, C.c_void_p]
     L.solr_hip_iso_field.restype = C.c_int
@@ -399,6 +405,14 @@ def _declare_host(L):
     L.SolRx_JpegFromCoefficientsOptimised.argtypes = [C.c_char_p, C.c_void_p, C.c_long, i, i, i, i, i]
     L.SolRx_JpegOptimiseTable.argtypes = [C.c_void_p, i, C.c_void_p, C.c_void_p]
     L.SolRx_JpegCensus.argtypes = [C.c_void_p, C.c_long, i, C.c_void_p]
+    L.SolRx_RenderJpegBegin.argtypes = [d, i, i, i, i]
+    L.SolRx_RenderJpegEnd.argtypes = [i, C.c_void_p, C.c_long, P(C.c_long)]
+    L.SolRx_RenderJpegTicketError.argtypes = [C.c_char_p, i]
+    L.SolRx_JpegParkPixels.argtypes = [C.c_void_p, i, i, i, i, i, i, i]
+    L.SolRx_JpegEntropyPlan.argtypes = [C.c_ulonglong, i, C.c_long, P(C.c_ulonglong)]
+    L.SolRx_JpegEntropyPlan.restype = None
+    L.SolRx_JpegEntropyStreamSizes.argtypes = [C.c_ulonglong, P(C.c_ulonglong)]
+    L.SolRx_JpegEntropyStreamSizes.restype = None
     L.SolRx_JpegEntropyGranularity.argtypes = [P(i)]
     L.SolRx_JpegEntropyGranularity.restype = None
     L.SolRx_JpegEntropyPrefix.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
@@ -954,6 +968,62 @@ class Kernel:
         entry = self.L.SolRx_RenderJpegOptimised if optimise else self.L.SolRx_RenderJpeg
         return self._jpeg_file(lambda to, n, size: entry(0.0, quality, sampling[0], sampling[1], to, n, size),
                                "SolRx_RenderJpegOptimised" if optimise else "SolRx_RenderJpeg", room)
+
+    def render_jpeg_begin(self, quality=85, sampling=(2, 2), optimise=False, **scene_info):
+        """The next frame rendered and submitted for delivery as a JPEG file (SolRx_RenderJpegBegin): a ticket for
+        render_jpeg_end.  With the HIP engine nothing waits for the device here - the frame takes the next flight of
+        SolRx_SetFramesInFlight(n), is coded on the device behind its renderer and comes to the host as a file only;
+        frames in flight are not flushed and the host bitmap is not refreshed.  Where the engine declines (no device,
+        strips, several devices) the frame is rendered and encoded at once and kept under the ticket.  A ticket stays good
+        until three more have been handed out."""
+        if scene_info:
+            self.set_scene_info(**scene_info)
+        ticket = self.L.SolRx_RenderJpegBegin(0.0, quality, sampling[0], sampling[1], int(bool(optimise)))
+        if ticket < 0:
+            text = C.create_string_buffer(512)
+            if self.L.SolRx_LastError(text, 512) != 0:
+                raise SolrError("SolRx_RenderJpegBegin failed: %s" % text.value.decode())
+            raise SolrError("SolRx_RenderJpegBegin refused its arguments (out of range)")
+        return ticket
+
+    def render_jpeg_end(self, ticket, room=None):
+        """The bytes of the JPEG file of the frame render_jpeg_begin returned `ticket` for (SolRx_RenderJpegEnd): waits
+        for that frame alone.  A file larger than the first buffer costs a second call with the size the first one
+        reported - not a second frame: the ticket stays good."""
+        if room is None:
+            room = max(1 << 16, self.info["width"] * self.info["height"] // 2)
+        for _ in range(2):
+            buf = np.empty(room, np.uint8)
+            size = C.c_long(0)
+            if self.L.SolRx_RenderJpegEnd(ticket, buf.ctypes.data, room, C.byref(size)) == 0:
+                return buf[:size.value].tobytes()
+            if size.value <= room:
+                break
+            room = size.value
+        text = C.create_string_buffer(512)
+        if self.L.SolRx_RenderJpegTicketError(text, 512) != 0 and not self.L.SolRx_LastError(None, 0):
+            raise SolrError("SolRx_RenderJpegEnd: %s" % text.value.decode())
+        if self.L.SolRx_LastError(text, 512) != 0:
+            raise SolrError("SolRx_RenderJpegEnd failed: %s" % text.value.decode())
+        raise SolrError("SolRx_RenderJpegEnd refused its arguments")
+
+    def jpeg_stream(self, frames, step=None, depth=None, **jpeg):
+        """A generator over `frames` JPEG files in order, `depth` frames submitted ahead of the one that is collected
+        (render_jpeg_begin / render_jpeg_end): depth defaults to the frames in flight (SolRx_SetFramesInFlight) and is
+        clamped to 1 ... 4, the tickets that stay good.  step(i), when given, is called before frame i is submitted: the
+        place to move the camera or the scene.  **jpeg goes to render_jpeg_begin (quality, sampling, optimise)."""
+        if depth is None:
+            depth = self.L.SolRx_GetFramesInFlight()
+        depth = max(1, min(int(depth), 4))
+        tickets = []
+        for i in range(frames):
+            if step is not None:
+                step(i)
+            tickets.append(self.render_jpeg_begin(**jpeg))
+            if len(tickets) >= depth:
+                yield self.render_jpeg_end(tickets.pop(0))
+        while tickets:
+            yield self.render_jpeg_end(tickets.pop(0))
 
     def jpeg_from_coefficients(self, blocks, width, height, quality=85, sampling=(2, 2), optimise=False):
         """The bytes of the JPEG file of quantised coefficient `blocks` (n, 64) int16 in MCU and zigzag order, coded by

@@ -12,8 +12,8 @@
  * Randoms and SceneFacts (the resident scene, cut by who writes them; what a request on it changes: RequestKind and
  * Scene::requestServed, how many an engine has served: Engine::served), KernelTimer, WalkRecording, TileSchedule (the
  * cost-ordered launch), Flight (a frame in flight: its stream and per-pixel buffers; Engine::flight[0] is the one of a
- * process that renders one frame at a time), CopyLane (the device's part of the pipelined read-back) and ImageStreaming (a
- * frame read back in bands); ImageRing - the page-locked host images of the pipelined read-back and their tickets - exists
+ * process that renders one frame at a time), CopyLane (the device's part of the pipelined read-back), ImageStreaming (a
+ * frame read back in bands) and JpegStream with JpegSlot (JPEG frames in flight: resident buffers and tickets); ImageRing - the page-locked host images of the pipelined read-back and their tickets - exists
  * once per process (gImageRing), whatever the number of
  * engines.  gfx950 only.
  */
@@ -929,6 +929,55 @@ struct WalkRecording
     }
 };
 
+/* JPEG frames in flight (solr_jpeg_entropy.hip; solr_hip_frame_to_jpeg_async, solr_hip_jpeg_wait): a slot is everything
+ * one frame's JPEG takes on the device, allocated at the first use for a number of blocks and kept - until reshape_scene,
+ * finalize_scene or a frame of more blocks - so that a submission allocates nothing and waits for nothing.  One device
+ * allocation, cut into: the pixel stage's tables and the coefficient blocks; the bit items and their offsets; hipcub's
+ * temporaries for both scans; the unstuffed stream, the chunks' 0xFF counts and their offsets, the stuffed output (stream
+ * and output sized for the worst frame the tables allow: jpn::maxStreamBytes, jpn::maxStuffedBytes - nothing overflows);
+ * histogram and tables of the optimised mode; and the small record the steps hand each other, whose page-locked host copy
+ * is all that comes back with the event.  Tickets carry their generation as the image ring's do. */
+const int JPEG_SLOTS = MAX_FLIGHTS;
+struct JpegSlot
+{
+    DeviceBuffer block;
+    long capacityBlocks = 0;                   /* coefficient blocks the cuts below were made for */
+    size_t scanBytes = 0, chunkScanBytes = 0;  /* hipcub's temporaries */
+    size_t streamBytes = 0;                    /* of the unstuffed stream's buffer */
+    unsigned char *encodeTables = nullptr, *coefficients = nullptr, *bits = nullptr, *offsets = nullptr, *scanTemp = nullptr,
+                  *stream = nullptr, *counts = nullptr, *before = nullptr, *chunkScanTemp = nullptr, *out = nullptr,
+                  *histogram = nullptr, *tables = nullptr, *record = nullptr;
+    void *hostRecord = nullptr; /* page-locked: flag, total bits, stuffed size, the optimised tables */
+    hipEvent_t done = nullptr;  /* behind the read-back of the record */
+    bool used = false;          /* `done` has been recorded */
+    bool clean = false;         /* the stream's buffer is zero once the work before `done` is through */
+    long serial = -1;           /* of the ticket that holds the slot, -1: none */
+    long nbBlocks = 0;
+    bool optimised = false, fromFrame = false, collected = false;
+};
+/* what a slot held before it was made anew for a frame of more blocks: given back once `done` has come (asked, never
+ * waited for, by the submissions that follow; waited for by JpegStream::release) */
+struct JpegRetired
+{
+    DeviceBuffer block;
+    void *hostRecord = nullptr;
+    hipEvent_t done = nullptr;
+};
+struct JpegStream
+{
+    JpegSlot slot[JPEG_SLOTS];
+    std::vector<JpegRetired> retired;
+    static const size_t RETIRED_MOST = 2 * JPEG_SLOTS; /* beyond that a submission waits for the oldest, and counts it */
+    long issued = 0;                    /* tickets handed out since the library was loaded: never reset */
+    hipStream_t probeStream = nullptr;  /* solr_hip_probe_jpeg_stream_blocks uploads and runs here */
+    hipStream_t copyStream = nullptr;   /* solr_hip_jpeg_wait's copy of the segment */
+    unsigned long long allocations = 0, hostWaits = 0, bytesDelivered = 0;
+    /* a ticket is (serial mod TICKET_PERIOD) * JPEG_SLOTS + slot, the slot serial mod JPEG_SLOTS (ImageRing::ticketOf) */
+    static const long TICKET_PERIOD = ((long)0x7fffffff / JPEG_SLOTS / JPEG_SLOTS - 1) * JPEG_SLOTS;
+    static int ticketOf(long serial) { return (int)((serial % TICKET_PERIOD) * JPEG_SLOTS + serial % JPEG_SLOTS); }
+    void release(); /* every slot's last use waited for, its memory given back, its ticket void (solr_jpeg_entropy.hip) */
+};
+
 struct Engine
 {
     bool initialized = false;
@@ -988,6 +1037,7 @@ struct Engine
 
     CopyLane copyLane;        /* this device's part of the pipelined read-back (the ring of host images: gImageRing) */
     ImageStreaming streaming; /* the read-back of a frame taken one at a time, in bands */
+    JpegStream jpeg;          /* JPEG frames in flight: the resident slots and their tickets */
     /* the reciprocal of tilesX that was verified for a frame geometry (renderImpl) */
     int tileCheckedX = 0, tileCheckedTiles = 0, tileCheckedShift = 0;
     unsigned tileCheckedMagic = 0;

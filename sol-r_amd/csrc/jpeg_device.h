@@ -27,6 +27,10 @@ bool jpegSourceAccepted(const char *who, const SolrJpegSource *source, long *nbB
  * it must live until the stream has been waited for */
 void launchJpegCoefficients(const SolrJpegSource &source, JpegEncodeTables &tables, JpegEncodeTables *dTables,
                             const unsigned char *dRgb, short *dCoefficients, long nbBlocks, hipStream_t stream);
+/* The same for a caller that does not wait (solr_hip_frame_to_jpeg_async): the tables travel to dTables as a kernel's
+ * argument (k_jpegPutTables), so nothing of the host's has to outlive the call */
+void launchJpegCoefficientsResident(const SolrJpegSource &source, JpegEncodeTables *dTables, const unsigned char *dRgb,
+                                    short *dCoefficients, long nbBlocks, hipStream_t stream);
 /* ... and the caller counts the blocks (solr_hip_jpeg_encoded_blocks) once the call they were made for has delivered: a
  * call that only found out how large its result is, and is made again with room for it, counts once */
 void countJpegEncodedBlocks(long nbBlocks);

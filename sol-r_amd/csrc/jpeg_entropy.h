@@ -566,6 +566,74 @@ JPE_HD inline int bytesOfWord(u64 index, u64 nbBytes)
     return from >= nbBytes ? 0 : (nbBytes - from < 4u ? (int)(nbBytes - from) : 4);
 }
 
+/* ---- the plan of a resident pipeline ---------------------------------------------------------------------------------- */
+/* A pipeline that keeps its buffers and never asks the device how far it got (csrc/solr_jpeg_entropy.hip, the slots of
+ * solr_hip_frame_to_jpeg_async) sizes buffers and launches by what the host knows - the number of blocks - and lets one
+ * step on the device turn the prefix sum's total into the extents the later steps read.  What a frame of nbBlocks blocks
+ * can take with ANY table of 16-bit codes: so many bits unstuffed (the tail's seven included), so many bytes, so many
+ * chunks, and twice the bytes stuffed (every byte a 0xFF).  No frame inside the domain is larger: there is no overflow */
+JPE_HD inline u64 maxStreamBits(long nbBlocks)
+{
+    return (u64)nbBlocks * (u64)MAX_BLOCK_BITS_ANY_TABLE + 7u;
+}
+JPE_HD inline u64 chunksOf(u64 nbBytes)
+{
+    return (nbBytes + (u64)STUFF_CHUNK_BYTES - 1u) / (u64)STUFF_CHUNK_BYTES;
+}
+JPE_HD inline u64 maxStreamBytes(long nbBlocks) { return streamBytes(maxStreamBits(nbBlocks)); }
+JPE_HD inline u64 maxStreamChunks(long nbBlocks) { return chunksOf(maxStreamBytes(nbBlocks)); }
+JPE_HD inline u64 maxStuffedBytes(long nbBlocks) { return 2u * maxStreamBytes(nbBlocks); }
+
+/* what the steps behind the prefix sum read in place of arguments the host would have had to wait for */
+struct ScanPlan
+{
+    u64 totalBits;      /* of the blocks, without the tail */
+    u64 unstuffedBytes; /* streamBytes(totalBits): the tail completes the last one */
+    u64 streamWords;    /* the words of the unstuffed stream the emit step touches: those the stuff step reads */
+    u64 nbChunks;       /* chunks of STUFF_CHUNK_BYTES that hold a byte */
+    u32 flag;           /* a block is outside the domain: every extent above is 0, the later steps write nothing */
+    u32 pad;
+};
+JPE_HD inline ScanPlan planScan(u64 totalBits, u32 flag)
+{
+    ScanPlan plan = {0, 0, 0, 0, flag ? 1u : 0u, 0};
+    if (flag)
+        return plan;
+    plan.totalBits = totalBits;
+    plan.unstuffedBytes = streamBytes(totalBits);
+    plan.streamWords = streamWords(totalBits + (u64)tailBits(totalBits));
+    plan.nbChunks = chunksOf(plan.unstuffedBytes);
+    return plan;
+}
+/* bytesOfWord with the extent from the plan: a word of a chunk beyond it holds none */
+JPE_HD inline int planBytesOfWord(const ScanPlan &plan, u64 index)
+{
+    return index / (u64)(STUFF_CHUNK_BYTES / 4) >= plan.nbChunks ? 0 : bytesOfWord(index, plan.unstuffedBytes);
+}
+/* the count and the stuff step of one chunk with the extent from the plan, as loops (the device: a lane per word).
+ * chunkCountFF: the 0xFF bytes of the chunk, 0 beyond the extent.  chunkStuff: the chunk's bytes to `out` at the chunk's
+ * offset plus `before` (the 0xFF of the chunks in front), nothing beyond the extent; clearBehind: every word read is left
+ * zero, so that the stream a resident buffer holds is zero again for the next emit step - the work follows the file */
+inline u64 chunkCountFF(const u32 *stream, const ScanPlan &plan, u64 chunk)
+{
+    u64 n = 0;
+    for (u64 index = chunk * (STUFF_CHUNK_BYTES / 4); index < (chunk + 1) * (STUFF_CHUNK_BYTES / 4); ++index)
+        if (const int bytes = planBytesOfWord(plan, index))
+            n += countFF(stream[index], bytes);
+    return n;
+}
+inline void chunkStuff(u32 *stream, const ScanPlan &plan, u64 chunk, u64 before, u8 *out, bool clearBehind)
+{
+    u64 at = chunk * (u64)STUFF_CHUNK_BYTES + before;
+    for (u64 index = chunk * (STUFF_CHUNK_BYTES / 4); index < (chunk + 1) * (STUFF_CHUNK_BYTES / 4); ++index)
+        if (const int bytes = planBytesOfWord(plan, index))
+        {
+            at += stuffWord(stream[index], bytes, out + at);
+            if (clearBehind)
+                stream[index] = 0;
+        }
+}
+
 /* ---- prefix sums ------------------------------------------------------------------------------------------------------ */
 /* offsets[i] = lengths[0] + ... + lengths[i - 1] for i = 0 ... n (n + 1 results, the last the total), 64 bits wide:
  * SOLR_JPEG_MAX_PIXELS is 2^26 pixels, 1.5 M blocks of up to 1660 bits pass 2^32 */

@@ -252,6 +252,7 @@ static void finalizeOne()
         if (flight.stream)
             (void)hipStreamSynchronize(flight.stream);
     collectEvents();
+    g.jpeg.release(); /* JPEG frames in flight: their slots go, outstanding tickets are void */
     /* the read-back first - the copy stream is waited for before an image goes (the ring of host images is the process's:
      * it goes with engine 0, and stays when a later engine goes alone) - then the frames' buffers, the streams but
      * flight 0's, streamed frames, the launch order */
@@ -301,6 +302,7 @@ static void reshapeOne(const SceneInfo &sceneInfo)
     if (!ready("reshape_scene"))
         return;
     quiesce();
+    g.jpeg.release(); /* the slots of JPEG frames in flight were cut for the size before */
     g.width = sceneInfo.size.x;
     g.height = sceneInfo.size.y;
     allocateFrame();

@@ -119,6 +119,16 @@ __global__ __launch_bounds__(64) void k_jpegCoefficients(const JpegEncodeGeometr
     }
 }
 
+/* the tables as an argument to their place on the device: what a launch carries needs no host memory that outlives the
+ * call (launchJpegCoefficientsResident; 768 bytes, 192 words) */
+static_assert(sizeof(JpegEncodeTables) == 192 * sizeof(unsigned), "three words a lane");
+__global__ __launch_bounds__(64) void k_jpegPutTables(const JpegEncodeTables tables, JpegEncodeTables *__restrict__ to)
+{
+    const unsigned *from = reinterpret_cast<const unsigned *>(&tables);
+    for (int i = threadIdx.x; i < 192; i += 64)
+        reinterpret_cast<unsigned *>(to)[i] = from[i];
+}
+
 std::atomic<unsigned long long> gEncodedBlocks{0};
 
 inline size_t roundUp(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
@@ -163,6 +173,29 @@ void launchJpegCoefficients(const SolrJpegSource &source, JpegEncodeTables &tabl
     const int mcusPerRow = (source.width + 8 * source.lumaH - 1) / (8 * source.lumaH);
     const int mcuRows = (source.height + 8 * source.lumaV - 1) / (8 * source.lumaV);
     HIPCHECK(hipMemcpyAsync(dTables, &tables, sizeof(tables), hipMemcpyHostToDevice, stream));
+    if (!ok())
+        return;
+    const JpegEncodeGeometry geo = {source.width,       source.height,           source.lumaH, source.lumaV,
+                                    source.turned != 0, source.swapRedBlue != 0, mcusPerRow};
+    const dim3 grid((unsigned)((mcusPerRow + MCUS_PER_GROUP - 1) / MCUS_PER_GROUP), (unsigned)mcuRows);
+    k_jpegCoefficients<<<grid, dim3(64), 0, stream>>>(geo, dTables, dRgb, dCoefficients);
+    HIPCHECK(hipGetLastError());
+}
+
+void launchJpegCoefficientsResident(const SolrJpegSource &source, JpegEncodeTables *dTables, const unsigned char *dRgb,
+                                    short *dCoefficients, long nbBlocks, hipStream_t stream)
+{
+    JpegEncodeTables tables;
+    for (int t = 0; t < 2; ++t)
+    {
+        jpe::quantTable(source.quality, t, tables.quant[t]);
+        for (int k = 0; k < 64; ++k)
+            tables.recip[t][k] = jpe::reciprocal(tables.quant[t][k]);
+    }
+    const int mcusPerRow = (source.width + 8 * source.lumaH - 1) / (8 * source.lumaH);
+    const int mcuRows = (source.height + 8 * source.lumaV - 1) / (8 * source.lumaV);
+    k_jpegPutTables<<<dim3(1), dim3(64), 0, stream>>>(tables, dTables);
+    HIPCHECK(hipGetLastError());
     if (!ok())
         return;
     const JpegEncodeGeometry geo = {source.width,       source.height,           source.lumaH, source.lumaV,

@@ -654,6 +654,321 @@ int frameToScan(const char *who, int quality, int lumaH, int lumaV, unsigned cha
 }
 }
 
+/* ---- JPEG frames in flight: the resident, wait-free pipeline (engine.h JpegSlot; solr_hip_frame_to_jpeg_async) ----------
+ * The steps above with nothing read back between them.  Buffers and launches are sized by the number of blocks alone
+ * (jpn::maxStreamBytes, maxStreamChunks, maxStuffedBytes); k_jpegPlan turns the scan's total into the extents
+ * (jpn::ScanPlan) that k_jpegCountFFResident and k_jpegStuffResident read where their namesakes took arguments: a chunk
+ * beyond the extent counts zero and writes nothing.  The stream's buffer stays: k_jpegEmit ORs into zeros, so the words a
+ * use dirtied are zeroed behind it by the step that reads them last (k_jpegStuffResident) - or, SOLR_HIP_JPEG_ZERO_BOUND=1,
+ * the whole bound is zeroed in front of every emit (the alternative, kept for the measurement).  A block outside the
+ * domain: the plan's extents are zero and k_jpegPlan zeroes the offsets, at which k_jpegEmit's guard returns - nothing is
+ * written beyond the record. */
+namespace
+{
+/* what the steps hand each other and, copied to the slot's page-locked record, the host */
+struct JpegRecord
+{
+    jpn::ScanPlan plan;
+    u64 stuffedBytes; /* the segment: plan.unstuffedBytes + the 0xFF of all chunks */
+    u32 flag;         /* raised by k_jpegBlockBits / k_jpegSymbolCounts */
+    u32 pad;
+    jpn::Huffman huffman; /* optimised mode: what the DHTs must say */
+};
+
+/* one wave: the total behind the offsets and the flag to the plan; a flagged frame's offsets all to zero */
+__global__ __launch_bounds__(GROUP) void k_jpegPlan(u64 *__restrict__ offsets, const int nbBlocks, JpegRecord *__restrict__ record)
+{
+    const u32 flag = record->flag;
+    if (threadIdx.x == 0)
+        record->plan = jpn::planScan(offsets[nbBlocks], flag);
+    if (flag)
+    {
+        __syncthreads(); /* (lane 0 has read the total) */
+        for (int i = threadIdx.x; i <= nbBlocks; i += GROUP)
+            offsets[i] = 0;
+    }
+}
+
+/* k_jpegCountFF over the bound: nbChunks is the bound's, the extent the record's */
+__global__ __launch_bounds__(GROUP) void k_jpegCountFFResident(const u32 *__restrict__ stream,
+                                                               const JpegRecord *__restrict__ record,
+                                                               u64 *__restrict__ counts, const long nbChunks)
+{
+    const int lane = threadIdx.x;
+    const u64 index = (u64)blockIdx.x * GROUP + lane;
+    const int n = jpn::planBytesOfWord(record->plan, index);
+    const u32 total = waveSum(n ? jpn::countFF(stream[index], n) : 0u);
+    if (lane == 0)
+    {
+        counts[blockIdx.x] = total;
+        if (blockIdx.x == 0)
+            counts[nbChunks] = 0; /* item n of the scan */
+    }
+}
+
+/* k_jpegStuff over the bound; chunk 0 also leaves the segment's size.  clearBehind: the words read are left zero */
+__global__ __launch_bounds__(GROUP) void k_jpegStuffResident(u32 *stream, JpegRecord *record, const u64 *__restrict__ before,
+                                                             u8 *__restrict__ out, const long nbChunks, const int clearBehind)
+{
+    const int lane = threadIdx.x;
+    const jpn::ScanPlan plan = record->plan;
+    if (blockIdx.x == 0 && lane == 0)
+        record->stuffedBytes = plan.unstuffedBytes + before[nbChunks];
+    if ((u64)blockIdx.x >= plan.nbChunks)
+        return;
+    const u64 index = (u64)blockIdx.x * GROUP + lane;
+    const int n = jpn::planBytesOfWord(plan, index);
+    const u32 word = n ? stream[index] : 0u;
+    const u32 mine = jpn::countFF(word, n);
+    u32 below = mine;
+    for (int step = 1; step < GROUP; step <<= 1)
+    {
+        const u32 other = __shfl_up(below, step, GROUP);
+        if (lane >= step)
+            below += other;
+    }
+    below -= mine;
+    if (n)
+    {
+        jpn::stuffWord(word, n, out + (index * 4u + before[blockIdx.x] + below));
+        if (clearBehind)
+            stream[index] = 0;
+    }
+}
+
+bool zeroTheBound()
+{
+    const char *env = getenv("SOLR_HIP_JPEG_ZERO_BOUND");
+    return env && env[0] == '1';
+}
+
+void freeSlot(solreng::JpegSlot &slot)
+{
+    if (slot.used && slot.done)
+        (void)hipEventSynchronize(slot.done); /* nothing of the slot's may still run when its memory goes */
+    solreng::release(slot.block);
+    if (slot.hostRecord)
+        (void)hipHostFree(slot.hostRecord);
+    if (slot.done)
+        (void)hipEventDestroy(slot.done);
+    slot = solreng::JpegSlot();
+}
+
+void freeRetired(solreng::JpegRetired &old)
+{
+    solreng::release(old.block);
+    if (old.hostRecord)
+        (void)hipHostFree(old.hostRecord);
+    if (old.done)
+        (void)hipEventDestroy(old.done);
+}
+
+/* the slots set aside whose last use is through are given back; none is waited for unless there are too many */
+void sweepRetired(solreng::JpegStream &js)
+{
+    for (size_t i = 0; i < js.retired.size();)
+        if (hipEventQuery(js.retired[i].done) == hipSuccess)
+        {
+            freeRetired(js.retired[i]);
+            js.retired.erase(js.retired.begin() + (long)i);
+        }
+        else
+            ++i;
+    while (js.retired.size() > solreng::JpegStream::RETIRED_MOST)
+    {
+        ++js.hostWaits;
+        (void)hipEventSynchronize(js.retired.front().done);
+        freeRetired(js.retired.front());
+        js.retired.erase(js.retired.begin());
+    }
+}
+
+/* the slot cut for nbBlocks blocks or more: as it is, or - the first use, a frame of more blocks - made anew */
+bool ensureSlot(solreng::JpegSlot &slot, long nbBlocks)
+{
+    using namespace solreng;
+    size_t scanBytes = 0, chunkScanBytes = 0;
+    const long nbChunks = (long)jpn::maxStreamChunks(nbBlocks);
+    HIPCHECK(exclusiveSum(nullptr, scanBytes, nullptr, nullptr, nbBlocks + 1, nullptr));
+    if (ok())
+        HIPCHECK(exclusiveSum(nullptr, chunkScanBytes, nullptr, nullptr, nbChunks + 1, nullptr));
+    if (!ok())
+        return false;
+    if (slot.block.ptr && slot.capacityBlocks >= nbBlocks && slot.scanBytes >= scanBytes && slot.chunkScanBytes >= chunkScanBytes)
+        return true;
+    /* a frame of more blocks than the slot was cut for: what its last use may still read is set aside, not waited for */
+    if (slot.used)
+    {
+        g.jpeg.retired.push_back({slot.block, slot.hostRecord, slot.done});
+        slot = JpegSlot();
+    }
+    freeSlot(slot);
+    const size_t itemBytes = roundUp((size_t)(nbBlocks + 1) * sizeof(u64));
+    const size_t chunkBytes = roundUp((size_t)(nbChunks + 1) * sizeof(u64));
+    /* whole chunks: k_jpegCountFFResident's grid is the bound's */
+    const size_t streamBytes = roundUp((size_t)nbChunks * jpn::STUFF_CHUNK_BYTES);
+    const size_t part = roundUp(sizeof(jpn::Tables));
+    const size_t cuts[] = {roundUp(sizeof(JpegEncodeTables)), roundUp((size_t)nbBlocks * 64 * sizeof(short)), itemBytes, itemBytes,
+                           roundUp(scanBytes), streamBytes, chunkBytes, chunkBytes, roundUp(chunkScanBytes),
+                           roundUp((size_t)jpn::maxStuffedBytes(nbBlocks) + 8), part, part, roundUp(sizeof(JpegRecord))};
+    size_t total = 0;
+    for (const size_t cut : cuts)
+        total += cut;
+    reserve(slot.block, total);
+    if (ok())
+    {
+        ++g.jpeg.allocations;
+        HIPCHECK(hipHostMalloc(&slot.hostRecord, sizeof(JpegRecord), hipHostMallocDefault));
+    }
+    if (ok())
+    {
+        ++g.jpeg.allocations;
+        HIPCHECK(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    }
+    if (!ok())
+    {
+        freeSlot(slot);
+        return false;
+    }
+    unsigned char *at = static_cast<unsigned char *>(slot.block.ptr);
+    unsigned char **const fields[] = {&slot.encodeTables, &slot.coefficients, &slot.bits, &slot.offsets, &slot.scanTemp,
+                                      &slot.stream, &slot.counts, &slot.before, &slot.chunkScanTemp, &slot.out,
+                                      &slot.histogram, &slot.tables, &slot.record};
+    for (size_t i = 0; i < sizeof(cuts) / sizeof(cuts[0]); ++i)
+    {
+        *fields[i] = at;
+        at += cuts[i];
+    }
+    slot.capacityBlocks = nbBlocks;
+    slot.scanBytes = roundUp(scanBytes);
+    slot.chunkScanBytes = roundUp(chunkScanBytes);
+    slot.streamBytes = streamBytes;
+    return true;
+}
+
+/* One implementation for frames and the probe: the next slot, behind its last use; the blocks from `image` (the pixel
+ * stage) or from the caller's `hostBlocks`; every entropy step; the record's read-back; the event.  The ticket, or -1 with
+ * the error set.  Nothing here waits for the device but the upload of pageable `hostBlocks` (the probe's) */
+int submitJpeg(const SolrJpegSource &source, const unsigned char *image, const short *hostBlocks, long nbBlocks, bool optimised,
+               hipStream_t stream)
+{
+    using namespace solreng;
+    JpegStream &js = g.jpeg;
+    JpegSlot &slot = js.slot[js.issued % JPEG_SLOTS];
+    slot.serial = -1; /* the ticket that held the slot is stale from here on */
+    if (!js.retired.empty())
+        sweepRetired(js);
+    if (!ensureSlot(slot, nbBlocks))
+        return -1;
+    const int lumaBlocks = source.lumaH * source.lumaV;
+    const long nbGroups = (nbBlocks + GROUP - 1) / GROUP;
+    const long nbChunks = (long)jpn::maxStreamChunks(nbBlocks);
+    const bool zeroBound = zeroTheBound();
+    short *dCoefficients = reinterpret_cast<short *>(slot.coefficients);
+    u64 *dBits = reinterpret_cast<u64 *>(slot.bits), *dOffsets = reinterpret_cast<u64 *>(slot.offsets);
+    u32 *dStream = reinterpret_cast<u32 *>(slot.stream);
+    u64 *dCounts = reinterpret_cast<u64 *>(slot.counts), *dBefore = reinterpret_cast<u64 *>(slot.before);
+    JpegRecord *dRecord = reinterpret_cast<JpegRecord *>(slot.record);
+    jpn::Tables *dTables = reinterpret_cast<jpn::Tables *>(slot.tables);
+    size_t scanBytes = slot.scanBytes, chunkScanBytes = slot.chunkScanBytes;
+    /* the slot's last use may have run on another stream */
+    if (slot.used)
+        HIPCHECK(hipStreamWaitEvent(stream, slot.done, 0));
+    if (ok() && (zeroBound || !slot.clean))
+        HIPCHECK(hipMemsetAsync(dStream, 0, slot.streamBytes, stream));
+    slot.clean = false;
+    if (ok())
+        HIPCHECK(hipMemsetAsync(dRecord, 0, sizeof(JpegRecord), stream));
+    if (ok() && image)
+        launchJpegCoefficientsResident(source, reinterpret_cast<JpegEncodeTables *>(slot.encodeTables), image, dCoefficients,
+                                       nbBlocks, stream);
+    else if (ok())
+    {
+        HIPCHECK(hipMemcpyAsync(dCoefficients, hostBlocks, (size_t)nbBlocks * 64 * sizeof(short), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipStreamSynchronize(stream)); /* (pageable memory of the caller's: his again when this returns) */
+    }
+    if (ok() && optimised)
+        launchOptimisedTables(dCoefficients, nbBlocks, lumaBlocks, stream, reinterpret_cast<u32 *>(slot.histogram), dTables,
+                              &dRecord->huffman, &dRecord->flag);
+    if (ok())
+    {
+        if (optimised)
+            k_jpegBlockBits<true><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks,
+                                                                                        lumaBlocks, dBits, &dRecord->flag, dTables);
+        else
+            k_jpegBlockBits<false><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks,
+                                                                                         lumaBlocks, dBits, &dRecord->flag, nullptr);
+        HIPCHECK(hipGetLastError());
+    }
+    if (ok())
+        HIPCHECK(exclusiveSum(slot.scanTemp, scanBytes, dBits, dOffsets, nbBlocks + 1, stream));
+    if (ok())
+    {
+        k_jpegPlan<<<dim3(1), dim3(GROUP), 0, stream>>>(dOffsets, (int)nbBlocks, dRecord);
+        HIPCHECK(hipGetLastError());
+    }
+    if (ok())
+    {
+        if (optimised)
+            k_jpegEmit<true><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks, lumaBlocks,
+                                                                                   dOffsets, dStream, dTables);
+        else
+            k_jpegEmit<false><<<dim3((unsigned)nbGroups), dim3(GROUP), 0, stream>>>(dCoefficients, (int)nbBlocks,
+                                                                                    lumaBlocks, dOffsets, dStream, nullptr);
+        HIPCHECK(hipGetLastError());
+    }
+    if (ok())
+    {
+        k_jpegCountFFResident<<<dim3((unsigned)nbChunks), dim3(GROUP), 0, stream>>>(dStream, dRecord, dCounts, nbChunks);
+        HIPCHECK(hipGetLastError());
+    }
+    if (ok())
+        HIPCHECK(exclusiveSum(slot.chunkScanTemp, chunkScanBytes, dCounts, dBefore, nbChunks + 1, stream));
+    if (ok())
+    {
+        k_jpegStuffResident<<<dim3((unsigned)nbChunks), dim3(GROUP), 0, stream>>>(dStream, dRecord, dBefore, slot.out, nbChunks,
+                                                                                  zeroBound ? 0 : 1);
+        HIPCHECK(hipGetLastError());
+    }
+    if (ok())
+        HIPCHECK(hipMemcpyAsync(slot.hostRecord, dRecord, optimised ? sizeof(JpegRecord) : offsetof(JpegRecord, huffman),
+                                hipMemcpyDeviceToHost, stream));
+    if (ok())
+        HIPCHECK(hipEventRecord(slot.done, stream));
+    if (!ok())
+        return -1; /* (the slot stays dirty: its next use zeroes the whole stream) */
+    slot.used = true;
+    slot.clean = !zeroBound;
+    slot.serial = js.issued++;
+    slot.nbBlocks = nbBlocks;
+    slot.optimised = optimised;
+    slot.fromFrame = image != nullptr;
+    slot.collected = false;
+    return JpegStream::ticketOf(slot.serial);
+}
+}
+
+namespace solreng
+{
+void JpegStream::release()
+{
+    for (JpegSlot &s : slot)
+        freeSlot(s);
+    for (JpegRetired &old : retired)
+    {
+        (void)hipEventSynchronize(old.done);
+        freeRetired(old);
+    }
+    retired.clear();
+    for (hipStream_t *stream : {&probeStream, &copyStream})
+    {
+        if (*stream)
+            (void)hipStreamDestroy(*stream);
+        *stream = nullptr;
+    }
+}
+}
+
 extern "C" {
 
 int solr_hip_jpeg_blocks_to_scan(const SolrJpegSource *source, const short *coefficients, long nbBlocks,
@@ -801,6 +1116,137 @@ int solr_hip_probe_jpeg_tables(const unsigned int *counts, SolrJpegHuffman *tabl
 unsigned long long solr_hip_jpeg_coded_blocks(void)
 {
     return gCodedBlocks.load();
+}
+
+/* ---- JPEG frames in flight ---- */
+int solr_hip_jpeg_stream_offered(void)
+{
+    using namespace solreng;
+    return g.initialized && gDevices == 1 && g.nbRows < 0 ? 1 : 0;
+}
+
+int solr_hip_frame_to_jpeg_async(int quality, int lumaH, int lumaV, int optimised)
+{
+    using namespace solreng;
+    const char *who = "solr_hip_frame_to_jpeg_async";
+    if (!ready(who))
+        return -1;
+    /* declined, and no error: solr_hip_frame_to_jpeg_scan's reasons */
+    Flight &set = g.flight[g.current];
+    const unsigned char *image = reinterpret_cast<const unsigned char *>(g.boundBitmap ? g.boundBitmap : set.shown().ptr);
+    if (gDevices > 1 || g.nbRows >= 0 || g.frameBufferType < 0 || !image)
+        return -1;
+    const SolrJpegSource source = {g.width, g.height, lumaH, lumaV, quality, 1, g.frameBufferType != (int)ftRGB ? 1 : 0};
+    long nbBlocks = 0;
+    if (!jpegSourceAccepted(who, &source, &nbBlocks))
+        return -1;
+    HIPCHECK(hipSetDevice(g.device));
+    if (!ok())
+        return -1;
+    /* behind the frame, on its stream */
+    return submitJpeg(source, image, nullptr, nbBlocks, optimised != 0, set.stream);
+}
+
+int solr_hip_probe_jpeg_stream_blocks(const SolrJpegSource *source, const short *coefficients, long nbBlocks, int optimised)
+{
+    using namespace solreng;
+    const char *who = "solr_hip_probe_jpeg_stream_blocks";
+    if (!ok())
+        return -1;
+    if (!source || !coefficients)
+    {
+        setError(-1, "solr_hip_probe_jpeg_stream_blocks: null source or coefficients", __FILE__, __LINE__);
+        return -1;
+    }
+    long expected = 0;
+    if (!jpegSourceAccepted(who, source, &expected))
+        return -1;
+    if (nbBlocks != expected)
+    {
+        setError(-1, "solr_hip_probe_jpeg_stream_blocks: nbBlocks does not match the image size and sampling", __FILE__,
+                 __LINE__);
+        return -1;
+    }
+    int before = -1;
+    if (hipGetDevice(&before) != hipSuccess)
+        before = -1;
+    HIPCHECK(hipSetDevice(solr_hip_get_device()));
+    if (ok() && !g.jpeg.probeStream)
+        HIPCHECK(hipStreamCreateWithFlags(&g.jpeg.probeStream, hipStreamNonBlocking));
+    const int ticket = ok() ? submitJpeg(*source, nullptr, coefficients, nbBlocks, optimised != 0, g.jpeg.probeStream) : -1;
+    if (before >= 0)
+        (void)hipSetDevice(before);
+    return ok() ? ticket : -1;
+}
+
+int solr_hip_jpeg_wait(int ticket, unsigned char *scan, long capacity, long *nbBytes, SolrJpegHuffman *tables)
+{
+    using namespace solreng;
+    const char *who = "solr_hip_jpeg_wait";
+    if (!ok() || !outputAccepted(who, scan, capacity, nbBytes))
+        return -1;
+    JpegStream &js = g.jpeg;
+    JpegSlot *slot = ticket >= 0 ? &js.slot[ticket % JPEG_SLOTS] : nullptr;
+    if (!slot || slot->serial < 0 || slot->serial % JpegStream::TICKET_PERIOD != (long)(ticket / JPEG_SLOTS))
+    {
+        setError(-1, "solr_hip_jpeg_wait: no such ticket: it was never handed out, four tickets have followed it, or the frame "
+                     "was re-shaped or the scene finalized since", __FILE__, __LINE__);
+        return -1;
+    }
+    if (slot->optimised && !tablesAccepted(who, tables))
+        return -1;
+    int before = -1;
+    if (hipGetDevice(&before) != hipSuccess)
+        before = -1;
+    HIPCHECK(hipSetDevice(g.initialized ? g.device : solr_hip_get_device()));
+    if (ok())
+        HIPCHECK(hipEventSynchronize(slot->done));
+    int result = -1;
+    const JpegRecord *record = static_cast<const JpegRecord *>(slot->hostRecord);
+    if (ok() && (record->flag || record->plan.flag))
+        setError(-1, "solr_hip_jpeg_wait: a block is outside what the tables code (|DC difference| <= 2047, |AC| <= 1023)",
+                 __FILE__, __LINE__);
+    else if (ok())
+    {
+        *nbBytes = (long)record->stuffedBytes;
+        if (*nbBytes <= capacity) /* (else no error: the caller comes back with a buffer of that size) */
+        {
+            if (!js.copyStream)
+                HIPCHECK(hipStreamCreateWithFlags(&js.copyStream, hipStreamNonBlocking));
+            if (ok())
+                HIPCHECK(hipMemcpyAsync(scan, slot->out, (size_t)*nbBytes, hipMemcpyDeviceToHost, js.copyStream));
+            if (ok())
+                HIPCHECK(hipStreamSynchronize(js.copyStream));
+            if (ok())
+            {
+                if (slot->optimised)
+                    memcpy(tables, &record->huffman, sizeof(jpn::Huffman));
+                if (!slot->collected)
+                {
+                    slot->collected = true;
+                    gCodedBlocks += (unsigned long long)slot->nbBlocks;
+                    if (slot->fromFrame)
+                        countJpegEncodedBlocks(slot->nbBlocks);
+                    js.bytesDelivered += (unsigned long long)*nbBytes;
+                }
+                result = 0;
+            }
+        }
+    }
+    if (before >= 0)
+        (void)hipSetDevice(before);
+    return ok() ? result : -1;
+}
+
+void solr_hip_jpeg_stream_stats(unsigned long long out[4])
+{
+    using namespace solreng;
+    if (!out)
+        return;
+    out[0] = (unsigned long long)g.jpeg.issued;
+    out[1] = g.jpeg.allocations;
+    out[2] = g.jpeg.hostWaits;
+    out[3] = g.jpeg.bytesDelivered;
 }
 
 } /* extern "C" */

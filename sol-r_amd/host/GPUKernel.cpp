@@ -2118,6 +2118,88 @@ bool GPUKernel::renderJpeg(const float timer, int jpegQuality, int lumaH, int lu
                       optimise);
 }
 
+int GPUKernel::jpegBeginOfFrame(int, int, int, bool)
+{
+    return -1;
+}
+
+bool GPUKernel::jpegEndOfFrame(int, std::vector<unsigned char> &, SolrJpegHuffman *)
+{
+    return false;
+}
+
+/* the next slot of m_jpegTickets, whatever it held forgotten, and its ticket */
+static int nextJpegTicket(long &issued, long period, int slots, long *serial)
+{
+    *serial = issued++;
+    return (int)((*serial % period) * slots + *serial % slots);
+}
+
+int GPUKernel::renderJpegBegin(const float timer, int jpegQuality, int lumaH, int lumaV, bool optimise)
+{
+    const SolrJpegSource source = {m_sceneInfo.size.x, m_sceneInfo.size.y, lumaH, lumaV, jpegQuality, 1,
+                                   m_sceneInfo.frameBufferType != ftRGB ? 1 : 0};
+    if (!jpegSourceInRange(source))
+        return -1;
+    JpegTicket parked;
+    parked.source = source;
+    parked.optimise = optimise;
+    if (jpegStreamOffered())
+    {
+        m_jpegFrame = m_jpegStreamFrame = true; /* (whole on the device: no bands, no image-ring copy) */
+        render_begin(timer);
+        m_jpegFrame = m_jpegStreamFrame = false;
+        if (lastError() != 0)
+            return -1;
+        parked.engineTicket = jpegBeginOfFrame(jpegQuality, lumaH, lumaV, optimise);
+        if (parked.engineTicket < 0)
+            return -1;
+    }
+    else if (!renderJpeg(timer, jpegQuality, lumaH, lumaV, parked.file, optimise))
+        return -1;
+    const int ticket = nextJpegTicket(m_jpegIssued, JPEG_TICKET_PERIOD, JPEG_TICKETS, &parked.serial);
+    m_jpegTickets[parked.serial % JPEG_TICKETS] = std::move(parked);
+    return ticket;
+}
+
+int GPUKernel::jpegParkPixels(const unsigned char *pixels, int width, int height, int jpegQuality, int lumaH, int lumaV,
+                              bool swapRedBlue, bool optimise)
+{
+    JpegTicket parked;
+    parked.source = {width, height, lumaH, lumaV, jpegQuality, 1, swapRedBlue ? 1 : 0};
+    parked.optimise = optimise;
+    if (!encodeJpeg(parked.file, pixels, width, height, jpegQuality, lumaH, lumaV, true, swapRedBlue, optimise))
+        return -1;
+    const int ticket = nextJpegTicket(m_jpegIssued, JPEG_TICKET_PERIOD, JPEG_TICKETS, &parked.serial);
+    m_jpegTickets[parked.serial % JPEG_TICKETS] = std::move(parked);
+    return ticket;
+}
+
+bool GPUKernel::renderJpegEnd(int ticket, std::vector<unsigned char> *&file)
+{
+    m_jpegTicketError.clear();
+    file = nullptr;
+    JpegTicket *parked = ticket >= 0 ? &m_jpegTickets[ticket % JPEG_TICKETS] : nullptr;
+    if (!parked || parked->serial < 0 || parked->serial % JPEG_TICKET_PERIOD != (long)(ticket / JPEG_TICKETS))
+    {
+        m_jpegTicketError = "renderJpegEnd: no such ticket: it was never handed out, or four tickets have followed it";
+        return false;
+    }
+    if (parked->file.empty())
+    {
+        std::vector<unsigned char> scan;
+        SolrJpegHuffman tables;
+        if (!jpegEndOfFrame(parked->engineTicket, scan, parked->optimise ? &tables : nullptr))
+        {
+            m_jpegTicketError = "renderJpegEnd: the engine did not deliver that ticket's frame";
+            return false;
+        }
+        jpegFileAround(parked->source, scan, parked->file, parked->optimise ? &tables : nullptr);
+    }
+    file = &parked->file;
+    return true;
+}
+
 /* reference: GPUKernel.cpp:2792-2852; what differs is said in GPUKernel.h */
 void GPUKernel::generateScreenshot(const std::string &filename, const unsigned int width, const unsigned int height,
                                    const unsigned int quality)

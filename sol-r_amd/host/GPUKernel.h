@@ -551,6 +551,24 @@ public:
 protected:
     BitmapBuffer *m_bitmapView = nullptr; /* see getBitmap */
     bool m_jpegFrame = false;             /* render_begin is renderJpeg's: the frame's image stays whole on the device */
+    bool m_jpegStreamFrame = false;       /* ... renderJpegBegin's, for a JPEG in flight: no image-ring copy either */
+    /* JPEG frames in flight (renderJpegBegin / renderJpegEnd): what a ticket stands for - the engine's ticket, or, where
+     * the engine declined, the file itself - four deep, as the engine's slots are.  A ticket is
+     * (serial mod JPEG_TICKET_PERIOD) * JPEG_TICKETS + slot, the slot serial mod JPEG_TICKETS: one whose slot has been
+     * handed out again is told from a live one by its generation */
+    static const int JPEG_TICKETS = 4;
+    static const long JPEG_TICKET_PERIOD = ((long)0x7fffffff / JPEG_TICKETS / JPEG_TICKETS - 1) * JPEG_TICKETS;
+    struct JpegTicket
+    {
+        long serial = -1;      /* -1: the slot holds none */
+        int engineTicket = -1; /* >= 0: the segment is collected from the engine at the first renderJpegEnd */
+        SolrJpegSource source = {};
+        bool optimise = false;
+        std::vector<unsigned char> file; /* once it exists: renderJpegEnd hands it over as often as it is asked */
+    };
+    JpegTicket m_jpegTickets[JPEG_TICKETS];
+    long m_jpegIssued = 0;
+    std::string m_jpegTicketError; /* why the last renderJpegEnd failed, empty when it did not */
 
 public:
 
@@ -684,6 +702,25 @@ public:
      * encoded from the host's bitmap: the same bytes.  false: an argument out of range or a failed frame */
     bool renderJpeg(const float timer, int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &file,
                     bool optimise = false);
+    /* JPEG frames in flight.  renderJpegBegin: renderJpeg up to the launch - the frame is rendered (render_begin with
+     * `timer`) on the next flight, as render_begin takes it with setFramesInFlight(n), and submitted to the engine for
+     * delivery as a JPEG (jpegBeginOfFrame); frames in flight are NOT flushed, the image stays whole on the device, no band
+     * leaves and no image-ring copy is made; ids on the device, getBitmap() not refreshed, as renderJpeg leaves them.
+     * Returns a ticket >= 0, or -1 (an argument out of range, a failed frame).  renderJpegEnd: that frame's file - the
+     * header (with the collected tables in optimised mode) around the collected segment, EOI; waits for that frame alone.
+     * A ticket may be collected any number of times until three more have been handed out; a stale or never-issued one
+     * gives false with jpegTicketError() set, never another frame's file.  Where the engine declines (no device, strips,
+     * several devices) renderJpegBegin renders and encodes at once by renderJpeg's road and parks the file under a ticket
+     * of the same rule: interface and protocol are those of both engines.  flushFrames, render_begin / render_end and
+     * renderJpeg may be mixed with outstanding tickets: a ticket's bytes are those of its own frame */
+    int renderJpegBegin(const float timer, int jpegQuality, int lumaH, int lumaV, bool optimise = false);
+    bool renderJpegEnd(int ticket, std::vector<unsigned char> *&file);
+    const std::string &jpegTicketError() const { return m_jpegTicketError; }
+    /* for the tests of the ticket rule where no frame can be rendered: the caller's pixels, read as a frame is read
+     * (turned; red and blue swapped when asked), encoded at once and parked under a ticket as a declined renderJpegBegin
+     * parks its file.  -1: an argument out of range */
+    int jpegParkPixels(const unsigned char *pixels, int width, int height, int jpegQuality, int lumaH, int lumaV,
+                       bool swapRedBlue, bool optimise);
 
     /* ---------- Scene (GPUKernel.h:208-221) ---------- */
     void setSceneInfo(int width, int height, float transparentColor, int graphicsLevel, float viewDistance,
@@ -943,6 +980,14 @@ protected:
      * not this way; the caller goes through render_end and encodeJpeg */
     virtual bool jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan,
                                  SolrJpegHuffman *optimised = nullptr);
+    /* engine hooks of renderJpegBegin / renderJpegEnd.  jpegStreamOffered: the engine would take the next frame for
+     * delivery as a JPEG in flight (here: never) - asked before the frame is rendered, because such a frame is rendered
+     * with m_jpegStreamFrame set.  jpegBeginOfFrame: the frame render_begin has just launched, submitted; the engine's
+     * ticket, or -1.  jpegEndOfFrame: that ticket's entropy-coded segment, and with `optimised` its tables; waits for
+     * that frame alone.  false: the ticket is stale or the engine failed (its error is pending) */
+    virtual bool jpegStreamOffered() { return false; }
+    virtual int jpegBeginOfFrame(int jpegQuality, int lumaH, int lumaV, bool optimise);
+    virtual bool jpegEndOfFrame(int engineTicket, std::vector<unsigned char> &scan, SolrJpegHuffman *optimised);
     /* engine hooks: the iso-surface of a field of metaballs (csrc/iso_surface.h).  isoSurface: balls to triangles, cubes in
      * index order (`triangles` is resized); isoField: balls to (N+1)^3 records of {nx, ny, nz, value}; isoTriangles: such
      * a field to triangles - the number the surface has, the first min(count, capacity) written, -1 on failure.  Here:

@@ -201,9 +201,10 @@ void HipKernel::render_begin(const float timer)
                    m_angles);
         mark("render_begin: cudaRender");
         m_streamed = stream && solr_hip_stream_next_image(-1) == 1;
-        if (m_flights > 1)
+        if (m_flights > 1 && !m_jpegStreamFrame)
         {
-            /* frames in flight: the image starts for the host behind the kernel, on the engine's copy stream */
+            /* frames in flight: the image starts for the host behind the kernel, on the engine's copy stream (not that
+             * of a frame that leaves as a JPEG in flight: renderJpegBegin) */
             const int ticket = solr_hip_d2h_image_async();
             if (ticket >= 0)
                 m_tickets.push_back(ticket);
@@ -371,6 +372,37 @@ bool HipKernel::jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vect
     m_idsOnDevice = true;
     m_bitmapOnDevice = false;
     return true;
+}
+
+bool HipKernel::jpegStreamOffered()
+{
+    return m_deviceInitialized && solr_hip_jpeg_stream_offered() == 1;
+}
+
+int HipKernel::jpegBeginOfFrame(int jpegQuality, int lumaH, int lumaV, bool optimise)
+{
+    if (!m_deviceInitialized)
+        return -1;
+    const int ticket = solr_hip_frame_to_jpeg_async(jpegQuality, lumaH, lumaV, optimise ? 1 : 0);
+    if (ticket < 0)
+        return -1;
+    /* what jpegScanOfFrame leaves: m_bitmap is not brought up to date, now or when asked (with frames in flight the image
+     * on show stays the one delivered last) */
+    if (m_flights == 1)
+        m_bitmapView = nullptr;
+    m_streamed = false;
+    m_idsOnDevice = true;
+    m_bitmapOnDevice = false;
+    return ticket;
+}
+
+bool HipKernel::jpegEndOfFrame(int engineTicket, std::vector<unsigned char> &scan, SolrJpegHuffman *optimised)
+{
+    /* (a buffer too small costs a second wait, never a second frame: the ticket stays good) */
+    return m_deviceInitialized &&
+           jpegScanInto(scan, m_jpegCapacity, [&](unsigned char *to, long capacity, long *nbBytes) {
+               return solr_hip_jpeg_wait(engineTicket, to, capacity, nbBytes, optimised);
+           });
 }
 
 bool HipKernel::isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,

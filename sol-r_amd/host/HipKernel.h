@@ -101,6 +101,10 @@ protected:
                     SolrJpegHuffman *optimised = nullptr) override;
     bool jpegScanOfFrame(int jpegQuality, int lumaH, int lumaV, std::vector<unsigned char> &scan,
                          SolrJpegHuffman *optimised = nullptr) override;
+    /* JPEG frames in flight: solr_hip_jpeg_stream_offered, solr_hip_frame_to_jpeg_async, solr_hip_jpeg_wait */
+    bool jpegStreamOffered() override;
+    int jpegBeginOfFrame(int jpegQuality, int lumaH, int lumaV, bool optimise) override;
+    bool jpegEndOfFrame(int engineTicket, std::vector<unsigned char> &scan, SolrJpegHuffman *optimised) override;
     /* solr_hip_metaballs, solr_hip_iso_field, solr_hip_iso_surface (include/solr_hip.h) where there is a device, the base
      * class's loops where there is none */
     bool isoSurface(const SolrIsoGrid &grid, const float *balls, int nbBalls,

@@ -150,6 +150,12 @@ int SolRx_SetFramesInFlight(int n)
     return engineStatus();
 }
 
+/* ... and what it is set to (1 for an engine without a device) */
+int SolRx_GetFramesInFlight()
+{
+    return SingletonKernel::kernel()->getFramesInFlight();
+}
+
 /* Extension: the frame shared out over n devices of THIS process (the reference's occupancyParameters.x, which its
  * API cannot set: CudaKernel.cpp:90); returns the number in use after the change (fewer when fewer are there) or -1 */
 int SolRx_SetGpuCount(int n)
@@ -341,6 +347,77 @@ int SolRx_RenderJpegOptimised(double timer, int jpegQuality, int lumaH, int luma
                               long *nbBytes)
 {
     return renderJpeg(timer, jpegQuality, lumaH, lumaV, file, capacity, nbBytes, true);
+}
+
+/* Extensions: JPEG frames in flight (GPUKernel::renderJpegBegin / renderJpegEnd).  SolRx_RenderJpegBegin: the next frame
+ * rendered and submitted for delivery as a JPEG file; a ticket >= 0, or -1.  SolRx_RenderJpegEnd: that ticket's file - 0;
+ * -1 with *nbBytes = the size when `capacity` is too small (nothing written; the ticket stays good, no frame is rendered
+ * again); -1 with *nbBytes = 0 for a stale or never-issued ticket or a failed frame, SolRx_RenderJpegTicketError then says
+ * which.  SolRx_JpegParkPixels (for the tests): the caller's pixels, read as a frame is read, parked under a ticket */
+int SolRx_RenderJpegBegin(double timer, int jpegQuality, int lumaH, int lumaV, int optimised)
+{
+    solr::GPUKernel *kernel = SingletonKernel::kernel();
+    kernel->setSceneInfo(gSceneInfoStub);
+    kernel->setPostProcessingInfo(gPostProcessingInfoStub);
+    return kernel->renderJpegBegin(static_cast<float>(timer), jpegQuality, lumaH, lumaV, optimised != 0);
+}
+
+int SolRx_RenderJpegEnd(int ticket, unsigned char *file, long capacity, long *nbBytes)
+{
+    if (!nbBytes)
+        return -1;
+    *nbBytes = 0;
+    if (!file || capacity < 0)
+        return -1;
+    std::vector<unsigned char> *bytes = nullptr;
+    if (!SingletonKernel::kernel()->renderJpegEnd(ticket, bytes))
+        return -1;
+    return jpegFileOut(*bytes, file, capacity, nbBytes);
+}
+
+int SolRx_RenderJpegTicketError(char *buf, int len)
+{
+    const std::string &message = SingletonKernel::kernel()->jpegTicketError();
+    if (buf && len > 0)
+    {
+        strncpy(buf, message.c_str(), len - 1);
+        buf[len - 1] = 0;
+    }
+    return message.empty() ? 0 : -1;
+}
+
+int SolRx_JpegParkPixels(const unsigned char *pixels, int width, int height, int jpegQuality, int lumaH, int lumaV,
+                         int swapRedBlue, int optimised)
+{
+    if (!pixels)
+        return -1;
+    return SingletonKernel::kernel()->jpegParkPixels(pixels, width, height, jpegQuality, lumaH, lumaV, swapRedBlue != 0,
+                                                     optimised != 0);
+}
+
+/* Extension for the tests of the plan of a resident pipeline (csrc/jpeg_entropy.h, planScan): out[0 ... 4] = total bits,
+ * unstuffed bytes, stream words, chunks, flag for a scan's total and flag; out[5 ... 8] = the bounds of nbBlocks blocks:
+ * bits, bytes, chunks, stuffed bytes */
+void SolRx_JpegEntropyPlan(unsigned long long totalBits, int flag, long nbBlocks, unsigned long long out[9])
+{
+    const jpn::ScanPlan plan = jpn::planScan(totalBits, (jpn::u32)flag);
+    out[0] = plan.totalBits;
+    out[1] = plan.unstuffedBytes;
+    out[2] = plan.streamWords;
+    out[3] = plan.nbChunks;
+    out[4] = plan.flag;
+    out[5] = jpn::maxStreamBits(nbBlocks);
+    out[6] = jpn::maxStreamBytes(nbBlocks);
+    out[7] = jpn::maxStreamChunks(nbBlocks);
+    out[8] = jpn::maxStuffedBytes(nbBlocks);
+}
+
+/* ... and of the functions it is held to: out[0 ... 2] = streamBytes, streamWords, tailBits of totalBits */
+void SolRx_JpegEntropyStreamSizes(unsigned long long totalBits, unsigned long long out[3])
+{
+    out[0] = jpn::streamBytes(totalBits);
+    out[1] = jpn::streamWords(totalBits);
+    out[2] = (unsigned long long)jpn::tailBits(totalBits);
 }
 
 /* Extensions for the tests of the optimised tables (csrc/jpeg_entropy.h): the table builder on a histogram of the

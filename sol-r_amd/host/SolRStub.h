@@ -181,6 +181,23 @@ int SolRx_JpegOptimiseTable(const unsigned int *counts, int len, unsigned char *
 int SolRx_JpegCensus(const short *coefficients, long nbBlocks, int lumaBlocks, unsigned int *counts);
 int SolRx_JpegFromCoefficientsOptimised(const char *filename, const short *coefficients, long nbBlocks, int width,
                                         int height, int jpegQuality, int lumaH, int lumaV);
+/* JPEG frames in flight: SolRx_RenderJpegBegin renders the next frame - on the next flight with SolRx_SetFramesInFlight(n),
+ * nothing flushed - and submits it for delivery as a JPEG file (optimised != 0: with tables built for the frame); a ticket
+ * >= 0, or -1.  SolRx_RenderJpegEnd waits for that frame alone and hands over its file: 0, or -1 as SolRx_RenderJpeg - a
+ * capacity too small leaves the size in *nbBytes and the ticket good: the second call renders nothing.  A ticket may be
+ * collected any number of times until three more have been handed out; a stale or never-issued one gives -1 with
+ * *nbBytes = 0 and SolRx_RenderJpegTicketError's text set (0: the last SolRx_RenderJpegEnd had nothing to say).  With the
+ * HIP engine nothing waits for the device between the two calls; where it declines (no device, strips, several devices)
+ * the frame is rendered and encoded at once and the file kept under the ticket.  May be mixed with SolRx_FlushFrames,
+ * SolR_RunKernel and SolRx_RenderJpeg */
+int SolRx_RenderJpegBegin(double timer, int jpegQuality, int lumaH, int lumaV, int optimised);
+int SolRx_RenderJpegEnd(int ticket, unsigned char *file, long capacity, long *nbBytes);
+int SolRx_RenderJpegTicketError(char *buf, int len);
+/* for the tests: pixels parked under such a ticket; the plan of the resident entropy pipeline (SolRStub.cpp) */
+int SolRx_JpegParkPixels(const unsigned char *pixels, int width, int height, int jpegQuality, int lumaH, int lumaV,
+                         int swapRedBlue, int optimised);
+void SolRx_JpegEntropyPlan(unsigned long long totalBits, int flag, long nbBlocks, unsigned long long out[9]);
+void SolRx_JpegEntropyStreamSizes(unsigned long long totalBits, unsigned long long out[3]);
 /* csrc/jpeg_entropy.h for the tests (SolRStub.cpp) */
 void SolRx_JpegEntropyGranularity(int out[2]);
 void SolRx_JpegEntropyPrefix(const unsigned int *lengths, long n, unsigned long long *offsets);
@@ -216,6 +233,7 @@ int SolRx_Render(double timer);
  * protocol): a call delivers the image of the frame n - 1 calls back while the newer ones render;
  * SolRx_FlushFrames waits for all of them; SolRx_GetBitmap is the image delivered last, without a copy */
 int SolRx_SetFramesInFlight(int n);
+int SolRx_GetFramesInFlight();
 int SolRx_FlushFrames(void);
 /* the frame shared out over n devices of this process (occupancyParameters.x of the boundary, include/solr_hip.h);
  * returns the number in use, or -1.  With frames in flight the ids behind SolR_GetPrimitiveAt are the newest
