@@ -439,6 +439,29 @@ int solr_hip_metaballs(const SolrIsoGrid *grid, const float *balls, int nbBalls,
 /* cubes classified on the device since the library was loaded */
 unsigned long long solr_hip_iso_cubes(void);
 
+/* Which atoms of a molecule are joined by a stick, found on the device (sol-r_amd/csrc/solr_sticks.hip; the rule is
+ * sol-r_amd/csrc/stick_pairs.h, the pair search of the reference's solr/io/PDBReader.cpp:616-660, in IEEE binary32 in
+ * source order; the host-only engine runs the same header in loops and gives the same pairs).
+ *   atoms          n records of x, y, z and a spare word nobody reads; an atom's rank is its place here
+ *   backbone       n flags, as truth values: only atoms of equal flags are joined
+ *   reachPlain, reachBackbone   atom j is a partner of atom i != j (by rank: atoms at one place are partners) when
+ *                  sqrtf((ax*ax + ay*ay) + az*az) < the reach of their flag, a = i - j; a coordinate that is not finite
+ *                  has no partner
+ *   start          n + 1 entries: atom i's partners are partners[start[i] ... start[i + 1] - 1], their ranks ascending;
+ *                  start[n] is the number of pairs.  Nothing varies from run to run
+ * Returns the number of pairs there ARE, writes start whole and the first min(total, capacity) partners: a caller sizes
+ * its buffer with capacity = 0 (partners may then be null).  All pointers are host pointers.  Synchronous; on the device
+ * of solr_hip_get_device() on a stream of its own, with or without an initialised scene; the device buffers are given
+ * back before the call returns.  All pairs are tested, n * n per pass, a pass to count and a pass to store.
+ * -1 with the error set, and nothing launched, for a null pointer, n outside 0 ... NB_MAX_PRIMITIVES, a reach that is not
+ * finite or not positive, a negative capacity.  -1 WITHOUT an error - declined - when there are more than 2^31 - 1 pairs
+ * (start has been written; no partner has). */
+long long solr_hip_stick_pairs(const float *atoms /* n x 4: x, y, z, spare */, const unsigned char *backbone, int n,
+                               float reachPlain, float reachBackbone,
+                               long long *start /* n + 1 */, int *partners, long long capacity);
+/* ordered pairs (i, j) examined on the device since the library was loaded: n * n per kernel pass */
+unsigned long long solr_hip_stick_pair_tests(void);
+
 /* Device pointers of the current per-pixel buffers (strip-sized), for
  * collectives issued by the launcher (RCCL gather of the RGB strip). */
 void *solr_hip_device_bitmap(void);

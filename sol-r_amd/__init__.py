@@ -353,6 +353,10 @@ def _declare_hip(L):
     L.solr_hip_metaballs.argtypes = [P(IsoGrid), C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.solr_hip_metaballs.restype = C.c_int
     L.solr_hip_iso_cubes.restype = C.c_ulonglong
+    L.solr_hip_stick_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_longlong]
+    L.solr_hip_stick_pairs.restype = C.c_longlong
+    L.solr_hip_stick_pair_tests.restype = C.c_ulonglong
     # the by-value reference entry points are exercised from C++ (host/HipKernel.cpp);
     # ctypes cannot 16-byte align a by-value struct, so they get no argtypes here
     L.h2d_scene.argtypes = [C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -422,6 +426,15 @@ def _declare_host(L):
     L.SolRx_IsoField.argtypes = [P(IsoGrid), C.c_void_p, i, C.c_void_p]
     L.SolRx_IsoSurface.argtypes = [P(IsoGrid), C.c_void_p, C.c_void_p, i]
     L.SolRx_IsoCaseTable.argtypes = [C.c_void_p, C.c_void_p]
+    L.SolRx_StickPairs.argtypes = [C.c_void_p, C.c_void_p, i, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_longlong]
+    L.SolRx_StickPairs.restype = C.c_longlong
+    L.SolRx_StickSearches.argtypes = [P(C.c_longlong)]
+    L.SolRx_StickSearches.restype = None
+    L.SolRx_SetStickDeviceFrom.argtypes = [i]
+    L.SolRx_StickSquaredReach.argtypes = [C.c_float]
+    L.SolRx_StickSquaredReach.restype = C.c_float
+    L.SolRx_MoleculeLoadTimes.argtypes = [P(d)]
+    L.SolRx_MoleculeLoadTimes.restype = None
     L.SolRx_SelectEngine.argtypes = [C.c_char_p]
     L.SolRx_SetDeterministic.argtypes = [C.c_long]
     L.SolRx_LastError.argtypes = [C.c_char_p, i]
@@ -713,6 +726,52 @@ class Kernel:
         """Append a molecule from a PDB file (reference: PDBReader::loadAtomsFromFile via SolR_LoadMolecule);
         overwrites materials 0..118 with the element colours."""
         return self.L.SolR_LoadMolecule(os.fsencode(path), geometry_type, atom_size, stick_size, material_type, scale)
+
+    def molecule_load_times(self):
+        """Seconds the last load_molecule spent in its three steps (SolRx_MoleculeLoadTimes): the file into the reader's
+        map, the search for the sticks, the primitives added."""
+        out = (C.c_double * 3)()
+        self.L.SolRx_MoleculeLoadTimes(out)
+        return tuple(out)
+
+    def stick_pairs(self, positions, backbone, reach=(1.7, 1.7)):
+        """Which atoms are joined by a stick (SolRx_StickPairs; the rule is csrc/stick_pairs.h, the PDB reader's): atom j
+        is a partner of atom i != j when their backbone flags are equal and sqrtf((ax*ax + ay*ay) + az*az) < reach[flag]
+        in binary32, a = i - j.  positions: (n, 3) float32; backbone: n truth values.  With the HIP engine the search runs
+        on the device.  Returns (start, partners): start is n + 1 int64, atom i's partners are partners[start[i]:start[i + 1]],
+        int32 ranks ascending."""
+        p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        flags = np.ascontiguousarray(np.asarray(backbone).astype(bool), dtype=np.uint8).reshape(-1)
+        if len(flags) != len(p):
+            raise ValueError("stick_pairs: %d positions and %d backbone flags" % (len(p), len(flags)))
+        atoms = np.zeros((max(len(p), 1), 4), np.float32)
+        atoms[:len(p), :3] = p
+        room = np.zeros(max(len(p), 1), np.uint8)
+        room[:len(p)] = flags
+        start = np.zeros(len(p) + 1, np.int64)
+        partners = np.zeros(16 * len(p) + 64, np.int32)     # one search where the list fits, a second where it does not
+        for _ in range(2):
+            total = self.L.SolRx_StickPairs(atoms.ctypes.data, room.ctypes.data, len(p), reach[0], reach[1],
+                                            start.ctypes.data, partners.ctypes.data, len(partners))
+            if total < 0:
+                raise SolrError("SolRx_StickPairs refused its arguments")
+            if total <= len(partners):
+                break
+            partners = np.zeros(total, np.int32)
+        partners = partners[:total].copy()
+        return start, partners
+
+    def set_stick_device_from(self, n):
+        """The number of atoms from which the HIP engine searches for sticks on the device (SolRx_SetStickDeviceFrom);
+        smaller molecules take the loops on the CPU, which are quicker than the fixed cost of a call.  0: always on the
+        device.  Process-wide; returns the value before."""
+        return self.L.SolRx_SetStickDeviceFrom(int(n))
+
+    def stick_searches(self):
+        """(by a device, by the loops on the CPU): stick searches served since the library was loaded"""
+        out = (C.c_longlong * 2)()
+        self.L.SolRx_StickSearches(out)
+        return (out[0], out[1])
 
     def load_swc_morphology(self, path, position=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0, 1.0), material_id=0):
         """Append a neuron morphology (reference: SWCReader::loadMorphologyFromFile): spheres and

@@ -13,7 +13,9 @@
 #include "../csrc/jpeg_encode.h"
 #include "../csrc/jpeg_entropy.h"
 #include "../csrc/iso_surface.h"
+#include "../csrc/stick_pairs.h"
 
+#include <atomic>
 #include <chrono>
 #include <cstddef>
 #include <cstdio>
@@ -2008,6 +2010,44 @@ int GPUKernel::addMetaballs(const SolrIsoGrid &grid, const float *balls, int nbB
                             make_vec3f(t.n[2][0], t.n[2][1], t.n[2][2]));
     }
     return (int)triangles.size();
+}
+
+static std::atomic<long long> gStickSearches[2];
+static std::atomic<int> gStickDeviceFrom{solr::DEFAULT_STICK_DEVICE_FROM};
+
+int GPUKernel::setStickDeviceFrom(int n)
+{
+    return gStickDeviceFrom.exchange(n < 0 ? 0 : n);
+}
+
+int GPUKernel::stickDeviceFrom()
+{
+    return gStickDeviceFrom.load();
+}
+
+void GPUKernel::countStickSearch(bool onDevice)
+{
+    ++gStickSearches[onDevice ? 0 : 1];
+}
+
+void GPUKernel::stickSearches(long long out[2])
+{
+    out[0] = gStickSearches[0].load();
+    out[1] = gStickSearches[1].load();
+}
+
+bool GPUKernel::stickPairs(const float *atoms, const unsigned char *backbone, int n, float reachPlain, float reachBackbone,
+                           std::vector<long long> &start, std::vector<int> &partners)
+{
+    long long none = 0;
+    if (sticks::refusal(atoms, backbone, n, reachPlain, reachBackbone, &none, nullptr, 0))
+        return false;
+    const float limit[2] = {sticks::squaredReach(reachPlain), sticks::squaredReach(reachBackbone)};
+    start.resize((size_t)n + 1);
+    partners.clear();
+    sticks::walk(atoms, backbone, n, limit, start.data(), [&](long long, int partner) { partners.push_back(partner); });
+    countStickSearch(false);
+    return true;
 }
 
 /* the boundary's record of a file's four tables is the header's */

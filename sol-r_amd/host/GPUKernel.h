@@ -34,6 +34,14 @@
 
 namespace solr
 {
+/* The number of atoms from which the HIP engine searches for a molecule's sticks on the device (GPUKernel::
+ * setStickDeviceFrom).  A call of solr_hip_stick_pairs has a fixed cost - a stream, two allocations, four copies, two
+ * kernels, a scan, three waits - measured on an MI355X at 4.6 - 5.6 ms from 486 to 5 000 atoms alike, while the loops
+ * over csrc/stick_pairs.h on that machine's CPU grow with the square of the atoms: 2.7 ms at 2 500 atoms against the
+ * device's 5.0, 5.5 ms at 3 000 against 5.0 (tools/molecule_load_time.py with each route forced;
+ * profiles/r27/molecule_sticks.txt) */
+const int DEFAULT_STICK_DEVICE_FROM = 2500;
+
 /* reference: GPUKernel.h:46-65 */
 struct CPUPrimitive
 {
@@ -624,6 +632,22 @@ public:
     {
         return isoTriangles(grid, field, triangles, capacity);
     }
+    /* extension: which atoms of a molecule are joined by a stick (csrc/stick_pairs.h, include/solr_hip.h) - what the PDB
+     * reader asks between reading a file and adding its primitives.  atoms: n records of x, y, z, spare, an atom's rank its
+     * place there; backbone: n flags.  The pairs come from the engine (the stickPairs hook) as a list: start has n + 1
+     * entries, atom i's partners are partners[start[i] ... start[i + 1] - 1], ranks ascending.  false when an argument is
+     * out of range - nothing is written then */
+    bool stickPairsOf(const float *atoms, const unsigned char *backbone, int n, float reachPlain, float reachBackbone,
+                      std::vector<long long> &start, std::vector<int> &partners)
+    {
+        return stickPairs(atoms, backbone, n, reachPlain, reachBackbone, start, partners);
+    }
+    /* searches served since the library was loaded: out[0] by a device, out[1] by the loops on the CPU */
+    static void stickSearches(long long out[2]);
+    /* the rank count from which an engine with a device searches there (below it the loops are quicker than a call's fixed
+     * cost; DEFAULT_STICK_DEVICE_FROM).  0: always on the device.  Returns the value before.  Process-wide */
+    static int setStickDeviceFrom(int n);
+    static int stickDeviceFrom();
     int getLight(int index);
 
     /* rotation of the whole scene about a centre (GPUKernel.h:122-125) */
@@ -996,6 +1020,13 @@ protected:
                             std::vector<SolrIsoTriangle> &triangles);
     virtual bool isoField(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field);
     virtual int isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity);
+    /* engine hook of stickPairsOf.  Here: the loops of csrc/stick_pairs.h on the CPU; false = the arguments are out of
+     * range.  An engine with a device searches there and comes back here where it has none, where the device declines
+     * (more pairs than it indexes) or where it fails (its error is pending) */
+    virtual bool stickPairs(const float *atoms, const unsigned char *backbone, int n, float reachPlain, float reachBackbone,
+                            std::vector<long long> &start, std::vector<int> &partners);
+    /* a search has been served: by a device, or by the loops */
+    static void countStickSearch(bool onDevice);
     void rotatePrimitivesOnly(Frame &f, const vec3f &rotationCenter, const vec3f &cosA, const vec3f &sinA);
     /* translatePrimitives' loop over the level-0 boxes (no box is updated) */
     void translatePrimitivesOnly(Frame &f, const vec3f &translation);

@@ -443,6 +443,30 @@ int HipKernel::isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIso
     return solr_hip_iso_surface(&grid, field, triangles, capacity);
 }
 
+bool HipKernel::stickPairs(const float *atoms, const unsigned char *backbone, int n, float reachPlain, float reachBackbone,
+                           std::vector<long long> &start, std::vector<int> &partners)
+{
+    if (solr_hip_device_count() < 1 || !atoms || !backbone || n < 1 || n > NB_MAX_PRIMITIVES || n < stickDeviceFrom())
+        return GPUKernel::stickPairs(atoms, backbone, n, reachPlain, reachBackbone, start, partners);
+    /* one call where the pairs fit the buffer, which has room for 32 partners an atom (covalent sticks are about one an
+     * atom, a backbone's doubled reach finds about eight; the device allocates and copies what there is, not the room);
+     * the call is repeated when the list is longer than that */
+    start.resize((size_t)n + 1);
+    partners.resize((size_t)n * 32);
+    long long total = solr_hip_stick_pairs(atoms, backbone, n, reachPlain, reachBackbone, start.data(), partners.data(),
+                                           (long long)partners.size());
+    if (total > (long long)partners.size())
+    {
+        partners.resize((size_t)total);
+        total = solr_hip_stick_pairs(atoms, backbone, n, reachPlain, reachBackbone, start.data(), partners.data(), total);
+    }
+    if (total < 0)
+        return GPUKernel::stickPairs(atoms, backbone, n, reachPlain, reachBackbone, start, partners);
+    partners.resize((size_t)total);
+    countStickSearch(true);
+    return true;
+}
+
 int HipKernel::deviceBuildTree(const std::vector<Primitive> &primitives, const std::vector<unsigned char> &emissive,
                                const vec3f &minPos, const vec3f &maxPos, float viewDistance, int depthBefore,
                                std::vector<BoundingBox> &boxes, std::vector<int> &order, int &nbLamps)

@@ -111,6 +111,11 @@ protected:
                     std::vector<SolrIsoTriangle> &triangles) override;
     bool isoField(const SolrIsoGrid &grid, const float *balls, int nbBalls, float *field) override;
     int isoTriangles(const SolrIsoGrid &grid, const float *field, SolrIsoTriangle *triangles, int capacity) override;
+    /* solr_hip_stick_pairs (include/solr_hip.h) where there is a device and the molecule has stickDeviceFrom() atoms or
+     * more; the base class's loops below that, where there is no device, where
+     * the entry declines (more than 2^31 - 1 pairs) and where it reports an error (which stays pending) */
+    bool stickPairs(const float *atoms, const unsigned char *backbone, int n, float reachPlain, float reachBackbone,
+                    std::vector<long long> &start, std::vector<int> &partners) override;
 
 private:
     vec4i m_blockSize;

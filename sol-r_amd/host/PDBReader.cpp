@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <fstream>
@@ -127,6 +128,15 @@ vec4f PDBReader::loadAtomsFromFile(const std::string &filename, GPUKernel &kerne
                            kernel.getSceneInfo().viewDistance, 0.f, false);
     kernel.resetBoxes(true);
 
+    /* the three steps, timed: the file into the map, the search for the sticks, the primitives into the kernel */
+    auto last = std::chrono::steady_clock::now();
+    auto lap = [&](int step) {
+        const auto now = std::chrono::steady_clock::now();
+        m_seconds[step] = std::chrono::duration<double>(now - last).count();
+        last = now;
+    };
+    m_seconds[0] = m_seconds[1] = m_seconds[2] = 0.;
+
     const float distanceRatio = 2.f;
     std::map<int, Atom> atoms;
     float mn[3] = {100000.f, 100000.f, 100000.f}, mx[3] = {-100000.f, -100000.f, -100000.f};
@@ -222,6 +232,41 @@ vec4f PDBReader::loadAtomsFromFile(const std::string &filename, GPUKernel &kerne
                           sz * distanceRatio * atomDistance * (z - cz));
     };
 
+    lap(0);
+
+    /* the sticks (PDBReader.cpp:616-660): the map laid out in its order - an atom's rank is its place there, whatever its
+     * key - and the pairs from the engine (csrc/stick_pairs.h), per atom its partners' ranks ascending: the order the
+     * reference's inner loop over the map meets them in */
+    const bool withSticks = geometryType == gtSticks || geometryType == gtAtomsAndSticks || geometryType == gtBackbone;
+    std::vector<const Atom *> ranked;
+    std::vector<long long> start;
+    std::vector<int> partners;
+    if (withSticks)
+    {
+        std::vector<float> records;
+        std::vector<unsigned char> backbone;
+        ranked.reserve(atoms.size());
+        records.reserve(atoms.size() * 4);
+        backbone.reserve(atoms.size());
+        for (std::map<int, Atom>::iterator it = atoms.begin(); it != atoms.end(); ++it)
+        {
+            const Atom &atom = it->second;
+            ranked.push_back(&atom);
+            records.insert(records.end(), {atom.x, atom.y, atom.z, 0.f});
+            backbone.push_back(atom.isBackbone ? 1 : 0);
+        }
+        const float reachBackbone = (geometryType == gtBackbone) ? DEFAULT_STICK_DISTANCE * 2.f : DEFAULT_STICK_DISTANCE;
+        if (!kernel.stickPairsOf(records.data(), backbone.data(), (int)ranked.size(), DEFAULT_STICK_DISTANCE, reachBackbone,
+                                 start, partners))
+        {
+            std::cerr << "PDBReader: the search for the sticks failed; the molecule has none" << std::endl;
+            start.assign(ranked.size() + 1, 0);
+            partners.clear();
+        }
+    }
+    lap(1);
+
+    size_t rank = 0;
     for (std::map<int, Atom>::iterator it = atoms.begin(); it != atoms.end(); ++it)
     {
         const Atom &atom = it->second;
@@ -243,27 +288,21 @@ vec4f PDBReader::loadAtomsFromFile(const std::string &filename, GPUKernel &kerne
         default:
             break;
         }
-        if (geometryType == gtSticks || geometryType == gtAtomsAndSticks || geometryType == gtBackbone)
-            for (std::map<int, Atom>::iterator it2 = atoms.begin(); it2 != atoms.end(); ++it2)
+        if (withSticks)
+        {
+            for (long long at = start[rank]; at < start[rank + 1]; ++at)
             {
-                const Atom &other = it2->second;
-                if (it2 == it || atom.isBackbone != other.isBackbone)
-                    continue;
-                const float ax = atom.x - other.x, ay = atom.y - other.y, az = atom.z - other.z;
-                const float distance = sqrtf(ax * ax + ay * ay + az * az);
-                const float reach = (geometryType == gtBackbone && other.isBackbone) ? DEFAULT_STICK_DISTANCE * 2.f
-                                                                                     : DEFAULT_STICK_DISTANCE;
-                if (distance < reach)
-                {
-                    const vec3f a = place(atom.x, atom.y, atom.z);
-                    const vec3f h = place((atom.x + other.x) / 2.f, (atom.y + other.y) / 2.f, (atom.z + other.z) / 2.f);
-                    const int nb = kernel.addPrimitive(ptCylinder, true);
-                    kernel.setPrimitive(nb, a.x, a.y, a.z, h.x, h.y, h.z, sx * stickRadius, 0.f, 0.f,
-                                        (geometryType == gtSticks) ? atom.materialId : 1010);
-                    kernel.setPrimitiveTextureCoordinates(nb, vt0, vt1, vt2);
-                    ++m_nbPrimitives;
-                }
+                const Atom &other = *ranked[(size_t)partners[(size_t)at]];
+                const vec3f a = place(atom.x, atom.y, atom.z);
+                const vec3f h = place((atom.x + other.x) / 2.f, (atom.y + other.y) / 2.f, (atom.z + other.z) / 2.f);
+                const int nb = kernel.addPrimitive(ptCylinder, true);
+                kernel.setPrimitive(nb, a.x, a.y, a.z, h.x, h.y, h.z, sx * stickRadius, 0.f, 0.f,
+                                    (geometryType == gtSticks) ? atom.materialId : 1010);
+                kernel.setPrimitiveTextureCoordinates(nb, vt0, vt1, vt2);
+                ++m_nbPrimitives;
             }
+            ++rank;
+        }
         int m = atom.materialId;
         if (!useModels)
         {
@@ -284,6 +323,7 @@ vec4f PDBReader::loadAtomsFromFile(const std::string &filename, GPUKernel &kerne
         kernel.setPrimitiveTextureCoordinates(nb, vt0, vt1, vt2);
         ++m_nbPrimitives;
     }
+    lap(2);
     objectSize.x *= sx * distanceRatio * atomDistance;
     objectSize.y *= sy * distanceRatio * atomDistance;
     objectSize.z *= sz * distanceRatio * atomDistance;

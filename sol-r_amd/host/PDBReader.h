@@ -15,6 +15,10 @@
  *   - geometry by GeometryType: a sphere per atom; for the stick types a half-bond cylinder from every
  *     atom to the midpoint of every other atom closer than 1.7 (3.4 along a backbone) with the same
  *     backbone flag; everything scaled by scale / extent and spread by 2 x 30 around the centre.
+ * Three steps: the file into the reference's map (keys, collisions and extent as there); the map laid out in
+ * its order and the pairs of atoms a stick joins asked of the engine (GPUKernel::stickPairsOf: loops over
+ * csrc/stick_pairs.h, or the device); the primitives added, per atom its cylinders in partner order, then
+ * its spheres - the order of the reference's nested loop.
  * The element tables are data (sol-r_amd/host/pdb_elements.txt, tools/gen_pdb_elements.py), read once from
  * next to this library or from $SOLR_PDB_ELEMENTS.
  */
@@ -40,7 +44,7 @@ enum GeometryType
 class PDBReader
 {
 public:
-    PDBReader() : m_nbPrimitives(0), m_nbBoxes(0) {}
+    PDBReader() : m_nbPrimitives(0), m_nbBoxes(0), m_seconds{0., 0., 0.} {}
     virtual ~PDBReader() {}
 
     /* returns the size of the scaled molecule; (0, 0, 0, -1) if the element tables cannot be found */
@@ -49,9 +53,12 @@ public:
                             const vec4f scale, const bool useModels = false);
     int getNbBoxes() { return m_nbBoxes; }
     int getNbPrimitives() { return m_nbPrimitives; }
+    /* seconds the last load spent in its three steps: file to map, search for the sticks, primitives added */
+    const double *getStepSeconds() const { return m_seconds; }
 
 private:
     int m_nbPrimitives;
     int m_nbBoxes;
+    double m_seconds[3];
 };
 }

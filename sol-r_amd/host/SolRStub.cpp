@@ -17,6 +17,7 @@
 #include "../csrc/jpeg_encode.h"
 #include "../csrc/jpeg_entropy.h"
 #include "../csrc/iso_surface.h"
+#include "../csrc/stick_pairs.h"
 #include "OBJReader.h"
 #include "PDBReader.h"
 #include "SWCReader.h"
@@ -518,6 +519,43 @@ int SolRx_IsoCaseTable(unsigned char *count, unsigned char *edges)
     return 0;
 }
 
+/* Extension: GPUKernel::stickPairsOf */
+long long SolRx_StickPairs(const float *atoms, const unsigned char *backbone, int n, float reachPlain, float reachBackbone,
+                           long long *start, int *partners, long long capacity)
+{
+    if (sticks::refusal(atoms, backbone, n, reachPlain, reachBackbone, start, partners, capacity))
+        return -1;
+    std::vector<long long> starts;
+    std::vector<int> all;
+    if (!SingletonKernel::kernel()->stickPairsOf(atoms, backbone, n, reachPlain, reachBackbone, starts, all))
+        return -1;
+    std::copy(starts.begin(), starts.end(), start);
+    std::copy(all.begin(), all.begin() + (size_t)std::min<long long>((long long)all.size(), capacity), partners);
+    return (long long)all.size();
+}
+
+void SolRx_StickSearches(long long out[2])
+{
+    solr::GPUKernel::stickSearches(out);
+}
+
+int SolRx_SetStickDeviceFrom(int n)
+{
+    return solr::GPUKernel::setStickDeviceFrom(n);
+}
+
+float SolRx_StickSquaredReach(float reach)
+{
+    return sticks::squaredReach(reach);
+}
+
+static double gMoleculeLoadSeconds[3];
+
+void SolRx_MoleculeLoadTimes(double out[3])
+{
+    std::copy(gMoleculeLoadSeconds, gMoleculeLoadSeconds + 3, out);
+}
+
 int SolR_AddPrimitive(int type, int movable)
 {
     int id = SingletonKernel::kernel()->addPrimitive(static_cast<PrimitiveType>(type));
@@ -581,6 +619,7 @@ int SolR_LoadMolecule(char *filename, int geometryType, double defaultAtomSize, 
     reader.loadAtomsFromFile(filename ? filename : "", *SingletonKernel::kernel(),
                              static_cast<solr::GeometryType>(geometryType), static_cast<float>(defaultAtomSize),
                              static_cast<float>(defaultStickSize), atomMaterialType, solr::make_vec4f(s, s, s));
+    std::copy(reader.getStepSeconds(), reader.getStepSeconds() + 3, gMoleculeLoadSeconds);
     return (int)SingletonKernel::kernel()->getNbActivePrimitives();
 }
 

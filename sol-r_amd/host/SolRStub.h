@@ -215,6 +215,20 @@ int SolRx_AddMetaballs(const SolrIsoGrid *grid, const float *balls, int nbBalls,
 int SolRx_IsoField(const SolrIsoGrid *grid, const float *balls, int nbBalls, float *field);
 int SolRx_IsoSurface(const SolrIsoGrid *grid, const float *field, SolrIsoTriangle *triangles, int capacity);
 int SolRx_IsoCaseTable(unsigned char *count, unsigned char *edges);
+/* which atoms of a molecule are joined by a stick, through the current engine (GPUKernel::stickPairsOf: solr_hip_stick_pairs
+ * or the loops over csrc/stick_pairs.h; arguments and results as include/solr_hip.h gives them for solr_hip_stick_pairs: the
+ * number of pairs there are, start whole, the first min(total, capacity) partners).  -1 for arguments out of range */
+long long SolRx_StickPairs(const float *atoms, const unsigned char *backbone, int n, float reachPlain, float reachBackbone,
+                           long long *start, int *partners, long long capacity);
+/* searches served since the library was loaded: out[0] by a device, out[1] by the loops on the CPU */
+void SolRx_StickSearches(long long out[2]);
+/* the number of atoms from which the HIP engine searches on the device (GPUKernel::setStickDeviceFrom; below it the loops
+ * on the CPU are quicker than the fixed cost of a call; 0: always on the device).  Returns the value before */
+int SolRx_SetStickDeviceFrom(int n);
+/* for the tests: the threshold on the squared sum that stands for `reach` (csrc/stick_pairs.h squaredReach) */
+float SolRx_StickSquaredReach(float reach);
+/* seconds SolR_LoadMolecule spent last in its three steps: file to map, search for the sticks, primitives added */
+void SolRx_MoleculeLoadTimes(double out[3]);
 
 /* ---------- Extensions ---------- */
 /* "hip" (default) or "host-only"; destroys the current singleton */
