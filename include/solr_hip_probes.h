@@ -66,6 +66,19 @@ int solr_hip_probe_shader(const SceneInfo *sceneInfo, int n, const int *index, c
                           float *normal, float *closestColor, float *totalBlinn, float *attributes, float *returned,
                           float *shadowIntensity);
 
+/* The same call with the records of the hit handed over the way launchRayTracing hands them to the shader (rt_device.h
+ * HitRecords): per lane the material id, the index word and the material's hot half of the shaded primitive (record 0's for
+ * a negative material id, as the trace loads it), `given` by the trace's own ballot (a lane that shades a primitive with a
+ * negative material id sends its wave back to the shader's own gather), in the instantiation the renderer's kernel
+ * runs (F_ARGS where its trace sets it).  Returns the features, with
+ * SOLR_HIP_PROBE_HANDS_OVER set where that instantiation takes the records (handsOverHit); in the others the shader gathers
+ * them itself as in solr_hip_probe_shader. */
+#define SOLR_HIP_PROBE_HANDS_OVER (1 << 30)
+int solr_hip_probe_shader_given(const SceneInfo *sceneInfo, int n, const int *index, const float *origins, const int *objectId,
+                                const float *intersections, const float *areas, const int *iteration, int features,
+                                int exactNodes, float *normal, float *closestColor, float *totalBlinn, float *attributes,
+                                float *returned, float *shadowIntensity);
+
 /* the post-processing stage of cudaRender (CRT:1857-1890) over a frame buffer of the caller's (sceneInfo.size pixels):
  * k_depthOfField / k_ambientOcclusion / k_radiosity / k_filter / k_cartoon exactly as renderImpl launches them behind the
  * renderer, or, for ppe_none, the stand-alone k_default (CRT:1057-1073: the conversion the renderer otherwise fuses into

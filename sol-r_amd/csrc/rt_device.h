@@ -2498,7 +2498,9 @@ SOLR_DEV v3 primitiveShader(const Scene &S_, bool active, int index, const Scene
     {
         materialId = asint(primRow(S, pi, ROW_SIZE_MAT).w);
         primIndex = asint(primRow(S, pi, ROW_P1_INDEX).w);
-        mh = loadMaterialHot(S, materialId);
+        /* materials[MATERIAL_NONE] is read out of bounds by the reference; here the row offset is unsigned, and -1 would be a
+         * read 4 GiB past the table: record 0 in its place, as for a lamp without a material below and as the trace loads */
+        mh = loadMaterialHot(S, materialId < 0 ? 0 : materialId);
     }
     v3 lampsColor = V(0.f, 0.f, 0.f);
     v3 intersectionColor = V(0.f, 0.f, 0.f);
@@ -2511,7 +2513,8 @@ SOLR_DEV v3 primitiveShader(const Scene &S_, bool active, int index, const Scene
         shadowIntensity = 0.f;
         v3 bumpNormal = V(0.f, 0.f, 0.f);
         TexOut o = {&bumpNormal, &specular, &attributes, &ambientOcclusion};
-        float4 ic = intersectionShader<FEAT>(S, si, pi, type, materialId, mh, intersection, areas, o);
+        /* (record 0's cold half too, where record 0 carries a texture: the same unsigned row offset) */
+        float4 ic = intersectionShader<FEAT>(S, si, pi, type, materialId < 0 ? 0 : materialId, mh, intersection, areas, o);
         intersectionColor = V(ic.x, ic.y, ic.z);
         normal = normal + bumpNormal;
         normal = normalize(normal);
@@ -3049,8 +3052,8 @@ SOLR_DEV v3 launchRayTracing(const Scene &S_, bool active, int index, v3 rayO, v
             shadeIteration = lastIteration;
         }
 
-        /* (the trace clamps a negative material id for its own load and the shader does not, as the reference reads out of
-         * bounds: a wave in which a shading lane has one keeps the shader's own gather) */
+        /* (a wave in which a shading lane has a negative material id keeps the shader's own gather, which reads record 0
+         * for it as the load above does) */
         records.materialId = cpMaterial;
         records.given = HAND && ballot(shadeLane && cpMaterial < 0) == 0ull;
         v3 shaded = V(0.f, 0.f, 0.f);

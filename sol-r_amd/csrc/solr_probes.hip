@@ -316,6 +316,63 @@ __global__ __launch_bounds__(64) void k_probeShader(const SceneArgs SA, const Sc
     }
 }
 
+/* ---- primitiveShader with the records of the hit handed over, as launchRayTracing hands them ------------------------------
+ * The trace gathers the hit's material id, its index word and the material's hot half for its own bookkeeping and hands them to
+ * the shader (HitRecords) in the instantiations for which handsOverHit() holds - the lean rows, F_ARGS set by the renderer's
+ * kernel itself.  This kernel gathers the same three per lane (record 0 for a negative material id, as the trace), sets
+ * `given` by the trace's ballot (a shading lane with a negative material id sends the wave back to the shader's own gather)
+ * and calls the shader the way the trace does; lane 0 says whether the instantiation takes the records at all. */
+struct ShaderGivenArgs /* the head of k_probeShaderGiven's kernel-argument segment */
+{
+    SceneArgs SA;
+    SceneInfo si;
+};
+template <int FEAT>
+__global__ __launch_bounds__(64) void k_probeShaderGiven(const SceneArgs, const SceneInfo, int n, const int *index,
+                                                        const float *origins, const int *objectId, const float *intersections,
+                                                        const float *areas, const int *iteration, float *normal,
+                                                        float *closestColor, float *totalBlinn, float *attributes,
+                                                        float *returned, float *shadowIntensity, int *handsOver)
+{
+    constexpr int TRACE = (FEAT & (F_TRI | F_TEX)) ? FEAT : (FEAT | F_ARGS); /* as k_standardRenderer chooses its trace */
+    constexpr bool HAND = handsOverHit<0, TRACE>();
+    /* (F_ARGS: the scene and the frame are read where they lie, in the kernel-argument segment, as in k_standardRenderer) */
+    const ShaderGivenArgs &A = *(const ShaderGivenArgs *)(const SOLR_CONST_AS char *)__builtin_amdgcn_kernarg_segment_ptr();
+    const Scene &S = *(const Scene *)&A.SA;
+    const SceneInfo &si = A.si;
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    const bool active = e < n;
+    const int q = active ? e : 0;
+    Counters cnt;
+    memset(&cnt, 0, sizeof(cnt));
+    v3 nrm = at3(normal, q), cc = at3(closestColor, q), tb = at3(totalBlinn, q);
+    float4 attr = make_float4(attributes[4 * q], attributes[4 * q + 1], attributes[4 * q + 2], attributes[4 * q + 3]);
+    float shadow = 0.f;
+    const int cp = active ? objectId[q] : 0;
+    HitRecords records = {};
+    const int cpMaterial = asint(primRow(S, cp, ROW_SIZE_MAT).w);
+    records.primIndex = asint(primRow(S, cp, ROW_P1_INDEX).w);
+    records.mh = loadMaterialHot(S, cpMaterial < 0 ? 0 : cpMaterial);
+    records.materialId = cpMaterial;
+    records.given = HAND && ballot(active && cpMaterial < 0) == 0ull;
+    const v3 r = primitiveShader<0, TRACE>(S, active, index[q], si, at3(origins, q), nrm, objectId[q], at3(intersections, q),
+                                           at3(areas, q), cc, iteration[q], shadow, tb, attr, cnt, &records);
+    if (e == 0)
+        *handsOver = HAND ? 1 : 0;
+    if (active)
+    {
+        put3(normal, e, nrm);
+        put3(closestColor, e, cc);
+        put3(totalBlinn, e, tb);
+        attributes[4 * e] = attr.x;
+        attributes[4 * e + 1] = attr.y;
+        attributes[4 * e + 2] = attr.z;
+        attributes[4 * e + 3] = attr.w;
+        put3(returned, e, r);
+        shadowIntensity[e] = shadow;
+    }
+}
+
 /* ---- plain per-element functions ------------------------------------------------------------------------------ */
 __global__ __launch_bounds__(64) void k_probeVectors(int n, const float *incident, const float *normals, const float *n1,
                                                     const float *n2, float *refracted, float *reflected)
@@ -637,6 +694,33 @@ int solr_hip_probe_shader(const SceneInfo *sceneInfo, int n, const int *index, c
     PROBE_DISPATCH(k_probeShader, features, waves(n), stream, S, *sceneInfo, n, dIndex, dO, dObject, dI, dA, dIt, dN, dC, dB,
                    dAttr, dR, dS);
     return a.finish(stream) ? features : -1;
+}
+
+int solr_hip_probe_shader_given(const SceneInfo *sceneInfo, int n, const int *index, const float *origins, const int *objectId,
+                                const float *intersections, const float *areas, const int *iteration, int features,
+                                int exactNodes, float *normal, float *closestColor, float *totalBlinn, float *attributes,
+                                float *returned, float *shadowIntensity)
+{
+    SceneArgs S;
+    int need, deep;
+    hipStream_t stream;
+    if (n <= 0 || solrprobe::residentScene(*sceneInfo, exactNodes != 0, &S, &need, &deep, &stream) != 0)
+        return -1;
+    features = chooseFeatures(features, need, deep);
+    Arrays a;
+    const int *dIndex = a.in(index, n), *dObject = a.in(objectId, n), *dIt = a.in(iteration, n);
+    const float *dO = a.in(origins, 3 * (size_t)n), *dI = a.in(intersections, 3 * (size_t)n), *dA = a.in(areas, 3 * (size_t)n);
+    float *dN = a.out(normal, 3 * (size_t)n), *dC = a.out(closestColor, 3 * (size_t)n), *dB = a.out(totalBlinn, 3 * (size_t)n);
+    float *dAttr = a.out(attributes, 4 * (size_t)n), *dR = a.out(returned, 3 * (size_t)n), *dS = a.out(shadowIntensity, n);
+    int handsOver = 0;
+    int *dHands = a.out(&handsOver, 1);
+    if (a.failed)
+        return -1;
+    PROBE_DISPATCH(k_probeShaderGiven, features, waves(n), stream, S, *sceneInfo, n, dIndex, dO, dObject, dI, dA, dIt, dN, dC,
+                   dB, dAttr, dR, dS, dHands);
+    if (!a.finish(stream))
+        return -1;
+    return features | (handsOver ? SOLR_HIP_PROBE_HANDS_OVER : 0);
 }
 
 int solr_hip_probe_postprocess(const SceneInfo *sceneInfo, const PostProcessingInfo *postProcessingInfo,

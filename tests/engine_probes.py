@@ -18,6 +18,7 @@ F_SPHERE, F_PROC, F_CYL, F_ELL, F_TRI, F_PLANE, F_TEX, F_FULL, F_DEEP = 1, 2, 4,
 EVERYTHING = (255 & ~F_FULL) | F_DEEP
 NOBODY = -12345          # a Primitive.index no primitive has
 MAX_BITMAP_SIZE = 1920 * 1080   # Consts.h:39-41
+HANDS_OVER = 1 << 30            # SOLR_HIP_PROBE_HANDS_OVER of include/solr_hip_probes.h
 
 
 class TextureInfo(C.Structure):
@@ -40,6 +41,7 @@ def declare(hip):
     hip.solr_hip_probe_closest.argtypes = [v, i, v, v, v, v, i, i, v, v, v, v, v]
     hip.solr_hip_probe_shadow.argtypes = [v, i, v, v, v, v, v, i, i, v, v]
     hip.solr_hip_probe_shader.argtypes = [v, i, v, v, v, v, v, v, i, i, v, v, v, v, v, v]
+    hip.solr_hip_probe_shader_given.argtypes = hip.solr_hip_probe_shader.argtypes
     hip.solr_hip_probe_postprocess.argtypes = [v, v, v, v]
     hip.solr_hip_h2d_randoms_sized.argtypes = [v, C.c_long]
     hip.solr_hip_probe_ticket.argtypes = [C.c_longlong, v, v]
@@ -59,7 +61,7 @@ def declare(hip):
     hip.solr_hip_probe_walk_offer.argtypes = [v, i, v]
     hip.solr_hip_probe_free_lists.argtypes = [i, i, v, v, v, i, C.c_float, C.c_double, C.c_double, v, v, v, v, i]
     hip.solr_hip_probe_prune_list.argtypes = [i, i, v, v, C.c_double, v, v, v, v, v, i]
-    for name in ("box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "vectors",
+    for name in ("box", "box_walk", "primitive", "closest", "shadow", "shader", "shader_given", "postprocess", "ticket", "vectors",
                  "make_color", "skybox", "intersection_shader", "order_tiles", "list_copy", "walk_offer", "free_lists",
                  "prune_list", "math", "vector_math"):
         getattr(hip, "solr_hip_probe_" + name).restype = i
@@ -251,6 +253,21 @@ def walk_outputs(hip, case, features=0, exact=0):
     return dict(result=result, color=color, features=used)
 
 
+def shader_outputs(hip, case, features=0, exact=0, given=False):
+    """a shader case over the scene that is resident now.  given: through solr_hip_probe_shader_given - the records of the hit
+    handed over as launchRayTracing hands them; `hands_over` says whether the instantiation takes them"""
+    n = len(case["origins"])
+    normal, cc, tb = case["normal"].copy(), case["closest_color"].copy(), case["total_blinn"].copy()
+    at = case["attributes"].copy()
+    ret, shadow = np.zeros((n, 3), f32), np.zeros(n, f32)
+    entry = hip.solr_hip_probe_shader_given if given else hip.solr_hip_probe_shader
+    used = _check(hip, entry(C.byref(case["si"]), n, _p(case["index"]), _p(case["origins"]), _p(case["object_id"]), _p(case["inter"]),
+                             _p(case["areas"]), _p(case["iteration"]), features, exact, _p(normal), _p(cc), _p(tb), _p(at), _p(ret),
+                             _p(shadow)), "probe_shader_given" if given else "probe_shader")
+    return dict(returned=ret, shadow=shadow, normal=normal, closest_color=cc, total_blinn=tb, attributes=at,
+                features=used & ~HANDS_OVER, hands_over=bool(used & HANDS_OVER))
+
+
 def engine_outputs(solr, case, features=0, exact=0):
     """the case evaluated by the engine's device functions; keys as oracle.probes.oracle_outputs"""
     hip = solr.hip_lib()
@@ -299,17 +316,8 @@ def engine_outputs(solr, case, features=0, exact=0):
             return walk_outputs(hip, case, features, exact)
     if name == "shader":
         s = case["scene"]
-        n = len(case["origins"])
-        normal, cc, tb = case["normal"].copy(), case["closest_color"].copy(), case["total_blinn"].copy()
-        at = case["attributes"].copy()
-        ret, shadow = np.zeros((n, 3), f32), np.zeros(n, f32)
         with Resident(solr, si, s.boxes, s.prims, s.materials, s.textures, s.lights, s.nb_lamps, s.randoms):
-            used = _check(hip, hip.solr_hip_probe_shader(C.byref(si), n, _p(case["index"]), _p(case["origins"]),
-                                                         _p(case["object_id"]), _p(case["inter"]), _p(case["areas"]),
-                                                         _p(case["iteration"]), features, exact, _p(normal), _p(cc), _p(tb),
-                                                         _p(at), _p(ret), _p(shadow)), "probe_shader")
-        return dict(returned=ret, shadow=shadow, normal=normal, closest_color=cc, total_blinn=tb, attributes=at,
-                    features=used)
+            return shader_outputs(hip, case, features, exact)
     if name == "launch":
         # the case's rays are the camera rays of k_standardRenderer for this eye / look-at point and no rotation
         # (oracle.probes.case_launch): the frame goes through the renderer itself, pass 0

@@ -295,22 +295,22 @@ def test_the_probes_run_the_instantiations_the_renderer_launches(solr, probes, f
         assert E.engine_outputs(solr, case)["features"] == features, name
 
 
-def test_all_twenty_one_probe_entry_points_are_exported(solr):
-    """(CPU) include/solr_hip_probes.h is test-only, but what it declares must be in the library: the seventeen probes of the
-    device functions and of a frame - fifteen of the device functions (two of them the math stand-ins per element, scalar
-    and vector) and the read-back tickets, two of the frame's launch (the tile sort, the last frame) - the two of the
-    resident lists (their copies read back, what a walk is offered) and the two of the list builders on a node list of the
-    caller's (the order-free lists, the prune decisions): twenty-one.
+def test_all_twenty_two_probe_entry_points_are_exported(solr):
+    """(CPU) include/solr_hip_probes.h is test-only, but what it declares must be in the library: the eighteen probes of the
+    device functions and of a frame - sixteen of the device functions (two of them the math stand-ins per element, scalar
+    and vector; one the shader with the hit's records handed over) and the read-back tickets, two of the frame's launch
+    (the tile sort, the last frame) - the two of the resident lists (their copies read back, what a walk is offered) and
+    the two of the list builders on a node list of the caller's (the order-free lists, the prune decisions): twenty-two.
     And nothing of the product calls the last two: they are named in their own unit alone."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     text = open(os.path.join(root, "include", "solr_hip_probes.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     names = sorted(set(re.findall(r"\b(solr_hip_probe_\w+)\s*\(", text)))
-    assert len(names) == 21
+    assert len(names) == 22
     assert names == sorted("solr_hip_probe_" + n for n in (
-        "box", "box_walk", "primitive", "closest", "shadow", "shader", "postprocess", "ticket", "image_serial", "vectors",
-        "make_color", "skybox", "intersection_shader", "order_tiles", "last_frame", "list_copy", "walk_offer", "free_lists",
+        "box", "box_walk", "primitive", "closest", "shadow", "shader", "shader_given", "postprocess", "ticket", "image_serial",
+        "vectors", "make_color", "skybox", "intersection_shader", "order_tiles", "last_frame", "list_copy", "walk_offer", "free_lists",
         "prune_list", "math", "vector_math")), names
     hip = solr.hip_lib()
     assert all(hasattr(hip, n) for n in names), [n for n in names if not hasattr(hip, n)]

@@ -11,8 +11,6 @@
     are held by how many families and equalities;
   * the generator is deterministic (the digests are checked again on the GPU, tests/test_primitive_edges_gpu.py).
 """
-import contextlib
-import inspect
 import os
 import sys
 import types
@@ -23,6 +21,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cuda_text_model as M  # noqa: E402
 import primitive_edge_cases as G  # noqa: E402
+import text_mutants  # noqa: E402
 
 F = np.float32
 GROUP_NAMES = ("dyadic", "decimal", "flat", "camera")
@@ -185,30 +184,8 @@ def _unit_ray(r):
     return M.compute_ray_attributes(r.origin, M.normalize(r.direction))
 
 
-@contextlib.contextmanager
 def mutant(name):
-    func, old, new, nth = MUTANTS[name]
-    original = getattr(M, func)
-    src = inspect.getsource(original)
-    count = src.count(old)
-    if nth is None:
-        assert count == 1, (name, count)
-        src = src.replace(old, new)
-    elif nth == "all":
-        assert count >= 1, name
-        src = src.replace(old, new)
-    else:
-        assert count > nth, (name, count)
-        parts = src.split(old)
-        src = old.join(parts[: nth + 1]) + new + old.join(parts[nth + 1:])
-    space = dict(vars(M), _unit_ray=_unit_ray)
-    exec(compile(src, "<mutant %s>" % name, "exec"), space)
-    made = space[func]
-    setattr(M, func, made)
-    try:
-        yield
-    finally:
-        setattr(M, func, original)
+    return text_mutants.mutant(MUTANTS, name, dict(_unit_ray=_unit_ray))
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------------
